@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- the Deep Fluids velocity-field train step on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--scaling weak|strong] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up and K timed train steps, writes the last timed step's outputs if --dump-outputs is given, and prints
+the line: `value` / `ms_per_step` are the timed steps' throughput and mean wall time.  Everything else the benchmark measures or checks
+(parity with the oracle, live rooflines, the dispatch log, PMC passes, standalone stencil rooflines, the extra shapes and precisions, the
+CPU baseline, at N > 1 the other-scaling leg, the cross-rank check and the extra legs, the sidecar record) runs with --full only.
 
 N > 1: one rank per GPU over RCCL.  Either launch it under ``python -m torch.distributed.run --nproc-per-node N ...`` (the
 ranks read RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or run it as plain ``python bench.py --gpus N``:
@@ -15,7 +20,7 @@ cosine LR.  Synthetic inputs resident in HBM, random-init (Xavier) weights.
   --scaling strong global batch 16 split N ways (16 -> 2 per GPU at N = 8).
 --config picks another BASELINE.json workload for the SAME contract line (default cfg3, the metric's own): cfg2 = 2-D 128x96 batch 64
 per GPU (Trainer, GeneratorBE), cfg4 = 3-D 112x160x112 batch 4 per GPU (32 / 8 GPUs), cfg5 = AE3 128^3 filters 64 batch 4 per GPU
-(AETrainer: encoder + decoder).  At N > 1 the cfg3 line additionally carries short cfg2 and cfg4 data-parallel legs (`extra_leg_cfg2`,
+(AETrainer: encoder + decoder).  With --full, at N > 1 the cfg3 line additionally carries short cfg2 and cfg4 data-parallel legs (`extra_leg_cfg2`,
 `extra_leg_cfg4`; --no-extra-legs skips them) and every leg a `cross_rank` check: the reduced flat gradient is bit-identical on every
 rank and the mean of the shard losses equals ONE process's loss on the gathered global batch to 1e-6.
 Prints ONE JSON line on rank 0.
@@ -80,9 +85,20 @@ def parse():
                          "profiles/pmc_latest.json is used instead)")
     ap.add_argument("--no-other-leg", action="store_true", help="N > 1: skip the short leg in the other scaling mode")
     ap.add_argument("--other-steps", type=int, default=5)
-    ap.add_argument("--sidecar", default=None, help="where the full record goes (default gpurun_out/bench_full_n<N>.json)")
+    ap.add_argument("--sidecar", default=None, help="where the full record goes (--full: default bench_out/bench_full_n<N>.json; given explicitly, "
+                                                    "a plain run writes its record there too)")
     ap.add_argument("--full-line", action="store_true", help="print the full record instead of the compact line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: oracle parity figures, live HIP-event rooflines of the timed steps, the "
+                         "dispatch log, PMC passes, standalone stencil rooflines, the extra shapes / precisions, the CPU baseline, at N > 1 the "
+                         "other-scaling leg, the cross-rank check and the cfg2 / cfg4 legs, and the sidecar record (the --no-* switches still apply)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the tensors of the graph train_step returns and the "
+                         "parameters after its update) as DIR/<name>.npy, float32, %d MiB at most in all (larger arrays as a fixed, seeded "
+                         "sample)" % (DUMP_BUDGET_BYTES >> 20))
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     wl = WORKLOADS[a.config]
     a.batch = wl["batch"] if a.batch is None else a.batch
     a.res = list(wl["res"]) if a.res is None else list(a.res)
@@ -90,6 +106,41 @@ def parse():
     if len(a.res) != len(wl["res"]):
         ap.error("--config %s takes a %d-D grid" % (a.config, len(wl["res"])))
     return a
+
+
+DUMP_BUDGET_BYTES = 48 << 20      # --dump-outputs: all arrays together, headers aside
+
+
+def dump_outputs(path, tr, m, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what the timed path computed in its last step, as ``path/<name>.npy``: every tensor of the graph ``train_step``
+    returned (velocity field `G_`, the generator's output, the loss terms, ...) and the parameters after the step's optimizer update
+    (`params`, the trainer's flat slab), float32 (float64 for float64 / integer tensors).  The arrays share ``budget`` bytes, smallest
+    first; one larger than its share is stored as a fixed sample of k elements: one from each of k equal slices of the flattened array, at
+    offsets drawn from np.random.RandomState(0), so the same arguments always select the same elements."""
+    import numpy as np
+    import torch
+    arrays, seen = [], set()
+    for name, v in sorted(vars(m).items()):
+        if isinstance(v, torch.Tensor) and (v.data_ptr(), tuple(v.shape)) not in seen:      # (the AE graph names one tensor twice)
+            seen.add((v.data_ptr(), tuple(v.shape)))
+            arrays.append((name, v.detach()))
+    arrays.append(("params", tr.flat_p.detach()))
+    os.makedirs(path, exist_ok=True)
+    left, todo = budget, len(arrays)
+    for name, t in sorted(arrays, key=lambda q: q[1].numel()):
+        dt = np.float32 if t.dtype in (torch.float32, torch.float16, torch.bfloat16) else np.float64
+        n = t.numel()
+        k = min(n, left // todo // np.dtype(dt).itemsize)
+        flat = t.reshape(-1)
+        if k < n:
+            lo = np.arange(k, dtype=np.int64) * n // k
+            hi = np.arange(1, k + 1, dtype=np.int64) * n // k
+            idx = lo + (np.random.RandomState(0).random_sample(k) * (hi - lo)).astype(np.int64)
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arr = flat.float().cpu().numpy().astype(dt) if dt == np.float32 else flat.cpu().numpy().astype(dt)
+        np.save(os.path.join(path, name + ".npy"), arr.reshape(t.shape) if k == n else arr)
+        left -= arr.nbytes
+        todo -= 1
 
 
 def self_launch(a):
@@ -893,9 +944,11 @@ def cross_rank_check(tr, x, y, world, rank, dist, torch, max_samples=2):
     return out
 
 
-def dp_leg(name, a, world, rank, dist, torch, steps, warmup, scaling="weak", res=None, batch=None, filters=None, timer=None, other=True):
+def dp_leg(name, a, world, rank, dist, torch, steps, warmup, scaling="weak", res=None, batch=None, filters=None, timer=None, other=True,
+           dump=None):
     """One data-parallel leg of workload `name`: warm-up + `steps` timed steps (barrier + device sync on both sides, MAX over ranks),
-    all-reduce timing, optionally the short leg in the other scaling mode, and the cross-rank check.  Returns (record, state) where
+    all-reduce timing, (``dump``: rank 0 writes the last timed step's outputs there), optionally the short leg in the other scaling mode,
+    and (--full) the cross-rank check.  Returns (record, state) where
     state = (trainer, x, y, last graph, per-step HIP-event times) for the caller's own diagnostics."""
     wl = WORKLOADS[name]
     res = list(res or wl["res"]); batch = batch or wl["batch"]; filters = filters or wl["filters"]
@@ -915,6 +968,8 @@ def dp_leg(name, a, world, rank, dist, torch, steps, warmup, scaling="weak", res
         tr.train_step(xm, ym)
     torch.cuda.synchronize()
     elapsed, step_ms, last, comm = run_leg(tr, sync, xm, ym, max(warmup - 1, 0), steps, world, dist, torch, timer)
+    if dump and rank == 0:
+        dump_outputs(dump, tr, last)
     loss = float(last.g_loss.detach())
     assert loss == loss, "Model diverged with loss = NaN"        # trainer.py:275
     rec = {"config": name, "workload": "%s fp32, %s filters=%d num_conv=4, per-GPU batch %d, full train step (%s)" % (
@@ -933,7 +988,7 @@ def dp_leg(name, a, world, rank, dist, torch, steps, warmup, scaling="weak", res
                                         "ms_per_step": o_el / a.other_steps * 1e3, "value": o_glob * units * a.other_steps / o_el,
                                         "unit": wl["unit"], "allreduce": o_comm, "loss": float(o_last.g_loss.detach())}
             del o_last, xo, yo
-    if world > 1 and not a.no_cross_rank_check:
+    if world > 1 and a.full and not a.no_cross_rank_check:
         rec["cross_rank"] = cross_rank_check(tr, xm, ym, world, rank, dist, torch)
     return rec, (tr, xm, ym, last, step_ms, elapsed)
 
@@ -968,17 +1023,17 @@ def main():
     is_3d = len(a.res) == 3
     with ops.options(conv_precision=a.precision):
         rel_l1 = None
-        if rank == 0:
+        if rank == 0 and a.full:
             rel_l1 = l1_vs_oracle_ae(a.filters) if wl["kind"] == "ae" else l1_vs_oracle(a.filters, a.precision, is_3d=is_3d)
         if dog:
             dog.arm("first leg (first gradient all-reduces)", a.init_timeout + 60.0 * (a.warmup + a.steps))
-        timer = _lib.KernelTimer(select_kernel)
+        timer = _lib.KernelTimer(select_kernel) if a.full else None
         rec, (tr, xm, ym, last, step_ms, elapsed) = dp_leg(a.config, a, world, rank, dist, torch, a.steps, a.warmup, a.scaling, a.res, a.batch,
-                                                           a.filters, timer, other=not a.no_other_leg)
+                                                           a.filters, timer, other=a.full and not a.no_other_leg, dump=a.dump_outputs)
         if dog:
             dog.disarm()
         per_gpu, global_batch = rec["batch_per_gpu"], rec["global_batch"]
-        ks = timer.summary()
+        ks = timer.summary() if timer is not None else {}
         pct = lambda q: step_ms[min(len(step_ms) - 1, int(q * (len(step_ms) - 1) + 0.5))]
         step_stats = {"median_ms": pct(0.5), "p10_ms": pct(0.1), "p90_ms": pct(0.9), "min_ms": step_ms[0], "max_ms": step_ms[-1],
                       "source": "HIP events on the launch stream, one per step"}
@@ -986,15 +1041,16 @@ def main():
 
         # which algorithm every conv / weight-gradient call of a step takes (one extra, untimed step)
         dispatch = {}
-        with ops.options(dispatch_counts=dispatch):
-            tr.train_step(xm, ym)
-        torch.cuda.synchronize()
+        if a.full:
+            with ops.options(dispatch_counts=dispatch):
+                tr.train_step(xm, ym)
+            torch.cuda.synchronize()
         n_params = tr.n_params
 
         # N > 1, the metric's own config: short data-parallel legs of the 2-D workload and of cfg4's grid in the SAME job, so that one
         # driver invocation per N yields the 2-D and the 3-D numbers north_star asks for
         extra_legs = {}
-        if world > 1 and a.config == "cfg3" and not a.no_extra_legs and a.precision == "fp32":
+        if world > 1 and a.full and a.config == "cfg3" and not a.no_extra_legs and a.precision == "fp32":
             del tr, last, xm, ym
             torch.cuda.empty_cache()
             units0 = 1
@@ -1037,12 +1093,12 @@ def main():
     grid_s = "x".join(str(r) for r in a.res)
 
     default_shape = a.config == "cfg3" and list(a.res) == [64, 96, 64] and per_gpu == 16 and a.filters == 128 and a.precision == "fp32"   # the PMC passes' shape
-    pmc, pmc_source = None, None
-    if world == 1 and default_shape and not a.no_live_pmc:
+    pmc, pmc_source = {}, None
+    if world == 1 and default_shape and a.full and not a.no_live_pmc:
         pmc = live_pmc()
         if pmc:
             pmc_source = "measured in this run: rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE passes over tools/pmc_target.py (2 x FETCH_SIZE + WRITE_SIZE)"
-    if not pmc:
+    if not pmc and a.full:
         try:
             pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_latest.json")))["kernels"]
         except (OSError, ValueError, KeyError):
@@ -1097,7 +1153,7 @@ def main():
                        "wino2d43_kernel": out["roofline_wino2d_fwd_f24"]}.get(dom)
     for key in ("alt_bf16x3_mode", "extra_ref_grids", "extra_2d_128x96", "extra_cfg4_slice", "extra_ae_cfg5"):
         out[key] = None
-    if world == 1 and is_3d:
+    if a.full and world == 1 and is_3d:
         try:
             out["stencils_standalone"] = stencil_rooflines(per_gpu, *a.res)
             out["roofline_stencil"] = dict(out["stencils_standalone"]["jacobian3d_fwd_kernel<j,c>"], kernel="jacobian3d_fwd_kernel<j,c>",
@@ -1112,30 +1168,31 @@ def main():
                     out[k]["avg_launch_us"] = out[k]["avg_launch_ms"] * 1e3
         except Exception as e:
             out["stencils_standalone"] = {"error": repr(e)[:300]}
-    elif world == 1:
+    elif a.full and world == 1:
         out["roofline_stencil"] = roofline_of(ks, "jacobian2d_fwd_kernel", {}, False)
-    if world == 1 and not a.no_alt and a.precision == "fp32" and a.config == "cfg3":
+    if world == 1 and a.full and not a.no_alt and a.precision == "fp32" and a.config == "cfg3":
         from deep_fluids_amd.trainer import default_config
         cfg = default_config(is_3d=True, res_x=a.res[2], res_y=a.res[1], res_z=a.res[0], filters=a.filters, batch_size=global_batch,
                              num_samples=wl["num_samples"], random_seed=123)
         del tr, last
         extras(out, a, cfg, xm, ym, vox_per_step, pmc)
     try:
-        if world == 1 and not a.no_cpu_baseline and wl["kind"] == "de":
+        if world == 1 and a.full and not a.no_cpu_baseline and wl["kind"] == "de":
             par = {} if (a.precision == "fp32" and is_3d) else None
             out["cpu_baseline"] = cpu_baseline(a.res, a.filters, a.cpu_seconds, par)
             out["l1_vs_ref_fullsize"] = par
     except Exception as e:      # an extra must never take the metric line down with it
         out["cpu_baseline"] = {"error": repr(e)[:300]}
-    # the full record goes to a sidecar file, the printed line stays short (headline objects first)
-    try:
-        side = a.sidecar or os.path.join(ROOT, "gpurun_out", "bench_full_n%d%s.json" % (world, "" if a.config == "cfg3" else "_" + a.config))
-        os.makedirs(os.path.dirname(side), exist_ok=True)
-        out["sidecar"] = os.path.relpath(side, ROOT)
-        with open(side, "w") as f:
-            json.dump(out, f, indent=1)
-    except OSError as e:
-        out["sidecar"] = "not written: %r" % (e,)
+    # --full: the full record goes to a sidecar file, the printed line stays short (headline objects first)
+    if a.full or a.sidecar:
+        try:
+            side = a.sidecar or os.path.join(ROOT, "bench_out", "bench_full_n%d%s.json" % (world, "" if a.config == "cfg3" else "_" + a.config))
+            os.makedirs(os.path.dirname(os.path.abspath(side)), exist_ok=True)
+            out["sidecar"] = os.path.relpath(side, ROOT)
+            with open(side, "w") as f:
+                json.dump(out, f, indent=1)
+        except OSError as e:
+            out["sidecar"] = "not written: %r" % (e,)
     print(json.dumps(out if a.full_line else compact(out)))
     if world > 1:
         dist.barrier()

@@ -167,3 +167,37 @@ def test_watchdog_soft_stage_prints_the_fallback_line_and_exits_zero():
     code1 = code.replace("d = m.Watchdog(0, 8)", "d = m.Watchdog(3, 8)").replace(", fallback={'metric': 'm', 'value': 1.5e8, 'n_gpus': 8}", "")
     r1 = subprocess.run([sys.executable, "-c", code1], capture_output=True, text=True, timeout=60)
     assert r1.returncode == 0 and r1.stdout.strip() == ""
+
+
+def test_plain_run_options_and_output_dump(monkeypatch, tmp_path):
+    """--full is off by default (a plain run times the steps and prints the line); --steps must be >= 1.  --dump-outputs writes every tensor
+    of the step's graph once plus the parameters, float32, within the byte budget, larger arrays as the same seeded sample every time."""
+    import numpy as np
+    import torch
+    from types import SimpleNamespace
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1", "--full", "--dump-outputs", str(tmp_path)])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path) and (a.steps, a.warmup) == (3, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        b.parse()
+    assert b.DUMP_BUDGET_BYTES <= 64 * 10 ** 6
+    g = torch.arange(3 * 1000 * 1000, dtype=torch.float32).reshape(1000, 1000, 3)
+    m = SimpleNamespace(G_=g, x_=g, G_s=torch.ones(7, 3), g_loss=torch.tensor(0.5), G_jaco_=None, tag="not an array")
+    tr = SimpleNamespace(flat_p=torch.linspace(0, 1, 2000000))
+    budget = 4 << 20
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), tr, m, budget=budget)
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == ["G_.npy", "G_s.npy", "g_loss.npy", "params.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= budget + 256 * len(files)
+    for f in files:
+        x, y = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+    assert np.load(str(tmp_path / "a" / "G_s.npy")).shape == (7, 3) and float(np.load(str(tmp_path / "a" / "g_loss.npy"))) == 0.5
+    s = np.load(str(tmp_path / "a" / "G_.npy"))          # the velocity's values are their flat indices: one per slice, in order
+    assert s.ndim == 1 and 0 < s.size < g.numel() and np.all(np.diff(s) > 0) and s[-1] < g.numel()

@@ -22,7 +22,7 @@ def _run(args, tmp_path, timeout=1500):
         env["DF_DIST_BACKEND"] = "gloo"
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     side = str(tmp_path / "side.json")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--other-steps", "2", "--sidecar", side] + args
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--other-steps", "2", "--sidecar", side, "--full"] + args
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout, cwd=str(tmp_path))
     assert r.returncode == 0, (r.stdout.decode()[-2000:], r.stderr.decode()[-4000:])
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
@@ -70,3 +70,35 @@ def test_bench_two_ranks_cfg3_line_carries_cfg2_and_cfg4_legs(tmp_path):
         assert leg["grid"] == grid and leg["batch_per_gpu"] == per and leg["global_batch"] == 2 * per
         _check_leg(leg)
         assert line["extra_leg_" + name]["cross_rank"]["ok"] is True
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_step(tmp_path):
+    """A plain one-GPU run (no --full) prints the headline line only -- no oracle parity, no rooflines, no CPU baseline, no sidecar -- and
+    --dump-outputs writes what the last timed step computed.  A second run with the same arguments starts from the same inputs and weights
+    and writes the same outputs."""
+    import numpy as np
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--res", "16", "24", "16", "--batch", "2", "--filters", "16"]
+    lines, dumps = [], []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(d)], stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, timeout=600, cwd=str(tmp_path))
+        assert r.returncode == 0, (r.stdout.decode()[-2000:], r.stderr.decode()[-4000:])
+        out = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
+        assert len(out) == 1, out
+        lines.append(json.loads(out[0]))
+        dumps.append(d)
+    line = lines[0]
+    assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["unit"] == "voxels/s" and line["dtype"] == "f32"
+    assert line["higher_is_better"] is True and line["ms_per_step"] > 0
+    assert abs(line["value"] - 2 * 16 * 24 * 16 / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert line["l1_vs_ref"]["value"] is None and line["roofline"] is None and line["cpu_baseline"] is None and line["sidecar"] is None
+    names = sorted(os.listdir(str(dumps[0])))
+    assert {"G_.npy", "G_s.npy", "g_loss.npy", "params.npy"} <= set(names) and names == sorted(os.listdir(str(dumps[1])))
+    assert sum(os.path.getsize(str(dumps[0] / n)) for n in names) <= 64 * 10 ** 6
+    assert np.load(str(dumps[0] / "G_.npy")).shape == (2, 16, 24, 16, 3)
+    assert abs(float(np.load(str(dumps[0] / "g_loss.npy"))) - line["loss"]) <= 1e-6 * abs(line["loss"])
+    for n in names:
+        a, b = np.load(str(dumps[0] / n)), np.load(str(dumps[1] / n))
+        assert a.dtype == np.float32 and a.shape == b.shape and np.isfinite(a).all(), n
+        np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-6, err_msg=n)

@@ -9,6 +9,6 @@ for V in spx2 spx4; do
 import sys,json
 d=json.load(sys.stdin)['kernels']
 for k in ('wino43_kernel','wino43_kernel_dgrad_mask'): print('$V', k, round(d[k]['traffic_bytes']/1e9,2), 'GB x', round(d[k]['traffic_over_algorithmic'],2))"
-  python $R/bench.py --steps 10 --warmup 3 --no-alt --no-cpu-baseline --no-live-pmc 2>/dev/null | python -c "
+  python $R/bench.py --full --steps 10 --warmup 3 --no-alt --no-cpu-baseline --no-live-pmc 2>/dev/null | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('$V step ms', round(d['ms_per_step'],2), 'launch ms', round(d['roofline']['avg_launch_ms'],3))"
 done

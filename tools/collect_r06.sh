@@ -6,10 +6,10 @@ O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 if [ -z "$SKIP_BENCH" ]; then
-  python $R/bench.py --sidecar $O/r06_bench_full_n1.json > $O/r06_bench_n1.json 2> $O/r06_bench_n1.err
+  python $R/bench.py --full --sidecar $O/r06_bench_full_n1.json > $O/r06_bench_n1.json 2> $O/r06_bench_n1.err
 fi
 for C in ${CONFIGS:-cfg3 cfg2 cfg4 cfg5}; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$C -- python $R/bench.py --config $C --steps 5 --warmup 2 --no-alt --no-cpu-baseline --no-live-pmc --sidecar /tmp/side_$C.json > $O/r06_bench_prof_$C.json 2> /dev/null
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$C -- python $R/bench.py --full --config $C --steps 5 --warmup 2 --no-alt --no-cpu-baseline --no-live-pmc --sidecar /tmp/side_$C.json > $O/r06_bench_prof_$C.json 2> /dev/null
   python $R/tools/summarize_trace.py $(find $O/prof_$C -name "*kernel_trace.csv" | head -1) > $O/r06_${C}_kernel_by_grid.md
   rm -rf $O/prof_$C
 done
