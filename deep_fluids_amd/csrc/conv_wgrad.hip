@@ -16,6 +16,10 @@
 //   * workgroup = the four quadrants of 128x128; grid = (voxel ranges x (dz,dy)) x ci-blocks x co-blocks;
 //     each workgroup writes its partial [3][128][128] to the workspace, a second kernel reduces the
 //     ranges in a fixed order (deterministic), and also finishes the bias gradient sum_voxels G.
+// The Winograd forms below (x | (x,y) | (x,y,z)) keep this streaming; the one exception is the default of the 128 -> 128 layers at
+// W = 64 | 32, wgrad_wxyz_staged_kernel: there the WORKGROUP fetches each raw row once with 16-byte loads, applies the (xi_z, xi_y)
+// combination once and keeps the combined operands of a tile-row pair in LDS, from where the four quadrant waves read them
+// (ds_read_b64) -- half the operand requests per MFMA, the same partials bit for bit (algo 4 = the register-ring kernel it replaced).
 #include "df_common.hpp"
 
 namespace {
@@ -1389,6 +1393,246 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad_wxyz_up_fused_kernel(const 
   else wgrad_wxyz_body<WP8, CS, false, false, true, 0>(aa, range, selz * 2 + sely, sLds);
 }
 
+// ---- staged (x,y,z) weight gradient: one pre-combined operand stream per workgroup -------------------------------------------------
+// Same arithmetic, partial layout and summation order as wgrad_wxyz_fused_kernel<WP8, 128> (bitwise the same gW / gb); what changes
+// is the operand path.  There every wave loads the 4 + (1 | 2 | 4) raw rows of its quadrant with 8-byte accesses and forms the
+// (xi_z, xi_y) combination itself, so inside a workgroup every row segment is requested twice and combined twice, out of 8-deep
+// register rings.  Here the WORKGROUP fetches each raw row segment once, with 16-byte accesses, combines it once and keeps the
+// COMBINED operands of one whole tile-row pair in LDS:
+//   position p of the row: [tile row 0 | 1][128 ci of X_c | 128 co of G_c] = 2 KB;  Wc positions = 128 KB (W = 64) | 64 KB (W = 32).
+// The four quadrant waves read them back with one ds_read_b64 per operand and position in the MFMA lane layout (lane (half, r) =
+// tile row `half`, channels 2r, 2r+1: 32 lanes x 8 B contiguous, conflict-free) and do only the x transform.
+// Staging is a continuous stream of UNITS of 4 positions (one position per wave; lane (half, c4) = tile row, channels 4 c4 .. +3 of
+// both operands): in x-step 2k the X half of unit k + L is combined out of registers and stored (one ds_write_b128 per lane) and the
+// loads of unit k + L + 2 are issued into the registers just freed; x-step 2k+1 does the same for G.  So a load has two units = four
+// x-steps (64 MFMAs) to arrive, every step carries at most 4 loads + 1 store per lane, and no wave ever writes a burst.
+// The LDS image is a ring of NU = Wc / 4 units (exactly one row pair, so every LDS offset is a compile-time constant); one barrier per
+// BI = NU / 4 units (16 | 8 positions).  A unit written during unit m - L must be visible before the reads of unit m - 1 start
+// (operands are read one x-step ahead):  L >= BI + 1;  it overwrites unit m - NU, last read during unit m - NU:  L <= NU - BI.
+constexpr int kStgPos = 2 * 256;      // floats per staged position
+template <int WP8> struct WxyzStage {
+  static constexpr int Wc = WP8 * 8, NU = Wc / 4, BI = NU / 4, L = BI + 2;
+  static constexpr int kLdsBytes = Wc * kStgPos * 4;
+  static_assert(L >= BI + 1 && L <= NU - BI && L + 2 <= NU, "staging ring: write lead outside the barrier window");
+  static_assert(kLdsBytes <= 160 * 1024, "staged (x,y,z) weight gradient: LDS image above gfx950's 160 KB");
+};
+static_assert(kWxyzLds * 4 <= 160 * 1024, "64-channel (x,y,z) weight gradient: LDS above gfx950's 160 KB");
+
+template <int WP8, bool GZ, bool GY>
+__device__ __forceinline__ void wgrad_wxyz_staged_body(const WxyzArgs& aa, int range, int sel, float* lds) {
+  using ST = WxyzStage<WP8>;
+  constexpr int Wc = ST::Wc, NU = ST::NU, BI = ST::BI, L = ST::L;
+  const WgradArgs& a = aa.w;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int qi = wave >> 1, qj = wave & 1;
+  const int half = lane >> 5, r = lane & 31;
+
+  const int xiz = GZ ? 1 + sel / 2 : 3 * (sel / 2);
+  const int xiy = GY ? 1 + sel % 2 : 3 * (sel % 2);
+  const int zy = xiz * 4 + xiy;
+  const int ci0 = qi * 64, co0 = qj * 64;      // (Cin = Cout = 128: one channel block)
+  const int p0 = range * a.pairs_per_range;
+  int p1 = (range + 1) * a.pairs_per_range;
+  if (p1 > a.npairs) p1 = a.npairs;
+
+  const float* zb = a.zeros;
+  const int yoa = xiy == 0 ? -1 : xiy == 2 ? 1 : 0, yob = xiy == 0 ? 1 : xiy == 1 ? 1 : xiy == 2 ? 0 : 2;
+  const int zoa = xiz == 0 ? -1 : xiz == 2 ? 1 : 0, zob = xiz == 0 ? 1 : xiz == 1 ? 1 : xiz == 2 ? 0 : 2;
+  const float syf = xiy == 1 ? 1.f : -1.f, szf = xiz == 1 ? 1.f : -1.f;
+  const int gya = xiy == 3 ? 1 : 0, gza = xiz == 3 ? 1 : 0;
+  const f32x2 sy2 = {syf, syf}, sz2 = {szf, szf};      // (the gradient combination of xi in {1, 2} has the same signs)
+  // staging role of this lane: position `wave` of a unit, tile row `half`, channels 4r .. 4r+3 of X and of G
+  const int soff = wave * 128 + 4 * r;
+  struct Row { const float* x[2][2]; const float* g[2][2]; };      // [plane a|b][row a|b], at this lane's staging offset
+  auto row_setup = [&](int pair) -> Row {
+    Row rw;
+    const int trow = 2 * pair + half;
+    const bool ok = pair < p1 && trow < aa.ntrows;
+    const int yt = trow % aa.Ht;
+    const int t = trow / aa.Ht;
+    const int zt = t % aa.Dt;
+    const int b = t / aa.Dt;
+    const int z0 = 2 * zt, y0 = 2 * yt;
+    const int64_t bbase = static_cast<int64_t>(b) * a.D;
+#pragma unroll
+    for (int pz = 0; pz < 2; ++pz) {
+      const int zs = z0 + (pz ? zob : zoa);
+      const bool zv = ok && zs >= 0 && zs < a.D;
+#pragma unroll
+      for (int py = 0; py < 2; ++py) {
+        const int ys = y0 + (py ? yob : yoa);
+        rw.x[pz][py] = (zv && ys >= 0 && ys < a.H) ? a.x + ((bbase + zs) * a.H + ys) * Wc * 128 + soff : zb;
+      }
+      const int gz = z0 + (pz ? 1 : gza);
+#pragma unroll
+      for (int py = 0; py < 2; ++py) {
+        const int gy = y0 + (py ? 1 : gya);
+        const bool need = (pz == 0 || GZ) && (py == 0 || GY);
+        rw.g[pz][py] = (need && ok) ? a.g + ((bbase + gz) * a.H + gy) * Wc * 128 + soff : zb;
+      }
+    }
+    return rw;
+  };
+  auto ld4 = [&](const float* base, int unit) -> f32x4 { return *reinterpret_cast<const f32x4*>(base + unit * (4 * 128)); };
+  auto pkfma = [&](f32x2 x, f32x2 y, f32x2 z) -> f32x2 {
+    f32x2 d;
+    asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "v"(y), "v"(z));
+    return d;
+  };
+  auto fma4 = [&](f32x4 x, f32x2 s, f32x4 z) -> f32x4 {
+    const f32x2 lo = pkfma(f32x2{x[0], x[1]}, s, f32x2{z[0], z[1]}), hi = pkfma(f32x2{x[2], x[3]}, s, f32x2{z[2], z[3]});
+    return f32x4{lo[0], lo[1], hi[0], hi[1]};
+  };
+
+  f32x16 acc[4][2][2];
+#pragma unroll
+  for (int d = 0; d < 4; ++d)
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[d][s][t][e] = 0.f;
+  f32x2 bsum = {0.f, 0.f};
+  const bool do_bias = a.want_bias && GZ && GY && sel == 0 && qi == 0;
+
+  // raw rows in flight, by unit parity: [set][plane a|b][row a|b]
+  f32x4 sx[2][2][2], sg[2][2][2];
+  float* const wst = lds + wave * kStgPos + half * 256 + 4 * r;      // + unit * 4 * kStgPos (+ 128: G)
+  const float* const rdx = lds + half * 256 + ci0 + 2 * r;           // + position * kStgPos
+  const float* const rdg = lds + half * 256 + 128 + co0 + 2 * r;
+  auto load_x = [&](const Row& lr, int set, int unit) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) sx[set][q >> 1][q & 1] = ld4(lr.x[q >> 1][q & 1], unit);
+  };
+  auto load_g = [&](const Row& lr, int set, int unit) {
+    sg[set][0][0] = ld4(lr.g[0][0], unit);
+    if (GY) sg[set][0][1] = ld4(lr.g[0][1], unit);
+    if (GZ) sg[set][1][0] = ld4(lr.g[1][0], unit);
+    if (GZ && GY) sg[set][1][1] = ld4(lr.g[1][1], unit);
+  };
+  // (the operation order of wgrad_wxyz_body's xcomb / gcomb)
+  auto store_x = [&](int set, int unit) {
+    const f32x4 ta = fma4(sx[set][0][1], sy2, sx[set][0][0]), tb = fma4(sx[set][1][1], sy2, sx[set][1][0]);
+    *reinterpret_cast<f32x4*>(wst + unit * (4 * kStgPos)) = fma4(tb, sz2, ta);
+  };
+  auto store_g = [&](int set, int unit) {
+    f32x4 v;
+    if (GZ && GY) {
+      const f32x4 ta = fma4(sg[set][0][1], sy2, sg[set][0][0]), tb = fma4(sg[set][1][1], sy2, sg[set][1][0]);
+      v = fma4(tb, sz2, ta);
+    } else if (GY) v = fma4(sg[set][0][1], sy2, sg[set][0][0]);
+    else if (GZ) v = fma4(sg[set][1][0], sz2, sg[set][0][0]);
+    else v = sg[set][0][0];
+    *reinterpret_cast<f32x4*>(wst + unit * (4 * kStgPos) + 128) = v;
+  };
+  auto lds_sync = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+
+  // combined operands of this wave's quadrant by position % 8 (X: x-1 .. x+4) and % 4 (G: x .. x+3)
+  f32x2 xq[8], gq[4];
+  auto rd_x = [&](int pos) { xq[pos & 7] = *reinterpret_cast<const f32x2*>(rdx + (pos % Wc) * kStgPos); };
+  auto rd_g = [&](int pos) { gq[pos & 3] = *reinterpret_cast<const f32x2*>(rdg + (pos % Wc) * kStgPos); };
+
+  Row cur = row_setup(p0);
+  // prologue: units 0 .. L-1 of the first row pair, then the loads of units L and L+1 stay in flight
+#pragma unroll
+  for (int u = 0; u < L; ++u) {
+    load_x(cur, u & 1, u); load_g(cur, u & 1, u);
+    store_x(u & 1, u); store_g(u & 1, u);
+  }
+#pragma unroll
+  for (int u = L; u < L + 2; ++u) { load_x(cur, u & 1, u); load_g(cur, u & 1, u); }
+  lds_sync();
+  rd_x(0); rd_x(1); rd_x(2); rd_g(0); rd_g(1);
+  xq[7] = f32x2{0.f, 0.f};
+
+  // x-step u of a row pair: positions x = 2u, 2u+1
+  auto step = [&](int u, const Row& lc, const Row& ln) {
+    const int x = 2 * u, k = u >> 1;
+    __builtin_amdgcn_sched_barrier(0);
+    const f32x2 g0 = gq[x & 3], g1 = gq[(x + 1) & 3];
+    f32x2 dm = xq[(x + 7) & 7], d0 = xq[x & 7], d1 = xq[(x + 1) & 7], d2 = xq[(x + 2) & 7];
+    if (x == 0) dm = f32x2{0.f, 0.f};
+    if (x == Wc - 2) d2 = f32x2{0.f, 0.f};
+    const f32x2 v0 = wpk_sub(dm, d1), v1 = wpk_add(d0, d1), v2 = wpk_sub(d1, d0), v3 = wpk_sub(d0, d2);
+    const f32x2 m1 = wpk_add(g0, g1), m2 = wpk_sub(g0, g1);
+    bsum = wpk_add(bsum, m1);
+    __builtin_amdgcn_sched_barrier(0);
+    // the next x-step's operands (positions past the row end are the next pair's first ones: same ring)
+    rd_x(x + 3); rd_x(x + 4); rd_g(x + 2); rd_g(x + 3);
+    {
+      const int m = k + L, set = m & 1;
+      if ((u & 1) == 0) {
+        store_x(set, m % NU);
+        load_x(m + 2 < NU ? lc : ln, set, (m + 2) % NU);
+      } else {
+        store_g(set, m % NU);
+        load_g(m + 2 < NU ? lc : ln, set, (m + 2) % NU);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        acc[0][s][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(v0[s], g0[t], acc[0][s][t], 0, 0, 0);
+        acc[1][s][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(v1[s], m1[t], acc[1][s][t], 0, 0, 0);
+        acc[2][s][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(v2[s], m2[t], acc[2][s][t], 0, 0, 0);
+        acc[3][s][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(v3[s], g1[t], acc[3][s][t], 0, 0, 0);
+      }
+    if ((u & 1) && (k + 1) % BI == 0) lds_sync();
+  };
+
+  for (int pair = p0; pair < p1; ++pair) {
+    const Row nxt = row_setup(pair + 1);
+#pragma unroll
+    for (int u = 0; u < Wc / 2; ++u) step(u, cur, nxt);
+    cur = nxt;
+  }
+
+  // ---- partial: slot = (xi_z, xi_y) * 4 + xi_x (the layout wgrad_wxyz_reduce_kernel sums in a fixed order) ------------------------
+  float* P = a.partial + static_cast<int64_t>(range) * 64 * a.Cinp * a.Coutp;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    const int slot = zy * 4 + d;
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int i = (e & 3) + 8 * (e >> 2) + 4 * half;
+          const int ci = ci0 + 2 * i + s, co = co0 + 2 * r + t;
+          P[(static_cast<int64_t>(slot) * a.Cinp + ci) * a.Coutp + co] = acc[d][s][t][e];
+        }
+  }
+  if (do_bias) {
+    bsum[0] += __shfl_xor(bsum[0], 32, 64);
+    bsum[1] += __shfl_xor(bsum[1], 32, 64);
+    if (half == 0) {
+      float* pb = a.bpartial + static_cast<int64_t>(range) * a.Coutp + co0 + 2 * r;
+      pb[0] = bsum[0]; pb[1] = bsum[1];
+    }
+  }
+}
+
+// one launch of all 16 (xi_z, xi_y) types of a range, adjacent in the grid (as wgrad_wxyz_fused_kernel); Cin = Cout = 128, W = 8 WP8
+template <int WP8>
+__global__ __launch_bounds__(kThreads, 1) void wgrad_wxyz_staged_kernel(const WxyzArgs aa) {
+  const int wg = wxyz_wg(aa.w.nranges * 16);
+  const int range = wg >> 4, type = wg & 15;
+  const int xiz = type >> 2, xiy = type & 3;
+  const bool gz = xiz == 1 || xiz == 2, gy = xiy == 1 || xiy == 2;
+  const int sel = (gz ? xiz - 1 : xiz / 3) * 2 + (gy ? xiy - 1 : xiy / 3);
+  __shared__ __attribute__((aligned(16))) float sStage[WxyzStage<WP8>::kLdsBytes / 4];
+  if (gz && gy) wgrad_wxyz_staged_body<WP8, true, true>(aa, range, sel, sStage);
+  else if (gz) wgrad_wxyz_staged_body<WP8, true, false>(aa, range, sel, sStage);
+  else if (gy) wgrad_wxyz_staged_body<WP8, false, true>(aa, range, sel, sStage);
+  else wgrad_wxyz_staged_body<WP8, false, false>(aa, range, sel, sStage);
+}
+
 // gw[dz][dy][dx][ci][co] = G^T_z G^T_y G^T_x of the summed (fixed order) partials U[xi_z][xi_y][xi_x]; index 3 of every axis carries a
 // flipped sign.  Workgroup = 32 consecutive (ci, co) elements x 8 range groups; every group applies the (linear) transform to its own
 // sums, the 8 x 27 results are combined in a fixed order through LDS.
@@ -2447,6 +2691,13 @@ static int conv_wgrad_impl(const float* x, const float* gy, float* gw, float* gb
     const dim3 gridq((unsigned)(p.nranges * 4), grid.y, grid.z);      // 4 workgroup types per launch
 #endif
     const dim3 gridf((unsigned)(p.nranges * 16), grid.y, grid.z);       // all 16 (xi_z, xi_y) types of a range, adjacent
+    // the default (req 0) at the 128 -> 128, W = 64 | 32 levels: the staged form (operands fetched and combined once per workgroup,
+    // same partials bit for bit); req 4 keeps wgrad_wxyz_fused_kernel, the comparison and the form of every other shape
+    const bool staged = req == 0 && Cin == 128 && Cout == 128 && (W == 64 || W == 32);
+    if (staged) {
+      if (W == 64) hipLaunchKernelGGL((wgrad_wxyz_staged_kernel<8>), gridf, dim3(kThreads), 0, s, aa);
+      else hipLaunchKernelGGL((wgrad_wxyz_staged_kernel<4>), gridf, dim3(kThreads), 0, s, aa);
+    } else {
 #define DF_WXYZ(WP) hipLaunchKernelGGL((wgrad_wxyz_fused_kernel<WP, 128>), gridf, dim3(kThreads), 0, s, aa)
 #ifdef DF_TUNING
     // experiments of tools/wgrad_diag.py (W = 64 rows): four launches by (GZ, GY) class (the round-1 form) with DBGV variants
@@ -2476,6 +2727,7 @@ static int conv_wgrad_impl(const float* x, const float* gy, float* gw, float* gb
     if (W == 64) DF_WXYZ(8); else if (W == 32) DF_WXYZ(4); else if (W == 16) DF_WXYZ(2); else if (W == 112) DF_WXYZ(14); else if (W == 128) DF_WXYZ(16); else DF_WXYZ(7);
 #undef DF_WXYZ
 #undef DF_WXYZ64
+    }
     const int64_t rgx = ceil_div(Cin * Cout, 32);
     hipLaunchKernelGGL(wgrad_wxyz_reduce_kernel, dim3((unsigned)rgx), dim3(kThreads), 0, s, a.partial, a.bpartial, gw, gb,
                        Cin == 64 ? p.nranges : p.nranges * p.nsub, (int)Cin, (int)Cout, p.Cinp, p.Coutp, 0);      // (64 -> 64: summed in the workgroup)
