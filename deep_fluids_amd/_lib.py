@@ -122,6 +122,9 @@ SIGNATURES = {
     "df_upconv_wgrad_algo": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, P, I64, I32, P]),
     "df_conv_wgrad_form": (I32, [I64, I64, I64, I64, I64, I64, I32, I32]),
     "df_upconv_wgrad_form": (I32, [I64, I64, I64, I64, I64, I64, I32, I32]),
+    "df_plane_views3d": (I32, [P, P, P, P, P, I64, I64, I64, I64, I64, P]),
+    "df_velocity_views3d": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P]),
+    "df_denorm_img2d": (I32, [P, P, I64, I64, I64, I64, I32, P]),
 }
 
 DF_CONV_LRELU, DF_CONV_RESIDUAL, DF_CONV_MASK, DF_CONV_BIAS, DF_CONV_ADDUP, DF_CONV_VALU_ONLY = 1, 2, 4, 8, 16, 32

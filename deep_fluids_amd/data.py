@@ -160,6 +160,58 @@ class BatchManager(object):
                 yield np.array(x_batch), []
                 x_batch = []
 
+    # ---- fixed ground-truth samples of the sample sheets (data.py:197-308) ---------------------------------
+    def list_from_p(self, p_list):
+        """File paths of the samples with parameter indices ``p_list`` (data.py:197-202)."""
+        path_format = os.path.join(self.root, self.data_type[0], self.args["path_format"])
+        return [path_format % tuple(p) for p in p_list]
+
+    def _random_p(self):
+        p = [self.rng.randint(y_max) for y_max in self.y_num]
+        z = [(pi / float(self.y_num[i] - 1)) * 2 - 1 for i, pi in enumerate(p)]      # [-1,1]
+        return p, z
+
+    def random_list(self, num):
+        """``num`` samples at random parameter indices ``p`` (their normalised values ``z = p/(num-1)*2-1``), on the host.
+        2-D (data.py:204-229): ``(xs, pis, zis)`` with xs [num,Y,X,3|1] float images in [0,255] -- velocity gets a zero third channel,
+        a level set is thresholded at 0.5 first.  3-D (data.py:231-302): a dict with the fields ``x``, labels ``y``, the four
+        ``plane_view_np`` images of every field (``xy, zy, xym, zym``) and of its curl (``*_c``), ``p`` and ``z``."""
+        from .ops import plane_view_np
+        if not self.is_3d:
+            xs, pis, zis = [], [], []
+            for _ in range(num):
+                pi, zi = self._random_p()
+                x, _ = preprocess(self.list_from_p([pi])[0], self.data_type, self.x_range, self.y_range)
+                x = x.astype(np.float32)          # the reference normalises in place: the sample stays fp32
+                if self.data_type[0] == "v":
+                    x = np.concatenate((x, np.zeros((self.res_y, self.res_x, 1))), axis=-1)
+                elif self.data_type[0] == "l":
+                    x[x < (0.5 + 1e-3)] = -1
+                    x[x > -1] = 1
+                xs.append(np.clip((x + 1) * 127.5, 0, 255))
+                pis.append(pi)
+                zis.append(zi)
+            return np.array(xs), pis, zis
+        keys = ("xy", "zy", "xym", "zym")
+        sample = {k: [] for k in ("x", "y") + keys + tuple(k + "_c" for k in keys) + ("p", "z")}
+        for _ in range(num):
+            p, z = self._random_p()
+            sample["p"].append(p)
+            sample["z"].append(z)
+            x, y = preprocess(self.list_from_p([p])[0], self.data_type, self.x_range, self.y_range)
+            x = x.astype(np.float32)              # the reference normalises in place: the sample stays fp32
+            sample["x"].append(x)
+            sample["y"].append(y)
+            x_c = _curl_np3(x)
+            for k in keys:
+                kw = dict(xy_plane=k[0] == "x", project=not k.endswith("m"))
+                sample[k].append(plane_view_np(x, **kw))
+                sample[k + "_c"].append(plane_view_np(x_c, **kw))
+        for k in sample:
+            if k not in ("p", "z"):
+                sample[k] = np.array(sample[k])
+        return sample
+
     def denorm(self, x=None, y=None):
         """[-1,1] -> original range (data.py:186-195)."""
         if x is not None:
@@ -168,6 +220,16 @@ class BatchManager(object):
             for i, ri in enumerate(self.y_range):
                 y[:, i] = (y[:, i] + 1) * 0.5 * (ri[1] - ri[0]) + ri[0]
         return x, y
+
+
+def _curl_np3(x):
+    """Host NumPy curl of x [Z,Y,X,3] -- the ``c`` of ``jacobian_np3`` (ops.py:344-374): forward differences with the last difference
+    replicated, c = (dwdy - dvdz, dudz - dwdx, dvdx - dudy).  On the host because ``random_list`` runs once, on ``b_num`` samples."""
+    def d(a, axis):
+        g = np.diff(a, axis=axis)
+        return np.concatenate([g, np.take(g, [-1], axis=axis)], axis=axis)
+    u, v, w = x[..., 0], x[..., 1], x[..., 2]
+    return np.stack([d(w, 1) - d(v, 0), d(u, 0) - d(w, 2), d(v, 2) - d(u, 1)], axis=-1)
 
 
 def write_synthetic_dataset(root, spatial, num_p=(3, 2), num_frames=4, seed=0, ae=False):

@@ -28,6 +28,7 @@ __all__ = [
     "int_shape", "get_conv_shape", "nchw_to_nhwc", "nhwc_to_nchw", "add", "concat", "sigmoid", "mse_mean",
     "jacobian", "jacobian3", "curl", "curl3", "divergence", "divergence3", "pgrad",
     "vort_np", "curl_np", "grad_np", "jacobian_np3", "l1_mean", "velocity_loss",
+    "denorm_img", "plane_view", "denorm_img3", "plane_view_np", "velocity_views3", "add_channels", "remove_channels",
     "variable_scope", "get_variables", "get_variable", "reset_variables", "set_random_seed", "all_variables",
 ]
 
@@ -1595,6 +1596,84 @@ def velocity_loss(psi, x):
     ``u = curl(psi) | jacobian3(psi)[1]``, ``l1 = reduce_mean(abs(u - x))``, ``j_l1 = reduce_mean(abs(jacobian(u)[0] - jacobian(x)[0]))``.
     Gradients flow to ``psi`` through ``l1`` and ``j_l1``; ``u`` is returned detached (for metrics / summaries)."""
     return _VelocityLoss.apply(psi, x)
+
+
+# ---- uint8 image views (ops.py:138-188): inference only, no autograd, torch.uint8 out ----
+def add_channels(x, num_ch=1, data_format="NHWC"):
+    """ops.py:138-144: append ``num_ch`` zero channels."""
+    b, h, w, _ = get_conv_shape(x, data_format)
+    if data_format == "NCHW":
+        return torch.cat([x, torch.zeros((b, num_ch, h, w), dtype=x.dtype, device=x.device)], dim=1)
+    return torch.cat([x, torch.zeros((b, h, w, num_ch), dtype=x.dtype, device=x.device)], dim=-1)
+
+
+def remove_channels(x, data_format="NHWC"):
+    """ops.py:146-152: keep the first three channels."""
+    return x[:, :3] if data_format == "NCHW" else x[..., :3]
+
+
+def _u8(shape, like):
+    return torch.empty(shape, dtype=torch.uint8, device=like.device)
+
+
+def denorm_img(norm, data_format="NHWC"):
+    """ops.py:154-161: [-1,1] -> uint8 [B,H,W,1|3] (always channels-last); 2 channels get a zero third one, more than 3 lose the rest --
+    folded into the one kernel together with the layout change."""
+    x = _prep(norm.detach(), "norm")
+    if x.dim() != 4:
+        raise ValueError("denorm_img expects a 4-D tensor, got %s" % (tuple(x.shape),))
+    B, H, W, C = get_conv_shape(x, data_format)
+    out = _u8((B, H, W, 3 if (C == 2 or C > 3) else C), x)
+    call("df_denorm_img2d", _ptr(x), _ptr(out), B, H, W, C, 1 if data_format == "NCHW" else 0, _stream())
+    return out
+
+
+_VIEW_KEYS = ("xy", "zy", "xym", "zym")
+
+
+def _views3(x, keys):
+    x = _prep(x.detach(), "x")
+    if x.dim() != 5:
+        raise ValueError("plane views expect [B,Z,Y,X,C], got %s" % (tuple(x.shape),))
+    B, Z, Y, X, C = x.shape
+    out = {k: _u8((B, Y, X if k[0] == "x" else Z, C), x) for k in keys}
+    call("df_plane_views3d", _ptr(x), *([_ptr(out.get(k)) for k in _VIEW_KEYS] + [B, Z, Y, X, C, _stream()]))
+    return out
+
+
+def plane_view(x, xy_plane=True, project=True):
+    """ops.py:163-181: one uint8 view of x [B,Z,Y,X,C] -- the z mean / the Z//2 slice [B,Y,X,C], or the x mean / the X//2 slice with y as
+    the row [B,Y,Z,C]."""
+    k = ("xy" if xy_plane else "zy") + ("" if project else "m")
+    return _views3(x, (k,))[k]
+
+
+def denorm_img3(x):
+    """ops.py:183-188: {'xy', 'zy', 'xym', 'zym'} from ONE pass over x."""
+    return _views3(x, _VIEW_KEYS)
+
+
+def velocity_views3(u):
+    """(denorm_img3(u), denorm_img3(curl3(u))) -- the reference's ``G`` and ``G_vort`` (trainer3.py:22-25) -- from one pass over u, the
+    curl never written; bit-identical to the composition.  (No reference name: TF fuses nothing here.)"""
+    u = _prep(u.detach(), "u")
+    if u.dim() != 5 or u.shape[-1] != 3:
+        raise ValueError("velocity_views3 expects a 3-channel field [B,Z,Y,X,3], got %s" % (tuple(u.shape),))
+    B, Z, Y, X, _ = u.shape
+    ou = {k: _u8((B, Y, X if k[0] == "x" else Z, 3), u) for k in _VIEW_KEYS}
+    oc = {k: _u8((B, Y, X if k[0] == "x" else Z, 3), u) for k in _VIEW_KEYS}
+    call("df_velocity_views3d", _ptr(u), *([_ptr(ou[k]) for k in _VIEW_KEYS] + [_ptr(oc[k]) for k in _VIEW_KEYS] + [B, Z, Y, X, _stream()]))
+    return ou, oc
+
+
+def plane_view_np(x, xy_plane=True, project=True):
+    """ops.py:326-342: host NumPy, x [Z,Y,X,C] -> float image in [0,255] (no uint8 cast)."""
+    x = np.asarray(x)
+    if xy_plane:
+        x = np.mean(x, axis=0) if project else x[int(x.shape[0] / 2)]
+    else:
+        x = (np.mean(x, axis=2) if project else x[:, :, int(x.shape[2] / 2)]).transpose([1, 0, 2])
+    return np.clip((x + 1) * 127.5, 0, 255)
 
 
 # ---- NumPy-facing twins (ops.py:305-324, 344-374): ndarray in, ndarray out, computed on the GPU ----

@@ -29,6 +29,7 @@ from .ops import curl, curl3, jacobian, jacobian3, l1_mean, mse_mean, get_conv_s
 from .model import GeneratorBE, GeneratorBE3, AE, AE3, DiscriminatorPatch, DiscriminatorPatch3
 from .ops import concat, kl_bernoulli
 from .dist import GradSync, broadcast_trainer_state
+from .util import save_image, vort_image
 
 
 def default_config(**over):
@@ -39,7 +40,7 @@ def default_config(**over):
              start_step=0, random_seed=123, num_samples=21000, c_num=3, use_curl3_alias=True,
              z_num=16, use_sparse=False, sparsity=0.01, w4=1.0, w5=1.0, p_num=2, x_channels=None, w3=0.005,
              log_step=500, test_step=1000, test_batch_size=100, model_dir=None, load_path="", code_path="", save_sec=3600,   # config.py:62-68
-             fused_tail=True, graph=False, direct_grads=True)
+             fused_tail=True, graph=False, direct_grads=True, sample_images=False)
     c.update(over)
     return SimpleNamespace(**c)
 
@@ -271,7 +272,8 @@ class Trainer(object):
         if self.config.use_curl and self.fused_tail:
             # the whole tail -- curl, both Jacobians (the ground truth's, trainer.py:29-32, recomputed on the fly), both L1 means --
             # as one fused op: 36 B/voxel instead of 240, no 9-channel tensors (velocity_loss.hip); G_jaco_ / G_vort_ are not
-            # materialised (the summaries that show them, trainer.py:186-189, are out of scope)
+            # materialised (the pictures of G_vort_, trainer.py:186-189 / trainer3.py:22-25, come from `sample_images`, which forms the
+            # vorticity views from G_ on its own)
             g_loss_l1, g_loss_j_l1, G_ = ops.velocity_loss(out, x)
             g_loss = g_loss_l1 * self.w1 + g_loss_j_l1 * self.w2    # trainer.py:172
             return SimpleNamespace(G_s=out, G_=G_, G_jaco_=None, G_vort_=None, x_jaco=None, g_loss_l1=g_loss_l1,
@@ -303,6 +305,79 @@ class Trainer(object):
             if self.config.use_curl:
                 out = curl3(out) if self.is_3d else curl(out)
         return out
+
+    # ---- sample sheets (trainer.py:244-257, 750-778; trainer3.py:131-144, 193-237) ------------------------------------------------
+    _vort_normalize = None           # None: by config.arch ('ae' pictures keep the vorticity's own scale, trainer.py:775)
+
+    def get_vort_image(self, x):
+        """trainer.py:773-778: RdBu picture of the vorticity of x [B,H,W,>=2] in [-1,1] (host NumPy, float64)."""
+        norm = self._vort_normalize
+        if norm is None:
+            norm = "ae" not in str(getattr(self.config, "arch", "de"))
+        return vort_image(x, normalize=norm)
+
+    def sample_images(self, inputs, root_path, idx):
+        """The reference's ``generate(inputs, root_path, idx)`` (trainer.py:750-771 / trainer3.py:193-237; ``generate`` itself keeps its
+        meaning here): run the generator on every parameter batch of ``inputs`` -- the sweeps along each control parameter, then the
+        parameters of the fixed ground-truth samples -- and write the PNG sheets, ``b_num`` pictures per row.
+        2-D: ``<idx>_c.png`` (the sweeps), ``<idx>_cv.png`` (their vorticity), ``x_fixed_<idx>.png`` (last batch over its vorticity).
+        3-D: ``<idx>_xym.png`` / ``<idx>_zym.png`` (mid slices of the sweeps, then of their curl) and ``x_fixed_xym_<idx>.png`` /
+        ``x_fixed_zym_<idx>.png``, padding 1; the eight views of a batch come from ONE pass over the field (``ops.velocity_views3``) and
+        only the two mid-slice pairs are copied to the host.  Returns the written paths."""
+        os.makedirs(root_path, exist_ok=True)
+        paths = []
+
+        def write(arr, name, **kw):
+            path = os.path.join(root_path, name)
+            save_image(arr, path, nrow=self.b_num, **kw)
+            print("[*] Samples saved: {}".format(path))
+            paths.append(path)
+        fields = [self.generate(torch.as_tensor(np.asarray(z, np.float32)).to(self.device)) for z in inputs]
+        if not self.is_3d:
+            generated = [ops.denorm_img(g).cpu().numpy() for g in fields]
+            c_concat = np.concatenate(generated[:-1], axis=0)
+            write(c_concat, "{}_c.png".format(idx))
+            write(self.get_vort_image(c_concat / 127.5 - 1), "{}_cv.png".format(idx))
+            x = generated[-1]
+            write(np.concatenate((x, self.get_vort_image(x / 127.5 - 1)), axis=0), "x_fixed_{}.png".format(idx))
+            return paths
+        views = [ops.velocity_views3(g) for g in fields]
+        for tag in ("xym", "zym"):
+            vel = [vu[tag].cpu().numpy() for vu, _ in views]
+            vort = [vc[tag].cpu().numpy() for _, vc in views]
+            write(np.concatenate(vel[:-1] + vort[:-1], axis=0), "{}_{}.png".format(idx, tag), padding=1)
+        for tag in ("xym", "zym"):
+            vu, vc = views[-1]
+            write(np.concatenate((vu[tag].cpu().numpy(), vc[tag].cpu().numpy()), axis=0), "x_fixed_{}_{}.png".format(tag, idx), padding=1)
+        return paths
+
+    def _write_gt_txt(self, model_dir, p, z):
+        with open(os.path.join(model_dir, "x_fixed_gt.txt"), "w") as f:        # trainer.py:250-252
+            f.write(str(p) + "\n")
+            f.write(str(z))
+
+    def _sheets_begin(self, batch_manager, model_dir, z_samples):
+        """Once before the loop (trainer.py:244-257 / trainer3.py:131-144): ``b_num`` fixed ground-truth samples -> ``x_fixed_gt.png`` (2-D:
+        the samples over their vorticity) or ``x_fixed_xym_gt.png`` / ``x_fixed_zym_gt.png`` (3-D: mid slices over those of the curl) and
+        ``x_fixed_gt.txt`` (parameter indices and values); their parameters become the last entry of ``z_samples``."""
+        if self.is_3d:
+            s = batch_manager.random_list(self.b_num)
+            for tag in ("xym", "zym"):
+                save_image(np.concatenate((s[tag], s[tag + "_c"]), axis=0), os.path.join(model_dir, "x_fixed_%s_gt.png" % tag),
+                           padding=1, nrow=self.b_num)
+            p, z = s["p"], s["z"]
+        else:
+            x, p, z = batch_manager.random_list(self.b_num)
+            x = np.concatenate((x, self.get_vort_image(x / 127.5 - 1)), axis=0)
+            save_image(x, os.path.join(model_dir, "x_fixed_gt.png"), nrow=self.b_num)
+        self._write_gt_txt(model_dir, p, z)
+        zi = np.zeros((self.b_num, self.c_num), np.float32)
+        for i, z_gt in enumerate(z):
+            zi[i, :] = z_gt
+        return z_samples + [zi]
+
+    def _sheets_step(self, state, model_dir, step):
+        return self.sample_images(state, model_dir, step)
 
     # ---- one `sess.run(g_optim)` + `sess.run(g_lr_update)` (trainer.py:269, 284-288) -------------------------
     def forward_backward(self, x, y):
@@ -451,9 +526,12 @@ class Trainer(object):
         ``config.save_sec`` seconds of wall time (config.py:68; the Supervisor's timed saver).  Every ``log_step``
         steps (and at the last) the scalars of the reference's summary op are appended as one JSON line to
         ``<model_dir>/scalars.jsonl`` (the counterpart of the TensorBoard event file) and the loss is checked for NaN
-        (trainer.py:271-276); every ``test_step`` steps the fixed parameter sweeps are generated (trainer.py:230-241, 281-282;
-        stored as ``<model_dir>/<step>_G.npz`` instead of PNG sheets); the last checkpoint is written at the end
-        (trainer.py:290-292).  Only rank 0 of a data-parallel job writes files.  Returns the logged records."""
+        (trainer.py:271-276); every ``test_step`` steps the fixed parameter sweeps are generated (trainer.py:230-241, 281-282) and
+        stored as ``<model_dir>/<step>_G.npz`` (every field at full size) or, with ``config.sample_images``, as the reference's PNG
+        sheets (``sample_images``; the fixed ground-truth samples ``x_fixed*_gt.png`` + ``x_fixed_gt.txt`` are written once before the
+        loop and their parameters join the sweeps, trainer.py:244-257).  The sheets run eagerly, between graph replays when
+        ``graph=True``.  The last checkpoint is written at the end (trainer.py:290-292).  Only rank 0 of a data-parallel job writes
+        files.  Returns the logged records."""
         model_dir = model_dir or self.effective_model_dir()
         log_step = log_step or self.config.log_step
         test_step = test_step or self.config.test_step
@@ -469,6 +547,9 @@ class Trainer(object):
             zi = np.zeros((self.b_num, self.c_num), np.float32)
             zi[:, i] = np.linspace(-1, 1, num=self.b_num)
             z_samples.append(zi)
+        sheets = None
+        if model_dir and rank0 and getattr(self.config, "sample_images", False):
+            sheets = self._sheets_begin(batch_manager, model_dir, z_samples)
         records = []
         t0 = time.time()
         last_save = time.time()
@@ -493,7 +574,9 @@ class Trainer(object):
                             f.write(json.dumps(rec) + "\n")
                 if on_log is not None:
                     on_log(rec)
-            if model_dir and rank0 and (step % test_step == 0 or step == max_step - 1):
+            if sheets is not None and (step % test_step == 0 or step == max_step - 1):
+                self._sheets_step(sheets, model_dir, step)
+            elif model_dir and rank0 and (step % test_step == 0 or step == max_step - 1):
                 G = np.stack([self.generate(torch.from_numpy(z).to(self.device)).cpu().numpy() for z in z_samples])
                 np.savez_compressed(os.path.join(model_dir, "%d_G.npz" % step), G=G, z=np.stack(z_samples))
         if model_dir and rank0:
@@ -620,6 +703,57 @@ class AETrainer(Trainer):
         return SimpleNamespace(s=out, G_=x_, x_=x_, z=z, G_jaco_=x_jaco_, G_vort_=x_vort_, x_jaco=x_jaco,
                                g_loss_l1=loss_l1, g_loss_j_l1=loss_j_l1, loss_p=loss_p, loss_kl=loss_kl, g_loss=loss, loss=loss)
 
+
+    # ---- sample sheets of `train_ae` (trainer.py:425-432, 450-451, 780-790; trainer3.py:311-318, 333-334, 358-368) ----------------
+    _vort_normalize = False
+
+    def reconstruct(self, x):
+        """``x_`` of the inference graph (``build_test_model_ae``): encoder -> (sigmoid) -> decoder -> (curl)."""
+        ae = AE3 if self.is_3d else AE
+        with torch.no_grad():
+            out, _, _ = ae(x, self.filters, self.z_num, name=self.name, num_conv=self.num_conv, repeat=self.repeat,
+                           use_sparse=self.use_sparse, reuse=True)
+            if self.config.use_curl:
+                out = curl3(out) if self.is_3d else curl(out)
+        return out
+
+    def autoencode(self, inputs, root_path, idx):
+        """``autoencode`` of both reference trainers.  2-D (trainer.py:780-790): ``inputs`` are the pictures ``random_list`` returned
+        ([n,Y,X,3] in [0,255], the last channel is padding) -> ``<idx>.png``: the reconstructions over their vorticity.  3-D
+        (trainer3.py:358-368): ``inputs`` are the fields [n,Z,Y,X,3] -> ``xym_<idx>.png`` / ``zym_<idx>.png``.  Returns the paths."""
+        os.makedirs(root_path, exist_ok=True)
+        if self.is_3d:
+            x = torch.as_tensor(np.ascontiguousarray(inputs, np.float32)).to(self.device)
+            img = ops.denorm_img3(self.reconstruct(x))
+            paths = []
+            for tag in ("xym", "zym"):
+                paths.append(os.path.join(root_path, "{}_{}.png".format(tag, idx)))
+                save_image(img[tag].cpu().numpy(), paths[-1], nrow=self.b_num)
+                print("[*] Samples saved: {}".format(paths[-1]))
+            return paths
+        x_gt = np.asarray(inputs)[:self.b_num, ..., :-1] / 127.5 - 1      # take the padding channel off, to [-1,1]
+        x = ops.denorm_img(self.reconstruct(torch.as_tensor(np.ascontiguousarray(x_gt, np.float32)).to(self.device))).cpu().numpy()
+        x = np.concatenate((x, self.get_vort_image(x / 127.5 - 1)), axis=0)
+        path = os.path.join(root_path, "{}.png".format(idx))
+        save_image(x, path, nrow=self.b_num)
+        print("[*] Samples saved: {}".format(path))
+        return [path]
+
+    def _sheets_begin(self, batch_manager, model_dir, z_samples):
+        if self.is_3d:                                                    # trainer3.py:311-317
+            s = batch_manager.random_list(self.b_num)
+            save_image(s["xym"], os.path.join(model_dir, "xym_gt.png"), nrow=self.b_num)
+            save_image(s["zym"], os.path.join(model_dir, "zym_gt.png"), nrow=self.b_num)
+            self._write_gt_txt(model_dir, s["p"], s["z"])
+            return s["x"]
+        x, p, z = batch_manager.random_list(self.b_num)                   # trainer.py:426-433
+        save_image(np.concatenate((x, self.get_vort_image(x / 127.5 - 1)), axis=0), os.path.join(model_dir, "x_fixed_gt.png"),
+                   nrow=self.b_num)
+        self._write_gt_txt(model_dir, p, z)
+        return x
+
+    def _sheets_step(self, state, model_dir, step):
+        return self.autoencode(state, model_dir, step)
 
     # ---- `test_ae` (trainer.py:475-583, trainer3.py:311-367; `--arch=ae --is_train=False`) ------------------------------------
     def encode(self, x):

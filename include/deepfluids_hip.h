@@ -444,6 +444,26 @@ int df_conv_wgrad_algo(const float* x, const float* gy, float* gw, float* gb, in
 int df_conv_wgrad_form(int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int kz, int algo);
 int df_upconv_wgrad_form(int64_t B, int64_t Dc, int64_t Hc, int64_t Wc, int64_t Cin, int64_t Cout, int kz, int algo);
 
+/* ---- uint8 image views for the sample sheets written during training (ops.py:154-188; trainer.py:144-147, trainer3.py:22-25) ----
+ * Every value is uint8(clip((v + 1) * 127.5, 0, 255)) in fp32 (the cast truncates).  Outputs are DEVICE pointers to uint8.
+ *
+ * denorm_img3 / plane_view (ops.py:163-188) of x [B,Z,Y,X,C], C in 1..4, in one pass over x:
+ *   xy [B,Y,X,C] = mean over z;  zy [B,Y,Z,C] = mean over x, y as the row (plane_view(.., xy_plane=False));
+ *   xym [B,Y,X,C] = slice z = Z/2;  zym [B,Y,Z,C] = slice x = X/2.   Any output may be NULL (skipped), not all of them.
+ * The means are sequential fp32 sums (ascending z / x) divided by the extent; run-to-run bitwise deterministic.
+ * Errors: DF_EINVAL null input / non-positive extent / every output null, DF_ESHAPE C outside 1..4 or a [Z, X*C] row-plane beyond the
+ * workgroup's LDS, DF_EALIGN input not 4-byte aligned. */
+int df_plane_views3d(const float* x, uint8_t* xy, uint8_t* zy, uint8_t* xym, uint8_t* zym, int64_t B, int64_t Z, int64_t Y, int64_t X,
+                     int64_t C, df_stream_t stream);
+/* The same four views of u [B,Z,Y,X,3] and of curl(u) = the c of df_jacobian3d_fwd (trainer3.py:22-25: G and G_vort), the curl never
+ * written: the c* views equal df_plane_views3d of df_jacobian3d_fwd's c bit for bit.  Every extent >= 2 (DF_ESHAPE otherwise). */
+int df_velocity_views3d(const float* u, uint8_t* xy, uint8_t* zy, uint8_t* xym, uint8_t* zym, uint8_t* cxy, uint8_t* czy, uint8_t* cxym,
+                        uint8_t* czym, int64_t B, int64_t Z, int64_t Y, int64_t X, df_stream_t stream);
+/* denorm_img (ops.py:154-161): x [B,H,W,C] (nchw = 0) or [B,C,H,W] (nchw != 0) -> out [B,H,W,Co] uint8, always channels-last;
+ * C = 2 gets a zero third channel (mapped like every value: 127), C > 3 keeps the first three, C = 1 | 3 is kept.
+ * Errors: DF_EINVAL null pointer / non-positive extent, DF_ESHAPE C < 1, DF_EALIGN input not 4-byte aligned. */
+int df_denorm_img2d(const float* x, uint8_t* out, int64_t B, int64_t H, int64_t W, int64_t C, int nchw, df_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
