@@ -125,6 +125,13 @@ SIGNATURES = {
     "df_plane_views3d": (I32, [P, P, P, P, P, I64, I64, I64, I64, I64, P]),
     "df_velocity_views3d": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P]),
     "df_denorm_img2d": (I32, [P, P, I64, I64, I64, I64, I32, P]),
+    "df_advect_sl2d": (I32, [P, P, P, I64, I64, I64, F32, F32, I32, P]),
+    "df_advect_sl3d": (I32, [P, P, P, I64, I64, I64, I64, F32, F32, I32, P]),
+    "df_advect_mc2d": (I32, [P, P, P, P, I64, I64, I64, F32, F32, I32, I32, P]),
+    "df_advect_mc3d": (I32, [P, P, P, P, I64, I64, I64, I64, F32, F32, I32, I32, P]),
+    "df_density_source": (I32, [P, P, F32, P, I64, P]),
+    "df_density_image2d": (I32, [P, P, I64, I64, I64, P]),
+    "df_density_image3d": (I32, [P, P, I64, I64, I64, I64, P]),
 }
 
 DF_CONV_LRELU, DF_CONV_RESIDUAL, DF_CONV_MASK, DF_CONV_BIAS, DF_CONV_ADDUP, DF_CONV_VALU_ONLY = 1, 2, 4, 8, 16, 32

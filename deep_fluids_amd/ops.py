@@ -29,6 +29,7 @@ __all__ = [
     "jacobian", "jacobian3", "curl", "curl3", "divergence", "divergence3", "pgrad",
     "vort_np", "curl_np", "grad_np", "jacobian_np3", "l1_mean", "velocity_loss",
     "denorm_img", "plane_view", "denorm_img3", "plane_view_np", "velocity_views3", "add_channels", "remove_channels",
+    "advect", "advect_sequence", "advect_workspace", "density_image", "sphere_mask",
     "variable_scope", "get_variables", "get_variable", "reset_variables", "set_random_seed", "all_variables",
 ]
 
@@ -1664,6 +1665,149 @@ def velocity_views3(u):
     oc = {k: _u8((B, Y, X if k[0] == "x" else Z, 3), u) for k in _VIEW_KEYS}
     call("df_velocity_views3d", _ptr(u), *([_ptr(ou[k]) for k in _VIEW_KEYS] + [_ptr(oc[k]) for k in _VIEW_KEYS] + [B, Z, Y, X, _stream()]))
     return ou, oc
+
+
+# ---- density advection through a velocity field (the advect() mode of the reference's scene scripts, scene/smoke_pos_size.py:45-109):
+#      inference only, no autograd.  The step is defined in include/deepfluids_hip.h; mantaflow, which the reference calls for it, cannot
+#      be run here, so bit parity with it is not claimed ----
+def _advect_dims(density, vel):
+    d = _prep(density.detach(), "density")
+    v = _prep(vel.detach(), "vel")
+    if d.dim() not in (3, 4):
+        raise ValueError("advect expects a density [B,(Z,)Y,X], got %s" % (tuple(d.shape),))
+    nd = d.dim() - 1
+    if tuple(v.shape) != tuple(d.shape) + (nd,):
+        raise ValueError("advect expects a velocity %s for a density %s, got %s" % (tuple(d.shape) + (nd,), tuple(d.shape), tuple(v.shape)))
+    return d, v, nd
+
+
+def _source_mask(source, like):
+    m = source if isinstance(source, torch.Tensor) else torch.as_tensor(np.asarray(source))
+    if not m.is_cuda:
+        m = m.to(like.device)
+    if m.dtype != torch.uint8:
+        m = (m != 0).to(torch.uint8)
+    if tuple(m.shape) != tuple(like.shape):
+        m = m.expand(like.shape)
+    return m.contiguous()
+
+
+def advect_workspace(density, order=2, source=False):
+    """The scratch ``advect`` needs for one step on ``density``: one grid for the source-stamped density, one for the forward pass of
+    order 2.  Reusable across calls of the same shape."""
+    n = density.numel() * ((1 if source else 0) + (1 if order == 2 else 0))
+    return torch.empty((max(n, 1),), dtype=torch.float32, device=density.device)
+
+
+def _advect_step(d, v, nd, out, fwd, dt, order, clamp_mode, bnd, vel_scale):
+    sfx = "%dd" % nd
+    dims = list(d.shape)
+    if order == 1:
+        call("df_advect_sl" + sfx, _ptr(d), _ptr(v), _ptr(out), *(dims + [dt, vel_scale, bnd, _stream()]))
+    else:
+        call("df_advect_sl" + sfx, _ptr(d), _ptr(v), _ptr(fwd), *(dims + [dt, vel_scale, bnd, _stream()]))
+        call("df_advect_mc" + sfx, _ptr(d), _ptr(fwd), _ptr(v), _ptr(out), *(dims + [dt, vel_scale, bnd, clamp_mode, _stream()]))
+
+
+def _advect_args(order, clamp_mode, bnd):
+    if order not in (1, 2):
+        raise ValueError("advect: order must be 1 (semi-Lagrangian) or 2 (MacCormack), got %r" % (order,))
+    if clamp_mode not in (1, 2):
+        raise ValueError("advect: clamp_mode must be 1 or 2, got %r" % (clamp_mode,))
+    if int(bnd) != bnd or bnd < 1:
+        raise ValueError("advect: bnd must be an integer >= 1, got %r" % (bnd,))
+
+
+def advect(density, vel, dt, order=2, clamp_mode=2, bnd=1, vel_scale=1.0, source=None, source_value=1.0, out=None, workspace=None):
+    """One advection step of ``density`` [B,(Z,)Y,X] through ``vel`` [B,(Z,)Y,X,C] (MAC face values, C = 2 | 3), modelled on mantaflow's
+    ``advectSemiLagrange(order, boundaryWidth=bnd, clampMode=clamp_mode)`` as the reference's scene scripts call it
+    (scene/smoke_pos_size.py:99-101) -- NOT bit-identical to mantaflow, which cannot be run here; include/deepfluids_hip.h holds the
+    definition that is tested.  ``vel_scale`` multiplies the velocities inside the kernel (``x_range`` for a generator's normalised
+    output); ``source`` is an optional mask [B,(Z,)Y,X] (or one broadcastable to it) of cells set to ``source_value`` before the step.
+    Returns a new density (``out`` if given; it must not be ``density``).  ``workspace``: see ``advect_workspace``."""
+    with torch.no_grad():
+        _advect_args(order, clamp_mode, bnd)
+        d, v, nd = _advect_dims(density, vel)
+        n = d.numel()
+        need = n * ((1 if source is not None else 0) + (1 if order == 2 else 0))
+        ws = workspace if workspace is not None else advect_workspace(d, order, source is not None)
+        if ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < need:
+            raise ValueError("advect: workspace must be a contiguous float32 GPU tensor of >= %d elements" % need)
+        ws = ws.view(-1)
+        if out is None:
+            out = _empty(d.shape, d)
+        elif out.data_ptr() == d.data_ptr() or tuple(out.shape) != tuple(d.shape) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("advect: out must be a contiguous float32 tensor of the density's shape, and not the density itself")
+        off = 0
+        if source is not None:
+            stamped = ws[:n].view(d.shape)
+            call("df_density_source", _ptr(d), _ptr(_source_mask(source, d)), float(source_value), _ptr(stamped), n, _stream())
+            d, off = stamped, n
+        fwd = ws[off:off + n] if order == 2 else None
+        _advect_step(d, v, nd, out, fwd, float(dt), order, clamp_mode, int(bnd), float(vel_scale))
+        return out
+
+
+def density_image(d, out=None):
+    """The ``d_adv`` frame of density [B,(Z,)Y,X] (scene/smoke_pos_size.py:105-106): uint8 [B,Y,X], rows flipped in y, of
+    ``clip(255 * d, 0, 255)`` (3-D: of the z mean).  The reference casts without clipping, so values outside [0,1] wrap there."""
+    with torch.no_grad():
+        d = _prep(d.detach(), "density")
+        if d.dim() not in (3, 4):
+            raise ValueError("density_image expects [B,(Z,)Y,X], got %s" % (tuple(d.shape),))
+        shape = (d.shape[0], d.shape[-2], d.shape[-1])
+        if out is None:
+            out = _u8(shape, d)
+        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous():
+            raise ValueError("density_image: out must be a contiguous uint8 tensor %s" % (shape,))
+        call("df_density_image%dd" % (d.dim() - 1), _ptr(d), _ptr(out), *(list(d.shape) + [_stream()]))
+        return out
+
+
+def advect_sequence(density0, vels, dt, order=2, clamp_mode=2, bnd=1, vel_scale=1.0, source=None, source_value=1.0, images=False):
+    """``T`` chained ``advect`` steps over ``vels`` [T,B,(Z,)Y,X,C] (a tensor or a sequence of T tensors), the source stamped before
+    every step, ping-ponging two density buffers (``density0`` is left untouched).  Returns the final density, and with ``images`` also
+    the uint8 frames [T,B,Y,X] of ``density_image`` after each step, produced on the device and copied to the host once (a NumPy
+    array)."""
+    with torch.no_grad():
+        _advect_args(order, clamp_mode, bnd)
+        T = len(vels)
+        if T < 1:
+            raise ValueError("advect_sequence: no velocity frames")
+        cur, _, nd = _advect_dims(density0, vels[0])
+        cur = cur.clone()
+        nxt = torch.empty_like(cur)
+        fwd = torch.empty_like(cur) if order == 2 else None
+        mask = _source_mask(source, cur) if source is not None else None
+        n = cur.numel()
+        imgs = _u8((T, cur.shape[0], cur.shape[-2], cur.shape[-1]), cur) if images else None
+        for t in range(T):
+            _, v, _ = _advect_dims(cur, vels[t])
+            if mask is not None:
+                call("df_density_source", _ptr(cur), _ptr(mask), float(source_value), _ptr(cur), n, _stream())
+            _advect_step(cur, v, nd, nxt, fwd, float(dt), order, clamp_mode, int(bnd), float(vel_scale))
+            cur, nxt = nxt, cur
+            if images:
+                density_image(cur, out=imgs[t])
+        if images:
+            return cur, imgs.cpu().numpy()
+        return cur
+
+
+def sphere_mask(shape, center, radius, device=None):
+    """mantaflow's ``Sphere.applyToGrid`` as a mask: uint8 [(Z,)Y,X], 1 where the cell centre (i+.5, j+.5[, k+.5]) lies within ``radius``
+    of ``center`` (cell units, xyz order).  Built on the host (it is made once per sweep); ``device=None`` keeps it there."""
+    shape = tuple(int(n) for n in shape)
+    if len(shape) not in (2, 3) or len(center) != len(shape):
+        raise ValueError("sphere_mask expects a 2-D or 3-D shape and a centre of as many coordinates, got %s, %s" % (shape, tuple(center)))
+    r2 = np.zeros(shape, np.float64)
+    for a, c in enumerate(center):                      # a = 0 is x: the last array axis
+        ax = len(shape) - 1 - a
+        sh = [1] * len(shape)
+        sh[ax] = shape[ax]
+        r2 = r2 + ((np.arange(shape[ax]) + 0.5 - float(c)) ** 2).reshape(sh)
+    m = torch.from_numpy((r2 <= float(radius) * float(radius)).astype(np.uint8))
+    return m if device is None else m.to(device)
 
 
 def plane_view_np(x, xy_plane=True, project=True):

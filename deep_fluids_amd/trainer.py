@@ -585,17 +585,12 @@ class Trainer(object):
             batch_manager.stop_thread()
         return records
 
-    # ---- `test_` (trainer.py:314-354): one parameter pair, every frame, de-normalised, one .npz per frame ----------------------
-    def test_(self, batch_manager, model_dir=None, p1=10, p2=2, test_b_num=None):
-        """The inference sweep of ``Trainer.test_``: fix the first two control parameters at grid indices (p1, p2) -> c = p/(num-1)*2-1,
-        sweep the last one (the frame number) over its ``y_num[2]`` values in [-1, 1], run the inference graph in batches of
-        ``test_batch_size``, de-normalise with the dataset's velocity range (``batch_manager.denorm``) and dump frame i to
-        ``<model_dir>/<p1>_<p2>/<i>.npz`` under key ``x`` (np.savez_compressed) -- the files the reference's visualisation scripts read."""
-        model_dir = model_dir or self.effective_model_dir()
+    def _sweep_codes(self, batch_manager, p1, p2, test_b_num, who):
+        """The parameter sweep of ``test_`` (trainer.py:319-333): ``(z_c [y3, c_num], number of batches, batch size)``."""
         test_b_num = test_b_num or self.config.test_batch_size
         y1, y2, y3 = (int(v) for v in batch_manager.y_num[:3])
         if y3 % test_b_num != 0:                                     # trainer.py:324 asserts; the default 100 rarely divides test data
-            raise ValueError("test_: the number of frames (%d) must be a multiple of test_batch_size (%d)" % (y3, test_b_num))
+            raise ValueError("%s: the number of frames (%d) must be a multiple of test_batch_size (%d)" % (who, y3, test_b_num))
         niter = y3 // test_b_num
         c1 = p1 / float(y1 - 1) * 2 - 1
         c2 = p2 / float(y2 - 1) * 2 - 1
@@ -603,6 +598,16 @@ class Trainer(object):
         z_c[:, 0] = c1
         z_c[:, 1] = c2
         z_c[:, -1] = np.linspace(-1, 1, num=y3)
+        return z_c, niter, test_b_num
+
+    # ---- `test_` (trainer.py:314-354): one parameter pair, every frame, de-normalised, one .npz per frame ----------------------
+    def test_(self, batch_manager, model_dir=None, p1=10, p2=2, test_b_num=None):
+        """The inference sweep of ``Trainer.test_``: fix the first two control parameters at grid indices (p1, p2) -> c = p/(num-1)*2-1,
+        sweep the last one (the frame number) over its ``y_num[2]`` values in [-1, 1], run the inference graph in batches of
+        ``test_batch_size``, de-normalise with the dataset's velocity range (``batch_manager.denorm``) and dump frame i to
+        ``<model_dir>/<p1>_<p2>/<i>.npz`` under key ``x`` (np.savez_compressed) -- the files the reference's visualisation scripts read."""
+        model_dir = model_dir or self.effective_model_dir()
+        z_c, niter, test_b_num = self._sweep_codes(batch_manager, p1, p2, test_b_num, "test_")
         G = []
         for b in range(niter):
             z = torch.from_numpy(z_c[test_b_num * b:test_b_num * (b + 1)]).to(self.device)
@@ -615,6 +620,35 @@ class Trainer(object):
         for i, G_ in enumerate(G):
             np.savez_compressed(os.path.join(out_dir, "%d.npz" % i), x=G_)
         return out_dir
+
+    # ---- `advect()` of the scene scripts (scene/smoke_pos_size.py:45-109): smoke carried through the generated velocities ------
+    def advect_(self, batch_manager, model_dir=None, p1=10, p2=2, test_b_num=None, *, source, dt=None, order=2, clamp_mode=2, bnd=1):
+        """The sweep of ``test_`` looked at the way the reference's scene scripts do (their ``advect()`` mode): generate every frame of the
+        parameter pair (p1, p2), keep the frames on the device -- they are never de-normalised on the host, the advection kernels scale
+        them by ``batch_manager.x_range`` -- and, per frame, stamp ``source`` into a density grid that starts empty, advect it through
+        the frame's velocity (``ops.advect_sequence``: mantaflow's advectSemiLagrange restated, not bit-identical to it) and write the
+        grey frame ``<model_dir>/<p1>_<p2>/d_adv/%04d.png`` (3-D: of the z mean; values are clipped to [0,255] where the reference's
+        cast wraps).  ``source``: a mask [(Z,)Y,X] or ``{"center": xyz, "radius": r}`` in cell units (``smoke_pos_size_source`` builds
+        the one of scene/smoke_pos_size.py); ``dt``: the dataset's ``time_step`` when args.txt has it, else 0.5.
+        Returns ``(out_dir, final density [1,(Z,)Y,X] on the device)``."""
+        from PIL import Image
+        model_dir = model_dir or self.effective_model_dir()
+        z_c, niter, test_b_num = self._sweep_codes(batch_manager, p1, p2, test_b_num, "advect_")
+        if dt is None:
+            dt = float(batch_manager.args["time_step"]) if "time_step" in batch_manager.args else 0.5
+        frames = [self.generate(torch.from_numpy(z_c[test_b_num * b:test_b_num * (b + 1)]).to(self.device)) for b in range(niter)]
+        frames = torch.cat(frames, dim=0)                                   # [y3,(Z,)Y,X,C]
+        spatial = tuple(frames.shape[1:-1])
+        if isinstance(source, dict):
+            source = ops.sphere_mask(spatial, source["center"], source["radius"], self.device)
+        density0 = torch.zeros((1,) + spatial, dtype=torch.float32, device=frames.device)
+        final, imgs = ops.advect_sequence(density0, frames.unsqueeze(1), dt, order=order, clamp_mode=clamp_mode, bnd=bnd,
+                                          vel_scale=float(batch_manager.x_range), source=source, source_value=1.0, images=True)
+        out_dir = os.path.join(model_dir, "%d_%d" % (p1, p2), "d_adv")
+        os.makedirs(out_dir, exist_ok=True)
+        for t in range(imgs.shape[0]):
+            Image.fromarray(imgs[t, 0]).save(os.path.join(out_dir, "%04d.png" % t))
+        return out_dir, final
 
     def _optimizer_scalars(self, grad_scale):
         """The optimizer's per-step host scalars ``[lr_t | lr, grad_scale]``; advances Adam's step count (beta powers)."""
@@ -646,6 +680,21 @@ class Trainer(object):
     def _apply_adam(self, grad_scale):
         """(kept for callers of the pre-graph API) one eager optimizer step with the gradients scaled by ``grad_scale``."""
         self._apply_optimizer(self._optimizer_scalars(grad_scale), None)
+
+
+def smoke_pos_size_source(batch_manager, p1, p2):
+    """The smoke source of scene/smoke_pos_size.py:46-55,81 for grid indices (p1, p2) of a dataset written by that scene:
+    ``{"center": (X * x_pos, Y * src_y_pos), "radius": X * r}`` with x_pos and r interpolated from the min_/max_/num_ keys of args.txt."""
+    a = batch_manager.args
+    keys = ["min_src_x_pos", "max_src_x_pos", "num_src_x_pos", "min_src_radius", "max_src_radius", "num_src_radius", "src_y_pos"]
+    missing = [k for k in keys if k not in a]
+    if missing:
+        raise KeyError("smoke_pos_size_source: args.txt of %s lacks %s -- the dataset is not a smoke_pos_size scene; pass the source of "
+                       "its own scene script as a mask or {'center', 'radius'}" % (batch_manager.root, ", ".join(missing)))
+    x_pos = p1 / float(int(a["num_src_x_pos"]) - 1) * (float(a["max_src_x_pos"]) - float(a["min_src_x_pos"])) + float(a["min_src_x_pos"])
+    rad = p2 / float(int(a["num_src_radius"]) - 1) * (float(a["max_src_radius"]) - float(a["min_src_radius"])) + float(a["min_src_radius"])
+    rx, ry = int(batch_manager.res_x), int(batch_manager.res_y)
+    return {"center": (rx * x_pos, ry * float(a["src_y_pos"])), "radius": rx * rad}
 
 
 class Trainer3(Trainer):

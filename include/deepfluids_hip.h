@@ -464,6 +464,45 @@ int df_velocity_views3d(const float* u, uint8_t* xy, uint8_t* zy, uint8_t* xym, 
  * Errors: DF_EINVAL null pointer / non-positive extent, DF_ESHAPE C < 1, DF_EALIGN input not 4-byte aligned. */
 int df_denorm_img2d(const float* x, uint8_t* out, int64_t B, int64_t H, int64_t W, int64_t C, int nchw, df_stream_t stream);
 
+/* ---- density advection through a velocity field: the advect() mode of the reference's scene scripts (scene/smoke_pos_size.py:45-109,
+ * scene/smoke3_vel_buo.py:49-125), which call mantaflow's advectSemiLagrange(order, boundaryWidth, clampMode).  mantaflow cannot be run
+ * beside this library, so bit parity with it is NOT claimed: the definition below is the contract (tests/advect_ref.py restates it).
+ *
+ * density [B,(Z,)Y,X], velocity [B,(Z,)Y,X,C] with C = 2 (2-D) | 3 (3-D), fp32; channels are the (x, y[, z]) MAC face values
+ * (copyArrayToGridMAC: component x of cell i sits on its low-x face); cell (i,j,k) is [..,k,j,i].  bnd >= 1 is the boundary width with
+ * 2*bnd + 2 <= every extent; a cell is interior when bnd <= index < extent - bnd on every axis, else it is on the band.
+ *   uc          = (0.5 * (vx(i,j,k) + vx(i+1,j,k))) * vel_scale, likewise y and z (interior cells only)
+ *   interp(g,p) = linear interpolation of the cell-centred grid g, per axis q = p - 0.5, n = (int)q, s1 = q - n, s0 = 1 - s1;
+ *                 q < 0 -> n = 0, s0 = 1, s1 = 0;  n >= extent - 1 -> n = extent - 2, s0 = 0, s1 = 1;  sum over the 2^d corners n, n+1,
+ *                 s0*a + s1*b per axis, x innermost
+ *   SL(g, +-dt) = interp(g, (i+.5, j+.5, k+.5) -+ dt*uc) on interior cells, 0 on the band
+ * df_advect_sl*:  fwd = SL(density, dt) -- the whole step of order 1, the first half of order 2.
+ * df_advect_mc*:  the second half of order 2 (MacCormack), one pass: bwd = SL(fwd, -dt), cor = fwd + 0.5 * (orig - bwd);
+ *                 c = trunc((i,j,k) - dt*uc) per axis (no +0.5: mantaflow's doClampComponent) clamped to [0, extent - 2]; min / max of
+ *                 orig over those of the 2^d corners c, c+1 that are interior cells (clamp_mode 1: also those around
+ *                 trunc((i,j,k) + dt*uc)); none interior -> out = fwd;  clamp_mode 2 (the reference's default): out = fwd if
+ *                 cor < min or cor > max, else cor;  clamp_mode 1: out = clamp(cor, min, max);  band: out = 0.
+ * The order of the scheme is the caller's choice of entry points (1: sl alone; 2: sl, then mc on its result).  The step gathers: the
+ * output must not alias an input.  Non-finite velocities select edge cells, never memory outside the arrays.
+ * Errors: DF_EINVAL null pointer / non-positive extent / bnd < 1 / clamp_mode not 1 | 2 / output aliasing an input, DF_ESHAPE an
+ * extent < 2*bnd + 2 or too large, DF_EALIGN a pointer not 4-byte aligned. */
+int df_advect_sl2d(const float* density, const float* vel, float* fwd, int64_t B, int64_t Y, int64_t X, float dt, float vel_scale, int bnd,
+                   df_stream_t stream);
+int df_advect_sl3d(const float* density, const float* vel, float* fwd, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt,
+                   float vel_scale, int bnd, df_stream_t stream);
+int df_advect_mc2d(const float* orig, const float* fwd, const float* vel, float* out, int64_t B, int64_t Y, int64_t X, float dt,
+                   float vel_scale, int bnd, int clamp_mode, df_stream_t stream);
+int df_advect_mc3d(const float* orig, const float* fwd, const float* vel, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt,
+                   float vel_scale, int bnd, int clamp_mode, df_stream_t stream);
+/* Source stamp before a step (Sphere.applyToGrid): out[i] = mask[i] ? value : density[i] over n cells, mask a DEVICE pointer to uint8;
+ * out == density stamps in place. */
+int df_density_source(const float* density, const uint8_t* mask, float value, float* out, int64_t n, df_stream_t stream);
+/* The d_adv frame (scene/smoke_pos_size.py:105-106): img [B,Y,X] uint8, row Y-1-y = uint8(clip(255 * density[b,y,:], 0, 255)); 3-D: of
+ * the z mean (sequential ascending fp32 sum divided by Z).  The reference casts without the clip, so values outside [0,1] wrap there
+ * and saturate here. */
+int df_density_image2d(const float* density, uint8_t* img, int64_t B, int64_t Y, int64_t X, df_stream_t stream);
+int df_density_image3d(const float* density, uint8_t* img, int64_t B, int64_t Z, int64_t Y, int64_t X, df_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
