@@ -132,6 +132,13 @@ SIGNATURES = {
     "df_density_source": (I32, [P, P, F32, P, I64, P]),
     "df_density_image2d": (I32, [P, P, I64, I64, I64, P]),
     "df_density_image3d": (I32, [P, P, I64, I64, I64, I64, P]),
+    "df_particles_advect2d": (I32, [P, P, P, I64, I64, I64, I64, F32, F32, I32, P]),
+    "df_particles_advect3d": (I32, [P, P, P, I64, I64, I64, I64, I64, F32, F32, I32, P]),
+    "df_particles_cell_keys2d": (I32, [P, P, I64, I64, I64, I64, P]),
+    "df_particles_cell_keys3d": (I32, [P, P, I64, I64, I64, I64, I64, P]),
+    "df_particles_gather": (I32, [P, P, P, I64, I32, P]),
+    "df_particle_levelset_union2d": (I32, [P, P, P, I64, I64, I64, I64, F32, P]),
+    "df_particle_levelset_union3d": (I32, [P, P, P, I64, I64, I64, I64, I64, F32, P]),
 }
 
 DF_CONV_LRELU, DF_CONV_RESIDUAL, DF_CONV_MASK, DF_CONV_BIAS, DF_CONV_ADDUP, DF_CONV_VALU_ONLY = 1, 2, 4, 8, 16, 32

@@ -30,6 +30,7 @@ __all__ = [
     "vort_np", "curl_np", "grad_np", "jacobian_np3", "l1_mean", "velocity_loss",
     "denorm_img", "plane_view", "denorm_img3", "plane_view_np", "velocity_views3", "add_channels", "remove_channels",
     "advect", "advect_sequence", "advect_workspace", "density_image", "sphere_mask",
+    "advect_particles", "particle_cells", "particle_levelset", "liquid_sequence", "seed_particles", "box_levelset", "sphere_levelset",
     "variable_scope", "get_variables", "get_variable", "reset_variables", "set_random_seed", "all_variables",
 ]
 
@@ -1808,6 +1809,171 @@ def sphere_mask(shape, center, radius, device=None):
         r2 = r2 + ((np.arange(shape[ax]) + 0.5 - float(c)) ** 2).reshape(sh)
     m = torch.from_numpy((r2 <= float(radius) * float(radius)).astype(np.uint8))
     return m if device is None else m.to(device)
+
+
+# ---- a liquid carried through a velocity field (the advect() mode of the reference's liquid scene scripts, scene/liquid3_vis.py:47-148,
+#      scene/liquid_pos_size.py:47-132): marker particles traced with RK4, a union level set rebuilt from them.  Inference only, no
+#      autograd.  The step is defined in include/deepfluids_hip.h; mantaflow, which the reference calls for it, cannot be run here, so
+#      bit parity with it is not claimed.  Left out: extrapolateMACSimple, markFluidCells, resetOutflow, adjustNumber resampling,
+#      averagedParticleLevelset / phi.setBound (the 2-D scene runs through the union form its script carries commented out), meshing ----
+def _particle_pos(pos, who):
+    p = _prep(pos.detach(), "pos")
+    if p.dim() != 3 or p.shape[-1] not in (2, 3):
+        raise ValueError("%s expects positions [B,N,2|3], got %s" % (who, tuple(p.shape)))
+    return p
+
+
+def _grid_shape(shape, nd, who):
+    shape = tuple(int(n) for n in shape)
+    if len(shape) != nd:
+        raise ValueError("%s: positions of %d coordinates need a grid shape of %d extents, got %s" % (who, nd, nd, shape))
+    return shape
+
+
+def advect_particles(pos, vel, dt, bnd=1, vel_scale=1.0, out=None):
+    """One RK4 trace of the particles ``pos`` [B,N,D] (cell units, xyz order) through ``vel`` [B,(Z,)Y,X,D] (MAC face values, times
+    ``vel_scale``), then clamped to [bnd, extent - bnd - 2^-10] per axis -- modelled on mantaflow's ``pp.advectInGrid(IntRK4,
+    deleteInObstacle=False)`` (scene/liquid3_vis.py:134), NOT bit-identical to it; include/deepfluids_hip.h holds the definition that
+    is tested.  Returns the new positions (``out`` if given; it may be ``pos`` itself)."""
+    with torch.no_grad():
+        p = _particle_pos(pos, "advect_particles")
+        v = _prep(vel.detach(), "vel")
+        B, N, nd = p.shape
+        if v.dim() != nd + 2 or v.shape[0] != B or v.shape[-1] != nd:
+            raise ValueError("advect_particles expects a velocity [%d,%s%d] for positions %s, got %s" %
+                             (B, "Z,Y,X," if nd == 3 else "Y,X,", nd, tuple(p.shape), tuple(v.shape)))
+        if int(bnd) != bnd or bnd < 0:
+            raise ValueError("advect_particles: bnd must be an integer >= 0, got %r" % (bnd,))
+        if out is None:
+            out = torch.empty_like(p)
+        elif tuple(out.shape) != tuple(p.shape) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("advect_particles: out must be a contiguous float32 GPU tensor of the positions' shape")
+        call("df_particles_advect%dd" % nd, _ptr(p), _ptr(out), _ptr(v), B, N, *(list(v.shape[1:-1]) + [float(dt), float(vel_scale), int(bnd), _stream()]))
+        return out
+
+
+def particle_cells(pos, shape):
+    """The cell index of mantaflow's ``gridParticleIndex``: ``(sorted_pos [B,N,D], cell_start [B*ncell + 1] int32, order [B*N] int64)``
+    for positions ``pos`` [B,N,D] on a grid ``shape`` [(Z,)Y,X].  Keys (batch entry, cell) come from a HIP kernel, the stable sort and
+    the ranges from torch, the permutation of the positions from a HIP kernel again: ``sorted_pos.view(-1, D) == pos.view(-1, D)[order]``
+    and the particles of key c are rows ``cell_start[c] .. cell_start[c+1] - 1``, in their original index order."""
+    with torch.no_grad():
+        p = _particle_pos(pos, "particle_cells")
+        B, N, nd = p.shape
+        shape = _grid_shape(shape, nd, "particle_cells")
+        ncell = int(np.prod(shape))
+        keys = torch.empty((B * N,), dtype=torch.int32, device=p.device)
+        call("df_particles_cell_keys%dd" % nd, _ptr(p), _ptr(keys), B, N, *(list(shape) + [_stream()]))
+        skeys, order = torch.sort(keys, stable=True)
+        spos = torch.empty_like(p)
+        call("df_particles_gather", _ptr(p), _ptr(order), _ptr(spos), B * N, nd, _stream())
+        edges = torch.arange(B * ncell + 1, dtype=torch.int32, device=p.device)
+        cell_start = torch.searchsorted(skeys, edges, out_int32=True)
+        return spos, cell_start, order
+
+
+def particle_levelset(pos, shape, radius_factor=1.0, out=None):
+    """The surface level set of the particles ``pos`` [B,N,D] on a grid ``shape``: phi [B,(Z,)Y,X] = min(radius, min over the particles
+    within +-((int)radius_factor + 1) cells of |cell centre - p| - radius), radius = 0.5*sqrt(D)*(radius_factor + 0.01) -- modelled on
+    mantaflow's ``gridParticleIndex`` + ``unionParticleLevelset`` (scene/liquid3_vis.py:112-113), NOT bit-identical to it.  Negative
+    inside the liquid.  No particles: phi = radius everywhere."""
+    with torch.no_grad():
+        p = _particle_pos(pos, "particle_levelset")
+        B, N, nd = p.shape
+        shape = _grid_shape(shape, nd, "particle_levelset")
+        if out is None:
+            out = _empty((B,) + shape, p)
+        elif tuple(out.shape) != (B,) + shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("particle_levelset: out must be a contiguous float32 GPU tensor %s" % ((B,) + shape,))
+        spos, cell_start, _ = particle_cells(p, shape)
+        call("df_particle_levelset_union%dd" % nd, _ptr(spos), _ptr(cell_start), _ptr(out), B, N, *(list(shape) + [float(radius_factor), _stream()]))
+        return out
+
+
+def liquid_sequence(pos0, vels, dt, bnd=1, vel_scale=1.0, radius_factor=1.0, images=False):
+    """The frame loop of the liquid scenes' ``advect()`` (scene/liquid3_vis.py:100-148) over ``vels`` [T,B,(Z,)Y,X,D] (a tensor or a
+    sequence of T tensors): per frame build the level set of the current particles, optionally render it with ``density_image`` (the
+    ``l_adv`` frame: clipped where the reference's cast wraps), then trace the particles through the frame's velocity.  ``pos0`` is left
+    untouched.  Returns ``(final positions [B,N,D], last phi [B,(Z,)Y,X])`` -- the last phi is the level set of the positions BEFORE the
+    last trace, as in the reference's loop -- and with ``images`` also the uint8 frames [T,B,Y,X], copied to the host once."""
+    with torch.no_grad():
+        T = len(vels)
+        if T < 1:
+            raise ValueError("liquid_sequence: no velocity frames")
+        cur = _particle_pos(pos0, "liquid_sequence").clone()
+        shape = tuple(vels[0].shape[1:-1])
+        phi = _empty((cur.shape[0],) + shape, cur)
+        imgs = _u8((T, cur.shape[0], shape[-2], shape[-1]), cur) if images else None
+        for t in range(T):
+            particle_levelset(cur, shape, radius_factor, out=phi)
+            if images:
+                density_image(phi, out=imgs[t])
+            advect_particles(cur, vels[t], dt, bnd=bnd, vel_scale=vel_scale, out=cur)
+        if images:
+            return cur, phi, imgs.cpu().numpy()
+        return cur, phi
+
+
+def _centres(shape, a):
+    """centre coordinate along axis a (0 = x) of every cell, broadcastable against [(Z,)Y,X]"""
+    ax = len(shape) - 1 - a
+    sh = [1] * len(shape)
+    sh[ax] = shape[ax]
+    return (np.arange(shape[ax]) + 0.5).reshape(sh)
+
+
+def box_levelset(shape, p0, p1):
+    """Signed distance of the cell centres of a grid ``shape`` [(Z,)Y,X] to the box p0 .. p1 (cell units, xyz order), negative inside
+    (mantaflow's ``Box.computeLevelset``); float32, host.  Join two level sets with ``np.minimum``."""
+    shape = tuple(int(n) for n in shape)
+    if len(shape) not in (2, 3) or len(p0) != len(shape) or len(p1) != len(shape):
+        raise ValueError("box_levelset expects a 2-D or 3-D shape and corners of as many coordinates, got %s, %s, %s" % (shape, tuple(p0), tuple(p1)))
+    q = []
+    for a in range(len(shape)):
+        mid, half = 0.5 * (float(p0[a]) + float(p1[a])), 0.5 * (float(p1[a]) - float(p0[a]))
+        q.append(np.broadcast_to(np.abs(_centres(shape, a) - mid) - half, shape))
+    q = np.stack(q)
+    outside = np.sqrt((np.maximum(q, 0.0) ** 2).sum(axis=0))
+    return (outside + np.minimum(q.max(axis=0), 0.0)).astype(np.float32)
+
+
+def sphere_levelset(shape, center, radius):
+    """Signed distance of the cell centres of a grid ``shape`` [(Z,)Y,X] to the sphere (cell units, xyz order), negative inside;
+    float32, host."""
+    shape = tuple(int(n) for n in shape)
+    if len(shape) not in (2, 3) or len(center) != len(shape):
+        raise ValueError("sphere_levelset expects a 2-D or 3-D shape and a centre of as many coordinates, got %s, %s" % (shape, tuple(center)))
+    r2 = np.zeros(shape, np.float64)
+    for a, c in enumerate(center):
+        r2 = r2 + (_centres(shape, a) - float(c)) ** 2
+    return (np.sqrt(r2) - float(radius)).astype(np.float32)
+
+
+def seed_particles(phi0, discretization=2, randomness=0.05, seed=123, bnd=1):
+    """Marker particles of the liquid body ``phi0`` [(Z,)Y,X] (negative inside), after mantaflow's ``sampleLevelsetWithParticles``
+    (scene/liquid3_vis.py:89): every cell with phi0 < 0 that is not on the ``bnd`` band gets discretization^D particles at its sub-cell
+    centres (i + (s + 0.5)/discretization, ...), each moved by a uniform jitter of +-randomness/discretization per axis drawn from
+    ``np.random.RandomState(seed)``.  Cells in [(Z,)Y,X] order, sub-cells likewise with x innermost.  Host NumPy; returns [N,D] float32
+    in xyz order."""
+    phi0 = np.asarray(phi0)
+    nd = phi0.ndim
+    if nd not in (2, 3):
+        raise ValueError("seed_particles expects a level set [(Z,)Y,X], got %s" % (phi0.shape,))
+    disc = int(discretization)
+    if disc < 1 or not 0 <= randomness < 0.5:
+        raise ValueError("seed_particles: discretization must be >= 1 and randomness in [0, 0.5)")
+    inside = phi0 < 0
+    for ax, n in enumerate(phi0.shape):
+        idx = np.arange(n)
+        sh = [1] * nd
+        sh[ax] = n
+        inside = inside & ((idx >= bnd) & (idx < n - bnd)).reshape(sh)
+    cells = np.argwhere(inside)[:, ::-1].astype(np.float64)                                   # [M, D] in xyz order
+    sub = np.argwhere(np.ones((disc,) * nd, bool))[:, ::-1].astype(np.float64)                # [disc^D, D], x innermost
+    pos = (cells[:, None, :] + (sub[None, :, :] + 0.5) / disc).reshape(-1, nd)
+    rng = np.random.RandomState(seed)
+    pos = pos + rng.uniform(-1.0, 1.0, size=pos.shape) * (float(randomness) / disc)
+    return pos.astype(np.float32)
 
 
 def plane_view_np(x, xy_plane=True, project=True):

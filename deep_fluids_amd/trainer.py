@@ -650,6 +650,47 @@ class Trainer(object):
             Image.fromarray(imgs[t, 0]).save(os.path.join(out_dir, "%04d.png" % t))
         return out_dir, final
 
+    # ---- `advect()` of the liquid scene scripts (scene/liquid3_vis.py:47-148, scene/liquid_pos_size.py:47-132) ------------------
+    def advect_liquid_(self, batch_manager, model_dir=None, p1=10, p2=2, test_b_num=None, *, body, dt=None, bnd=1, radius_factor=1.0,
+                       discretization=2, randomness=0.05, seed=123):
+        """The sweep of ``test_`` looked at as a liquid, the way the reference's liquid scene scripts do (their ``advect()`` mode):
+        seed marker particles in ``body`` (``ops.seed_particles``), generate every frame of the parameter pair (p1, p2), keep the frames
+        on the device -- the kernels scale them by ``batch_manager.x_range`` -- and, per frame, rebuild the surface level set from the
+        particles, write it as the grey frame ``<model_dir>/<p1>_<p2>/l_adv/%04d.png`` (3-D: of the z mean; clipped to [0,255] where
+        the reference's cast wraps), then trace the particles through the frame's velocity with RK4 (``ops.liquid_sequence``).
+        mantaflow's advectInGrid / gridParticleIndex / unionParticleLevelset are restated, not bit-identical; extrapolateMACSimple,
+        markFluidCells, resetOutflow, adjustNumber resampling, averagedParticleLevelset (the 2-D scene runs through the union form)
+        and meshing are left out.  ``body``: a level set [(Z,)Y,X], negative inside, or ``{"boxes": [(p0, p1), ...], "spheres":
+        [(center, radius), ...]}`` in fractions of the grid (xyz order; a radius in fractions of X), joined by a minimum
+        (``liquid3_vis_body`` builds the one of scene/liquid3_vis.py).  ``dt``: 1.0 by default, as scene/liquid3_vis.py sets
+        ``s.timestep = 1``; ``"dataset"`` takes args.txt's ``time_step``, as scene/liquid_pos_size.py does.
+        Returns ``(out_dir, final positions [1,N,D], last phi [1,(Z,)Y,X])``, both on the device; the last phi is the level set of the
+        positions before the last trace."""
+        from PIL import Image
+        model_dir = model_dir or self.effective_model_dir()
+        z_c, niter, test_b_num = self._sweep_codes(batch_manager, p1, p2, test_b_num, "advect_liquid_")
+        if dt is None:
+            dt = 1.0
+        elif isinstance(dt, str):
+            if dt != "dataset":
+                raise ValueError("advect_liquid_: dt must be a number, None or 'dataset', got %r" % (dt,))
+            dt = float(batch_manager.args["time_step"])
+        frames = [self.generate(torch.from_numpy(z_c[test_b_num * b:test_b_num * (b + 1)]).to(self.device)) for b in range(niter)]
+        frames = torch.cat(frames, dim=0)                                   # [y3,(Z,)Y,X,C]
+        spatial = tuple(frames.shape[1:-1])
+        phi0 = body_levelset(spatial, body)
+        pos0 = ops.seed_particles(phi0, discretization=discretization, randomness=randomness, seed=seed, bnd=bnd)
+        if pos0.shape[0] == 0:
+            raise ValueError("advect_liquid_: the body holds no cell inside the boundary band: nothing to trace")
+        pos0 = torch.from_numpy(pos0).to(frames.device).unsqueeze(0)
+        pos, phi, imgs = ops.liquid_sequence(pos0, frames.unsqueeze(1), dt, bnd=bnd, vel_scale=float(batch_manager.x_range),
+                                             radius_factor=radius_factor, images=True)
+        out_dir = os.path.join(model_dir, "%d_%d" % (p1, p2), "l_adv")
+        os.makedirs(out_dir, exist_ok=True)
+        for t in range(imgs.shape[0]):
+            Image.fromarray(imgs[t, 0]).save(os.path.join(out_dir, "%04d.png" % t))
+        return out_dir, pos, phi
+
     def _optimizer_scalars(self, grad_scale):
         """The optimizer's per-step host scalars ``[lr_t | lr, grad_scale]``; advances Adam's step count (beta powers)."""
         if self.config.optimizer == "gd":                       # trainer.py:163-165
@@ -695,6 +736,35 @@ def smoke_pos_size_source(batch_manager, p1, p2):
     rad = p2 / float(int(a["num_src_radius"]) - 1) * (float(a["max_src_radius"]) - float(a["min_src_radius"])) + float(a["min_src_radius"])
     rx, ry = int(batch_manager.res_x), int(batch_manager.res_y)
     return {"center": (rx * x_pos, ry * float(a["src_y_pos"])), "radius": rx * rad}
+
+
+def body_levelset(spatial, body):
+    """The initial liquid body of ``Trainer.advect_liquid_`` on a grid ``spatial`` [(Z,)Y,X] as a host level set, negative inside: a
+    level set is passed through; ``{"boxes": [(p0, p1), ...], "spheres": [(center, radius), ...]}`` is given in fractions of the grid
+    (xyz order; a radius in fractions of X, as the scenes' ``gs.x*dropRadius``) and joined by a minimum."""
+    spatial = tuple(int(n) for n in spatial)
+    if not isinstance(body, dict):
+        phi = np.asarray(body.detach().cpu().numpy() if isinstance(body, torch.Tensor) else body, np.float32)
+        if phi.shape != spatial:
+            raise ValueError("body: a level set %s does not match the generated frames %s" % (phi.shape, spatial))
+        return phi
+    unknown = sorted(set(body) - {"boxes", "spheres"})
+    if unknown or not (body.get("boxes") or body.get("spheres")):
+        raise ValueError("body: expected {'boxes': [(p0, p1), ...], 'spheres': [(center, radius), ...]}, got %r" % (body,))
+    gs = spatial[::-1]                                                       # (X, Y[, Z])
+    parts = [ops.box_levelset(spatial, [g * c for g, c in zip(gs, p0)], [g * c for g, c in zip(gs, p1)]) for p0, p1 in body.get("boxes", ())]
+    parts += [ops.sphere_levelset(spatial, [g * c for g, c in zip(gs, center)], gs[0] * radius) for center, radius in body.get("spheres", ())]
+    phi = parts[0]
+    for q in parts[1:]:
+        phi = np.minimum(phi, q)
+    return phi
+
+
+def liquid3_vis_body(batch_manager):
+    """The liquid body of scene/liquid3_vis.py:84-85: the box 0.3..0.7 x 0..0.8 x 0.3..0.7 of the grid."""
+    if not batch_manager.is_3d:
+        raise ValueError("liquid3_vis_body: the liquid3_vis scene is 3-D")
+    return {"boxes": [((0.3, 0.0, 0.3), (0.7, 0.8, 0.7))]}
 
 
 class Trainer3(Trainer):

@@ -503,6 +503,51 @@ int df_density_source(const float* density, const uint8_t* mask, float value, fl
 int df_density_image2d(const float* density, uint8_t* img, int64_t B, int64_t Y, int64_t X, df_stream_t stream);
 int df_density_image3d(const float* density, uint8_t* img, int64_t B, int64_t Z, int64_t Y, int64_t X, df_stream_t stream);
 
+/* ---- a liquid carried through a velocity field: the advect() mode of the reference's liquid scene scripts (scene/liquid3_vis.py:47-148,
+ * scene/liquid_pos_size.py:47-132), which seed marker particles in the liquid body and, per frame, trace them with mantaflow's
+ * pp.advectInGrid(IntRK4, deleteInObstacle=False) and rebuild a surface level set with gridParticleIndex + unionParticleLevelset.
+ * mantaflow cannot be run beside this library, so bit parity with it is NOT claimed: the definition below is the contract
+ * (tests/particles_ref.py restates it).  Left out: extrapolateMACSimple (a generator emits velocities everywhere), markFluidCells,
+ * resetOutflow, adjustNumber resampling (N is constant over a sequence), averagedParticleLevelset, phi.setBound and meshing.
+ *
+ * pos [B,N,D] fp32 positions in cell units (x, y[, z]), D = 2 | 3; cell (i,j,k) spans [i,i+1) x [j,j+1) x [k,k+1) and is [..,k,j,i] in
+ * the grids.  vel [B,(Z,)Y,X,D] fp32 MAC face values (component a of cell i sits on the cell's low-a face: the layout of df_advect_*),
+ * multiplied by vel_scale.  phi [B,(Z,)Y,X] fp32.  All arithmetic fp32, no fused multiply-add, in the order written.
+ *   u(p)     MAC sample.  Component a is interpolated multilinearly in the frame q_a = p_a, q_b = p_b - 0.5 (b != a).  Per axis:
+ *            q < 0 or NaN -> n = 0, s0 = 1, s1 = 0;  trunc(q) >= extent - 1 -> n = extent - 2, s0 = 0, s1 = 1;  else n = (int)q,
+ *            s1 = q - n, s0 = 1 - s1.  Sum over the 2^D corners n, n+1 as s0*a + s1*b per axis, x innermost; then * vel_scale.
+ *   trace    k1 = u(p), k2 = u(p + (0.5*dt)*k1), k3 = u(p + (0.5*dt)*k2), k4 = u(p + dt*k3),
+ *            p' = p + (dt * (((k1 + 2*k2) + 2*k3) + k4)) / 6, then per axis p' = min(max(p', bnd), (extent - bnd) - 2^-10) (a NaN
+ *            becomes bnd): particles are pushed back into the domain, none is deleted.  bnd >= 0, 2*bnd + 2 <= every extent.
+ *   keys     key = b*ncell + ((k*Y + j)*X + i), int32, i = min((int)p_x, X - 1) (p_x < 0 or NaN -> 0), likewise j, k.
+ *   ranges   the caller sorts the B*N keys STABLY (particles of one cell keep their index order), permutes the positions with
+ *            df_particles_gather and builds cell_start [B*ncell + 1] int32: cell_start[c] = the number of keys < c, so that the
+ *            particles of cell c are rows cell_start[c] .. cell_start[c+1] - 1 of pos_sorted [B*N,D].
+ *   levelset radius = (0.5 * sqrt(D)) * (radius_factor + 0.01), w = (int)radius_factor + 1;  phi(c) = min(radius, min over the particles
+ *            p of the cells within +-w of c on every axis that lie inside the grid of |centre(c) - p| - radius), centre = (i+.5, j+.5
+ *            [, k+.5]), |v| = sqrt((vx*vx + vy*vy) + vz*vz).  A particle outside the window is farther than w + 0.5 from the centre,
+ *            so whenever 2*radius <= w + 0.5 -- which holds for radius_factor 0.5, 1 and 2 in 2-D and 3-D, NOT for every value --
+ *            this equals the minimum over ALL particles of the batch entry.  No atomics: results are deterministic.
+ * df_particles_advect*: pos_out may be pos_in.  N = 0: nothing is launched (positions may then be null), phi = radius everywhere.
+ * Non-finite positions or velocities and out-of-range entries of order / cell_start select edge cells or edge particles, never
+ * memory outside the arrays.
+ * Errors: DF_EINVAL null pointer / non-positive extent / N < 0 / bnd < 0 / radius_factor outside [0, 1024] / gather in place,
+ * DF_ESHAPE an extent < 2 or < 2*bnd + 2 or too large, B*N or (keys, level set) B*ncell beyond int32, DF_EALIGN a pointer not 4-byte
+ * (order: 8-byte) aligned. */
+int df_particles_advect2d(const float* pos_in, float* pos_out, const float* vel, int64_t B, int64_t N, int64_t Y, int64_t X, float dt,
+                          float vel_scale, int bnd, df_stream_t stream);
+int df_particles_advect3d(const float* pos_in, float* pos_out, const float* vel, int64_t B, int64_t N, int64_t Z, int64_t Y, int64_t X,
+                          float dt, float vel_scale, int bnd, df_stream_t stream);
+int df_particles_cell_keys2d(const float* pos, int32_t* keys, int64_t B, int64_t N, int64_t Y, int64_t X, df_stream_t stream);
+int df_particles_cell_keys3d(const float* pos, int32_t* keys, int64_t B, int64_t N, int64_t Z, int64_t Y, int64_t X, df_stream_t stream);
+/* pos_sorted[r] = pos[order[r]] over n = B*N records of dim = 2 | 3 floats; order is a DEVICE pointer to int64 (the indices a sort
+ * returns). */
+int df_particles_gather(const float* pos, const int64_t* order, float* pos_sorted, int64_t n, int dim, df_stream_t stream);
+int df_particle_levelset_union2d(const float* pos_sorted, const int32_t* cell_start, float* phi, int64_t B, int64_t N, int64_t Y, int64_t X,
+                                 float radius_factor, df_stream_t stream);
+int df_particle_levelset_union3d(const float* pos_sorted, const int32_t* cell_start, float* phi, int64_t B, int64_t N, int64_t Z, int64_t Y,
+                                 int64_t X, float radius_factor, df_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
