@@ -573,18 +573,25 @@ __global__ __launch_bounds__(kThreads) void curl2d_bwd_kernel(const float* __res
   gpsi[v] = a - b;
 }
 
-template <bool WJ, bool WW>
-__global__ __launch_bounds__(kThreads) void jacobian2d_fwd_kernel(const float2* __restrict__ x, float4* __restrict__ j,
+// one (u, v) record of x: an 8-byte load where the caller's pointer allows it (A8), two 4-byte loads otherwise
+template <bool A8>
+__device__ __forceinline__ float2 ld_uv(const float* __restrict__ x, int64_t v) {
+  if (A8) return reinterpret_cast<const float2*>(x)[v];
+  return make_float2(x[v * 2], x[v * 2 + 1]);
+}
+
+template <bool WJ, bool WW, bool A8>
+__global__ __launch_bounds__(kThreads) void jacobian2d_fwd_kernel(const float* __restrict__ x, float4* __restrict__ j,
                                                                   float* __restrict__ w, Dims2 dm) {
   const int64_t v = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
   if (v >= dm.npix) return;
   const int64_t row = v / dm.X;
   const int xx = static_cast<int>(v - row * dm.X);
   const int yy = static_cast<int>(row % dm.Y);
-  const float2 own = x[v];
+  const float2 own = ld_uv<A8>(x, v);
   const bool ly = yy == dm.Y - 1, lx = xx == dm.X - 1;
-  const float2 ny = x[ly ? v - dm.X : v + dm.X];
-  const float2 nx = x[lx ? v - 1 : v + 1];
+  const float2 ny = ld_uv<A8>(x, ly ? v - dm.X : v + dm.X);
+  const float2 nx = ld_uv<A8>(x, lx ? v - 1 : v + 1);
   float4 r;
   r.x = lx ? own.x - nx.x : nx.x - own.x;   // dudx
   r.y = ly ? own.x - ny.x : ny.x - own.x;   // dudy
@@ -644,6 +651,8 @@ constexpr int g_stencil_group = dfst::kXcdGroup;
 constexpr int g_stencil_nt = 1;      // non-temporal output stores
 constexpr int g_stencil_lds = 1;     // LDS-staged adjoints where they apply
 #endif
+
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 int check3(const void* in, int64_t B, int64_t Z, int64_t Y, int64_t X, const char* fn) {
   DF_REQUIRE(in != nullptr, DF_EINVAL, "%s: null input", fn);
@@ -732,6 +741,7 @@ int df_divergence3d(const float* x, float* d, int64_t B, int64_t Z, int64_t Y, i
 int df_curl2d_fwd(const float* psi, float* u, int64_t B, int64_t Y, int64_t X, df_stream_t stream) {
   if (int e = check2(psi, B, Y, X, "df_curl2d_fwd")) return e;
   DF_REQUIRE(u != nullptr, DF_EINVAL, "df_curl2d_fwd: null output");
+  DF_REQUIRE(aligned8(u), DF_EALIGN, "df_curl2d_fwd: u must be 8-byte aligned");      // written as float2 records
   Dims2 dm{B * Y * X, (int)Y, (int)X};
   hipLaunchKernelGGL(curl2d_fwd_kernel, dim3((unsigned)ceil_div(dm.npix, kThreads)), dim3(kThreads), 0,
                      df::as_stream(stream), psi, reinterpret_cast<float2*>(u), dm);
@@ -754,11 +764,13 @@ int df_jacobian2d_fwd(const float* x, float* j, float* w, int64_t B, int64_t Y, 
   Dims2 dm{B * Y * X, (int)Y, (int)X};
   dim3 grid((unsigned)ceil_div(dm.npix, kThreads)), block(kThreads);
   hipStream_t s = df::as_stream(stream);
-  const float2* x2 = reinterpret_cast<const float2*>(x);
   float4* j4 = reinterpret_cast<float4*>(j);
-  if (j && w) hipLaunchKernelGGL((jacobian2d_fwd_kernel<true, true>), grid, block, 0, s, x2, j4, w, dm);
-  else if (j) hipLaunchKernelGGL((jacobian2d_fwd_kernel<true, false>), grid, block, 0, s, x2, j4, w, dm);
-  else hipLaunchKernelGGL((jacobian2d_fwd_kernel<false, true>), grid, block, 0, s, x2, j4, w, dm);
+  // x is read as 8-byte (u, v) records where it is 8-byte aligned, by 4-byte loads otherwise
+#define DF_J2(WJ, WW)                                                                                       \
+  if (aligned8(x)) hipLaunchKernelGGL((jacobian2d_fwd_kernel<WJ, WW, true>), grid, block, 0, s, x, j4, w, dm); \
+  else hipLaunchKernelGGL((jacobian2d_fwd_kernel<WJ, WW, false>), grid, block, 0, s, x, j4, w, dm)
+  if (j && w) { DF_J2(true, true); } else if (j) { DF_J2(true, false); } else { DF_J2(false, true); }
+#undef DF_J2
   return df::launched("df_jacobian2d_fwd");
 }
 
@@ -766,6 +778,7 @@ int df_jacobian2d_bwd(const float* gj, const float* gw, float* gx, int64_t B, in
                       df_stream_t stream) {
   if (int e = check2(gx, B, Y, X, "df_jacobian2d_bwd")) return e;
   DF_REQUIRE(gj || gw, DF_EINVAL, "df_jacobian2d_bwd: both incoming gradients null");
+  DF_REQUIRE(aligned8(gx), DF_EALIGN, "df_jacobian2d_bwd: gx must be 8-byte aligned");      // written as float2 records
   Dims2 dm{B * Y * X, (int)Y, (int)X};
   dim3 grid((unsigned)ceil_div(dm.npix, kThreads)), block(kThreads);
   hipStream_t s = df::as_stream(stream);

@@ -991,6 +991,7 @@ int df_velocity_loss2d_bwd(const float* u, const float* x, const float* g_l1, co
   DF_REQUIRE(gpsi && workspace, DF_EINVAL, "df_velocity_loss2d_bwd: null output / workspace");
   const Geo2 g{B * Y * X, (int)Y, (int)X};
   DF_REQUIRE(workspace_bytes >= g.npix * 2 * static_cast<int64_t>(sizeof(float)), DF_EWORKSPACE, "df_velocity_loss2d_bwd: workspace too small");
+  DF_REQUIRE(df::aligned16(workspace), DF_EALIGN, "df_velocity_loss2d_bwd: workspace must be 16-byte aligned");
   float* du = static_cast<float*>(workspace);
   hipLaunchKernelGGL(velocity_loss2d_bwd_kernel, dim3((unsigned)ceil_div(g.npix, kThreads)), dim3(kThreads), 0, df::as_stream(stream), u, x,
                      g_l1, g_jl1, 1.f / static_cast<float>(2 * g.npix), 1.f / static_cast<float>(4 * g.npix), du, g);

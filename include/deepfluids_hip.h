@@ -36,7 +36,7 @@ enum {
   DF_OK = 0,
   DF_EINVAL = -1,    /* null pointer / non-positive extent */
   DF_ESHAPE = -2,    /* extent unsupported by this kernel (e.g. forward difference needs n >= 2) */
-  DF_EALIGN = -3,    /* pointer not 16-byte aligned */
+  DF_EALIGN = -3,    /* pointer not aligned as the function's comment requires (16 bytes where it names no figure) */
   DF_EWORKSPACE = -4 /* workspace too small */
 };
 
@@ -56,30 +56,44 @@ typedef void* df_stream_t; /* hipStream_t */
 int df_version(void);
 const char* df_last_error(void);
 
-/* ---- forward-difference stencils (HBM-bound) ---------------------------------------------- */
+/* ---- forward-difference stencils (HBM-bound) ----------------------------------------------
+ * Alignment.  Every pointer is a float pointer and must be 4-byte aligned.  Where a function needs more, its comment names the
+ * pointer and the alignment, and the function returns DF_EALIGN when the pointer has less (NULL counts as aligned).  The rule: an
+ * OUTPUT that a kernel writes through a vector type must be aligned to that type; an INPUT that a fast kernel reads through a vector
+ * type may have any 4-byte alignment -- the function then takes a kernel that reads it by 4-byte loads, with the same results bit
+ * for bit.  Buffers are dense (no strides) and exactly as long as their shape says; nothing outside them is read or written. */
 
-/* curl(x) ops.py:264-274.  psi [B,Y,X,1] -> u [B,Y,X,2] = (D_y psi, -D_x psi). */
+/* curl(x) ops.py:264-274.  psi [B,Y,X,1] -> u [B,Y,X,2] = (D_y psi, -D_x psi).
+ * Alignment: psi 4 bytes; u 8 bytes (DF_EALIGN). */
 int df_curl2d_fwd(const float* psi, float* u, int64_t B, int64_t Y, int64_t X, df_stream_t stream);
-/* adjoint of df_curl2d_fwd: gu [B,Y,X,2] -> gpsi [B,Y,X,1]. */
+/* adjoint of df_curl2d_fwd: gu [B,Y,X,2] -> gpsi [B,Y,X,1].
+ * Alignment: gu 4 bytes; gpsi 4 bytes. */
 int df_curl2d_bwd(const float* gu, float* gpsi, int64_t B, int64_t Y, int64_t X, df_stream_t stream);
 
 /* jacobian(x) ops.py:205-225.  x [B,Y,X,2] -> j [B,Y,X,4] = (dudx,dudy,dvdx,dvdy), w [B,Y,X,1] = dvdx-dudy.
- * j or w may be NULL (that output is not produced). */
+ * j or w may be NULL (that output is not produced).
+ * Alignment: x 4 bytes (8-byte loads where it is 8-byte aligned, 4-byte loads otherwise); j 16 bytes (DF_EALIGN); w 4 bytes. */
 int df_jacobian2d_fwd(const float* x, float* j, float* w, int64_t B, int64_t Y, int64_t X, df_stream_t stream);
-/* adjoint: gj [..,4] and/or gw [..,1] (either may be NULL, not both) -> gx [..,2]. */
+/* adjoint: gj [..,4] and/or gw [..,1] (either may be NULL, not both) -> gx [..,2].
+ * Alignment: gj 4 bytes; gw 4 bytes; gx 8 bytes (DF_EALIGN). */
 int df_jacobian2d_bwd(const float* gj, const float* gw, float* gx, int64_t B, int64_t Y, int64_t X,
                       df_stream_t stream);
 
 /* jacobian3(x) ops.py:227-262.  x [B,Z,Y,X,3] -> j [..,9] = (dudx,dudy,dudz,dvdx,dvdy,dvdz,dwdx,dwdy,dwdz),
  * c [..,3] = (dwdy-dvdz, dudz-dwdx, dvdx-dudy).  j or c may be NULL.
- * `curl3(x)` of the north star == df_jacobian3d_fwd(x, NULL, c, ...)  (trainer3.py:18). */
+ * `curl3(x)` of the north star == df_jacobian3d_fwd(x, NULL, c, ...)  (trainer3.py:18).
+ * Alignment: x 4 bytes (the 16-byte-load kernel needs X % 4 == 0 and x 16-byte aligned; otherwise the one-voxel-per-lane kernel
+ * runs); j 16 bytes, c 16 bytes (DF_EALIGN). */
 int df_jacobian3d_fwd(const float* x, float* j, float* c, int64_t B, int64_t Z, int64_t Y, int64_t X,
                       df_stream_t stream);
-/* adjoint: gj [..,9] and/or gc [..,3] (either may be NULL, not both) -> gx [..,3]. */
+/* adjoint: gj [..,9] and/or gc [..,3] (either may be NULL, not both) -> gx [..,3].
+ * Alignment: gj, gc, gx 4 bytes (the 16-byte kernels need X % 4 == 0 and all three 16-byte aligned; otherwise the one-voxel-per-lane
+ * kernel runs, which reads and writes single floats). */
 int df_jacobian3d_bwd(const float* gj, const float* gc, float* gx, int64_t B, int64_t Z, int64_t Y, int64_t X,
                       df_stream_t stream);
 
-/* divergence ops.py:276-284: x [B,Y,X,2] -> [B,Y-1,X-1,1];  divergence3 ops.py:286-290: x [B,Z,Y,X,3] -> [B,Z-1,Y-1,X-1,1]. */
+/* divergence ops.py:276-284: x [B,Y,X,2] -> [B,Y-1,X-1,1];  divergence3 ops.py:286-290: x [B,Z,Y,X,3] -> [B,Z-1,Y-1,X-1,1].
+ * Alignment: x 4 bytes; d 4 bytes. */
 int df_divergence2d(const float* x, float* d, int64_t B, int64_t Y, int64_t X, df_stream_t stream);
 int df_divergence3d(const float* x, float* d, int64_t B, int64_t Z, int64_t Y, int64_t X, df_stream_t stream);
 
@@ -90,7 +104,12 @@ int df_divergence3d(const float* x, float* d, int64_t B, int64_t Z, int64_t Y, i
  *   psi [B,Z,Y,X,3] | [B,Y,X,1], x [B,Z,Y,X,3] | [B,Y,X,2];  u (nullable) receives the velocity field, bit-identical to
  *   df_jacobian3d_fwd(psi, NULL, u) | df_curl2d_fwd;  l1 / jl1: device scalars.
  * Backward: gpsi = curl^T( g_l1/N1 sign(u - x) + J^T( g_jl1/NJ sign(J(u) - J(x)) ) ) from the saved u and x;  g_l1 / g_jl1 are
- * device scalars (NULL = 1).  One workspace serves both directions (df_velocity_loss*_workspace_bytes, 16-byte aligned). */
+ * device scalars (NULL = 1).  One workspace serves both directions (df_velocity_loss*_workspace_bytes = the larger of the two needs;
+ * a workspace of exactly that size is enough, no byte outside it is touched, and neither direction reads what an earlier call left).
+ * Alignment: psi, x, u, gpsi, l1, jl1, g_l1, g_jl1 4 bytes -- in 3-D the tiled and the 16-byte kernels need psi, x and u (backward:
+ * u and x) 16-byte aligned and X % 4 == 0, and any other input, u == NULL included, takes the one-voxel-per-lane kernels; gpsi as gx
+ * of df_jacobian3d_bwd.  workspace: 8 bytes for *_fwd (fp64 partial sums), 16 bytes for *_bwd (DF_EALIGN); one shared workspace is
+ * therefore 16-byte aligned.  workspace_bytes below the direction's own need: DF_EWORKSPACE. */
 int64_t df_velocity_loss3d_workspace_bytes(int64_t B, int64_t Z, int64_t Y, int64_t X);
 int df_velocity_loss3d_fwd(const float* psi, const float* x, float* u, float* l1, float* jl1, int64_t B, int64_t Z, int64_t Y,
                            int64_t X, void* workspace, int64_t workspace_bytes, df_stream_t stream);

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 import elementwise_ref as ref
-from gpu_util import host
+from gpu_util import Out, assert_bits, host      # (the guarded output buffer and the bit comparison are shared with the stencil tests)
 
 pytestmark = pytest.mark.gpu
 F32, F64 = np.float32, np.float64
@@ -29,32 +29,6 @@ def k():
     from deep_fluids_amd._lib import call, query
     from deep_fluids_amd.ops import _ptr, _stream
     return call, query, _ptr, _stream()
-
-
-class Out(object):
-    """An output buffer: NaN everywhere, the tensor in front, a guard of one row (last extent) or one element behind it."""
-
-    def __init__(self, shape, data=None):
-        self.shape = tuple(shape)
-        self.n = int(np.prod(self.shape)) if self.shape else 1
-        self.buf = torch.full((self.n + (self.shape[-1] if self.shape else 1),), NAN, dtype=torch.float32, device="cuda")
-        if data is not None:
-            self.buf[:self.n] = dev(data).reshape(-1)
-        self.ptr = self.buf.data_ptr()
-
-    def get(self):
-        assert bool(torch.isnan(self.buf[self.n:]).all()), "the guard behind the output was written"
-        return host(self.buf[:self.n]).reshape(self.shape)
-
-
-def assert_bits(got, want, what=""):
-    """equal bit for bit: distinguishes -0.0 from +0.0, and a NaN left from the pre-fill never matches"""
-    got = np.ascontiguousarray(got, F32); want = np.ascontiguousarray(want, F32)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = got.view(np.int32) != want.view(np.int32)
-    if bad.any():
-        i = np.unravel_index(int(np.argmax(bad)), bad.shape)
-        raise AssertionError("%s: %d of %d elements differ, first at %s: got %r, want %r" % (what, int(bad.sum()), bad.size, i, got[i], want[i]))
 
 
 def rule(name, got, r64, twin):
