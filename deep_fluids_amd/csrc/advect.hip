@@ -22,45 +22,22 @@
 // cell, never an address outside the arrays.
 #include <cmath>
 
+#include "advect_common.hpp"
 #include "df_common.hpp"
 #include "stencil_common.hpp"
 
 namespace {
 
 using df::ceil_div;
+using dfadv::AdvDims;
+using dfadv::axis_weights;
+using dfadv::Cell;
+using dfadv::corner_range;
+using dfadv::decode;
+using dfadv::interp;
 using dfst::f32x4;
 using dfst::kThreads;
 using dfst::xcd_block;
-
-struct AdvDims {
-  int64_t ncell;   // B*Z*Y*X
-  int Z, Y, X;     // Z = 1 in 2-D
-  int bnd;
-  float dt, vs;
-};
-
-template <int D>
-struct Cell {
-  int64_t idx;     // flat cell index
-  int64_t base;    // flat index of cell (0,0,0) of this batch entry
-  int p[3];        // i, j, k
-  bool interior;
-};
-
-template <int D>
-__device__ __forceinline__ Cell<D> decode(int64_t idx, const AdvDims& d) {
-  Cell<D> c;
-  c.idx = idx;
-  const int64_t row = idx / d.X;
-  c.p[0] = static_cast<int>(idx - row * d.X);
-  const int64_t slab = row / d.Y;
-  c.p[1] = static_cast<int>(row - slab * d.Y);
-  c.p[2] = D == 3 ? static_cast<int>(slab % d.Z) : 0;
-  c.base = idx - ((static_cast<int64_t>(c.p[2]) * d.Y + c.p[1]) * d.X + c.p[0]);
-  c.interior = c.p[0] >= d.bnd && c.p[0] < d.X - d.bnd && c.p[1] >= d.bnd && c.p[1] < d.Y - d.bnd &&
-               (D == 2 || (c.p[2] >= d.bnd && c.p[2] < d.Z - d.bnd));
-  return c;
-}
 
 template <int D>
 struct VelRec { float v[D]; };
@@ -77,65 +54,6 @@ __device__ __forceinline__ void displacement(const float* __restrict__ vel, cons
   if (D == 3) nb[2] = v[sy * d.Y + 2];
 #pragma unroll
   for (int a = 0; a < D; ++a) du[a] = d.dt * ((0.5f * (own.v[a] + nb[a])) * d.vs);
-}
-
-// one axis of interp(): q = p - 0.5, n = (int)q, s1 = q - n, s0 = 1 - s1; q < 0 -> (0, 1, 0); n >= ext - 1 -> (ext - 2, 0, 1)
-__device__ __forceinline__ void axis_weights(float p, int ext, int& n, float& s0, float& s1) {
-  const float q = p - 0.5f;
-  if (!(q >= 0.0f)) {
-    n = 0; s0 = 1.0f; s1 = 0.0f;
-  } else if (q >= static_cast<float>(ext - 1)) {        // trunc(q) >= ext - 1
-    n = ext - 2; s0 = 0.0f; s1 = 1.0f;
-  } else {
-    n = static_cast<int>(q);
-    s1 = q - static_cast<float>(n);
-    s0 = 1.0f - s1;
-  }
-}
-
-// interp(g, pos) of one batch entry's grid g: tensor product over the 2^D corners, x innermost
-template <int D>
-__device__ __forceinline__ float interp(const float* __restrict__ g, const float* pos, const AdvDims& d) {
-  int n[3];
-  float s0[3], s1[3];
-  axis_weights(pos[0], d.X, n[0], s0[0], s1[0]);
-  axis_weights(pos[1], d.Y, n[1], s0[1], s1[1]);
-  if (D == 3) axis_weights(pos[2], d.Z, n[2], s0[2], s1[2]);
-  else n[2] = 0;
-  const int64_t sy = d.X, sz = static_cast<int64_t>(d.X) * d.Y;
-  const float* q = g + (static_cast<int64_t>(n[2]) * d.Y + n[1]) * d.X + n[0];
-  const float r00 = s0[0] * q[0] + s1[0] * q[1];
-  const float r01 = s0[0] * q[sy] + s1[0] * q[sy + 1];
-  const float r0 = s0[1] * r00 + s1[1] * r01;
-  if (D == 2) return r0;
-  const float r10 = s0[0] * q[sz] + s1[0] * q[sz + 1];
-  const float r11 = s0[0] * q[sz + sy] + s1[0] * q[sz + sy + 1];
-  const float r1 = s0[1] * r10 + s1[1] * r11;
-  return s0[2] * r0 + s1[2] * r1;
-}
-
-// min / max of orig over the interior corners c, c+1 of the integer cell c = clamp(trunc(t), 0, ext - 2) per axis
-template <int D>
-__device__ __forceinline__ void corner_range(const float* __restrict__ g, const float* t, const AdvDims& d, float& mn, float& mx, bool& found) {
-  const int ext[3] = {d.X, d.Y, d.Z};
-  int c[3] = {0, 0, 0};
-#pragma unroll
-  for (int a = 0; a < D; ++a) c[a] = static_cast<int>(fminf(fmaxf(t[a], 0.0f), static_cast<float>(ext[a] - 2)));
-#pragma unroll
-  for (int dz = 0; dz < (D == 3 ? 2 : 1); ++dz)
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-      for (int dx = 0; dx < 2; ++dx) {
-        const int x = c[0] + dx, y = c[1] + dy, z = c[2] + dz;
-        const bool in = x >= d.bnd && x < d.X - d.bnd && y >= d.bnd && y < d.Y - d.bnd && (D == 2 || (z >= d.bnd && z < d.Z - d.bnd));
-        if (in) {
-          const float v = g[(static_cast<int64_t>(z) * d.Y + y) * d.X + x];
-          mn = found ? fminf(mn, v) : v;
-          mx = found ? fmaxf(mx, v) : v;
-          found = true;
-        }
-      }
 }
 
 template <int D>

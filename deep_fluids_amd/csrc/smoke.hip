@@ -1,0 +1,576 @@
+// The solver half of the reference's smoke scene (scene/smoke_pos_size.py:186-195 main(): advectSemiLagrange(vel, vel), setWallBcs,
+// addBuoyancy, solvePressure, setWallBcs for a closed box), written for gfx950 from the step definition in include/deepfluids_hip.h.
+// Bit parity with mantaflow is NOT claimed (it cannot be run here); tests/smoke_ref.py restates the definition.
+//
+//   velocity [B,(Z,)Y,X,D] fp32 MAC face values (component a of cell c on c's low-a face), density / pressure [B,(Z,)Y,X] fp32, cell
+//   (i,j,k) = [..,k,j,i]; interior: bnd <= index < extent - bnd on every axis, else a wall cell.
+//
+//   mac_sl / mac_mc   the velocity carried through itself, one thread = one cell and its D components, the helpers of advect.hip read
+//                     with stride D.  As there: the gathers are data dependent and served by L1/L2, no LDS.
+//   wall_buoyancy     element-wise: wall faces 0, kept faces += (0.5*force[a]) * (rho(c) + rho(c - e_a)).
+//   pressure          plain conjugate gradients on the 5- / 7-point Neumann Laplacian of the interior cells, two launches per iteration:
+//     direction(k)    every workgroup first combines its entry's r.r and max|r| partials (fixed order) and takes the entry's decision
+//                     (converged / max_iter / go on, beta = rr / rr_old); then p = r + beta*p_old is recomputed at the cell and at its
+//                     neighbours, p and q = A p are written and the p.q partial of the workgroup is stored.
+//     update(k)       every workgroup combines the p.q partials, alpha = rr / p.q; x += alpha p, r -= alpha q, r.r and max|r| partials.
+//   All per-entry scalars live in the workspace (two copies: a launch reads one and writes the other, so no workgroup reads a word that
+//   another workgroup of the same launch writes).  A workgroup belongs to ONE batch entry and the partials are combined in an order that
+//   depends on the grid extents alone: an entry's result does not depend on the rest of the batch.  No floating-point atomics.
+//   The grids of one entry at the sizes this is used for (96x128: 48 KiB per array) live in L2; the XCD remap hands each XCD a contiguous
+//   run of workgroups, so an entry's neighbours in y and z are on the same L2.
+//
+// Float -> int conversions are taken only of values already known to be inside the grid (advect_common.hpp).
+#include "advect_common.hpp"
+#include "df_common.hpp"
+#include "stencil_common.hpp"
+
+namespace {
+
+using df::ceil_div;
+using dfadv::AdvDims;
+using dfadv::Cell;
+using dfadv::corner_range;
+using dfadv::decode;
+using dfadv::interp;
+using dfst::kThreads;
+using dfst::xcd_block;
+
+template <int D>
+struct VelRec { float v[D]; };
+
+// ---- MAC self-advection ------------------------------------------------------------------------------------------------------------------
+// dt * uface_a of an interior cell: the own component as it is, every other component b the mean of the four faces around the a-face
+template <int D>
+__device__ __forceinline__ void face_displacement(const float* __restrict__ vel, const Cell<D>& c, const AdvDims& d, int a, float* du) {
+  const int64_t st[3] = {D, static_cast<int64_t>(d.X) * D, static_cast<int64_t>(d.X) * d.Y * D};
+  const float* v = vel + c.idx * D;
+#pragma unroll
+  for (int b = 0; b < D; ++b) {
+    if (b == a) du[b] = d.dt * v[a];
+    else du[b] = d.dt * (0.25f * (((v[b] + v[b - st[a]]) + v[b + st[b]]) + v[b - st[a] + st[b]]));
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(kThreads) void mac_sl_kernel(const float* __restrict__ vel, float* __restrict__ fwd, AdvDims d) {
+  const int64_t idx = xcd_block(blockIdx.x, gridDim.x, 0) * kThreads + threadIdx.x;
+  if (idx >= d.ncell) return;
+  const Cell<D> c = decode<D>(idx, d);
+  VelRec<D> r;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    r.v[a] = 0.0f;
+    if (c.interior) {
+      float du[3], pos[3];
+      face_displacement<D>(vel, c, d, a, du);
+#pragma unroll
+      for (int b = 0; b < D; ++b) pos[b] = (static_cast<float>(c.p[b]) + 0.5f) - du[b];
+      r.v[a] = interp<D, D>(vel + c.base * D + a, pos, d);
+    }
+  }
+  *reinterpret_cast<VelRec<D>*>(fwd + idx * D) = r;
+}
+
+template <int D, int MODE>
+__global__ __launch_bounds__(kThreads) void mac_mc_kernel(const float* __restrict__ orig, const float* __restrict__ fwd,
+                                                          float* __restrict__ out, AdvDims d) {
+  const int64_t idx = xcd_block(blockIdx.x, gridDim.x, 0) * kThreads + threadIdx.x;
+  if (idx >= d.ncell) return;
+  const Cell<D> c = decode<D>(idx, d);
+  VelRec<D> r;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    r.v[a] = 0.0f;
+    if (c.interior) {
+      const float f = fwd[idx * D + a];
+      r.v[a] = f;
+      if (c.p[a] > d.bnd) {                            // c - e_a is interior too
+        float du[3], pos[3], t[3];
+        face_displacement<D>(orig, c, d, a, du);
+#pragma unroll
+        for (int b = 0; b < D; ++b) pos[b] = (static_cast<float>(c.p[b]) + 0.5f) + du[b];
+        const float bwd = interp<D, D>(fwd + c.base * D + a, pos, d);
+        const float cor = f + 0.5f * (orig[idx * D + a] - bwd);
+        float mn = 0.0f, mx = 0.0f;
+        bool found = false;
+#pragma unroll
+        for (int b = 0; b < D; ++b) t[b] = static_cast<float>(c.p[b]) - du[b];
+        corner_range<D, D>(orig + c.base * D + a, t, d, mn, mx, found);
+        if (MODE == 1) {
+#pragma unroll
+          for (int b = 0; b < D; ++b) t[b] = static_cast<float>(c.p[b]) + du[b];
+          corner_range<D, D>(orig + c.base * D + a, t, d, mn, mx, found);
+        }
+        if (!found) r.v[a] = f;
+        else if (MODE == 2) r.v[a] = (cor < mn || cor > mx) ? f : cor;
+        else r.v[a] = fminf(fmaxf(cor, mn), mx);
+      }
+    }
+  }
+  *reinterpret_cast<VelRec<D>*>(out + idx * D) = r;
+}
+
+// ---- walls and buoyancy --------------------------------------------------------------------------------------------------------------------
+struct Force { float f[3]; };
+
+template <int D>
+__global__ __launch_bounds__(kThreads) void wall_buoyancy_kernel(const float* vel, const float* __restrict__ rho, float* out, Force force,
+                                                                 AdvDims d) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (idx >= d.ncell) return;
+  const Cell<D> c = decode<D>(idx, d);
+  const int64_t st[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
+  const VelRec<D> v = *reinterpret_cast<const VelRec<D>*>(vel + idx * D);
+  VelRec<D> r;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    r.v[a] = 0.0f;
+    if (c.interior && c.p[a] > d.bnd) r.v[a] = v.v[a] + (0.5f * force.f[a]) * (rho[idx] + rho[idx - st[a]]);
+  }
+  *reinterpret_cast<VelRec<D>*>(out + idx * D) = r;
+}
+
+// ---- pressure projection ---------------------------------------------------------------------------------------------------------------------
+struct PDims {
+  int64_t n;       // cells of one batch entry
+  int nblk;        // workgroups of one batch entry
+  int B, Z, Y, X, bnd;
+};
+
+struct CgState {   // per batch entry, 32 bytes
+  float rr, maxr, alpha, beta, pq;
+  int active, iters, pad;
+};
+
+struct PCell {
+  int64_t cell;    // index inside the entry
+  int e;           // batch entry
+  int j;           // workgroup inside the entry
+  int p[3];
+  bool interior;
+};
+
+template <int D>
+__device__ __forceinline__ PCell pdecode(const PDims& d) {
+  PCell c;
+  const int64_t logical = xcd_block(blockIdx.x, gridDim.x, 0);
+  c.e = static_cast<int>(logical / d.nblk);
+  c.j = static_cast<int>(logical - static_cast<int64_t>(c.e) * d.nblk);
+  c.cell = static_cast<int64_t>(c.j) * kThreads + threadIdx.x;
+  const int64_t row = c.cell / d.X;
+  c.p[0] = static_cast<int>(c.cell - row * d.X);
+  c.p[1] = static_cast<int>(row % d.Y);
+  c.p[2] = D == 3 ? static_cast<int>(row / d.Y) : 0;
+  c.interior = c.cell < d.n && c.p[0] >= d.bnd && c.p[0] < d.X - d.bnd && c.p[1] >= d.bnd && c.p[1] < d.Y - d.bnd &&
+               (D == 2 || (c.p[2] >= d.bnd && c.p[2] < d.Z - d.bnd));
+  return c;
+}
+
+// Fixed-order reductions over the workgroup: xor butterfly inside a wave (every lane ends with the same bits: a + b == b + a), then the
+// four wave results in ascending order.  Every thread returns the total.  `lds` holds 4 floats and is free again after the call.
+template <bool MAX>
+__device__ __forceinline__ float block_reduce(float v, float* lds) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const float o = __shfl_xor(v, m);
+    v = MAX ? fmaxf(v, o) : v + o;
+  }
+  __syncthreads();                                      // the previous use of lds is over
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return MAX ? fmaxf(fmaxf(fmaxf(lds[0], lds[1]), lds[2]), lds[3]) : ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+// the nblk partials of one entry, combined by every workgroup of the entry in the same order
+template <bool MAX>
+__device__ __forceinline__ float entry_reduce(const float* __restrict__ part, int nblk, float* lds) {
+  float a = 0.0f;
+  for (int t = threadIdx.x; t < nblk; t += kThreads) a = MAX ? fmaxf(a, part[t]) : a + part[t];
+  return block_reduce<MAX>(a, lds);
+}
+
+struct PWs {
+  float *r, *p[2], *q, *pq_part, *rr_part, *mx_part;
+  CgState* state[2];
+};
+
+int64_t ws_floats(int64_t B, int64_t n, int64_t nblk) { return 4 * B * n + 3 * B * nblk + 2 * B * (int64_t)(sizeof(CgState) / 4); }
+
+PWs carve(void* ws, int64_t B, int64_t n, int64_t nblk) {
+  PWs w;
+  float* f = static_cast<float*>(ws);
+  const int64_t N = B * n, P = B * nblk;
+  w.r = f; w.p[0] = f + N; w.p[1] = f + 2 * N; w.q = f + 3 * N;
+  w.pq_part = f + 4 * N; w.rr_part = w.pq_part + P; w.mx_part = w.rr_part + P;
+  w.state[0] = reinterpret_cast<CgState*>(w.mx_part + P);
+  w.state[1] = w.state[0] + B;
+  return w;
+}
+
+template <int D>
+__global__ __launch_bounds__(kThreads) void pressure_init_kernel(const float* __restrict__ vel, float* __restrict__ x, PWs w, PDims d) {
+  __shared__ float lds[4];
+  const PCell c = pdecode<D>(d);
+  const int64_t g = static_cast<int64_t>(c.e) * d.n + c.cell;
+  float b = 0.0f;
+  if (c.interior) {
+    const int64_t st[3] = {D, static_cast<int64_t>(d.X) * D, static_cast<int64_t>(d.X) * d.Y * D};
+    const float* v = vel + g * D;
+    float div = v[st[0]] - v[0];
+    div = div + (v[st[1] + 1] - v[1]);
+    if (D == 3) div = div + (v[st[2] + 2] - v[2]);
+    b = -div;
+  }
+  if (c.cell < d.n) {
+    x[g] = 0.0f; w.r[g] = b; w.p[0][g] = b; w.p[1][g] = 0.0f; w.q[g] = 0.0f;
+  }
+  const float rr = block_reduce<false>(b * b, lds);
+  const float mx = block_reduce<true>(fabsf(b), lds);
+  if (threadIdx.x == 0) {
+    w.rr_part[static_cast<int64_t>(c.e) * d.nblk + c.j] = rr;
+    w.mx_part[static_cast<int64_t>(c.e) * d.nblk + c.j] = mx;
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(kThreads) void cg_direction_kernel(PWs w, PDims d, int par, int first, float accuracy, int max_iter) {
+  __shared__ float lds[4];
+  const PCell c = pdecode<D>(d);
+  const bool writer = c.j == 0 && threadIdx.x == 0;
+  CgState s;
+  if (first) s = CgState{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1, 0, 0};
+  else s = w.state[par][c.e];
+  if (!s.active) {                                      // frozen: carry the record over, touch nothing else
+    if (writer) w.state[par ^ 1][c.e] = s;
+    return;
+  }
+  const int64_t po = static_cast<int64_t>(c.e) * d.nblk;
+  const float rr = entry_reduce<false>(w.rr_part + po, d.nblk, lds);
+  const float mx = entry_reduce<true>(w.mx_part + po, d.nblk, lds);
+  const bool act = mx > accuracy && rr > 0.0f && s.iters < max_iter;
+  const float beta = first ? 0.0f : rr / s.rr;          // s.rr > 0: the entry was active
+  if (writer) w.state[par ^ 1][c.e] = CgState{rr, mx, s.alpha, act ? beta : s.beta, s.pq, act ? 1 : 0, s.iters + (act ? 1 : 0), 0};
+  if (!act) return;
+  float pq = 0.0f;
+  if (c.interior) {
+    const int64_t eo = static_cast<int64_t>(c.e) * d.n;
+    const float* __restrict__ r = w.r + eo;
+    const float* __restrict__ po_ = w.p[par] + eo;
+    const int64_t st[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
+    const int ext[3] = {d.X, d.Y, d.Z};
+    const float pc = r[c.cell] + beta * po_[c.cell];
+    float sum = 0.0f;
+    int cnt = 0;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+      if (c.p[a] > d.bnd) { const int64_t nb = c.cell - st[a]; sum += r[nb] + beta * po_[nb]; ++cnt; }
+      if (c.p[a] + 1 < ext[a] - d.bnd) { const int64_t nb = c.cell + st[a]; sum += r[nb] + beta * po_[nb]; ++cnt; }
+    }
+    const float qv = static_cast<float>(cnt) * pc - sum;
+    w.p[par ^ 1][eo + c.cell] = pc;
+    w.q[eo + c.cell] = qv;
+    pq = pc * qv;
+  }
+  pq = block_reduce<false>(pq, lds);
+  if (threadIdx.x == 0) w.pq_part[po + c.j] = pq;
+}
+
+template <int D>
+__global__ __launch_bounds__(kThreads) void cg_update_kernel(float* __restrict__ x, PWs w, PDims d, int par) {
+  __shared__ float lds[4];
+  const PCell c = pdecode<D>(d);
+  CgState* s = w.state[par ^ 1] + c.e;                  // what direction(k) has just written
+  if (!s->active) return;
+  const float rr_old = s->rr;
+  const int64_t po = static_cast<int64_t>(c.e) * d.nblk;
+  const float pq = entry_reduce<false>(w.pq_part + po, d.nblk, lds);
+  const float alpha = pq > 0.0f ? rr_old / pq : 0.0f;
+  if (c.j == 0 && threadIdx.x == 0) { s->alpha = alpha; s->pq = pq; }   // words no workgroup of this launch reads
+  float rr = 0.0f, mx = 0.0f;
+  if (c.interior) {
+    const int64_t g = static_cast<int64_t>(c.e) * d.n + c.cell;
+    x[g] = x[g] + alpha * w.p[par ^ 1][g];
+    const float rn = w.r[g] - alpha * w.q[g];
+    w.r[g] = rn;
+    rr = rn * rn;
+    mx = fabsf(rn);
+  }
+  rr = block_reduce<false>(rr, lds);
+  mx = block_reduce<true>(mx, lds);
+  if (threadIdx.x == 0) { w.rr_part[po + c.j] = rr; w.mx_part[po + c.j] = mx; }
+}
+
+// one workgroup: the number of active entries (an integer sum: order-free) and, if asked for, every entry's iteration count
+__global__ __launch_bounds__(kThreads) void cg_status_kernel(const CgState* __restrict__ s, int B, int32_t* __restrict__ count,
+                                                            int32_t* __restrict__ iters) {
+  __shared__ int lds[4];
+  int n = 0;
+  for (int e = threadIdx.x; e < B; e += kThreads) {
+    n += s[e].active ? 1 : 0;
+    if (iters) iters[e] = s[e].iters;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) n += __shfl_xor(n, m);
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0 && count) count[0] = lds[0] + lds[1] + lds[2] + lds[3];
+}
+
+template <int D>
+__global__ __launch_bounds__(kThreads) void pressure_correct_kernel(const float* vel, const float* __restrict__ pr, float* out, AdvDims d) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (idx >= d.ncell) return;
+  const Cell<D> c = decode<D>(idx, d);
+  const int64_t st[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
+  const VelRec<D> v = *reinterpret_cast<const VelRec<D>*>(vel + idx * D);
+  VelRec<D> r;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    r.v[a] = 0.0f;
+    if (c.interior && c.p[a] > d.bnd) r.v[a] = v.v[a] - (pr[idx] - pr[idx - st[a]]);
+  }
+  *reinterpret_cast<VelRec<D>*>(out + idx * D) = r;
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------------------
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+int check_dims(const char* fn, int dim, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd) {
+  DF_REQUIRE(B > 0 && Z > 0 && Y > 0 && X > 0, DF_EINVAL, "%s: non-positive extent", fn);
+  DF_REQUIRE(bnd >= 1, DF_EINVAL, "%s: boundary width must be >= 1 (got %d)", fn, bnd);
+  DF_REQUIRE(B < (1 << 24) && Z < (1 << 24) && Y < (1 << 24) && X < (1 << 24), DF_ESHAPE, "%s: extent too large", fn);
+  const int64_t need = 2 * static_cast<int64_t>(bnd) + 2;
+  DF_REQUIRE(X >= need && Y >= need && (dim == 2 || Z >= need), DF_ESHAPE, "%s: every extent must be >= 2*bnd + 2 = %lld", fn,
+             (long long)need);
+  DF_REQUIRE(Z * Y * X < (1ll << 40) / B, DF_ESHAPE, "%s: extent too large", fn);
+  return DF_OK;
+}
+
+// the cell-per-thread grid over all B*Z*Y*X cells
+int plan(const char* fn, int dim, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, float dt, AdvDims* d, unsigned* nblk) {
+  if (int e = check_dims(fn, dim, B, Z, Y, X, bnd)) return e;
+  const int64_t n = B * Z * Y * X;
+  DF_REQUIRE(ceil_div(n, kThreads) < (1ll << 31), DF_ESHAPE, "%s: extent too large", fn);
+  *d = AdvDims{n, (int)Z, (int)Y, (int)X, bnd, dt, 1.0f};
+  *nblk = static_cast<unsigned>(ceil_div(n, kThreads));
+  return DF_OK;
+}
+
+// the grid of the solver: workgroups that never straddle batch entries
+int pplan(const char* fn, int dim, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, PDims* d, unsigned* grid) {
+  if (int e = check_dims(fn, dim, B, Z, Y, X, bnd)) return e;
+  const int64_t n = Z * Y * X, nblk = ceil_div(n, kThreads);
+  DF_REQUIRE(nblk * B < (1ll << 31), DF_ESHAPE, "%s: extent too large", fn);
+  *d = PDims{n, (int)nblk, (int)B, (int)Z, (int)Y, (int)X, bnd};
+  *grid = static_cast<unsigned>(nblk * B);
+  return DF_OK;
+}
+
+int check_ws(const char* fn, const void* ws, int64_t ws_bytes, const PDims& d) {
+  DF_REQUIRE(ws, DF_EINVAL, "%s: null workspace", fn);
+  DF_REQUIRE(aligned4(ws), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  const int64_t need = 4 * ws_floats(d.B, d.n, d.nblk);
+  DF_REQUIRE(ws_bytes >= need, DF_EWORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes, (long long)need);
+  return DF_OK;
+}
+
+// the workspace (the `need`ed part of it) must not share a byte with an array the kernels read or write beside it
+int check_apart(const char* fn, const void* ws, const PDims& d, const void* p, int64_t bytes, const char* what) {
+  if (!p) return DF_OK;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(ws), b = reinterpret_cast<uintptr_t>(p);
+  const uintptr_t na = static_cast<uintptr_t>(4 * ws_floats(d.B, d.n, d.nblk)), nb = static_cast<uintptr_t>(bytes);
+  DF_REQUIRE(a + na <= b || b + nb <= a, DF_EINVAL, "%s: the workspace overlaps the %s", fn, what);
+  return DF_OK;
+}
+
+template <int D>
+int mac_sl(const char* fn, const float* vel, float* fwd, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt, int bnd, df_stream_t stream) {
+  DF_REQUIRE(vel && fwd, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : "output");
+  AdvDims d;
+  unsigned nblk;
+  if (int e = plan(fn, D, B, Z, Y, X, bnd, dt, &d, &nblk)) return e;
+  DF_REQUIRE(fwd != vel, DF_EINVAL, "%s: the output must not be the input (the step gathers)", fn);
+  DF_REQUIRE(aligned4(vel) && aligned4(fwd), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  hipLaunchKernelGGL((mac_sl_kernel<D>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, fwd, d);
+  return df::launched(fn);
+}
+
+template <int D>
+int mac_mc(const char* fn, const float* vel, const float* fwd, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt, int bnd,
+           int clamp_mode, df_stream_t stream) {
+  DF_REQUIRE(vel && fwd && out, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : !fwd ? "input" : "output");
+  DF_REQUIRE(clamp_mode == 1 || clamp_mode == 2, DF_EINVAL, "%s: clamp_mode must be 1 or 2 (got %d)", fn, clamp_mode);
+  AdvDims d;
+  unsigned nblk;
+  if (int e = plan(fn, D, B, Z, Y, X, bnd, dt, &d, &nblk)) return e;
+  DF_REQUIRE(out != vel && out != fwd, DF_EINVAL, "%s: the output must not be an input (the step gathers)", fn);
+  DF_REQUIRE(aligned4(vel) && aligned4(fwd) && aligned4(out), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  hipStream_t s = df::as_stream(stream);
+  if (clamp_mode == 2) hipLaunchKernelGGL((mac_mc_kernel<D, 2>), dim3(nblk), dim3(kThreads), 0, s, vel, fwd, out, d);
+  else hipLaunchKernelGGL((mac_mc_kernel<D, 1>), dim3(nblk), dim3(kThreads), 0, s, vel, fwd, out, d);
+  return df::launched(fn);
+}
+
+template <int D>
+int wall_buoyancy(const char* fn, const float* vel, const float* rho, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, Force f, int bnd,
+                  df_stream_t stream) {
+  DF_REQUIRE(vel && rho && out, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : !rho ? "density" : "output");
+  AdvDims d;
+  unsigned nblk;
+  if (int e = plan(fn, D, B, Z, Y, X, bnd, 0.0f, &d, &nblk)) return e;
+  DF_REQUIRE(static_cast<const void*>(out) != static_cast<const void*>(rho), DF_EINVAL,
+             "%s: the output must not be the density (it is read at a neighbour)", fn);
+  DF_REQUIRE(aligned4(vel) && aligned4(rho) && aligned4(out), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  hipLaunchKernelGGL((wall_buoyancy_kernel<D>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, rho, out, f, d);
+  return df::launched(fn);
+}
+
+template <int D>
+int pressure_init(const char* fn, const float* vel, float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X,
+                  int bnd, df_stream_t stream) {
+  DF_REQUIRE(vel && pressure, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : "pressure");
+  PDims d;
+  unsigned grid;
+  if (int e = pplan(fn, D, B, Z, Y, X, bnd, &d, &grid)) return e;
+  if (int e = check_ws(fn, ws, ws_bytes, d)) return e;
+  DF_REQUIRE(static_cast<const void*>(pressure) != static_cast<const void*>(vel), DF_EINVAL,
+             "%s: the pressure must not be the velocity (it is read at a neighbour)", fn);
+  if (int e = check_apart(fn, ws, d, vel, 4 * d.n * B * D, "velocity")) return e;
+  if (int e = check_apart(fn, ws, d, pressure, 4 * d.n * B, "pressure")) return e;
+  DF_REQUIRE(aligned4(vel) && aligned4(pressure), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  hipLaunchKernelGGL((pressure_init_kernel<D>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), vel, pressure, carve(ws, B, d.n, d.nblk), d);
+  return df::launched(fn);
+}
+
+template <int D>
+int cg_direction(const char* fn, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k, float accuracy,
+                 int64_t max_iter, df_stream_t stream) {
+  PDims d;
+  unsigned grid;
+  if (int e = pplan(fn, D, B, Z, Y, X, bnd, &d, &grid)) return e;
+  if (int e = check_ws(fn, ws, ws_bytes, d)) return e;
+  DF_REQUIRE(k >= 0 && max_iter >= 0 && max_iter < (1ll << 31), DF_EINVAL, "%s: iteration %lld of at most %lld", fn, (long long)k,
+             (long long)max_iter);
+  DF_REQUIRE(accuracy >= 0.0f, DF_EINVAL, "%s: accuracy must be >= 0", fn);
+  hipLaunchKernelGGL((cg_direction_kernel<D>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), carve(ws, B, d.n, d.nblk), d, (int)(k & 1),
+                     k == 0 ? 1 : 0, accuracy, (int)max_iter);
+  return df::launched(fn);
+}
+
+template <int D>
+int cg_update(const char* fn, float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k,
+              df_stream_t stream) {
+  DF_REQUIRE(pressure, DF_EINVAL, "%s: null pressure", fn);
+  PDims d;
+  unsigned grid;
+  if (int e = pplan(fn, D, B, Z, Y, X, bnd, &d, &grid)) return e;
+  if (int e = check_ws(fn, ws, ws_bytes, d)) return e;
+  DF_REQUIRE(k >= 0, DF_EINVAL, "%s: iteration %lld", fn, (long long)k);
+  if (int e = check_apart(fn, ws, d, pressure, 4 * d.n * B, "pressure")) return e;
+  DF_REQUIRE(aligned4(pressure), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  hipLaunchKernelGGL((cg_update_kernel<D>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), pressure, carve(ws, B, d.n, d.nblk), d,
+                     (int)(k & 1));
+  return df::launched(fn);
+}
+
+template <int D>
+int pressure_correct(const char* fn, const float* vel, const float* pressure, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                     df_stream_t stream) {
+  DF_REQUIRE(vel && pressure && out, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : !pressure ? "pressure" : "output");
+  AdvDims d;
+  unsigned nblk;
+  if (int e = plan(fn, D, B, Z, Y, X, bnd, 0.0f, &d, &nblk)) return e;
+  DF_REQUIRE(static_cast<const void*>(out) != static_cast<const void*>(pressure), DF_EINVAL,
+             "%s: the output must not be the pressure (it is read at a neighbour)", fn);
+  DF_REQUIRE(aligned4(vel) && aligned4(pressure) && aligned4(out), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  hipLaunchKernelGGL((pressure_correct_kernel<D>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, pressure, out, d);
+  return df::launched(fn);
+}
+
+}  // namespace
+
+extern "C" {
+
+int df_mac_advect_sl2d(const float* vel, float* fwd, int64_t B, int64_t Y, int64_t X, float dt, int bnd, df_stream_t stream) {
+  return mac_sl<2>("df_mac_advect_sl2d", vel, fwd, B, 1, Y, X, dt, bnd, stream);
+}
+int df_mac_advect_sl3d(const float* vel, float* fwd, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt, int bnd, df_stream_t stream) {
+  return mac_sl<3>("df_mac_advect_sl3d", vel, fwd, B, Z, Y, X, dt, bnd, stream);
+}
+int df_mac_advect_mc2d(const float* vel, const float* fwd, float* out, int64_t B, int64_t Y, int64_t X, float dt, int bnd, int clamp_mode,
+                       df_stream_t stream) {
+  return mac_mc<2>("df_mac_advect_mc2d", vel, fwd, out, B, 1, Y, X, dt, bnd, clamp_mode, stream);
+}
+int df_mac_advect_mc3d(const float* vel, const float* fwd, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt, int bnd,
+                       int clamp_mode, df_stream_t stream) {
+  return mac_mc<3>("df_mac_advect_mc3d", vel, fwd, out, B, Z, Y, X, dt, bnd, clamp_mode, stream);
+}
+
+int df_wall_buoyancy2d(const float* vel, const float* density, float* out, int64_t B, int64_t Y, int64_t X, float fx, float fy, int bnd,
+                       df_stream_t stream) {
+  return wall_buoyancy<2>("df_wall_buoyancy2d", vel, density, out, B, 1, Y, X, Force{{fx, fy, 0.0f}}, bnd, stream);
+}
+int df_wall_buoyancy3d(const float* vel, const float* density, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, float fx, float fy,
+                       float fz, int bnd, df_stream_t stream) {
+  return wall_buoyancy<3>("df_wall_buoyancy3d", vel, density, out, B, Z, Y, X, Force{{fx, fy, fz}}, bnd, stream);
+}
+
+int64_t df_pressure_workspace_bytes(int64_t B, int64_t Z, int64_t Y, int64_t X) {
+  if (B <= 0 || Z <= 0 || Y <= 0 || X <= 0 || B >= (1 << 24) || Z >= (1 << 24) || Y >= (1 << 24) || X >= (1 << 24)) return DF_EINVAL;
+  if (Z * Y * X >= (1ll << 40) / B) return DF_ESHAPE;
+  const int64_t n = Z * Y * X;
+  return 4 * ws_floats(B, n, ceil_div(n, kThreads));
+}
+
+int df_pressure_init2d(const float* vel, float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int64_t X, int bnd,
+                       df_stream_t stream) {
+  return pressure_init<2>("df_pressure_init2d", vel, pressure, ws, ws_bytes, B, 1, Y, X, bnd, stream);
+}
+int df_pressure_init3d(const float* vel, float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                       df_stream_t stream) {
+  return pressure_init<3>("df_pressure_init3d", vel, pressure, ws, ws_bytes, B, Z, Y, X, bnd, stream);
+}
+int df_pressure_cg_direction2d(void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k, float accuracy,
+                               int64_t max_iter, df_stream_t stream) {
+  return cg_direction<2>("df_pressure_cg_direction2d", ws, ws_bytes, B, 1, Y, X, bnd, k, accuracy, max_iter, stream);
+}
+int df_pressure_cg_direction3d(void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k, float accuracy,
+                               int64_t max_iter, df_stream_t stream) {
+  return cg_direction<3>("df_pressure_cg_direction3d", ws, ws_bytes, B, Z, Y, X, bnd, k, accuracy, max_iter, stream);
+}
+int df_pressure_cg_update2d(float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k,
+                            df_stream_t stream) {
+  return cg_update<2>("df_pressure_cg_update2d", pressure, ws, ws_bytes, B, 1, Y, X, bnd, k, stream);
+}
+int df_pressure_cg_update3d(float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k,
+                            df_stream_t stream) {
+  return cg_update<3>("df_pressure_cg_update3d", pressure, ws, ws_bytes, B, Z, Y, X, bnd, k, stream);
+}
+
+int df_pressure_status(const void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int64_t k, int32_t* active_count,
+                       int32_t* iterations, df_stream_t stream) {
+  const char* fn = "df_pressure_status";
+  DF_REQUIRE(B > 0 && Z > 0 && Y > 0 && X > 0, DF_EINVAL, "%s: non-positive extent", fn);
+  DF_REQUIRE(B < (1 << 24) && Z < (1 << 24) && Y < (1 << 24) && X < (1 << 24) && Z * Y * X < (1ll << 40) / B, DF_ESHAPE,
+             "%s: extent too large", fn);
+  const PDims d{Z * Y * X, (int)ceil_div(Z * Y * X, kThreads), (int)B, (int)Z, (int)Y, (int)X, 1};
+  if (int e = check_ws(fn, ws, ws_bytes, d)) return e;
+  DF_REQUIRE(active_count || iterations, DF_EINVAL, "%s: null outputs", fn);
+  if (int e = check_apart(fn, ws, d, active_count, 4, "active count")) return e;
+  if (int e = check_apart(fn, ws, d, iterations, 4 * B, "iteration counts")) return e;
+  DF_REQUIRE(k >= 0, DF_EINVAL, "%s: iteration %lld", fn, (long long)k);
+  DF_REQUIRE(aligned4(active_count) && aligned4(iterations), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  const PWs w = carve(const_cast<void*>(ws), B, d.n, d.nblk);
+  hipLaunchKernelGGL(cg_status_kernel, dim3(1), dim3(kThreads), 0, df::as_stream(stream), w.state[(k & 1) ^ 1], (int)B, active_count, iterations);
+  return df::launched(fn);
+}
+
+int df_pressure_correct2d(const float* vel, const float* pressure, float* out, int64_t B, int64_t Y, int64_t X, int bnd, df_stream_t stream) {
+  return pressure_correct<2>("df_pressure_correct2d", vel, pressure, out, B, 1, Y, X, bnd, stream);
+}
+int df_pressure_correct3d(const float* vel, const float* pressure, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                          df_stream_t stream) {
+  return pressure_correct<3>("df_pressure_correct3d", vel, pressure, out, B, Z, Y, X, bnd, stream);
+}
+
+}  // extern "C"

@@ -4,6 +4,7 @@ On-disk format (written by the reference's ``scene/*.py``, e.g. scene/smoke_pos_
   <root>/args.txt            "key: value" lines (num_param, p0.., min_/max_/num_<pname>, num_frames, num_dof, path_format ...)
   <root>/v/%d_%d_%d.npz      x: [Y,X,2] | [Z,Y,X,3] float32 velocity, y: [c_num] parameters  (AE sets: y [dof, frames])
   <root>/v_range.txt         two numbers; x is normalised by max(|r0|, |r1|)     (data.py:87-88, 329)
+``generate_smoke_dataset`` writes such a directory for the reference's default 2-D smoke scene with this library's own solver.
 Labels are mapped to [-1,1] with min_/max_<pname> (data.py:331-332).
 
 The reference feeds a tf.FIFOQueue from N Python threads that share one RandomState (data.py:116-144) and dequeues
@@ -287,3 +288,61 @@ def write_synthetic_ae_dataset(root, spatial, num_scenes=2, num_frames=4, seed=0
     with open(os.path.join(root, "v_range.txt"), "w") as f:
         f.write("%.3f\n%.3f\n" % (-vmax, vmax))
     return num_scenes * num_frames
+
+
+def generate_smoke_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="src_x_pos", p1="src_radius", p2="frames", num_src_x_pos=21,
+                           min_src_x_pos=0.2, max_src_x_pos=0.8, src_y_pos=0.1, num_src_radius=5, min_src_radius=0.04, max_src_radius=0.12,
+                           num_frames=200, min_frames=0, max_frames=None, num_simulations=None, resolution_x=96, resolution_y=128,
+                           buoyancy=-4e-3, bWidth=1, open_bound=False, time_step=0.5, adv_order=2, clamp_mode=2, scenes_per_batch=None,
+                           accuracy=1e-4, device="cuda"):
+    """Simulate the reference's default 2-D training set (scene/smoke_pos_size.py:111-254, ``smoke_pos21_size5_f200``) on the GPU and
+    write it in the reference's on-disk format: ``args.txt`` with every argument of the scene script, ``v/%d_%d_%d.npz`` (x [Y,X,2]
+    float32 velocity after frame t, y = [p0, p1, t]) and ``v_range.txt``.  The keyword arguments are the script's, with its defaults.
+    Every scene is one batch entry of ``ops.simulate_smoke`` (``scenes_per_batch`` splits the set into chunks; an entry's result does
+    not depend on the rest of its batch).  The step is this library's restatement (include/deepfluids_hip.h), not mantaflow's: closed
+    box only (``open_bound=True`` is refused), plain CG in place of MIC(0)-preconditioned CG.  Returns the number of files written."""
+    from . import ops
+    if open_bound:
+        raise NotImplementedError("generate_smoke_dataset: open_bound=True is not restated (closed box only)")
+    if num_param != 3 or (p0, p1, p2) != ("src_x_pos", "src_radius", "frames"):
+        raise ValueError("generate_smoke_dataset: the scene has the parameters (src_x_pos, src_radius, frames)")
+    max_frames = num_frames - 1 if max_frames is None else max_frames
+    num_simulations = num_src_x_pos * num_src_radius * num_frames if num_simulations is None else num_simulations
+    args = [("log_dir", root), ("num_param", num_param), ("path_format", path_format), ("p0", p0), ("p1", p1), ("p2", p2),
+            ("num_src_x_pos", num_src_x_pos), ("min_src_x_pos", min_src_x_pos), ("max_src_x_pos", max_src_x_pos), ("src_y_pos", src_y_pos),
+            ("num_src_radius", num_src_radius), ("min_src_radius", min_src_radius), ("max_src_radius", max_src_radius),
+            ("num_frames", num_frames), ("min_frames", min_frames), ("max_frames", max_frames), ("num_simulations", num_simulations),
+            ("resolution_x", resolution_x), ("resolution_y", resolution_y), ("buoyancy", buoyancy), ("bWidth", bWidth),
+            ("open_bound", open_bound), ("time_step", time_step), ("adv_order", adv_order), ("clamp_mode", clamp_mode)]
+    os.makedirs(os.path.join(root, "v"), exist_ok=True)
+    with open(os.path.join(root, "args.txt"), "w") as f:
+        for k, v in args:
+            f.write("%s: %s\n" % (k, v))
+
+    def param(i, num, lo, hi):                       # get_param of the scene script (what trainer.smoke_pos_size_source evaluates)
+        return i / float(num - 1) * (hi - lo) + lo if num > 1 else lo
+
+    scenes = [(i, j, param(i, num_src_x_pos, min_src_x_pos, max_src_x_pos), param(j, num_src_radius, min_src_radius, max_src_radius))
+              for i in range(num_src_x_pos) for j in range(num_src_radius)]
+    X, Y = int(resolution_x), int(resolution_y)
+    chunk = len(scenes) if not scenes_per_batch else int(scenes_per_batch)
+    force = ops.default_buoyancy_force((Y, X), time_step, gravity=buoyancy)
+    v_range = [np.finfo(np.float64).max, np.finfo(np.float64).min]
+    written = 0
+    for c0 in range(0, len(scenes), chunk):
+        part = scenes[c0:c0 + chunk]
+        mask = torch.stack([ops.sphere_mask((Y, X), (X * px, Y * src_y_pos), X * pr) for _, _, px, pr in part]).to(device)
+        d0 = torch.zeros((len(part), Y, X), dtype=torch.float32, device=device)
+        v0 = torch.zeros((len(part), Y, X, 2), dtype=torch.float32, device=device)
+        frames = ops.simulate_smoke(d0, v0, num_frames, dt=time_step, source=mask, force=force, order=adv_order, clamp_mode=clamp_mode,
+                                    bnd=bWidth, accuracy=accuracy, stack=False)
+        for t, (_, v) in enumerate(frames):
+            vh = v.cpu().numpy()
+            v_range = [min(v_range[0], float(vh.min())), max(v_range[1], float(vh.max()))]
+            for e, (i, j, px, pr) in enumerate(part):
+                np.savez_compressed(os.path.join(root, "v", path_format % (i, j, t)), x=vh[e], y=[px, pr, t])
+                written += 1
+    with open(os.path.join(root, "v_range.txt"), "w") as f:
+        f.write("%.3f\n" % v_range[0])
+        f.write("%.3f" % v_range[1])
+    return written

@@ -30,6 +30,7 @@ __all__ = [
     "vort_np", "curl_np", "grad_np", "jacobian_np3", "l1_mean", "velocity_loss",
     "denorm_img", "plane_view", "denorm_img3", "plane_view_np", "velocity_views3", "add_channels", "remove_channels",
     "advect", "advect_sequence", "advect_workspace", "density_image", "sphere_mask",
+    "advect_velocity", "wall_buoyancy", "solve_pressure", "pressure_workspace", "smoke_step", "simulate_smoke", "default_buoyancy_force", "default_max_iter",
     "advect_particles", "particle_cells", "particle_levelset", "liquid_sequence", "seed_particles", "box_levelset", "sphere_levelset",
     "variable_scope", "get_variables", "get_variable", "reset_variables", "set_random_seed", "all_variables",
 ]
@@ -1809,6 +1810,225 @@ def sphere_mask(shape, center, radius, device=None):
         r2 = r2 + ((np.arange(shape[ax]) + 0.5 - float(c)) ** 2).reshape(sh)
     m = torch.from_numpy((r2 <= float(radius) * float(radius)).astype(np.uint8))
     return m if device is None else m.to(device)
+
+
+# ---- the smoke solver step (the main() loop of the reference's scene/smoke_pos_size.py:186-195, a closed box): MAC self-advection, walls
+#      and buoyancy, a conjugate-gradient pressure projection.  Inference only, no autograd.  The step is defined in
+#      include/deepfluids_hip.h; parity is with the fp64 restatement of tests/smoke_ref.py, NOT with mantaflow, which cannot be run here.
+#      Left out: open bounds, obstacles, outflow, noise-modulated inflow (the reference's 3-D scenes need them), the MIC(0)
+#      preconditioner ----
+DEFAULT_CHECK_EVERY = 16      # iterations between two looks at the active count; the sweep over 1, 4, 16, 64 is in profiles/smoke.md
+
+
+def _smoke_vel(vel, who):
+    v = _prep(vel.detach(), "vel")
+    if v.dim() not in (4, 5) or v.shape[-1] != v.dim() - 2:
+        raise ValueError("%s expects a velocity [B,(Z,)Y,X,D] with D = 2 | 3 matching the grid, got %s" % (who, tuple(v.shape)))
+    return v, v.dim() - 2
+
+
+def _smoke_out(out, like, who):
+    if out is None:
+        return torch.empty_like(like)
+    if tuple(out.shape) != tuple(like.shape) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("%s: out must be a contiguous float32 GPU tensor of shape %s" % (who, tuple(like.shape)))
+    return out
+
+
+def advect_velocity(vel, dt, order=2, clamp_mode=2, bnd=1, out=None, workspace=None):
+    """The MAC velocity ``vel`` [B,(Z,)Y,X,D] carried through itself for ``dt`` (cells per unit time), modelled on mantaflow's
+    ``advectSemiLagrange(vel, vel, order, boundaryWidth=bnd, clampMode=clamp_mode)``; include/deepfluids_hip.h holds the definition
+    that is tested.  Returns a new velocity (``out`` if given; not ``vel`` itself).  ``workspace``: a float32 GPU tensor of
+    ``vel.numel()`` elements for order 2."""
+    with torch.no_grad():
+        _advect_args(order, clamp_mode, bnd)
+        v, nd = _smoke_vel(vel, "advect_velocity")
+        out = _smoke_out(out, v, "advect_velocity")
+        if out.data_ptr() == v.data_ptr():
+            raise ValueError("advect_velocity: out must not be the velocity itself (the step gathers)")
+        dims = list(v.shape[:-1])
+        sfx = "%dd" % nd
+        if order == 1:
+            call("df_mac_advect_sl" + sfx, _ptr(v), _ptr(out), *(dims + [float(dt), int(bnd), _stream()]))
+            return out
+        ws = workspace if workspace is not None else torch.empty((v.numel(),), dtype=torch.float32, device=v.device)
+        if ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < v.numel():
+            raise ValueError("advect_velocity: workspace must be a contiguous float32 GPU tensor of >= %d elements" % v.numel())
+        call("df_mac_advect_sl" + sfx, _ptr(v), _ptr(ws), *(dims + [float(dt), int(bnd), _stream()]))
+        call("df_mac_advect_mc" + sfx, _ptr(v), _ptr(ws), _ptr(out), *(dims + [float(dt), int(bnd), int(clamp_mode), _stream()]))
+        return out
+
+
+def wall_buoyancy(vel, density, force, bnd=1, out=None):
+    """``setWallBcs`` of a closed box and ``addBuoyancy`` in one element-wise pass: component a of cell c is 0 unless c and c - e_a are
+    both interior; kept components get ``+ (0.5 * force[a]) * (density[c] + density[c-e_a])``.  ``force``: D numbers (x, y[, z]).
+    ``out`` may be ``vel`` (in place)."""
+    with torch.no_grad():
+        v, nd = _smoke_vel(vel, "wall_buoyancy")
+        d = _prep(density.detach(), "density")
+        if tuple(d.shape) != tuple(v.shape[:-1]):
+            raise ValueError("wall_buoyancy expects a density %s for a velocity %s, got %s" % (tuple(v.shape[:-1]), tuple(v.shape), tuple(d.shape)))
+        f = [float(x) for x in force]
+        if len(f) != nd:
+            raise ValueError("wall_buoyancy: force must have %d components, got %r" % (nd, force))
+        if int(bnd) != bnd or bnd < 1:
+            raise ValueError("wall_buoyancy: bnd must be an integer >= 1, got %r" % (bnd,))
+        out = _smoke_out(out, v, "wall_buoyancy")
+        call("df_wall_buoyancy%dd" % nd, _ptr(v), _ptr(d), _ptr(out), *(list(d.shape) + f + [int(bnd), _stream()]))
+        return out
+
+
+def _read_word(t):
+    """the one word the host reads during a solve: the number of batch entries still iterating (a device-to-host copy that waits for
+    the stream); tools/smoke_probe.py times it"""
+    return int(t.item())
+
+
+def _pressure_dims(v, nd):
+    dims = list(v.shape[:-1])
+    return dims, (dims if nd == 3 else [dims[0], 1] + dims[1:])
+
+
+def pressure_workspace(vel):
+    """The scratch ``solve_pressure`` needs for ``vel`` [B,(Z,)Y,X,D] (residual, two directions, A p, partial sums, per-entry scalars): a
+    float32 GPU tensor, reusable across calls of the same shape."""
+    v, nd = _smoke_vel(vel, "pressure_workspace")
+    nbytes = query("df_pressure_workspace_bytes", *[int(x) for x in _pressure_dims(v, nd)[1]])
+    if nbytes < 0:
+        raise ValueError("pressure_workspace: unsupported extents %s" % (tuple(v.shape),))
+    return torch.empty((nbytes // 4,), dtype=torch.float32, device=v.device)
+
+
+def default_max_iter(shape):
+    """mantaflow's ``cgMaxIterFac=10``: ``int(10 * max(extent))``, times 4 in 2-D."""
+    return int(10 * max(shape)) * (1 if len(shape) == 3 else 4)
+
+
+def solve_pressure(vel, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, out=None, workspace=None):
+    """Make ``vel`` [B,(Z,)Y,X,D] divergence free inside a closed box: plain conjugate gradients on the Neumann Laplacian of the interior
+    cells from p = 0, every batch entry on its own until its ``max|r| <= accuracy`` or ``max_iter`` iterations (default
+    ``int(10*max(extent))``, times 4 in 2-D), then ``vel -= grad p`` with the wall faces 0.  The wall faces of ``vel`` must be 0 already
+    (``wall_buoyancy``).  All scalars of the iteration stay on the device; the host reads one word, the number of entries still
+    iterating, every ``check_every`` iterations (the result does not depend on it).  mantaflow preconditions with MIC(0), this solver
+    does not: both stop at the same criterion, so the fields agree to the solve's accuracy and not beyond.
+    Returns ``(vel_projected, pressure, iterations)``; ``iterations`` is an int32 tensor [B].  ``out`` may be ``vel``."""
+    with torch.no_grad():
+        v, nd = _smoke_vel(vel, "solve_pressure")
+        if int(bnd) != bnd or bnd < 1:
+            raise ValueError("solve_pressure: bnd must be an integer >= 1, got %r" % (bnd,))
+        if not accuracy >= 0:
+            raise ValueError("solve_pressure: accuracy must be >= 0, got %r" % (accuracy,))
+        dims, dims4 = _pressure_dims(v, nd)
+        if max_iter is None:
+            max_iter = default_max_iter(dims[1:])
+        check_every = DEFAULT_CHECK_EVERY if check_every is None else int(check_every)
+        if max_iter < 0 or check_every < 1:
+            raise ValueError("solve_pressure: max_iter must be >= 0 and check_every >= 1, got %r, %r" % (max_iter, check_every))
+        out = _smoke_out(out, v, "solve_pressure")
+        ws = workspace if workspace is not None else pressure_workspace(v)
+        if ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous():
+            raise ValueError("solve_pressure: workspace must be a contiguous float32 GPU tensor (pressure_workspace)")
+        nbytes = ws.numel() * 4
+        sfx = "%dd" % nd
+        pressure = _empty(dims, v)
+        words = torch.empty((1 + dims[0],), dtype=torch.int32, device=v.device)
+        count, iters = words[:1], words[1:]
+        bnd, acc, max_iter = int(bnd), float(accuracy), int(max_iter)
+        call("df_pressure_init" + sfx, _ptr(v), _ptr(pressure), _ptr(ws), nbytes, *(dims + [bnd, _stream()]))
+        k = 0
+        while True:
+            call("df_pressure_cg_direction" + sfx, _ptr(ws), nbytes, *(dims + [bnd, k, acc, max_iter, _stream()]))
+            if k % check_every == check_every - 1 or k >= max_iter:
+                call("df_pressure_status", _ptr(ws), nbytes, *(dims4 + [k, _ptr(count), None, _stream()]))
+                if _read_word(count) == 0:
+                    break
+            call("df_pressure_cg_update" + sfx, _ptr(pressure), _ptr(ws), nbytes, *(dims + [bnd, k, _stream()]))
+            k += 1
+        call("df_pressure_status", _ptr(ws), nbytes, *(dims4 + [k, None, _ptr(iters), _stream()]))
+        call("df_pressure_correct" + sfx, _ptr(v), _ptr(pressure), _ptr(out), *(dims + [bnd, _stream()]))
+        return out, pressure, iters.clone()
+
+
+def default_buoyancy_force(shape, dt, gravity=-4e-3):
+    """The ``force`` of ``wall_buoyancy`` for the reference's scene: (0, -gravity * dt * max(extent)[, 0]) -- mantaflow's
+    ``-gravity * dt / dx`` with ``dx = 1 / max(gridSize)`` and the scene's ``buoyancy = (0, -4e-3, 0)``.  Restated from memory of
+    mantaflow's addBuoyancy; it cannot be checked here."""
+    f = [0.0] * len(shape)
+    f[1] = -float(gravity) * float(dt) * max(int(n) for n in shape)
+    return tuple(f)
+
+
+class _SmokeBuffers(object):
+    """Everything a smoke step needs besides its inputs, allocated once for a shape."""
+
+    def __init__(self, density, vel, order, source):
+        self.adv = advect_workspace(density, order, source)
+        self.fwd = torch.empty((vel.numel(),), dtype=torch.float32, device=vel.device) if order == 2 else None
+        self.pws = pressure_workspace(vel)
+
+
+def _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every):
+    advect(d, v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, source=mask, out=d_out, workspace=buf.adv)
+    advect_velocity(v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, out=v_out, workspace=buf.fwd)
+    wall_buoyancy(v_out, d_out, force, bnd=bnd, out=v_out)
+    _, _, iters = solve_pressure(v_out, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=v_out, workspace=buf.pws)
+    return iters
+
+
+def smoke_step(density, vel, dt, source=None, force=None, order=2, clamp_mode=2, bnd=1, accuracy=1e-4, max_iter=None, check_every=None):
+    """One frame of the reference's smoke scene (scene/smoke_pos_size.py:187-195) on ``density`` [B,(Z,)Y,X] and the MAC velocity ``vel``
+    [B,(Z,)Y,X,D] of a closed box: stamp ``source`` (a mask) with 1, advect the density and the velocity through the OLD velocity, zero
+    the wall faces, add buoyancy (``force``; default ``default_buoyancy_force``), project.  Returns new ``(density, vel)``."""
+    with torch.no_grad():
+        d, v, nd = _advect_dims(density, vel)
+        force = default_buoyancy_force(d.shape[1:], dt) if force is None else force
+        mask = _source_mask(source, d) if source is not None else None
+        buf = _SmokeBuffers(d, v, order, mask is not None)
+        d_out, v_out = torch.empty_like(d), torch.empty_like(v)
+        _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every)
+        return d_out, v_out
+
+
+def _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, stats):
+    d, v, nd = _advect_dims(density0, vel0)
+    force = default_buoyancy_force(d.shape[1:], dt) if force is None else force
+    mask = _source_mask(source, d) if source is not None else None
+    buf = _SmokeBuffers(d, v, order, mask is not None)
+    d, v = d.clone(), v.clone()
+    d2, v2 = torch.empty_like(d), torch.empty_like(v)
+    for _ in range(int(steps)):
+        iters = _smoke_step(d, v, d2, v2, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every)
+        if stats is not None:
+            stats.append(iters)
+        d, d2, v, v2 = d2, d, v2, v
+        yield d, v
+
+
+def simulate_smoke(density0, vel0, steps, dt=0.5, source=None, force=None, order=2, clamp_mode=2, bnd=1, accuracy=1e-4, max_iter=None,
+                   check_every=None, stack=True, stats=None):
+    """``steps`` chained ``smoke_step`` frames from ``(density0, vel0)`` (left untouched); every buffer is allocated once.  With
+    ``stack`` returns ``(density, vels)``, ``vels`` [steps,B,(Z,)Y,X,D] the velocity after each step; without it returns a generator of
+    ``(density, vel)`` per step -- views of buffers the next step overwrites, so copy what is to be kept.  ``stats``: a list that
+    receives the iteration counts [B] of every step's solve."""
+    with torch.no_grad():
+        gen = _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, stats)
+        if not stack:
+            return _no_grad_iter(gen)
+        vels = torch.empty((int(steps),) + tuple(vel0.shape), dtype=torch.float32, device=vel0.device)
+        d = density0
+        for t, (d, v) in enumerate(gen):
+            vels[t].copy_(v)
+        return (d.clone() if int(steps) > 0 else density0.clone()), vels
+
+
+def _no_grad_iter(gen):
+    while True:
+        with torch.no_grad():
+            try:
+                item = next(gen)
+            except StopIteration:
+                return
+        yield item
 
 
 # ---- a liquid carried through a velocity field (the advect() mode of the reference's liquid scene scripts, scene/liquid3_vis.py:47-148,

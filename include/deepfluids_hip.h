@@ -567,6 +567,87 @@ int df_particle_levelset_union2d(const float* pos_sorted, const int32_t* cell_st
 int df_particle_levelset_union3d(const float* pos_sorted, const int32_t* cell_start, float* phi, int64_t B, int64_t N, int64_t Z, int64_t Y,
                                  int64_t X, float radius_factor, df_stream_t stream);
 
+/* ---- the smoke solver step: the main() loop of the reference's default 2-D scene (scene/smoke_pos_size.py:186-195), a closed box
+ * (open_bound=False):  source.applyToGrid, advectSemiLagrange(vel, density), advectSemiLagrange(vel, vel), setWallBcs, addBuoyancy,
+ * solvePressure(cgAccuracy, cgMaxIterFac), setWallBcs.  The first two statements are df_density_source and df_advect_* above; the
+ * rest is below.  mantaflow cannot be run beside this library, so bit parity with it is NOT claimed: the definition below is the
+ * contract (tests/smoke_ref.py restates it).  Left out: open bounds, obstacles, outflow, the MIC(0) preconditioner.
+ *
+ * Layouts as for df_advect_*: density, pressure [B,(Z,)Y,X]; velocity [B,(Z,)Y,X,D], D = 2 | 3 MAC face values, component a of cell c
+ * on c's low-a face; cell (i,j,k) is [..,k,j,i]; e_a the unit step along axis a.  A cell is interior when bnd <= index < extent - bnd
+ * on every axis, else a wall cell; bnd >= 1 and every extent >= 2*bnd + 2.  Velocities are in cells per unit time (no vel_scale).  All
+ * arithmetic fp32, no fused multiply-add, in the order written.
+ *
+ * 1. MAC self-advection (SemiLagrangeMAC / MacCormackCorrectMAC / the MAC clamp).  For component a of an interior cell c
+ *      uface_a(c)[a] = vel[c][a];  uface_a(c)[b] = 0.25 * (((vel[c][b] + vel[c-e_a][b]) + vel[c+e_b][b]) + vel[c-e_a+e_b][b]), b != a
+ *      fwd[c][a]     = interp(vel[..,a], centre(c) - dt*uface_a(c)), centre = (i+.5, j+.5[, k+.5]);  wall cells: 0 in every component
+ *    interp is the rule of df_advect_* (q = p - 0.5 on EVERY axis, the same edge cases, s0*a + s1*b per axis, x innermost) applied to
+ *    the one component as a cell-centred grid.  df_mac_advect_sl* is this, the whole step of order 1.
+ *    df_mac_advect_mc* is the second half of order 2, one pass, neither bwd nor cor is stored:  where c and c - e_a are both interior
+ *      bwd = interp(fwd[..,a], centre(c) + dt*uface_a(c)),  cor = fwd[c][a] + 0.5 * (vel[c][a] - bwd)
+ *    and the clamp of df_advect_mc* per component with dt*uface_a in place of dt*uc: min / max of vel[..,a] over the interior cells among
+ *    the corners of clamp(trunc((i,j,k) - dt*uface_a), 0, extent - 2) (clamp_mode 1: and of ... + dt*uface_a); none interior -> fwd;
+ *    clamp_mode 2: fwd if cor < min or cor > max, else cor; clamp_mode 1: clamp(cor, min, max).  Elsewhere in interior cells out = fwd;
+ *    wall cells 0.  Both gather: the output must not alias an input.
+ * 2. Walls and buoyancy, df_wall_buoyancy*: component a of cell c is kept where c and c - e_a are both interior, else it is 0 (for a
+ *    closed box this is setWallBcs).  Kept: out = vel[c][a] + (0.5 * force[a]) * (rho[c] + rho[c-e_a]).  out may be vel.  mantaflow's
+ *    addBuoyancy uses force = -gravity * dt / dx; the drivers in ops.py default to dx = 1 / max(extent), restated from memory and not
+ *    checked against mantaflow.
+ * 3. Pressure projection.  On interior cells b[c] = -(((vel[c+e_x][x] - vel[c][x]) + (vel[c+e_y][y] - vel[c][y])) [+ (.. z ..)]) and
+ *    (A x)[c] = n_c * x[c] - (sum of x over the interior neighbours, in the order x-, x+, y-, y+, z-, z+), n_c their number.  A is
+ *    singular (constants); the system is consistent when the wall faces of vel are 0, as after step 2 (the b then sum to zero).
+ *    Plain conjugate gradients from x = 0, per batch entry:  r = p = b, rr = r.r;  an entry stops, and is frozen from then on, when
+ *    max|r| <= accuracy, when rr is not > 0, or after max_iter iterations;  else  beta = rr / rr_old (0 in the first iteration),
+ *    p = r + beta*p, q = A p, alpha = rr / p.q (0 if p.q is not > 0), x = x + alpha*p, r = r - alpha*q.  An entry with b = 0 stops at
+ *    iteration 0 with x = 0; nothing divides 0 by 0.  Dot products and max|r| are sums of one partial per workgroup of 256 consecutive
+ *    cells of ONE entry (inside it: xor butterfly over the 64 lanes, then the 4 waves ascending), combined by 256 strided running sums
+ *    and the same tree: the order depends on the extents alone, so an entry's result does not depend on the rest of the batch, and two
+ *    runs agree bit for bit.  No floating-point atomics.
+ *    mantaflow preconditions its CG with MIC(0), a sequential sweep; this solver does not.  Both stop at the same criterion, so the
+ *    projected fields agree to the accuracy of the solve and not beyond.
+ *      df_pressure_workspace_bytes(B, Z, Y, X)  (Z = 1 in 2-D) the caller's scratch: r, two p, q, partials, per-entry scalars
+ *      df_pressure_init*          b, r = p = b, pressure = 0, first partials
+ *      df_pressure_cg_direction*  iteration k = 0, 1, ..: the entry's decision, then p, q and the p.q partials     (launch 1)
+ *      df_pressure_cg_update*     iteration k: alpha, x and r updates, the r.r and max|r| partials                    (launch 2)
+ *      df_pressure_status         after direction(k): *active_count = entries still iterating, iterations[e] = updates entry e has
+ *                                 been given (either pointer may be null; device pointers to int32)
+ *      df_pressure_correct*       out[c][a] = vel[c][a] - (p[c] - p[c-e_a]) where c and c - e_a are interior, else 0 (the second
+ *                                 setWallBcs); out may be vel.
+ *    The caller runs init, then direction(k), update(k) for k = 0, 1, .. with the SAME accuracy and max_iter until status reports no
+ *    active entry -- which direction(max_iter) guarantees -- and then correct.  Calls after an entry froze leave it untouched, so the
+ *    result does not depend on how often the caller looks.
+ * Errors: DF_EINVAL null pointer / non-positive extent / bnd < 1 / clamp_mode not 1 | 2 / negative k, max_iter or accuracy / an output
+ * aliasing an array that is read at a neighbour / the workspace overlapping the velocity, the pressure or an int32 output, DF_ESHAPE an extent < 2*bnd + 2 or too large, DF_EALIGN a pointer not 4-byte
+ * aligned, DF_EWORKSPACE ws_bytes below df_pressure_workspace_bytes (which itself returns a negative DF_E* code for bad extents). */
+int df_mac_advect_sl2d(const float* vel, float* fwd, int64_t B, int64_t Y, int64_t X, float dt, int bnd, df_stream_t stream);
+int df_mac_advect_sl3d(const float* vel, float* fwd, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt, int bnd, df_stream_t stream);
+int df_mac_advect_mc2d(const float* vel, const float* fwd, float* out, int64_t B, int64_t Y, int64_t X, float dt, int bnd, int clamp_mode,
+                       df_stream_t stream);
+int df_mac_advect_mc3d(const float* vel, const float* fwd, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt, int bnd,
+                       int clamp_mode, df_stream_t stream);
+int df_wall_buoyancy2d(const float* vel, const float* density, float* out, int64_t B, int64_t Y, int64_t X, float fx, float fy, int bnd,
+                       df_stream_t stream);
+int df_wall_buoyancy3d(const float* vel, const float* density, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, float fx, float fy,
+                       float fz, int bnd, df_stream_t stream);
+int64_t df_pressure_workspace_bytes(int64_t B, int64_t Z, int64_t Y, int64_t X);
+int df_pressure_init2d(const float* vel, float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int64_t X, int bnd,
+                       df_stream_t stream);
+int df_pressure_init3d(const float* vel, float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                       df_stream_t stream);
+int df_pressure_cg_direction2d(void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k, float accuracy,
+                               int64_t max_iter, df_stream_t stream);
+int df_pressure_cg_direction3d(void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k, float accuracy,
+                               int64_t max_iter, df_stream_t stream);
+int df_pressure_cg_update2d(float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k,
+                            df_stream_t stream);
+int df_pressure_cg_update3d(float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k,
+                            df_stream_t stream);
+int df_pressure_status(const void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int64_t k, int32_t* active_count,
+                       int32_t* iterations, df_stream_t stream);
+int df_pressure_correct2d(const float* vel, const float* pressure, float* out, int64_t B, int64_t Y, int64_t X, int bnd, df_stream_t stream);
+int df_pressure_correct3d(const float* vel, const float* pressure, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                          df_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
