@@ -73,14 +73,18 @@ __global__ __launch_bounds__(kThreads) void advect_sl_kernel(const float* __rest
   fwd[idx] = r;
 }
 
-template <int D, int MODE>
+// MASKED (df_advect_mc*_flags): the correction and the clamp where the cell is fluid, over fluid corners; other interior cells keep fwd
+template <int D, int MODE, bool MASKED>
 __global__ __launch_bounds__(kThreads) void advect_mc_kernel(const float* __restrict__ orig, const float* __restrict__ fwd,
-                                                             const float* __restrict__ vel, float* __restrict__ out, AdvDims d) {
+                                                             const float* __restrict__ vel, float* __restrict__ out,
+                                                             const uint8_t* __restrict__ flags, AdvDims d) {
   const int64_t idx = xcd_block(blockIdx.x, gridDim.x, 0) * kThreads + threadIdx.x;
   if (idx >= d.ncell) return;
   const Cell<D> c = decode<D>(idx, d);
   float r = 0.0f;
-  if (c.interior) {
+  if (MASKED && c.interior && !(flags[idx] & dfadv::kFluid)) {
+    r = fwd[idx];
+  } else if (c.interior) {
     float du[3], pos[3], t[3];
     displacement<D>(vel, c, d, du);
 #pragma unroll
@@ -92,11 +96,12 @@ __global__ __launch_bounds__(kThreads) void advect_mc_kernel(const float* __rest
     bool found = false;
 #pragma unroll
     for (int a = 0; a < D; ++a) t[a] = static_cast<float>(c.p[a]) - du[a];
-    corner_range<D>(orig + c.base, t, d, mn, mx, found);
+    const uint8_t* fl = MASKED ? flags + c.base : nullptr;
+    corner_range<D, 1, MASKED>(orig + c.base, t, d, mn, mx, found, fl);
     if (MODE == 1) {
 #pragma unroll
       for (int a = 0; a < D; ++a) t[a] = static_cast<float>(c.p[a]) + du[a];
-      corner_range<D>(orig + c.base, t, d, mn, mx, found);
+      corner_range<D, 1, MASKED>(orig + c.base, t, d, mn, mx, found, fl);
     }
     if (!found) r = f;
     else if (MODE == 2) r = (cor < mn || cor > mx) ? f : cor;
@@ -175,19 +180,20 @@ int advect_sl(const char* fn, const float* density, const float* vel, float* fwd
   return df::launched(fn);
 }
 
-template <int D>
-int advect_mc(const char* fn, const float* orig, const float* fwd, const float* vel, float* out, int64_t B, int64_t Z, int64_t Y,
-              int64_t X, float dt, float vel_scale, int bnd, int clamp_mode, df_stream_t stream) {
+template <int D, bool MASKED>
+int advect_mc(const char* fn, const float* orig, const float* fwd, const float* vel, float* out, const uint8_t* flags, int64_t B, int64_t Z,
+              int64_t Y, int64_t X, float dt, float vel_scale, int bnd, int clamp_mode, df_stream_t stream) {
   DF_REQUIRE(orig && fwd && vel && out, DF_EINVAL, "%s: null %s", fn, !orig || !fwd ? "input" : !vel ? "velocity" : "output");
   DF_REQUIRE(clamp_mode == 1 || clamp_mode == 2, DF_EINVAL, "%s: clamp_mode must be 1 or 2 (got %d)", fn, clamp_mode);
   AdvDims d;
   unsigned nblk;
   if (int e = plan(fn, D, B, Z, Y, X, bnd, dt, vel_scale, &d, &nblk)) return e;
   DF_REQUIRE(out != orig && out != fwd, DF_EINVAL, "%s: the output must not be an input (the step gathers)", fn);
+  if (int e = dfadv::check_flags<MASKED>(fn, flags, d.ncell, out, 4 * d.ncell, "output")) return e;
   DF_REQUIRE(aligned4(orig) && aligned4(fwd) && aligned4(vel) && aligned4(out), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
   hipStream_t s = df::as_stream(stream);
-  if (clamp_mode == 2) hipLaunchKernelGGL((advect_mc_kernel<D, 2>), dim3(nblk), dim3(kThreads), 0, s, orig, fwd, vel, out, d);
-  else hipLaunchKernelGGL((advect_mc_kernel<D, 1>), dim3(nblk), dim3(kThreads), 0, s, orig, fwd, vel, out, d);
+  if (clamp_mode == 2) hipLaunchKernelGGL((advect_mc_kernel<D, 2, MASKED>), dim3(nblk), dim3(kThreads), 0, s, orig, fwd, vel, out, flags, d);
+  else hipLaunchKernelGGL((advect_mc_kernel<D, 1, MASKED>), dim3(nblk), dim3(kThreads), 0, s, orig, fwd, vel, out, flags, d);
   return df::launched(fn);
 }
 
@@ -223,12 +229,22 @@ int df_advect_sl3d(const float* density, const float* vel, float* fwd, int64_t B
 
 int df_advect_mc2d(const float* orig, const float* fwd, const float* vel, float* out, int64_t B, int64_t Y, int64_t X, float dt,
                    float vel_scale, int bnd, int clamp_mode, df_stream_t stream) {
-  return advect_mc<2>("df_advect_mc2d", orig, fwd, vel, out, B, 1, Y, X, dt, vel_scale, bnd, clamp_mode, stream);
+  return advect_mc<2, false>("df_advect_mc2d", orig, fwd, vel, out, nullptr, B, 1, Y, X, dt, vel_scale, bnd, clamp_mode, stream);
 }
 
 int df_advect_mc3d(const float* orig, const float* fwd, const float* vel, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt,
                    float vel_scale, int bnd, int clamp_mode, df_stream_t stream) {
-  return advect_mc<3>("df_advect_mc3d", orig, fwd, vel, out, B, Z, Y, X, dt, vel_scale, bnd, clamp_mode, stream);
+  return advect_mc<3, false>("df_advect_mc3d", orig, fwd, vel, out, nullptr, B, Z, Y, X, dt, vel_scale, bnd, clamp_mode, stream);
+}
+
+int df_advect_mc2d_flags(const float* orig, const float* fwd, const float* vel, float* out, const uint8_t* flags, int64_t B, int64_t Y,
+                         int64_t X, float dt, float vel_scale, int bnd, int clamp_mode, df_stream_t stream) {
+  return advect_mc<2, true>("df_advect_mc2d_flags", orig, fwd, vel, out, flags, B, 1, Y, X, dt, vel_scale, bnd, clamp_mode, stream);
+}
+
+int df_advect_mc3d_flags(const float* orig, const float* fwd, const float* vel, float* out, const uint8_t* flags, int64_t B, int64_t Z,
+                         int64_t Y, int64_t X, float dt, float vel_scale, int bnd, int clamp_mode, df_stream_t stream) {
+  return advect_mc<3, true>("df_advect_mc3d_flags", orig, fwd, vel, out, flags, B, Z, Y, X, dt, vel_scale, bnd, clamp_mode, stream);
 }
 
 int df_density_source(const float* density, const uint8_t* mask, float value, float* out, int64_t n, df_stream_t stream) {

@@ -4,6 +4,7 @@
 #ifndef DF_ADVECT_COMMON_HPP
 #define DF_ADVECT_COMMON_HPP
 #include <cmath>
+#include <cstdint>
 
 #include "df_common.hpp"
 
@@ -74,9 +75,17 @@ __device__ __forceinline__ float interp(const float* __restrict__ g, const float
   return s0[2] * r0 + s1[2] * r1;
 }
 
-// min / max of orig over the interior corners c, c+1 of the integer cell c = clamp(trunc(t), 0, ext - 2) per axis
-template <int D, int S = 1>
-__device__ __forceinline__ void corner_range(const float* __restrict__ g, const float* t, const AdvDims& d, float& mn, float& mx, bool& found) {
+// The obstacle flags of df_obstacle_flags*: one byte per cell, bit 0 = the cell is fluid (interior and no obstacle), bits 1-6 = its x-, x+,
+// y-, y+, z-, z+ neighbour is fluid.  Component a of cell c is a kept face when c and c - e_a are both fluid.
+constexpr unsigned kFluid = 1u;
+__device__ __forceinline__ unsigned lo_bit(int a) { return 2u << (2 * a); }
+__device__ __forceinline__ unsigned hi_bit(int a) { return 4u << (2 * a); }
+
+// min / max of orig over the interior corners c, c+1 of the integer cell c = clamp(trunc(t), 0, ext - 2) per axis; with MASKED only
+// those of them that are fluid (fl: the flags of this batch entry)
+template <int D, int S = 1, bool MASKED = false>
+__device__ __forceinline__ void corner_range(const float* __restrict__ g, const float* t, const AdvDims& d, float& mn, float& mx, bool& found,
+                                             const uint8_t* __restrict__ fl = nullptr) {
   const int ext[3] = {d.X, d.Y, d.Z};
   int c[3] = {0, 0, 0};
 #pragma unroll
@@ -88,14 +97,31 @@ __device__ __forceinline__ void corner_range(const float* __restrict__ g, const 
 #pragma unroll
       for (int dx = 0; dx < 2; ++dx) {
         const int x = c[0] + dx, y = c[1] + dy, z = c[2] + dz;
-        const bool in = x >= d.bnd && x < d.X - d.bnd && y >= d.bnd && y < d.Y - d.bnd && (D == 2 || (z >= d.bnd && z < d.Z - d.bnd));
+        bool in = x >= d.bnd && x < d.X - d.bnd && y >= d.bnd && y < d.Y - d.bnd && (D == 2 || (z >= d.bnd && z < d.Z - d.bnd));
+        const int64_t at = (static_cast<int64_t>(z) * d.Y + y) * d.X + x;
+        if (MASKED) in = in && (fl[at] & kFluid);
         if (in) {
-          const float v = g[((static_cast<int64_t>(z) * d.Y + y) * d.X + x) * S];
+          const float v = g[at * S];
           mn = found ? fminf(mn, v) : v;
           mx = found ? fmaxf(mx, v) : v;
           found = true;
         }
       }
+}
+
+// host side of the `_flags` entry points: two byte ranges share no byte
+inline bool apart(const void* p, int64_t np, const void* q, int64_t nq) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return a + static_cast<uintptr_t>(np) <= b || b + static_cast<uintptr_t>(nq) <= a;
+}
+
+// the flags of a `_flags` entry point: present, and sharing no byte with an array the launch writes (`out` may be null: none)
+template <bool MASKED>
+int check_flags(const char* fn, const uint8_t* flags, int64_t ncell, const void* out, int64_t out_bytes, const char* what) {
+  if (!MASKED) return DF_OK;
+  DF_REQUIRE(flags, DF_EINVAL, "%s: null flags", fn);
+  DF_REQUIRE(!out || apart(flags, ncell, out, out_bytes), DF_EINVAL, "%s: the flags overlap the %s", fn, what);
+  return DF_OK;
 }
 
 }  // namespace dfadv

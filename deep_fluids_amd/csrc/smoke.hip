@@ -19,6 +19,12 @@
 //   The grids of one entry at the sizes this is used for (96x128: 48 KiB per array) live in L2; the XCD remap hands each XCD a contiguous
 //   run of workgroups, so an entry's neighbours in y and z are on the same L2.
 //
+//   obstacles         the `_flags` entry points are the same kernels with MASKED set: "interior" reads "fluid" (interior and no obstacle),
+//                     taken from ONE byte per cell that obstacle_flags packs once per sequence (the cell is fluid, each of its six
+//                     neighbours is fluid): n_c is a popcount, the stencil's neighbour loads are predicated on the bits.  A flags byte is
+//                     only believed where the cell is interior by its index, so no flags array can send a load outside the arrays.
+//                     With an all-zero obstacle every branch is taken as without flags: the same bits.
+//
 // Float -> int conversions are taken only of values already known to be inside the grid (advect_common.hpp).
 #include "advect_common.hpp"
 #include "df_common.hpp"
@@ -28,10 +34,15 @@ namespace {
 
 using df::ceil_div;
 using dfadv::AdvDims;
+using dfadv::apart;
 using dfadv::Cell;
+using dfadv::check_flags;
 using dfadv::corner_range;
 using dfadv::decode;
+using dfadv::hi_bit;
 using dfadv::interp;
+using dfadv::kFluid;
+using dfadv::lo_bit;
 using dfst::kThreads;
 using dfst::xcd_block;
 
@@ -71,12 +82,21 @@ __global__ __launch_bounds__(kThreads) void mac_sl_kernel(const float* __restric
   *reinterpret_cast<VelRec<D>*>(fwd + idx * D) = r;
 }
 
-template <int D, int MODE>
+// component a of cell c is a kept face: c and c - e_a are both interior (MASKED: fluid, read from the cell's flags byte)
+template <bool MASKED>
+__device__ __forceinline__ bool kept_face(bool interior, int pa, int bnd, unsigned fl, int a) {
+  if (MASKED) return interior && (fl & kFluid) && (fl & lo_bit(a));
+  return interior && pa > bnd;
+}
+
+template <int D, int MODE, bool MASKED>
 __global__ __launch_bounds__(kThreads) void mac_mc_kernel(const float* __restrict__ orig, const float* __restrict__ fwd,
-                                                          float* __restrict__ out, AdvDims d) {
+                                                          float* __restrict__ out, const uint8_t* __restrict__ flags, AdvDims d) {
   const int64_t idx = xcd_block(blockIdx.x, gridDim.x, 0) * kThreads + threadIdx.x;
   if (idx >= d.ncell) return;
   const Cell<D> c = decode<D>(idx, d);
+  const unsigned fl = MASKED ? flags[idx] : 0u;
+  const uint8_t* efl = MASKED ? flags + c.base : nullptr;
   VelRec<D> r;
 #pragma unroll
   for (int a = 0; a < D; ++a) {
@@ -84,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void mac_mc_kernel(const float* __restric
     if (c.interior) {
       const float f = fwd[idx * D + a];
       r.v[a] = f;
-      if (c.p[a] > d.bnd) {                            // c - e_a is interior too
+      if (kept_face<MASKED>(true, c.p[a], d.bnd, fl, a)) {   // c - e_a is interior (MASKED: fluid) too
         float du[3], pos[3], t[3];
         face_displacement<D>(orig, c, d, a, du);
 #pragma unroll
@@ -95,11 +115,11 @@ __global__ __launch_bounds__(kThreads) void mac_mc_kernel(const float* __restric
         bool found = false;
 #pragma unroll
         for (int b = 0; b < D; ++b) t[b] = static_cast<float>(c.p[b]) - du[b];
-        corner_range<D, D>(orig + c.base * D + a, t, d, mn, mx, found);
+        corner_range<D, D, MASKED>(orig + c.base * D + a, t, d, mn, mx, found, efl);
         if (MODE == 1) {
 #pragma unroll
           for (int b = 0; b < D; ++b) t[b] = static_cast<float>(c.p[b]) + du[b];
-          corner_range<D, D>(orig + c.base * D + a, t, d, mn, mx, found);
+          corner_range<D, D, MASKED>(orig + c.base * D + a, t, d, mn, mx, found, efl);
         }
         if (!found) r.v[a] = f;
         else if (MODE == 2) r.v[a] = (cor < mn || cor > mx) ? f : cor;
@@ -110,22 +130,48 @@ __global__ __launch_bounds__(kThreads) void mac_mc_kernel(const float* __restric
   *reinterpret_cast<VelRec<D>*>(out + idx * D) = r;
 }
 
-// ---- walls and buoyancy --------------------------------------------------------------------------------------------------------------------
-struct Force { float f[3]; };
-
+// ---- obstacle flags --------------------------------------------------------------------------------------------------------------------------
+// one byte per cell: bit 0 = the cell is fluid, bits 1-6 = its x-, x+, y-, y+, z-, z+ neighbour is (a neighbour outside the grid is not)
 template <int D>
-__global__ __launch_bounds__(kThreads) void wall_buoyancy_kernel(const float* vel, const float* __restrict__ rho, float* out, Force force,
-                                                                 AdvDims d) {
+__global__ __launch_bounds__(kThreads) void obstacle_flags_kernel(const uint8_t* __restrict__ obs, uint8_t* __restrict__ flags, AdvDims d) {
   const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
   if (idx >= d.ncell) return;
   const Cell<D> c = decode<D>(idx, d);
+  const int64_t st[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
+  const int ext[3] = {d.X, d.Y, d.Z};
+  bool in[3] = {true, true, true};
+#pragma unroll
+  for (int a = 0; a < D; ++a) in[a] = c.p[a] >= d.bnd && c.p[a] < ext[a] - d.bnd;
+  unsigned f = (c.interior && !obs[idx]) ? kFluid : 0u;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    bool rest = true;                                   // the neighbours along a share the cell's other coordinates
+#pragma unroll
+    for (int b = 0; b < D; ++b) if (b != a) rest = rest && in[b];
+    // bnd >= 1: a neighbour whose index passes the interior test is inside the grid
+    if (rest && c.p[a] - 1 >= d.bnd && c.p[a] - 1 < ext[a] - d.bnd && !obs[idx - st[a]]) f |= lo_bit(a);
+    if (rest && c.p[a] + 1 >= d.bnd && c.p[a] + 1 < ext[a] - d.bnd && !obs[idx + st[a]]) f |= hi_bit(a);
+  }
+  flags[idx] = static_cast<uint8_t>(f);
+}
+
+// ---- walls and buoyancy --------------------------------------------------------------------------------------------------------------------
+struct Force { float f[3]; };
+
+template <int D, bool MASKED>
+__global__ __launch_bounds__(kThreads) void wall_buoyancy_kernel(const float* vel, const float* __restrict__ rho, float* out,
+                                                                 const uint8_t* __restrict__ flags, Force force, AdvDims d) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (idx >= d.ncell) return;
+  const Cell<D> c = decode<D>(idx, d);
+  const unsigned fl = MASKED ? flags[idx] : 0u;
   const int64_t st[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
   const VelRec<D> v = *reinterpret_cast<const VelRec<D>*>(vel + idx * D);
   VelRec<D> r;
 #pragma unroll
   for (int a = 0; a < D; ++a) {
     r.v[a] = 0.0f;
-    if (c.interior && c.p[a] > d.bnd) r.v[a] = v.v[a] + (0.5f * force.f[a]) * (rho[idx] + rho[idx - st[a]]);
+    if (kept_face<MASKED>(c.interior, c.p[a], d.bnd, fl, a)) r.v[a] = v.v[a] + (0.5f * force.f[a]) * (rho[idx] + rho[idx - st[a]]);
   }
   *reinterpret_cast<VelRec<D>*>(out + idx * D) = r;
 }
@@ -147,11 +193,12 @@ struct PCell {
   int e;           // batch entry
   int j;           // workgroup inside the entry
   int p[3];
-  bool interior;
+  bool interior;   // MASKED: fluid
+  unsigned fl;     // MASKED: the flags byte of a fluid cell, else 0
 };
 
-template <int D>
-__device__ __forceinline__ PCell pdecode(const PDims& d) {
+template <int D, bool MASKED = false>
+__device__ __forceinline__ PCell pdecode(const PDims& d, const uint8_t* __restrict__ flags = nullptr) {
   PCell c;
   const int64_t logical = xcd_block(blockIdx.x, gridDim.x, 0);
   c.e = static_cast<int>(logical / d.nblk);
@@ -163,6 +210,12 @@ __device__ __forceinline__ PCell pdecode(const PDims& d) {
   c.p[2] = D == 3 ? static_cast<int>(row / d.Y) : 0;
   c.interior = c.cell < d.n && c.p[0] >= d.bnd && c.p[0] < d.X - d.bnd && c.p[1] >= d.bnd && c.p[1] < d.Y - d.bnd &&
                (D == 2 || (c.p[2] >= d.bnd && c.p[2] < d.Z - d.bnd));
+  c.fl = 0u;
+  if (MASKED) {
+    if (c.interior) c.fl = flags[static_cast<int64_t>(c.e) * d.n + c.cell];
+    c.interior = (c.fl & kFluid) != 0u;
+    if (!c.interior) c.fl = 0u;
+  }
   return c;
 }
 
@@ -207,10 +260,11 @@ PWs carve(void* ws, int64_t B, int64_t n, int64_t nblk) {
   return w;
 }
 
-template <int D>
-__global__ __launch_bounds__(kThreads) void pressure_init_kernel(const float* __restrict__ vel, float* __restrict__ x, PWs w, PDims d) {
+template <int D, bool MASKED>
+__global__ __launch_bounds__(kThreads) void pressure_init_kernel(const float* __restrict__ vel, float* __restrict__ x,
+                                                                 const uint8_t* __restrict__ flags, PWs w, PDims d) {
   __shared__ float lds[4];
-  const PCell c = pdecode<D>(d);
+  const PCell c = pdecode<D, MASKED>(d, flags);
   const int64_t g = static_cast<int64_t>(c.e) * d.n + c.cell;
   float b = 0.0f;
   if (c.interior) {
@@ -232,10 +286,11 @@ __global__ __launch_bounds__(kThreads) void pressure_init_kernel(const float* __
   }
 }
 
-template <int D>
-__global__ __launch_bounds__(kThreads) void cg_direction_kernel(PWs w, PDims d, int par, int first, float accuracy, int max_iter) {
+template <int D, bool MASKED>
+__global__ __launch_bounds__(kThreads) void cg_direction_kernel(PWs w, const uint8_t* __restrict__ flags, PDims d, int par, int first,
+                                                                float accuracy, int max_iter) {
   __shared__ float lds[4];
-  const PCell c = pdecode<D>(d);
+  const PCell c = pdecode<D, MASKED>(d, flags);
   const bool writer = c.j == 0 && threadIdx.x == 0;
   CgState s;
   if (first) s = CgState{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1, 0, 0};
@@ -263,9 +318,12 @@ __global__ __launch_bounds__(kThreads) void cg_direction_kernel(PWs w, PDims d, 
     int cnt = 0;
 #pragma unroll
     for (int a = 0; a < D; ++a) {
-      if (c.p[a] > d.bnd) { const int64_t nb = c.cell - st[a]; sum += r[nb] + beta * po_[nb]; ++cnt; }
-      if (c.p[a] + 1 < ext[a] - d.bnd) { const int64_t nb = c.cell + st[a]; sum += r[nb] + beta * po_[nb]; ++cnt; }
+      const bool lo = MASKED ? (c.fl & lo_bit(a)) != 0u : c.p[a] > d.bnd;
+      const bool hi = MASKED ? (c.fl & hi_bit(a)) != 0u : c.p[a] + 1 < ext[a] - d.bnd;
+      if (lo) { const int64_t nb = c.cell - st[a]; sum += r[nb] + beta * po_[nb]; if (!MASKED) ++cnt; }
+      if (hi) { const int64_t nb = c.cell + st[a]; sum += r[nb] + beta * po_[nb]; if (!MASKED) ++cnt; }
     }
+    if (MASKED) cnt = __popc((c.fl >> 1) & ((1u << (2 * D)) - 1u));   // n_c: the neighbour bits of the D axes, those the loop visited
     const float qv = static_cast<float>(cnt) * pc - sum;
     w.p[par ^ 1][eo + c.cell] = pc;
     w.q[eo + c.cell] = qv;
@@ -275,10 +333,10 @@ __global__ __launch_bounds__(kThreads) void cg_direction_kernel(PWs w, PDims d, 
   if (threadIdx.x == 0) w.pq_part[po + c.j] = pq;
 }
 
-template <int D>
-__global__ __launch_bounds__(kThreads) void cg_update_kernel(float* __restrict__ x, PWs w, PDims d, int par) {
+template <int D, bool MASKED>
+__global__ __launch_bounds__(kThreads) void cg_update_kernel(float* __restrict__ x, PWs w, const uint8_t* __restrict__ flags, PDims d, int par) {
   __shared__ float lds[4];
-  const PCell c = pdecode<D>(d);
+  const PCell c = pdecode<D, MASKED>(d, flags);
   CgState* s = w.state[par ^ 1] + c.e;                  // what direction(k) has just written
   if (!s->active) return;
   const float rr_old = s->rr;
@@ -316,18 +374,20 @@ __global__ __launch_bounds__(kThreads) void cg_status_kernel(const CgState* __re
   if (threadIdx.x == 0 && count) count[0] = lds[0] + lds[1] + lds[2] + lds[3];
 }
 
-template <int D>
-__global__ __launch_bounds__(kThreads) void pressure_correct_kernel(const float* vel, const float* __restrict__ pr, float* out, AdvDims d) {
+template <int D, bool MASKED>
+__global__ __launch_bounds__(kThreads) void pressure_correct_kernel(const float* vel, const float* __restrict__ pr, float* out,
+                                                                    const uint8_t* __restrict__ flags, AdvDims d) {
   const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
   if (idx >= d.ncell) return;
   const Cell<D> c = decode<D>(idx, d);
+  const unsigned fl = MASKED ? flags[idx] : 0u;
   const int64_t st[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
   const VelRec<D> v = *reinterpret_cast<const VelRec<D>*>(vel + idx * D);
   VelRec<D> r;
 #pragma unroll
   for (int a = 0; a < D; ++a) {
     r.v[a] = 0.0f;
-    if (c.interior && c.p[a] > d.bnd) r.v[a] = v.v[a] - (pr[idx] - pr[idx - st[a]]);
+    if (kept_face<MASKED>(c.interior, c.p[a], d.bnd, fl, a)) r.v[a] = v.v[a] - (pr[idx] - pr[idx - st[a]]);
   }
   *reinterpret_cast<VelRec<D>*>(out + idx * D) = r;
 }
@@ -384,6 +444,18 @@ int check_apart(const char* fn, const void* ws, const PDims& d, const void* p, i
 }
 
 template <int D>
+int obstacle_flags(const char* fn, const uint8_t* obstacle, uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                   df_stream_t stream) {
+  DF_REQUIRE(obstacle && flags, DF_EINVAL, "%s: null %s", fn, !obstacle ? "obstacle" : "flags");
+  AdvDims d;
+  unsigned nblk;
+  if (int e = plan(fn, D, B, Z, Y, X, bnd, 0.0f, &d, &nblk)) return e;
+  DF_REQUIRE(apart(obstacle, d.ncell, flags, d.ncell), DF_EINVAL, "%s: the flags overlap the obstacle (it is read at a neighbour)", fn);
+  hipLaunchKernelGGL((obstacle_flags_kernel<D>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), obstacle, flags, d);
+  return df::launched(fn);
+}
+
+template <int D>
 int mac_sl(const char* fn, const float* vel, float* fwd, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt, int bnd, df_stream_t stream) {
   DF_REQUIRE(vel && fwd, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : "output");
   AdvDims d;
@@ -395,39 +467,41 @@ int mac_sl(const char* fn, const float* vel, float* fwd, int64_t B, int64_t Z, i
   return df::launched(fn);
 }
 
-template <int D>
-int mac_mc(const char* fn, const float* vel, const float* fwd, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt, int bnd,
-           int clamp_mode, df_stream_t stream) {
+template <int D, bool MASKED>
+int mac_mc(const char* fn, const float* vel, const float* fwd, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X,
+           float dt, int bnd, int clamp_mode, df_stream_t stream) {
   DF_REQUIRE(vel && fwd && out, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : !fwd ? "input" : "output");
   DF_REQUIRE(clamp_mode == 1 || clamp_mode == 2, DF_EINVAL, "%s: clamp_mode must be 1 or 2 (got %d)", fn, clamp_mode);
   AdvDims d;
   unsigned nblk;
   if (int e = plan(fn, D, B, Z, Y, X, bnd, dt, &d, &nblk)) return e;
   DF_REQUIRE(out != vel && out != fwd, DF_EINVAL, "%s: the output must not be an input (the step gathers)", fn);
+  if (int e = check_flags<MASKED>(fn, flags, d.ncell, out, 4 * d.ncell * D, "output")) return e;
   DF_REQUIRE(aligned4(vel) && aligned4(fwd) && aligned4(out), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
   hipStream_t s = df::as_stream(stream);
-  if (clamp_mode == 2) hipLaunchKernelGGL((mac_mc_kernel<D, 2>), dim3(nblk), dim3(kThreads), 0, s, vel, fwd, out, d);
-  else hipLaunchKernelGGL((mac_mc_kernel<D, 1>), dim3(nblk), dim3(kThreads), 0, s, vel, fwd, out, d);
+  if (clamp_mode == 2) hipLaunchKernelGGL((mac_mc_kernel<D, 2, MASKED>), dim3(nblk), dim3(kThreads), 0, s, vel, fwd, out, flags, d);
+  else hipLaunchKernelGGL((mac_mc_kernel<D, 1, MASKED>), dim3(nblk), dim3(kThreads), 0, s, vel, fwd, out, flags, d);
   return df::launched(fn);
 }
 
-template <int D>
-int wall_buoyancy(const char* fn, const float* vel, const float* rho, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, Force f, int bnd,
-                  df_stream_t stream) {
+template <int D, bool MASKED>
+int wall_buoyancy(const char* fn, const float* vel, const float* rho, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
+                  int64_t X, Force f, int bnd, df_stream_t stream) {
   DF_REQUIRE(vel && rho && out, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : !rho ? "density" : "output");
   AdvDims d;
   unsigned nblk;
   if (int e = plan(fn, D, B, Z, Y, X, bnd, 0.0f, &d, &nblk)) return e;
   DF_REQUIRE(static_cast<const void*>(out) != static_cast<const void*>(rho), DF_EINVAL,
              "%s: the output must not be the density (it is read at a neighbour)", fn);
+  if (int e = check_flags<MASKED>(fn, flags, d.ncell, out, 4 * d.ncell * D, "output")) return e;
   DF_REQUIRE(aligned4(vel) && aligned4(rho) && aligned4(out), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  hipLaunchKernelGGL((wall_buoyancy_kernel<D>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, rho, out, f, d);
+  hipLaunchKernelGGL((wall_buoyancy_kernel<D, MASKED>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, rho, out, flags, f, d);
   return df::launched(fn);
 }
 
-template <int D>
-int pressure_init(const char* fn, const float* vel, float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X,
-                  int bnd, df_stream_t stream) {
+template <int D, bool MASKED>
+int pressure_init(const char* fn, const float* vel, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z,
+                  int64_t Y, int64_t X, int bnd, df_stream_t stream) {
   DF_REQUIRE(vel && pressure, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : "pressure");
   PDims d;
   unsigned grid;
@@ -437,14 +511,17 @@ int pressure_init(const char* fn, const float* vel, float* pressure, void* ws, i
              "%s: the pressure must not be the velocity (it is read at a neighbour)", fn);
   if (int e = check_apart(fn, ws, d, vel, 4 * d.n * B * D, "velocity")) return e;
   if (int e = check_apart(fn, ws, d, pressure, 4 * d.n * B, "pressure")) return e;
+  if (int e = check_flags<MASKED>(fn, flags, d.n * B, pressure, 4 * d.n * B, "pressure")) return e;
+  if (MASKED) if (int e = check_apart(fn, ws, d, flags, d.n * B, "flags")) return e;
   DF_REQUIRE(aligned4(vel) && aligned4(pressure), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  hipLaunchKernelGGL((pressure_init_kernel<D>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), vel, pressure, carve(ws, B, d.n, d.nblk), d);
+  hipLaunchKernelGGL((pressure_init_kernel<D, MASKED>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), vel, pressure, flags,
+                     carve(ws, B, d.n, d.nblk), d);
   return df::launched(fn);
 }
 
-template <int D>
-int cg_direction(const char* fn, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k, float accuracy,
-                 int64_t max_iter, df_stream_t stream) {
+template <int D, bool MASKED>
+int cg_direction(const char* fn, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                 int64_t k, float accuracy, int64_t max_iter, df_stream_t stream) {
   PDims d;
   unsigned grid;
   if (int e = pplan(fn, D, B, Z, Y, X, bnd, &d, &grid)) return e;
@@ -452,14 +529,16 @@ int cg_direction(const char* fn, void* ws, int64_t ws_bytes, int64_t B, int64_t 
   DF_REQUIRE(k >= 0 && max_iter >= 0 && max_iter < (1ll << 31), DF_EINVAL, "%s: iteration %lld of at most %lld", fn, (long long)k,
              (long long)max_iter);
   DF_REQUIRE(accuracy >= 0.0f, DF_EINVAL, "%s: accuracy must be >= 0", fn);
-  hipLaunchKernelGGL((cg_direction_kernel<D>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), carve(ws, B, d.n, d.nblk), d, (int)(k & 1),
-                     k == 0 ? 1 : 0, accuracy, (int)max_iter);
+  if (int e = check_flags<MASKED>(fn, flags, d.n * B, nullptr, 0, "")) return e;
+  if (MASKED) if (int e = check_apart(fn, ws, d, flags, d.n * B, "flags")) return e;
+  hipLaunchKernelGGL((cg_direction_kernel<D, MASKED>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), carve(ws, B, d.n, d.nblk), flags, d,
+                     (int)(k & 1), k == 0 ? 1 : 0, accuracy, (int)max_iter);
   return df::launched(fn);
 }
 
-template <int D>
-int cg_update(const char* fn, float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k,
-              df_stream_t stream) {
+template <int D, bool MASKED>
+int cg_update(const char* fn, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X,
+              int bnd, int64_t k, df_stream_t stream) {
   DF_REQUIRE(pressure, DF_EINVAL, "%s: null pressure", fn);
   PDims d;
   unsigned grid;
@@ -467,23 +546,26 @@ int cg_update(const char* fn, float* pressure, void* ws, int64_t ws_bytes, int64
   if (int e = check_ws(fn, ws, ws_bytes, d)) return e;
   DF_REQUIRE(k >= 0, DF_EINVAL, "%s: iteration %lld", fn, (long long)k);
   if (int e = check_apart(fn, ws, d, pressure, 4 * d.n * B, "pressure")) return e;
+  if (int e = check_flags<MASKED>(fn, flags, d.n * B, pressure, 4 * d.n * B, "pressure")) return e;
+  if (MASKED) if (int e = check_apart(fn, ws, d, flags, d.n * B, "flags")) return e;
   DF_REQUIRE(aligned4(pressure), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  hipLaunchKernelGGL((cg_update_kernel<D>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), pressure, carve(ws, B, d.n, d.nblk), d,
-                     (int)(k & 1));
+  hipLaunchKernelGGL((cg_update_kernel<D, MASKED>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), pressure, carve(ws, B, d.n, d.nblk),
+                     flags, d, (int)(k & 1));
   return df::launched(fn);
 }
 
-template <int D>
-int pressure_correct(const char* fn, const float* vel, const float* pressure, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
-                     df_stream_t stream) {
+template <int D, bool MASKED>
+int pressure_correct(const char* fn, const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
+                     int64_t X, int bnd, df_stream_t stream) {
   DF_REQUIRE(vel && pressure && out, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : !pressure ? "pressure" : "output");
   AdvDims d;
   unsigned nblk;
   if (int e = plan(fn, D, B, Z, Y, X, bnd, 0.0f, &d, &nblk)) return e;
   DF_REQUIRE(static_cast<const void*>(out) != static_cast<const void*>(pressure), DF_EINVAL,
              "%s: the output must not be the pressure (it is read at a neighbour)", fn);
+  if (int e = check_flags<MASKED>(fn, flags, d.ncell, out, 4 * d.ncell * D, "output")) return e;
   DF_REQUIRE(aligned4(vel) && aligned4(pressure) && aligned4(out), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  hipLaunchKernelGGL((pressure_correct_kernel<D>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, pressure, out, d);
+  hipLaunchKernelGGL((pressure_correct_kernel<D, MASKED>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, pressure, out, flags, d);
   return df::launched(fn);
 }
 
@@ -499,20 +581,20 @@ int df_mac_advect_sl3d(const float* vel, float* fwd, int64_t B, int64_t Z, int64
 }
 int df_mac_advect_mc2d(const float* vel, const float* fwd, float* out, int64_t B, int64_t Y, int64_t X, float dt, int bnd, int clamp_mode,
                        df_stream_t stream) {
-  return mac_mc<2>("df_mac_advect_mc2d", vel, fwd, out, B, 1, Y, X, dt, bnd, clamp_mode, stream);
+  return mac_mc<2, false>("df_mac_advect_mc2d", vel, fwd, out, nullptr, B, 1, Y, X, dt, bnd, clamp_mode, stream);
 }
 int df_mac_advect_mc3d(const float* vel, const float* fwd, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt, int bnd,
                        int clamp_mode, df_stream_t stream) {
-  return mac_mc<3>("df_mac_advect_mc3d", vel, fwd, out, B, Z, Y, X, dt, bnd, clamp_mode, stream);
+  return mac_mc<3, false>("df_mac_advect_mc3d", vel, fwd, out, nullptr, B, Z, Y, X, dt, bnd, clamp_mode, stream);
 }
 
 int df_wall_buoyancy2d(const float* vel, const float* density, float* out, int64_t B, int64_t Y, int64_t X, float fx, float fy, int bnd,
                        df_stream_t stream) {
-  return wall_buoyancy<2>("df_wall_buoyancy2d", vel, density, out, B, 1, Y, X, Force{{fx, fy, 0.0f}}, bnd, stream);
+  return wall_buoyancy<2, false>("df_wall_buoyancy2d", vel, density, out, nullptr, B, 1, Y, X, Force{{fx, fy, 0.0f}}, bnd, stream);
 }
 int df_wall_buoyancy3d(const float* vel, const float* density, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, float fx, float fy,
                        float fz, int bnd, df_stream_t stream) {
-  return wall_buoyancy<3>("df_wall_buoyancy3d", vel, density, out, B, Z, Y, X, Force{{fx, fy, fz}}, bnd, stream);
+  return wall_buoyancy<3, false>("df_wall_buoyancy3d", vel, density, out, nullptr, B, Z, Y, X, Force{{fx, fy, fz}}, bnd, stream);
 }
 
 int64_t df_pressure_workspace_bytes(int64_t B, int64_t Z, int64_t Y, int64_t X) {
@@ -524,27 +606,27 @@ int64_t df_pressure_workspace_bytes(int64_t B, int64_t Z, int64_t Y, int64_t X) 
 
 int df_pressure_init2d(const float* vel, float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int64_t X, int bnd,
                        df_stream_t stream) {
-  return pressure_init<2>("df_pressure_init2d", vel, pressure, ws, ws_bytes, B, 1, Y, X, bnd, stream);
+  return pressure_init<2, false>("df_pressure_init2d", vel, pressure, ws, ws_bytes, nullptr, B, 1, Y, X, bnd, stream);
 }
 int df_pressure_init3d(const float* vel, float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
                        df_stream_t stream) {
-  return pressure_init<3>("df_pressure_init3d", vel, pressure, ws, ws_bytes, B, Z, Y, X, bnd, stream);
+  return pressure_init<3, false>("df_pressure_init3d", vel, pressure, ws, ws_bytes, nullptr, B, Z, Y, X, bnd, stream);
 }
 int df_pressure_cg_direction2d(void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k, float accuracy,
                                int64_t max_iter, df_stream_t stream) {
-  return cg_direction<2>("df_pressure_cg_direction2d", ws, ws_bytes, B, 1, Y, X, bnd, k, accuracy, max_iter, stream);
+  return cg_direction<2, false>("df_pressure_cg_direction2d", ws, ws_bytes, nullptr, B, 1, Y, X, bnd, k, accuracy, max_iter, stream);
 }
 int df_pressure_cg_direction3d(void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k, float accuracy,
                                int64_t max_iter, df_stream_t stream) {
-  return cg_direction<3>("df_pressure_cg_direction3d", ws, ws_bytes, B, Z, Y, X, bnd, k, accuracy, max_iter, stream);
+  return cg_direction<3, false>("df_pressure_cg_direction3d", ws, ws_bytes, nullptr, B, Z, Y, X, bnd, k, accuracy, max_iter, stream);
 }
 int df_pressure_cg_update2d(float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k,
                             df_stream_t stream) {
-  return cg_update<2>("df_pressure_cg_update2d", pressure, ws, ws_bytes, B, 1, Y, X, bnd, k, stream);
+  return cg_update<2, false>("df_pressure_cg_update2d", pressure, ws, ws_bytes, nullptr, B, 1, Y, X, bnd, k, stream);
 }
 int df_pressure_cg_update3d(float* pressure, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k,
                             df_stream_t stream) {
-  return cg_update<3>("df_pressure_cg_update3d", pressure, ws, ws_bytes, B, Z, Y, X, bnd, k, stream);
+  return cg_update<3, false>("df_pressure_cg_update3d", pressure, ws, ws_bytes, nullptr, B, Z, Y, X, bnd, k, stream);
 }
 
 int df_pressure_status(const void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int64_t k, int32_t* active_count,
@@ -566,11 +648,67 @@ int df_pressure_status(const void* ws, int64_t ws_bytes, int64_t B, int64_t Z, i
 }
 
 int df_pressure_correct2d(const float* vel, const float* pressure, float* out, int64_t B, int64_t Y, int64_t X, int bnd, df_stream_t stream) {
-  return pressure_correct<2>("df_pressure_correct2d", vel, pressure, out, B, 1, Y, X, bnd, stream);
+  return pressure_correct<2, false>("df_pressure_correct2d", vel, pressure, out, nullptr, B, 1, Y, X, bnd, stream);
 }
 int df_pressure_correct3d(const float* vel, const float* pressure, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
                           df_stream_t stream) {
-  return pressure_correct<3>("df_pressure_correct3d", vel, pressure, out, B, Z, Y, X, bnd, stream);
+  return pressure_correct<3, false>("df_pressure_correct3d", vel, pressure, out, nullptr, B, Z, Y, X, bnd, stream);
+}
+
+// ---- the same steps around obstacles: "interior" reads "fluid", taken from the flags of df_obstacle_flags* ----
+int df_obstacle_flags2d(const uint8_t* obstacle, uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd, df_stream_t stream) {
+  return obstacle_flags<2>("df_obstacle_flags2d", obstacle, flags, B, 1, Y, X, bnd, stream);
+}
+int df_obstacle_flags3d(const uint8_t* obstacle, uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, df_stream_t stream) {
+  return obstacle_flags<3>("df_obstacle_flags3d", obstacle, flags, B, Z, Y, X, bnd, stream);
+}
+int df_mac_advect_mc2d_flags(const float* vel, const float* fwd, float* out, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, float dt,
+                             int bnd, int clamp_mode, df_stream_t stream) {
+  return mac_mc<2, true>("df_mac_advect_mc2d_flags", vel, fwd, out, flags, B, 1, Y, X, dt, bnd, clamp_mode, stream);
+}
+int df_mac_advect_mc3d_flags(const float* vel, const float* fwd, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X,
+                             float dt, int bnd, int clamp_mode, df_stream_t stream) {
+  return mac_mc<3, true>("df_mac_advect_mc3d_flags", vel, fwd, out, flags, B, Z, Y, X, dt, bnd, clamp_mode, stream);
+}
+int df_wall_buoyancy2d_flags(const float* vel, const float* density, float* out, const uint8_t* flags, int64_t B, int64_t Y, int64_t X,
+                             float fx, float fy, int bnd, df_stream_t stream) {
+  return wall_buoyancy<2, true>("df_wall_buoyancy2d_flags", vel, density, out, flags, B, 1, Y, X, Force{{fx, fy, 0.0f}}, bnd, stream);
+}
+int df_wall_buoyancy3d_flags(const float* vel, const float* density, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
+                             int64_t X, float fx, float fy, float fz, int bnd, df_stream_t stream) {
+  return wall_buoyancy<3, true>("df_wall_buoyancy3d_flags", vel, density, out, flags, B, Z, Y, X, Force{{fx, fy, fz}}, bnd, stream);
+}
+int df_pressure_init2d_flags(const float* vel, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y,
+                             int64_t X, int bnd, df_stream_t stream) {
+  return pressure_init<2, true>("df_pressure_init2d_flags", vel, pressure, ws, ws_bytes, flags, B, 1, Y, X, bnd, stream);
+}
+int df_pressure_init3d_flags(const float* vel, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z,
+                             int64_t Y, int64_t X, int bnd, df_stream_t stream) {
+  return pressure_init<3, true>("df_pressure_init3d_flags", vel, pressure, ws, ws_bytes, flags, B, Z, Y, X, bnd, stream);
+}
+int df_pressure_cg_direction2d_flags(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k,
+                                     float accuracy, int64_t max_iter, df_stream_t stream) {
+  return cg_direction<2, true>("df_pressure_cg_direction2d_flags", ws, ws_bytes, flags, B, 1, Y, X, bnd, k, accuracy, max_iter, stream);
+}
+int df_pressure_cg_direction3d_flags(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                                     int64_t k, float accuracy, int64_t max_iter, df_stream_t stream) {
+  return cg_direction<3, true>("df_pressure_cg_direction3d_flags", ws, ws_bytes, flags, B, Z, Y, X, bnd, k, accuracy, max_iter, stream);
+}
+int df_pressure_cg_update2d_flags(float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd,
+                                  int64_t k, df_stream_t stream) {
+  return cg_update<2, true>("df_pressure_cg_update2d_flags", pressure, ws, ws_bytes, flags, B, 1, Y, X, bnd, k, stream);
+}
+int df_pressure_cg_update3d_flags(float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X,
+                                  int bnd, int64_t k, df_stream_t stream) {
+  return cg_update<3, true>("df_pressure_cg_update3d_flags", pressure, ws, ws_bytes, flags, B, Z, Y, X, bnd, k, stream);
+}
+int df_pressure_correct2d_flags(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Y, int64_t X,
+                                int bnd, df_stream_t stream) {
+  return pressure_correct<2, true>("df_pressure_correct2d_flags", vel, pressure, out, flags, B, 1, Y, X, bnd, stream);
+}
+int df_pressure_correct3d_flags(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
+                                int64_t X, int bnd, df_stream_t stream) {
+  return pressure_correct<3, true>("df_pressure_correct3d_flags", vel, pressure, out, flags, B, Z, Y, X, bnd, stream);
 }
 
 }  // extern "C"

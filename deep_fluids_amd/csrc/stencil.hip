@@ -394,12 +394,12 @@ __global__ __launch_bounds__(kThreads) void jacobian3d_bwd_lds_kernel(const floa
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
       const int64_t q = z_first + k * kThreads + tid;
-      tz[k] = g4[q > 0 ? q : 0];
+      tz[k] = g4[q > 0 ? (q < g_last ? q : g_last) : 0];            // a ragged last block: the span may pass the end as well
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int64_t q = own_first - npre + k * kThreads + tid;        // second round: only the first npre - 256 lanes are kept
-      tp[k] = g4[q > 0 ? q : 0];
+      tp[k] = g4[q > 0 ? (q < g_last ? q : g_last) : 0];
       asm volatile("" : "+v"(tp[k]));                                 // keep the load up here (not sunk into the guarded LDS write)
     }
     f32x4* a4 = reinterpret_cast<f32x4*>(sA);

@@ -4,7 +4,8 @@ On-disk format (written by the reference's ``scene/*.py``, e.g. scene/smoke_pos_
   <root>/args.txt            "key: value" lines (num_param, p0.., min_/max_/num_<pname>, num_frames, num_dof, path_format ...)
   <root>/v/%d_%d_%d.npz      x: [Y,X,2] | [Z,Y,X,3] float32 velocity, y: [c_num] parameters  (AE sets: y [dof, frames])
   <root>/v_range.txt         two numbers; x is normalised by max(|r0|, |r1|)     (data.py:87-88, 329)
-``generate_smoke_dataset`` writes such a directory for the reference's default 2-D smoke scene with this library's own solver.
+``generate_smoke_dataset`` writes such a directory for the reference's default 2-D smoke scene with this library's own solver,
+``generate_smoke3_obs_dataset`` for its 3-D scene with a sphere obstacle (scene/smoke3_obs_buo.py).
 Labels are mapped to [-1,1] with min_/max_<pname> (data.py:331-332).
 
 The reference feeds a tf.FIFOQueue from N Python threads that share one RandomState (data.py:116-144) and dequeues
@@ -342,6 +343,70 @@ def generate_smoke_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="sr
             for e, (i, j, px, pr) in enumerate(part):
                 np.savez_compressed(os.path.join(root, "v", path_format % (i, j, t)), x=vh[e], y=[px, pr, t])
                 written += 1
+    with open(os.path.join(root, "v_range.txt"), "w") as f:
+        f.write("%.3f\n" % v_range[0])
+        f.write("%.3f" % v_range[1])
+    return written
+
+
+def generate_smoke3_obs_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="obs_x_pos", p1="buoyancy", p2="frames", min_obs_x_pos=0.2,
+                                max_obs_x_pos=0.8, num_obs_x_pos=11, obs_radius=0.15, obs_y_pos=0.5, obs_z_pos=0.5, min_buoyancy=-8e-3,
+                                max_buoyancy=-16e-3, num_buoyancy=4, src_x_pos=0.5, src_y_pos=0.13, src_z_pos=0.5, src_radius=0.12,
+                                min_frames=0, max_frames=None, num_frames=150, num_simulations=None, resolution_x=64, resolution_y=96,
+                                resolution_z=64, bWidth=1, open_bound=False, time_step=0.5, adv_order=2, clamp_mode=2, scenes_per_batch=None,
+                                accuracy=1e-4, device="cuda"):
+    """Simulate the reference's 3-D obstacle training set (scene/smoke3_obs_buo.py:126-294, ``smoke3_obs11_buo4_f150``) on the GPU and
+    write it in the reference's on-disk format: ``args.txt`` with every argument of the scene script, ``v/%d_%d_%d.npz`` (x [Z,Y,X,3]
+    float32 velocity after frame t, y = [p0, p1, t]) and ``v_range.txt``.  The keyword arguments are the script's, with its defaults
+    (``max_frames`` and ``num_simulations`` follow ``num_frames`` and the grid of scenes unless given).  A closed box with a sphere
+    source at ``gs * (src_x_pos, src_y_pos, src_z_pos)`` of radius ``X * src_radius`` and a sphere obstacle at ``gs * (p0, obs_y_pos,
+    obs_z_pos)`` of radius ``X * obs_radius``; the buoyancy is (0, p1, 0).  Every scene is one batch entry of ``ops.simulate_smoke``.
+    The buoyancy is one number per launch, so a chunk holds the scenes of ONE buoyancy value (all obstacle positions: 11 by default);
+    ``scenes_per_batch`` splits a chunk further, and an entry's result does not depend on the rest of its batch.  The step is this
+    library's restatement (include/deepfluids_hip.h), not mantaflow's: closed box only (``open_bound=True`` is refused), plain CG in
+    place of MIC(0)-preconditioned CG.  Returns the number of files written."""
+    from . import ops
+    if open_bound:
+        raise NotImplementedError("generate_smoke3_obs_dataset: open_bound=True is not restated (closed box only)")
+    if num_param != 3 or (p0, p1, p2) != ("obs_x_pos", "buoyancy", "frames"):
+        raise ValueError("generate_smoke3_obs_dataset: the scene has the parameters (obs_x_pos, buoyancy, frames)")
+    max_frames = num_frames - 1 if max_frames is None else max_frames
+    num_simulations = num_obs_x_pos * num_buoyancy * num_frames if num_simulations is None else num_simulations
+    args = [("log_dir", root), ("num_param", num_param), ("path_format", path_format), ("p0", p0), ("p1", p1), ("p2", p2),
+            ("min_obs_x_pos", min_obs_x_pos), ("max_obs_x_pos", max_obs_x_pos), ("num_obs_x_pos", num_obs_x_pos), ("obs_radius", obs_radius),
+            ("obs_y_pos", obs_y_pos), ("obs_z_pos", obs_z_pos), ("min_buoyancy", min_buoyancy), ("max_buoyancy", max_buoyancy),
+            ("num_buoyancy", num_buoyancy), ("src_x_pos", src_x_pos), ("src_y_pos", src_y_pos), ("src_z_pos", src_z_pos),
+            ("src_radius", src_radius), ("min_frames", min_frames), ("max_frames", max_frames), ("num_frames", num_frames),
+            ("num_simulations", num_simulations), ("resolution_x", resolution_x), ("resolution_y", resolution_y),
+            ("resolution_z", resolution_z), ("bWidth", bWidth), ("open_bound", open_bound), ("time_step", time_step),
+            ("adv_order", adv_order), ("clamp_mode", clamp_mode)]
+    os.makedirs(os.path.join(root, "v"), exist_ok=True)
+    with open(os.path.join(root, "args.txt"), "w") as f:
+        for k, v in args:
+            f.write("%s: %s\n" % (k, v))
+    X, Y, Z = int(resolution_x), int(resolution_y), int(resolution_z)
+    shape = (Z, Y, X)
+    xs = np.linspace(min_obs_x_pos, max_obs_x_pos, num_obs_x_pos)            # p1_space / p2_space of the scene script
+    bs = np.linspace(min_buoyancy, max_buoyancy, num_buoyancy)
+    source = ops.sphere_mask(shape, (X * src_x_pos, Y * src_y_pos, Z * src_z_pos), X * src_radius).to(device)
+    chunk = num_obs_x_pos if not scenes_per_batch else int(scenes_per_batch)
+    v_range = [np.finfo(np.float64).max, np.finfo(np.float64).min]
+    written = 0
+    for j, buo in enumerate(bs):
+        force = ops.default_buoyancy_force(shape, time_step, gravity=float(buo))
+        for c0 in range(0, num_obs_x_pos, chunk):
+            part = list(range(c0, min(c0 + chunk, num_obs_x_pos)))
+            obs = torch.stack([ops.sphere_mask(shape, (X * xs[i], Y * obs_y_pos, Z * obs_z_pos), X * obs_radius) for i in part]).to(device)
+            d0 = torch.zeros((len(part),) + shape, dtype=torch.float32, device=device)
+            v0 = torch.zeros((len(part),) + shape + (3,), dtype=torch.float32, device=device)
+            frames = ops.simulate_smoke(d0, v0, num_frames, dt=time_step, source=source, force=force, order=adv_order, clamp_mode=clamp_mode,
+                                        bnd=bWidth, accuracy=accuracy, stack=False, obstacle=ops.obstacle_flags(obs, bWidth))
+            for t, (_, v) in enumerate(frames):
+                vh = v.cpu().numpy()
+                v_range = [min(v_range[0], float(vh.min())), max(v_range[1], float(vh.max()))]
+                for e, i in enumerate(part):
+                    np.savez_compressed(os.path.join(root, "v", path_format % (i, j, t)), x=vh[e], y=[xs[i], buo, t])
+                    written += 1
     with open(os.path.join(root, "v_range.txt"), "w") as f:
         f.write("%.3f\n" % v_range[0])
         f.write("%.3f" % v_range[1])

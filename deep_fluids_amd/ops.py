@@ -30,7 +30,7 @@ __all__ = [
     "vort_np", "curl_np", "grad_np", "jacobian_np3", "l1_mean", "velocity_loss",
     "denorm_img", "plane_view", "denorm_img3", "plane_view_np", "velocity_views3", "add_channels", "remove_channels",
     "advect", "advect_sequence", "advect_workspace", "density_image", "sphere_mask",
-    "advect_velocity", "wall_buoyancy", "solve_pressure", "pressure_workspace", "smoke_step", "simulate_smoke", "default_buoyancy_force", "default_max_iter",
+    "advect_velocity", "wall_buoyancy", "solve_pressure", "pressure_workspace", "smoke_step", "simulate_smoke", "default_buoyancy_force", "default_max_iter", "obstacle_flags", "ObstacleFlags",
     "advect_particles", "particle_cells", "particle_levelset", "liquid_sequence", "seed_particles", "box_levelset", "sphere_levelset",
     "variable_scope", "get_variables", "get_variable", "reset_variables", "set_random_seed", "all_variables",
 ]
@@ -1694,6 +1694,78 @@ def _source_mask(source, like):
     return m.contiguous()
 
 
+# Obstacles: a uint8 / bool mask [B,(Z,)Y,X] (nonzero = solid; [(Z,)Y,X] is shared by the batch) is packed once into the flags of
+# include/deepfluids_hip.h (one byte per cell: the cell is fluid, each of its six neighbours is fluid), which every `_flags` kernel reads.
+class ObstacleFlags(torch.Tensor):
+    """What ``obstacle_flags`` returns: a uint8 tensor whose TYPE says that it holds flags, not a mask, and that carries the boundary
+    width it was packed for.  Slices along the batch, clones and copies to another device stay ``ObstacleFlags`` and keep ``bnd``, so
+    ``flags[e:e + 1]`` is still taken for flags.  Anything COMPUTED from flags (``flags & 1``, ``flags != 0``) is an ordinary tensor again,
+    as is what ``as_subclass(torch.Tensor)`` or a trip through NumPy returns: a plain array is taken for a mask."""
+    bnd = None
+    _KEEP = frozenset(["__getitem__", "clone", "contiguous", "detach", "to", "cuda", "cpu", "expand", "unsqueeze", "squeeze", "pin_memory"])
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        out = super().__torch_function__(func, types, args, kwargs or {})
+        if isinstance(out, ObstacleFlags):
+            src = args[0] if args and isinstance(args[0], ObstacleFlags) else None
+            if src is not None and getattr(func, "__name__", None) in cls._KEEP and out.dtype == torch.uint8:
+                out.bnd = src.bnd                       # the same bytes, seen or copied: still flags
+            else:
+                out = out.as_subclass(torch.Tensor)     # computed from flags: an ordinary tensor
+        return out
+
+
+def obstacle_flags(obstacle, bnd=1, dim=None):
+    """The flags tensor (``ObstacleFlags``, uint8 [B,(Z,)Y,X]) of an obstacle mask for boundary width ``bnd``: bit 0 = the cell is fluid
+    (interior and not solid), bits 1-6 = its x-, x+, y-, y+, z-, z+ neighbour is.  ``obstacle``: bool / uint8 [B,(Z,)Y,X] or [(Z,)Y,X]
+    (then B = 1, and every op broadcasts it over its batch).  A 3-dimensional mask is [B,Y,X] unless ``dim=3`` says it is [Z,Y,X].
+    Build it once per sequence and hand it to the ``obstacle=`` keyword of the ops below; the tensor remembers ``bnd``."""
+    with torch.no_grad():
+        if int(bnd) != bnd or bnd < 1:
+            raise ValueError("obstacle_flags: bnd must be an integer >= 1, got %r" % (bnd,))
+        if isinstance(obstacle, ObstacleFlags):
+            raise ValueError("obstacle_flags expects a mask of solid cells, got flags that are packed already")
+        m = obstacle if isinstance(obstacle, torch.Tensor) else torch.as_tensor(np.asarray(obstacle))
+        if not m.is_cuda:
+            m = m.cuda()
+        if m.dtype != torch.uint8:
+            m = (m != 0).to(torch.uint8)
+        if dim is None:
+            dim = 3 if m.dim() == 4 else 2
+        if dim not in (2, 3) or m.dim() not in (dim, dim + 1):
+            raise ValueError("obstacle_flags expects a mask [B,(Z,)Y,X] or [(Z,)Y,X], got %s (dim=%r)" % (tuple(m.shape), dim))
+        if m.dim() == dim:
+            m = m[None]
+        m = m.contiguous()
+        flags = torch.empty_like(m).as_subclass(ObstacleFlags)
+        flags.bnd = int(bnd)
+        call("df_obstacle_flags%dd" % dim, _ptr(m), _ptr(flags), *(list(m.shape) + [int(bnd), _stream()]))
+        return flags
+
+
+def _obstacle_arg(obstacle, shape, bnd, who):
+    """flags [B,(Z,)Y,X] for a field of ``shape`` from the ``obstacle=`` keyword: a flags tensor of ``obstacle_flags`` or a mask"""
+    shape = tuple(shape)
+    nd = len(shape) - 1
+    if isinstance(obstacle, ObstacleFlags):
+        if obstacle.dtype != torch.uint8 or obstacle.bnd is None:
+            raise ValueError("%s: obstacle was derived from flags by an operation that does not keep them flags (dtype %s); pass the "
+                             "flags of obstacle_flags, or a mask" % (who, obstacle.dtype))
+        if obstacle.bnd != int(bnd):
+            raise ValueError("%s: the obstacle flags were built for bnd=%d, the step uses bnd=%d" % (who, obstacle.bnd, int(bnd)))
+    else:
+        m = obstacle if isinstance(obstacle, torch.Tensor) else torch.as_tensor(np.asarray(obstacle))
+        if tuple(m.shape) not in (shape, shape[1:], (1,) + shape[1:]):
+            raise ValueError("%s: obstacle must be a mask %s or %s, got %s" % (who, shape, shape[1:], tuple(m.shape)))
+        obstacle = obstacle_flags(m, bnd, dim=nd)
+    if tuple(obstacle.shape) == shape:
+        return obstacle if obstacle.is_contiguous() else obstacle.contiguous()
+    if tuple(obstacle.shape) != (1,) + shape[1:]:
+        raise ValueError("%s: obstacle flags %s do not fit a field %s" % (who, tuple(obstacle.shape), shape))
+    return obstacle.expand(shape).contiguous()
+
+
 def advect_workspace(density, order=2, source=False):
     """The scratch ``advect`` needs for one step on ``density``: one grid for the source-stamped density, one for the forward pass of
     order 2.  Reusable across calls of the same shape."""
@@ -1701,14 +1773,18 @@ def advect_workspace(density, order=2, source=False):
     return torch.empty((max(n, 1),), dtype=torch.float32, device=density.device)
 
 
-def _advect_step(d, v, nd, out, fwd, dt, order, clamp_mode, bnd, vel_scale):
+def _advect_step(d, v, nd, out, fwd, dt, order, clamp_mode, bnd, vel_scale, flags=None):
     sfx = "%dd" % nd
     dims = list(d.shape)
-    if order == 1:
+    if order == 1:                                      # the first-order value ignores obstacles
         call("df_advect_sl" + sfx, _ptr(d), _ptr(v), _ptr(out), *(dims + [dt, vel_scale, bnd, _stream()]))
     else:
         call("df_advect_sl" + sfx, _ptr(d), _ptr(v), _ptr(fwd), *(dims + [dt, vel_scale, bnd, _stream()]))
-        call("df_advect_mc" + sfx, _ptr(d), _ptr(fwd), _ptr(v), _ptr(out), *(dims + [dt, vel_scale, bnd, clamp_mode, _stream()]))
+        if flags is None:
+            call("df_advect_mc" + sfx, _ptr(d), _ptr(fwd), _ptr(v), _ptr(out), *(dims + [dt, vel_scale, bnd, clamp_mode, _stream()]))
+        else:
+            call("df_advect_mc" + sfx + "_flags", _ptr(d), _ptr(fwd), _ptr(v), _ptr(out), _ptr(flags),
+                 *(dims + [dt, vel_scale, bnd, clamp_mode, _stream()]))
 
 
 def _advect_args(order, clamp_mode, bnd):
@@ -1720,16 +1796,20 @@ def _advect_args(order, clamp_mode, bnd):
         raise ValueError("advect: bnd must be an integer >= 1, got %r" % (bnd,))
 
 
-def advect(density, vel, dt, order=2, clamp_mode=2, bnd=1, vel_scale=1.0, source=None, source_value=1.0, out=None, workspace=None):
+def advect(density, vel, dt, order=2, clamp_mode=2, bnd=1, vel_scale=1.0, source=None, source_value=1.0, out=None, workspace=None,
+           obstacle=None):
     """One advection step of ``density`` [B,(Z,)Y,X] through ``vel`` [B,(Z,)Y,X,C] (MAC face values, C = 2 | 3), modelled on mantaflow's
     ``advectSemiLagrange(order, boundaryWidth=bnd, clampMode=clamp_mode)`` as the reference's scene scripts call it
     (scene/smoke_pos_size.py:99-101) -- NOT bit-identical to mantaflow, which cannot be run here; include/deepfluids_hip.h holds the
     definition that is tested.  ``vel_scale`` multiplies the velocities inside the kernel (``x_range`` for a generator's normalised
     output); ``source`` is an optional mask [B,(Z,)Y,X] (or one broadcastable to it) of cells set to ``source_value`` before the step.
-    Returns a new density (``out`` if given; it must not be ``density``).  ``workspace``: see ``advect_workspace``."""
+    Returns a new density (``out`` if given; it must not be ``density``).  ``workspace``: see ``advect_workspace``.  ``obstacle``: a
+    mask of solid cells or the flags of ``obstacle_flags``; the MacCormack correction and its clamp then run over fluid cells only (the
+    first-order value and the source stamp ignore obstacles, as mantaflow's do)."""
     with torch.no_grad():
         _advect_args(order, clamp_mode, bnd)
         d, v, nd = _advect_dims(density, vel)
+        flags = _obstacle_arg(obstacle, d.shape, bnd, "advect") if obstacle is not None else None
         n = d.numel()
         need = n * ((1 if source is not None else 0) + (1 if order == 2 else 0))
         ws = workspace if workspace is not None else advect_workspace(d, order, source is not None)
@@ -1746,7 +1826,7 @@ def advect(density, vel, dt, order=2, clamp_mode=2, bnd=1, vel_scale=1.0, source
             call("df_density_source", _ptr(d), _ptr(_source_mask(source, d)), float(source_value), _ptr(stamped), n, _stream())
             d, off = stamped, n
         fwd = ws[off:off + n] if order == 2 else None
-        _advect_step(d, v, nd, out, fwd, float(dt), order, clamp_mode, int(bnd), float(vel_scale))
+        _advect_step(d, v, nd, out, fwd, float(dt), order, clamp_mode, int(bnd), float(vel_scale), flags)
         return out
 
 
@@ -1766,11 +1846,12 @@ def density_image(d, out=None):
         return out
 
 
-def advect_sequence(density0, vels, dt, order=2, clamp_mode=2, bnd=1, vel_scale=1.0, source=None, source_value=1.0, images=False):
+def advect_sequence(density0, vels, dt, order=2, clamp_mode=2, bnd=1, vel_scale=1.0, source=None, source_value=1.0, images=False,
+                    obstacle=None):
     """``T`` chained ``advect`` steps over ``vels`` [T,B,(Z,)Y,X,C] (a tensor or a sequence of T tensors), the source stamped before
     every step, ping-ponging two density buffers (``density0`` is left untouched).  Returns the final density, and with ``images`` also
     the uint8 frames [T,B,Y,X] of ``density_image`` after each step, produced on the device and copied to the host once (a NumPy
-    array)."""
+    array).  ``obstacle``: as for ``advect``; its flags are built once for the sequence."""
     with torch.no_grad():
         _advect_args(order, clamp_mode, bnd)
         T = len(vels)
@@ -1781,13 +1862,14 @@ def advect_sequence(density0, vels, dt, order=2, clamp_mode=2, bnd=1, vel_scale=
         nxt = torch.empty_like(cur)
         fwd = torch.empty_like(cur) if order == 2 else None
         mask = _source_mask(source, cur) if source is not None else None
+        flags = _obstacle_arg(obstacle, cur.shape, bnd, "advect_sequence") if obstacle is not None else None
         n = cur.numel()
         imgs = _u8((T, cur.shape[0], cur.shape[-2], cur.shape[-1]), cur) if images else None
         for t in range(T):
             _, v, _ = _advect_dims(cur, vels[t])
             if mask is not None:
                 call("df_density_source", _ptr(cur), _ptr(mask), float(source_value), _ptr(cur), n, _stream())
-            _advect_step(cur, v, nd, nxt, fwd, float(dt), order, clamp_mode, int(bnd), float(vel_scale))
+            _advect_step(cur, v, nd, nxt, fwd, float(dt), order, clamp_mode, int(bnd), float(vel_scale), flags)
             cur, nxt = nxt, cur
             if images:
                 density_image(cur, out=imgs[t])
@@ -1815,8 +1897,8 @@ def sphere_mask(shape, center, radius, device=None):
 # ---- the smoke solver step (the main() loop of the reference's scene/smoke_pos_size.py:186-195, a closed box): MAC self-advection, walls
 #      and buoyancy, a conjugate-gradient pressure projection.  Inference only, no autograd.  The step is defined in
 #      include/deepfluids_hip.h; parity is with the fp64 restatement of tests/smoke_ref.py, NOT with mantaflow, which cannot be run here.
-#      Left out: open bounds, obstacles, outflow, noise-modulated inflow (the reference's 3-D scenes need them), the MIC(0)
-#      preconditioner ----
+#      Obstacles (the reference's scene/smoke3_obs_buo.py) enter through the ``obstacle=`` keyword: "interior" then reads "fluid".
+#      Left out: open bounds, outflow, noise-modulated inflow (the reference's other 3-D scenes need them), the MIC(0) preconditioner ----
 DEFAULT_CHECK_EVERY = 16      # iterations between two looks at the active count; the sweep over 1, 4, 16, 64 is in profiles/smoke.md
 
 
@@ -1835,14 +1917,16 @@ def _smoke_out(out, like, who):
     return out
 
 
-def advect_velocity(vel, dt, order=2, clamp_mode=2, bnd=1, out=None, workspace=None):
+def advect_velocity(vel, dt, order=2, clamp_mode=2, bnd=1, out=None, workspace=None, obstacle=None):
     """The MAC velocity ``vel`` [B,(Z,)Y,X,D] carried through itself for ``dt`` (cells per unit time), modelled on mantaflow's
     ``advectSemiLagrange(vel, vel, order, boundaryWidth=bnd, clampMode=clamp_mode)``; include/deepfluids_hip.h holds the definition
     that is tested.  Returns a new velocity (``out`` if given; not ``vel`` itself).  ``workspace``: a float32 GPU tensor of
-    ``vel.numel()`` elements for order 2."""
+    ``vel.numel()`` elements for order 2.  ``obstacle``: a mask or the flags of ``obstacle_flags``; component a is then corrected and
+    clamped only where c and c - e_a are fluid, over fluid corners (the first-order value ignores obstacles)."""
     with torch.no_grad():
         _advect_args(order, clamp_mode, bnd)
         v, nd = _smoke_vel(vel, "advect_velocity")
+        flags = _obstacle_arg(obstacle, v.shape[:-1], bnd, "advect_velocity") if obstacle is not None else None
         out = _smoke_out(out, v, "advect_velocity")
         if out.data_ptr() == v.data_ptr():
             raise ValueError("advect_velocity: out must not be the velocity itself (the step gathers)")
@@ -1855,14 +1939,19 @@ def advect_velocity(vel, dt, order=2, clamp_mode=2, bnd=1, out=None, workspace=N
         if ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < v.numel():
             raise ValueError("advect_velocity: workspace must be a contiguous float32 GPU tensor of >= %d elements" % v.numel())
         call("df_mac_advect_sl" + sfx, _ptr(v), _ptr(ws), *(dims + [float(dt), int(bnd), _stream()]))
-        call("df_mac_advect_mc" + sfx, _ptr(v), _ptr(ws), _ptr(out), *(dims + [float(dt), int(bnd), int(clamp_mode), _stream()]))
+        if flags is None:
+            call("df_mac_advect_mc" + sfx, _ptr(v), _ptr(ws), _ptr(out), *(dims + [float(dt), int(bnd), int(clamp_mode), _stream()]))
+        else:
+            call("df_mac_advect_mc" + sfx + "_flags", _ptr(v), _ptr(ws), _ptr(out), _ptr(flags),
+                 *(dims + [float(dt), int(bnd), int(clamp_mode), _stream()]))
         return out
 
 
-def wall_buoyancy(vel, density, force, bnd=1, out=None):
+def wall_buoyancy(vel, density, force, bnd=1, out=None, obstacle=None):
     """``setWallBcs`` of a closed box and ``addBuoyancy`` in one element-wise pass: component a of cell c is 0 unless c and c - e_a are
     both interior; kept components get ``+ (0.5 * force[a]) * (density[c] + density[c-e_a])``.  ``force``: D numbers (x, y[, z]).
-    ``out`` may be ``vel`` (in place)."""
+    ``out`` may be ``vel`` (in place).  ``obstacle``: a mask or the flags of ``obstacle_flags``; "interior" then reads "fluid", so the
+    faces of solid cells are 0 as well."""
     with torch.no_grad():
         v, nd = _smoke_vel(vel, "wall_buoyancy")
         d = _prep(density.detach(), "density")
@@ -1874,7 +1963,11 @@ def wall_buoyancy(vel, density, force, bnd=1, out=None):
         if int(bnd) != bnd or bnd < 1:
             raise ValueError("wall_buoyancy: bnd must be an integer >= 1, got %r" % (bnd,))
         out = _smoke_out(out, v, "wall_buoyancy")
-        call("df_wall_buoyancy%dd" % nd, _ptr(v), _ptr(d), _ptr(out), *(list(d.shape) + f + [int(bnd), _stream()]))
+        if obstacle is None:
+            call("df_wall_buoyancy%dd" % nd, _ptr(v), _ptr(d), _ptr(out), *(list(d.shape) + f + [int(bnd), _stream()]))
+        else:
+            flags = _obstacle_arg(obstacle, d.shape, bnd, "wall_buoyancy")
+            call("df_wall_buoyancy%dd_flags" % nd, _ptr(v), _ptr(d), _ptr(out), _ptr(flags), *(list(d.shape) + f + [int(bnd), _stream()]))
         return out
 
 
@@ -1904,14 +1997,16 @@ def default_max_iter(shape):
     return int(10 * max(shape)) * (1 if len(shape) == 3 else 4)
 
 
-def solve_pressure(vel, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, out=None, workspace=None):
+def solve_pressure(vel, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, out=None, workspace=None, obstacle=None):
     """Make ``vel`` [B,(Z,)Y,X,D] divergence free inside a closed box: plain conjugate gradients on the Neumann Laplacian of the interior
     cells from p = 0, every batch entry on its own until its ``max|r| <= accuracy`` or ``max_iter`` iterations (default
     ``int(10*max(extent))``, times 4 in 2-D), then ``vel -= grad p`` with the wall faces 0.  The wall faces of ``vel`` must be 0 already
     (``wall_buoyancy``).  All scalars of the iteration stay on the device; the host reads one word, the number of entries still
     iterating, every ``check_every`` iterations (the result does not depend on it).  mantaflow preconditions with MIC(0), this solver
     does not: both stop at the same criterion, so the fields agree to the solve's accuracy and not beyond.
-    Returns ``(vel_projected, pressure, iterations)``; ``iterations`` is an int32 tensor [B].  ``out`` may be ``vel``."""
+    Returns ``(vel_projected, pressure, iterations)``; ``iterations`` is an int32 tensor [B].  ``out`` may be ``vel``.
+    ``obstacle``: a mask or the flags of ``obstacle_flags``; the Laplacian then lives on the fluid cells (every connected fluid region is
+    its own singular system), the solid faces of ``vel`` must be 0 already and stay 0, and the pressure is 0 outside the fluid."""
     with torch.no_grad():
         v, nd = _smoke_vel(vel, "solve_pressure")
         if int(bnd) != bnd or bnd < 1:
@@ -1934,18 +2029,22 @@ def solve_pressure(vel, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, o
         words = torch.empty((1 + dims[0],), dtype=torch.int32, device=v.device)
         count, iters = words[:1], words[1:]
         bnd, acc, max_iter = int(bnd), float(accuracy), int(max_iter)
-        call("df_pressure_init" + sfx, _ptr(v), _ptr(pressure), _ptr(ws), nbytes, *(dims + [bnd, _stream()]))
+        # with obstacles: the `_flags` twin of every launch, the flags pointer right after the array arguments
+        flags = None if obstacle is None else _obstacle_arg(obstacle, dims, bnd, "solve_pressure")     # held until the last launch
+        fl = [] if flags is None else [_ptr(flags)]
+        sfx += "_flags" if fl else ""
+        call("df_pressure_init" + sfx, _ptr(v), _ptr(pressure), _ptr(ws), nbytes, *(fl + dims + [bnd, _stream()]))
         k = 0
         while True:
-            call("df_pressure_cg_direction" + sfx, _ptr(ws), nbytes, *(dims + [bnd, k, acc, max_iter, _stream()]))
+            call("df_pressure_cg_direction" + sfx, _ptr(ws), nbytes, *(fl + dims + [bnd, k, acc, max_iter, _stream()]))
             if k % check_every == check_every - 1 or k >= max_iter:
                 call("df_pressure_status", _ptr(ws), nbytes, *(dims4 + [k, _ptr(count), None, _stream()]))
                 if _read_word(count) == 0:
                     break
-            call("df_pressure_cg_update" + sfx, _ptr(pressure), _ptr(ws), nbytes, *(dims + [bnd, k, _stream()]))
+            call("df_pressure_cg_update" + sfx, _ptr(pressure), _ptr(ws), nbytes, *(fl + dims + [bnd, k, _stream()]))
             k += 1
         call("df_pressure_status", _ptr(ws), nbytes, *(dims4 + [k, None, _ptr(iters), _stream()]))
-        call("df_pressure_correct" + sfx, _ptr(v), _ptr(pressure), _ptr(out), *(dims + [bnd, _stream()]))
+        call("df_pressure_correct" + sfx, _ptr(v), _ptr(pressure), _ptr(out), *(fl + dims + [bnd, _stream()]))
         return out, pressure, iters.clone()
 
 
@@ -1967,37 +2066,43 @@ class _SmokeBuffers(object):
         self.pws = pressure_workspace(vel)
 
 
-def _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every):
-    advect(d, v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, source=mask, out=d_out, workspace=buf.adv)
-    advect_velocity(v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, out=v_out, workspace=buf.fwd)
-    wall_buoyancy(v_out, d_out, force, bnd=bnd, out=v_out)
-    _, _, iters = solve_pressure(v_out, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=v_out, workspace=buf.pws)
+def _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags=None):
+    advect(d, v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, source=mask, out=d_out, workspace=buf.adv, obstacle=flags)
+    advect_velocity(v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, out=v_out, workspace=buf.fwd, obstacle=flags)
+    wall_buoyancy(v_out, d_out, force, bnd=bnd, out=v_out, obstacle=flags)
+    _, _, iters = solve_pressure(v_out, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=v_out, workspace=buf.pws,
+                                 obstacle=flags)
     return iters
 
 
-def smoke_step(density, vel, dt, source=None, force=None, order=2, clamp_mode=2, bnd=1, accuracy=1e-4, max_iter=None, check_every=None):
+def smoke_step(density, vel, dt, source=None, force=None, order=2, clamp_mode=2, bnd=1, accuracy=1e-4, max_iter=None, check_every=None,
+               obstacle=None):
     """One frame of the reference's smoke scene (scene/smoke_pos_size.py:187-195) on ``density`` [B,(Z,)Y,X] and the MAC velocity ``vel``
     [B,(Z,)Y,X,D] of a closed box: stamp ``source`` (a mask) with 1, advect the density and the velocity through the OLD velocity, zero
-    the wall faces, add buoyancy (``force``; default ``default_buoyancy_force``), project.  Returns new ``(density, vel)``."""
+    the wall faces, add buoyancy (``force``; default ``default_buoyancy_force``), project.  Returns new ``(density, vel)``.
+    ``obstacle`` (a mask of solid cells or the flags of ``obstacle_flags``) makes it the loop of scene/smoke3_obs_buo.py:211-219: the same
+    statements with the obstacle in the flag grid, the solid faces 0 after the walls and after the projection."""
     with torch.no_grad():
         d, v, nd = _advect_dims(density, vel)
         force = default_buoyancy_force(d.shape[1:], dt) if force is None else force
         mask = _source_mask(source, d) if source is not None else None
         buf = _SmokeBuffers(d, v, order, mask is not None)
+        flags = _obstacle_arg(obstacle, d.shape, bnd, "smoke_step") if obstacle is not None else None
         d_out, v_out = torch.empty_like(d), torch.empty_like(v)
-        _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every)
+        _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags)
         return d_out, v_out
 
 
-def _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, stats):
+def _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, stats, obstacle=None):
     d, v, nd = _advect_dims(density0, vel0)
     force = default_buoyancy_force(d.shape[1:], dt) if force is None else force
     mask = _source_mask(source, d) if source is not None else None
     buf = _SmokeBuffers(d, v, order, mask is not None)
+    flags = _obstacle_arg(obstacle, d.shape, bnd, "simulate_smoke") if obstacle is not None else None      # once per sequence
     d, v = d.clone(), v.clone()
     d2, v2 = torch.empty_like(d), torch.empty_like(v)
     for _ in range(int(steps)):
-        iters = _smoke_step(d, v, d2, v2, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every)
+        iters = _smoke_step(d, v, d2, v2, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags)
         if stats is not None:
             stats.append(iters)
         d, d2, v, v2 = d2, d, v2, v
@@ -2005,13 +2110,13 @@ def _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, b
 
 
 def simulate_smoke(density0, vel0, steps, dt=0.5, source=None, force=None, order=2, clamp_mode=2, bnd=1, accuracy=1e-4, max_iter=None,
-                   check_every=None, stack=True, stats=None):
+                   check_every=None, stack=True, stats=None, obstacle=None):
     """``steps`` chained ``smoke_step`` frames from ``(density0, vel0)`` (left untouched); every buffer is allocated once.  With
     ``stack`` returns ``(density, vels)``, ``vels`` [steps,B,(Z,)Y,X,D] the velocity after each step; without it returns a generator of
     ``(density, vel)`` per step -- views of buffers the next step overwrites, so copy what is to be kept.  ``stats``: a list that
-    receives the iteration counts [B] of every step's solve."""
+    receives the iteration counts [B] of every step's solve.  ``obstacle``: as for ``smoke_step``, packed into flags once."""
     with torch.no_grad():
-        gen = _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, stats)
+        gen = _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, stats, obstacle)
         if not stack:
             return _no_grad_iter(gen)
         vels = torch.empty((int(steps),) + tuple(vel0.shape), dtype=torch.float32, device=vel0.device)

@@ -622,14 +622,17 @@ class Trainer(object):
         return out_dir
 
     # ---- `advect()` of the scene scripts (scene/smoke_pos_size.py:45-109): smoke carried through the generated velocities ------
-    def advect_(self, batch_manager, model_dir=None, p1=10, p2=2, test_b_num=None, *, source, dt=None, order=2, clamp_mode=2, bnd=1):
+    def advect_(self, batch_manager, model_dir=None, p1=10, p2=2, test_b_num=None, *, source, dt=None, order=2, clamp_mode=2, bnd=1,
+                obstacle=None):
         """The sweep of ``test_`` looked at the way the reference's scene scripts do (their ``advect()`` mode): generate every frame of the
         parameter pair (p1, p2), keep the frames on the device -- they are never de-normalised on the host, the advection kernels scale
         them by ``batch_manager.x_range`` -- and, per frame, stamp ``source`` into a density grid that starts empty, advect it through
         the frame's velocity (``ops.advect_sequence``: mantaflow's advectSemiLagrange restated, not bit-identical to it) and write the
         grey frame ``<model_dir>/<p1>_<p2>/d_adv/%04d.png`` (3-D: of the z mean; values are clipped to [0,255] where the reference's
         cast wraps).  ``source``: a mask [(Z,)Y,X] or ``{"center": xyz, "radius": r}`` in cell units (``smoke_pos_size_source`` builds
-        the one of scene/smoke_pos_size.py); ``dt``: the dataset's ``time_step`` when args.txt has it, else 0.5.
+        the one of scene/smoke_pos_size.py); ``dt``: the dataset's ``time_step`` when args.txt has it, else 0.5.  ``obstacle``: a mask of
+        solid cells [(Z,)Y,X] or ``{"center", "radius"}`` like the source (``smoke3_obs_buo_scene`` builds both for
+        scene/smoke3_obs_buo.py); it is handed to ``ops.advect_sequence``.
         Returns ``(out_dir, final density [1,(Z,)Y,X] on the device)``."""
         from PIL import Image
         model_dir = model_dir or self.effective_model_dir()
@@ -641,9 +644,12 @@ class Trainer(object):
         spatial = tuple(frames.shape[1:-1])
         if isinstance(source, dict):
             source = ops.sphere_mask(spatial, source["center"], source["radius"], self.device)
+        if isinstance(obstacle, dict):
+            obstacle = ops.sphere_mask(spatial, obstacle["center"], obstacle["radius"], self.device)
         density0 = torch.zeros((1,) + spatial, dtype=torch.float32, device=frames.device)
         final, imgs = ops.advect_sequence(density0, frames.unsqueeze(1), dt, order=order, clamp_mode=clamp_mode, bnd=bnd,
-                                          vel_scale=float(batch_manager.x_range), source=source, source_value=1.0, images=True)
+                                          vel_scale=float(batch_manager.x_range), source=source, source_value=1.0, images=True,
+                                          obstacle=obstacle)
         out_dir = os.path.join(model_dir, "%d_%d" % (p1, p2), "d_adv")
         os.makedirs(out_dir, exist_ok=True)
         for t in range(imgs.shape[0]):
@@ -736,6 +742,26 @@ def smoke_pos_size_source(batch_manager, p1, p2):
     rad = p2 / float(int(a["num_src_radius"]) - 1) * (float(a["max_src_radius"]) - float(a["min_src_radius"])) + float(a["min_src_radius"])
     rx, ry = int(batch_manager.res_x), int(batch_manager.res_y)
     return {"center": (rx * x_pos, ry * float(a["src_y_pos"])), "radius": rx * rad}
+
+
+def smoke3_obs_buo_scene(batch_manager, p1, p2):
+    """The smoke source and the obstacle of scene/smoke3_obs_buo.py:52-64,89-95 for grid indices (p1, p2) of a dataset written by that
+    scene: ``(source, obstacle)``, each ``{"center": gs * (x, y, z), "radius": X * r}`` in cell units; the obstacle's x position is
+    interpolated from the min_/max_/num_obs_x_pos keys of args.txt (p2, the buoyancy, moves neither sphere)."""
+    a = batch_manager.args
+    keys = ["min_obs_x_pos", "max_obs_x_pos", "num_obs_x_pos", "obs_radius", "obs_y_pos", "obs_z_pos", "src_x_pos", "src_y_pos", "src_z_pos",
+            "src_radius"]
+    missing = [k for k in keys if k not in a]
+    if missing:
+        raise KeyError("smoke3_obs_buo_scene: args.txt of %s lacks %s -- the dataset is not a smoke3_obs_buo scene; pass the source and the "
+                       "obstacle of its own scene script as masks or {'center', 'radius'}" % (batch_manager.root, ", ".join(missing)))
+    num = int(a["num_obs_x_pos"])
+    lo, hi = float(a["min_obs_x_pos"]), float(a["max_obs_x_pos"])
+    x_pos = p1 / float(num - 1) * (hi - lo) + lo if num > 1 else lo
+    gs = (int(batch_manager.res_x), int(batch_manager.res_y), int(batch_manager.res_z))
+    source = {"center": tuple(g * float(a[k]) for g, k in zip(gs, ("src_x_pos", "src_y_pos", "src_z_pos"))), "radius": gs[0] * float(a["src_radius"])}
+    obstacle = {"center": (gs[0] * x_pos, gs[1] * float(a["obs_y_pos"]), gs[2] * float(a["obs_z_pos"])), "radius": gs[0] * float(a["obs_radius"])}
+    return source, obstacle
 
 
 def body_levelset(spatial, body):

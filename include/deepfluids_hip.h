@@ -571,7 +571,8 @@ int df_particle_levelset_union3d(const float* pos_sorted, const int32_t* cell_st
  * (open_bound=False):  source.applyToGrid, advectSemiLagrange(vel, density), advectSemiLagrange(vel, vel), setWallBcs, addBuoyancy,
  * solvePressure(cgAccuracy, cgMaxIterFac), setWallBcs.  The first two statements are df_density_source and df_advect_* above; the
  * rest is below.  mantaflow cannot be run beside this library, so bit parity with it is NOT claimed: the definition below is the
- * contract (tests/smoke_ref.py restates it).  Left out: open bounds, obstacles, outflow, the MIC(0) preconditioner.
+ * contract (tests/smoke_ref.py restates it; tests/smoke_obs_ref.py the obstacle rules further down).  Left out: open bounds, outflow,
+ * noise-modulated inflow, the MIC(0) preconditioner.
  *
  * Layouts as for df_advect_*: density, pressure [B,(Z,)Y,X]; velocity [B,(Z,)Y,X,D], D = 2 | 3 MAC face values, component a of cell c
  * on c's low-a face; cell (i,j,k) is [..,k,j,i]; e_a the unit step along axis a.  A cell is interior when bnd <= index < extent - bnd
@@ -647,6 +648,63 @@ int df_pressure_status(const void* ws, int64_t ws_bytes, int64_t B, int64_t Z, i
 int df_pressure_correct2d(const float* vel, const float* pressure, float* out, int64_t B, int64_t Y, int64_t X, int bnd, df_stream_t stream);
 int df_pressure_correct3d(const float* vel, const float* pressure, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
                           df_stream_t stream);
+
+/* ---- the same step around obstacles: the main() loop of the reference's scene/smoke3_obs_buo.py:211-219 (a closed box with a sphere
+ * obstacle stamped into the flag grid).  setWallBcs, KnAddBuoyancy and MacCormackCorrect(MAC) with obstacle flags are restated from
+ * memory of mantaflow and cannot be checked against it here; as for the rest of this block, parity is with the restatement under
+ * tests/ (tests/smoke_obs_ref.py), not with mantaflow.
+ *
+ * obstacle [B,(Z,)Y,X] uint8, nonzero = solid, one per batch entry (the sphere's position is a scene parameter).  A cell is FLUID when
+ * it is interior in the sense above and not an obstacle.  df_obstacle_flags* packs, in one pass, one byte per cell into flags
+ * [B,(Z,)Y,X]: bit 0 = the cell is fluid, bits 1..6 = its x-, x+, y-, y+, z-, z+ neighbour is fluid (a neighbour outside the grid is
+ * not; the z bits are 0 in 2-D).  flags must not overlap obstacle.  Every `_flags` entry point takes such a flags array, built with the
+ * SAME bnd, right after its array arguments and is otherwise its counterpart above with "interior" read as "fluid":
+ *   - a face is kept by df_wall_buoyancy*_flags, updated by df_pressure_correct*_flags and corrected by df_mac_advect_mc*_flags where c
+ *     and c - e_a are both fluid; every other face is 0 after the first two (solid faces carry no flow);
+ *   - b, n_c and the neighbour sums of A run over fluid cells and fluid neighbours (n_c is the popcount of bits 1..6); p stays 0 on
+ *     every other cell;
+ *   - the min / max of the MacCormack clamps run over the fluid cells among the corners (none fluid -> fwd).
+ * Two things keep ignoring obstacles, as mantaflow's SemiLagrange / SemiLagrangeMAC do: the first-order value fwd is that of
+ * df_advect_sl* / df_mac_advect_sl*, which have no `_flags` variant, and df_density_source stamps regardless.  The MacCormack
+ * correction and clamp apply where c is fluid (df_advect_mc*_flags) or where c and c - e_a are (df_mac_advect_mc*_flags, component
+ * a); elsewhere in the interior the output is fwd, on wall cells 0.
+ * A is now singular once per connected fluid region; the system stays consistent when the solid faces of vel are 0, as after
+ * df_wall_buoyancy*_flags (b then sums to zero over every region).  A fluid cell without a fluid neighbour has n_c = 0 and only solid
+ * faces, so b = 0 there: r never leaves 0, p stays 0, its velocity stays 0, nothing divides by n_c.  An entry that is solid everywhere
+ * has b = 0 and stops at iteration 0.  df_pressure_workspace_bytes and df_pressure_status are shared with the entry points above.
+ * Bit rule: with an all-zero obstacle every `_flags` entry point returns the bits of its counterpart.
+ * A flags byte is believed only where the cell is interior by its index, so no flags content selects memory outside the arrays.
+ * Errors: those of the counterparts, and DF_EINVAL for null flags or flags that overlap an output or the workspace. */
+int df_obstacle_flags2d(const uint8_t* obstacle, uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd, df_stream_t stream);
+int df_obstacle_flags3d(const uint8_t* obstacle, uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, df_stream_t stream);
+int df_advect_mc2d_flags(const float* orig, const float* fwd, const float* vel, float* out, const uint8_t* flags, int64_t B, int64_t Y,
+                         int64_t X, float dt, float vel_scale, int bnd, int clamp_mode, df_stream_t stream);
+int df_advect_mc3d_flags(const float* orig, const float* fwd, const float* vel, float* out, const uint8_t* flags, int64_t B, int64_t Z,
+                         int64_t Y, int64_t X, float dt, float vel_scale, int bnd, int clamp_mode, df_stream_t stream);
+int df_mac_advect_mc2d_flags(const float* vel, const float* fwd, float* out, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, float dt,
+                             int bnd, int clamp_mode, df_stream_t stream);
+int df_mac_advect_mc3d_flags(const float* vel, const float* fwd, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X,
+                             float dt, int bnd, int clamp_mode, df_stream_t stream);
+int df_wall_buoyancy2d_flags(const float* vel, const float* density, float* out, const uint8_t* flags, int64_t B, int64_t Y, int64_t X,
+                             float fx, float fy, int bnd, df_stream_t stream);
+int df_wall_buoyancy3d_flags(const float* vel, const float* density, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
+                             int64_t X, float fx, float fy, float fz, int bnd, df_stream_t stream);
+int df_pressure_init2d_flags(const float* vel, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y,
+                             int64_t X, int bnd, df_stream_t stream);
+int df_pressure_init3d_flags(const float* vel, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z,
+                             int64_t Y, int64_t X, int bnd, df_stream_t stream);
+int df_pressure_cg_direction2d_flags(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k,
+                                     float accuracy, int64_t max_iter, df_stream_t stream);
+int df_pressure_cg_direction3d_flags(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                                     int64_t k, float accuracy, int64_t max_iter, df_stream_t stream);
+int df_pressure_cg_update2d_flags(float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd,
+                                  int64_t k, df_stream_t stream);
+int df_pressure_cg_update3d_flags(float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X,
+                                  int bnd, int64_t k, df_stream_t stream);
+int df_pressure_correct2d_flags(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Y, int64_t X,
+                                int bnd, df_stream_t stream);
+int df_pressure_correct3d_flags(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
+                                int64_t X, int bnd, df_stream_t stream);
 
 #ifdef __cplusplus
 }
