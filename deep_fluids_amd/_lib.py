@@ -171,6 +171,20 @@ SIGNATURES = {
     "df_pressure_cg_update3d_flags": (I32, [P, P, I64, P, I64, I64, I64, I64, I32, I64, P]),
     "df_pressure_correct2d_flags": (I32, [P, P, P, P, I64, I64, I64, I32, P]),
     "df_pressure_correct3d_flags": (I32, [P, P, P, P, I64, I64, I64, I64, I32, P]),
+    "df_mac_advect_sl2d_open": (I32, [P, P, I64, I64, I64, F32, I32, I32, P]),
+    "df_mac_advect_sl3d_open": (I32, [P, P, I64, I64, I64, I64, F32, I32, I32, P]),
+    "df_mac_advect_mc2d_open": (I32, [P, P, P, P, I64, I64, I64, F32, I32, I32, I32, P]),
+    "df_mac_advect_mc3d_open": (I32, [P, P, P, P, I64, I64, I64, I64, F32, I32, I32, I32, P]),
+    "df_wall_buoyancy2d_open": (I32, [P, P, P, P, I64, I64, I64, F32, F32, I32, I32, P]),
+    "df_wall_buoyancy3d_open": (I32, [P, P, P, P, I64, I64, I64, I64, F32, F32, F32, I32, I32, P]),
+    "df_pressure_cg_direction2d_open": (I32, [P, I64, P, I64, I64, I64, I32, I32, I64, F32, I64, P]),
+    "df_pressure_cg_direction3d_open": (I32, [P, I64, P, I64, I64, I64, I64, I32, I32, I64, F32, I64, P]),
+    "df_pressure_correct2d_open": (I32, [P, P, P, P, I64, I64, I64, I32, I32, P]),
+    "df_pressure_correct3d_open": (I32, [P, P, P, P, I64, I64, I64, I64, I32, I32, P]),
+    "df_open_extrapolate2d": (I32, [P, I64, I64, I64, I32, I32, P]),
+    "df_open_extrapolate3d": (I32, [P, I64, I64, I64, I64, I32, I32, P]),
+    "df_density_sphere_source2d": (I32, [P, P, F32, F32, P, I64, I64, I64, P]),
+    "df_density_sphere_source3d": (I32, [P, P, F32, F32, P, I64, I64, I64, I64, P]),
 }
 
 DF_CONV_LRELU, DF_CONV_RESIDUAL, DF_CONV_MASK, DF_CONV_BIAS, DF_CONV_ADDUP, DF_CONV_VALU_ONLY = 1, 2, 4, 8, 16, 32

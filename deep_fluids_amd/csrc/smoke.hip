@@ -25,6 +25,16 @@
 //                     only believed where the cell is interior by its index, so no flags array can send a load outside the arrays.
 //                     With an all-zero obstacle every branch is taken as without flags: the same bits.
 //
+//   open sides        the `_open` entry points are the same kernels again with OPEN set and `open_sides` (bits 0..5: x-, x+, y-, y+, z-,
+//                     z+) as a trailing scalar: a band cell is OPEN when every side it lies beyond is open, a face is LIVE when one of
+//                     its two cells is fluid and the other fluid or open.  All of it is integer compares on the cell's own index; the one
+//                     thing read that was not read before is the low-neighbour bit of the flags byte of a high-side boundary cell (the
+//                     byte itself is loaded by every thread already), and the loads that bit guards are valid by the index alone.
+//                     open_sides = 0 is dispatched to the closed instantiations on the host: the same bits by construction.
+//   open_extrapolate  zero-gradient fill of the open cells, in place: every open cell copies, per component, from the fixed point of a
+//                     clamp of its index; a fixed point only ever copies onto itself, so there is no race.
+//   sphere_source     the source stamp with one sphere per batch entry, the centres read from device memory.
+//
 // Float -> int conversions are taken only of values already known to be inside the grid (advect_common.hpp).
 #include "advect_common.hpp"
 #include "df_common.hpp"
@@ -49,6 +59,42 @@ using dfst::xcd_block;
 template <int D>
 struct VelRec { float v[D]; };
 
+// ---- open sides ----------------------------------------------------------------------------------------------------------------------------
+// open_sides `os`: bit 2a = the low side of axis a is open, bit 2a + 1 = its high side (the order of the flags byte's neighbour bits)
+__device__ __forceinline__ bool open_lo(int os, int a) { return ((os >> (2 * a)) & 1) != 0; }
+__device__ __forceinline__ bool open_hi(int os, int a) { return ((os >> (2 * a + 1)) & 1) != 0; }
+
+// a band cell is open when, on every axis where its index lies outside [bnd, extent - bnd), the side it lies on is open (an edge or a
+// corner shared with a closed side stays wall)
+template <int D>
+__device__ __forceinline__ bool open_cell(const int* p, const int* ext, int bnd, int os) {
+  bool band = false, ok = true;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    const bool lo = p[a] < bnd, hi = p[a] >= ext[a] - bnd;
+    band = band || lo || hi;
+    ok = ok && (!lo || open_lo(os, a)) && (!hi || open_hi(os, a));
+  }
+  return band && ok;
+}
+
+// component a of a band cell sits on the high-side boundary face of axis a: c - e_a is interior by its index
+template <int D>
+__device__ __forceinline__ bool high_face(const int* p, const int* ext, int bnd, int a) {
+  bool r = p[a] == ext[a] - bnd;
+#pragma unroll
+  for (int b = 0; b < D; ++b) if (b != a) r = r && p[b] >= bnd && p[b] < ext[b] - bnd;
+  return r;
+}
+
+// component a of cell c is live although c and c - e_a are not both fluid: a fluid cell whose a- neighbour is open, or an open cell on
+// the high-side boundary face whose a- neighbour is fluid (MASKED: the low-neighbour bit of the cell's own flags byte)
+template <int D, bool MASKED>
+__device__ __forceinline__ bool open_live_face(const int* p, const int* ext, bool interior, unsigned fl, int bnd, int a, int os) {
+  if (interior) return (!MASKED || (fl & kFluid)) && p[a] == bnd && open_lo(os, a);
+  return high_face<D>(p, ext, bnd, a) && open_hi(os, a) && (!MASKED || (fl & lo_bit(a)));
+}
+
 // ---- MAC self-advection ------------------------------------------------------------------------------------------------------------------
 // dt * uface_a of an interior cell: the own component as it is, every other component b the mean of the four faces around the a-face
 template <int D>
@@ -62,16 +108,19 @@ __device__ __forceinline__ void face_displacement(const float* __restrict__ vel,
   }
 }
 
-template <int D>
-__global__ __launch_bounds__(kThreads) void mac_sl_kernel(const float* __restrict__ vel, float* __restrict__ fwd, AdvDims d) {
+// OPEN: also component a of an open cell on the high-side boundary face of axis a (every cell face_displacement and interp read for it
+// is inside the grid: c - e_a is interior, c + e_b stays within the extent because c is inside on every axis b != a)
+template <int D, bool OPEN>
+__global__ __launch_bounds__(kThreads) void mac_sl_kernel(const float* __restrict__ vel, float* __restrict__ fwd, AdvDims d, int os) {
   const int64_t idx = xcd_block(blockIdx.x, gridDim.x, 0) * kThreads + threadIdx.x;
   if (idx >= d.ncell) return;
   const Cell<D> c = decode<D>(idx, d);
+  const int ext[3] = {d.X, d.Y, d.Z};
   VelRec<D> r;
 #pragma unroll
   for (int a = 0; a < D; ++a) {
     r.v[a] = 0.0f;
-    if (c.interior) {
+    if (c.interior || (OPEN && high_face<D>(c.p, ext, d.bnd, a) && open_hi(os, a))) {
       float du[3], pos[3];
       face_displacement<D>(vel, c, d, a, du);
 #pragma unroll
@@ -89,22 +138,24 @@ __device__ __forceinline__ bool kept_face(bool interior, int pa, int bnd, unsign
   return interior && pa > bnd;
 }
 
-template <int D, int MODE, bool MASKED>
+template <int D, int MODE, bool MASKED, bool OPEN>
 __global__ __launch_bounds__(kThreads) void mac_mc_kernel(const float* __restrict__ orig, const float* __restrict__ fwd,
-                                                          float* __restrict__ out, const uint8_t* __restrict__ flags, AdvDims d) {
+                                                          float* __restrict__ out, const uint8_t* __restrict__ flags, AdvDims d, int os) {
   const int64_t idx = xcd_block(blockIdx.x, gridDim.x, 0) * kThreads + threadIdx.x;
   if (idx >= d.ncell) return;
   const Cell<D> c = decode<D>(idx, d);
   const unsigned fl = MASKED ? flags[idx] : 0u;
   const uint8_t* efl = MASKED ? flags + c.base : nullptr;
+  const int ext[3] = {d.X, d.Y, d.Z};
   VelRec<D> r;
 #pragma unroll
   for (int a = 0; a < D; ++a) {
     r.v[a] = 0.0f;
-    if (c.interior) {
+    if (c.interior || (OPEN && high_face<D>(c.p, ext, d.bnd, a) && open_hi(os, a))) {   // where mac_sl_kernel has written fwd
       const float f = fwd[idx * D + a];
       r.v[a] = f;
-      if (kept_face<MASKED>(true, c.p[a], d.bnd, fl, a)) {   // c - e_a is interior (MASKED: fluid) too
+      // c - e_a is interior (MASKED: fluid) too; OPEN: or the face is live
+      if (kept_face<MASKED>(c.interior, c.p[a], d.bnd, fl, a) || (OPEN && open_live_face<D, MASKED>(c.p, ext, c.interior, fl, d.bnd, a, os))) {
         float du[3], pos[3], t[3];
         face_displacement<D>(orig, c, d, a, du);
 #pragma unroll
@@ -158,20 +209,25 @@ __global__ __launch_bounds__(kThreads) void obstacle_flags_kernel(const uint8_t*
 // ---- walls and buoyancy --------------------------------------------------------------------------------------------------------------------
 struct Force { float f[3]; };
 
-template <int D, bool MASKED>
+// OPEN: a live face that is not between two fluid cells is kept without the buoyancy term, and every other component of an open cell is
+// copied through (it holds filled values) -- so an open cell keeps all of its components
+template <int D, bool MASKED, bool OPEN>
 __global__ __launch_bounds__(kThreads) void wall_buoyancy_kernel(const float* vel, const float* __restrict__ rho, float* out,
-                                                                 const uint8_t* __restrict__ flags, Force force, AdvDims d) {
+                                                                 const uint8_t* __restrict__ flags, Force force, AdvDims d, int os) {
   const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
   if (idx >= d.ncell) return;
   const Cell<D> c = decode<D>(idx, d);
   const unsigned fl = MASKED ? flags[idx] : 0u;
   const int64_t st[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
   const VelRec<D> v = *reinterpret_cast<const VelRec<D>*>(vel + idx * D);
+  const int ext[3] = {d.X, d.Y, d.Z};
+  const bool opn = OPEN && !c.interior && open_cell<D>(c.p, ext, d.bnd, os);
   VelRec<D> r;
 #pragma unroll
   for (int a = 0; a < D; ++a) {
-    r.v[a] = 0.0f;
+    r.v[a] = opn ? v.v[a] : 0.0f;
     if (kept_face<MASKED>(c.interior, c.p[a], d.bnd, fl, a)) r.v[a] = v.v[a] + (0.5f * force.f[a]) * (rho[idx] + rho[idx - st[a]]);
+    else if (OPEN && open_live_face<D, MASKED>(c.p, ext, c.interior, fl, d.bnd, a, os)) r.v[a] = v.v[a];
   }
   *reinterpret_cast<VelRec<D>*>(out + idx * D) = r;
 }
@@ -286,9 +342,10 @@ __global__ __launch_bounds__(kThreads) void pressure_init_kernel(const float* __
   }
 }
 
-template <int D, bool MASKED>
+// OPEN: p = 0 in open cells (Dirichlet), so an open neighbour counts in n_c and adds nothing to the sum
+template <int D, bool MASKED, bool OPEN>
 __global__ __launch_bounds__(kThreads) void cg_direction_kernel(PWs w, const uint8_t* __restrict__ flags, PDims d, int par, int first,
-                                                                float accuracy, int max_iter) {
+                                                                float accuracy, int max_iter, int os) {
   __shared__ float lds[4];
   const PCell c = pdecode<D, MASKED>(d, flags);
   const bool writer = c.j == 0 && threadIdx.x == 0;
@@ -324,6 +381,10 @@ __global__ __launch_bounds__(kThreads) void cg_direction_kernel(PWs w, const uin
       if (hi) { const int64_t nb = c.cell + st[a]; sum += r[nb] + beta * po_[nb]; if (!MASKED) ++cnt; }
     }
     if (MASKED) cnt = __popc((c.fl >> 1) & ((1u << (2 * D)) - 1u));   // n_c: the neighbour bits of the D axes, those the loop visited
+    if (OPEN) {
+#pragma unroll
+      for (int a = 0; a < D; ++a) cnt += ((c.p[a] == d.bnd && open_lo(os, a)) ? 1 : 0) + ((c.p[a] + 1 == ext[a] - d.bnd && open_hi(os, a)) ? 1 : 0);
+    }
     const float qv = static_cast<float>(cnt) * pc - sum;
     w.p[par ^ 1][eo + c.cell] = pc;
     w.q[eo + c.cell] = qv;
@@ -374,22 +435,63 @@ __global__ __launch_bounds__(kThreads) void cg_status_kernel(const CgState* __re
   if (threadIdx.x == 0 && count) count[0] = lds[0] + lds[1] + lds[2] + lds[3];
 }
 
-template <int D, bool MASKED>
+// OPEN: live faces are corrected with p as the array holds it (0 outside the fluid), open cells keep their other components
+template <int D, bool MASKED, bool OPEN>
 __global__ __launch_bounds__(kThreads) void pressure_correct_kernel(const float* vel, const float* __restrict__ pr, float* out,
-                                                                    const uint8_t* __restrict__ flags, AdvDims d) {
+                                                                    const uint8_t* __restrict__ flags, AdvDims d, int os) {
   const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
   if (idx >= d.ncell) return;
   const Cell<D> c = decode<D>(idx, d);
   const unsigned fl = MASKED ? flags[idx] : 0u;
   const int64_t st[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
   const VelRec<D> v = *reinterpret_cast<const VelRec<D>*>(vel + idx * D);
+  const int ext[3] = {d.X, d.Y, d.Z};
+  const bool opn = OPEN && !c.interior && open_cell<D>(c.p, ext, d.bnd, os);
   VelRec<D> r;
 #pragma unroll
   for (int a = 0; a < D; ++a) {
-    r.v[a] = 0.0f;
-    if (kept_face<MASKED>(c.interior, c.p[a], d.bnd, fl, a)) r.v[a] = v.v[a] - (pr[idx] - pr[idx - st[a]]);
+    r.v[a] = opn ? v.v[a] : 0.0f;
+    if (kept_face<MASKED>(c.interior, c.p[a], d.bnd, fl, a) || (OPEN && open_live_face<D, MASKED>(c.p, ext, c.interior, fl, d.bnd, a, os)))
+      r.v[a] = v.v[a] - (pr[idx] - pr[idx - st[a]]);    // a live face has p[a] >= bnd >= 1: c - e_a is inside the grid
   }
   *reinterpret_cast<VelRec<D>*>(out + idx * D) = r;
+}
+
+// ---- the fill of the open cells, the sphere stamp ------------------------------------------------------------------------------------------
+// in place: vel[c][a] = vel[c'][a], c' = c clamped to [bnd, extent - bnd] along a and to [bnd, extent - bnd - 1] along every other axis
+template <int D>
+__global__ __launch_bounds__(kThreads) void open_extrapolate_kernel(float* vel, AdvDims d, int os) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (idx >= d.ncell) return;
+  const Cell<D> c = decode<D>(idx, d);
+  const int ext[3] = {d.X, d.Y, d.Z};
+  if (c.interior || !open_cell<D>(c.p, ext, d.bnd, os)) return;
+  VelRec<D> r;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    int q[3] = {0, 0, 0};
+#pragma unroll
+    for (int b = 0; b < D; ++b) q[b] = min(max(c.p[b], d.bnd), ext[b] - d.bnd - (b == a ? 0 : 1));
+    r.v[a] = vel[(c.base + (static_cast<int64_t>(q[2]) * d.Y + q[1]) * d.X + q[0]) * D + a];
+  }
+  *reinterpret_cast<VelRec<D>*>(vel + idx * D) = r;
+}
+
+// out = value where the cell centre lies within radius of the entry's centre, else density; out may be density
+template <int D>
+__global__ __launch_bounds__(kThreads) void sphere_source_kernel(const float* density, const float* __restrict__ centers, float radius,
+                                                                 float value, float* out, AdvDims d) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (idx >= d.ncell) return;
+  const Cell<D> c = decode<D>(idx, d);
+  const float* ctr = centers + c.base / (static_cast<int64_t>(d.X) * d.Y * d.Z) * D;
+  const float dx = (static_cast<float>(c.p[0]) + 0.5f) - ctr[0], dy = (static_cast<float>(c.p[1]) + 0.5f) - ctr[1];
+  float s = dx * dx + dy * dy;
+  if (D == 3) {
+    const float dz = (static_cast<float>(c.p[2]) + 0.5f) - ctr[2];
+    s = s + dz * dz;
+  }
+  out[idx] = s <= radius * radius ? value : density[idx];   // a NaN centre compares false: nothing is stamped
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------------
@@ -443,6 +545,13 @@ int check_apart(const char* fn, const void* ws, const PDims& d, const void* p, i
   return DF_OK;
 }
 
+// open_sides of an `_open` entry point: bits 0..5, and no z bit in 2-D
+int check_open(const char* fn, int dim, int open_sides) {
+  DF_REQUIRE(open_sides >= 0 && open_sides <= 63, DF_EINVAL, "%s: open_sides must be in 0..63 (got %d)", fn, open_sides);
+  DF_REQUIRE(dim == 3 || open_sides < 16, DF_EINVAL, "%s: open_sides %d opens a z side of a 2-D grid", fn, open_sides);
+  return DF_OK;
+}
+
 template <int D>
 int obstacle_flags(const char* fn, const uint8_t* obstacle, uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
                    df_stream_t stream) {
@@ -455,21 +564,22 @@ int obstacle_flags(const char* fn, const uint8_t* obstacle, uint8_t* flags, int6
   return df::launched(fn);
 }
 
-template <int D>
-int mac_sl(const char* fn, const float* vel, float* fwd, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt, int bnd, df_stream_t stream) {
+template <int D, bool OPEN = false>
+int mac_sl(const char* fn, const float* vel, float* fwd, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt, int bnd, df_stream_t stream,
+           int os = 0) {
   DF_REQUIRE(vel && fwd, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : "output");
   AdvDims d;
   unsigned nblk;
   if (int e = plan(fn, D, B, Z, Y, X, bnd, dt, &d, &nblk)) return e;
   DF_REQUIRE(fwd != vel, DF_EINVAL, "%s: the output must not be the input (the step gathers)", fn);
   DF_REQUIRE(aligned4(vel) && aligned4(fwd), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  hipLaunchKernelGGL((mac_sl_kernel<D>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, fwd, d);
+  hipLaunchKernelGGL((mac_sl_kernel<D, OPEN>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, fwd, d, os);
   return df::launched(fn);
 }
 
-template <int D, bool MASKED>
+template <int D, bool MASKED, bool OPEN = false>
 int mac_mc(const char* fn, const float* vel, const float* fwd, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X,
-           float dt, int bnd, int clamp_mode, df_stream_t stream) {
+           float dt, int bnd, int clamp_mode, df_stream_t stream, int os = 0) {
   DF_REQUIRE(vel && fwd && out, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : !fwd ? "input" : "output");
   DF_REQUIRE(clamp_mode == 1 || clamp_mode == 2, DF_EINVAL, "%s: clamp_mode must be 1 or 2 (got %d)", fn, clamp_mode);
   AdvDims d;
@@ -479,14 +589,14 @@ int mac_mc(const char* fn, const float* vel, const float* fwd, float* out, const
   if (int e = check_flags<MASKED>(fn, flags, d.ncell, out, 4 * d.ncell * D, "output")) return e;
   DF_REQUIRE(aligned4(vel) && aligned4(fwd) && aligned4(out), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
   hipStream_t s = df::as_stream(stream);
-  if (clamp_mode == 2) hipLaunchKernelGGL((mac_mc_kernel<D, 2, MASKED>), dim3(nblk), dim3(kThreads), 0, s, vel, fwd, out, flags, d);
-  else hipLaunchKernelGGL((mac_mc_kernel<D, 1, MASKED>), dim3(nblk), dim3(kThreads), 0, s, vel, fwd, out, flags, d);
+  if (clamp_mode == 2) hipLaunchKernelGGL((mac_mc_kernel<D, 2, MASKED, OPEN>), dim3(nblk), dim3(kThreads), 0, s, vel, fwd, out, flags, d, os);
+  else hipLaunchKernelGGL((mac_mc_kernel<D, 1, MASKED, OPEN>), dim3(nblk), dim3(kThreads), 0, s, vel, fwd, out, flags, d, os);
   return df::launched(fn);
 }
 
-template <int D, bool MASKED>
+template <int D, bool MASKED, bool OPEN = false>
 int wall_buoyancy(const char* fn, const float* vel, const float* rho, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
-                  int64_t X, Force f, int bnd, df_stream_t stream) {
+                  int64_t X, Force f, int bnd, df_stream_t stream, int os = 0) {
   DF_REQUIRE(vel && rho && out, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : !rho ? "density" : "output");
   AdvDims d;
   unsigned nblk;
@@ -495,7 +605,8 @@ int wall_buoyancy(const char* fn, const float* vel, const float* rho, float* out
              "%s: the output must not be the density (it is read at a neighbour)", fn);
   if (int e = check_flags<MASKED>(fn, flags, d.ncell, out, 4 * d.ncell * D, "output")) return e;
   DF_REQUIRE(aligned4(vel) && aligned4(rho) && aligned4(out), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  hipLaunchKernelGGL((wall_buoyancy_kernel<D, MASKED>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, rho, out, flags, f, d);
+  hipLaunchKernelGGL((wall_buoyancy_kernel<D, MASKED, OPEN>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, rho, out, flags, f, d,
+                     os);
   return df::launched(fn);
 }
 
@@ -519,9 +630,9 @@ int pressure_init(const char* fn, const float* vel, float* pressure, void* ws, i
   return df::launched(fn);
 }
 
-template <int D, bool MASKED>
+template <int D, bool MASKED, bool OPEN = false>
 int cg_direction(const char* fn, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
-                 int64_t k, float accuracy, int64_t max_iter, df_stream_t stream) {
+                 int64_t k, float accuracy, int64_t max_iter, df_stream_t stream, int os = 0) {
   PDims d;
   unsigned grid;
   if (int e = pplan(fn, D, B, Z, Y, X, bnd, &d, &grid)) return e;
@@ -531,8 +642,8 @@ int cg_direction(const char* fn, void* ws, int64_t ws_bytes, const uint8_t* flag
   DF_REQUIRE(accuracy >= 0.0f, DF_EINVAL, "%s: accuracy must be >= 0", fn);
   if (int e = check_flags<MASKED>(fn, flags, d.n * B, nullptr, 0, "")) return e;
   if (MASKED) if (int e = check_apart(fn, ws, d, flags, d.n * B, "flags")) return e;
-  hipLaunchKernelGGL((cg_direction_kernel<D, MASKED>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), carve(ws, B, d.n, d.nblk), flags, d,
-                     (int)(k & 1), k == 0 ? 1 : 0, accuracy, (int)max_iter);
+  hipLaunchKernelGGL((cg_direction_kernel<D, MASKED, OPEN>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), carve(ws, B, d.n, d.nblk),
+                     flags, d, (int)(k & 1), k == 0 ? 1 : 0, accuracy, (int)max_iter, os);
   return df::launched(fn);
 }
 
@@ -554,9 +665,9 @@ int cg_update(const char* fn, float* pressure, void* ws, int64_t ws_bytes, const
   return df::launched(fn);
 }
 
-template <int D, bool MASKED>
+template <int D, bool MASKED, bool OPEN = false>
 int pressure_correct(const char* fn, const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
-                     int64_t X, int bnd, df_stream_t stream) {
+                     int64_t X, int bnd, df_stream_t stream, int os = 0) {
   DF_REQUIRE(vel && pressure && out, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : !pressure ? "pressure" : "output");
   AdvDims d;
   unsigned nblk;
@@ -565,9 +676,45 @@ int pressure_correct(const char* fn, const float* vel, const float* pressure, fl
              "%s: the output must not be the pressure (it is read at a neighbour)", fn);
   if (int e = check_flags<MASKED>(fn, flags, d.ncell, out, 4 * d.ncell * D, "output")) return e;
   DF_REQUIRE(aligned4(vel) && aligned4(pressure) && aligned4(out), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  hipLaunchKernelGGL((pressure_correct_kernel<D, MASKED>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, pressure, out, flags, d);
+  hipLaunchKernelGGL((pressure_correct_kernel<D, MASKED, OPEN>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, pressure, out, flags,
+                     d, os);
   return df::launched(fn);
 }
+
+template <int D>
+int open_extrapolate(const char* fn, float* vel, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int open_sides, df_stream_t stream) {
+  DF_REQUIRE(vel, DF_EINVAL, "%s: null velocity", fn);
+  if (int e = check_open(fn, D, open_sides)) return e;
+  AdvDims d;
+  unsigned nblk;
+  if (int e = plan(fn, D, B, Z, Y, X, bnd, 0.0f, &d, &nblk)) return e;
+  DF_REQUIRE(aligned4(vel), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  if (!open_sides) return DF_OK;                        // no open cell: nothing to write
+  hipLaunchKernelGGL((open_extrapolate_kernel<D>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, d, open_sides);
+  return df::launched(fn);
+}
+
+template <int D>
+int sphere_source(const char* fn, const float* density, const float* centers, float radius, float value, float* out, int64_t B, int64_t Z,
+                  int64_t Y, int64_t X, df_stream_t stream) {
+  DF_REQUIRE(density && centers && out, DF_EINVAL, "%s: null %s", fn, !density ? "density" : !centers ? "centres" : "output");
+  DF_REQUIRE(B > 0 && Z > 0 && Y > 0 && X > 0, DF_EINVAL, "%s: non-positive extent", fn);
+  DF_REQUIRE(B < (1 << 24) && Z < (1 << 24) && Y < (1 << 24) && X < (1 << 24) && Z * Y * X < (1ll << 40) / B, DF_ESHAPE,
+             "%s: extent too large", fn);
+  const int64_t n = B * Z * Y * X;
+  DF_REQUIRE(ceil_div(n, kThreads) < (1ll << 31), DF_ESHAPE, "%s: extent too large", fn);
+  DF_REQUIRE(apart(centers, 4 * B * D, out, 4 * n), DF_EINVAL, "%s: the centres overlap the output", fn);
+  DF_REQUIRE(aligned4(density) && aligned4(centers) && aligned4(out), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  const AdvDims d{n, (int)Z, (int)Y, (int)X, 0, 0.0f, 1.0f};
+  hipLaunchKernelGGL((sphere_source_kernel<D>), dim3((unsigned)ceil_div(n, kThreads)), dim3(kThreads), 0, df::as_stream(stream), density,
+                     centers, radius, value, out, d);
+  return df::launched(fn);
+}
+
+// an `_open` entry point: the closed instantiation for open_sides = 0 (the same bits by construction), flags may be null (no obstacles)
+#define DF_OPEN_CALL(F, D, ...)                                                                                       \
+  (open_sides == 0 ? (flags ? F<D, true, false>(__VA_ARGS__) : F<D, false, false>(__VA_ARGS__))                      \
+                   : (flags ? F<D, true, true>(__VA_ARGS__, open_sides) : F<D, false, true>(__VA_ARGS__, open_sides)))
 
 }  // namespace
 
@@ -709,6 +856,82 @@ int df_pressure_correct2d_flags(const float* vel, const float* pressure, float* 
 int df_pressure_correct3d_flags(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
                                 int64_t X, int bnd, df_stream_t stream) {
   return pressure_correct<3, true>("df_pressure_correct3d_flags", vel, pressure, out, flags, B, Z, Y, X, bnd, stream);
+}
+
+// ---- the same steps with open sides: flags may be null (no obstacles), open_sides follows bnd ----
+int df_mac_advect_sl2d_open(const float* vel, float* fwd, int64_t B, int64_t Y, int64_t X, float dt, int bnd, int open_sides,
+                            df_stream_t stream) {
+  const char* fn = "df_mac_advect_sl2d_open";
+  if (int e = check_open(fn, 2, open_sides)) return e;
+  return open_sides ? mac_sl<2, true>(fn, vel, fwd, B, 1, Y, X, dt, bnd, stream, open_sides) : mac_sl<2>(fn, vel, fwd, B, 1, Y, X, dt, bnd, stream);
+}
+int df_mac_advect_sl3d_open(const float* vel, float* fwd, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt, int bnd, int open_sides,
+                            df_stream_t stream) {
+  const char* fn = "df_mac_advect_sl3d_open";
+  if (int e = check_open(fn, 3, open_sides)) return e;
+  return open_sides ? mac_sl<3, true>(fn, vel, fwd, B, Z, Y, X, dt, bnd, stream, open_sides) : mac_sl<3>(fn, vel, fwd, B, Z, Y, X, dt, bnd, stream);
+}
+int df_mac_advect_mc2d_open(const float* vel, const float* fwd, float* out, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, float dt,
+                            int bnd, int open_sides, int clamp_mode, df_stream_t stream) {
+  const char* fn = "df_mac_advect_mc2d_open";
+  if (int e = check_open(fn, 2, open_sides)) return e;
+  return DF_OPEN_CALL(mac_mc, 2, fn, vel, fwd, out, flags, B, 1, Y, X, dt, bnd, clamp_mode, stream);
+}
+int df_mac_advect_mc3d_open(const float* vel, const float* fwd, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X,
+                            float dt, int bnd, int open_sides, int clamp_mode, df_stream_t stream) {
+  const char* fn = "df_mac_advect_mc3d_open";
+  if (int e = check_open(fn, 3, open_sides)) return e;
+  return DF_OPEN_CALL(mac_mc, 3, fn, vel, fwd, out, flags, B, Z, Y, X, dt, bnd, clamp_mode, stream);
+}
+int df_wall_buoyancy2d_open(const float* vel, const float* density, float* out, const uint8_t* flags, int64_t B, int64_t Y, int64_t X,
+                            float fx, float fy, int bnd, int open_sides, df_stream_t stream) {
+  const char* fn = "df_wall_buoyancy2d_open";
+  if (int e = check_open(fn, 2, open_sides)) return e;
+  return DF_OPEN_CALL(wall_buoyancy, 2, fn, vel, density, out, flags, B, 1, Y, X, Force{{fx, fy, 0.0f}}, bnd, stream);
+}
+int df_wall_buoyancy3d_open(const float* vel, const float* density, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
+                            int64_t X, float fx, float fy, float fz, int bnd, int open_sides, df_stream_t stream) {
+  const char* fn = "df_wall_buoyancy3d_open";
+  if (int e = check_open(fn, 3, open_sides)) return e;
+  return DF_OPEN_CALL(wall_buoyancy, 3, fn, vel, density, out, flags, B, Z, Y, X, Force{{fx, fy, fz}}, bnd, stream);
+}
+int df_pressure_cg_direction2d_open(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd,
+                                    int open_sides, int64_t k, float accuracy, int64_t max_iter, df_stream_t stream) {
+  const char* fn = "df_pressure_cg_direction2d_open";
+  if (int e = check_open(fn, 2, open_sides)) return e;
+  return DF_OPEN_CALL(cg_direction, 2, fn, ws, ws_bytes, flags, B, 1, Y, X, bnd, k, accuracy, max_iter, stream);
+}
+int df_pressure_cg_direction3d_open(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                                    int open_sides, int64_t k, float accuracy, int64_t max_iter, df_stream_t stream) {
+  const char* fn = "df_pressure_cg_direction3d_open";
+  if (int e = check_open(fn, 3, open_sides)) return e;
+  return DF_OPEN_CALL(cg_direction, 3, fn, ws, ws_bytes, flags, B, Z, Y, X, bnd, k, accuracy, max_iter, stream);
+}
+int df_pressure_correct2d_open(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Y, int64_t X,
+                               int bnd, int open_sides, df_stream_t stream) {
+  const char* fn = "df_pressure_correct2d_open";
+  if (int e = check_open(fn, 2, open_sides)) return e;
+  return DF_OPEN_CALL(pressure_correct, 2, fn, vel, pressure, out, flags, B, 1, Y, X, bnd, stream);
+}
+int df_pressure_correct3d_open(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
+                               int64_t X, int bnd, int open_sides, df_stream_t stream) {
+  const char* fn = "df_pressure_correct3d_open";
+  if (int e = check_open(fn, 3, open_sides)) return e;
+  return DF_OPEN_CALL(pressure_correct, 3, fn, vel, pressure, out, flags, B, Z, Y, X, bnd, stream);
+}
+int df_open_extrapolate2d(float* vel, int64_t B, int64_t Y, int64_t X, int bnd, int open_sides, df_stream_t stream) {
+  return open_extrapolate<2>("df_open_extrapolate2d", vel, B, 1, Y, X, bnd, open_sides, stream);
+}
+int df_open_extrapolate3d(float* vel, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int open_sides, df_stream_t stream) {
+  return open_extrapolate<3>("df_open_extrapolate3d", vel, B, Z, Y, X, bnd, open_sides, stream);
+}
+int df_density_sphere_source2d(const float* density, const float* centers, float radius, float value, float* out, int64_t B, int64_t Y,
+                               int64_t X, df_stream_t stream) {
+  return sphere_source<2>("df_density_sphere_source2d", density, centers, radius, value, out, B, 1, Y, X, stream);
+}
+int df_density_sphere_source3d(const float* density, const float* centers, float radius, float value, float* out, int64_t B, int64_t Z,
+                               int64_t Y, int64_t X, df_stream_t stream) {
+  return sphere_source<3>("df_density_sphere_source3d", density, centers, radius, value, out, B, Z, Y, X, stream);
 }
 
 }  // extern "C"

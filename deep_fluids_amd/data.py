@@ -55,7 +55,7 @@ class BatchManager(object):
 
             def sortf(p):
                 n = os.path.basename(p)[:-4].split("_")
-                return int(n[0]) * nf + int(n[1])
+                return int(n[0]) * nf + int(n[1]) if len(n) > 1 else int(n[0])      # "%d.npz": one scene (scene/smoke3_rot.py)
             self.paths = sorted(glob(pattern), key=sortf)
         else:
             self.paths = sorted(glob(pattern))
@@ -300,11 +300,16 @@ def generate_smoke_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="sr
     write it in the reference's on-disk format: ``args.txt`` with every argument of the scene script, ``v/%d_%d_%d.npz`` (x [Y,X,2]
     float32 velocity after frame t, y = [p0, p1, t]) and ``v_range.txt``.  The keyword arguments are the script's, with its defaults.
     Every scene is one batch entry of ``ops.simulate_smoke`` (``scenes_per_batch`` splits the set into chunks; an entry's result does
-    not depend on the rest of its batch).  The step is this library's restatement (include/deepfluids_hip.h), not mantaflow's: closed
-    box only (``open_bound=True`` is refused), plain CG in place of MIC(0)-preconditioned CG.  Returns the number of files written."""
+    not depend on the rest of its batch).  The step is this library's restatement (include/deepfluids_hip.h), not mantaflow's: plain CG
+    in place of MIC(0)-preconditioned CG.  ``open_bound``: a string of the open sides, ``'xXyY'`` being what the script's
+    ``--open_bound True`` opens, simulated with this library's open-side rules and zero-gradient fill (tests/smoke_open_ref.py), not
+    mantaflow's outflow.  The bare ``True`` is still refused: it would promise the script's mantaflow outflow, which is not restated;
+    name the sides.  Returns the number of files written."""
     from . import ops
-    if open_bound:
-        raise NotImplementedError("generate_smoke_dataset: open_bound=True is not restated (closed box only)")
+    if open_bound is True:
+        raise NotImplementedError("generate_smoke_dataset: open_bound=True (mantaflow's outflow) is not restated; pass the open sides as "
+                                  "a string, 'xXyY' for the script's, to simulate them with this library's open-side rules")
+    sides = ops.open_sides(open_bound, 2)
     if num_param != 3 or (p0, p1, p2) != ("src_x_pos", "src_radius", "frames"):
         raise ValueError("generate_smoke_dataset: the scene has the parameters (src_x_pos, src_radius, frames)")
     max_frames = num_frames - 1 if max_frames is None else max_frames
@@ -336,7 +341,7 @@ def generate_smoke_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="sr
         d0 = torch.zeros((len(part), Y, X), dtype=torch.float32, device=device)
         v0 = torch.zeros((len(part), Y, X, 2), dtype=torch.float32, device=device)
         frames = ops.simulate_smoke(d0, v0, num_frames, dt=time_step, source=mask, force=force, order=adv_order, clamp_mode=clamp_mode,
-                                    bnd=bWidth, accuracy=accuracy, stack=False)
+                                    bnd=bWidth, accuracy=accuracy, stack=False, open_bound=sides)
         for t, (_, v) in enumerate(frames):
             vh = v.cpu().numpy()
             v_range = [min(v_range[0], float(vh.min())), max(v_range[1], float(vh.max()))]
@@ -363,11 +368,15 @@ def generate_smoke3_obs_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p
     obs_z_pos)`` of radius ``X * obs_radius``; the buoyancy is (0, p1, 0).  Every scene is one batch entry of ``ops.simulate_smoke``.
     The buoyancy is one number per launch, so a chunk holds the scenes of ONE buoyancy value (all obstacle positions: 11 by default);
     ``scenes_per_batch`` splits a chunk further, and an entry's result does not depend on the rest of its batch.  The step is this
-    library's restatement (include/deepfluids_hip.h), not mantaflow's: closed box only (``open_bound=True`` is refused), plain CG in
-    place of MIC(0)-preconditioned CG.  Returns the number of files written."""
+    library's restatement (include/deepfluids_hip.h), not mantaflow's: plain CG in place of MIC(0)-preconditioned CG.  The script hands
+    ``open_bound`` to advectSemiLagrange only and never calls setOpenBound, so its ``True`` names no sides and is still refused; a
+    string of ``xXyYzZ`` opens those sides with this library's open-side rules (tests/smoke_open_ref.py).  Returns the number of files
+    written."""
     from . import ops
-    if open_bound:
-        raise NotImplementedError("generate_smoke3_obs_dataset: open_bound=True is not restated (closed box only)")
+    if open_bound is True:
+        raise NotImplementedError("generate_smoke3_obs_dataset: open_bound=True names no sides (the script never calls setOpenBound); pass "
+                                  "the open sides as a string of xXyYzZ")
+    sides = ops.open_sides(open_bound, 3)
     if num_param != 3 or (p0, p1, p2) != ("obs_x_pos", "buoyancy", "frames"):
         raise ValueError("generate_smoke3_obs_dataset: the scene has the parameters (obs_x_pos, buoyancy, frames)")
     max_frames = num_frames - 1 if max_frames is None else max_frames
@@ -400,7 +409,8 @@ def generate_smoke3_obs_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p
             d0 = torch.zeros((len(part),) + shape, dtype=torch.float32, device=device)
             v0 = torch.zeros((len(part),) + shape + (3,), dtype=torch.float32, device=device)
             frames = ops.simulate_smoke(d0, v0, num_frames, dt=time_step, source=source, force=force, order=adv_order, clamp_mode=clamp_mode,
-                                        bnd=bWidth, accuracy=accuracy, stack=False, obstacle=ops.obstacle_flags(obs, bWidth))
+                                        bnd=bWidth, accuracy=accuracy, stack=False, obstacle=ops.obstacle_flags(obs, bWidth),
+                                        open_bound=sides)
             for t, (_, v) in enumerate(frames):
                 vh = v.cpu().numpy()
                 v_range = [min(v_range[0], float(vh.min())), max(v_range[1], float(vh.max()))]
@@ -411,3 +421,129 @@ def generate_smoke3_obs_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p
         f.write("%.3f\n" % v_range[0])
         f.write("%.3f" % v_range[1])
     return written
+
+
+# ---- the moving-source scenes (scene/smoke3_rot.py, scene/smoke3_mov.py): open sides, a sphere source whose centre changes every frame ----
+def smooth_source_paths(num_scenes, num_frames, lo, hi, seed=123, modes=3):
+    """Seeded smooth source paths [num_scenes, num_frames, 2] (x and z as fractions of the grid) inside ``[lo, hi]``: per scene and
+    coordinate a sum of ``modes`` sines of random period (100..400 frames), phase and weight, normalised by the sum of the weights.
+    This is the project's own stand-in: it is NOT the reference's tileable Perlin noise (scene/perlin.py), only a path of the same
+    kind -- smooth, bounded, different per scene and reproducible from the seed."""
+    rng = np.random.RandomState(seed)
+    t = np.arange(num_frames, dtype=np.float64)
+    out = np.empty((num_scenes, num_frames, 2), np.float64)
+    for i in range(num_scenes):
+        for c in range(2):
+            w = rng.uniform(0.4, 1.0, modes)
+            period = rng.uniform(100.0, 400.0, modes)
+            phase = rng.uniform(0.0, 2 * np.pi, modes)
+            n = (w[:, None] * np.sin(2 * np.pi * t[None] / period[:, None] + phase[:, None])).sum(axis=0) / w.sum()      # [-1, 1]
+            out[i, :, c] = (n + 1) * 0.5 * (hi - lo) + lo
+    return out
+
+
+def _simulate_moving_source(root, args, positions, name, src_y_pos, src_radius, num_frames, resolution, buoyancy, bWidth, open_bound,
+                            time_step, adv_order, clamp_mode, scenes_per_batch, accuracy, device):
+    """what the two generators below share: args.txt, the frames of every scene (scenes are batch entries), v_range.txt, n.npz"""
+    from . import ops
+    os.makedirs(os.path.join(root, "v"), exist_ok=True)
+    with open(os.path.join(root, "args.txt"), "w") as f:
+        for k, v in args:
+            f.write("%s: %s\n" % (k, v))
+    X, Y, Z = (int(n) for n in resolution)
+    shape = (Z, Y, X)
+    S, T = positions.shape[:2]
+    sides = ops.open_sides(open_bound, 3)
+    force = ops.default_buoyancy_force(shape, time_step, gravity=buoyancy)
+    chunk = S if not scenes_per_batch else int(scenes_per_batch)
+    v_range = [np.finfo(np.float64).max, np.finfo(np.float64).min]
+    written = 0
+    for c0 in range(0, S, chunk):
+        part = list(range(c0, min(c0 + chunk, S)))
+        pos = positions[part]                                                        # [b, T, 2]
+        centers = np.stack([X * pos[..., 0], np.full(pos.shape[:2], Y * src_y_pos), Z * pos[..., 1]], axis=-1)      # gs * (px, y, pz)
+        src = ops.SphereSource(torch.from_numpy(np.ascontiguousarray(centers.transpose(1, 0, 2), dtype=np.float32)).to(device), X * src_radius)
+        d0 = torch.zeros((len(part),) + shape, dtype=torch.float32, device=device)
+        v0 = torch.zeros((len(part),) + shape + (3,), dtype=torch.float32, device=device)
+        frames = ops.simulate_smoke(d0, v0, T, dt=time_step, source=src, force=force, order=adv_order, clamp_mode=clamp_mode, bnd=bWidth,
+                                    accuracy=accuracy, stack=False, open_bound=sides)
+        for t, (_, v) in enumerate(frames):
+            vh = v.cpu().numpy()
+            v_range = [min(v_range[0], float(vh.min())), max(v_range[1], float(vh.max()))]
+            for e, i in enumerate(part):
+                y = np.full((2, num_frames), -1.0)                                   # the scripts' deque([-1]*num_frames, num_frames)
+                y[:, num_frames - 1 - t:] = positions[i, :t + 1].T
+                np.savez_compressed(os.path.join(root, "v", name(i, t)), x=vh[e], y=y)
+                written += 1
+    np.savez_compressed(os.path.join(root, "n.npz"), nx=positions[..., 0], nz=positions[..., 1])
+    with open(os.path.join(root, "v_range.txt"), "w") as f:
+        f.write("%.3f\n" % v_range[0])
+        f.write("%.3f" % v_range[1])
+    return written
+
+
+def generate_smoke3_rot_dataset(root, num_param=1, path_format="%d.npz", p0="frames", min_src_pos=0.1, max_src_pos=0.9, src_y_pos=0.1,
+                                src_radius=0.08, circle_radius=0.25, circle_period=100, min_frames=0, max_frames=None, num_frames=500,
+                                num_simulations=None, num_dof=2, resolution_x=48, resolution_y=72, resolution_z=48, buoyancy=-4e-3, bWidth=1,
+                                open_bound="xXyYzZ", time_step=0.5, adv_order=2, clamp_mode=2, accuracy=1e-4, device="cuda"):
+    """Simulate the reference's rotating-source set (scene/smoke3_rot.py, ``smoke3_rot_f500``) on the GPU and write it as that script
+    does: ``args.txt`` with every argument of the script, ``v/%d.npz`` (x [Z,Y,X,3] float32 velocity after frame t, y [2, num_frames] =
+    the last ``num_frames`` source positions (px; pz) as fractions of the grid, oldest first, padded in front with -1), ``n.npz`` (nx,
+    nz [1, num_frames]) and ``v_range.txt``.  One scene: a sphere of radius ``X * src_radius`` at ``gs * (px, src_y_pos, pz)`` with
+    ``px = 0.5 + circle_radius * cos(2 pi t / circle_period)``, ``pz`` the sine, all sides open by default.  The keyword arguments are
+    the script's, with its defaults (``max_frames`` and ``num_simulations`` follow ``num_frames`` unless given).  The step is this
+    library's restatement (include/deepfluids_hip.h: open sides, zero-gradient fill, plain CG; tests/smoke_open_ref.py), NOT
+    mantaflow's.  Returns the number of files written."""
+    if num_param != 1 or p0 != "frames":
+        raise ValueError("generate_smoke3_rot_dataset: the scene has the one parameter frames")
+    max_frames = num_frames - 1 if max_frames is None else max_frames
+    num_simulations = num_frames if num_simulations is None else num_simulations
+    args = [("log_dir", root), ("num_param", num_param), ("path_format", path_format), ("p0", p0), ("min_src_pos", min_src_pos),
+            ("max_src_pos", max_src_pos), ("src_y_pos", src_y_pos), ("src_radius", src_radius), ("circle_radius", circle_radius),
+            ("circle_period", circle_period), ("min_frames", min_frames), ("max_frames", max_frames), ("num_frames", num_frames),
+            ("num_simulations", num_simulations), ("num_dof", num_dof), ("resolution_x", resolution_x), ("resolution_y", resolution_y),
+            ("resolution_z", resolution_z), ("buoyancy", buoyancy), ("bWidth", bWidth), ("open_bound", open_bound), ("time_step", time_step),
+            ("adv_order", adv_order), ("clamp_mode", clamp_mode)]
+    t = np.arange(num_frames)
+    positions = np.stack([0.5 + circle_radius * np.cos(t * 2 * np.pi / circle_period), 0.5 + circle_radius * np.sin(t * 2 * np.pi / circle_period)],
+                         axis=-1)[None]
+    return _simulate_moving_source(root, args, positions, lambda i, t: path_format % t, src_y_pos, src_radius, num_frames,
+                                   (resolution_x, resolution_y, resolution_z), buoyancy, bWidth, open_bound, time_step, adv_order, clamp_mode,
+                                   None, accuracy, device)
+
+
+def generate_smoke3_mov_dataset(root, num_param=2, path_format="%d_%d.npz", p0="scenes", p1="frames", min_src_pos=0.1, max_src_pos=0.9,
+                                src_y_pos=0.1, src_radius=0.08, min_scenes=0, max_scenes=None, num_scenes=200, min_frames=0, max_frames=None,
+                                num_frames=400, num_simulations=None, num_dof=2, resolution_x=48, resolution_y=72, resolution_z=48,
+                                buoyancy=-4e-3, bWidth=1, open_bound="xXyYzZ", time_step=0.5, adv_order=2, clamp_mode=2, nscale=0.01,
+                                nrepeat=1000, nseed=123, positions=None, scenes_per_batch=None, accuracy=1e-4, device="cuda"):
+    """Simulate the reference's moving-source set (scene/smoke3_mov.py, ``smoke3_mov200_f400``) on the GPU and write it as that script
+    does: ``args.txt`` with every argument of the script, ``v/%d_%d.npz`` (scene, frame: x [Z,Y,X,3] float32 velocity after frame t, y
+    [2, num_frames] = the last ``num_frames`` source positions (px; pz), oldest first, padded in front with -1), ``n.npz`` (nx, nz
+    [num_scenes, num_frames]) and ``v_range.txt``.  Scenes are batch entries of ``ops.simulate_smoke`` (``scenes_per_batch`` splits
+    them into chunks; an entry's result does not depend on the rest of its batch).  ``positions`` [num_scenes, num_frames, 2]: the
+    source paths (px, pz) as fractions of the grid.  The default is ``smooth_source_paths(num_scenes, num_frames, min_src_pos,
+    max_src_pos, seed=nseed)``, a seeded smooth path of this project's own: it is NOT the reference's Perlin noise, and ``nscale`` /
+    ``nrepeat`` are written to args.txt but do not shape it.  The step is this library's restatement (include/deepfluids_hip.h: open
+    sides, zero-gradient fill, plain CG; tests/smoke_open_ref.py), NOT mantaflow's.  Returns the number of files written."""
+    if num_param != 2 or (p0, p1) != ("scenes", "frames"):
+        raise ValueError("generate_smoke3_mov_dataset: the scene has the parameters (scenes, frames)")
+    max_scenes = num_scenes - 1 if max_scenes is None else max_scenes
+    max_frames = num_frames - 1 if max_frames is None else max_frames
+    num_simulations = num_scenes * num_frames if num_simulations is None else num_simulations
+    if positions is None:
+        positions = smooth_source_paths(num_scenes, num_frames, min_src_pos, max_src_pos, seed=nseed)
+    positions = np.asarray(positions, np.float64)
+    if positions.shape != (num_scenes, num_frames, 2):
+        raise ValueError("generate_smoke3_mov_dataset: positions must be [num_scenes, num_frames, 2] = %s, got %s" %
+                         ((num_scenes, num_frames, 2), positions.shape))
+    args = [("log_dir", root), ("num_param", num_param), ("path_format", path_format), ("p0", p0), ("p1", p1), ("min_src_pos", min_src_pos),
+            ("max_src_pos", max_src_pos), ("src_y_pos", src_y_pos), ("src_radius", src_radius), ("min_scenes", min_scenes),
+            ("max_scenes", max_scenes), ("num_scenes", num_scenes), ("min_frames", min_frames), ("max_frames", max_frames),
+            ("num_frames", num_frames), ("num_simulations", num_simulations), ("num_dof", num_dof), ("resolution_x", resolution_x),
+            ("resolution_y", resolution_y), ("resolution_z", resolution_z), ("buoyancy", buoyancy), ("bWidth", bWidth),
+            ("open_bound", open_bound), ("time_step", time_step), ("adv_order", adv_order), ("clamp_mode", clamp_mode), ("nscale", nscale),
+            ("nrepeat", nrepeat), ("nseed", nseed)]
+    return _simulate_moving_source(root, args, positions, lambda i, t: path_format % (i, t), src_y_pos, src_radius, num_frames,
+                                   (resolution_x, resolution_y, resolution_z), buoyancy, bWidth, open_bound, time_step, adv_order, clamp_mode,
+                                   scenes_per_batch, accuracy, device)

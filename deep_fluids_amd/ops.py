@@ -31,6 +31,7 @@ __all__ = [
     "denorm_img", "plane_view", "denorm_img3", "plane_view_np", "velocity_views3", "add_channels", "remove_channels",
     "advect", "advect_sequence", "advect_workspace", "density_image", "sphere_mask",
     "advect_velocity", "wall_buoyancy", "solve_pressure", "pressure_workspace", "smoke_step", "simulate_smoke", "default_buoyancy_force", "default_max_iter", "obstacle_flags", "ObstacleFlags",
+    "open_sides", "SphereSource",
     "advect_particles", "particle_cells", "particle_levelset", "liquid_sequence", "seed_particles", "box_levelset", "sphere_levelset",
     "variable_scope", "get_variables", "get_variable", "reset_variables", "set_random_seed", "all_variables",
 ]
@@ -1694,6 +1695,89 @@ def _source_mask(source, like):
     return m.contiguous()
 
 
+class SphereSource(object):
+    """A sphere source whose centre is read from device memory: ``centers`` [B,D] in cell units (x, y[, z]), one sphere per batch entry,
+    or [T,B,D] for the sequence forms (``advect_sequence``, ``simulate_smoke``: frame t stamps ``centers[t]``); ``radius`` in cells.  A
+    tensor, or anything ``torch.as_tensor`` converts -- once, here.  ``source=`` of ``advect``, ``advect_sequence``, ``smoke_step`` and
+    ``simulate_smoke`` accepts it beside a mask; it goes through ``df_density_sphere_source*``, no mask is built on the host."""
+
+    def __init__(self, centers, radius):
+        c = centers if isinstance(centers, torch.Tensor) else torch.as_tensor(np.asarray(centers, dtype=np.float32))
+        if c.dim() not in (2, 3) or c.shape[-1] not in (2, 3):
+            raise ValueError("SphereSource: centers must be [B,D] or [T,B,D] with D = 2 | 3, got %s" % (tuple(c.shape),))
+        self.centers = c.detach().to(dtype=torch.float32)
+        self.radius = float(radius)
+
+    def frame(self, t):
+        """the source of frame ``t``: [T,B,D] centres are indexed, [B,D] centres serve every frame"""
+        if self.centers.dim() == 2:
+            return self
+        if not 0 <= t < self.centers.shape[0]:
+            raise ValueError("SphereSource: frame %d of %d" % (t, self.centers.shape[0]))
+        return SphereSource(self.centers[t], self.radius)
+
+    def on(self, like):
+        """centres [B,D] on ``like``'s device, contiguous, checked against its shape [B,(Z,)Y,X]"""
+        c = self.centers
+        if c.dim() != 2 or tuple(c.shape) != (like.shape[0], like.dim() - 1):
+            raise ValueError("SphereSource: centres %s do not fit a density %s (one step takes [B,D])" % (tuple(c.shape), tuple(like.shape)))
+        return c.to(like.device).contiguous()
+
+
+def _stamp(d, source, value, out):
+    """``source`` (a mask or a SphereSource) stamped into ``d`` -> ``out`` (which may be ``d``)"""
+    if isinstance(source, SphereSource):
+        call("df_density_sphere_source%dd" % (d.dim() - 1), _ptr(d), _ptr(source.on(d)), source.radius, float(value), _ptr(out),
+             *(list(d.shape) + [_stream()]))
+    else:
+        call("df_density_source", _ptr(d), _ptr(_source_mask(source, d)), float(value), _ptr(out), d.numel(), _stream())
+
+
+def _source_arg(source, like):
+    """what the sequence forms hold: a mask on the device, packed once, or the SphereSource with its centres on the device"""
+    if source is None:
+        return None
+    if isinstance(source, SphereSource):
+        return SphereSource(source.centers.to(like.device), source.radius)
+    return _source_mask(source, like)
+
+
+def _source_frame(source, t):
+    return source.frame(t) if isinstance(source, SphereSource) else source
+
+
+def open_sides(spec, dim):
+    """The ``open_sides`` bits of include/deepfluids_hip.h (bit 0..5: x-, x+, y-, y+, z-, z+) from what the reference's scene scripts
+    pass to ``setOpenBound``: a string of ``xXyYzZ`` (lower case: the low side, upper case: the high side), ``True`` (every side of the
+    grid's ``dim`` axes), ``False`` / ``None`` / ``''`` (closed), or the bits themselves."""
+    if dim not in (2, 3):
+        raise ValueError("open_sides: dim must be 2 or 3, got %r" % (dim,))
+    if spec is None or spec is False or (isinstance(spec, str) and spec == ""):
+        return 0
+    if spec is True:
+        return (1 << (2 * dim)) - 1
+    if isinstance(spec, str):
+        bits = 0
+        for ch in spec:
+            at = "xXyYzZ".find(ch)
+            if at < 0:
+                raise ValueError("open_sides: %r is not one of xXyYzZ (in %r)" % (ch, spec))
+            bits |= 1 << at
+    elif isinstance(spec, (int, np.integer)):
+        bits = int(spec)
+        if not 0 <= bits <= 63:
+            raise ValueError("open_sides: bits must be in 0..63, got %r" % (spec,))
+    else:
+        raise ValueError("open_sides: expected a string of xXyYzZ, a bool, None or the bits, got %r" % (spec,))
+    if dim == 2 and bits >= 16:
+        raise ValueError("open_sides: %r opens a z side of a 2-D grid" % (spec,))
+    return bits
+
+
+def _fill_open(v, nd, bnd, osd):
+    call("df_open_extrapolate%dd" % nd, _ptr(v), *(list(v.shape[:-1]) + [int(bnd), osd, _stream()]))
+
+
 # Obstacles: a uint8 / bool mask [B,(Z,)Y,X] (nonzero = solid; [(Z,)Y,X] is shared by the batch) is packed once into the flags of
 # include/deepfluids_hip.h (one byte per cell: the cell is fluid, each of its six neighbours is fluid), which every `_flags` kernel reads.
 class ObstacleFlags(torch.Tensor):
@@ -1802,7 +1886,8 @@ def advect(density, vel, dt, order=2, clamp_mode=2, bnd=1, vel_scale=1.0, source
     ``advectSemiLagrange(order, boundaryWidth=bnd, clampMode=clamp_mode)`` as the reference's scene scripts call it
     (scene/smoke_pos_size.py:99-101) -- NOT bit-identical to mantaflow, which cannot be run here; include/deepfluids_hip.h holds the
     definition that is tested.  ``vel_scale`` multiplies the velocities inside the kernel (``x_range`` for a generator's normalised
-    output); ``source`` is an optional mask [B,(Z,)Y,X] (or one broadcastable to it) of cells set to ``source_value`` before the step.
+    output); ``source`` is an optional mask [B,(Z,)Y,X] (or one broadcastable to it) of cells set to ``source_value`` before the step,
+    or a ``SphereSource`` (one sphere per batch entry, centres on the device).
     Returns a new density (``out`` if given; it must not be ``density``).  ``workspace``: see ``advect_workspace``.  ``obstacle``: a
     mask of solid cells or the flags of ``obstacle_flags``; the MacCormack correction and its clamp then run over fluid cells only (the
     first-order value and the source stamp ignore obstacles, as mantaflow's do)."""
@@ -1823,7 +1908,7 @@ def advect(density, vel, dt, order=2, clamp_mode=2, bnd=1, vel_scale=1.0, source
         off = 0
         if source is not None:
             stamped = ws[:n].view(d.shape)
-            call("df_density_source", _ptr(d), _ptr(_source_mask(source, d)), float(source_value), _ptr(stamped), n, _stream())
+            _stamp(d, source, source_value, stamped)
             d, off = stamped, n
         fwd = ws[off:off + n] if order == 2 else None
         _advect_step(d, v, nd, out, fwd, float(dt), order, clamp_mode, int(bnd), float(vel_scale), flags)
@@ -1861,14 +1946,13 @@ def advect_sequence(density0, vels, dt, order=2, clamp_mode=2, bnd=1, vel_scale=
         cur = cur.clone()
         nxt = torch.empty_like(cur)
         fwd = torch.empty_like(cur) if order == 2 else None
-        mask = _source_mask(source, cur) if source is not None else None
+        mask = _source_arg(source, cur)                    # a SphereSource [T,B,D] stamps centers[t] before step t
         flags = _obstacle_arg(obstacle, cur.shape, bnd, "advect_sequence") if obstacle is not None else None
-        n = cur.numel()
         imgs = _u8((T, cur.shape[0], cur.shape[-2], cur.shape[-1]), cur) if images else None
         for t in range(T):
             _, v, _ = _advect_dims(cur, vels[t])
             if mask is not None:
-                call("df_density_source", _ptr(cur), _ptr(mask), float(source_value), _ptr(cur), n, _stream())
+                _stamp(cur, _source_frame(mask, t), source_value, cur)
             _advect_step(cur, v, nd, nxt, fwd, float(dt), order, clamp_mode, int(bnd), float(vel_scale), flags)
             cur, nxt = nxt, cur
             if images:
@@ -1898,7 +1982,11 @@ def sphere_mask(shape, center, radius, device=None):
 #      and buoyancy, a conjugate-gradient pressure projection.  Inference only, no autograd.  The step is defined in
 #      include/deepfluids_hip.h; parity is with the fp64 restatement of tests/smoke_ref.py, NOT with mantaflow, which cannot be run here.
 #      Obstacles (the reference's scene/smoke3_obs_buo.py) enter through the ``obstacle=`` keyword: "interior" then reads "fluid".
-#      Left out: open bounds, outflow, noise-modulated inflow (the reference's other 3-D scenes need them), the MIC(0) preconditioner ----
+#      Open sides (scene/smoke3_rot.py, smoke3_mov.py, smoke3_vel_buo.py, the open_bound option of smoke_pos_size.py) enter through
+#      ``open_bound=`` (``open_sides`` parses it) and combine with obstacles; a moving source is a ``SphereSource``.  Parity is with
+#      tests/smoke_open_ref.py, NOT with mantaflow.
+#      Left out: noise-modulated inflow (densityInflow) and the inflow velocity stamp of scene/smoke3_vel_buo.py, mantaflow's convective
+#      outflow extrapolation (a zero-gradient fill stands in for it), the MIC(0) preconditioner ----
 DEFAULT_CHECK_EVERY = 16      # iterations between two looks at the active count; the sweep over 1, 4, 16, 64 is in profiles/smoke.md
 
 
@@ -1917,29 +2005,40 @@ def _smoke_out(out, like, who):
     return out
 
 
-def advect_velocity(vel, dt, order=2, clamp_mode=2, bnd=1, out=None, workspace=None, obstacle=None):
+def advect_velocity(vel, dt, order=2, clamp_mode=2, bnd=1, out=None, workspace=None, obstacle=None, open_bound=None):
     """The MAC velocity ``vel`` [B,(Z,)Y,X,D] carried through itself for ``dt`` (cells per unit time), modelled on mantaflow's
     ``advectSemiLagrange(vel, vel, order, boundaryWidth=bnd, clampMode=clamp_mode)``; include/deepfluids_hip.h holds the definition
     that is tested.  Returns a new velocity (``out`` if given; not ``vel`` itself).  ``workspace``: a float32 GPU tensor of
     ``vel.numel()`` elements for order 2.  ``obstacle``: a mask or the flags of ``obstacle_flags``; component a is then corrected and
-    clamped only where c and c - e_a are fluid, over fluid corners (the first-order value ignores obstacles)."""
+    clamped only where c and c - e_a are fluid, over fluid corners (the first-order value ignores obstacles).  ``open_bound``: the open
+    sides (see ``open_sides``); the high-side boundary faces are then advected too, faces between a fluid and an open cell are corrected,
+    and the open cells are filled (zero gradient) before returning, so the result is complete."""
     with torch.no_grad():
         _advect_args(order, clamp_mode, bnd)
         v, nd = _smoke_vel(vel, "advect_velocity")
+        osd = open_sides(open_bound, nd)
         flags = _obstacle_arg(obstacle, v.shape[:-1], bnd, "advect_velocity") if obstacle is not None else None
         out = _smoke_out(out, v, "advect_velocity")
         if out.data_ptr() == v.data_ptr():
             raise ValueError("advect_velocity: out must not be the velocity itself (the step gathers)")
         dims = list(v.shape[:-1])
         sfx = "%dd" % nd
+        osa = [osd] if osd else []                          # the `_open` twins: open_sides right after bnd, flags nullable
+        slx = sfx + ("_open" if osd else "")
         if order == 1:
-            call("df_mac_advect_sl" + sfx, _ptr(v), _ptr(out), *(dims + [float(dt), int(bnd), _stream()]))
+            call("df_mac_advect_sl" + slx, _ptr(v), _ptr(out), *(dims + [float(dt), int(bnd)] + osa + [_stream()]))
+            if osd:
+                _fill_open(out, nd, bnd, osd)
             return out
         ws = workspace if workspace is not None else torch.empty((v.numel(),), dtype=torch.float32, device=v.device)
         if ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < v.numel():
             raise ValueError("advect_velocity: workspace must be a contiguous float32 GPU tensor of >= %d elements" % v.numel())
-        call("df_mac_advect_sl" + sfx, _ptr(v), _ptr(ws), *(dims + [float(dt), int(bnd), _stream()]))
-        if flags is None:
+        call("df_mac_advect_sl" + slx, _ptr(v), _ptr(ws), *(dims + [float(dt), int(bnd)] + osa + [_stream()]))
+        if osd:
+            call("df_mac_advect_mc" + sfx + "_open", _ptr(v), _ptr(ws), _ptr(out), None if flags is None else _ptr(flags),
+                 *(dims + [float(dt), int(bnd), osd, int(clamp_mode), _stream()]))
+            _fill_open(out, nd, bnd, osd)
+        elif flags is None:
             call("df_mac_advect_mc" + sfx, _ptr(v), _ptr(ws), _ptr(out), *(dims + [float(dt), int(bnd), int(clamp_mode), _stream()]))
         else:
             call("df_mac_advect_mc" + sfx + "_flags", _ptr(v), _ptr(ws), _ptr(out), _ptr(flags),
@@ -1947,13 +2046,15 @@ def advect_velocity(vel, dt, order=2, clamp_mode=2, bnd=1, out=None, workspace=N
         return out
 
 
-def wall_buoyancy(vel, density, force, bnd=1, out=None, obstacle=None):
+def wall_buoyancy(vel, density, force, bnd=1, out=None, obstacle=None, open_bound=None):
     """``setWallBcs`` of a closed box and ``addBuoyancy`` in one element-wise pass: component a of cell c is 0 unless c and c - e_a are
     both interior; kept components get ``+ (0.5 * force[a]) * (density[c] + density[c-e_a])``.  ``force``: D numbers (x, y[, z]).
     ``out`` may be ``vel`` (in place).  ``obstacle``: a mask or the flags of ``obstacle_flags``; "interior" then reads "fluid", so the
-    faces of solid cells are 0 as well."""
+    faces of solid cells are 0 as well.  ``open_bound``: the open sides (see ``open_sides``); a face between a fluid and an open cell is
+    then kept, without the buoyancy term, and open cells keep all their components."""
     with torch.no_grad():
         v, nd = _smoke_vel(vel, "wall_buoyancy")
+        osd = open_sides(open_bound, nd)
         d = _prep(density.detach(), "density")
         if tuple(d.shape) != tuple(v.shape[:-1]):
             raise ValueError("wall_buoyancy expects a density %s for a velocity %s, got %s" % (tuple(v.shape[:-1]), tuple(v.shape), tuple(d.shape)))
@@ -1963,7 +2064,11 @@ def wall_buoyancy(vel, density, force, bnd=1, out=None, obstacle=None):
         if int(bnd) != bnd or bnd < 1:
             raise ValueError("wall_buoyancy: bnd must be an integer >= 1, got %r" % (bnd,))
         out = _smoke_out(out, v, "wall_buoyancy")
-        if obstacle is None:
+        if osd:
+            flags = None if obstacle is None else _obstacle_arg(obstacle, d.shape, bnd, "wall_buoyancy")
+            call("df_wall_buoyancy%dd_open" % nd, _ptr(v), _ptr(d), _ptr(out), None if flags is None else _ptr(flags),
+                 *(list(d.shape) + f + [int(bnd), osd, _stream()]))
+        elif obstacle is None:
             call("df_wall_buoyancy%dd" % nd, _ptr(v), _ptr(d), _ptr(out), *(list(d.shape) + f + [int(bnd), _stream()]))
         else:
             flags = _obstacle_arg(obstacle, d.shape, bnd, "wall_buoyancy")
@@ -1997,7 +2102,7 @@ def default_max_iter(shape):
     return int(10 * max(shape)) * (1 if len(shape) == 3 else 4)
 
 
-def solve_pressure(vel, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, out=None, workspace=None, obstacle=None):
+def solve_pressure(vel, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, out=None, workspace=None, obstacle=None, open_bound=None):
     """Make ``vel`` [B,(Z,)Y,X,D] divergence free inside a closed box: plain conjugate gradients on the Neumann Laplacian of the interior
     cells from p = 0, every batch entry on its own until its ``max|r| <= accuracy`` or ``max_iter`` iterations (default
     ``int(10*max(extent))``, times 4 in 2-D), then ``vel -= grad p`` with the wall faces 0.  The wall faces of ``vel`` must be 0 already
@@ -2006,9 +2111,13 @@ def solve_pressure(vel, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, o
     does not: both stop at the same criterion, so the fields agree to the solve's accuracy and not beyond.
     Returns ``(vel_projected, pressure, iterations)``; ``iterations`` is an int32 tensor [B].  ``out`` may be ``vel``.
     ``obstacle``: a mask or the flags of ``obstacle_flags``; the Laplacian then lives on the fluid cells (every connected fluid region is
-    its own singular system), the solid faces of ``vel`` must be 0 already and stay 0, and the pressure is 0 outside the fluid."""
+    its own singular system), the solid faces of ``vel`` must be 0 already and stay 0, and the pressure is 0 outside the fluid.
+    ``open_bound``: the open sides (see ``open_sides``); p = 0 in open cells (Dirichlet), so a fluid region that touches one is a
+    non-singular system, the faces between fluid and open cells are corrected too (every fluid cell ends divergence free -- mantaflow,
+    as far as can be recalled, leaves those faces alone), and the open cells are filled (zero gradient) before returning."""
     with torch.no_grad():
         v, nd = _smoke_vel(vel, "solve_pressure")
+        osd = open_sides(open_bound, nd)
         if int(bnd) != bnd or bnd < 1:
             raise ValueError("solve_pressure: bnd must be an integer >= 1, got %r" % (bnd,))
         if not accuracy >= 0:
@@ -2034,9 +2143,14 @@ def solve_pressure(vel, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, o
         fl = [] if flags is None else [_ptr(flags)]
         sfx += "_flags" if fl else ""
         call("df_pressure_init" + sfx, _ptr(v), _ptr(pressure), _ptr(ws), nbytes, *(fl + dims + [bnd, _stream()]))
+        # open sides: only the direction launch (n_c) and the correction differ; their `_open` twins take a nullable flags pointer
+        fo = [_ptr(flags) if fl else None]
         k = 0
         while True:
-            call("df_pressure_cg_direction" + sfx, _ptr(ws), nbytes, *(fl + dims + [bnd, k, acc, max_iter, _stream()]))
+            if osd:
+                call("df_pressure_cg_direction%dd_open" % nd, _ptr(ws), nbytes, *(fo + dims + [bnd, osd, k, acc, max_iter, _stream()]))
+            else:
+                call("df_pressure_cg_direction" + sfx, _ptr(ws), nbytes, *(fl + dims + [bnd, k, acc, max_iter, _stream()]))
             if k % check_every == check_every - 1 or k >= max_iter:
                 call("df_pressure_status", _ptr(ws), nbytes, *(dims4 + [k, _ptr(count), None, _stream()]))
                 if _read_word(count) == 0:
@@ -2044,7 +2158,11 @@ def solve_pressure(vel, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, o
             call("df_pressure_cg_update" + sfx, _ptr(pressure), _ptr(ws), nbytes, *(fl + dims + [bnd, k, _stream()]))
             k += 1
         call("df_pressure_status", _ptr(ws), nbytes, *(dims4 + [k, None, _ptr(iters), _stream()]))
-        call("df_pressure_correct" + sfx, _ptr(v), _ptr(pressure), _ptr(out), *(fl + dims + [bnd, _stream()]))
+        if osd:
+            call("df_pressure_correct%dd_open" % nd, _ptr(v), _ptr(pressure), _ptr(out), *(fo + dims + [bnd, osd, _stream()]))
+            _fill_open(out, nd, bnd, osd)
+        else:
+            call("df_pressure_correct" + sfx, _ptr(v), _ptr(pressure), _ptr(out), *(fl + dims + [bnd, _stream()]))
         return out, pressure, iters.clone()
 
 
@@ -2066,43 +2184,51 @@ class _SmokeBuffers(object):
         self.pws = pressure_workspace(vel)
 
 
-def _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags=None):
+def _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags=None, osd=0):
     advect(d, v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, source=mask, out=d_out, workspace=buf.adv, obstacle=flags)
-    advect_velocity(v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, out=v_out, workspace=buf.fwd, obstacle=flags)
-    wall_buoyancy(v_out, d_out, force, bnd=bnd, out=v_out, obstacle=flags)
+    advect_velocity(v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, out=v_out, workspace=buf.fwd, obstacle=flags, open_bound=osd)
+    wall_buoyancy(v_out, d_out, force, bnd=bnd, out=v_out, obstacle=flags, open_bound=osd)
     _, _, iters = solve_pressure(v_out, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=v_out, workspace=buf.pws,
-                                 obstacle=flags)
+                                 obstacle=flags, open_bound=osd)
     return iters
 
 
 def smoke_step(density, vel, dt, source=None, force=None, order=2, clamp_mode=2, bnd=1, accuracy=1e-4, max_iter=None, check_every=None,
-               obstacle=None):
+               obstacle=None, open_bound=None):
     """One frame of the reference's smoke scene (scene/smoke_pos_size.py:187-195) on ``density`` [B,(Z,)Y,X] and the MAC velocity ``vel``
     [B,(Z,)Y,X,D] of a closed box: stamp ``source`` (a mask) with 1, advect the density and the velocity through the OLD velocity, zero
     the wall faces, add buoyancy (``force``; default ``default_buoyancy_force``), project.  Returns new ``(density, vel)``.
     ``obstacle`` (a mask of solid cells or the flags of ``obstacle_flags``) makes it the loop of scene/smoke3_obs_buo.py:211-219: the same
-    statements with the obstacle in the flag grid, the solid faces 0 after the walls and after the projection."""
+    statements with the obstacle in the flag grid, the solid faces 0 after the walls and after the projection.  ``source`` may be a
+    ``SphereSource`` [B,D].  ``open_bound`` (see ``open_sides``) makes it the loop of scene/smoke3_rot.py / smoke3_mov.py: the velocity
+    steps treat those sides as open; the density needs nothing, its band is 0 after every advection (``resetOutflow``)."""
     with torch.no_grad():
         d, v, nd = _advect_dims(density, vel)
+        osd = open_sides(open_bound, nd)
         force = default_buoyancy_force(d.shape[1:], dt) if force is None else force
-        mask = _source_mask(source, d) if source is not None else None
+        mask = _source_arg(source, d)
         buf = _SmokeBuffers(d, v, order, mask is not None)
         flags = _obstacle_arg(obstacle, d.shape, bnd, "smoke_step") if obstacle is not None else None
         d_out, v_out = torch.empty_like(d), torch.empty_like(v)
-        _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags)
+        _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags, osd)
         return d_out, v_out
 
 
-def _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, stats, obstacle=None):
+def _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, stats, obstacle=None,
+                  open_bound=None):
     d, v, nd = _advect_dims(density0, vel0)
+    osd = open_sides(open_bound, nd)
     force = default_buoyancy_force(d.shape[1:], dt) if force is None else force
-    mask = _source_mask(source, d) if source is not None else None
+    mask = _source_arg(source, d)
+    if isinstance(mask, SphereSource) and mask.centers.dim() == 3 and mask.centers.shape[0] < int(steps):
+        raise ValueError("simulate_smoke: %d frames of source centres for %d steps" % (mask.centers.shape[0], int(steps)))
     buf = _SmokeBuffers(d, v, order, mask is not None)
     flags = _obstacle_arg(obstacle, d.shape, bnd, "simulate_smoke") if obstacle is not None else None      # once per sequence
     d, v = d.clone(), v.clone()
     d2, v2 = torch.empty_like(d), torch.empty_like(v)
-    for _ in range(int(steps)):
-        iters = _smoke_step(d, v, d2, v2, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags)
+    for t in range(int(steps)):
+        iters = _smoke_step(d, v, d2, v2, buf, dt, _source_frame(mask, t), force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags,
+                            osd)
         if stats is not None:
             stats.append(iters)
         d, d2, v, v2 = d2, d, v2, v
@@ -2110,13 +2236,15 @@ def _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, b
 
 
 def simulate_smoke(density0, vel0, steps, dt=0.5, source=None, force=None, order=2, clamp_mode=2, bnd=1, accuracy=1e-4, max_iter=None,
-                   check_every=None, stack=True, stats=None, obstacle=None):
+                   check_every=None, stack=True, stats=None, obstacle=None, open_bound=None):
     """``steps`` chained ``smoke_step`` frames from ``(density0, vel0)`` (left untouched); every buffer is allocated once.  With
     ``stack`` returns ``(density, vels)``, ``vels`` [steps,B,(Z,)Y,X,D] the velocity after each step; without it returns a generator of
     ``(density, vel)`` per step -- views of buffers the next step overwrites, so copy what is to be kept.  ``stats``: a list that
-    receives the iteration counts [B] of every step's solve.  ``obstacle``: as for ``smoke_step``, packed into flags once."""
+    receives the iteration counts [B] of every step's solve.  ``obstacle``: as for ``smoke_step``, packed into flags once.  ``source``
+    may be a ``SphereSource`` [B,D] or [T,B,D] (step t stamps ``centers[t]``); ``open_bound``: as for ``smoke_step``."""
     with torch.no_grad():
-        gen = _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, stats, obstacle)
+        gen = _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, stats, obstacle,
+                            open_bound)
         if not stack:
             return _no_grad_iter(gen)
         vels = torch.empty((int(steps),) + tuple(vel0.shape), dtype=torch.float32, device=vel0.device)

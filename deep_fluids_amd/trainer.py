@@ -632,7 +632,8 @@ class Trainer(object):
         cast wraps).  ``source``: a mask [(Z,)Y,X] or ``{"center": xyz, "radius": r}`` in cell units (``smoke_pos_size_source`` builds
         the one of scene/smoke_pos_size.py); ``dt``: the dataset's ``time_step`` when args.txt has it, else 0.5.  ``obstacle``: a mask of
         solid cells [(Z,)Y,X] or ``{"center", "radius"}`` like the source (``smoke3_obs_buo_scene`` builds both for
-        scene/smoke3_obs_buo.py); it is handed to ``ops.advect_sequence``.
+        scene/smoke3_obs_buo.py); it is handed to ``ops.advect_sequence``.  ``source`` may also be an ``ops.SphereSource`` with centres
+        [T,1,D], one per generated frame (``moving_source`` reads it from a stored moving-source sequence).
         Returns ``(out_dir, final density [1,(Z,)Y,X] on the device)``."""
         from PIL import Image
         model_dir = model_dir or self.effective_model_dir()
@@ -727,6 +728,29 @@ class Trainer(object):
     def _apply_adam(self, grad_scale):
         """(kept for callers of the pre-graph API) one eager optimizer step with the gradients scaled by ``grad_scale``."""
         self._apply_optimizer(self._optimizer_scalars(grad_scale), None)
+
+
+def moving_source(batch_manager, scene=0, device="cuda"):
+    """The source of a stored sequence of scene/smoke3_rot.py / scene/smoke3_mov.py as an ``ops.SphereSource`` with centres [T,1,D]: frame
+    t's position is ``y[:, -1]`` of its file, as the scripts' ``advect()`` reads it (nx = p[0,-1], nz = p[1,-1], 0.5 without a second
+    row), the centre ``gs * (nx, src_y_pos, nz)`` and the radius ``X * src_radius`` from args.txt.  ``scene``: the first index of a
+    two-parameter ``path_format`` (ignored for ``%d.npz``).  Hand it to ``Trainer.advect_(source=...)`` or ``ops.advect_sequence``."""
+    a = batch_manager.args
+    missing = [k for k in ("src_y_pos", "src_radius", "num_frames", "path_format") if k not in a]
+    if missing:
+        raise KeyError("moving_source: args.txt of %s lacks %s -- the dataset is not a moving-source scene" % (batch_manager.root, ", ".join(missing)))
+    T = int(a["num_frames"])
+    fmt = os.path.join(batch_manager.root, "v", a["path_format"])
+    is_3d = bool(batch_manager.is_3d)
+    gs = (int(batch_manager.res_x), int(batch_manager.res_y), int(batch_manager.res_z))
+    centers = np.empty((T, 1, 3 if is_3d else 2), np.float32)
+    for t in range(T):
+        with np.load(fmt % ((scene, t) if int(a["num_param"]) > 1 else t)) as f:
+            y = f["y"]
+        nx = float(y[0, -1])
+        nz = float(y[1, -1]) if is_3d and y.shape[0] > 1 else 0.5
+        centers[t, 0] = (gs[0] * nx, gs[1] * float(a["src_y_pos"]), gs[2] * nz)[:centers.shape[-1]]
+    return ops.SphereSource(torch.from_numpy(centers).to(device), gs[0] * float(a["src_radius"]))
 
 
 def smoke_pos_size_source(batch_manager, p1, p2):

@@ -571,8 +571,9 @@ int df_particle_levelset_union3d(const float* pos_sorted, const int32_t* cell_st
  * (open_bound=False):  source.applyToGrid, advectSemiLagrange(vel, density), advectSemiLagrange(vel, vel), setWallBcs, addBuoyancy,
  * solvePressure(cgAccuracy, cgMaxIterFac), setWallBcs.  The first two statements are df_density_source and df_advect_* above; the
  * rest is below.  mantaflow cannot be run beside this library, so bit parity with it is NOT claimed: the definition below is the
- * contract (tests/smoke_ref.py restates it; tests/smoke_obs_ref.py the obstacle rules further down).  Left out: open bounds, outflow,
- * noise-modulated inflow, the MIC(0) preconditioner.
+ * contract (tests/smoke_ref.py restates it; tests/smoke_obs_ref.py the obstacle rules and tests/smoke_open_ref.py the open sides further
+ * down).  Left out: noise-modulated inflow (densityInflow) and the inflow velocity stamp of scene/smoke3_vel_buo.py, mantaflow's
+ * convective outflow extrapolation (a zero-gradient fill stands in for it), the MIC(0) preconditioner.
  *
  * Layouts as for df_advect_*: density, pressure [B,(Z,)Y,X]; velocity [B,(Z,)Y,X,D], D = 2 | 3 MAC face values, component a of cell c
  * on c's low-a face; cell (i,j,k) is [..,k,j,i]; e_a the unit step along axis a.  A cell is interior when bnd <= index < extent - bnd
@@ -705,6 +706,78 @@ int df_pressure_correct2d_flags(const float* vel, const float* pressure, float* 
                                 int bnd, df_stream_t stream);
 int df_pressure_correct3d_flags(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
                                 int64_t X, int bnd, df_stream_t stream);
+
+/* ---- the same step with open sides and a moving source: the main() loops of the reference's scene/smoke3_rot.py and scene/smoke3_mov.py
+ * (open_bound 'xXyYzZ', a sphere source whose centre changes every frame), of scene/smoke3_vel_buo.py ('XyY', without its noise inflow) and
+ * the open_bound option of scene/smoke_pos_size.py ('xXyY').  mantaflow cannot be run beside this library: setOpenBound's corner rule, the
+ * Dirichlet cells of its pressure solve and KnAddBuoyancy are restated from memory, and parity is with the NumPy restatement of THIS
+ * definition (tests/smoke_open_ref.py), NOT with mantaflow.
+ *
+ * Layouts, bnd, "interior", "fluid" and the flags byte are those of the blocks above.
+ * open_sides: an int; bits 0..5 mark the sides x-, x+, y-, y+, z-, z+ as open (the order of the flags byte's neighbour bits).  In 2-D
+ * the z bits must be 0.
+ * Cell classes.  A band cell (not interior by its index) is OPEN when, on every axis where its index lies outside [bnd, extent - bnd),
+ * the side it lies on is open; every other band cell is a WALL cell, so an edge or corner shared with a closed side stays wall
+ * (setOpenBound's rule).  The class depends on the index alone, an obstacle mask does not change it.  A face neighbour of an interior
+ * cell is never an edge or corner cell, so "the a- neighbour of c is open" is p[a] == bnd && open(a-), and likewise on the high side.
+ * Live face.  Component a of cell c is LIVE when one of c, c - e_a is fluid and the other is fluid or open.  With open_sides = 0 this
+ * is the "kept face" above.
+ *   - Pressure: p = 0 in open cells (Dirichlet).  n_c = fluid neighbours + open neighbours, the neighbour sums still run over fluid
+ *     neighbours only, b is unchanged.  A fluid region that touches an open cell is a non-singular SPD system and its b need not sum to
+ *     zero; a region that touches none is what it was.  ONLY df_pressure_cg_direction*_open differs from its counterpart, in n_c:
+ *     df_pressure_init*(_flags), df_pressure_cg_update*(_flags), df_pressure_status and the workspace are used as they are.
+ *   - Walls and buoyancy: a live face is kept; the buoyancy term is added only where c and c - e_a are both fluid (KnAddBuoyancy), a
+ *     fluid-open face is kept without it.  Non-live components of fluid, solid and wall cells are 0; every component of an open cell that
+ *     is not live is copied through unchanged, because it holds filled values.
+ *   - Correction: on live faces out = vel - (p[c] - p[c - e_a]) with p read from the array (0 outside the fluid); everything else follows
+ *     the walls-and-buoyancy rule.  This also corrects the face between the last fluid cell and an open cell, so EVERY fluid cell ends
+ *     divergence free.  Deviation: as far as can be recalled, mantaflow's CorrectVelocity skips outflow cells there.
+ *   - MAC self-advection: fwd as above for every component of an interior cell, and additionally for component a of an open cell whose
+ *     c - e_a is interior by its index (the high-side boundary face; df_mac_advect_sl*_open has no flags argument because the
+ *     first-order value keeps ignoring obstacles).  The MacCormack correction and clamp apply where the face is live; min / max still
+ *     run over fluid corners only (none fluid -> fwd).  Other components of open cells are written 0, wall cells 0.
+ *   - Fill, df_open_extrapolate*: in place, for every open cell c and component a, vel[c][a] = vel[c'][a] with c' = c clamped to
+ *     [bnd, extent_a - bnd] on axis a and to [bnd, extent_b - bnd - 1] on every other axis b.  The sources are exactly the fixed points
+ *     of that map (interior cells and the first high layer along a), and a fixed point copies onto itself: race free in place.  This is a
+ *     zero-gradient fill, NOT mantaflow's extrapolateVelConvectiveBC, which divides by a bulk velocity and cannot be restated from
+ *     memory.  Density needs nothing: df_advect_* already write 0 on the band, which is what resetOutflow(real=density) does.  The
+ *     callers in ops.py run the fill after the self-advection and after the correction.
+ *   - Sphere stamp, df_density_sphere_source*: out[c] = value where ((i+.5-cx)^2 + (j+.5-cy)^2) [+ (k+.5-cz)^2] <= radius*radius, else
+ *     density[c]; (cx, cy[, cz]) = centers[b] for batch entry b, centers [B,D] fp32 in DEVICE memory.  fp32, no fused multiply-add, in
+ *     that order.  out may be density.  A NaN centre stamps nothing.
+ * Every `_open` entry point takes flags (may be NULL: no obstacles) after its arrays and open_sides after bnd.
+ * Bit rule: with open_sides = 0 every `_open` entry point returns the bits of its closed counterpart -- with flags == NULL those of the
+ * plain one, with flags those of the `_flags` one -- and df_open_extrapolate* writes nothing.
+ * As for the flags: a byte is believed where the cell is interior by its index, and its low-neighbour bit also where the cell is a
+ * high-side boundary cell by its index; no flags content selects memory outside the arrays.
+ * Errors: those of the counterparts, and DF_EINVAL for open_sides outside 0..63, for z bits in 2-D, and for centres that overlap the
+ * output. */
+int df_mac_advect_sl2d_open(const float* vel, float* fwd, int64_t B, int64_t Y, int64_t X, float dt, int bnd, int open_sides,
+                            df_stream_t stream);
+int df_mac_advect_sl3d_open(const float* vel, float* fwd, int64_t B, int64_t Z, int64_t Y, int64_t X, float dt, int bnd, int open_sides,
+                            df_stream_t stream);
+int df_mac_advect_mc2d_open(const float* vel, const float* fwd, float* out, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, float dt,
+                            int bnd, int open_sides, int clamp_mode, df_stream_t stream);
+int df_mac_advect_mc3d_open(const float* vel, const float* fwd, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X,
+                            float dt, int bnd, int open_sides, int clamp_mode, df_stream_t stream);
+int df_wall_buoyancy2d_open(const float* vel, const float* density, float* out, const uint8_t* flags, int64_t B, int64_t Y, int64_t X,
+                            float fx, float fy, int bnd, int open_sides, df_stream_t stream);
+int df_wall_buoyancy3d_open(const float* vel, const float* density, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
+                            int64_t X, float fx, float fy, float fz, int bnd, int open_sides, df_stream_t stream);
+int df_pressure_cg_direction2d_open(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd,
+                                    int open_sides, int64_t k, float accuracy, int64_t max_iter, df_stream_t stream);
+int df_pressure_cg_direction3d_open(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                                    int open_sides, int64_t k, float accuracy, int64_t max_iter, df_stream_t stream);
+int df_pressure_correct2d_open(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Y, int64_t X,
+                               int bnd, int open_sides, df_stream_t stream);
+int df_pressure_correct3d_open(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
+                               int64_t X, int bnd, int open_sides, df_stream_t stream);
+int df_open_extrapolate2d(float* vel, int64_t B, int64_t Y, int64_t X, int bnd, int open_sides, df_stream_t stream);
+int df_open_extrapolate3d(float* vel, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int open_sides, df_stream_t stream);
+int df_density_sphere_source2d(const float* density, const float* centers, float radius, float value, float* out, int64_t B, int64_t Y,
+                               int64_t X, df_stream_t stream);
+int df_density_sphere_source3d(const float* density, const float* centers, float radius, float value, float* out, int64_t B, int64_t Z,
+                               int64_t Y, int64_t X, df_stream_t stream);
 
 #ifdef __cplusplus
 }
