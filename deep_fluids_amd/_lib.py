@@ -185,6 +185,20 @@ SIGNATURES = {
     "df_open_extrapolate3d": (I32, [P, I64, I64, I64, I64, I32, I32, P]),
     "df_density_sphere_source2d": (I32, [P, P, F32, F32, P, I64, I64, I64, P]),
     "df_density_sphere_source3d": (I32, [P, P, F32, F32, P, I64, I64, I64, I64, P]),
+    "df_liquid_p2g2d": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, P]),
+    "df_liquid_p2g3d": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, P]),
+    "df_mac_extrapolate2d": (I32, [P, P, P, P, I64, I64, I64, I32, I32, P]),
+    "df_mac_extrapolate3d": (I32, [P, P, P, P, I64, I64, I64, I64, I32, I32, P]),
+    "df_liquid_flags2d": (I32, [P, P, P, I64, I64, I64, I64, I32, P]),
+    "df_liquid_flags3d": (I32, [P, P, P, I64, I64, I64, I64, I64, I32, P]),
+    "df_liquid_forces2d": (I32, [P, P, P, I64, I64, I64, F32, F32, I32, P]),
+    "df_liquid_forces3d": (I32, [P, P, P, I64, I64, I64, I64, F32, F32, F32, I32, P]),
+    "df_pressure_cg_direction2d_liquid": (I32, [P, I64, P, I64, I64, I64, I32, I64, F32, I64, P]),
+    "df_pressure_cg_direction3d_liquid": (I32, [P, I64, P, I64, I64, I64, I64, I32, I64, F32, I64, P]),
+    "df_pressure_correct2d_liquid": (I32, [P, P, P, P, I64, I64, I64, I32, P]),
+    "df_pressure_correct3d_liquid": (I32, [P, P, P, P, I64, I64, I64, I64, I32, P]),
+    "df_flip_update2d": (I32, [P, P, P, P, P, I64, I64, I64, I64, F32, P]),
+    "df_flip_update3d": (I32, [P, P, P, P, P, I64, I64, I64, I64, I64, F32, P]),
 }
 
 DF_CONV_LRELU, DF_CONV_RESIDUAL, DF_CONV_MASK, DF_CONV_BIAS, DF_CONV_ADDUP, DF_CONV_VALU_ONLY = 1, 2, 4, 8, 16, 32

@@ -343,7 +343,9 @@ __global__ __launch_bounds__(kThreads) void pressure_init_kernel(const float* __
 }
 
 // OPEN: p = 0 in open cells (Dirichlet), so an open neighbour counts in n_c and adds nothing to the sum
-template <int D, bool MASKED, bool OPEN>
+// LIQUID (with MASKED; "fluid" reads "liquid"): p = 0 in air cells, so n_c counts every neighbour that is interior by its index, as
+// the unmasked path does, while the sums run over the liquid neighbours of the flags byte
+template <int D, bool MASKED, bool OPEN, bool LIQUID = false>
 __global__ __launch_bounds__(kThreads) void cg_direction_kernel(PWs w, const uint8_t* __restrict__ flags, PDims d, int par, int first,
                                                                 float accuracy, int max_iter, int os) {
   __shared__ float lds[4];
@@ -381,6 +383,11 @@ __global__ __launch_bounds__(kThreads) void cg_direction_kernel(PWs w, const uin
       if (hi) { const int64_t nb = c.cell + st[a]; sum += r[nb] + beta * po_[nb]; if (!MASKED) ++cnt; }
     }
     if (MASKED) cnt = __popc((c.fl >> 1) & ((1u << (2 * D)) - 1u));   // n_c: the neighbour bits of the D axes, those the loop visited
+    if (LIQUID) {
+      cnt = 0;
+#pragma unroll
+      for (int a = 0; a < D; ++a) cnt += (c.p[a] > d.bnd ? 1 : 0) + (c.p[a] + 1 < ext[a] - d.bnd ? 1 : 0);
+    }
     if (OPEN) {
 #pragma unroll
       for (int a = 0; a < D; ++a) cnt += ((c.p[a] == d.bnd && open_lo(os, a)) ? 1 : 0) + ((c.p[a] + 1 == ext[a] - d.bnd && open_hi(os, a)) ? 1 : 0);
@@ -436,7 +443,9 @@ __global__ __launch_bounds__(kThreads) void cg_status_kernel(const CgState* __re
 }
 
 // OPEN: live faces are corrected with p as the array holds it (0 outside the fluid), open cells keep their other components
-template <int D, bool MASKED, bool OPEN>
+// LIQUID (with MASKED): a face between two interior cells is corrected when at least one of them is liquid, with p as the array holds it
+// (0 in air), and copied through otherwise; wall faces are 0
+template <int D, bool MASKED, bool OPEN, bool LIQUID = false>
 __global__ __launch_bounds__(kThreads) void pressure_correct_kernel(const float* vel, const float* __restrict__ pr, float* out,
                                                                     const uint8_t* __restrict__ flags, AdvDims d, int os) {
   const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
@@ -451,7 +460,10 @@ __global__ __launch_bounds__(kThreads) void pressure_correct_kernel(const float*
 #pragma unroll
   for (int a = 0; a < D; ++a) {
     r.v[a] = opn ? v.v[a] : 0.0f;
-    if (kept_face<MASKED>(c.interior, c.p[a], d.bnd, fl, a) || (OPEN && open_live_face<D, MASKED>(c.p, ext, c.interior, fl, d.bnd, a, os)))
+    if (LIQUID) {                                       // fl is read of an interior cell only
+      if (kept_face<false>(c.interior, c.p[a], d.bnd, 0u, a))
+        r.v[a] = ((fl & kFluid) || (fl & lo_bit(a))) ? v.v[a] - (pr[idx] - pr[idx - st[a]]) : v.v[a];
+    } else if (kept_face<MASKED>(c.interior, c.p[a], d.bnd, fl, a) || (OPEN && open_live_face<D, MASKED>(c.p, ext, c.interior, fl, d.bnd, a, os)))
       r.v[a] = v.v[a] - (pr[idx] - pr[idx - st[a]]);    // a live face has p[a] >= bnd >= 1: c - e_a is inside the grid
   }
   *reinterpret_cast<VelRec<D>*>(out + idx * D) = r;
@@ -630,7 +642,7 @@ int pressure_init(const char* fn, const float* vel, float* pressure, void* ws, i
   return df::launched(fn);
 }
 
-template <int D, bool MASKED, bool OPEN = false>
+template <int D, bool MASKED, bool OPEN = false, bool LIQUID = false>
 int cg_direction(const char* fn, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
                  int64_t k, float accuracy, int64_t max_iter, df_stream_t stream, int os = 0) {
   PDims d;
@@ -642,7 +654,7 @@ int cg_direction(const char* fn, void* ws, int64_t ws_bytes, const uint8_t* flag
   DF_REQUIRE(accuracy >= 0.0f, DF_EINVAL, "%s: accuracy must be >= 0", fn);
   if (int e = check_flags<MASKED>(fn, flags, d.n * B, nullptr, 0, "")) return e;
   if (MASKED) if (int e = check_apart(fn, ws, d, flags, d.n * B, "flags")) return e;
-  hipLaunchKernelGGL((cg_direction_kernel<D, MASKED, OPEN>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), carve(ws, B, d.n, d.nblk),
+  hipLaunchKernelGGL((cg_direction_kernel<D, MASKED, OPEN, LIQUID>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), carve(ws, B, d.n, d.nblk),
                      flags, d, (int)(k & 1), k == 0 ? 1 : 0, accuracy, (int)max_iter, os);
   return df::launched(fn);
 }
@@ -665,7 +677,7 @@ int cg_update(const char* fn, float* pressure, void* ws, int64_t ws_bytes, const
   return df::launched(fn);
 }
 
-template <int D, bool MASKED, bool OPEN = false>
+template <int D, bool MASKED, bool OPEN = false, bool LIQUID = false>
 int pressure_correct(const char* fn, const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
                      int64_t X, int bnd, df_stream_t stream, int os = 0) {
   DF_REQUIRE(vel && pressure && out, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : !pressure ? "pressure" : "output");
@@ -676,7 +688,7 @@ int pressure_correct(const char* fn, const float* vel, const float* pressure, fl
              "%s: the output must not be the pressure (it is read at a neighbour)", fn);
   if (int e = check_flags<MASKED>(fn, flags, d.ncell, out, 4 * d.ncell * D, "output")) return e;
   DF_REQUIRE(aligned4(vel) && aligned4(pressure) && aligned4(out), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  hipLaunchKernelGGL((pressure_correct_kernel<D, MASKED, OPEN>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, pressure, out, flags,
+  hipLaunchKernelGGL((pressure_correct_kernel<D, MASKED, OPEN, LIQUID>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, pressure, out, flags,
                      d, os);
   return df::launched(fn);
 }
@@ -918,6 +930,23 @@ int df_pressure_correct3d_open(const float* vel, const float* pressure, float* o
   const char* fn = "df_pressure_correct3d_open";
   if (int e = check_open(fn, 3, open_sides)) return e;
   return DF_OPEN_CALL(pressure_correct, 3, fn, vel, pressure, out, flags, B, Z, Y, X, bnd, stream);
+}
+// ---- the free-surface projection of the liquid step (liquid.hip): the flags of df_liquid_flags*, p = 0 in air cells ----
+int df_pressure_cg_direction2d_liquid(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k,
+                                      float accuracy, int64_t max_iter, df_stream_t stream) {
+  return cg_direction<2, true, false, true>("df_pressure_cg_direction2d_liquid", ws, ws_bytes, flags, B, 1, Y, X, bnd, k, accuracy, max_iter, stream);
+}
+int df_pressure_cg_direction3d_liquid(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                                      int64_t k, float accuracy, int64_t max_iter, df_stream_t stream) {
+  return cg_direction<3, true, false, true>("df_pressure_cg_direction3d_liquid", ws, ws_bytes, flags, B, Z, Y, X, bnd, k, accuracy, max_iter, stream);
+}
+int df_pressure_correct2d_liquid(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Y, int64_t X,
+                                 int bnd, df_stream_t stream) {
+  return pressure_correct<2, true, false, true>("df_pressure_correct2d_liquid", vel, pressure, out, flags, B, 1, Y, X, bnd, stream);
+}
+int df_pressure_correct3d_liquid(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
+                                 int64_t X, int bnd, df_stream_t stream) {
+  return pressure_correct<3, true, false, true>("df_pressure_correct3d_liquid", vel, pressure, out, flags, B, Z, Y, X, bnd, stream);
 }
 int df_open_extrapolate2d(float* vel, int64_t B, int64_t Y, int64_t X, int bnd, int open_sides, df_stream_t stream) {
   return open_extrapolate<2>("df_open_extrapolate2d", vel, B, 1, Y, X, bnd, open_sides, stream);

@@ -354,6 +354,124 @@ def generate_smoke_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="sr
     return written
 
 
+def _simulate_liquid_scenes(root, path_format, scenes, shape, num_frames, time_step, gravity, bWidth, accuracy, flip_ratio, device, keep):
+    """the frame loop of the liquid scene scripts: ``scenes`` = (i, j, p0, p1, phi0, velocity spheres); scenes that seed the same number
+    of particles run as one batch of ``ops.simulate_liquid``.  Writes v/ and v_range.txt; returns the number of files written."""
+    from . import ops
+    states = [ops.liquid_initial_state(shape, phi, spheres, bnd=bWidth, device=device) for _, _, _, _, phi, spheres in scenes]
+    groups = {}
+    for n, st in enumerate(states):
+        groups.setdefault(int(st[0].shape[1]), []).append(n)
+    force = ops.default_gravity_force(shape, time_step, gravity=gravity)
+    v_range = [np.finfo(np.float64).max, np.finfo(np.float64).min]
+    written = 0
+    for N in sorted(groups):
+        part = groups[N]
+        pos, pvel, vel = [torch.cat([states[n][k] for n in part]) for k in range(3)]
+        frames = ops.simulate_liquid(pos, pvel, vel, num_frames, dt=time_step, force=force, bnd=bWidth, accuracy=accuracy, flip_ratio=flip_ratio,
+                                     stack=False)
+        for t, (_, _, v) in enumerate(frames):
+            vh = v.cpu().numpy()
+            v_range = [min(v_range[0], float(vh.min())), max(v_range[1], float(vh.max()))]
+            for e, n in enumerate(part):
+                i, j, q0, q1 = scenes[n][:4]
+                np.savez_compressed(os.path.join(root, "v", path_format % (i, j, t)), x=vh[e][..., :keep], y=[q0, q1, t])
+                written += 1
+    with open(os.path.join(root, "v_range.txt"), "w") as f:
+        f.write("%.3f\n" % v_range[0])
+        f.write("%.3f" % v_range[1])
+    return written
+
+
+def _write_args(root, args):
+    os.makedirs(os.path.join(root, "v"), exist_ok=True)
+    with open(os.path.join(root, "args.txt"), "w") as f:
+        for k, v in args:
+            f.write("%s: %s\n" % (k, v))
+
+
+def _liquid_refusals(who, open_bound, num_param, names, want):
+    if open_bound:
+        raise NotImplementedError("%s: open_bound (setOpenBound + resetOutflow) is not implemented for the liquid solver" % who)
+    if num_param != 3 or tuple(names) != tuple(want):
+        raise ValueError("%s: the scene has the parameters %s" % (who, (want,)))
+
+
+def generate_liquid_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="src_x_pos", p1="src_radius", p2="frames", num_src_x_pos=10,
+                            min_src_x_pos=0.2, max_src_x_pos=0.8, src_y_pos=0.6, num_src_radius=4, min_src_radius=0.04, max_src_radius=0.08,
+                            basin_y_pos=0.2, num_frames=200, min_frames=0, max_frames=None, num_simulations=None, resolution_x=128,
+                            resolution_y=64, gravity=-1e-3, radius_factor=1, min_particles=2, bWidth=1, open_bound=False, time_step=0.5,
+                            accuracy=1e-4, flip_ratio=0.97, device="cuda"):
+    """Simulate the reference's 2-D liquid training set (scene/liquid_pos_size.py:148-325, ``liquid_pos10_size4_f200``) on the GPU and
+    write it in the reference's on-disk format: ``args.txt`` with every argument of the scene script, ``v/%d_%d_%d.npz`` (x [Y,X,2]
+    float32 velocity after frame t, y = [p0, p1, t]) and ``v_range.txt``.  The keyword arguments are the script's, with its defaults
+    (``radius_factor`` and ``min_particles`` are recorded only: the level set and adjustNumber are left out).  A drop of radius p1 at
+    (p0, src_y_pos) falls into a basin of height basin_y_pos; scenes that seed the same number of particles run as one batch of
+    ``ops.simulate_liquid``.  The step is this library's restatement (include/deepfluids_hip.h: first-order free surface, plain CG),
+    not mantaflow's.  ``open_bound=True`` is refused.  Returns the number of files written."""
+    from . import ops
+    _liquid_refusals("generate_liquid_dataset", open_bound, num_param, (p0, p1, p2), ("src_x_pos", "src_radius", "frames"))
+    max_frames = num_frames - 1 if max_frames is None else max_frames
+    num_simulations = num_src_x_pos * num_src_radius * num_frames if num_simulations is None else num_simulations
+    _write_args(root, [("log_dir", root), ("num_param", num_param), ("path_format", path_format), ("p0", p0), ("p1", p1), ("p2", p2),
+                       ("num_src_x_pos", num_src_x_pos), ("min_src_x_pos", min_src_x_pos), ("max_src_x_pos", max_src_x_pos),
+                       ("src_y_pos", src_y_pos), ("num_src_radius", num_src_radius), ("min_src_radius", min_src_radius),
+                       ("max_src_radius", max_src_radius), ("basin_y_pos", basin_y_pos), ("num_frames", num_frames),
+                       ("min_frames", min_frames), ("max_frames", max_frames), ("num_simulations", num_simulations),
+                       ("resolution_x", resolution_x), ("resolution_y", resolution_y), ("gravity", gravity), ("radius_factor", radius_factor),
+                       ("min_particles", min_particles), ("bWidth", bWidth), ("open_bound", open_bound), ("time_step", time_step)])
+
+    def param(i, num, lo, hi):
+        return i / float(num - 1) * (hi - lo) + lo if num > 1 else lo
+
+    X, Y = int(resolution_x), int(resolution_y)
+    basin = ops.box_levelset((Y, X), (0.0, 0.0), (X * 1.0, Y * basin_y_pos))
+    scenes = []
+    for i in range(num_src_x_pos):
+        for j in range(num_src_radius):
+            px, pr = param(i, num_src_x_pos, min_src_x_pos, max_src_x_pos), param(j, num_src_radius, min_src_radius, max_src_radius)
+            c = (X * px, Y * src_y_pos)
+            phi = np.minimum(basin, ops.sphere_levelset((Y, X), c, X * pr))
+            scenes.append((i, j, px, pr, phi, [(c, X * (pr + 0.05))]))
+    return _simulate_liquid_scenes(root, path_format, scenes, (Y, X), num_frames, time_step, gravity, bWidth, accuracy, flip_ratio, device, 2)
+
+
+def generate_liquid3_d_r_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="dist", p1="rot", p2="frames", min_dist=0.15, max_dist=0.25,
+                                 num_dist=5, min_rot=0, max_rot=162, num_rot=10, src_y_pos=0.6, src_radius=0.1, basin_y_pos=0.2,
+                                 min_frames=0, max_frames=None, num_frames=150, num_simulations=None, resolution_x=96, resolution_y=48,
+                                 resolution_z=96, gravity=-1e-3, radius_factor=1, min_particles=3, bWidth=1, open_bound=False,
+                                 time_step=0.8, accuracy=1e-4, flip_ratio=0.97, device="cuda"):
+    """Simulate the reference's 3-D liquid training set (scene/liquid3_d_r.py main(), ``liquid3_d5_r10_f150``) on the GPU, in the same
+    on-disk format (x [Z,Y,X,3]): two drops of radius src_radius at distance p0 (fractions of X) either side of the centre, the pair
+    rotated by p1 degrees about the vertical axis, fall into a basin.  The keyword arguments are the script's, with its defaults; what
+    ``generate_liquid_dataset`` says about the step and about what is left out holds here too."""
+    from . import ops
+    _liquid_refusals("generate_liquid3_d_r_dataset", open_bound, num_param, (p0, p1, p2), ("dist", "rot", "frames"))
+    max_frames = num_frames - 1 if max_frames is None else max_frames
+    num_simulations = num_dist * num_rot * num_frames if num_simulations is None else num_simulations
+    _write_args(root, [("log_dir", root), ("num_param", num_param), ("path_format", path_format), ("p0", p0), ("p1", p1), ("p2", p2),
+                       ("min_dist", min_dist), ("max_dist", max_dist), ("num_dist", num_dist), ("min_rot", min_rot), ("max_rot", max_rot),
+                       ("num_rot", num_rot), ("src_y_pos", src_y_pos), ("src_radius", src_radius), ("basin_y_pos", basin_y_pos),
+                       ("min_frames", min_frames), ("max_frames", max_frames), ("num_frames", num_frames),
+                       ("num_simulations", num_simulations), ("resolution_x", resolution_x), ("resolution_y", resolution_y),
+                       ("resolution_z", resolution_z), ("gravity", gravity), ("radius_factor", radius_factor),
+                       ("min_particles", min_particles), ("bWidth", bWidth), ("open_bound", open_bound), ("time_step", time_step)])
+    X, Y, Z = int(resolution_x), int(resolution_y), int(resolution_z)
+    shape = (Z, Y, X)
+    basin = ops.box_levelset(shape, (0.0, 0.0, 0.0), (X * 1.0, Y * basin_y_pos, Z * 1.0))
+    centre = (X * 0.5, Y * src_y_pos, Z * 0.5)
+    scenes = []
+    for i, dist in enumerate(np.linspace(min_dist, max_dist, num_dist)):
+        for j, rot in enumerate(np.linspace(min_rot, max_rot, num_rot)):
+            r, th = X * dist, rot / 180.0 * np.pi
+            cs = [(centre[0] + r * np.cos(t), centre[1], centre[2] + r * np.sin(t)) for t in (th, th + np.pi)]
+            phi = basin
+            for c in cs:
+                phi = np.minimum(phi, ops.sphere_levelset(shape, c, X * src_radius))
+            scenes.append((i, j, float(dist), float(rot), phi, [(c, X * (src_radius + 0.05)) for c in cs]))
+    return _simulate_liquid_scenes(root, path_format, scenes, shape, num_frames, time_step, gravity, bWidth, accuracy, flip_ratio, device, 3)
+
+
 def generate_smoke3_obs_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="obs_x_pos", p1="buoyancy", p2="frames", min_obs_x_pos=0.2,
                                 max_obs_x_pos=0.8, num_obs_x_pos=11, obs_radius=0.15, obs_y_pos=0.5, obs_z_pos=0.5, min_buoyancy=-8e-3,
                                 max_buoyancy=-16e-3, num_buoyancy=4, src_x_pos=0.5, src_y_pos=0.13, src_z_pos=0.5, src_radius=0.12,

@@ -2429,6 +2429,312 @@ def seed_particles(phi0, discretization=2, randomness=0.05, seed=123, bnd=1):
     return pos.astype(np.float32)
 
 
+# ---- the liquid solver step (the main() loops of the reference's liquid scenes, scene/liquid_pos_size.py:254-295 and
+#      scene/liquid3_d_r.py): FLIP.  The step is defined in include/deepfluids_hip.h (tests/liquid_ref.py restates it); mantaflow cannot
+#      be run here, so parity with it is not claimed.  Left out: the ghost-fluid surface treatment of solvePressure(phi=) (p = 0 sits at
+#      the air cell centres: a first-order surface), adjustNumber resampling (N is constant), averagedParticleLevelset /
+#      extrapolateLsSimple / phi.setBound (the solve does not read phi), resetOutflow and open sides, obstacles inside the liquid,
+#      MIC(0), per-entry particle counts (one call, one N) ----
+DEFAULT_FLIP_RATIO = 0.97
+
+
+def _liquid_vel(vel, B, nd, who):
+    v = _prep(vel.detach(), "vel")
+    if v.dim() != nd + 2 or v.shape[0] != B or v.shape[-1] != nd:
+        raise ValueError("%s expects a velocity [%d,%s%d], got %s" % (who, B, "Z,Y,X," if nd == 3 else "Y,X,", nd, tuple(v.shape)))
+    return v
+
+
+def _liquid_bnd(bnd, who):
+    if int(bnd) != bnd or bnd < 1:
+        raise ValueError("%s: bnd must be an integer >= 1, got %r" % (who, bnd))
+    return int(bnd)
+
+
+def _marks(t, like, who):
+    if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(like.shape):
+        raise ValueError("%s: marks must be a contiguous uint8 GPU tensor of shape %s" % (who, tuple(like.shape)))
+    return t
+
+
+def particles_to_grid(pos_sorted, pvel_sorted, cell_start, shape):
+    """mantaflow's ``mapPartsToMAC`` as a gather: ``(vel, weight, known)`` on a grid ``shape`` [(Z,)Y,X] from particles SORTED by cell
+    (``particle_cells``; ``pvel`` permuted by the same order).  Component a of a face is ``sum(w * pvel_a) / sum(w)`` over the
+    particles whose ``u(p)`` reads that face, w the weight of that read (the scatter is the transpose of the sample of
+    ``advect_particles``), 0 where ``sum(w)`` is 0; ``weight`` is ``sum(w)``, ``known`` (uint8) marks ``weight > 0``.  The sums run in
+    ascending cell order and, inside a cell, in sorted order: deterministic, no atomics."""
+    with torch.no_grad():
+        p = _particle_pos(pos_sorted, "particles_to_grid")
+        u = _particle_pos(pvel_sorted, "particles_to_grid")
+        B, N, nd = p.shape
+        if tuple(u.shape) != tuple(p.shape):
+            raise ValueError("particles_to_grid: velocities %s for positions %s" % (tuple(u.shape), tuple(p.shape)))
+        shape = _grid_shape(shape, nd, "particles_to_grid")
+        ncell = int(np.prod(shape))
+        if cell_start.dtype != torch.int32 or not cell_start.is_cuda or not cell_start.is_contiguous() or cell_start.numel() != B * ncell + 1:
+            raise ValueError("particles_to_grid: cell_start must be the int32 GPU tensor [B*ncell + 1] of particle_cells")
+        vel = _empty((B,) + shape + (nd,), p)
+        weight = torch.empty_like(vel)
+        known = torch.empty(vel.shape, dtype=torch.uint8, device=p.device)
+        call("df_liquid_p2g%dd" % nd, _ptr(p), _ptr(u), _ptr(cell_start), _ptr(vel), _ptr(weight), _ptr(known), B, N,
+             *(list(shape) + [_stream()]))
+        return vel, weight, known
+
+
+def extrapolate_mac(vel, known, distance, bnd=1):
+    """mantaflow's ``extrapolateMACFromWeight`` / ``extrapolateMACSimple`` in one form: ``known`` [B,(Z,)Y,X,D] uint8 marks the faces that
+    hold a value (1) or not (0).  For layer d = 1..distance an unknown face between two interior cells takes the mean of its axis
+    neighbours (x-, x+, y-, y+[, z-, z+]) marked 1..d and the mark d + 1; wall faces are never filled.  One launch per layer between
+    two buffers.  Returns new ``(vel, marks)``; the inputs are left untouched."""
+    with torch.no_grad():
+        v, nd = _smoke_vel(vel, "extrapolate_mac")
+        bnd = _liquid_bnd(bnd, "extrapolate_mac")
+        m = _marks(known, v, "extrapolate_mac")
+        distance = int(distance)
+        if not 0 <= distance <= 254:
+            raise ValueError("extrapolate_mac: distance must be in 0..254, got %r" % (distance,))
+        dims = list(v.shape[:-1])
+        cur = (v.clone(), m.clone()) if distance == 0 else (v, m)
+        bufs = [(torch.empty_like(v), torch.empty_like(m)) for _ in range(min(distance, 2))]
+        for d in range(1, distance + 1):
+            nxt = bufs[(d - 1) % 2]
+            call("df_mac_extrapolate%dd" % nd, _ptr(cur[0]), _ptr(cur[1]), _ptr(nxt[0]), _ptr(nxt[1]), *(dims + [bnd, d, _stream()]))
+            cur = nxt
+        return cur
+
+
+def liquid_flags(cell_start, shape, batch, n_particles, bnd=1):
+    """mantaflow's ``markFluidCells`` from the ranges of ``particle_cells``: ``(flags, touch)``.  An interior cell is liquid when it
+    holds a particle, every other interior cell is air.  ``flags`` [B,(Z,)Y,X] uint8 has the layout of ``obstacle_flags`` (bit 0: the
+    cell is liquid, bits 1..6: that neighbour is); ``touch`` [B,(Z,)Y,X,D] uint8 marks the faces with a liquid cell on either side."""
+    with torch.no_grad():
+        shape = tuple(int(n) for n in shape)
+        nd = len(shape)
+        if nd not in (2, 3):
+            raise ValueError("liquid_flags expects a grid shape [(Z,)Y,X], got %s" % (shape,))
+        bnd = _liquid_bnd(bnd, "liquid_flags")
+        B, ncell = int(batch), int(np.prod(shape))
+        if cell_start.dtype != torch.int32 or not cell_start.is_cuda or not cell_start.is_contiguous() or cell_start.numel() != B * ncell + 1:
+            raise ValueError("liquid_flags: cell_start must be the int32 GPU tensor [B*ncell + 1] of particle_cells")
+        flags = torch.empty((B,) + shape, dtype=torch.uint8, device=cell_start.device)
+        touch = torch.empty((B,) + shape + (nd,), dtype=torch.uint8, device=cell_start.device)
+        call("df_liquid_flags%dd" % nd, _ptr(cell_start), _ptr(flags), _ptr(touch), B, int(n_particles), *(list(shape) + [bnd, _stream()]))
+        return flags, touch
+
+
+def _liquid_flags_arg(flags, v, who):
+    if flags.dtype != torch.uint8 or not flags.is_cuda or not flags.is_contiguous() or tuple(flags.shape) != tuple(v.shape[:-1]):
+        raise ValueError("%s: flags must be the uint8 GPU tensor %s of liquid_flags" % (who, tuple(v.shape[:-1])))
+    return flags
+
+
+def liquid_forces(vel, flags, force, bnd=1, out=None):
+    """``addGravity`` + ``setWallBcs`` in one element-wise pass: a face with a wall cell becomes 0, a face between two interior cells of
+    which at least one is liquid gets ``+ force[a]``, every other face is left unchanged.  ``force``: D numbers in cells per step.
+    ``out`` may be ``vel``."""
+    with torch.no_grad():
+        v, nd = _smoke_vel(vel, "liquid_forces")
+        bnd = _liquid_bnd(bnd, "liquid_forces")
+        fl = _liquid_flags_arg(flags, v, "liquid_forces")
+        f = [float(x) for x in force]
+        if len(f) != nd:
+            raise ValueError("liquid_forces: force must have %d components, got %r" % (nd, force))
+        out = _smoke_out(out, v, "liquid_forces")
+        call("df_liquid_forces%dd" % nd, _ptr(v), _ptr(fl), _ptr(out), *(list(v.shape[:-1]) + f + [bnd, _stream()]))
+        return out
+
+
+def default_gravity_force(shape, dt, gravity=-1e-3):
+    """The ``force`` of ``liquid_forces`` for the reference's liquid scenes: (0, gravity * dt * max(extent)[, 0]) -- mantaflow's
+    ``gravity * dt / dx`` with ``dx = 1 / max(gridSize)`` and the scenes' ``gravity = -1e-3``, the convention of
+    ``default_buoyancy_force``.  Restated from memory of mantaflow's addGravity; it cannot be checked here."""
+    f = [0.0] * len(shape)
+    f[1] = float(gravity) * float(dt) * max(int(n) for n in shape)
+    return tuple(f)
+
+
+def _cg_loop(direction, update, ws, nbytes, dims4, count, max_iter, check_every):
+    """the host loop of a solve: ``direction(k)`` and ``update(k)`` launch one iteration's two kernels; returns the last k"""
+    k = 0
+    while True:
+        direction(k)
+        if k % check_every == check_every - 1 or k >= max_iter:
+            call("df_pressure_status", _ptr(ws), nbytes, *(dims4 + [k, _ptr(count), None, _stream()]))
+            if _read_word(count) == 0:
+                return k
+        update(k)
+        k += 1
+
+
+def solve_pressure_liquid(vel, flags, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, out=None, workspace=None):
+    """The free-surface projection: ``solve_pressure`` with rows for the liquid cells of ``flags`` (``liquid_flags``) only and p = 0 in
+    the air cells -- n_c counts every neighbour that is interior by its index, the neighbour sums run over the liquid ones.  Faces
+    between two interior cells of which at least one is liquid are corrected with p as the array holds it (0 in air), other interior
+    faces are left unchanged, wall faces become 0: every liquid cell ends divergence free to the solve's accuracy.  p = 0 sits at the
+    air cell centres (first-order surface; mantaflow's ghost-fluid treatment is left out), and there is no preconditioner.  A liquid
+    region that touches no air is singular but consistent, as a closed box is.  Returns ``(vel_projected, pressure, iterations)``;
+    ``out`` may be ``vel``."""
+    with torch.no_grad():
+        v, nd = _smoke_vel(vel, "solve_pressure_liquid")
+        bnd = _liquid_bnd(bnd, "solve_pressure_liquid")
+        if not accuracy >= 0:
+            raise ValueError("solve_pressure_liquid: accuracy must be >= 0, got %r" % (accuracy,))
+        fl = _liquid_flags_arg(flags, v, "solve_pressure_liquid")
+        dims, dims4 = _pressure_dims(v, nd)
+        if max_iter is None:
+            max_iter = default_max_iter(dims[1:])
+        check_every = DEFAULT_CHECK_EVERY if check_every is None else int(check_every)
+        if max_iter < 0 or check_every < 1:
+            raise ValueError("solve_pressure_liquid: max_iter must be >= 0 and check_every >= 1, got %r, %r" % (max_iter, check_every))
+        out = _smoke_out(out, v, "solve_pressure_liquid")
+        ws = workspace if workspace is not None else pressure_workspace(v)
+        if ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous():
+            raise ValueError("solve_pressure_liquid: workspace must be a contiguous float32 GPU tensor (pressure_workspace)")
+        nbytes = ws.numel() * 4
+        pressure = _empty(dims, v)
+        words = torch.empty((1 + dims[0],), dtype=torch.int32, device=v.device)
+        count, iters = words[:1], words[1:]
+        acc, max_iter = float(accuracy), int(max_iter)
+        call("df_pressure_init%dd_flags" % nd, _ptr(v), _ptr(pressure), _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, _stream()]))
+        k = _cg_loop(lambda k: call("df_pressure_cg_direction%dd_liquid" % nd, _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, acc, max_iter, _stream()])),
+                     lambda k: call("df_pressure_cg_update%dd_flags" % nd, _ptr(pressure), _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, _stream()])),
+                     ws, nbytes, dims4, count, max_iter, check_every)
+        call("df_pressure_status", _ptr(ws), nbytes, *(dims4 + [k, None, _ptr(iters), _stream()]))
+        call("df_pressure_correct%dd_liquid" % nd, _ptr(v), _ptr(pressure), _ptr(out), _ptr(fl), *(dims + [bnd, _stream()]))
+        return out, pressure, iters.clone()
+
+
+def flip_update(pos, pvel, vel, vel_old, flip_ratio=DEFAULT_FLIP_RATIO, out=None):
+    """mantaflow's ``flipVelocityUpdate``: with ``u(.)`` the MAC sample of ``advect_particles``, ``un = u(vel, p)``,
+    ``d = un - u(vel_old, p)``, ``pvel = flip_ratio * (pvel + d) + (1 - flip_ratio) * un``.  ``out`` may be ``pvel``."""
+    with torch.no_grad():
+        p = _particle_pos(pos, "flip_update")
+        u = _particle_pos(pvel, "flip_update")
+        B, N, nd = p.shape
+        if tuple(u.shape) != tuple(p.shape):
+            raise ValueError("flip_update: velocities %s for positions %s" % (tuple(u.shape), tuple(p.shape)))
+        v = _liquid_vel(vel, B, nd, "flip_update")
+        vo = _liquid_vel(vel_old, B, nd, "flip_update")
+        if tuple(vo.shape) != tuple(v.shape):
+            raise ValueError("flip_update: vel_old %s for vel %s" % (tuple(vo.shape), tuple(v.shape)))
+        if not 0.0 <= flip_ratio <= 1.0:
+            raise ValueError("flip_update: flip_ratio must lie in [0, 1], got %r" % (flip_ratio,))
+        if out is None:
+            out = torch.empty_like(u)
+        elif tuple(out.shape) != tuple(u.shape) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("flip_update: out must be a contiguous float32 GPU tensor of the velocities' shape")
+        call("df_flip_update%dd" % nd, _ptr(p), _ptr(u), _ptr(out), _ptr(v), _ptr(vo), B, N, *(list(v.shape[1:-1]) + [float(flip_ratio), _stream()]))
+        return out
+
+
+def sample_velocity(vel, pos):
+    """``u(vel, p)`` at the particles (mantaflow's ``mapGridToPartsVec3`` of a MAC grid): the FLIP update with ratio 0 from zero particle
+    velocities, which is ``0 * (0 + 0) + 1 * u`` -- the sample's own bits."""
+    with torch.no_grad():
+        p = _particle_pos(pos, "sample_velocity")
+        return flip_update(p, torch.zeros_like(p), vel, vel, flip_ratio=0.0)
+
+
+def _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws):
+    nd = p.shape[-1]
+    shape = tuple(v.shape[1:-1])
+    B, N = p.shape[0], p.shape[1]
+    moved = advect_particles(p, v, dt, bnd=bnd)
+    spos, cell_start, order = particle_cells(moved, shape)
+    su = torch.empty_like(u)
+    call("df_particles_gather", _ptr(u), _ptr(order), _ptr(su), B * N, nd, _stream())
+    vel, weight, known = particles_to_grid(spos, su, cell_start, shape)
+    vel_old = vel                                            # extrapolate_mac leaves its input untouched
+    vel, _ = extrapolate_mac(vel, known, 2, bnd=bnd)
+    flags, touch = liquid_flags(cell_start, shape, B, N, bnd=bnd)
+    liquid_forces(vel, flags, force, bnd=bnd, out=vel)
+    _, _, iters = solve_pressure_liquid(vel, flags, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=vel, workspace=pws)
+    vel, _ = extrapolate_mac(vel, touch, 4, bnd=bnd)
+    flip_update(spos, su, vel, vel_old, flip_ratio=flip_ratio, out=su)
+    return spos, su, vel, iters
+
+
+def _liquid_state(pos, pvel, vel, who):
+    p = _particle_pos(pos, who)
+    u = _particle_pos(pvel, who)
+    if tuple(u.shape) != tuple(p.shape):
+        raise ValueError("%s: particle velocities %s for positions %s" % (who, tuple(u.shape), tuple(p.shape)))
+    v = _liquid_vel(vel, p.shape[0], p.shape[-1], who)
+    return p, u, v
+
+
+def liquid_step(pos, pvel, vel, dt, force=None, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, flip_ratio=DEFAULT_FLIP_RATIO,
+                open_bound=False):
+    """One frame of the reference's liquid scenes (scene/liquid_pos_size.py:254-295) on particles ``pos``, ``pvel`` [B,N,D] and the MAC
+    velocity ``vel`` [B,(Z,)Y,X,D], in the script's order: trace the particles through ``vel`` (RK4), sort them by cell, map their
+    velocities to the grid, extrapolate 2 layers from the faces that received weight, mark the liquid cells, add gravity (``force``,
+    cells per step; default ``default_gravity_force``, restated from memory of mantaflow's addGravity) and zero the wall faces, project
+    with p = 0 in the air cells, extrapolate 4 layers from the faces of liquid cells, update the particle velocities (FLIP,
+    ``flip_ratio``).  Returns ``(pos, pvel, vel, iterations)``: the particles come back SORTED by cell, so the step permutes them
+    (``pos`` and ``pvel`` alike); ``vel`` is the frame the script saves.  Left out, as named in include/deepfluids_hip.h: the
+    ghost-fluid surface, adjustNumber, the averaged level set, open sides (``open_bound=True`` is refused), obstacles, MIC(0)."""
+    if open_bound:
+        raise NotImplementedError("liquid_step: open sides (resetOutflow) are not implemented for the liquid solver")
+    with torch.no_grad():
+        p, u, v = _liquid_state(pos, pvel, vel, "liquid_step")
+        bnd = _liquid_bnd(bnd, "liquid_step")
+        force = default_gravity_force(v.shape[1:-1], dt) if force is None else force
+        return _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pressure_workspace(v))
+
+
+def _liquid_frames(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats):
+    p, u, v = _liquid_state(pos0, pvel0, vel0, "simulate_liquid")
+    bnd = _liquid_bnd(bnd, "simulate_liquid")
+    force = default_gravity_force(v.shape[1:-1], dt) if force is None else force
+    pws = pressure_workspace(v)
+    for t in range(int(steps)):
+        p, u, v, iters = _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws)
+        if stats is not None:
+            stats.append(iters)
+        yield p, u, v
+
+
+def simulate_liquid(pos0, pvel0, vel0, steps, dt=0.5, force=None, bnd=1, accuracy=1e-4, max_iter=None, check_every=None,
+                    flip_ratio=DEFAULT_FLIP_RATIO, stack=True, stats=None, open_bound=False):
+    """``steps`` chained ``liquid_step`` frames from ``(pos0, pvel0, vel0)`` (left untouched).  With ``stack`` returns
+    ``(pos, pvel, vels)``, ``vels`` [steps,B,(Z,)Y,X,D] the velocity after each step; without it a generator of ``(pos, pvel, vel)`` per
+    step.  ``stats``: a list that receives the iteration counts [B] of every step's solve."""
+    if open_bound:
+        raise NotImplementedError("simulate_liquid: open sides (resetOutflow) are not implemented for the liquid solver")
+    with torch.no_grad():
+        gen = _liquid_frames(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats)
+        if not stack:
+            return _no_grad_iter(gen)
+        vels = torch.empty((int(steps),) + tuple(vel0.shape), dtype=torch.float32, device=vel0.device)
+        p, u = pos0, pvel0
+        for t, (p, u, v) in enumerate(gen):
+            vels[t].copy_(v)
+        return p, u, vels
+
+
+def liquid_initial_state(shape, phi0, vel_spheres=(), discretization=2, randomness=0.05, seed=123, bnd=1, device="cuda"):
+    """The state the liquid scenes start from (scene/liquid_pos_size.py:235-252): particles seeded in ``phi0`` [(Z,)Y,X] < 0
+    (``seed_particles``; join bodies with ``np.minimum``), a velocity that is (0, -1[, 0]) on the faces whose centre lies inside one of
+    ``vel_spheres`` ((centre xyz, radius) pairs, cell units; ``Sphere.applyToGrid`` on a MAC grid, restated from memory) and 0
+    elsewhere, and ``pvel = u(vel, p)``.  Returns ``(pos [1,N,D], pvel [1,N,D], vel [1,(Z,)Y,X,D])`` on ``device``."""
+    shape = tuple(int(n) for n in shape)
+    nd = len(shape)
+    if nd not in (2, 3) or tuple(np.shape(phi0)) != shape:
+        raise ValueError("liquid_initial_state expects a shape [(Z,)Y,X] and a level set of that shape, got %s, %s" % (shape, np.shape(phi0)))
+    pos = seed_particles(phi0, discretization, randomness, seed, bnd)
+    vel = np.zeros(shape + (nd,), np.float32)
+    for centre, radius in vel_spheres:
+        if len(centre) != nd:
+            raise ValueError("liquid_initial_state: a sphere centre of %d coordinates on a %d-D grid" % (len(centre), nd))
+        d2 = np.zeros(shape, np.float64)
+        for a, c in enumerate(centre):
+            d2 = d2 + ((_centres(shape, a) - (0.5 if a == 1 else 0.0)) - float(c)) ** 2       # the y face: (i + .5, j[, k + .5])
+        vel[..., 1] = np.where(d2 <= float(radius) ** 2, np.float32(-1.0), vel[..., 1])
+    p = torch.from_numpy(pos[None]).to(device)
+    v = torch.from_numpy(vel[None]).to(device)
+    return p, sample_velocity(v, p), v
+
+
 def plane_view_np(x, xy_plane=True, project=True):
     """ops.py:326-342: host NumPy, x [Z,Y,X,C] -> float image in [0,255] (no uint8 cast)."""
     x = np.asarray(x)

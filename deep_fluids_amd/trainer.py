@@ -817,6 +817,28 @@ def liquid3_vis_body(batch_manager):
     return {"boxes": [((0.3, 0.0, 0.3), (0.7, 0.8, 0.7))]}
 
 
+def liquid_pos_size_body(batch_manager, p1, p2):
+    """The liquid body of scene/liquid_pos_size.py:235-242 for grid indices (p1, p2) of a dataset written by that scene (or by
+    ``data.generate_liquid_dataset``): the basin 0..1 x 0..basin_y_pos and the drop at (x_pos, src_y_pos) of radius r (fractions of the
+    grid, the radius of X), x_pos and r interpolated from the min_/max_/num_ keys of args.txt.  A ``body`` for
+    ``Trainer.advect_liquid_``."""
+    if batch_manager.is_3d:
+        raise ValueError("liquid_pos_size_body: the liquid_pos_size scene is 2-D")
+    a = batch_manager.args
+    keys = ["min_src_x_pos", "max_src_x_pos", "num_src_x_pos", "min_src_radius", "max_src_radius", "num_src_radius", "src_y_pos", "basin_y_pos"]
+    missing = [k for k in keys if k not in a]
+    if missing:
+        raise KeyError("liquid_pos_size_body: args.txt of %s lacks %s -- the dataset is not a liquid_pos_size scene" %
+                       (batch_manager.root, ", ".join(missing)))
+
+    def param(i, name):
+        lo, hi, num = float(a["min_" + name]), float(a["max_" + name]), int(a["num_" + name])
+        return i / float(num - 1) * (hi - lo) + lo if num > 1 else lo
+
+    return {"boxes": [((0.0, 0.0), (1.0, float(a["basin_y_pos"])))],
+            "spheres": [((param(p1, "src_x_pos"), float(a["src_y_pos"])), param(p2, "src_radius"))]}
+
+
 class Trainer3(Trainer):
     """trainer3.py: the 3-D overrides are selected by ``config.is_3d``; kept as a name for call-site parity."""
 

@@ -779,6 +779,78 @@ int df_density_sphere_source2d(const float* density, const float* centers, float
 int df_density_sphere_source3d(const float* density, const float* centers, float radius, float value, float* out, int64_t B, int64_t Z,
                                int64_t Y, int64_t X, df_stream_t stream);
 
+/* ---- the liquid solver step: the main() loops of the reference's liquid scenes (scene/liquid_pos_size.py:254-295, scene/liquid3_d_r.py),
+ * a FLIP step in the script's order:  pp.advectInGrid(IntRK4), mapPartsToMAC, extrapolateMACFromWeight(distance=2), markFluidCells,
+ * addGravity, setWallBcs, solvePressure, setWallBcs, extrapolateMACSimple(distance=4), flipVelocityUpdate(flipRatio).  The trace, the keys,
+ * the gather and the ranges are df_particles_* above, the solve reuses df_pressure_init*_flags, df_pressure_cg_update*_flags,
+ * df_pressure_status and the workspace; the rest is below.  mantaflow cannot be run beside this library: its kernels are restated from
+ * memory, and parity is with the NumPy restatement of THIS definition (tests/liquid_ref.py), NOT with mantaflow.
+ * Left out: the ghost-fluid surface treatment (solvePressure(phi=)): p = 0 sits at the centres of the air cells, a first-order surface;
+ * adjustNumber resampling (N is constant); averagedParticleLevelset, extrapolateLsSimple and phi.setBound (the solve does not read phi);
+ * resetOutflow and open sides; obstacles inside the liquid; the MIC(0) preconditioner; per-entry particle counts (one call, one N).
+ *
+ * Layouts, bnd, "interior", e_a, u(p) and the per-axis weights (n; s0, s1) are those of the blocks above.  pos, pvel [B,N,D] fp32 SORTED
+ * by key (df_particles_gather with the order of the key sort, for both); vel, weight [B,(Z,)Y,X,D] fp32; marks [B,(Z,)Y,X,D] uint8;
+ * flags [B,(Z,)Y,X] uint8.  All arithmetic fp32, no fused multiply-add, in the order written; no floating-point atomics; the result of a
+ * batch entry does not depend on the rest of the batch.
+ *   p2g      df_liquid_p2g*: the transpose of u(p).  For component a of cell c, every particle p of the 3^D cells around c that lie inside
+ *            the grid is visited in ascending cell order (z, then y, then x), inside a cell in sorted order, with
+ *            w = (w_x * w_y) [* w_z],  w_b = s0 if n == c_b, s1 if n + 1 == c_b, else 0, (n; s0, s1) the weights of q_b = p_b (b == a) or
+ *            q_b = p_b - 0.5 (b != a): the weight with which u(p) reads that face (only the 2 cells along a and the 3 along every other
+ *            axis can reach it; the others add w = 0).  num += w * pvel_a, den += w from 0;  weight = den, vel = den > 0 ? num / den : 0,
+ *            known (may be NULL) = den > 0 ? 1 : 0.  N = 0: zeros everywhere, the particle arrays and cell_start may be NULL.
+ *   extrapolate  df_mac_extrapolate*, ONE layer per call, layer = 1, 2, ...: a component a of cell c with mark 0, c and c - e_a interior,
+ *            looks at the same component of c - e_x, c + e_x, c - e_y, c + e_y[, c - e_z, c + e_z] in that order; with cnt > 0 of them
+ *            marked in 1..layer it becomes (sum of their values in that order) / (float)cnt and takes mark layer + 1.  Everything else
+ *            is copied, so wall faces are never filled (they may be sources).  Reads (vel, mark), writes (vel_out, mark_out): no overlap.
+ *   flags    df_liquid_flags*: the byte of df_obstacle_flags* with "fluid" = LIQUID = interior and cell_start[c + 1] > cell_start[c]
+ *            (bit 0 the cell, bits 1..6 its x-, x+, y-, y+, z-, z+ neighbour).  touch (may be NULL) [..,D]: 1 where c or c - e_a is
+ *            liquid -- the "known" of the second extrapolation.  N = 0: all air, cell_start may be NULL.
+ *   forces   df_liquid_forces*: component a of c is 0 unless c and c - e_a are interior; there it gets + force[a] when c or c - e_a is
+ *            liquid and is copied otherwise.  out may be vel.
+ *   pressure rows for liquid cells only: b = -div, n_c = the neighbours interior by their index (liquid or air), the neighbour sums run
+ *            over liquid neighbours, p = 0 in air.  ONLY df_pressure_cg_direction*_liquid differs from the `_flags` solve, in n_c.
+ *            df_pressure_correct*_liquid: where c and c - e_a are interior and one of them is liquid, out = vel - (p[c] - p[c - e_a])
+ *            with p as the array holds it; other faces between interior cells are copied, wall faces are 0.  A liquid region with no air
+ *            neighbour is singular but consistent, as in a closed box.
+ *            Bit rule: with every interior cell liquid both return the bits of df_pressure_cg_direction* / df_pressure_correct*.
+ *   flip     df_flip_update*: un = u(vel, p), d = un - u(vel_old, p), pvel' = flip_ratio * (pvel + d) + (1 - flip_ratio) * un with
+ *            1 - flip_ratio rounded to fp32 once on the host.  pvel_out may be pvel_in.  N = 0: nothing is launched.
+ * Non-finite values and out-of-range entries of cell_start select edge cells or edge particles, never memory outside the arrays; a flags
+ * byte is believed only where the cell is interior by its index.
+ * Errors: DF_EINVAL null pointer / non-positive extent / N < 0 / bnd < 1 / layer outside 1..254 / flip_ratio outside [0, 1] / an output
+ * that is or overlaps an array the launch gathers from (extrapolate in place, marks or flags over a velocity, outputs over cell_start),
+ * DF_ESHAPE an extent < 2*bnd + 2 or too large, B*N or B*ncell beyond int32, DF_EALIGN a float or int32 pointer not 4-byte aligned,
+ * DF_EWORKSPACE (the pressure entry points) a workspace smaller than df_pressure_workspace_bytes. */
+int df_liquid_p2g2d(const float* pos_sorted, const float* pvel_sorted, const int32_t* cell_start, float* vel, float* weight, uint8_t* known,
+                    int64_t B, int64_t N, int64_t Y, int64_t X, df_stream_t stream);
+int df_liquid_p2g3d(const float* pos_sorted, const float* pvel_sorted, const int32_t* cell_start, float* vel, float* weight, uint8_t* known,
+                    int64_t B, int64_t N, int64_t Z, int64_t Y, int64_t X, df_stream_t stream);
+int df_mac_extrapolate2d(const float* vel, const uint8_t* mark, float* vel_out, uint8_t* mark_out, int64_t B, int64_t Y, int64_t X, int bnd,
+                         int layer, df_stream_t stream);
+int df_mac_extrapolate3d(const float* vel, const uint8_t* mark, float* vel_out, uint8_t* mark_out, int64_t B, int64_t Z, int64_t Y, int64_t X,
+                         int bnd, int layer, df_stream_t stream);
+int df_liquid_flags2d(const int32_t* cell_start, uint8_t* flags, uint8_t* touch, int64_t B, int64_t N, int64_t Y, int64_t X, int bnd,
+                      df_stream_t stream);
+int df_liquid_flags3d(const int32_t* cell_start, uint8_t* flags, uint8_t* touch, int64_t B, int64_t N, int64_t Z, int64_t Y, int64_t X,
+                      int bnd, df_stream_t stream);
+int df_liquid_forces2d(const float* vel, const uint8_t* flags, float* out, int64_t B, int64_t Y, int64_t X, float fx, float fy, int bnd,
+                       df_stream_t stream);
+int df_liquid_forces3d(const float* vel, const uint8_t* flags, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, float fx, float fy,
+                       float fz, int bnd, df_stream_t stream);
+int df_pressure_cg_direction2d_liquid(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k,
+                                      float accuracy, int64_t max_iter, df_stream_t stream);
+int df_pressure_cg_direction3d_liquid(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                                      int64_t k, float accuracy, int64_t max_iter, df_stream_t stream);
+int df_pressure_correct2d_liquid(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Y, int64_t X,
+                                 int bnd, df_stream_t stream);
+int df_pressure_correct3d_liquid(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
+                                 int64_t X, int bnd, df_stream_t stream);
+int df_flip_update2d(const float* pos, const float* pvel_in, float* pvel_out, const float* vel, const float* vel_old, int64_t B, int64_t N,
+                     int64_t Y, int64_t X, float flip_ratio, df_stream_t stream);
+int df_flip_update3d(const float* pos, const float* pvel_in, float* pvel_out, const float* vel, const float* vel_old, int64_t B, int64_t N,
+                     int64_t Z, int64_t Y, int64_t X, float flip_ratio, df_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
