@@ -199,6 +199,15 @@ SIGNATURES = {
     "df_pressure_correct3d_liquid": (I32, [P, P, P, P, I64, I64, I64, I64, I32, P]),
     "df_flip_update2d": (I32, [P, P, P, P, P, I64, I64, I64, I64, F32, P]),
     "df_flip_update3d": (I32, [P, P, P, P, P, I64, I64, I64, I64, I64, F32, P]),
+    "df_diffuse_workspace_bytes": (I64, [I64, I64, I64, I64, I32]),
+    "df_diffuse_init2d": (I32, [P, P, P, I64, I64, I64, I64, I32, P]),
+    "df_diffuse_init3d": (I32, [P, P, P, I64, I64, I64, I64, I64, I32, P]),
+    "df_diffuse_cg_direction2d": (I32, [P, P, I64, I64, I64, I64, I32, I64, F32, I64, P]),
+    "df_diffuse_cg_direction3d": (I32, [P, P, I64, I64, I64, I64, I64, I32, I64, F32, I64, P]),
+    "df_diffuse_cg_update2d": (I32, [P, I64, I64, I64, I64, I32, I64, P]),
+    "df_diffuse_cg_update3d": (I32, [P, I64, I64, I64, I64, I64, I32, I64, P]),
+    "df_diffuse_finish2d": (I32, [P, I64, P, I64, I64, I64, I32, P]),
+    "df_diffuse_finish3d": (I32, [P, I64, P, I64, I64, I64, I64, I32, P]),
 }
 
 DF_CONV_LRELU, DF_CONV_RESIDUAL, DF_CONV_MASK, DF_CONV_BIAS, DF_CONV_ADDUP, DF_CONV_VALU_ONLY = 1, 2, 4, 8, 16, 32

@@ -34,6 +34,12 @@
 //   open_extrapolate  zero-gradient fill of the open cells, in place: every open cell copies, per component, from the fixed point of a
 //                     clamp of its index; a fixed point only ever copies onto itself, so there is no race.
 //   sphere_source     the source stamp with one sphere per batch entry, the centres read from device memory.
+//   diffusion         cgSolveDiffusion of the viscous liquid scene (scene/liquid3_vis.py:281), restated from memory as the header says: the
+//                     same CG over the B*D components of a velocity, each its own system (I + alpha * Laplacian on the interior cells,
+//                     the band Dirichlet data).  diffuse_init de-interleaves into planar x, r, p; the DIFFUSE instantiation of the
+//                     direction kernel reads the entry's alpha from device memory; the update kernel is the pressure solve's;
+//                     diffuse_finish interleaves x back.  The component reads of init (stride D) and the component gathers of finish
+//                     (D planes) are each coalesced along x within a plane; every other pass is planar.
 //
 // Float -> int conversions are taken only of values already known to be inside the grid (advect_common.hpp).
 #include "advect_common.hpp"
@@ -345,9 +351,11 @@ __global__ __launch_bounds__(kThreads) void pressure_init_kernel(const float* __
 // OPEN: p = 0 in open cells (Dirichlet), so an open neighbour counts in n_c and adds nothing to the sum
 // LIQUID (with MASKED; "fluid" reads "liquid"): p = 0 in air cells, so n_c counts every neighbour that is interior by its index, as
 // the unmasked path does, while the sums run over the liquid neighbours of the flags byte
-template <int D, bool MASKED, bool OPEN, bool LIQUID = false>
+// DIFFUSE (unmasked, closed): the entries are the B*D (entry, component) pairs of a velocity, A = I + alpha * (2D - neighbours in I), the
+// alpha of pair e is dalpha[e / D]; the sum is the one of the unmasked path (the direction is 0 off I)
+template <int D, bool MASKED, bool OPEN, bool LIQUID = false, bool DIFFUSE = false>
 __global__ __launch_bounds__(kThreads) void cg_direction_kernel(PWs w, const uint8_t* __restrict__ flags, PDims d, int par, int first,
-                                                                float accuracy, int max_iter, int os) {
+                                                                float accuracy, int max_iter, int os, const float* __restrict__ dalpha) {
   __shared__ float lds[4];
   const PCell c = pdecode<D, MASKED>(d, flags);
   const bool writer = c.j == 0 && threadIdx.x == 0;
@@ -392,7 +400,8 @@ __global__ __launch_bounds__(kThreads) void cg_direction_kernel(PWs w, const uin
 #pragma unroll
       for (int a = 0; a < D; ++a) cnt += ((c.p[a] == d.bnd && open_lo(os, a)) ? 1 : 0) + ((c.p[a] + 1 == ext[a] - d.bnd && open_hi(os, a)) ? 1 : 0);
     }
-    const float qv = static_cast<float>(cnt) * pc - sum;
+    float qv = static_cast<float>(cnt) * pc - sum;
+    if (DIFFUSE) qv = pc + dalpha[c.e / D] * (static_cast<float>(2 * D) * pc - sum);
     w.p[par ^ 1][eo + c.cell] = pc;
     w.q[eo + c.cell] = qv;
     pq = pc * qv;
@@ -440,6 +449,49 @@ __global__ __launch_bounds__(kThreads) void cg_status_kernel(const CgState* __re
   if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = n;
   __syncthreads();
   if (threadIdx.x == 0 && count) count[0] = lds[0] + lds[1] + lds[2] + lds[3];
+}
+
+// ---- implicit velocity diffusion: the CG above over the B*D (entry, component) pairs of a velocity ----------------------------------------
+// planar x, r, p from the interleaved velocity: x = u everywhere (the band is Dirichlet data and stays), r = b - A u =
+// alpha * (sum of all 2D neighbours - 2D * u) on I and 0 off it.  d.B = B*D pairs; pair e is component e % D of entry e / D.
+template <int D>
+__global__ __launch_bounds__(kThreads) void diffuse_init_kernel(const float* __restrict__ vel, const float* __restrict__ dalpha,
+                                                                float* __restrict__ x, PWs w, PDims d) {
+  __shared__ float lds[4];
+  const PCell c = pdecode<D>(d);
+  const int be = c.e / D, a = c.e - be * D;
+  const int64_t g = static_cast<int64_t>(c.e) * d.n + c.cell;
+  float r = 0.0f;
+  if (c.cell < d.n) {
+    const float* v = vel + (static_cast<int64_t>(be) * d.n + c.cell) * D + a;
+    const float u = v[0];
+    if (c.interior) {                                   // bnd >= 1: all 2D neighbours are inside the entry
+      const int64_t st[3] = {D, static_cast<int64_t>(d.X) * D, static_cast<int64_t>(d.X) * d.Y * D};
+      float sum = 0.0f;
+#pragma unroll
+      for (int b = 0; b < D; ++b) { sum += v[-st[b]]; sum += v[st[b]]; }
+      r = dalpha[be] * (sum - static_cast<float>(2 * D) * u);
+    }
+    x[g] = u; w.r[g] = r; w.p[0][g] = r; w.p[1][g] = 0.0f; w.q[g] = 0.0f;
+  }
+  const float rr = block_reduce<false>(r * r, lds);
+  const float mx = block_reduce<true>(fabsf(r), lds);
+  if (threadIdx.x == 0) {
+    w.rr_part[static_cast<int64_t>(c.e) * d.nblk + c.j] = rr;
+    w.mx_part[static_cast<int64_t>(c.e) * d.nblk + c.j] = mx;
+  }
+}
+
+// the planar x back into the interleaved velocity, one thread = one cell and its D components; x holds the input's bits off I
+template <int D>
+__global__ __launch_bounds__(kThreads) void diffuse_finish_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t n, int64_t ncell) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (idx >= ncell) return;
+  const int64_t e = idx / n, cell = idx - e * n;
+  VelRec<D> r;
+#pragma unroll
+  for (int a = 0; a < D; ++a) r.v[a] = x[(e * D + a) * n + cell];
+  *reinterpret_cast<VelRec<D>*>(out + idx * D) = r;
 }
 
 // OPEN: live faces are corrected with p as the array holds it (0 outside the fluid), open cells keep their other components
@@ -642,9 +694,9 @@ int pressure_init(const char* fn, const float* vel, float* pressure, void* ws, i
   return df::launched(fn);
 }
 
-template <int D, bool MASKED, bool OPEN = false, bool LIQUID = false>
+template <int D, bool MASKED, bool OPEN = false, bool LIQUID = false, bool DIFFUSE = false>
 int cg_direction(const char* fn, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
-                 int64_t k, float accuracy, int64_t max_iter, df_stream_t stream, int os = 0) {
+                 int64_t k, float accuracy, int64_t max_iter, df_stream_t stream, int os = 0, const float* dalpha = nullptr) {
   PDims d;
   unsigned grid;
   if (int e = pplan(fn, D, B, Z, Y, X, bnd, &d, &grid)) return e;
@@ -654,8 +706,8 @@ int cg_direction(const char* fn, void* ws, int64_t ws_bytes, const uint8_t* flag
   DF_REQUIRE(accuracy >= 0.0f, DF_EINVAL, "%s: accuracy must be >= 0", fn);
   if (int e = check_flags<MASKED>(fn, flags, d.n * B, nullptr, 0, "")) return e;
   if (MASKED) if (int e = check_apart(fn, ws, d, flags, d.n * B, "flags")) return e;
-  hipLaunchKernelGGL((cg_direction_kernel<D, MASKED, OPEN, LIQUID>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), carve(ws, B, d.n, d.nblk),
-                     flags, d, (int)(k & 1), k == 0 ? 1 : 0, accuracy, (int)max_iter, os);
+  hipLaunchKernelGGL((cg_direction_kernel<D, MASKED, OPEN, LIQUID, DIFFUSE>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream),
+                     carve(ws, B, d.n, d.nblk), flags, d, (int)(k & 1), k == 0 ? 1 : 0, accuracy, (int)max_iter, os, dalpha);
   return df::launched(fn);
 }
 
@@ -720,6 +772,79 @@ int sphere_source(const char* fn, const float* density, const float* centers, fl
   const AdvDims d{n, (int)Z, (int)Y, (int)X, 0, 0.0f, 1.0f};
   hipLaunchKernelGGL((sphere_source_kernel<D>), dim3((unsigned)ceil_div(n, kThreads)), dim3(kThreads), 0, df::as_stream(stream), density,
                      centers, radius, value, out, d);
+  return df::launched(fn);
+}
+
+// the solve over B*D pairs: its plan, and the workspace = the CG's for B*D entries, then the planar x
+template <int D>
+int dplan(const char* fn, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, PDims* d, unsigned* grid, float** x) {
+  DF_REQUIRE(B > 0 && B < (1 << 24) / D, B > 0 ? DF_ESHAPE : DF_EINVAL, "%s: %s", fn, B > 0 ? "extent too large" : "non-positive extent");
+  if (int e = pplan(fn, D, B * D, Z, Y, X, bnd, d, grid)) return e;
+  DF_REQUIRE(ws, DF_EINVAL, "%s: null workspace", fn);
+  DF_REQUIRE(aligned4(ws), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  const int64_t cg = ws_floats(d->B, d->n, d->nblk), need = 4 * (cg + d->B * d->n);
+  DF_REQUIRE(ws_bytes >= need, DF_EWORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes, (long long)need);
+  *x = static_cast<float*>(ws) + cg;
+  return DF_OK;
+}
+
+// an array beside the workspace shares no byte with it
+int dapart(const char* fn, const void* ws, const PDims& d, const void* p, int64_t bytes, const char* what) {
+  DF_REQUIRE(apart(ws, 4 * (ws_floats(d.B, d.n, d.nblk) + d.B * d.n), p, bytes), DF_EINVAL, "%s: the workspace overlaps the %s", fn, what);
+  return DF_OK;
+}
+
+template <int D>
+int diffuse_init(const char* fn, const float* vel, const float* alpha, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X,
+                 int bnd, df_stream_t stream) {
+  DF_REQUIRE(vel && alpha, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : "alpha");
+  PDims d;
+  unsigned grid;
+  float* x;
+  if (int e = dplan<D>(fn, ws, ws_bytes, B, Z, Y, X, bnd, &d, &grid, &x)) return e;
+  if (int e = dapart(fn, ws, d, vel, 4 * d.n * d.B, "velocity")) return e;
+  if (int e = dapart(fn, ws, d, alpha, 4 * B, "alpha")) return e;
+  DF_REQUIRE(aligned4(vel) && aligned4(alpha), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  hipLaunchKernelGGL((diffuse_init_kernel<D>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), vel, alpha, x, carve(ws, d.B, d.n, d.nblk), d);
+  return df::launched(fn);
+}
+
+template <int D>
+int diffuse_direction(const char* fn, const float* alpha, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                      int64_t k, float accuracy, int64_t max_iter, df_stream_t stream) {
+  DF_REQUIRE(alpha, DF_EINVAL, "%s: null alpha", fn);
+  PDims d;
+  unsigned grid;
+  float* x;
+  if (int e = dplan<D>(fn, ws, ws_bytes, B, Z, Y, X, bnd, &d, &grid, &x)) return e;
+  if (int e = dapart(fn, ws, d, alpha, 4 * B, "alpha")) return e;
+  DF_REQUIRE(aligned4(alpha), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  return cg_direction<D, false, false, false, true>(fn, ws, ws_bytes, nullptr, d.B, Z, Y, X, bnd, k, accuracy, max_iter, stream, 0, alpha);
+}
+
+template <int D>
+int diffuse_update(const char* fn, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k,
+                   df_stream_t stream) {
+  PDims d;
+  unsigned grid;
+  float* x;
+  if (int e = dplan<D>(fn, ws, ws_bytes, B, Z, Y, X, bnd, &d, &grid, &x)) return e;
+  return cg_update<D, false>(fn, x, ws, ws_bytes, nullptr, d.B, Z, Y, X, bnd, k, stream);
+}
+
+template <int D>
+int diffuse_finish(const char* fn, void* ws, int64_t ws_bytes, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                   df_stream_t stream) {
+  DF_REQUIRE(out, DF_EINVAL, "%s: null output", fn);
+  PDims d;
+  unsigned grid;
+  float* x;
+  if (int e = dplan<D>(fn, ws, ws_bytes, B, Z, Y, X, bnd, &d, &grid, &x)) return e;
+  if (int e = dapart(fn, ws, d, out, 4 * d.n * d.B, "output")) return e;
+  DF_REQUIRE(aligned4(out), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  const int64_t ncell = B * d.n;                        // B * nblk < 2^31 (pplan): so is ceil(ncell / kThreads)
+  hipLaunchKernelGGL((diffuse_finish_kernel<D>), dim3((unsigned)ceil_div(ncell, kThreads)), dim3(kThreads), 0, df::as_stream(stream), x, out,
+                     d.n, ncell);
   return df::launched(fn);
 }
 
@@ -947,6 +1072,41 @@ int df_pressure_correct2d_liquid(const float* vel, const float* pressure, float*
 int df_pressure_correct3d_liquid(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
                                  int64_t X, int bnd, df_stream_t stream) {
   return pressure_correct<3, true, false, true>("df_pressure_correct3d_liquid", vel, pressure, out, flags, B, Z, Y, X, bnd, stream);
+}
+// ---- implicit velocity diffusion (cgSolveDiffusion): the CG over the B*D components, alpha[B] in device memory ----
+int64_t df_diffuse_workspace_bytes(int64_t B, int64_t Z, int64_t Y, int64_t X, int dim) {
+  if (dim != 2 && dim != 3) return DF_EINVAL;
+  if (B <= 0 || B >= (1 << 24) / dim) return B <= 0 ? DF_EINVAL : DF_ESHAPE;
+  const int64_t cg = df_pressure_workspace_bytes(B * dim, Z, Y, X);
+  return cg < 0 ? cg : cg + 4 * B * dim * Z * Y * X;
+}
+int df_diffuse_init2d(const float* vel, const float* alpha, void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int64_t X, int bnd,
+                      df_stream_t stream) {
+  return diffuse_init<2>("df_diffuse_init2d", vel, alpha, ws, ws_bytes, B, 1, Y, X, bnd, stream);
+}
+int df_diffuse_init3d(const float* vel, const float* alpha, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                      df_stream_t stream) {
+  return diffuse_init<3>("df_diffuse_init3d", vel, alpha, ws, ws_bytes, B, Z, Y, X, bnd, stream);
+}
+int df_diffuse_cg_direction2d(const float* alpha, void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k,
+                              float accuracy, int64_t max_iter, df_stream_t stream) {
+  return diffuse_direction<2>("df_diffuse_cg_direction2d", alpha, ws, ws_bytes, B, 1, Y, X, bnd, k, accuracy, max_iter, stream);
+}
+int df_diffuse_cg_direction3d(const float* alpha, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k,
+                              float accuracy, int64_t max_iter, df_stream_t stream) {
+  return diffuse_direction<3>("df_diffuse_cg_direction3d", alpha, ws, ws_bytes, B, Z, Y, X, bnd, k, accuracy, max_iter, stream);
+}
+int df_diffuse_cg_update2d(void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k, df_stream_t stream) {
+  return diffuse_update<2>("df_diffuse_cg_update2d", ws, ws_bytes, B, 1, Y, X, bnd, k, stream);
+}
+int df_diffuse_cg_update3d(void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k, df_stream_t stream) {
+  return diffuse_update<3>("df_diffuse_cg_update3d", ws, ws_bytes, B, Z, Y, X, bnd, k, stream);
+}
+int df_diffuse_finish2d(void* ws, int64_t ws_bytes, float* out, int64_t B, int64_t Y, int64_t X, int bnd, df_stream_t stream) {
+  return diffuse_finish<2>("df_diffuse_finish2d", ws, ws_bytes, out, B, 1, Y, X, bnd, stream);
+}
+int df_diffuse_finish3d(void* ws, int64_t ws_bytes, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, df_stream_t stream) {
+  return diffuse_finish<3>("df_diffuse_finish3d", ws, ws_bytes, out, B, Z, Y, X, bnd, stream);
 }
 int df_open_extrapolate2d(float* vel, int64_t B, int64_t Y, int64_t X, int bnd, int open_sides, df_stream_t stream) {
   return open_extrapolate<2>("df_open_extrapolate2d", vel, B, 1, Y, X, bnd, open_sides, stream);

@@ -354,10 +354,16 @@ def generate_smoke_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="sr
     return written
 
 
-def _simulate_liquid_scenes(root, path_format, scenes, shape, num_frames, time_step, gravity, bWidth, accuracy, flip_ratio, device, keep):
+def _simulate_liquid_scenes(root, path_format, scenes, shape, num_frames, time_step, gravity, bWidth, accuracy, flip_ratio, device, keep,
+                            alphas=None, substeps=1, label=None):
     """the frame loop of the liquid scene scripts: ``scenes`` = (i, j, p0, p1, phi0, velocity spheres); scenes that seed the same number
-    of particles run as one batch of ``ops.simulate_liquid``.  Writes v/ and v_range.txt; returns the number of files written."""
+    of particles run as one batch of ``ops.simulate_liquid``.  Writes v/ and v_range.txt; returns the number of files written.
+    ``alphas``: one diffusion number per scene (the viscous step); ``substeps``: solver steps per frame, frame f is step f * substeps;
+    ``label(scene, frame)``: the numbers of a file's name and its ``y``."""
     from . import ops
+    if label is None:
+        def label(sc, t):
+            return (sc[0], sc[1], t), [sc[2], sc[3], t]
     states = [ops.liquid_initial_state(shape, phi, spheres, bnd=bWidth, device=device) for _, _, _, _, phi, spheres in scenes]
     groups = {}
     for n, st in enumerate(states):
@@ -368,14 +374,16 @@ def _simulate_liquid_scenes(root, path_format, scenes, shape, num_frames, time_s
     for N in sorted(groups):
         part = groups[N]
         pos, pvel, vel = [torch.cat([states[n][k] for n in part]) for k in range(3)]
-        frames = ops.simulate_liquid(pos, pvel, vel, num_frames, dt=time_step, force=force, bnd=bWidth, accuracy=accuracy, flip_ratio=flip_ratio,
-                                     stack=False)
+        more = {} if alphas is None and substeps == 1 else dict(viscosity_alpha=None if alphas is None else [alphas[n] for n in part],
+                                                                keep_every=substeps)
+        frames = ops.simulate_liquid(pos, pvel, vel, (num_frames - 1) * substeps + 1 if num_frames > 0 else 0, dt=time_step, force=force,
+                                     bnd=bWidth, accuracy=accuracy, flip_ratio=flip_ratio, stack=False, **more)
         for t, (_, _, v) in enumerate(frames):
             vh = v.cpu().numpy()
             v_range = [min(v_range[0], float(vh.min())), max(v_range[1], float(vh.max()))]
             for e, n in enumerate(part):
-                i, j, q0, q1 = scenes[n][:4]
-                np.savez_compressed(os.path.join(root, "v", path_format % (i, j, t)), x=vh[e][..., :keep], y=[q0, q1, t])
+                name, y = label(scenes[n], t)
+                np.savez_compressed(os.path.join(root, "v", path_format % name), x=vh[e][..., :keep], y=y)
                 written += 1
     with open(os.path.join(root, "v_range.txt"), "w") as f:
         f.write("%.3f\n" % v_range[0])
@@ -393,7 +401,7 @@ def _write_args(root, args):
 def _liquid_refusals(who, open_bound, num_param, names, want):
     if open_bound:
         raise NotImplementedError("%s: open_bound (setOpenBound + resetOutflow) is not implemented for the liquid solver" % who)
-    if num_param != 3 or tuple(names) != tuple(want):
+    if num_param != len(want) or tuple(names) != tuple(want):
         raise ValueError("%s: the scene has the parameters %s" % (who, (want,)))
 
 
@@ -470,6 +478,50 @@ def generate_liquid3_d_r_dataset(root, num_param=3, path_format="%d_%d_%d.npz", 
                 phi = np.minimum(phi, ops.sphere_levelset(shape, c, X * src_radius))
             scenes.append((i, j, float(dist), float(rot), phi, [(c, X * (src_radius + 0.05)) for c in cs]))
     return _simulate_liquid_scenes(root, path_format, scenes, shape, num_frames, time_step, gravity, bWidth, accuracy, flip_ratio, device, 3)
+
+
+def generate_liquid3_vis_dataset(root, num_param=2, path_format="%d_%d.npz", p0="viscosity", p1="frames", viscosity_base=2, vmin=-5, vmax=-2,
+                                 min_viscosity=0, max_viscosity=3, num_viscosity=4, src_x_pos=0.4, src_y_pos=0.8, src_z_pos=0.4,
+                                 min_frames=0, max_frames=None, num_frames=150, num_simulations=None, resolution_x=96, resolution_y=72,
+                                 resolution_z=48, gravity=-1e-3, radius_factor=1, min_particles=3, bWidth=1, open_bound=False,
+                                 time_step=0.125, accuracy=1e-4, flip_ratio=0.97, device="cuda"):
+    """Simulate the reference's viscous 3-D liquid training set (scene/liquid3_vis.py main(), ``liquid3_vis4_f150``) on the GPU, in the
+    on-disk format of the script: ``args.txt`` with every script argument, ``v/%d_%d.npz`` (x [Z,Y,X,3] float32 velocity of frame f,
+    y = [p, f]) and ``v_range.txt``.  The box 0.3..0.7 x 0..0.8 x 0.3..0.7 of the grid (``trainer.liquid3_vis_body``) collapses from rest
+    under gravity at ``num_viscosity`` viscosities ``vis_list[int(p)]``, ``p`` the parameter values
+    ``linspace(min_viscosity, max_viscosity, num_viscosity)`` and ``vis_list = viscosity_base * logspace(vmin, vmax, num_viscosity)``.  Every
+    solver step diffuses the velocity implicitly (``ops.diffuse_velocity``) with ``alpha = ops.diffusion_alpha(visc, time_step,
+    resolution_x)``; a frame is ``round(1 / time_step)`` steps, frame f is saved after step ``f * substeps`` (the script's
+    ``timeTotal.is_integer()``), and a ``time_step`` whose reciprocal is not an integer is refused.  All scenes seed the same particles
+    and run as ONE batch.  ``src_*_pos``, ``radius_factor`` and ``min_particles`` are recorded only (the script does not use the first
+    three either; the level set and adjustNumber are left out).  What ``generate_liquid_dataset`` says about the step holds here too.
+    ``open_bound=True`` is refused.  Returns the number of files written."""
+    from . import ops
+    _liquid_refusals("generate_liquid3_vis_dataset", open_bound, num_param, (p0, p1), ("viscosity", "frames"))
+    steps_per_frame = 1.0 / float(time_step) if time_step > 0 else 0.0
+    substeps = int(round(steps_per_frame))
+    if substeps < 1 or abs(steps_per_frame - substeps) > 1e-9 * substeps:
+        raise ValueError("generate_liquid3_vis_dataset: 1 / time_step must be a whole number of steps per frame, got time_step = %r" % (time_step,))
+    max_frames = num_frames - 1 if max_frames is None else max_frames
+    num_simulations = num_viscosity * num_frames if num_simulations is None else num_simulations
+    p_list = np.linspace(min_viscosity, max_viscosity, num_viscosity)
+    vis_list = viscosity_base * np.logspace(vmin, vmax, num_viscosity)
+    if any(not 0 <= int(p) < num_viscosity for p in p_list):
+        raise ValueError("generate_liquid3_vis_dataset: the parameter values %s do not index the %d viscosities" % (p_list.tolist(), num_viscosity))
+    _write_args(root, [("log_dir", root), ("num_param", num_param), ("path_format", path_format), ("p0", p0), ("p1", p1),
+                       ("viscosity_base", viscosity_base), ("vmin", vmin), ("vmax", vmax), ("min_viscosity", min_viscosity),
+                       ("max_viscosity", max_viscosity), ("num_viscosity", num_viscosity), ("src_x_pos", src_x_pos), ("src_y_pos", src_y_pos),
+                       ("src_z_pos", src_z_pos), ("min_frames", min_frames), ("max_frames", max_frames), ("num_frames", num_frames),
+                       ("num_simulations", num_simulations), ("resolution_x", resolution_x), ("resolution_y", resolution_y),
+                       ("resolution_z", resolution_z), ("gravity", gravity), ("radius_factor", radius_factor),
+                       ("min_particles", min_particles), ("bWidth", bWidth), ("open_bound", open_bound), ("time_step", time_step)])
+    X, Y, Z = int(resolution_x), int(resolution_y), int(resolution_z)
+    shape = (Z, Y, X)
+    phi = ops.box_levelset(shape, (X * 0.3, 0.0, Z * 0.3), (X * 0.7, Y * 0.8, Z * 0.7))
+    scenes = [(i, None, float(p), None, phi, []) for i, p in enumerate(p_list)]
+    alphas = [ops.diffusion_alpha(float(vis_list[int(p)]), float(time_step), X) for p in p_list]
+    return _simulate_liquid_scenes(root, path_format, scenes, shape, num_frames, time_step, gravity, bWidth, accuracy, flip_ratio, device, 3,
+                                   alphas=alphas, substeps=substeps, label=lambda sc, f: ((sc[0], f), [sc[2], f]))
 
 
 def generate_smoke3_obs_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="obs_x_pos", p1="buoyancy", p2="frames", min_obs_x_pos=0.2,

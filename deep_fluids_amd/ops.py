@@ -2604,6 +2604,94 @@ def solve_pressure_liquid(vel, flags, bnd=1, accuracy=1e-4, max_iter=None, check
         return out, pressure, iters.clone()
 
 
+# ---- implicit velocity diffusion: cgSolveDiffusion of the viscous liquid scene (scene/liquid3_vis.py:277-281), the definition of
+#      include/deepfluids_hip.h ----
+def diffusion_alpha(viscosity, dt, resolution_x):
+    """The script's ``alphaV = visc * s.timestep * float(resolution_x * resolution_x)`` (scene/liquid3_vis.py:277): the diffusion number
+    ``viscosity * dt / dx^2`` with ``dx = 1 / resolution_x`` -- x, not the largest extent."""
+    return viscosity * dt * resolution_x ** 2
+
+
+def default_diffusion_max_iter(shape):
+    """mantaflow's ``cgMaxIterFac=1.0`` of cgSolveDiffusion: ``int(max(extent))``, times 4 in 2-D."""
+    return int(max(shape)) * (1 if len(shape) == 3 else 4)
+
+
+def diffusion_workspace(vel):
+    """The scratch ``diffuse_velocity`` needs for ``vel`` [B,(Z,)Y,X,D] (the pressure solve's arrays for B*D entries and the planar
+    solution): a float32 GPU tensor, reusable across calls of the same shape."""
+    v, nd = _smoke_vel(vel, "diffusion_workspace")
+    nbytes = query("df_diffuse_workspace_bytes", *([int(x) for x in _pressure_dims(v, nd)[1]] + [nd]))
+    if nbytes < 0:
+        raise ValueError("diffusion_workspace: unsupported extents %s" % (tuple(v.shape),))
+    return torch.empty((nbytes // 4,), dtype=torch.float32, device=v.device)
+
+
+def _diffusion_alpha_arg(alpha, B, who):
+    """[B] float32 on the host: a number for every entry or B of them, finite and >= 0"""
+    a = np.asarray(alpha, dtype=np.float64)
+    if a.ndim == 0:
+        a = np.full((B,), float(a))
+    if a.shape != (B,):
+        raise ValueError("%s: alpha must be a number or %d numbers, got shape %s" % (who, B, a.shape))
+    if not (np.isfinite(a).all() and (a >= 0).all()):
+        raise ValueError("%s: alpha must be finite and >= 0, got %r" % (who, alpha))
+    a32 = a.astype(np.float32)
+    if not np.isfinite(a32).all():
+        raise ValueError("%s: alpha must be finite in float32, got %r" % (who, alpha))
+    return a32
+
+
+def diffuse_velocity(vel, alpha, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, out=None, workspace=None):
+    """mantaflow's ``cgSolveDiffusion(flags, vel, alpha)`` as include/deepfluids_hip.h restates it: every component of ``vel``
+    [B,(Z,)Y,X,D] is diffused implicitly, ``(I - alpha * Laplacian) x = u`` on the cells interior by index with the ``bnd`` band as
+    Dirichlet data (copied through bit for bit), by plain conjugate gradients from ``x = u``.  ``alpha``: a number or B numbers on the
+    host (``diffusion_alpha``), finite and >= 0.  Every (entry, component) pair is its own system and stops on its own at
+    ``max|r| <= accuracy`` or after ``max_iter`` iterations (default ``default_diffusion_max_iter``); the host reads one word every
+    ``check_every`` iterations, as in ``solve_pressure``.  ``alpha = 0`` returns the input's bits.  No preconditioner, no obstacles.
+    Returns ``(vel_out, iterations)``, ``iterations`` int32 [B, D].  ``out`` may be ``vel``."""
+    with torch.no_grad():
+        if not isinstance(vel, torch.Tensor) or vel.dtype != torch.float32 or not vel.is_cuda or not vel.is_contiguous():
+            raise ValueError("diffuse_velocity: vel must be a contiguous float32 GPU tensor [B,(Z,)Y,X,D]")
+        v, nd = _smoke_vel(vel, "diffuse_velocity")
+        bnd = _liquid_bnd(bnd, "diffuse_velocity")
+        if not accuracy >= 0:
+            raise ValueError("diffuse_velocity: accuracy must be >= 0, got %r" % (accuracy,))
+        dims, dims4 = _pressure_dims(v, nd)
+        B = dims[0]
+        a32 = _diffusion_alpha_arg(alpha, B, "diffuse_velocity")
+        if max_iter is None:
+            max_iter = default_diffusion_max_iter(dims[1:])
+        check_every = DEFAULT_CHECK_EVERY if check_every is None else int(check_every)
+        if max_iter < 0 or check_every < 1:
+            raise ValueError("diffuse_velocity: max_iter must be >= 0 and check_every >= 1, got %r, %r" % (max_iter, check_every))
+        out = _smoke_out(out, v, "diffuse_velocity")
+        ws = workspace if workspace is not None else diffusion_workspace(v)
+        if ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous():
+            raise ValueError("diffuse_velocity: workspace must be a contiguous float32 GPU tensor (diffusion_workspace)")
+        nbytes = ws.numel() * 4
+        need = query("df_diffuse_workspace_bytes", *([int(x) for x in dims4] + [nd]))
+        if need < 0 or nbytes < need:
+            raise ValueError("diffuse_velocity: unsupported extents %s or a workspace of %d bytes where %d are needed (diffusion_workspace)"
+                             % (tuple(v.shape), nbytes, need))
+        return _diffuse(v, torch.from_numpy(a32).to(v.device), out, ws, nbytes, nd, dims, dims4, bnd, float(accuracy), int(max_iter), check_every)
+
+
+def _diffuse(v, al, out, ws, nbytes, nd, dims, dims4, bnd, acc, max_iter, check_every):
+    """the launches of ``diffuse_velocity``; ``al`` [B] float32 on the device"""
+    B = dims[0]
+    pairs4 = [B * nd] + dims4[1:]                            # df_pressure_status over the B*D pairs
+    words = torch.empty((1 + B * nd,), dtype=torch.int32, device=v.device)
+    count, iters = words[:1], words[1:]
+    call("df_diffuse_init%dd" % nd, _ptr(v), _ptr(al), _ptr(ws), nbytes, *(dims + [bnd, _stream()]))
+    k = _cg_loop(lambda k: call("df_diffuse_cg_direction%dd" % nd, _ptr(al), _ptr(ws), nbytes, *(dims + [bnd, k, acc, max_iter, _stream()])),
+                 lambda k: call("df_diffuse_cg_update%dd" % nd, _ptr(ws), nbytes, *(dims + [bnd, k, _stream()])),
+                 ws, nbytes, pairs4, count, max_iter, check_every)
+    call("df_pressure_status", _ptr(ws), nbytes, *(pairs4 + [k, None, _ptr(iters), _stream()]))
+    call("df_diffuse_finish%dd" % nd, _ptr(ws), nbytes, _ptr(out), *(dims + [bnd, _stream()]))
+    return out, iters.clone().reshape(B, nd)
+
+
 def flip_update(pos, pvel, vel, vel_old, flip_ratio=DEFAULT_FLIP_RATIO, out=None):
     """mantaflow's ``flipVelocityUpdate``: with ``u(.)`` the MAC sample of ``advect_particles``, ``un = u(vel, p)``,
     ``d = un - u(vel_old, p)``, ``pvel = flip_ratio * (pvel + d) + (1 - flip_ratio) * un``.  ``out`` may be ``pvel``."""
@@ -2635,7 +2723,9 @@ def sample_velocity(vel, pos):
         return flip_update(p, torch.zeros_like(p), vel, vel, flip_ratio=0.0)
 
 
-def _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws):
+def _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws, visc=None):
+    """``visc``: None, or (alpha [B] float32 on the device, the diffusion workspace): the viscous step of scene/liquid3_vis.py:256-296;
+    the iteration counts [B, D] of its diffusion are then returned as a fifth element"""
     nd = p.shape[-1]
     shape = tuple(v.shape[1:-1])
     B, N = p.shape[0], p.shape[1]
@@ -2647,10 +2737,19 @@ def _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_
     vel_old = vel                                            # extrapolate_mac leaves its input untouched
     vel, _ = extrapolate_mac(vel, known, 2, bnd=bnd)
     flags, touch = liquid_flags(cell_start, shape, B, N, bnd=bnd)
+    if visc is not None:
+        # setWallBcs as a zero-force pass (+ 0.0 leaves a value's bits but for -0), then cgSolveDiffusion: the step's accuracy, the
+        # iteration cap of cgSolveDiffusion's own default (max_iter is the pressure solve's)
+        liquid_forces(vel, flags, (0.0,) * nd, bnd=bnd, out=vel)
+        dims, dims4 = _pressure_dims(vel, nd)
+        _, diters = _diffuse(vel, visc[0], vel, visc[1], visc[1].numel() * 4, nd, dims, dims4, bnd, float(accuracy),
+                             default_diffusion_max_iter(shape), DEFAULT_CHECK_EVERY if check_every is None else int(check_every))
     liquid_forces(vel, flags, force, bnd=bnd, out=vel)
     _, _, iters = solve_pressure_liquid(vel, flags, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=vel, workspace=pws)
     vel, _ = extrapolate_mac(vel, touch, 4, bnd=bnd)
     flip_update(spos, su, vel, vel_old, flip_ratio=flip_ratio, out=su)
+    if visc is not None:
+        return spos, su, vel, iters, diters
     return spos, su, vel, iters
 
 
@@ -2663,8 +2762,16 @@ def _liquid_state(pos, pvel, vel, who):
     return p, u, v
 
 
+def _viscosity_arg(viscosity_alpha, v, who):
+    """None, or (alpha [B] float32 on the device, the diffusion workspace) for ``_liquid_step``"""
+    if viscosity_alpha is None:
+        return None
+    a32 = _diffusion_alpha_arg(viscosity_alpha, v.shape[0], who)
+    return torch.from_numpy(a32).to(v.device), diffusion_workspace(v)
+
+
 def liquid_step(pos, pvel, vel, dt, force=None, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, flip_ratio=DEFAULT_FLIP_RATIO,
-                open_bound=False):
+                open_bound=False, viscosity_alpha=None):
     """One frame of the reference's liquid scenes (scene/liquid_pos_size.py:254-295) on particles ``pos``, ``pvel`` [B,N,D] and the MAC
     velocity ``vel`` [B,(Z,)Y,X,D], in the script's order: trace the particles through ``vel`` (RK4), sort them by cell, map their
     velocities to the grid, extrapolate 2 layers from the faces that received weight, mark the liquid cells, add gravity (``force``,
@@ -2672,40 +2779,56 @@ def liquid_step(pos, pvel, vel, dt, force=None, bnd=1, accuracy=1e-4, max_iter=N
     with p = 0 in the air cells, extrapolate 4 layers from the faces of liquid cells, update the particle velocities (FLIP,
     ``flip_ratio``).  Returns ``(pos, pvel, vel, iterations)``: the particles come back SORTED by cell, so the step permutes them
     (``pos`` and ``pvel`` alike); ``vel`` is the frame the script saves.  Left out, as named in include/deepfluids_hip.h: the
-    ghost-fluid surface, adjustNumber, the averaged level set, open sides (``open_bound=True`` is refused), obstacles, MIC(0)."""
+    ghost-fluid surface, adjustNumber, the averaged level set, open sides (``open_bound=True`` is refused), obstacles, MIC(0).
+    ``viscosity_alpha`` (a number or B numbers, ``diffusion_alpha``): the viscous step of scene/liquid3_vis.py:256-296 -- after the
+    liquid cells are marked the wall faces are zeroed (setWallBcs, a zero-force ``liquid_forces`` pass) and the velocity is diffused
+    (``diffuse_velocity`` at the step's ``accuracy`` and its own default iteration cap), then gravity and the rest as above; the
+    result is then ``(pos, pvel, vel, iterations, diffusion_iterations [B, D])``.  With ``None`` nothing of this is launched."""
     if open_bound:
         raise NotImplementedError("liquid_step: open sides (resetOutflow) are not implemented for the liquid solver")
     with torch.no_grad():
         p, u, v = _liquid_state(pos, pvel, vel, "liquid_step")
         bnd = _liquid_bnd(bnd, "liquid_step")
         force = default_gravity_force(v.shape[1:-1], dt) if force is None else force
-        return _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pressure_workspace(v))
+        visc = _viscosity_arg(viscosity_alpha, v, "liquid_step")
+        return _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pressure_workspace(v), visc)
 
 
-def _liquid_frames(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats):
+def _liquid_frames(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats, viscosity_alpha=None,
+                   keep_every=1):
     p, u, v = _liquid_state(pos0, pvel0, vel0, "simulate_liquid")
     bnd = _liquid_bnd(bnd, "simulate_liquid")
     force = default_gravity_force(v.shape[1:-1], dt) if force is None else force
     pws = pressure_workspace(v)
+    visc = _viscosity_arg(viscosity_alpha, v, "simulate_liquid")
     for t in range(int(steps)):
-        p, u, v, iters = _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws)
+        p, u, v, iters = _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws, visc)[:4]
         if stats is not None:
             stats.append(iters)
-        yield p, u, v
+        if t % keep_every == 0:
+            yield p, u, v
 
 
 def simulate_liquid(pos0, pvel0, vel0, steps, dt=0.5, force=None, bnd=1, accuracy=1e-4, max_iter=None, check_every=None,
-                    flip_ratio=DEFAULT_FLIP_RATIO, stack=True, stats=None, open_bound=False):
+                    flip_ratio=DEFAULT_FLIP_RATIO, stack=True, stats=None, open_bound=False, viscosity_alpha=None, keep_every=1):
     """``steps`` chained ``liquid_step`` frames from ``(pos0, pvel0, vel0)`` (left untouched).  With ``stack`` returns
     ``(pos, pvel, vels)``, ``vels`` [steps,B,(Z,)Y,X,D] the velocity after each step; without it a generator of ``(pos, pvel, vel)`` per
-    step.  ``stats``: a list that receives the iteration counts [B] of every step's solve."""
+    step.  ``stats``: a list that receives the iteration counts [B] of every step's solve.  ``viscosity_alpha``: as in ``liquid_step``.
+    ``keep_every=k``: only the steps 0, k, 2k, ... (0-based) are yielded or stacked (``vels`` [ceil(steps/k),...]; a scene whose frame
+    is ``k`` solver steps) -- every step still runs and reports to ``stats``, and with ``stack`` the returned particles are those after
+    the LAST step."""
     if open_bound:
         raise NotImplementedError("simulate_liquid: open sides (resetOutflow) are not implemented for the liquid solver")
+    keep_every = int(keep_every)
+    if keep_every < 1:
+        raise ValueError("simulate_liquid: keep_every must be >= 1, got %r" % (keep_every,))
     with torch.no_grad():
-        gen = _liquid_frames(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats)
+        gen = _liquid_frames(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats, viscosity_alpha,
+                             keep_every)
         if not stack:
             return _no_grad_iter(gen)
-        vels = torch.empty((int(steps),) + tuple(vel0.shape), dtype=torch.float32, device=vel0.device)
+        kept = (int(steps) + keep_every - 1) // keep_every
+        vels = torch.empty((kept,) + tuple(vel0.shape), dtype=torch.float32, device=vel0.device)
         p, u = pos0, pvel0
         for t, (p, u, v) in enumerate(gen):
             vels[t].copy_(v)

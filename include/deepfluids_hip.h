@@ -851,6 +851,47 @@ int df_flip_update2d(const float* pos, const float* pvel_in, float* pvel_out, co
 int df_flip_update3d(const float* pos, const float* pvel_in, float* pvel_out, const float* vel, const float* vel_old, int64_t B, int64_t N,
                      int64_t Z, int64_t Y, int64_t X, float flip_ratio, df_stream_t stream);
 
+/* ---- implicit velocity diffusion: cgSolveDiffusion(flags, vel, alphaV) of the reference's viscous liquid scene (scene/liquid3_vis.py:277-281),
+ * once per solver step between setWallBcs and addGravity.  mantaflow cannot be run beside this library: the system is restated from
+ * memory (MakeLaplaceMatrix on an all-fluid dummy flag grid, scaled by alpha, plus the identity, identity rows in obstacle cells; u handed
+ * in as the first guess) and reduced to its symmetric positive definite interior block; parity is with the NumPy restatement of THIS
+ * definition (tests/diffuse_ref.py), NOT with mantaflow.
+ * Left out: adjustNumber; the level set (the solve does not read phi); the ghost-fluid surface; the MIC(0) preconditioner; obstacles --
+ * mantaflow's identity rows are the bnd band only.
+ *
+ * vel [B,(Z,)Y,X,D] fp32, alpha [B] fp32 >= 0 in DEVICE memory (the caller checks the values; a negative or non-finite alpha yields
+ * meaningless numbers, never an access outside the arrays).  For every entry e and component a, u = vel[e,..,a] is a scalar grid, I the
+ * cells interior by index (bnd <= index < extent - bnd on every axis; bnd >= 1, so all 2D axis neighbours of a cell of I exist):
+ *      (1 + 2D*alpha) x_c - alpha * sum_{nb in I} x_nb  =  u_c + alpha * sum_{nb not in I} u_nb          for c in I,
+ * cells outside I are Dirichlet data and are copied through bit for bit.  Plain conjugate gradients, the iteration and the stop rule of
+ * the pressure solve (an entry is active while max|r| > accuracy && r.r > 0 && iterations < max_iter), over the B*D (entry, component)
+ * pairs, each its own system that converges on its own; pair e*D + a takes the place of batch entry e of the pressure workspace:
+ *      df_diffuse_workspace_bytes(B, Z, Y, X, D)  (Z = 1 for D = 2): df_pressure_workspace_bytes(B*D, Z, Y, X), then the planar x [B*D,n]
+ *      df_diffuse_init*           x = u (every cell), r = p = alpha * (sum of all 2D neighbours of u, x-, x+, y-, y+[, z-, z+] from 0,
+ *                                 - 2D * u) on I and 0 off it, the first partials.  alpha = 0: r = 0, no iteration, the input's bits.
+ *      df_diffuse_cg_direction*   df_pressure_cg_direction* with q_c = p_c + alpha * (2D * p_c - sum_{nb in I} p_nb)
+ *      df_diffuse_cg_update*      df_pressure_cg_update* on x (the same kernel)
+ *      df_pressure_status         with B*D for B, on the same workspace pointer: iterations[e*D + a]
+ *      df_diffuse_finish*         out[e,..,a] = x of pair e*D + a.  out may be vel (init has read all of it).
+ * All arithmetic fp32, no fused multiply-add, in the order written; the partial sums are combined in an order that depends on the grid
+ * extents alone, so a pair's result depends neither on the rest of the batch nor on the other components; frozen pairs are not touched.
+ * Errors, on the host and before any launch: DF_EINVAL null pointer / non-positive extent / bnd < 1 / k < 0 / max_iter < 0 / accuracy < 0
+ * / the workspace overlapping vel, alpha or out, DF_ESHAPE an extent < 2*bnd + 2 or too large, DF_EALIGN a pointer not 4-byte aligned,
+ * DF_EWORKSPACE ws_bytes below df_diffuse_workspace_bytes (which itself returns a negative DF_E* code for bad extents or D). */
+int64_t df_diffuse_workspace_bytes(int64_t B, int64_t Z, int64_t Y, int64_t X, int dim);
+int df_diffuse_init2d(const float* vel, const float* alpha, void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int64_t X, int bnd,
+                      df_stream_t stream);
+int df_diffuse_init3d(const float* vel, const float* alpha, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                      df_stream_t stream);
+int df_diffuse_cg_direction2d(const float* alpha, void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k,
+                              float accuracy, int64_t max_iter, df_stream_t stream);
+int df_diffuse_cg_direction3d(const float* alpha, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k,
+                              float accuracy, int64_t max_iter, df_stream_t stream);
+int df_diffuse_cg_update2d(void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k, df_stream_t stream);
+int df_diffuse_cg_update3d(void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k, df_stream_t stream);
+int df_diffuse_finish2d(void* ws, int64_t ws_bytes, float* out, int64_t B, int64_t Y, int64_t X, int bnd, df_stream_t stream);
+int df_diffuse_finish3d(void* ws, int64_t ws_bytes, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, df_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
