@@ -185,6 +185,12 @@ SIGNATURES = {
     "df_open_extrapolate3d": (I32, [P, I64, I64, I64, I64, I32, I32, P]),
     "df_density_sphere_source2d": (I32, [P, P, F32, F32, P, I64, I64, I64, P]),
     "df_density_sphere_source3d": (I32, [P, P, F32, F32, P, I64, I64, I64, I64, P]),
+    "df_density_noise_inflow2d": (I32, [P, P, P, P, F32, F32, F32, I64, I64, I64, I32, P]),
+    "df_density_noise_inflow3d": (I32, [P, P, P, P, F32, F32, F32, I64, I64, I64, I64, I32, P]),
+    "df_mac_cylinder_stamp2d": (I32, [P, P, P, P, I64, I64, I64, P]),
+    "df_mac_cylinder_stamp3d": (I32, [P, P, P, P, I64, I64, I64, I64, P]),
+    "df_wall_buoyancy2d_open_dev": (I32, [P, P, P, P, P, I64, I64, I64, I32, I32, P]),
+    "df_wall_buoyancy3d_open_dev": (I32, [P, P, P, P, P, I64, I64, I64, I64, I32, I32, P]),
     "df_liquid_p2g2d": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, P]),
     "df_liquid_p2g3d": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, P]),
     "df_mac_extrapolate2d": (I32, [P, P, P, P, I64, I64, I64, I32, I32, P]),
@@ -211,6 +217,13 @@ SIGNATURES = {
 }
 
 DF_CONV_LRELU, DF_CONV_RESIDUAL, DF_CONV_MASK, DF_CONV_BIAS, DF_CONV_ADDUP, DF_CONV_VALU_ONLY = 1, 2, 4, 8, 16, 32
+
+
+class NoiseParams(ctypes.Structure):
+    """``df_noise_params`` of the header: the host-side argument of ``df_density_noise_inflow*`` (pass ``ctypes.addressof`` of it)"""
+    _fields_ = [("pos_scale", F32 * 3), ("pos_offset", F32 * 3), ("time_anim", F32), ("val_offset", F32), ("val_scale", F32),
+                ("clamp", ctypes.c_int32), ("clamp_neg", F32), ("clamp_pos", F32), ("seed", ctypes.c_uint32), ("inv_extent", F32)]
+
 
 _lib = None
 

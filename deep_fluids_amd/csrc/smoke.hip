@@ -7,7 +7,8 @@
 //
 //   mac_sl / mac_mc   the velocity carried through itself, one thread = one cell and its D components, the helpers of advect.hip read
 //                     with stride D.  As there: the gathers are data dependent and served by L1/L2, no LDS.
-//   wall_buoyancy     element-wise: wall faces 0, kept faces += (0.5*force[a]) * (rho(c) + rho(c - e_a)).
+//   wall_buoyancy     element-wise: wall faces 0, kept faces += (0.5*force[a]) * (rho(c) + rho(c - e_a)).  The `_dev` entry points read
+//                     force from device memory, one per batch entry, and run the same cell function: equal forces, equal bits.
 //   pressure          plain conjugate gradients on the 5- / 7-point Neumann Laplacian of the interior cells, two launches per iteration:
 //     direction(k)    every workgroup first combines its entry's r.r and max|r| partials (fixed order) and takes the entry's decision
 //                     (converged / max_iter / go on, beta = rr / rr_old); then p = r + beta*p_old is recomputed at the cell and at its
@@ -218,11 +219,9 @@ struct Force { float f[3]; };
 // OPEN: a live face that is not between two fluid cells is kept without the buoyancy term, and every other component of an open cell is
 // copied through (it holds filled values) -- so an open cell keeps all of its components
 template <int D, bool MASKED, bool OPEN>
-__global__ __launch_bounds__(kThreads) void wall_buoyancy_kernel(const float* vel, const float* __restrict__ rho, float* out,
-                                                                 const uint8_t* __restrict__ flags, Force force, AdvDims d, int os) {
-  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
-  if (idx >= d.ncell) return;
-  const Cell<D> c = decode<D>(idx, d);
+__device__ __forceinline__ void wall_buoyancy_cell(const float* vel, const float* __restrict__ rho, float* out, const uint8_t* __restrict__ flags,
+                                                   const float* force, const Cell<D>& c, const AdvDims& d, int os) {
+  const int64_t idx = c.idx;
   const unsigned fl = MASKED ? flags[idx] : 0u;
   const int64_t st[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
   const VelRec<D> v = *reinterpret_cast<const VelRec<D>*>(vel + idx * D);
@@ -232,10 +231,34 @@ __global__ __launch_bounds__(kThreads) void wall_buoyancy_kernel(const float* ve
 #pragma unroll
   for (int a = 0; a < D; ++a) {
     r.v[a] = opn ? v.v[a] : 0.0f;
-    if (kept_face<MASKED>(c.interior, c.p[a], d.bnd, fl, a)) r.v[a] = v.v[a] + (0.5f * force.f[a]) * (rho[idx] + rho[idx - st[a]]);
+    if (kept_face<MASKED>(c.interior, c.p[a], d.bnd, fl, a)) r.v[a] = v.v[a] + (0.5f * force[a]) * (rho[idx] + rho[idx - st[a]]);
     else if (OPEN && open_live_face<D, MASKED>(c.p, ext, c.interior, fl, d.bnd, a, os)) r.v[a] = v.v[a];
   }
   *reinterpret_cast<VelRec<D>*>(out + idx * D) = r;
+}
+
+template <int D, bool MASKED, bool OPEN>
+__global__ __launch_bounds__(kThreads) void wall_buoyancy_kernel(const float* vel, const float* __restrict__ rho, float* out,
+                                                                 const uint8_t* __restrict__ flags, Force force, AdvDims d, int os) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (idx >= d.ncell) return;
+  wall_buoyancy_cell<D, MASKED, OPEN>(vel, rho, out, flags, force.f, decode<D>(idx, d), d, os);
+}
+
+// the same cell with the force of the cell's batch entry read from device memory, forces [B,D]: the same expression, so equal forces
+// give the bits of the kernel above
+template <int D, bool MASKED, bool OPEN>
+__global__ __launch_bounds__(kThreads) void wall_buoyancy_dev_kernel(const float* vel, const float* __restrict__ rho, float* out,
+                                                                     const uint8_t* __restrict__ flags, const float* __restrict__ forces,
+                                                                     AdvDims d, int os) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (idx >= d.ncell) return;
+  const Cell<D> c = decode<D>(idx, d);
+  const float* f = forces + c.base / (static_cast<int64_t>(d.X) * d.Y * d.Z) * D;
+  float force[D];
+#pragma unroll
+  for (int a = 0; a < D; ++a) force[a] = f[a];
+  wall_buoyancy_cell<D, MASKED, OPEN>(vel, rho, out, flags, force, c, d, os);
 }
 
 // ---- pressure projection ---------------------------------------------------------------------------------------------------------------------
@@ -674,6 +697,23 @@ int wall_buoyancy(const char* fn, const float* vel, const float* rho, float* out
   return df::launched(fn);
 }
 
+template <int D, bool MASKED, bool OPEN = false>
+int wall_buoyancy_dev(const char* fn, const float* vel, const float* rho, float* out, const uint8_t* flags, const float* forces, int64_t B,
+                      int64_t Z, int64_t Y, int64_t X, int bnd, df_stream_t stream, int os = 0) {
+  DF_REQUIRE(vel && rho && out && forces, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : !rho ? "density" : !out ? "output" : "forces");
+  AdvDims d;
+  unsigned nblk;
+  if (int e = plan(fn, D, B, Z, Y, X, bnd, 0.0f, &d, &nblk)) return e;
+  DF_REQUIRE(static_cast<const void*>(out) != static_cast<const void*>(rho), DF_EINVAL,
+             "%s: the output must not be the density (it is read at a neighbour)", fn);
+  DF_REQUIRE(apart(forces, 4 * B * D, out, 4 * d.ncell * D), DF_EINVAL, "%s: the forces overlap the output", fn);
+  if (int e = check_flags<MASKED>(fn, flags, d.ncell, out, 4 * d.ncell * D, "output")) return e;
+  DF_REQUIRE(aligned4(vel) && aligned4(rho) && aligned4(out) && aligned4(forces), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  hipLaunchKernelGGL((wall_buoyancy_dev_kernel<D, MASKED, OPEN>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, rho, out, flags,
+                     forces, d, os);
+  return df::launched(fn);
+}
+
 template <int D, bool MASKED>
 int pressure_init(const char* fn, const float* vel, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z,
                   int64_t Y, int64_t X, int bnd, df_stream_t stream) {
@@ -1031,6 +1071,18 @@ int df_wall_buoyancy3d_open(const float* vel, const float* density, float* out, 
   const char* fn = "df_wall_buoyancy3d_open";
   if (int e = check_open(fn, 3, open_sides)) return e;
   return DF_OPEN_CALL(wall_buoyancy, 3, fn, vel, density, out, flags, B, Z, Y, X, Force{{fx, fy, fz}}, bnd, stream);
+}
+int df_wall_buoyancy2d_open_dev(const float* vel, const float* density, float* out, const uint8_t* flags, const float* forces, int64_t B,
+                                int64_t Y, int64_t X, int bnd, int open_sides, df_stream_t stream) {
+  const char* fn = "df_wall_buoyancy2d_open_dev";
+  if (int e = check_open(fn, 2, open_sides)) return e;
+  return DF_OPEN_CALL(wall_buoyancy_dev, 2, fn, vel, density, out, flags, forces, B, 1, Y, X, bnd, stream);
+}
+int df_wall_buoyancy3d_open_dev(const float* vel, const float* density, float* out, const uint8_t* flags, const float* forces, int64_t B,
+                                int64_t Z, int64_t Y, int64_t X, int bnd, int open_sides, df_stream_t stream) {
+  const char* fn = "df_wall_buoyancy3d_open_dev";
+  if (int e = check_open(fn, 3, open_sides)) return e;
+  return DF_OPEN_CALL(wall_buoyancy_dev, 3, fn, vel, density, out, flags, forces, B, Z, Y, X, bnd, stream);
 }
 int df_pressure_cg_direction2d_open(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd,
                                     int open_sides, int64_t k, float accuracy, int64_t max_iter, df_stream_t stream) {

@@ -717,3 +717,82 @@ def generate_smoke3_mov_dataset(root, num_param=2, path_format="%d_%d.npz", p0="
     return _simulate_moving_source(root, args, positions, lambda i, t: path_format % (i, t), src_y_pos, src_radius, num_frames,
                                    (resolution_x, resolution_y, resolution_z), buoyancy, bWidth, open_bound, time_step, adv_order, clamp_mode,
                                    scenes_per_batch, accuracy, device)
+
+
+# ---- the noise-inflow scene (scene/smoke3_vel_buo.py): a cylinder source, a noise-modulated density inflow, an inflow velocity stamped
+#      every frame, one inflow value and one buoyancy per scene ----
+def smoke3_vel_buo_scenes(min_inflow, max_inflow, num_inflow, min_buoyancy, max_buoyancy, num_buoyancy):
+    """``(p_list [S,2], pi_list [S,2])`` of scene/smoke3_vel_buo.py:144-153: the (inflow, buoyancy) values and their grid indices in the
+    script's scene order, ``np.meshgrid(p1_space, p2_space).T.reshape(-1, 2)`` -- the buoyancy index runs fastest."""
+    p_list = np.array(np.meshgrid(np.linspace(min_inflow, max_inflow, num_inflow), np.linspace(min_buoyancy, max_buoyancy, num_buoyancy))).T.reshape(-1, 2)
+    pi_list = np.array(np.meshgrid(range(num_inflow), range(num_buoyancy))).T.reshape(-1, 2)
+    return p_list, pi_list
+
+
+def smoke3_vel_buo_inflow(resolution, src_x_pos=0.1, src_y_pos=0.25, src_z_pos=0.5, src_radius=0.14, src_height=0.04, time_step=0.5, nseed=123):
+    """The ``ops.NoiseInflow`` of scene/smoke3_vel_buo.py for a grid ``resolution`` = (X, Y, Z): a cylinder at ``gs * (src_x_pos,
+    src_y_pos, src_z_pos)`` of radius ``Y * src_radius`` and half-axis ``gs * (0, src_height, 0)``, the script's noise parameters with
+    ``nseed`` seeding this project's own lattice noise (NOT mantaflow's wavelet noise), ``scale=1``, ``sigma=0.5``."""
+    from . import ops
+    X, Y, Z = (int(n) for n in resolution)
+    shape = ops.CylinderShape((X * src_x_pos, Y * src_y_pos, Z * src_z_pos), (0.0, Y * src_height, 0.0), Y * src_radius)
+    return ops.NoiseInflow(shape, ops.NoiseField(seed=nseed), scale=1.0, sigma=0.5, time_step=time_step)
+
+
+def generate_smoke3_vel_buo_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="inflow", p1="buoyancy", p2="frames", min_inflow=1,
+                                    max_inflow=5, num_inflow=5, min_buoyancy=-2e-4, max_buoyancy=-10e-4, num_buoyancy=3, src_x_pos=0.1,
+                                    src_y_pos=0.25, src_z_pos=0.5, src_radius=0.14, src_height=0.04, min_frames=0, max_frames=None,
+                                    num_frames=250, num_simulations=None, resolution_x=112, resolution_y=64, resolution_z=32, bWidth=1,
+                                    open_bound="XyY", time_step=0.5, adv_order=2, clamp_mode=2, scenes_per_batch=None, accuracy=1e-4,
+                                    device="cuda", nseed=123):
+    """Simulate the reference's inflow / buoyancy set (scene/smoke3_vel_buo.py:127-308, ``smoke3_vel5_buo3_f250``) on the GPU and write it
+    as that script does: ``args.txt`` with every argument of the script in its order, ``v/%d_%d_%d.npz`` (x [Z,Y,X,3] float32 velocity
+    after frame t, y = [inflow, buoyancy, t]) and ``v_range.txt``.  The keyword arguments are the script's, with its defaults
+    (``max_frames`` and ``num_simulations`` follow ``num_frames`` and the grid of scenes unless given).  Per frame: the noise-modulated
+    density inflow through the cylinder of ``smoke3_vel_buo_inflow``, the inflow velocity (p0, 0, 0) stamped into the cylinder's faces,
+    both advections, resetOutflow, walls, buoyancy (0, p1, 0), projection, with the sides of ``open_bound`` open.  Scenes follow the
+    script's meshgrid order and are batch entries of ONE ``ops.simulate_smoke`` with a per-entry inflow value and force
+    (``scenes_per_batch`` splits them; an entry's result does not depend on the rest of its batch).  The step is this library's
+    restatement (include/deepfluids_hip.h; tests/smoke_inflow_ref.py), NOT mantaflow's, and the noise is this project's OWN seeded
+    lattice noise (``nseed``; it is not written to args.txt, which holds the script's keys only), not mantaflow's wavelet noise.
+    Returns the number of files written."""
+    from . import ops
+    if num_param != 3 or (p0, p1, p2) != ("inflow", "buoyancy", "frames"):
+        raise ValueError("generate_smoke3_vel_buo_dataset: the scene has the parameters (inflow, buoyancy, frames)")
+    sides = ops.open_sides(open_bound, 3)
+    max_frames = num_frames - 1 if max_frames is None else max_frames
+    num_simulations = num_inflow * num_buoyancy * num_frames if num_simulations is None else num_simulations
+    _write_args(root, [("log_dir", root), ("num_param", num_param), ("path_format", path_format), ("p0", p0), ("p1", p1), ("p2", p2),
+                       ("min_inflow", min_inflow), ("max_inflow", max_inflow), ("num_inflow", num_inflow), ("min_buoyancy", min_buoyancy),
+                       ("max_buoyancy", max_buoyancy), ("num_buoyancy", num_buoyancy), ("src_x_pos", src_x_pos), ("src_y_pos", src_y_pos),
+                       ("src_z_pos", src_z_pos), ("src_radius", src_radius), ("src_height", src_height), ("min_frames", min_frames),
+                       ("max_frames", max_frames), ("num_frames", num_frames), ("num_simulations", num_simulations),
+                       ("resolution_x", resolution_x), ("resolution_y", resolution_y), ("resolution_z", resolution_z), ("bWidth", bWidth),
+                       ("open_bound", open_bound), ("time_step", time_step), ("adv_order", adv_order), ("clamp_mode", clamp_mode)])
+    X, Y, Z = int(resolution_x), int(resolution_y), int(resolution_z)
+    shape = (Z, Y, X)
+    p_list, pi_list = smoke3_vel_buo_scenes(min_inflow, max_inflow, num_inflow, min_buoyancy, max_buoyancy, num_buoyancy)
+    inflow = smoke3_vel_buo_inflow((X, Y, Z), src_x_pos, src_y_pos, src_z_pos, src_radius, src_height, time_step, nseed)
+    S = len(p_list)
+    chunk = S if not scenes_per_batch else int(scenes_per_batch)
+    v_range = [np.finfo(np.float64).max, np.finfo(np.float64).min]
+    written = 0
+    for c0 in range(0, S, chunk):
+        part = list(range(c0, min(c0 + chunk, S)))
+        values = torch.tensor([[p_list[i][0], 0.0, 0.0] for i in part], dtype=torch.float32, device=device)      # inflow = vec3(p0, 0, 0)
+        force = ops.buoyancy_forces(shape, time_step, [p_list[i][1] for i in part]).to(device)                      # buoyancy = vec3(0, p1, 0)
+        d0 = torch.zeros((len(part),) + shape, dtype=torch.float32, device=device)
+        v0 = torch.zeros((len(part),) + shape + (3,), dtype=torch.float32, device=device)
+        frames = ops.simulate_smoke(d0, v0, num_frames, dt=time_step, source=inflow, force=force, order=adv_order, clamp_mode=clamp_mode,
+                                    bnd=bWidth, accuracy=accuracy, stack=False, open_bound=sides, inflow_velocity=(inflow.shape, values))
+        for t, (_, v) in enumerate(frames):
+            vh = v.cpu().numpy()
+            v_range = [min(v_range[0], float(vh.min())), max(v_range[1], float(vh.max()))]
+            for e, i in enumerate(part):
+                np.savez_compressed(os.path.join(root, "v", path_format % (tuple(pi_list[i].tolist()) + (t,))), x=vh[e],
+                                    y=[p_list[i][0], p_list[i][1], t])
+                written += 1
+    with open(os.path.join(root, "v_range.txt"), "w") as f:
+        f.write("%.3f\n" % v_range[0])
+        f.write("%.3f" % v_range[1])
+    return written

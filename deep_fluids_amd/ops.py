@@ -12,6 +12,7 @@ name-keyed registry: ``variable_scope(name, reuse)`` + ``get_variables(scope)``;
 follow slim: ``<scope>/<layer>/weights`` ``[k,(k,)k,Cin,Cout]`` / ``[in,out]`` and ``.../biases``.
 """
 import contextlib
+import ctypes
 import contextlib as _contextlib
 import math
 import os as _os
@@ -1724,9 +1725,132 @@ class SphereSource(object):
         return c.to(like.device).contiguous()
 
 
-def _stamp(d, source, value, out):
-    """``source`` (a mask or a SphereSource) stamped into ``d`` -> ``out`` (which may be ``d``)"""
-    if isinstance(source, SphereSource):
+class CylinderShape(object):
+    """mantaflow's ``Cylinder(center, radius, z)``, one per batch entry, packed for the kernels: ``centers`` and ``z`` (the HALF-axis
+    vector) are [B,D] or [D] (then shared by the batch) in cell units, xyz order; ``radius`` a float or [B].  Holds ``packed``
+    [B | 1, 2D+1] = (centre, z, radius) float32, moved to the device of the grid it is used on.  A zero-length ``z`` is refused here
+    when the numbers are on the host; on the device such an entry, like one that holds a NaN, stamps nothing."""
+
+    def __init__(self, centers, z, radius):
+        def as_t(x):
+            return x.detach().to(dtype=torch.float32) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float32))
+        c, zz, r = as_t(centers), as_t(z), as_t(radius)
+        D = c.shape[-1] if c.dim() else 0
+        if c.dim() not in (1, 2) or D not in (2, 3) or zz.dim() not in (1, 2) or zz.shape[-1] != D or r.dim() > 1:
+            raise ValueError("CylinderShape: centers and z must be [B,D] or [D] with D = 2 | 3 and radius a float or [B], got %s, %s, %s" %
+                             (tuple(c.shape), tuple(zz.shape), tuple(r.shape)))
+        Bs = set([c.shape[0]] if c.dim() == 2 else []) | set([zz.shape[0]] if zz.dim() == 2 else []) | set([r.shape[0]] if r.dim() == 1 else [])
+        if len(Bs - {1}) > 1:
+            raise ValueError("CylinderShape: centers, z and radius disagree about the batch: %s" % sorted(Bs))
+        B = max(Bs) if Bs else 1
+        dev = next((t.device for t in (c, zz, r) if t.is_cuda), c.device)
+        c, zz, r = c.to(dev).reshape(-1, D).expand(B, D), zz.to(dev).reshape(-1, D).expand(B, D), r.to(dev).reshape(-1, 1).expand(B, 1)
+        if not zz.is_cuda and bool((zz == 0).all(dim=-1).any()):
+            raise ValueError("CylinderShape: a half-axis z of length zero")
+        self.packed = torch.cat([c, zz, r], dim=-1).contiguous()
+        self._on = None
+
+    @property
+    def dim(self):
+        return (self.packed.shape[-1] - 1) // 2
+
+    def entry(self, b):
+        """the cylinder of batch entry ``b`` alone ([1, 2D+1])"""
+        out = CylinderShape.__new__(CylinderShape)
+        out.packed = self.packed if self.packed.shape[0] == 1 else self.packed[b:b + 1].contiguous()
+        out._on = None
+        return out
+
+    def on(self, like):
+        """``packed`` [B, 2D+1] on ``like``'s device, contiguous, for a grid ``like`` [B,(Z,)Y,X,...] of D axes"""
+        B, dev = like.shape[0], like.device
+        if self._on is not None and self._on.shape[0] == B and self._on.device == dev:
+            return self._on
+        if self.packed.shape[0] not in (1, B):
+            raise ValueError("CylinderShape: %d cylinders do not fit a batch of %d" % (self.packed.shape[0], B))
+        self._on = self.packed.to(dev).expand(B, self.packed.shape[-1]).contiguous()
+        return self._on
+
+
+class NoiseField(object):
+    """The parameters of mantaflow's ``NoiseField`` as scene/smoke3_vel_buo.py:185-191 sets them (the defaults here), for THIS
+    project's seeded lattice value noise (include/deepfluids_hip.h) -- NOT mantaflow's wavelet noise, which is read from a tile file and
+    cannot be restated.  ``pos_scale`` / ``pos_offset``: a number or D numbers (xyz).  A plain holder."""
+
+    def __init__(self, pos_scale=45, val_offset=0.75, val_scale=1, time_anim=0.2, clamp=True, clamp_neg=0, clamp_pos=1, pos_offset=0,
+                 seed=0x9E3779B9):
+        self.pos_scale, self.pos_offset = pos_scale, pos_offset
+        self.val_offset, self.val_scale, self.time_anim = float(val_offset), float(val_scale), float(time_anim)
+        self.clamp, self.clamp_neg, self.clamp_pos = bool(clamp), float(clamp_neg), float(clamp_pos)
+        self.seed = int(seed) & 0xFFFFFFFF
+
+    def vec(self, name, dim):
+        v = np.asarray(getattr(self, name), dtype=np.float32).reshape(-1)
+        if v.size not in (1, dim):
+            raise ValueError("NoiseField: %s must be a number or %d numbers, got %r" % (name, dim, getattr(self, name)))
+        return [float(x) for x in np.broadcast_to(v, (dim,))]
+
+    def params(self, dim, extent_x):
+        """the ``df_noise_params`` of a grid of ``dim`` axes whose x extent is ``extent_x``"""
+        from ._lib import NoiseParams
+        q = NoiseParams()
+        for a, (sc, of) in enumerate(zip(self.vec("pos_scale", dim), self.vec("pos_offset", dim))):
+            q.pos_scale[a], q.pos_offset[a] = sc, of
+        q.time_anim, q.val_offset, q.val_scale = self.time_anim, self.val_offset, self.val_scale
+        q.clamp, q.clamp_neg, q.clamp_pos = int(self.clamp), self.clamp_neg, self.clamp_pos
+        q.seed = self.seed
+        q.inv_extent = float(np.float32(1.0) / np.float32(extent_x))
+        return q
+
+
+class NoiseInflow(object):
+    """``densityInflow(flags, density, noise, shape, scale, sigma)`` of scene/smoke3_vel_buo.py:222 as a source: ``shape`` a
+    ``CylinderShape``, ``noise`` a ``NoiseField``.  ``source=`` of ``advect``, ``advect_sequence``, ``smoke_step`` and ``simulate_smoke``
+    accepts it beside a mask and a ``SphereSource``; ``source_value`` does not apply to it (``scale`` does).  Frame t of the sequence forms
+    evaluates the noise at ``time = t * time_step`` (the ``dt`` of the call when ``time_step`` is None), as the script's ``s.step()``
+    advances the solver time; the single-step forms take ``time=``.  The noise is this project's own, NOT mantaflow's."""
+
+    def __init__(self, shape, noise, scale=1.0, sigma=0.5, time_step=None):
+        if not isinstance(shape, CylinderShape) or not isinstance(noise, NoiseField):
+            raise ValueError("NoiseInflow expects a CylinderShape and a NoiseField, got %r, %r" % (type(shape).__name__, type(noise).__name__))
+        if not float(sigma) > 0:
+            raise ValueError("NoiseInflow: sigma must be > 0, got %r" % (sigma,))
+        self.shape, self.noise, self.scale, self.sigma = shape, noise, float(scale), float(sigma)
+        self.time_step = None if time_step is None else float(time_step)
+
+    def entry(self, b):
+        return NoiseInflow(self.shape.entry(b), self.noise, self.scale, self.sigma, self.time_step)
+
+    def time(self, t, dt):
+        return t * (float(dt) if self.time_step is None else self.time_step)
+
+
+def density_inflow(density, inflow, time=0.0, bnd=1, out=None):
+    """``inflow`` (a ``NoiseInflow``) applied to ``density`` [B,(Z,)Y,X] at solver time ``time``: inside the cylinder, and up to ``sigma``
+    outside it, interior cells become ``max(density, noise * scale * factor)``, factor falling from 1 at ``-sigma`` to 0 at ``sigma``
+    (include/deepfluids_hip.h has the definition).  Returns ``out`` (new unless given; it may be ``density``)."""
+    with torch.no_grad():
+        d = _prep(density.detach(), "density")
+        if d.dim() not in (3, 4) or not isinstance(inflow, NoiseInflow) or inflow.shape.dim != d.dim() - 1:
+            raise ValueError("density_inflow expects a density [B,(Z,)Y,X] and a NoiseInflow of as many axes, got %s" % (tuple(d.shape),))
+        if int(bnd) != bnd or bnd < 0:
+            raise ValueError("density_inflow: bnd must be an integer >= 0, got %r" % (bnd,))
+        if out is None:
+            out = torch.empty_like(d)
+        elif tuple(out.shape) != tuple(d.shape) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("density_inflow: out must be a contiguous float32 GPU tensor of the density's shape")
+        nd = d.dim() - 1
+        q = inflow.noise.params(nd, d.shape[-1])
+        call("df_density_noise_inflow%dd" % nd, _ptr(d), _ptr(out), _ptr(inflow.shape.on(d)), ctypes.addressof(q), float(time), inflow.scale,
+             inflow.sigma, *(list(d.shape) + [int(bnd), _stream()]))
+        return out
+
+
+def _stamp(d, source, value, out, time=0.0, bnd=1):
+    """``source`` (a mask, a SphereSource or a NoiseInflow) stamped into ``d`` -> ``out`` (which may be ``d``)"""
+    if isinstance(source, NoiseInflow):
+        density_inflow(d, source, time, bnd, out)
+    elif isinstance(source, SphereSource):
         call("df_density_sphere_source%dd" % (d.dim() - 1), _ptr(d), _ptr(source.on(d)), source.radius, float(value), _ptr(out),
              *(list(d.shape) + [_stream()]))
     else:
@@ -1734,9 +1858,12 @@ def _stamp(d, source, value, out):
 
 
 def _source_arg(source, like):
-    """what the sequence forms hold: a mask on the device, packed once, or the SphereSource with its centres on the device"""
+    """what the sequence forms hold: a mask on the device, packed once, the SphereSource with its centres on the device, or the
+    NoiseInflow (its cylinders move to the device at the first stamp, once)"""
     if source is None:
         return None
+    if isinstance(source, NoiseInflow):
+        return source
     if isinstance(source, SphereSource):
         return SphereSource(source.centers.to(like.device), source.radius)
     return _source_mask(source, like)
@@ -1744,6 +1871,10 @@ def _source_arg(source, like):
 
 def _source_frame(source, t):
     return source.frame(t) if isinstance(source, SphereSource) else source
+
+
+def _source_time(source, t, dt):
+    return source.time(t, dt) if isinstance(source, NoiseInflow) else 0.0
 
 
 def open_sides(spec, dim):
@@ -1881,13 +2012,13 @@ def _advect_args(order, clamp_mode, bnd):
 
 
 def advect(density, vel, dt, order=2, clamp_mode=2, bnd=1, vel_scale=1.0, source=None, source_value=1.0, out=None, workspace=None,
-           obstacle=None):
+           obstacle=None, time=0.0):
     """One advection step of ``density`` [B,(Z,)Y,X] through ``vel`` [B,(Z,)Y,X,C] (MAC face values, C = 2 | 3), modelled on mantaflow's
     ``advectSemiLagrange(order, boundaryWidth=bnd, clampMode=clamp_mode)`` as the reference's scene scripts call it
     (scene/smoke_pos_size.py:99-101) -- NOT bit-identical to mantaflow, which cannot be run here; include/deepfluids_hip.h holds the
     definition that is tested.  ``vel_scale`` multiplies the velocities inside the kernel (``x_range`` for a generator's normalised
     output); ``source`` is an optional mask [B,(Z,)Y,X] (or one broadcastable to it) of cells set to ``source_value`` before the step,
-    or a ``SphereSource`` (one sphere per batch entry, centres on the device).
+    or a ``SphereSource`` (one sphere per batch entry, centres on the device), or a ``NoiseInflow`` (evaluated at solver time ``time``).
     Returns a new density (``out`` if given; it must not be ``density``).  ``workspace``: see ``advect_workspace``.  ``obstacle``: a
     mask of solid cells or the flags of ``obstacle_flags``; the MacCormack correction and its clamp then run over fluid cells only (the
     first-order value and the source stamp ignore obstacles, as mantaflow's do)."""
@@ -1908,7 +2039,7 @@ def advect(density, vel, dt, order=2, clamp_mode=2, bnd=1, vel_scale=1.0, source
         off = 0
         if source is not None:
             stamped = ws[:n].view(d.shape)
-            _stamp(d, source, source_value, stamped)
+            _stamp(d, source, source_value, stamped, time, bnd)
             d, off = stamped, n
         fwd = ws[off:off + n] if order == 2 else None
         _advect_step(d, v, nd, out, fwd, float(dt), order, clamp_mode, int(bnd), float(vel_scale), flags)
@@ -1936,7 +2067,8 @@ def advect_sequence(density0, vels, dt, order=2, clamp_mode=2, bnd=1, vel_scale=
     """``T`` chained ``advect`` steps over ``vels`` [T,B,(Z,)Y,X,C] (a tensor or a sequence of T tensors), the source stamped before
     every step, ping-ponging two density buffers (``density0`` is left untouched).  Returns the final density, and with ``images`` also
     the uint8 frames [T,B,Y,X] of ``density_image`` after each step, produced on the device and copied to the host once (a NumPy
-    array).  ``obstacle``: as for ``advect``; its flags are built once for the sequence."""
+    array).  ``obstacle``: as for ``advect``; its flags are built once for the sequence.  A ``NoiseInflow`` source is evaluated at
+    ``t * dt`` (its own ``time_step`` if it has one) before step t."""
     with torch.no_grad():
         _advect_args(order, clamp_mode, bnd)
         T = len(vels)
@@ -1952,7 +2084,7 @@ def advect_sequence(density0, vels, dt, order=2, clamp_mode=2, bnd=1, vel_scale=
         for t in range(T):
             _, v, _ = _advect_dims(cur, vels[t])
             if mask is not None:
-                _stamp(cur, _source_frame(mask, t), source_value, cur)
+                _stamp(cur, _source_frame(mask, t), source_value, cur, _source_time(mask, t, dt), bnd)
             _advect_step(cur, v, nd, nxt, fwd, float(dt), order, clamp_mode, int(bnd), float(vel_scale), flags)
             cur, nxt = nxt, cur
             if images:
@@ -1978,6 +2110,49 @@ def sphere_mask(shape, center, radius, device=None):
     return m if device is None else m.to(device)
 
 
+def cylinder_mask(shape, center, z, radius, device=None):
+    """The host-side twin of ``sphere_mask`` for mantaflow's ``Cylinder``: uint8 [(Z,)Y,X], 1 where the cell centre (i+.5, j+.5[, k+.5])
+    lies inside the cylinder around ``center`` with HALF-axis vector ``z`` and ``radius`` (cell units, xyz order): with a = z/|z| and
+    d = centre - center, ``|d.a| <= |z|`` and ``|d|^2 - (d.a)^2 < radius^2`` (the test of ``stamp_velocity``, at cell centres)."""
+    shape = tuple(int(n) for n in shape)
+    if len(shape) not in (2, 3) or len(center) != len(shape) or len(z) != len(shape):
+        raise ValueError("cylinder_mask expects a 2-D or 3-D shape, a centre and an axis of as many coordinates, got %s, %s, %s" %
+                         (shape, tuple(center), tuple(z)))
+    zl = math.sqrt(sum(float(v) ** 2 for v in z))
+    if not zl > 0:
+        raise ValueError("cylinder_mask: a half-axis z of length zero")
+    h = np.zeros(shape, np.float64)
+    d2 = np.zeros(shape, np.float64)
+    for a in range(len(shape)):
+        d = _centres(shape, a) - float(center[a])
+        h = h + d * (float(z[a]) / zl)
+        d2 = d2 + d * d
+    m = torch.from_numpy(((np.abs(h) <= zl) & (np.maximum(d2 - h * h, 0.0) < float(radius) * float(radius))).astype(np.uint8))
+    return m if device is None else m.to(device)
+
+
+def stamp_velocity(vel, shape, values, out=None):
+    """mantaflow's ``Cylinder.applyToGrid(grid=vel, value=...)`` on the MAC velocity ``vel`` [B,(Z,)Y,X,D]: component a of a cell becomes
+    ``values[b][a]`` where the position of that FACE lies inside entry b's cylinder (``shape``, a ``CylinderShape``); faces are tested
+    one by one, obstacles and the band are ignored.  ``values``: [B,D] or [D].  Returns ``out`` (new unless given; it may be ``vel``)."""
+    with torch.no_grad():
+        v, nd = _smoke_vel(vel, "stamp_velocity")
+        if not isinstance(shape, CylinderShape) or shape.dim != nd:
+            raise ValueError("stamp_velocity expects a CylinderShape of %d axes" % nd)
+        vals = _entry_rows(values, v, nd, "stamp_velocity: values")
+        out = _smoke_out(out, v, "stamp_velocity")
+        call("df_mac_cylinder_stamp%dd" % nd, _ptr(v), _ptr(shape.on(v)), _ptr(vals), _ptr(out), *(list(v.shape[:-1]) + [_stream()]))
+        return out
+
+
+def _entry_rows(x, v, nd, what):
+    """[B,D] float32 on ``v``'s device from [B,D] or [D] (a tensor, or anything NumPy converts)"""
+    t = x.detach() if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float32))
+    if t.dim() not in (1, 2) or t.shape[-1] != nd or (t.dim() == 2 and t.shape[0] not in (1, v.shape[0])):
+        raise ValueError("%s must be [%d,%d] or [%d], got %s" % (what, v.shape[0], nd, nd, tuple(t.shape)))
+    return t.to(device=v.device, dtype=torch.float32).reshape(-1, nd).expand(v.shape[0], nd).contiguous()
+
+
 # ---- the smoke solver step (the main() loop of the reference's scene/smoke_pos_size.py:186-195, a closed box): MAC self-advection, walls
 #      and buoyancy, a conjugate-gradient pressure projection.  Inference only, no autograd.  The step is defined in
 #      include/deepfluids_hip.h; parity is with the fp64 restatement of tests/smoke_ref.py, NOT with mantaflow, which cannot be run here.
@@ -1985,8 +2160,10 @@ def sphere_mask(shape, center, radius, device=None):
 #      Open sides (scene/smoke3_rot.py, smoke3_mov.py, smoke3_vel_buo.py, the open_bound option of smoke_pos_size.py) enter through
 #      ``open_bound=`` (``open_sides`` parses it) and combine with obstacles; a moving source is a ``SphereSource``.  Parity is with
 #      tests/smoke_open_ref.py, NOT with mantaflow.
-#      Left out: noise-modulated inflow (densityInflow) and the inflow velocity stamp of scene/smoke3_vel_buo.py, mantaflow's convective
-#      outflow extrapolation (a zero-gradient fill stands in for it), the MIC(0) preconditioner ----
+#      The inflow of scene/smoke3_vel_buo.py enters through a ``NoiseInflow`` source (a seeded lattice noise of this project's own, NOT
+#      mantaflow's wavelet noise), ``inflow_velocity=`` (the cylinder stamp) and a ``force`` tensor [B,D] (one buoyancy per batch entry);
+#      parity is with tests/smoke_inflow_ref.py, NOT with mantaflow.
+#      Left out: mantaflow's convective outflow extrapolation (a zero-gradient fill stands in for it), the MIC(0) preconditioner ----
 DEFAULT_CHECK_EVERY = 16      # iterations between two looks at the active count; the sweep over 1, 4, 16, 64 is in profiles/smoke.md
 
 
@@ -2048,7 +2225,8 @@ def advect_velocity(vel, dt, order=2, clamp_mode=2, bnd=1, out=None, workspace=N
 
 def wall_buoyancy(vel, density, force, bnd=1, out=None, obstacle=None, open_bound=None):
     """``setWallBcs`` of a closed box and ``addBuoyancy`` in one element-wise pass: component a of cell c is 0 unless c and c - e_a are
-    both interior; kept components get ``+ (0.5 * force[a]) * (density[c] + density[c-e_a])``.  ``force``: D numbers (x, y[, z]).
+    both interior; kept components get ``+ (0.5 * force[a]) * (density[c] + density[c-e_a])``.  ``force``: D numbers (x, y[, z]), or a
+    tensor [B,D]: one force per batch entry, read on the device (equal rows give the bits of the D numbers).
     ``out`` may be ``vel`` (in place).  ``obstacle``: a mask or the flags of ``obstacle_flags``; "interior" then reads "fluid", so the
     faces of solid cells are 0 as well.  ``open_bound``: the open sides (see ``open_sides``); a face between a fluid and an open cell is
     then kept, without the buoyancy term, and open cells keep all their components."""
@@ -2058,11 +2236,20 @@ def wall_buoyancy(vel, density, force, bnd=1, out=None, obstacle=None, open_boun
         d = _prep(density.detach(), "density")
         if tuple(d.shape) != tuple(v.shape[:-1]):
             raise ValueError("wall_buoyancy expects a density %s for a velocity %s, got %s" % (tuple(v.shape[:-1]), tuple(v.shape), tuple(d.shape)))
+        if int(bnd) != bnd or bnd < 1:
+            raise ValueError("wall_buoyancy: bnd must be an integer >= 1, got %r" % (bnd,))
+        if isinstance(force, torch.Tensor):
+            if force.dim() != 2:
+                raise ValueError("wall_buoyancy: a force tensor must be [B,D], got %s" % (tuple(force.shape),))
+            rows = _entry_rows(force, v, nd, "wall_buoyancy: force")
+            out = _smoke_out(out, v, "wall_buoyancy")
+            flags = None if obstacle is None else _obstacle_arg(obstacle, d.shape, bnd, "wall_buoyancy")
+            call("df_wall_buoyancy%dd_open_dev" % nd, _ptr(v), _ptr(d), _ptr(out), None if flags is None else _ptr(flags), _ptr(rows),
+                 *(list(d.shape) + [int(bnd), osd, _stream()]))
+            return out
         f = [float(x) for x in force]
         if len(f) != nd:
             raise ValueError("wall_buoyancy: force must have %d components, got %r" % (nd, force))
-        if int(bnd) != bnd or bnd < 1:
-            raise ValueError("wall_buoyancy: bnd must be an integer >= 1, got %r" % (bnd,))
         out = _smoke_out(out, v, "wall_buoyancy")
         if osd:
             flags = None if obstacle is None else _obstacle_arg(obstacle, d.shape, bnd, "wall_buoyancy")
@@ -2175,6 +2362,12 @@ def default_buoyancy_force(shape, dt, gravity=-4e-3):
     return tuple(f)
 
 
+def buoyancy_forces(shape, dt, gravities):
+    """``default_buoyancy_force`` for one gravity per batch entry: a float32 tensor [B,D] (host), row b =
+    ``default_buoyancy_force(shape, dt, gravities[b])``, for the ``force=`` of ``wall_buoyancy``, ``smoke_step`` and ``simulate_smoke``."""
+    return torch.tensor([default_buoyancy_force(shape, dt, float(g)) for g in gravities], dtype=torch.float32).reshape(-1, len(shape))
+
+
 class _SmokeBuffers(object):
     """Everything a smoke step needs besides its inputs, allocated once for a shape."""
 
@@ -2184,8 +2377,20 @@ class _SmokeBuffers(object):
         self.pws = pressure_workspace(vel)
 
 
-def _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags=None, osd=0):
-    advect(d, v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, source=mask, out=d_out, workspace=buf.adv, obstacle=flags)
+def _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags=None, osd=0, time=0.0,
+                vstamp=None, v_stamped=None):
+    if vstamp is None:
+        advect(d, v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, source=mask, out=d_out, workspace=buf.adv, obstacle=flags, time=time)
+    else:
+        # the script's order: density inflow, velocity stamp (into ``v_stamped``, which may be ``v``), then both advections through it
+        n = d.numel()
+        if mask is not None:
+            stamped = buf.adv[:n].view(d.shape)
+            _stamp(d, mask, 1.0, stamped, time, bnd)
+            d = stamped
+        v = stamp_velocity(v, vstamp[0], vstamp[1], out=v_stamped)
+        advect(d, v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, out=d_out, workspace=buf.adv[n:] if mask is not None else buf.adv,
+               obstacle=flags)
     advect_velocity(v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, out=v_out, workspace=buf.fwd, obstacle=flags, open_bound=osd)
     wall_buoyancy(v_out, d_out, force, bnd=bnd, out=v_out, obstacle=flags, open_bound=osd)
     _, _, iters = solve_pressure(v_out, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=v_out, workspace=buf.pws,
@@ -2194,14 +2399,17 @@ def _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd
 
 
 def smoke_step(density, vel, dt, source=None, force=None, order=2, clamp_mode=2, bnd=1, accuracy=1e-4, max_iter=None, check_every=None,
-               obstacle=None, open_bound=None):
+               obstacle=None, open_bound=None, time=0.0, inflow_velocity=None):
     """One frame of the reference's smoke scene (scene/smoke_pos_size.py:187-195) on ``density`` [B,(Z,)Y,X] and the MAC velocity ``vel``
     [B,(Z,)Y,X,D] of a closed box: stamp ``source`` (a mask) with 1, advect the density and the velocity through the OLD velocity, zero
     the wall faces, add buoyancy (``force``; default ``default_buoyancy_force``), project.  Returns new ``(density, vel)``.
     ``obstacle`` (a mask of solid cells or the flags of ``obstacle_flags``) makes it the loop of scene/smoke3_obs_buo.py:211-219: the same
     statements with the obstacle in the flag grid, the solid faces 0 after the walls and after the projection.  ``source`` may be a
     ``SphereSource`` [B,D].  ``open_bound`` (see ``open_sides``) makes it the loop of scene/smoke3_rot.py / smoke3_mov.py: the velocity
-    steps treat those sides as open; the density needs nothing, its band is 0 after every advection (``resetOutflow``)."""
+    steps treat those sides as open; the density needs nothing, its band is 0 after every advection (``resetOutflow``).
+    With a ``NoiseInflow`` source (evaluated at solver time ``time``), ``inflow_velocity=(shape, values)`` (a ``CylinderShape`` and the
+    [B,D] or [D] values ``stamp_velocity`` writes) and ``force`` a tensor [B,D] it is the loop of scene/smoke3_vel_buo.py:222-232: density
+    inflow, velocity stamp, both advections through the STAMPED velocity, walls, buoyancy, projection.  ``vel`` itself is never written."""
     with torch.no_grad():
         d, v, nd = _advect_dims(density, vel)
         osd = open_sides(open_bound, nd)
@@ -2210,12 +2418,23 @@ def smoke_step(density, vel, dt, source=None, force=None, order=2, clamp_mode=2,
         buf = _SmokeBuffers(d, v, order, mask is not None)
         flags = _obstacle_arg(obstacle, d.shape, bnd, "smoke_step") if obstacle is not None else None
         d_out, v_out = torch.empty_like(d), torch.empty_like(v)
-        _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags, osd)
+        _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags, osd, time,
+                    _inflow_velocity_arg(inflow_velocity, v, nd))
         return d_out, v_out
 
 
+def _inflow_velocity_arg(inflow_velocity, v, nd):
+    """``(CylinderShape, values [B,D] on the device)`` from the ``inflow_velocity=`` keyword, or None"""
+    if inflow_velocity is None:
+        return None
+    shape, values = inflow_velocity
+    if not isinstance(shape, CylinderShape) or shape.dim != nd:
+        raise ValueError("inflow_velocity expects (CylinderShape of %d axes, values)" % nd)
+    return shape, _entry_rows(values, v, nd, "inflow_velocity: values")
+
+
 def _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, stats, obstacle=None,
-                  open_bound=None):
+                  open_bound=None, inflow_velocity=None):
     d, v, nd = _advect_dims(density0, vel0)
     osd = open_sides(open_bound, nd)
     force = default_buoyancy_force(d.shape[1:], dt) if force is None else force
@@ -2224,11 +2443,15 @@ def _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, b
         raise ValueError("simulate_smoke: %d frames of source centres for %d steps" % (mask.centers.shape[0], int(steps)))
     buf = _SmokeBuffers(d, v, order, mask is not None)
     flags = _obstacle_arg(obstacle, d.shape, bnd, "simulate_smoke") if obstacle is not None else None      # once per sequence
+    vstamp = _inflow_velocity_arg(inflow_velocity, v, nd)
+    if isinstance(force, torch.Tensor):
+        force = _entry_rows(force, v, nd, "simulate_smoke: force")                                         # on the device, once
     d, v = d.clone(), v.clone()
     d2, v2 = torch.empty_like(d), torch.empty_like(v)
     for t in range(int(steps)):
+        # the working copy ``v`` is stamped in place (v_stamped=v): the caller's vel0 is never written
         iters = _smoke_step(d, v, d2, v2, buf, dt, _source_frame(mask, t), force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags,
-                            osd)
+                            osd, _source_time(mask, t, dt), vstamp, v)
         if stats is not None:
             stats.append(iters)
         d, d2, v, v2 = d2, d, v2, v
@@ -2236,15 +2459,17 @@ def _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, b
 
 
 def simulate_smoke(density0, vel0, steps, dt=0.5, source=None, force=None, order=2, clamp_mode=2, bnd=1, accuracy=1e-4, max_iter=None,
-                   check_every=None, stack=True, stats=None, obstacle=None, open_bound=None):
+                   check_every=None, stack=True, stats=None, obstacle=None, open_bound=None, inflow_velocity=None):
     """``steps`` chained ``smoke_step`` frames from ``(density0, vel0)`` (left untouched); every buffer is allocated once.  With
     ``stack`` returns ``(density, vels)``, ``vels`` [steps,B,(Z,)Y,X,D] the velocity after each step; without it returns a generator of
     ``(density, vel)`` per step -- views of buffers the next step overwrites, so copy what is to be kept.  ``stats``: a list that
     receives the iteration counts [B] of every step's solve.  ``obstacle``: as for ``smoke_step``, packed into flags once.  ``source``
-    may be a ``SphereSource`` [B,D] or [T,B,D] (step t stamps ``centers[t]``); ``open_bound``: as for ``smoke_step``."""
+    may be a ``SphereSource`` [B,D] or [T,B,D] (step t stamps ``centers[t]``); ``open_bound``: as for ``smoke_step``.  A ``NoiseInflow``
+    source is evaluated at ``t * dt`` in step t; ``inflow_velocity`` and a ``force`` tensor [B,D]: as for ``smoke_step`` (the stamp goes
+    into the sequence's own working buffer)."""
     with torch.no_grad():
         gen = _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, stats, obstacle,
-                            open_bound)
+                            open_bound, inflow_velocity)
         if not stack:
             return _no_grad_iter(gen)
         vels = torch.empty((int(steps),) + tuple(vel0.shape), dtype=torch.float32, device=vel0.device)

@@ -753,6 +753,22 @@ def moving_source(batch_manager, scene=0, device="cuda"):
     return ops.SphereSource(torch.from_numpy(centers).to(device), gs[0] * float(a["src_radius"]))
 
 
+def smoke3_vel_buo_source(batch_manager, nseed=123):
+    """The density inflow of a data set written by ``data.generate_smoke3_vel_buo_dataset`` (scene/smoke3_vel_buo.py) as an
+    ``ops.NoiseInflow``, rebuilt from the source keys and ``time_step`` of its args.txt, for ``Trainer.advect_(source=...)`` and
+    ``ops.advect_sequence`` -- the script's ``advect()`` mode (lines 49-125).  ``nseed``: the generator's noise seed (args.txt holds the
+    script's keys only).  The noise is this project's own lattice noise, NOT mantaflow's wavelet noise."""
+    from .data import smoke3_vel_buo_inflow
+    a = batch_manager.args
+    keys = ["src_x_pos", "src_y_pos", "src_z_pos", "src_radius", "src_height", "time_step"]
+    missing = [k for k in keys if k not in a]
+    if missing:
+        raise KeyError("smoke3_vel_buo_source: args.txt of %s lacks %s -- the dataset is not a smoke3_vel_buo scene" %
+                       (batch_manager.root, ", ".join(missing)))
+    gs = (int(batch_manager.res_x), int(batch_manager.res_y), int(batch_manager.res_z))
+    return smoke3_vel_buo_inflow(gs, *[float(a[k]) for k in keys], nseed=nseed)
+
+
 def smoke_pos_size_source(batch_manager, p1, p2):
     """The smoke source of scene/smoke_pos_size.py:46-55,81 for grid indices (p1, p2) of a dataset written by that scene:
     ``{"center": (X * x_pos, Y * src_y_pos), "radius": X * r}`` with x_pos and r interpolated from the min_/max_/num_ keys of args.txt."""

@@ -572,7 +572,7 @@ int df_particle_levelset_union3d(const float* pos_sorted, const int32_t* cell_st
  * solvePressure(cgAccuracy, cgMaxIterFac), setWallBcs.  The first two statements are df_density_source and df_advect_* above; the
  * rest is below.  mantaflow cannot be run beside this library, so bit parity with it is NOT claimed: the definition below is the
  * contract (tests/smoke_ref.py restates it; tests/smoke_obs_ref.py the obstacle rules and tests/smoke_open_ref.py the open sides further
- * down).  Left out: noise-modulated inflow (densityInflow) and the inflow velocity stamp of scene/smoke3_vel_buo.py, mantaflow's
+ * down, tests/smoke_inflow_ref.py the noise inflow, the cylinder stamp and the per-entry force after that).  Left out: mantaflow's
  * convective outflow extrapolation (a zero-gradient fill stands in for it), the MIC(0) preconditioner.
  *
  * Layouts as for df_advect_*: density, pressure [B,(Z,)Y,X]; velocity [B,(Z,)Y,X,D], D = 2 | 3 MAC face values, component a of cell c
@@ -708,7 +708,7 @@ int df_pressure_correct3d_flags(const float* vel, const float* pressure, float* 
                                 int64_t X, int bnd, df_stream_t stream);
 
 /* ---- the same step with open sides and a moving source: the main() loops of the reference's scene/smoke3_rot.py and scene/smoke3_mov.py
- * (open_bound 'xXyYzZ', a sphere source whose centre changes every frame), of scene/smoke3_vel_buo.py ('XyY', without its noise inflow) and
+ * (open_bound 'xXyYzZ', a sphere source whose centre changes every frame), of scene/smoke3_vel_buo.py ('XyY'; its inflow is further down) and
  * the open_bound option of scene/smoke_pos_size.py ('xXyY').  mantaflow cannot be run beside this library: setOpenBound's corner rule, the
  * Dirichlet cells of its pressure solve and KnAddBuoyancy are restated from memory, and parity is with the NumPy restatement of THIS
  * definition (tests/smoke_open_ref.py), NOT with mantaflow.
@@ -778,6 +778,72 @@ int df_density_sphere_source2d(const float* density, const float* centers, float
                                int64_t X, df_stream_t stream);
 int df_density_sphere_source3d(const float* density, const float* centers, float radius, float value, float* out, int64_t B, int64_t Z,
                                int64_t Y, int64_t X, df_stream_t stream);
+
+/* ---- the noise inflow, the cylinder stamp and the per-entry force: what the main() loop of the reference's scene/smoke3_vel_buo.py:212-232
+ * does beyond the blocks above -- densityInflow(flags, density, noise, shape=Cylinder, scale, sigma), Cylinder.applyToGrid(grid=vel,
+ * value=inflow), and an inflow velocity and a buoyancy that differ per scene.  mantaflow cannot be run beside this library: KnApplyNoiseInfl,
+ * the cylinder's distance and ApplyShapeToMACGrid are restated from memory, and mantaflow's NoiseField(loadFromFile=True) is wavelet
+ * noise read from a tile file, which cannot be restated at all.  A seeded lattice value noise of this project's OWN stands in for it.
+ * Parity is with the NumPy restatement of THIS definition (tests/smoke_inflow_ref.py), NOT with mantaflow.
+ *
+ * Layouts as above.  All arithmetic fp32, no fused multiply-add, in the order written; sqrt and / are the correctly rounded ones;
+ * max(x, y) and min(x, y) are only ever taken of numbers.
+ * Cylinder.  cyl [B, 2*D + 1] fp32 in DEVICE memory, one per batch entry, in cell units: centre (cx, cy[, cz]), half-axis vector
+ * (zx, zy[, zz]), radius.  |z|^2 = (zx*zx + zy*zy) [+ zz*zz], |z| = sqrt(|z|^2), a = z / |z| per component.  An entry is VALID when all
+ * its 2*D + 1 numbers are finite and 0 < |z|^2 < inf; an entry that is not (a zero-length axis, a NaN) stamps nothing, in both entry
+ * points.  For a point q:  d = q - centre;  h = (dx*ax + dy*ay) [+ dz*az];  r2 = max(((dx*dx + dy*dy) [+ dz*dz]) - h*h, 0).
+ * Coordinates are meant to stay below 2^60 in magnitude, so that no square overflows.
+ *   - Noise inflow, df_density_noise_inflow*: a cell that is not interior (bnd, as above; bnd = 0 is allowed here: no band) is copied
+ *     through.  For an interior cell c, q = (i, j[, k]) -- the cell INDEX, as mantaflow's kernel passes it, not the centre:
+ *       dh = |h| - |z|,  dr = sqrt(r2) - radius,  sdf = min(max(dh, dr), 0) + sqrt(max(dh, 0)^2 + max(dr, 0)^2)
+ *     the exact signed distance of the finite cylinder.  Unless sdf <= sigma, out = density.  Else
+ *       factor = min(max(1 - (0.5 / sigma) * (sdf + sigma), 0), 1),  target = (N(c) * scale) * factor,
+ *       out = target > density ? target : density
+ *     so a density that is not below the target comes back with its own bits.  target is 0 at sdf = sigma.
+ *     A cell farther than (|z| + |radius|) + (sigma + 1) from the centre along any axis is copied without evaluating sdf; its sdf exceeds
+ *     sigma by a whole cell, so this changes no result.
+ *     N(c), the noise:  tq = time_anim * time;  per axis a  q_a = ((float(c_a) * pos_scale[a]) * inv_extent + pos_offset[a]) + tq, clamped
+ *     to [-2^30, 2^30] (a NaN becomes -2^30);  f_a = floor(q_a),  t_a = q_a - f_a,  l_a = int32(f_a) reinterpreted as uint32,
+ *     w_a = (t_a*t_a) * (3 - 2*t_a).  The lattice value at (ix, iy, iz), uint32 arithmetic mod 2^32, iz = 0 in 2-D:
+ *       h = seed ^ (ix * 0x8DA6B343) ^ (iy * 0xD8163841) ^ (iz * 0xCB1AB31F);
+ *       h ^= h >> 16;  h *= 0x7FEB352D;  h ^= h >> 15;  h *= 0x846CA68B;  h ^= h >> 16;   value = float(h >> 8) * 2^-23 - 1   in [-1, 1)
+ *     D-linear interpolation with lerp(a, b, w) = a + w*(b - a): along x with w_x at (ly, lz), (ly+1, lz)[, (ly, lz+1), (ly+1, lz+1)], then
+ *     along y with w_y[, then along z with w_z]; the high corners are l + 1 mod 2^32.  Then v = (v + val_offset) * val_scale, and with
+ *     clamp != 0  v = min(max(v, clamp_neg), clamp_pos).  The noise is continuous across lattice planes (w = 0 returns the low corner
+ *     exactly), so a floor that differs by rounding moves the value by rounding only.
+ *     noise is a HOST pointer read during the call; inv_extent is 1 / X for mantaflow's scaling by the grid's x extent.  out may be density.
+ *   - Cylinder stamp, df_mac_cylinder_stamp*: for batch entry b, component a of cell c is set to values[b][a] (values [B,D] fp32 in DEVICE
+ *     memory) when the position of that face, q = (i, j+.5[, k+.5]) for x, (i+.5, j[, k+.5]) for y, (i+.5, j+.5, k) for z, satisfies
+ *     |h| <= |z| and r2 < radius*radius; else it is copied through.  Faces are tested one by one.  There is no flags argument and no
+ *     bnd: the stamp ignores obstacles and the band.  out may be vel.
+ *   - Per-entry force, df_wall_buoyancy*_open_dev: df_wall_buoyancy*_open with force[a] of batch entry b read from forces [B,D] fp32 in
+ *     DEVICE memory.  flags may be NULL and open_sides may be 0.  Bit rule: when every row equals (fx, fy[, fz]) it returns the bits of
+ *     df_wall_buoyancy*_open with those scalars -- which, by that entry point's own bit rule, are those of the closed and `_flags` forms.
+ * Errors: DF_EINVAL null pointer / non-positive extent / sigma not a positive number / bnd < 0 (inflow), < 1 (force) / open_sides as above /
+ * cylinders, values or forces that overlap the output / out == density (force), DF_ESHAPE an extent too large (force: or < 2*bnd + 2),
+ * DF_EALIGN a pointer not 4-byte aligned.  The cylinders live in device memory, so a zero-length axis is not an error here: it stamps
+ * nothing. */
+typedef struct df_noise_params {
+  float pos_scale[3];   /* [2] is not read in 2-D */
+  float pos_offset[3];
+  float time_anim, val_offset, val_scale;
+  int32_t clamp;        /* nonzero: clamp to [clamp_neg, clamp_pos] */
+  float clamp_neg, clamp_pos;
+  uint32_t seed;
+  float inv_extent;
+} df_noise_params;
+int df_density_noise_inflow2d(const float* density, float* out, const float* cyl, const df_noise_params* noise, float time, float scale,
+                              float sigma, int64_t B, int64_t Y, int64_t X, int bnd, df_stream_t stream);
+int df_density_noise_inflow3d(const float* density, float* out, const float* cyl, const df_noise_params* noise, float time, float scale,
+                              float sigma, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, df_stream_t stream);
+int df_mac_cylinder_stamp2d(const float* vel, const float* cyl, const float* values, float* out, int64_t B, int64_t Y, int64_t X,
+                            df_stream_t stream);
+int df_mac_cylinder_stamp3d(const float* vel, const float* cyl, const float* values, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X,
+                            df_stream_t stream);
+int df_wall_buoyancy2d_open_dev(const float* vel, const float* density, float* out, const uint8_t* flags, const float* forces, int64_t B,
+                                int64_t Y, int64_t X, int bnd, int open_sides, df_stream_t stream);
+int df_wall_buoyancy3d_open_dev(const float* vel, const float* density, float* out, const uint8_t* flags, const float* forces, int64_t B,
+                                int64_t Z, int64_t Y, int64_t X, int bnd, int open_sides, df_stream_t stream);
 
 /* ---- the liquid solver step: the main() loops of the reference's liquid scenes (scene/liquid_pos_size.py:254-295, scene/liquid3_d_r.py),
  * a FLIP step in the script's order:  pp.advectInGrid(IntRK4), mapPartsToMAC, extrapolateMACFromWeight(distance=2), markFluidCells,
