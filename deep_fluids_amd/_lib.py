@@ -199,6 +199,19 @@ SIGNATURES = {
     "df_liquid_flags3d": (I32, [P, P, P, I64, I64, I64, I64, I64, I32, P]),
     "df_liquid_forces2d": (I32, [P, P, P, I64, I64, I64, F32, F32, I32, P]),
     "df_liquid_forces3d": (I32, [P, P, P, I64, I64, I64, I64, F32, F32, F32, I32, P]),
+    "df_particle_levelset_averaged2d": (I32, [P, P, P, I64, I64, I64, I64, F32, P]),
+    "df_particle_levelset_averaged3d": (I32, [P, P, P, I64, I64, I64, I64, I64, F32, P]),
+    "df_levelset_smooth2d": (I32, [P, P, I64, I64, I64, I32, I32, F32, P]),
+    "df_levelset_smooth3d": (I32, [P, P, I64, I64, I64, I64, I32, I32, F32, P]),
+    "df_pressure_workspace_bytes_gf": (I64, [I64, I64, I64, I64]),
+    "df_pressure_init2d_gf": (I32, [P, P, P, I64, P, P, I64, I64, I64, I32, F32, P]),
+    "df_pressure_init3d_gf": (I32, [P, P, P, I64, P, P, I64, I64, I64, I64, I32, F32, P]),
+    "df_pressure_cg_direction2d_gf": (I32, [P, I64, P, I64, I64, I64, I32, I64, F32, I64, P]),
+    "df_pressure_cg_direction3d_gf": (I32, [P, I64, P, I64, I64, I64, I64, I32, I64, F32, I64, P]),
+    "df_pressure_cg_update2d_gf": (I32, [P, P, I64, P, I64, I64, I64, I32, I64, P]),
+    "df_pressure_cg_update3d_gf": (I32, [P, P, I64, P, I64, I64, I64, I64, I32, I64, P]),
+    "df_pressure_correct2d_gf": (I32, [P, P, P, P, P, I64, I64, I64, I32, F32, P]),
+    "df_pressure_correct3d_gf": (I32, [P, P, P, P, P, I64, I64, I64, I64, I32, F32, P]),
     "df_pressure_cg_direction2d_liquid": (I32, [P, I64, P, I64, I64, I64, I32, I64, F32, I64, P]),
     "df_pressure_cg_direction3d_liquid": (I32, [P, I64, P, I64, I64, I64, I64, I32, I64, F32, I64, P]),
     "df_pressure_correct2d_liquid": (I32, [P, P, P, P, I64, I64, I64, I32, P]),

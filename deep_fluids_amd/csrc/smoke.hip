@@ -42,6 +42,13 @@
 //                     diffuse_finish interleaves x back.  The component reads of init (stride D) and the component gathers of finish
 //                     (D planes) are each coalesced along x within a plane; every other pass is planar.
 //
+//   ghost fluid       the `_gf` entry points: the liquid rows with the surface where phi = 0 between a liquid cell and an air neighbour
+//                     (mantaflow's solvePressure(phi=), restated from memory as the header says; parity is with tests/liquid_gf_ref.py).
+//                     New kernels, not instantiations of the ones above: init also writes diag (1 per liquid neighbour, 1/theta per
+//                     air neighbour) and z = r / diag behind the plain workspace, direction and update run the Jacobi-preconditioned
+//                     iteration with r.z in the place of r.r, the correction puts the ghost value on the air side of a surface face.
+//                     The loop, the partials, the state words and df_pressure_status are the plain solve's.
+//
 // Float -> int conversions are taken only of values already known to be inside the grid (advect_common.hpp).
 #include "advect_common.hpp"
 #include "df_common.hpp"
@@ -544,6 +551,169 @@ __global__ __launch_bounds__(kThreads) void pressure_correct_kernel(const float*
   *reinterpret_cast<VelRec<D>*>(out + idx * D) = r;
 }
 
+// ---- ghost-fluid free surface: the liquid rows with the surface where phi = 0 between a liquid cell and an air neighbour ------------------
+// theta of liquid cell i (phi pi) and an interior air neighbour (phi pa), as 1/theta: denom = pi - pa; theta = 0.5 if denom > -1e-4,
+// else min(max(pi / denom, gf_clamp), 1).  A NaN comes out as gf_clamp.
+__device__ __forceinline__ float gf_inv_theta(float pi, float pa, float gf_clamp) {
+  const float denom = pi - pa;
+  const float theta = denom > -1e-4f ? 0.5f : fminf(fmaxf(pi / denom, gf_clamp), 1.0f);
+  return 1.0f / theta;
+}
+
+struct GfWs {
+  float *diag, *z;
+};
+
+// the two arrays of the ghost-fluid path lie behind the workspace of the plain solve (df_pressure_status finds its words unchanged)
+GfWs carve_gf(void* ws, int64_t B, int64_t n, int64_t nblk) {
+  float* f = static_cast<float*>(ws) + ws_floats(B, n, nblk);
+  return GfWs{f, f + B * n};
+}
+
+// b = -div on the liquid cells; diag = (1 per liquid neighbour, 1/theta per interior air neighbour, summed from 0 in the order x-, x+, y-,
+// y+[, z-, z+]); z = b / diag; x = 0, r = b, p = z; the first r.z and max|r| partials.  Off the liquid: diag = 1, everything else 0.
+template <int D>
+__global__ __launch_bounds__(kThreads) void pressure_init_gf(const float* __restrict__ vel, float* __restrict__ x,
+                                                             const uint8_t* __restrict__ flags, const float* __restrict__ phi, PWs w, GfWs gw,
+                                                             PDims d, float gf_clamp) {
+  __shared__ float lds[4];
+  const PCell c = pdecode<D, true>(d, flags);
+  const int64_t g = static_cast<int64_t>(c.e) * d.n + c.cell;
+  float b = 0.0f, dg = 1.0f, z = 0.0f;
+  if (c.interior) {
+    const int64_t st[3] = {D, static_cast<int64_t>(d.X) * D, static_cast<int64_t>(d.X) * d.Y * D};
+    const float* v = vel + g * D;
+    float div = v[st[0]] - v[0];
+    div = div + (v[st[1] + 1] - v[1]);
+    if (D == 3) div = div + (v[st[2] + 2] - v[2]);
+    b = -div;
+    const int64_t sc[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
+    const int ext[3] = {d.X, d.Y, d.Z};
+    const float pi = phi[g];
+    dg = 0.0f;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {                         // a liquid cell is interior by its index: both neighbours are inside the entry
+      if (c.fl & lo_bit(a)) dg = dg + 1.0f;
+      else if (c.p[a] > d.bnd) dg = dg + gf_inv_theta(pi, phi[g - sc[a]], gf_clamp);
+      if (c.fl & hi_bit(a)) dg = dg + 1.0f;
+      else if (c.p[a] + 1 < ext[a] - d.bnd) dg = dg + gf_inv_theta(pi, phi[g + sc[a]], gf_clamp);
+    }
+    if (!(dg > 0.0f)) dg = 1.0f;                          // a liquid cell between walls alone: its row is 0 = b, never divided by
+    z = b / dg;
+  }
+  if (c.cell < d.n) {
+    x[g] = 0.0f; w.r[g] = b; w.p[0][g] = z; w.p[1][g] = 0.0f; w.q[g] = 0.0f; gw.diag[g] = dg; gw.z[g] = z;
+  }
+  const float rz = block_reduce<false>(b * z, lds);
+  const float mx = block_reduce<true>(fabsf(b), lds);
+  if (threadIdx.x == 0) {
+    w.rr_part[static_cast<int64_t>(c.e) * d.nblk + c.j] = rz;
+    w.mx_part[static_cast<int64_t>(c.e) * d.nblk + c.j] = mx;
+  }
+}
+
+// cg_direction_kernel for the Jacobi-preconditioned iteration: the `rr` partials and CgState::rr hold r.z, p = z + beta * p_old,
+// q = diag * p - (sum over the liquid neighbours); the decision reads max|r| of the UNscaled residual, as the plain solve does
+template <int D>
+__global__ __launch_bounds__(kThreads) void cg_direction_gf(PWs w, GfWs gw, const uint8_t* __restrict__ flags, PDims d, int par, int first,
+                                                            float accuracy, int max_iter) {
+  __shared__ float lds[4];
+  const PCell c = pdecode<D, true>(d, flags);
+  const bool writer = c.j == 0 && threadIdx.x == 0;
+  CgState s;
+  if (first) s = CgState{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1, 0, 0};
+  else s = w.state[par][c.e];
+  if (!s.active) {                                      // frozen: carry the record over, touch nothing else
+    if (writer) w.state[par ^ 1][c.e] = s;
+    return;
+  }
+  const int64_t po = static_cast<int64_t>(c.e) * d.nblk;
+  const float rz = entry_reduce<false>(w.rr_part + po, d.nblk, lds);
+  const float mx = entry_reduce<true>(w.mx_part + po, d.nblk, lds);
+  const bool act = mx > accuracy && rz > 0.0f && s.iters < max_iter;
+  const float beta = first ? 0.0f : rz / s.rr;          // s.rr > 0: the entry was active
+  if (writer) w.state[par ^ 1][c.e] = CgState{rz, mx, s.alpha, act ? beta : s.beta, s.pq, act ? 1 : 0, s.iters + (act ? 1 : 0), 0};
+  if (!act) return;
+  float pq = 0.0f;
+  if (c.interior) {
+    const int64_t eo = static_cast<int64_t>(c.e) * d.n;
+    const float* __restrict__ z = gw.z + eo;
+    const float* __restrict__ po_ = w.p[par] + eo;
+    const int64_t st[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
+    const float pc = z[c.cell] + beta * po_[c.cell];
+    float sum = 0.0f;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+      if (c.fl & lo_bit(a)) { const int64_t nb = c.cell - st[a]; sum += z[nb] + beta * po_[nb]; }
+      if (c.fl & hi_bit(a)) { const int64_t nb = c.cell + st[a]; sum += z[nb] + beta * po_[nb]; }
+    }
+    const float qv = gw.diag[eo + c.cell] * pc - sum;
+    w.p[par ^ 1][eo + c.cell] = pc;
+    w.q[eo + c.cell] = qv;
+    pq = pc * qv;
+  }
+  pq = block_reduce<false>(pq, lds);
+  if (threadIdx.x == 0) w.pq_part[po + c.j] = pq;
+}
+
+// cg_update_kernel with z = r / diag written beside r, and r.z for r.r in the partials
+template <int D>
+__global__ __launch_bounds__(kThreads) void cg_update_gf(float* __restrict__ x, PWs w, GfWs gw, const uint8_t* __restrict__ flags, PDims d,
+                                                         int par) {
+  __shared__ float lds[4];
+  const PCell c = pdecode<D, true>(d, flags);
+  CgState* s = w.state[par ^ 1] + c.e;                  // what direction(k) has just written
+  if (!s->active) return;
+  const float rz_old = s->rr;
+  const int64_t po = static_cast<int64_t>(c.e) * d.nblk;
+  const float pq = entry_reduce<false>(w.pq_part + po, d.nblk, lds);
+  const float alpha = pq > 0.0f ? rz_old / pq : 0.0f;
+  if (c.j == 0 && threadIdx.x == 0) { s->alpha = alpha; s->pq = pq; }   // words no workgroup of this launch reads
+  float rz = 0.0f, mx = 0.0f;
+  if (c.interior) {
+    const int64_t g = static_cast<int64_t>(c.e) * d.n + c.cell;
+    x[g] = x[g] + alpha * w.p[par ^ 1][g];
+    const float rn = w.r[g] - alpha * w.q[g];
+    const float zn = rn / gw.diag[g];
+    w.r[g] = rn;
+    gw.z[g] = zn;
+    rz = rn * zn;
+    mx = fabsf(rn);
+  }
+  rz = block_reduce<false>(rz, lds);
+  mx = block_reduce<true>(mx, lds);
+  if (threadIdx.x == 0) { w.rr_part[po + c.j] = rz; w.mx_part[po + c.j] = mx; }
+}
+
+// the correction with the ghost value on the air side of a surface face: between interior cells c and c - e_a, both liquid:
+// out = vel - (p[c] - p[c - e_a]); c liquid alone: out = vel - p[c] * (1/theta); c - e_a liquid alone: out = vel + p[c - e_a] * (1/theta),
+// theta of the liquid cell towards the air one; no liquid: copied; wall faces 0
+template <int D>
+__global__ __launch_bounds__(kThreads) void pressure_correct_gf(const float* vel, const float* __restrict__ pr, float* out,
+                                                                const uint8_t* __restrict__ flags, const float* __restrict__ phi, AdvDims d,
+                                                                float gf_clamp) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (idx >= d.ncell) return;
+  const Cell<D> c = decode<D>(idx, d);
+  const unsigned fl = c.interior ? flags[idx] : 0u;     // a flags byte is believed of an interior cell only
+  const int64_t st[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
+  const VelRec<D> v = *reinterpret_cast<const VelRec<D>*>(vel + idx * D);
+  VelRec<D> r;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    r.v[a] = 0.0f;
+    if (kept_face<false>(c.interior, c.p[a], d.bnd, 0u, a)) {   // c and c - e_a are interior: both inside the grid
+      const bool here = (fl & kFluid) != 0u, there = (fl & lo_bit(a)) != 0u;
+      const int64_t nb = idx - st[a];
+      if (here && there) r.v[a] = v.v[a] - (pr[idx] - pr[nb]);
+      else if (here) r.v[a] = v.v[a] - pr[idx] * gf_inv_theta(phi[idx], phi[nb], gf_clamp);
+      else if (there) r.v[a] = v.v[a] + pr[nb] * gf_inv_theta(phi[nb], phi[idx], gf_clamp);
+      else r.v[a] = v.v[a];
+    }
+  }
+  *reinterpret_cast<VelRec<D>*>(out + idx * D) = r;
+}
+
 // ---- the fill of the open cells, the sphere stamp ------------------------------------------------------------------------------------------
 // in place: vel[c][a] = vel[c'][a], c' = c clamped to [bnd, extent - bnd] along a and to [bnd, extent - bnd - 1] along every other axis
 template <int D>
@@ -888,6 +1058,99 @@ int diffuse_finish(const char* fn, void* ws, int64_t ws_bytes, float* out, int64
   return df::launched(fn);
 }
 
+// ---- the ghost-fluid solve: the workspace of the plain solve, then diag and z ----
+int64_t gf_bytes(const PDims& d) { return 4 * (ws_floats(d.B, d.n, d.nblk) + 2 * static_cast<int64_t>(d.B) * d.n); }
+
+int gf_ws(const char* fn, const void* ws, int64_t ws_bytes, const PDims& d) {
+  DF_REQUIRE(ws, DF_EINVAL, "%s: null workspace", fn);
+  DF_REQUIRE(aligned4(ws), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  DF_REQUIRE(ws_bytes >= gf_bytes(d), DF_EWORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes, (long long)gf_bytes(d));
+  return DF_OK;
+}
+
+int gf_apart(const char* fn, const void* ws, const PDims& d, const void* p, int64_t bytes, const char* what) {
+  DF_REQUIRE(!p || apart(ws, gf_bytes(d), p, bytes), DF_EINVAL, "%s: the workspace overlaps the %s", fn, what);
+  return DF_OK;
+}
+
+int gf_clamp_ok(const char* fn, float gf_clamp) {
+  DF_REQUIRE(gf_clamp > 0.0f && gf_clamp <= 1.0f, DF_EINVAL, "%s: gf_clamp must lie in (0, 1] (got %g)", fn, (double)gf_clamp);
+  return DF_OK;
+}
+
+template <int D>
+int pressure_init_gf_(const char* fn, const float* vel, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, const float* phi,
+                      int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, float gf_clamp, df_stream_t stream) {
+  DF_REQUIRE(vel && pressure && phi, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : !pressure ? "pressure" : "level set");
+  if (int e = gf_clamp_ok(fn, gf_clamp)) return e;
+  PDims d;
+  unsigned grid;
+  if (int e = pplan(fn, D, B, Z, Y, X, bnd, &d, &grid)) return e;
+  if (int e = gf_ws(fn, ws, ws_bytes, d)) return e;
+  DF_REQUIRE(static_cast<const void*>(pressure) != static_cast<const void*>(vel) && static_cast<const void*>(pressure) != static_cast<const void*>(phi),
+             DF_EINVAL, "%s: the pressure must not be the velocity or the level set (they are read at a neighbour)", fn);
+  if (int e = gf_apart(fn, ws, d, vel, 4 * d.n * B * D, "velocity")) return e;
+  if (int e = gf_apart(fn, ws, d, pressure, 4 * d.n * B, "pressure")) return e;
+  if (int e = gf_apart(fn, ws, d, phi, 4 * d.n * B, "level set")) return e;
+  if (int e = check_flags<true>(fn, flags, d.n * B, pressure, 4 * d.n * B, "pressure")) return e;
+  if (int e = gf_apart(fn, ws, d, flags, d.n * B, "flags")) return e;
+  DF_REQUIRE(aligned4(vel) && aligned4(pressure) && aligned4(phi), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  hipLaunchKernelGGL((pressure_init_gf<D>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), vel, pressure, flags, phi,
+                     carve(ws, B, d.n, d.nblk), carve_gf(ws, B, d.n, d.nblk), d, gf_clamp);
+  return df::launched(fn);
+}
+
+template <int D>
+int cg_direction_gf_(const char* fn, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                     int64_t k, float accuracy, int64_t max_iter, df_stream_t stream) {
+  PDims d;
+  unsigned grid;
+  if (int e = pplan(fn, D, B, Z, Y, X, bnd, &d, &grid)) return e;
+  if (int e = gf_ws(fn, ws, ws_bytes, d)) return e;
+  DF_REQUIRE(k >= 0 && max_iter >= 0 && max_iter < (1ll << 31), DF_EINVAL, "%s: iteration %lld of at most %lld", fn, (long long)k,
+             (long long)max_iter);
+  DF_REQUIRE(accuracy >= 0.0f, DF_EINVAL, "%s: accuracy must be >= 0", fn);
+  if (int e = check_flags<true>(fn, flags, d.n * B, nullptr, 0, "")) return e;
+  if (int e = gf_apart(fn, ws, d, flags, d.n * B, "flags")) return e;
+  hipLaunchKernelGGL((cg_direction_gf<D>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), carve(ws, B, d.n, d.nblk),
+                     carve_gf(ws, B, d.n, d.nblk), flags, d, (int)(k & 1), k == 0 ? 1 : 0, accuracy, (int)max_iter);
+  return df::launched(fn);
+}
+
+template <int D>
+int cg_update_gf_(const char* fn, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X,
+                  int bnd, int64_t k, df_stream_t stream) {
+  DF_REQUIRE(pressure, DF_EINVAL, "%s: null pressure", fn);
+  PDims d;
+  unsigned grid;
+  if (int e = pplan(fn, D, B, Z, Y, X, bnd, &d, &grid)) return e;
+  if (int e = gf_ws(fn, ws, ws_bytes, d)) return e;
+  DF_REQUIRE(k >= 0, DF_EINVAL, "%s: iteration %lld", fn, (long long)k);
+  if (int e = gf_apart(fn, ws, d, pressure, 4 * d.n * B, "pressure")) return e;
+  if (int e = check_flags<true>(fn, flags, d.n * B, pressure, 4 * d.n * B, "pressure")) return e;
+  if (int e = gf_apart(fn, ws, d, flags, d.n * B, "flags")) return e;
+  DF_REQUIRE(aligned4(pressure), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  hipLaunchKernelGGL((cg_update_gf<D>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), pressure, carve(ws, B, d.n, d.nblk),
+                     carve_gf(ws, B, d.n, d.nblk), flags, d, (int)(k & 1));
+  return df::launched(fn);
+}
+
+template <int D>
+int pressure_correct_gf_(const char* fn, const float* vel, const float* pressure, float* out, const uint8_t* flags, const float* phi, int64_t B,
+                         int64_t Z, int64_t Y, int64_t X, int bnd, float gf_clamp, df_stream_t stream) {
+  DF_REQUIRE(vel && pressure && out && phi, DF_EINVAL, "%s: null %s", fn, !vel ? "velocity" : !pressure ? "pressure" : !out ? "output" : "level set");
+  if (int e = gf_clamp_ok(fn, gf_clamp)) return e;
+  AdvDims d;
+  unsigned nblk;
+  if (int e = plan(fn, D, B, Z, Y, X, bnd, 0.0f, &d, &nblk)) return e;
+  DF_REQUIRE(apart(out, 4 * d.ncell * D, pressure, 4 * d.ncell) && apart(out, 4 * d.ncell * D, phi, 4 * d.ncell), DF_EINVAL,
+             "%s: the output overlaps the pressure or the level set (they are read at a neighbour)", fn);
+  if (int e = check_flags<true>(fn, flags, d.ncell, out, 4 * d.ncell * D, "output")) return e;
+  DF_REQUIRE(aligned4(vel) && aligned4(pressure) && aligned4(out) && aligned4(phi), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  hipLaunchKernelGGL((pressure_correct_gf<D>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, pressure, out, flags, phi, d, gf_clamp);
+  return df::launched(fn);
+}
+
 // an `_open` entry point: the closed instantiation for open_sides = 0 (the same bits by construction), flags may be null (no obstacles)
 #define DF_OPEN_CALL(F, D, ...)                                                                                       \
   (open_sides == 0 ? (flags ? F<D, true, false>(__VA_ARGS__) : F<D, false, false>(__VA_ARGS__))                      \
@@ -1124,6 +1387,43 @@ int df_pressure_correct2d_liquid(const float* vel, const float* pressure, float*
 int df_pressure_correct3d_liquid(const float* vel, const float* pressure, float* out, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y,
                                  int64_t X, int bnd, df_stream_t stream) {
   return pressure_correct<3, true, false, true>("df_pressure_correct3d_liquid", vel, pressure, out, flags, B, Z, Y, X, bnd, stream);
+}
+// ---- the ghost-fluid free-surface projection: phi beside the flags, Jacobi-preconditioned CG, diag and z behind the plain workspace ----
+int64_t df_pressure_workspace_bytes_gf(int64_t B, int64_t Z, int64_t Y, int64_t X) {
+  const int64_t cg = df_pressure_workspace_bytes(B, Z, Y, X);
+  return cg < 0 ? cg : cg + 8 * B * Z * Y * X;
+}
+int df_pressure_init2d_gf(const float* vel, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, const float* phi, int64_t B,
+                          int64_t Y, int64_t X, int bnd, float gf_clamp, df_stream_t stream) {
+  return pressure_init_gf_<2>("df_pressure_init2d_gf", vel, pressure, ws, ws_bytes, flags, phi, B, 1, Y, X, bnd, gf_clamp, stream);
+}
+int df_pressure_init3d_gf(const float* vel, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, const float* phi, int64_t B,
+                          int64_t Z, int64_t Y, int64_t X, int bnd, float gf_clamp, df_stream_t stream) {
+  return pressure_init_gf_<3>("df_pressure_init3d_gf", vel, pressure, ws, ws_bytes, flags, phi, B, Z, Y, X, bnd, gf_clamp, stream);
+}
+int df_pressure_cg_direction2d_gf(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k,
+                                  float accuracy, int64_t max_iter, df_stream_t stream) {
+  return cg_direction_gf_<2>("df_pressure_cg_direction2d_gf", ws, ws_bytes, flags, B, 1, Y, X, bnd, k, accuracy, max_iter, stream);
+}
+int df_pressure_cg_direction3d_gf(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                                  int64_t k, float accuracy, int64_t max_iter, df_stream_t stream) {
+  return cg_direction_gf_<3>("df_pressure_cg_direction3d_gf", ws, ws_bytes, flags, B, Z, Y, X, bnd, k, accuracy, max_iter, stream);
+}
+int df_pressure_cg_update2d_gf(float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd,
+                               int64_t k, df_stream_t stream) {
+  return cg_update_gf_<2>("df_pressure_cg_update2d_gf", pressure, ws, ws_bytes, flags, B, 1, Y, X, bnd, k, stream);
+}
+int df_pressure_cg_update3d_gf(float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X,
+                               int bnd, int64_t k, df_stream_t stream) {
+  return cg_update_gf_<3>("df_pressure_cg_update3d_gf", pressure, ws, ws_bytes, flags, B, Z, Y, X, bnd, k, stream);
+}
+int df_pressure_correct2d_gf(const float* vel, const float* pressure, float* out, const uint8_t* flags, const float* phi, int64_t B, int64_t Y,
+                             int64_t X, int bnd, float gf_clamp, df_stream_t stream) {
+  return pressure_correct_gf_<2>("df_pressure_correct2d_gf", vel, pressure, out, flags, phi, B, 1, Y, X, bnd, gf_clamp, stream);
+}
+int df_pressure_correct3d_gf(const float* vel, const float* pressure, float* out, const uint8_t* flags, const float* phi, int64_t B, int64_t Z,
+                             int64_t Y, int64_t X, int bnd, float gf_clamp, df_stream_t stream) {
+  return pressure_correct_gf_<3>("df_pressure_correct3d_gf", vel, pressure, out, flags, phi, B, Z, Y, X, bnd, gf_clamp, stream);
 }
 // ---- implicit velocity diffusion (cgSolveDiffusion): the CG over the B*D components, alpha[B] in device memory ----
 int64_t df_diffuse_workspace_bytes(int64_t B, int64_t Z, int64_t Y, int64_t X, int dim) {

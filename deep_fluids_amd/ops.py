@@ -33,7 +33,7 @@ __all__ = [
     "advect", "advect_sequence", "advect_workspace", "density_image", "sphere_mask",
     "advect_velocity", "wall_buoyancy", "solve_pressure", "pressure_workspace", "smoke_step", "simulate_smoke", "default_buoyancy_force", "default_max_iter", "obstacle_flags", "ObstacleFlags",
     "open_sides", "SphereSource",
-    "advect_particles", "particle_cells", "particle_levelset", "liquid_sequence", "seed_particles", "box_levelset", "sphere_levelset",
+    "advect_particles", "particle_cells", "particle_levelset", "particle_levelset_averaged", "liquid_sequence", "seed_particles", "box_levelset", "sphere_levelset",
     "variable_scope", "get_variables", "get_variable", "reset_variables", "set_random_seed", "all_variables",
 ]
 
@@ -2274,11 +2274,12 @@ def _pressure_dims(v, nd):
     return dims, (dims if nd == 3 else [dims[0], 1] + dims[1:])
 
 
-def pressure_workspace(vel):
+def pressure_workspace(vel, ghost_fluid=False):
     """The scratch ``solve_pressure`` needs for ``vel`` [B,(Z,)Y,X,D] (residual, two directions, A p, partial sums, per-entry scalars): a
-    float32 GPU tensor, reusable across calls of the same shape."""
+    float32 GPU tensor, reusable across calls of the same shape.  ``ghost_fluid=True`` adds the two arrays (diagonal, preconditioned
+    residual) that ``solve_pressure_liquid(phi=...)`` needs; such a workspace serves the plain solves too."""
     v, nd = _smoke_vel(vel, "pressure_workspace")
-    nbytes = query("df_pressure_workspace_bytes", *[int(x) for x in _pressure_dims(v, nd)[1]])
+    nbytes = query("df_pressure_workspace_bytes_gf" if ghost_fluid else "df_pressure_workspace_bytes", *[int(x) for x in _pressure_dims(v, nd)[1]])
     if nbytes < 0:
         raise ValueError("pressure_workspace: unsupported extents %s" % (tuple(v.shape),))
     return torch.empty((nbytes // 4,), dtype=torch.float32, device=v.device)
@@ -2493,7 +2494,8 @@ def _no_grad_iter(gen):
 #      scene/liquid_pos_size.py:47-132): marker particles traced with RK4, a union level set rebuilt from them.  Inference only, no
 #      autograd.  The step is defined in include/deepfluids_hip.h; mantaflow, which the reference calls for it, cannot be run here, so
 #      bit parity with it is not claimed.  Left out: extrapolateMACSimple, markFluidCells, resetOutflow, adjustNumber resampling,
-#      averagedParticleLevelset / phi.setBound (the 2-D scene runs through the union form its script carries commented out), meshing ----
+#      meshing; the frame loop uses the union form (the one the 2-D script carries commented out), the averaged form with phi.setBound
+#      is ``particle_levelset_averaged`` ----
 def _particle_pos(pos, who):
     p = _prep(pos.detach(), "pos")
     if p.dim() != 3 or p.shape[-1] not in (2, 3):
@@ -2566,6 +2568,63 @@ def particle_levelset(pos, shape, radius_factor=1.0, out=None):
         spos, cell_start, _ = particle_cells(p, shape)
         call("df_particle_levelset_union%dd" % nd, _ptr(spos), _ptr(cell_start), _ptr(out), B, N, *(list(shape) + [float(radius_factor), _stream()]))
         return out
+
+
+def _levelset_averaged(spos, cell_start, out, tmp, B, N, shape, radius_factor, smooth, smooth_neg, bound_value, bnd):
+    """the launches of ``particle_levelset_averaged`` on sorted particles; ``tmp`` is a second buffer of ``out``'s shape (None without
+    smoothing passes).  The passes alternate between the two buffers and end in ``out``; the band is fused into the last one."""
+    nd = len(shape)
+    dims = [B] + list(shape)
+    passes = [1] * smooth + [2] * smooth_neg
+    bufs = (out, tmp) if len(passes) % 2 == 0 else (tmp, out)
+    cur = bufs[0]
+    call("df_particle_levelset_averaged%dd" % nd, _ptr(spos), _ptr(cell_start), _ptr(cur), B, N, *(list(shape) + [float(radius_factor), _stream()]))
+    for n, mode in enumerate(passes):
+        nxt = bufs[(n + 1) % 2]
+        call("df_levelset_smooth%dd" % nd, _ptr(cur), _ptr(nxt), *(dims + [mode, bnd if n == len(passes) - 1 else 0, float(bound_value), _stream()]))
+        cur = nxt
+    if not passes and bnd > 0:
+        call("df_levelset_smooth%dd" % nd, _ptr(out), _ptr(out), *(dims + [0, bnd, float(bound_value), _stream()]))
+    return out
+
+
+def particle_levelset_averaged(pos, shape, radius_factor=1.0, smooth=1, smooth_neg=1, bound_value=1.0, bnd=1, out=None, cells=None):
+    """The averaged surface level set of the particles ``pos`` [B,N,D] on a grid ``shape`` -- modelled on mantaflow's
+    ``averagedParticleLevelset(pp, pindex, flags, gpi, phi, radius_factor, smooth, smooth_neg)`` followed by ``phi.setBound(bound_value,
+    bnd)`` (scene/liquid_pos_size.py:254-295), restated from memory and NOT bit-identical to it; include/deepfluids_hip.h holds the
+    definition that is tested, against tests/liquid_gf_ref.py.  With R = 0.5*sqrt(D)*(radius_factor + 0.01) and w = max(0, 1 -
+    |x_c - p|^2 / (4 R^2)) over the particles of the cells within +-(int(R) + 1) of cell c: phi = |x_c - sum(w p) / sum(w)| - R where
+    sum(w) > 1e-6, else R.  Then ``smooth`` passes of the (2D+1)-point average on every cell off the outermost layer, ``smooth_neg``
+    passes of the same average kept only where it is smaller, and the ``bnd``-wide band set to ``bound_value`` (``bnd=0``: no band).
+    ``cells=(sorted_pos, cell_start)`` of ``particle_cells`` reuses a sort already done (``pos`` is then only read for its shape).  The
+    sums run in ascending cell order and, inside a cell, in sorted order: deterministic, no atomics."""
+    with torch.no_grad():
+        smooth, smooth_neg = int(smooth), int(smooth_neg)
+        if smooth < 0 or smooth_neg < 0:
+            raise ValueError("particle_levelset_averaged: smooth and smooth_neg must be >= 0, got %r, %r" % (smooth, smooth_neg))
+        if int(bnd) != bnd or bnd < 0:
+            raise ValueError("particle_levelset_averaged: bnd must be an integer >= 0, got %r" % (bnd,))
+        if not 0.0 <= radius_factor <= 1024.0:
+            raise ValueError("particle_levelset_averaged: radius_factor must lie in [0, 1024], got %r" % (radius_factor,))
+        p = _particle_pos(pos, "particle_levelset_averaged")
+        B, N, nd = p.shape
+        shape = _grid_shape(shape, nd, "particle_levelset_averaged")
+        if out is None:
+            out = _empty((B,) + shape, p)
+        elif tuple(out.shape) != (B,) + shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("particle_levelset_averaged: out must be a contiguous float32 GPU tensor %s" % ((B,) + shape,))
+        if cells is None:
+            spos, cell_start, _ = particle_cells(p, shape)
+        else:
+            spos, cell_start = cells
+            spos = _particle_pos(spos, "particle_levelset_averaged")
+            if tuple(spos.shape) != tuple(p.shape):
+                raise ValueError("particle_levelset_averaged: cells hold positions %s for positions %s" % (tuple(spos.shape), tuple(p.shape)))
+            if (cell_start.dtype != torch.int32 or not cell_start.is_cuda or not cell_start.is_contiguous()
+                    or cell_start.numel() != B * int(np.prod(shape)) + 1):
+                raise ValueError("particle_levelset_averaged: cells[1] must be the int32 GPU tensor [B*ncell + 1] of particle_cells")
+        tmp = torch.empty_like(out) if smooth + smooth_neg else None
+        return _levelset_averaged(spos, cell_start, out, tmp, B, N, shape, radius_factor, smooth, smooth_neg, bound_value, int(bnd))
 
 
 def liquid_sequence(pos0, vels, dt, bnd=1, vel_scale=1.0, radius_factor=1.0, images=False):
@@ -2656,10 +2715,10 @@ def seed_particles(phi0, discretization=2, randomness=0.05, seed=123, bnd=1):
 
 # ---- the liquid solver step (the main() loops of the reference's liquid scenes, scene/liquid_pos_size.py:254-295 and
 #      scene/liquid3_d_r.py): FLIP.  The step is defined in include/deepfluids_hip.h (tests/liquid_ref.py restates it); mantaflow cannot
-#      be run here, so parity with it is not claimed.  Left out: the ghost-fluid surface treatment of solvePressure(phi=) (p = 0 sits at
-#      the air cell centres: a first-order surface), adjustNumber resampling (N is constant), averagedParticleLevelset /
-#      extrapolateLsSimple / phi.setBound (the solve does not read phi), resetOutflow and open sides, obstacles inside the liquid,
-#      MIC(0), per-entry particle counts (one call, one N) ----
+#      be run here, so parity with it is not claimed.  By default p = 0 sits at the air cell centres (a first-order surface);
+#      ``ghost_fluid=True`` adds averagedParticleLevelset / phi.setBound and the ghost-fluid surface of solvePressure(phi=)
+#      (tests/liquid_gf_ref.py restates them).  Left out: adjustNumber resampling (N is constant), extrapolateLsSimple, resetOutflow
+#      and open sides, obstacles inside the liquid, MIC(0), per-entry particle counts (one call, one N) ----
 DEFAULT_FLIP_RATIO = 0.97
 
 
@@ -2791,15 +2850,45 @@ def _cg_loop(direction, update, ws, nbytes, dims4, count, max_iter, check_every)
         k += 1
 
 
-def solve_pressure_liquid(vel, flags, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, out=None, workspace=None):
+def _gf_phi_arg(phi, vel, who):
+    """checked against ``vel``'s shape and device before anything asks where ``vel`` lives (a bad phi is refused without a GPU): a
+    contiguous float32 tensor of the cells' shape, on a GPU, and on the SAME device as ``vel`` -- the kernels take raw pointers"""
+    if not isinstance(vel, torch.Tensor) or vel.dim() < 2:
+        raise ValueError("%s expects a velocity tensor [B,(Z,)Y,X,D], got %r" % (who, type(vel)))
+    want = tuple(vel.shape[:-1])
+    if (not isinstance(phi, torch.Tensor) or phi.dtype != torch.float32 or tuple(phi.shape) != want or not phi.is_cuda
+            or phi.device != vel.device or not phi.is_contiguous()):
+        raise ValueError("%s: phi must be a contiguous float32 GPU tensor %s on the velocity's device" % (who, want))
+    return phi.detach()
+
+
+def _gf_clamp_arg(gf_clamp, who):
+    if not 0.0 < gf_clamp <= 1.0:
+        raise ValueError("%s: gf_clamp must lie in (0, 1], got %r" % (who, gf_clamp))
+    return float(gf_clamp)
+
+
+def solve_pressure_liquid(vel, flags, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, out=None, workspace=None, phi=None,
+                          gf_clamp=1e-4):
     """The free-surface projection: ``solve_pressure`` with rows for the liquid cells of ``flags`` (``liquid_flags``) only and p = 0 in
     the air cells -- n_c counts every neighbour that is interior by its index, the neighbour sums run over the liquid ones.  Faces
     between two interior cells of which at least one is liquid are corrected with p as the array holds it (0 in air), other interior
     faces are left unchanged, wall faces become 0: every liquid cell ends divergence free to the solve's accuracy.  p = 0 sits at the
     air cell centres (first-order surface; mantaflow's ghost-fluid treatment is left out), and there is no preconditioner.  A liquid
     region that touches no air is singular but consistent, as a closed box is.  Returns ``(vel_projected, pressure, iterations)``;
-    ``out`` may be ``vel``."""
+    ``out`` may be ``vel``.
+    ``phi`` [B,(Z,)Y,X] (``particle_levelset_averaged``): the ghost-fluid surface of mantaflow's ``solvePressure(phi=phi)``, restated
+    from memory; the definition that is tested is the one in include/deepfluids_hip.h (tests/liquid_gf_ref.py), NOT mantaflow.  Between a
+    liquid cell i and an interior air neighbour a the surface sits at theta = phi_i / (phi_i - phi_a) of the way (0.5 if phi_i - phi_a
+    > -1e-4, else clamped to [``gf_clamp``, 1]): the row of i gets p_i / theta for that neighbour, and the face is corrected with
+    p_i / theta.  The solve is then Jacobi-preconditioned CG (the clamp puts diagonals up to 1 / gf_clamp beside diagonals of 4-6),
+    stopping on the UNscaled residual as before, and needs ``pressure_workspace(vel, ghost_fluid=True)``.  With ``phi=None`` nothing of
+    this is launched."""
     with torch.no_grad():
+        gf = phi is not None
+        if gf:
+            gfc = _gf_clamp_arg(gf_clamp, "solve_pressure_liquid")
+            phi = _gf_phi_arg(phi, vel, "solve_pressure_liquid")
         v, nd = _smoke_vel(vel, "solve_pressure_liquid")
         bnd = _liquid_bnd(bnd, "solve_pressure_liquid")
         if not accuracy >= 0:
@@ -2812,7 +2901,7 @@ def solve_pressure_liquid(vel, flags, bnd=1, accuracy=1e-4, max_iter=None, check
         if max_iter < 0 or check_every < 1:
             raise ValueError("solve_pressure_liquid: max_iter must be >= 0 and check_every >= 1, got %r, %r" % (max_iter, check_every))
         out = _smoke_out(out, v, "solve_pressure_liquid")
-        ws = workspace if workspace is not None else pressure_workspace(v)
+        ws = workspace if workspace is not None else pressure_workspace(v, ghost_fluid=gf)
         if ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous():
             raise ValueError("solve_pressure_liquid: workspace must be a contiguous float32 GPU tensor (pressure_workspace)")
         nbytes = ws.numel() * 4
@@ -2820,6 +2909,14 @@ def solve_pressure_liquid(vel, flags, bnd=1, accuracy=1e-4, max_iter=None, check
         words = torch.empty((1 + dims[0],), dtype=torch.int32, device=v.device)
         count, iters = words[:1], words[1:]
         acc, max_iter = float(accuracy), int(max_iter)
+        if gf:
+            call("df_pressure_init%dd_gf" % nd, _ptr(v), _ptr(pressure), _ptr(ws), nbytes, _ptr(fl), _ptr(phi), *(dims + [bnd, gfc, _stream()]))
+            k = _cg_loop(lambda k: call("df_pressure_cg_direction%dd_gf" % nd, _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, acc, max_iter, _stream()])),
+                         lambda k: call("df_pressure_cg_update%dd_gf" % nd, _ptr(pressure), _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, _stream()])),
+                         ws, nbytes, dims4, count, max_iter, check_every)
+            call("df_pressure_status", _ptr(ws), nbytes, *(dims4 + [k, None, _ptr(iters), _stream()]))
+            call("df_pressure_correct%dd_gf" % nd, _ptr(v), _ptr(pressure), _ptr(out), _ptr(fl), _ptr(phi), *(dims + [bnd, gfc, _stream()]))
+            return out, pressure, iters.clone()
         call("df_pressure_init%dd_flags" % nd, _ptr(v), _ptr(pressure), _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, _stream()]))
         k = _cg_loop(lambda k: call("df_pressure_cg_direction%dd_liquid" % nd, _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, acc, max_iter, _stream()])),
                      lambda k: call("df_pressure_cg_update%dd_flags" % nd, _ptr(pressure), _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, _stream()])),
@@ -2948,9 +3045,10 @@ def sample_velocity(vel, pos):
         return flip_update(p, torch.zeros_like(p), vel, vel, flip_ratio=0.0)
 
 
-def _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws, visc=None):
+def _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws, visc=None, gf=None):
     """``visc``: None, or (alpha [B] float32 on the device, the diffusion workspace): the viscous step of scene/liquid3_vis.py:256-296;
-    the iteration counts [B, D] of its diffusion are then returned as a fifth element"""
+    the iteration counts [B, D] of its diffusion are then returned as a fifth element.  ``gf``: None, or (radius_factor, gf_clamp, two
+    phi buffers): the averaged level set of the step's sorted particles right after the flags, handed to the solve"""
     nd = p.shape[-1]
     shape = tuple(v.shape[1:-1])
     B, N = p.shape[0], p.shape[1]
@@ -2962,6 +3060,10 @@ def _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_
     vel_old = vel                                            # extrapolate_mac leaves its input untouched
     vel, _ = extrapolate_mac(vel, known, 2, bnd=bnd)
     flags, touch = liquid_flags(cell_start, shape, B, N, bnd=bnd)
+    phi = None
+    if gf is not None:
+        # averagedParticleLevelset(.., radius_factor, 1, 1) and phi.setBound(1, bWidth), from the sort above: no second sort
+        phi = _levelset_averaged(spos, cell_start, gf[2], gf[3], B, N, shape, gf[0], 1, 1, 1.0, bnd)
     if visc is not None:
         # setWallBcs as a zero-force pass (+ 0.0 leaves a value's bits but for -0), then cgSolveDiffusion: the step's accuracy, the
         # iteration cap of cgSolveDiffusion's own default (max_iter is the pressure solve's)
@@ -2970,7 +3072,11 @@ def _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_
         _, diters = _diffuse(vel, visc[0], vel, visc[1], visc[1].numel() * 4, nd, dims, dims4, bnd, float(accuracy),
                              default_diffusion_max_iter(shape), DEFAULT_CHECK_EVERY if check_every is None else int(check_every))
     liquid_forces(vel, flags, force, bnd=bnd, out=vel)
-    _, _, iters = solve_pressure_liquid(vel, flags, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=vel, workspace=pws)
+    if phi is None:
+        _, _, iters = solve_pressure_liquid(vel, flags, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=vel, workspace=pws)
+    else:
+        _, _, iters = solve_pressure_liquid(vel, flags, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=vel,
+                                            workspace=pws, phi=phi, gf_clamp=gf[1])
     vel, _ = extrapolate_mac(vel, touch, 4, bnd=bnd)
     flip_update(spos, su, vel, vel_old, flip_ratio=flip_ratio, out=su)
     if visc is not None:
@@ -2995,39 +3101,57 @@ def _viscosity_arg(viscosity_alpha, v, who):
     return torch.from_numpy(a32).to(v.device), diffusion_workspace(v)
 
 
+def _ghost_fluid_arg(ghost_fluid, radius_factor, gf_clamp, v, who):
+    """None, or (radius_factor, gf_clamp, two phi buffers) for ``_liquid_step``"""
+    if not ghost_fluid:
+        return None
+    if not 0.0 <= radius_factor <= 1024.0:
+        raise ValueError("%s: radius_factor must lie in [0, 1024], got %r" % (who, radius_factor))
+    phi = _empty(tuple(v.shape[:-1]), v)
+    return float(radius_factor), _gf_clamp_arg(gf_clamp, who), phi, torch.empty_like(phi)
+
+
 def liquid_step(pos, pvel, vel, dt, force=None, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, flip_ratio=DEFAULT_FLIP_RATIO,
-                open_bound=False, viscosity_alpha=None):
+                open_bound=False, viscosity_alpha=None, ghost_fluid=False, radius_factor=1.0, gf_clamp=1e-4):
     """One frame of the reference's liquid scenes (scene/liquid_pos_size.py:254-295) on particles ``pos``, ``pvel`` [B,N,D] and the MAC
     velocity ``vel`` [B,(Z,)Y,X,D], in the script's order: trace the particles through ``vel`` (RK4), sort them by cell, map their
     velocities to the grid, extrapolate 2 layers from the faces that received weight, mark the liquid cells, add gravity (``force``,
     cells per step; default ``default_gravity_force``, restated from memory of mantaflow's addGravity) and zero the wall faces, project
     with p = 0 in the air cells, extrapolate 4 layers from the faces of liquid cells, update the particle velocities (FLIP,
     ``flip_ratio``).  Returns ``(pos, pvel, vel, iterations)``: the particles come back SORTED by cell, so the step permutes them
-    (``pos`` and ``pvel`` alike); ``vel`` is the frame the script saves.  Left out, as named in include/deepfluids_hip.h: the
-    ghost-fluid surface, adjustNumber, the averaged level set, open sides (``open_bound=True`` is refused), obstacles, MIC(0).
+    (``pos`` and ``pvel`` alike); ``vel`` is the frame the script saves.  Left out, as named in include/deepfluids_hip.h:
+    adjustNumber, extrapolateLsSimple, open sides (``open_bound=True`` is refused), obstacles, MIC(0).
+    ``ghost_fluid=True``: right after the liquid cells are marked, the averaged level set of the step's own sorted particles
+    (``particle_levelset_averaged`` with ``radius_factor``, smooth 1, smooth_neg 1, the ``bnd`` band set to 1.0 -- the script's order) is
+    computed and handed to the solve (``solve_pressure_liquid(phi=..., gf_clamp=...)``): the velocity is projected against a surface
+    between the cell centres.  With ``False`` p = 0 sits at the air cell centres and nothing of this is launched.
     ``viscosity_alpha`` (a number or B numbers, ``diffusion_alpha``): the viscous step of scene/liquid3_vis.py:256-296 -- after the
     liquid cells are marked the wall faces are zeroed (setWallBcs, a zero-force ``liquid_forces`` pass) and the velocity is diffused
     (``diffuse_velocity`` at the step's ``accuracy`` and its own default iteration cap), then gravity and the rest as above; the
     result is then ``(pos, pvel, vel, iterations, diffusion_iterations [B, D])``.  With ``None`` nothing of this is launched."""
     if open_bound:
         raise NotImplementedError("liquid_step: open sides (resetOutflow) are not implemented for the liquid solver")
+    if ghost_fluid:
+        _gf_clamp_arg(gf_clamp, "liquid_step")
     with torch.no_grad():
         p, u, v = _liquid_state(pos, pvel, vel, "liquid_step")
         bnd = _liquid_bnd(bnd, "liquid_step")
         force = default_gravity_force(v.shape[1:-1], dt) if force is None else force
         visc = _viscosity_arg(viscosity_alpha, v, "liquid_step")
-        return _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pressure_workspace(v), visc)
+        gf = _ghost_fluid_arg(ghost_fluid, radius_factor, gf_clamp, v, "liquid_step")
+        return _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pressure_workspace(v, gf is not None), visc, gf)
 
 
 def _liquid_frames(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats, viscosity_alpha=None,
-                   keep_every=1):
+                   keep_every=1, ghost_fluid=False, radius_factor=1.0, gf_clamp=1e-4):
     p, u, v = _liquid_state(pos0, pvel0, vel0, "simulate_liquid")
     bnd = _liquid_bnd(bnd, "simulate_liquid")
     force = default_gravity_force(v.shape[1:-1], dt) if force is None else force
-    pws = pressure_workspace(v)
+    gf = _ghost_fluid_arg(ghost_fluid, radius_factor, gf_clamp, v, "simulate_liquid")
+    pws = pressure_workspace(v, gf is not None)
     visc = _viscosity_arg(viscosity_alpha, v, "simulate_liquid")
     for t in range(int(steps)):
-        p, u, v, iters = _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws, visc)[:4]
+        p, u, v, iters = _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws, visc, gf)[:4]
         if stats is not None:
             stats.append(iters)
         if t % keep_every == 0:
@@ -3035,21 +3159,24 @@ def _liquid_frames(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter,
 
 
 def simulate_liquid(pos0, pvel0, vel0, steps, dt=0.5, force=None, bnd=1, accuracy=1e-4, max_iter=None, check_every=None,
-                    flip_ratio=DEFAULT_FLIP_RATIO, stack=True, stats=None, open_bound=False, viscosity_alpha=None, keep_every=1):
+                    flip_ratio=DEFAULT_FLIP_RATIO, stack=True, stats=None, open_bound=False, viscosity_alpha=None, keep_every=1,
+                    ghost_fluid=False, radius_factor=1.0, gf_clamp=1e-4):
     """``steps`` chained ``liquid_step`` frames from ``(pos0, pvel0, vel0)`` (left untouched).  With ``stack`` returns
     ``(pos, pvel, vels)``, ``vels`` [steps,B,(Z,)Y,X,D] the velocity after each step; without it a generator of ``(pos, pvel, vel)`` per
     step.  ``stats``: a list that receives the iteration counts [B] of every step's solve.  ``viscosity_alpha``: as in ``liquid_step``.
     ``keep_every=k``: only the steps 0, k, 2k, ... (0-based) are yielded or stacked (``vels`` [ceil(steps/k),...]; a scene whose frame
     is ``k`` solver steps) -- every step still runs and reports to ``stats``, and with ``stack`` the returned particles are those after
-    the LAST step."""
+    the LAST step.  ``ghost_fluid``, ``radius_factor``, ``gf_clamp``: as in ``liquid_step``."""
     if open_bound:
         raise NotImplementedError("simulate_liquid: open sides (resetOutflow) are not implemented for the liquid solver")
     keep_every = int(keep_every)
     if keep_every < 1:
         raise ValueError("simulate_liquid: keep_every must be >= 1, got %r" % (keep_every,))
+    if ghost_fluid:
+        _gf_clamp_arg(gf_clamp, "simulate_liquid")
     with torch.no_grad():
         gen = _liquid_frames(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats, viscosity_alpha,
-                             keep_every)
+                             keep_every, ghost_fluid, radius_factor, gf_clamp)
         if not stack:
             return _no_grad_iter(gen)
         kept = (int(steps) + keep_every - 1) // keep_every

@@ -851,9 +851,10 @@ int df_wall_buoyancy3d_open_dev(const float* vel, const float* density, float* o
  * the gather and the ranges are df_particles_* above, the solve reuses df_pressure_init*_flags, df_pressure_cg_update*_flags,
  * df_pressure_status and the workspace; the rest is below.  mantaflow cannot be run beside this library: its kernels are restated from
  * memory, and parity is with the NumPy restatement of THIS definition (tests/liquid_ref.py), NOT with mantaflow.
- * Left out: the ghost-fluid surface treatment (solvePressure(phi=)): p = 0 sits at the centres of the air cells, a first-order surface;
- * adjustNumber resampling (N is constant); averagedParticleLevelset, extrapolateLsSimple and phi.setBound (the solve does not read phi);
- * resetOutflow and open sides; obstacles inside the liquid; the MIC(0) preconditioner; per-entry particle counts (one call, one N).
+ * In this block p = 0 sits at the centres of the air cells, a first-order surface; the averaged level set, phi.setBound and the
+ * ghost-fluid surface treatment (solvePressure(phi=)) are the opt-in block at the end of this header.
+ * Left out: adjustNumber resampling (N is constant); extrapolateLsSimple; resetOutflow and open sides; obstacles inside the liquid; the
+ * MIC(0) preconditioner; per-entry particle counts (one call, one N).
  *
  * Layouts, bnd, "interior", e_a, u(p) and the per-axis weights (n; s0, s1) are those of the blocks above.  pos, pvel [B,N,D] fp32 SORTED
  * by key (df_particles_gather with the order of the key sort, for both); vel, weight [B,(Z,)Y,X,D] fp32; marks [B,(Z,)Y,X,D] uint8;
@@ -922,7 +923,7 @@ int df_flip_update3d(const float* pos, const float* pvel_in, float* pvel_out, co
  * memory (MakeLaplaceMatrix on an all-fluid dummy flag grid, scaled by alpha, plus the identity, identity rows in obstacle cells; u handed
  * in as the first guess) and reduced to its symmetric positive definite interior block; parity is with the NumPy restatement of THIS
  * definition (tests/diffuse_ref.py), NOT with mantaflow.
- * Left out: adjustNumber; the level set (the solve does not read phi); the ghost-fluid surface; the MIC(0) preconditioner; obstacles --
+ * Left out: adjustNumber; the MIC(0) preconditioner; obstacles (the level set and the ghost-fluid surface: the block at the end) --
  * mantaflow's identity rows are the bnd band only.
  *
  * vel [B,(Z,)Y,X,D] fp32, alpha [B] fp32 >= 0 in DEVICE memory (the caller checks the values; a negative or non-finite alpha yields
@@ -957,6 +958,74 @@ int df_diffuse_cg_update2d(void* ws, int64_t ws_bytes, int64_t B, int64_t Y, int
 int df_diffuse_cg_update3d(void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int64_t k, df_stream_t stream);
 int df_diffuse_finish2d(void* ws, int64_t ws_bytes, float* out, int64_t B, int64_t Y, int64_t X, int bnd, df_stream_t stream);
 int df_diffuse_finish3d(void* ws, int64_t ws_bytes, float* out, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, df_stream_t stream);
+
+/* ---- the liquid solver's surface: averagedParticleLevelset(pp, pindex, flags, gpi, phi, radius_factor, 1, 1) + phi.setBound(1, bWidth)
+ * and solvePressure(flags, vel, pressure, phi=phi), the two calls every liquid loop of the reference makes (scene/liquid_pos_size.py:254-295,
+ * scene/liquid3_d_r.py, scene/liquid3_vis.py).  mantaflow cannot be run beside this library: both are restated from memory, the
+ * definitions below are this library's own, and parity is with the NumPy restatement of THESE definitions (tests/liquid_gf_ref.py), NOT
+ * with mantaflow.  Still left out: adjustNumber, extrapolateLsSimple, resetOutflow and open sides, obstacles inside the liquid, MIC(0).
+ * DF_VERSION is NOT raised by this block (it has stayed 207 through every solver block of this header): a client cannot tell from
+ * df_version() whether these symbols exist and has to look them up (dlsym), as for the smoke and liquid blocks above.
+ *
+ * Layouts, bnd, "interior", e_a and the sorted particles are those of the blocks above; phi [B,(Z,)Y,X] fp32.  All arithmetic fp32, no
+ * fused multiply-add, in the order written; no floating-point atomics; an entry's result does not depend on the rest of the batch.
+ *   averaged level set   df_particle_levelset_averaged*: R = (0.5 * sqrt(D)) * (radius_factor + 0.01) (the radius of the union form),
+ *            r = (int)R + 1, R4 = 4 * (R * R).  For cell c with centre x_c = index + 0.5, every particle p of the cells within +-r of c on
+ *            every axis that lie inside the grid is visited in ascending cell order (z, then y, then x), inside a cell in sorted order:
+ *            s2 = dx*dx + dy*dy [+ dz*dz] with d = x_c - p;  w = max(0, 1 - s2 / R4);  wacc += w;  pacc_a += w * p_a  (from 0).
+ *            wacc > 1e-6: phi = sqrt(ex*ex + ey*ey [+ ez*ez]) - R with e_a = x_c,a - pacc_a / wacc; otherwise phi = R.  N = 0: phi = R
+ *            everywhere, the particle arrays and cell_start may be NULL.
+ *   smoothing            df_levelset_smooth*, ONE pass per call, out != in unless mode is 0.  mode 1: a cell off the outermost layer of the
+ *            grid becomes t = (((self + x-) + x+) + y-) + y+ [+ z-) + z+] * (1 / (2D + 1)), that constant rounded to fp32 once; the
+ *            outermost layer is copied.  mode 2: the same t, kept only where t < self.  mode 0: a copy.  band > 0: the cells within `band`
+ *            of a side are set to bound_value instead of the pass's result (phi.setBound, fused into the last pass).
+ *   ghost-fluid system   rows for the liquid cells of flags (df_liquid_flags*).  For a liquid cell i and a neighbour a that is interior by
+ *            its index and not liquid:  denom = phi_i - phi_a;  theta = 0.5 if denom > -1e-4, else min(max(phi_i / denom, gf_clamp), 1)
+ *            (a NaN gives gf_clamp).  Row i:  sum over liquid neighbours (p_i - p_n) + sum over air neighbours p_i * (1 / theta) = -div_i;
+ *            wall neighbours contribute nothing.  diag_i = the sum, from 0 and in the order x-, x+, y-, y+[, z-, z+], of 1 per liquid
+ *            neighbour and 1 / theta per air neighbour (1 if that sum is 0); off-diagonals -1 between liquid cells.  Symmetric, positive
+ *            definite wherever a region touches air.
+ *   solve    Jacobi-preconditioned conjugate gradients from p = 0 in the loop of the plain solve (two launches per iteration, every scalar
+ *            on the device, fixed-order partials, entries converge on their own, frozen entries untouched):
+ *      df_pressure_workspace_bytes_gf(B, Z, Y, X)   df_pressure_workspace_bytes, then diag [B,n] and z [B,n]
+ *      df_pressure_init*_gf           x = 0, r = b, diag, z = p = r / diag, the first r.z and max|r| partials
+ *      df_pressure_cg_direction*_gf   beta = r.z / (r.z)_old, p = z + beta * p_old, q = diag * p - sum over liquid neighbours, the p.q partials;
+ *                                     an entry stays active while max|r| > accuracy (the UNscaled residual) && r.z > 0 && iterations < max_iter
+ *      df_pressure_cg_update*_gf      alpha = r.z / p.q, x += alpha p, r -= alpha q, z = r / diag, the next partials
+ *      df_pressure_status             unchanged, on the same workspace pointer (its words lie where the plain solve keeps them)
+ *   correction  df_pressure_correct*_gf: component a of cell c with c and c - e_a interior: both liquid: out = vel - (p[c] - p[c - e_a]);
+ *            c alone liquid: out = vel - p[c] * (1 / theta); c - e_a alone liquid: out = vel + p[c - e_a] * (1 / theta), theta of the liquid
+ *            cell towards the air cell (the air side's pressure replaced by the ghost value p_i * (1 - 1 / theta)); neither liquid:
+ *            copied; every other face 0.  out may be vel.
+ * A flags byte is believed only where the cell is interior by its index; non-finite phi changes numbers, never addresses.
+ * Errors, on the host and before any launch: those of the blocks above, and DF_EINVAL for gf_clamp outside (0, 1], a smoothing mode
+ * outside 0..2, a negative band, a null phi, a smoothing output that overlaps its input (modes 1, 2), a workspace that overlaps phi;
+ * DF_EWORKSPACE for ws_bytes below df_pressure_workspace_bytes_gf. */
+int df_particle_levelset_averaged2d(const float* pos_sorted, const int32_t* cell_start, float* phi, int64_t B, int64_t N, int64_t Y,
+                                    int64_t X, float radius_factor, df_stream_t stream);
+int df_particle_levelset_averaged3d(const float* pos_sorted, const int32_t* cell_start, float* phi, int64_t B, int64_t N, int64_t Z,
+                                    int64_t Y, int64_t X, float radius_factor, df_stream_t stream);
+int df_levelset_smooth2d(const float* phi_in, float* phi_out, int64_t B, int64_t Y, int64_t X, int mode, int band, float bound_value,
+                         df_stream_t stream);
+int df_levelset_smooth3d(const float* phi_in, float* phi_out, int64_t B, int64_t Z, int64_t Y, int64_t X, int mode, int band,
+                         float bound_value, df_stream_t stream);
+int64_t df_pressure_workspace_bytes_gf(int64_t B, int64_t Z, int64_t Y, int64_t X);
+int df_pressure_init2d_gf(const float* vel, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, const float* phi, int64_t B,
+                          int64_t Y, int64_t X, int bnd, float gf_clamp, df_stream_t stream);
+int df_pressure_init3d_gf(const float* vel, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, const float* phi, int64_t B,
+                          int64_t Z, int64_t Y, int64_t X, int bnd, float gf_clamp, df_stream_t stream);
+int df_pressure_cg_direction2d_gf(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k,
+                                  float accuracy, int64_t max_iter, df_stream_t stream);
+int df_pressure_cg_direction3d_gf(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                                  int64_t k, float accuracy, int64_t max_iter, df_stream_t stream);
+int df_pressure_cg_update2d_gf(float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd,
+                               int64_t k, df_stream_t stream);
+int df_pressure_cg_update3d_gf(float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X,
+                               int bnd, int64_t k, df_stream_t stream);
+int df_pressure_correct2d_gf(const float* vel, const float* pressure, float* out, const uint8_t* flags, const float* phi, int64_t B, int64_t Y,
+                             int64_t X, int bnd, float gf_clamp, df_stream_t stream);
+int df_pressure_correct3d_gf(const float* vel, const float* pressure, float* out, const uint8_t* flags, const float* phi, int64_t B, int64_t Z,
+                             int64_t Y, int64_t X, int bnd, float gf_clamp, df_stream_t stream);
 
 #ifdef __cplusplus
 }
