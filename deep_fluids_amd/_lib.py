@@ -13,6 +13,7 @@ TUNING_LIB_PATH = os.path.join(_HERE, "csrc", "libdeepfluids_hip_tuning.so")    
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "deepfluids_hip.h")
 
 P, I64, I32, F32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
+U32 = ctypes.c_uint32
 
 # name -> (restype, argtypes)
 SIGNATURES = {
@@ -227,6 +228,20 @@ SIGNATURES = {
     "df_diffuse_cg_update3d": (I32, [P, I64, I64, I64, I64, I64, I32, I64, P]),
     "df_diffuse_finish2d": (I32, [P, I64, P, I64, I64, I64, I32, P]),
     "df_diffuse_finish3d": (I32, [P, I64, P, I64, I64, I64, I64, I32, P]),
+    "df_particles_advect2d_ragged": (I32, [P, P, P, P, I64, I64, I64, I64, F32, F32, I32, P]),
+    "df_particles_advect3d_ragged": (I32, [P, P, P, P, I64, I64, I64, I64, I64, F32, F32, I32, P]),
+    "df_particles_cell_keys2d_ragged": (I32, [P, P, P, I64, I64, I64, I64, P]),
+    "df_particles_cell_keys3d_ragged": (I32, [P, P, P, I64, I64, I64, I64, I64, P]),
+    "df_flip_update2d_ragged": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, F32, P]),
+    "df_flip_update3d_ragged": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, F32, P]),
+    "df_levelset_extrapolate_marks2d": (I32, [P, P, I64, I64, I64, I32, P]),
+    "df_levelset_extrapolate_marks3d": (I32, [P, P, I64, I64, I64, I64, I32, P]),
+    "df_levelset_extrapolate_layer2d": (I32, [P, P, I64, I64, I64, I32, I32, P]),
+    "df_levelset_extrapolate_layer3d": (I32, [P, P, I64, I64, I64, I64, I32, I32, P]),
+    "df_resample_count2d": (I32, [P, P, P, P, P, P, P, I64, I64, I64, I64, I32, I32, I32, F32, P]),
+    "df_resample_count3d": (I32, [P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I32, I32, I32, F32, P]),
+    "df_resample_scatter2d": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I32, U32, U32, P]),
+    "df_resample_scatter3d": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I32, U32, U32, P]),
 }
 
 DF_CONV_LRELU, DF_CONV_RESIDUAL, DF_CONV_MASK, DF_CONV_BIAS, DF_CONV_ADDUP, DF_CONV_VALU_ONLY = 1, 2, 4, 8, 16, 32

@@ -38,16 +38,25 @@ using dfpart::check_dims;
 using dfpart::kInt32Max;
 using dfpart::mac_sample;
 using dfpart::PartDims;
+using dfpart::ragged_entry;
 using dfpart::Rec;
 using dfst::kThreads;
 using dfst::xcd_block;
 
-template <int D>
+// RAGGED: the entry of a row is found in entry_start [nb + 1] instead of idx / N; an unused row is neither read nor written
+template <int D, bool RAGGED>
 __global__ __launch_bounds__(kThreads) void particles_advect_kernel(const float* pos_in, float* pos_out, const float* __restrict__ vel,
-                                                                    PartDims d) {
+                                                                    PartDims d, const int32_t* __restrict__ entry_start, int nb) {
   const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
   if (idx >= d.total) return;
-  const float* vb = vel + (idx / d.N) * d.ncell * D;
+  int64_t entry = 0;
+  if (RAGGED) {
+    entry = ragged_entry(entry_start, nb, idx);
+    if (entry < 0) return;
+  } else {
+    entry = idx / d.N;
+  }
+  const float* vb = vel + entry * d.ncell * D;
   const Rec<D> own = *reinterpret_cast<const Rec<D>*>(pos_in + idx * D);
   float k1[D], k2[D], k3[D], k4[D], q[D];
   mac_sample<D>(vb, own.v, d, k1);
@@ -78,13 +87,25 @@ __device__ __forceinline__ int cell_of(float p, int ext) {
   return i < ext - 1 ? i : ext - 1;
 }
 
-template <int D>
-__global__ __launch_bounds__(kThreads) void particles_keys_kernel(const float* __restrict__ pos, int32_t* __restrict__ keys, PartDims d) {
+// RAGGED: as above; an unused row gets the key nb * ncell, behind every cell, and its position is not read
+template <int D, bool RAGGED>
+__global__ __launch_bounds__(kThreads) void particles_keys_kernel(const float* __restrict__ pos, int32_t* __restrict__ keys, PartDims d,
+                                                                  const int32_t* __restrict__ entry_start, int nb) {
   const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
   if (idx >= d.total) return;
+  int64_t entry = 0;
+  if (RAGGED) {
+    entry = ragged_entry(entry_start, nb, idx);
+    if (entry < 0) {
+      keys[idx] = static_cast<int32_t>(nb * d.ncell);
+      return;
+    }
+  } else {
+    entry = idx / d.N;
+  }
   const Rec<D> p = *reinterpret_cast<const Rec<D>*>(pos + idx * D);
   const int i = cell_of(p.v[0], d.X), j = cell_of(p.v[1], d.Y), k = D == 3 ? cell_of(p.v[D - 1], d.Z) : 0;
-  keys[idx] = static_cast<int32_t>((idx / d.N) * d.ncell + ((static_cast<int64_t>(k) * d.Y + j) * d.X + i));
+  keys[idx] = static_cast<int32_t>(entry * d.ncell + ((static_cast<int64_t>(k) * d.Y + j) * d.X + i));
 }
 
 template <int D>
@@ -251,9 +272,10 @@ __global__ __launch_bounds__(kThreads) void levelset_smooth_kernel(const float* 
 }
 
 template <int D>
-int particles_advect(const char* fn, const float* pos_in, float* pos_out, const float* vel, int64_t B, int64_t N, int64_t Z, int64_t Y,
-                     int64_t X, float dt, float vel_scale, int bnd, df_stream_t stream) {
-  if (int e = check_dims(fn, D, B, N, Z, Y, X, false)) return e;
+int particles_advect(const char* fn, const float* pos_in, float* pos_out, const float* vel, const int32_t* entry_start, bool ragged, int64_t B,
+                     int64_t N, int64_t Z, int64_t Y, int64_t X, float dt, float vel_scale, int bnd, df_stream_t stream) {
+  if (int e = check_dims(fn, D, B, N, Z, Y, X, ragged)) return e;
+  if (int e = dfpart::check_ragged(fn, entry_start, ragged, N)) return e;
   DF_REQUIRE(bnd >= 0, DF_EINVAL, "%s: boundary width must be >= 0 (got %d)", fn, bnd);
   const int64_t need = 2 * static_cast<int64_t>(bnd) + 2;
   DF_REQUIRE(X >= need && Y >= need && (D == 2 || Z >= need), DF_ESHAPE, "%s: every extent must be >= 2*bnd + 2 = %lld", fn, (long long)need);
@@ -268,14 +290,17 @@ int particles_advect(const char* fn, const float* pos_in, float* pos_out, const 
   for (int a = 0; a < 3; ++a) d.hi[a] = static_cast<float>(ext[a] - bnd) - 0.0009765625f;
   d.dt = dt; d.half_dt = 0.5f * dt; d.vs = vel_scale;
   const unsigned nblk = static_cast<unsigned>(ceil_div(d.total, kThreads));
-  hipLaunchKernelGGL((particles_advect_kernel<D>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), pos_in, pos_out, vel, d);
+  hipStream_t s = df::as_stream(stream);
+  if (ragged) hipLaunchKernelGGL((particles_advect_kernel<D, true>), dim3(nblk), dim3(kThreads), 0, s, pos_in, pos_out, vel, d, entry_start, (int)B);
+  else hipLaunchKernelGGL((particles_advect_kernel<D, false>), dim3(nblk), dim3(kThreads), 0, s, pos_in, pos_out, vel, d, entry_start, 0);
   return df::launched(fn);
 }
 
 template <int D>
-int particles_keys(const char* fn, const float* pos, int32_t* keys, int64_t B, int64_t N, int64_t Z, int64_t Y, int64_t X,
-                   df_stream_t stream) {
+int particles_keys(const char* fn, const float* pos, int32_t* keys, const int32_t* entry_start, bool ragged, int64_t B, int64_t N, int64_t Z,
+                   int64_t Y, int64_t X, df_stream_t stream) {
   if (int e = check_dims(fn, D, B, N, Z, Y, X, true)) return e;
+  if (int e = dfpart::check_ragged(fn, entry_start, ragged, N)) return e;
   DF_REQUIRE(N == 0 || (pos && keys), DF_EINVAL, "%s: null %s", fn, !pos ? "input" : "output");
   DF_REQUIRE(aligned4(pos) && aligned4(keys), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
   if (N == 0) return DF_OK;
@@ -283,7 +308,9 @@ int particles_keys(const char* fn, const float* pos, int32_t* keys, int64_t B, i
   d.total = B * N; d.N = N; d.ncell = Z * Y * X;
   d.Z = (int)Z; d.Y = (int)Y; d.X = (int)X;
   const unsigned nblk = static_cast<unsigned>(ceil_div(d.total, kThreads));
-  hipLaunchKernelGGL((particles_keys_kernel<D>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), pos, keys, d);
+  hipStream_t s = df::as_stream(stream);
+  if (ragged) hipLaunchKernelGGL((particles_keys_kernel<D, true>), dim3(nblk), dim3(kThreads), 0, s, pos, keys, d, entry_start, (int)B);
+  else hipLaunchKernelGGL((particles_keys_kernel<D, false>), dim3(nblk), dim3(kThreads), 0, s, pos, keys, d, entry_start, 0);
   return df::launched(fn);
 }
 
@@ -350,20 +377,40 @@ extern "C" {
 
 int df_particles_advect2d(const float* pos_in, float* pos_out, const float* vel, int64_t B, int64_t N, int64_t Y, int64_t X, float dt,
                           float vel_scale, int bnd, df_stream_t stream) {
-  return particles_advect<2>("df_particles_advect2d", pos_in, pos_out, vel, B, N, 1, Y, X, dt, vel_scale, bnd, stream);
+  return particles_advect<2>("df_particles_advect2d", pos_in, pos_out, vel, nullptr, false, B, N, 1, Y, X, dt, vel_scale, bnd, stream);
 }
 
 int df_particles_advect3d(const float* pos_in, float* pos_out, const float* vel, int64_t B, int64_t N, int64_t Z, int64_t Y, int64_t X,
                           float dt, float vel_scale, int bnd, df_stream_t stream) {
-  return particles_advect<3>("df_particles_advect3d", pos_in, pos_out, vel, B, N, Z, Y, X, dt, vel_scale, bnd, stream);
+  return particles_advect<3>("df_particles_advect3d", pos_in, pos_out, vel, nullptr, false, B, N, Z, Y, X, dt, vel_scale, bnd, stream);
 }
 
 int df_particles_cell_keys2d(const float* pos, int32_t* keys, int64_t B, int64_t N, int64_t Y, int64_t X, df_stream_t stream) {
-  return particles_keys<2>("df_particles_cell_keys2d", pos, keys, B, N, 1, Y, X, stream);
+  return particles_keys<2>("df_particles_cell_keys2d", pos, keys, nullptr, false, B, N, 1, Y, X, stream);
 }
 
 int df_particles_cell_keys3d(const float* pos, int32_t* keys, int64_t B, int64_t N, int64_t Z, int64_t Y, int64_t X, df_stream_t stream) {
-  return particles_keys<3>("df_particles_cell_keys3d", pos, keys, B, N, Z, Y, X, stream);
+  return particles_keys<3>("df_particles_cell_keys3d", pos, keys, nullptr, false, B, N, Z, Y, X, stream);
+}
+
+int df_particles_advect2d_ragged(const float* pos_in, float* pos_out, const float* vel, const int32_t* entry_start, int64_t B, int64_t N,
+                                 int64_t Y, int64_t X, float dt, float vel_scale, int bnd, df_stream_t stream) {
+  return particles_advect<2>("df_particles_advect2d_ragged", pos_in, pos_out, vel, entry_start, true, B, N, 1, Y, X, dt, vel_scale, bnd, stream);
+}
+
+int df_particles_advect3d_ragged(const float* pos_in, float* pos_out, const float* vel, const int32_t* entry_start, int64_t B, int64_t N,
+                                 int64_t Z, int64_t Y, int64_t X, float dt, float vel_scale, int bnd, df_stream_t stream) {
+  return particles_advect<3>("df_particles_advect3d_ragged", pos_in, pos_out, vel, entry_start, true, B, N, Z, Y, X, dt, vel_scale, bnd, stream);
+}
+
+int df_particles_cell_keys2d_ragged(const float* pos, int32_t* keys, const int32_t* entry_start, int64_t B, int64_t N, int64_t Y, int64_t X,
+                                    df_stream_t stream) {
+  return particles_keys<2>("df_particles_cell_keys2d_ragged", pos, keys, entry_start, true, B, N, 1, Y, X, stream);
+}
+
+int df_particles_cell_keys3d_ragged(const float* pos, int32_t* keys, const int32_t* entry_start, int64_t B, int64_t N, int64_t Z, int64_t Y,
+                                    int64_t X, df_stream_t stream) {
+  return particles_keys<3>("df_particles_cell_keys3d_ragged", pos, keys, entry_start, true, B, N, Z, Y, X, stream);
 }
 
 int df_particles_gather(const float* pos, const int64_t* order, float* pos_sorted, int64_t n, int dim, df_stream_t stream) {

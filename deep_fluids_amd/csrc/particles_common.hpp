@@ -71,6 +71,27 @@ __device__ __forceinline__ void mac_sample(const float* __restrict__ vel, const 
   }
 }
 
+// The entry of row idx of a ragged batch (the header's "ragged particle batches"): rows start[b] .. start[b+1] - 1 belong to entry b, so
+// the entry is (the number of b in 0..B with start[b] <= idx) - 1, found by bisection over the B + 1 non-decreasing starts.  -1: the
+// row is unused (idx >= start[B], or < start[0]).  Whatever the starts hold, the result lies in [-1, B - 1]: it selects a velocity
+// grid, never memory outside the arrays.
+__device__ __forceinline__ int ragged_entry(const int32_t* __restrict__ start, int B, int64_t idx) {
+  int lo = 0, hi = B + 1;                                   // the count lies in [lo, hi]
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;                         // < B + 1
+    if (static_cast<int64_t>(start[mid]) <= idx) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo == B + 1 ? -1 : lo - 1;
+}
+
+// The integer mix of the lattice noise (the header's noise inflow block), keyed by four words; uint32 arithmetic mod 2^32.
+__device__ __forceinline__ uint32_t mix4(uint32_t seed, uint32_t a, uint32_t b, uint32_t c) {
+  uint32_t h = seed ^ (a * 0x8DA6B343u) ^ (b * 0xD8163841u) ^ (c * 0xCB1AB31Fu);
+  h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
+  return h;
+}
+
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 constexpr int64_t kInt32Max = 2147483647ll;
@@ -84,6 +105,14 @@ inline int check_dims(const char* fn, int dim, int64_t B, int64_t N, int64_t Z, 
   const int64_t ncell = Z * Y * X;
   if (keyed) DF_REQUIRE(ncell <= kInt32Max / B, DF_ESHAPE, "%s: B*Z*Y*X = %lld cells: the cell keys do not fit an int32", fn, (long long)(B * ncell));
   else DF_REQUIRE(df::ceil_div(B * ncell, dfst::kThreads) < (1ll << 31), DF_ESHAPE, "%s: extent too large", fn);
+  return DF_OK;
+}
+
+// the entry_start argument of a ragged entry point ([B + 1] int32 in device memory; read by the kernels, never by the host)
+inline int check_ragged(const char* fn, const int32_t* entry_start, bool ragged, int64_t N) {
+  if (!ragged) return DF_OK;
+  DF_REQUIRE(entry_start || N == 0, DF_EINVAL, "%s: null entry_start", fn);
+  DF_REQUIRE(aligned4(entry_start), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
   return DF_OK;
 }
 

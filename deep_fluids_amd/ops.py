@@ -34,6 +34,7 @@ __all__ = [
     "advect_velocity", "wall_buoyancy", "solve_pressure", "pressure_workspace", "smoke_step", "simulate_smoke", "default_buoyancy_force", "default_max_iter", "obstacle_flags", "ObstacleFlags",
     "open_sides", "SphereSource",
     "advect_particles", "particle_cells", "particle_levelset", "particle_levelset_averaged", "liquid_sequence", "seed_particles", "box_levelset", "sphere_levelset",
+    "pack_particles", "unpack_particles", "extrapolate_levelset", "resample_particles", "Resample",
     "variable_scope", "get_variables", "get_variable", "reset_variables", "set_random_seed", "all_variables",
 ]
 
@@ -2510,12 +2511,77 @@ def _grid_shape(shape, nd, who):
     return shape
 
 
-def advect_particles(pos, vel, dt, bnd=1, vel_scale=1.0, out=None):
+def _ragged_arg(pos, entry_start, who):
+    """``(pos viewed [B,N,D], entry_start)`` of a ragged batch ``pos`` [P,D], ``entry_start`` [B+1] int32 -- checked before anything
+    asks where the tensors live, so a bad argument is refused without a GPU"""
+    if not isinstance(entry_start, torch.Tensor) or entry_start.dtype != torch.int32 or entry_start.dim() != 1 or entry_start.numel() < 2:
+        raise ValueError("%s: entry_start must be an int32 tensor [B+1], got %s" %
+                         (who, "%s %s" % (entry_start.dtype, tuple(entry_start.shape)) if isinstance(entry_start, torch.Tensor) else type(entry_start)))
+    if not isinstance(pos, torch.Tensor) or pos.dim() != 2 or pos.shape[-1] not in (2, 3):
+        raise ValueError("%s: a ragged batch holds its particles as [P,2|3], got %s" % (who, tuple(pos.shape) if isinstance(pos, torch.Tensor) else type(pos)))
+    B = entry_start.numel() - 1
+    if pos.shape[0] % B:
+        raise ValueError("%s: P = %d rows are not a multiple of B = %d (entry_start has %d elements)" % (who, pos.shape[0], B, B + 1))
+    if not pos.is_cuda or not entry_start.is_cuda or entry_start.device != pos.device or not entry_start.is_contiguous():
+        raise _lib.DeepFluidsHipError("%s: pos and entry_start must be contiguous tensors on the same GPU" % who)
+    return _prep(pos.detach(), "pos").view(B, pos.shape[0] // B, pos.shape[1]), entry_start
+
+
+def pack_particles(parts, capacity=None):
+    """A ragged particle batch from a list of B tensors [N_b,D] (float32, on the GPU): ``(pos [P,D], entry_start [B+1] int32)`` with
+    entry b in rows ``entry_start[b] .. entry_start[b+1] - 1`` and the rows from ``entry_start[B]`` on unused (zeros here; they hold no
+    meaning).  ``capacity``: P, at least the total and a multiple of B; by default the total rounded up to a multiple of B."""
+    parts = list(parts)
+    B = len(parts)
+    if B < 1:
+        raise ValueError("pack_particles: no entries")
+    nd = parts[0].shape[-1] if isinstance(parts[0], torch.Tensor) and parts[0].dim() == 2 else 0
+    for t in parts:
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[-1] != nd or nd not in (2, 3) or t.dtype != torch.float32:
+            raise ValueError("pack_particles expects float32 tensors [N_b,2|3] of one D")
+    counts = [int(t.shape[0]) for t in parts]
+    total = sum(counts)
+    P = -(-total // B) * B if capacity is None else int(capacity)
+    if P < total or P % B:
+        raise ValueError("pack_particles: capacity %d must be a multiple of B = %d and hold the %d particles" % (P, B, total))
+    pos = torch.zeros((P, nd), dtype=torch.float32, device=parts[0].device)
+    if total:
+        pos[:total] = torch.cat(parts, dim=0)
+    es = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)).to(parts[0].device)
+    return pos, es
+
+
+def unpack_particles(pos, entry_start):
+    """The list of B tensors [N_b,D] (views of ``pos`` [P,D]) of a ragged batch; reads ``entry_start`` on the host."""
+    if not isinstance(entry_start, torch.Tensor) or entry_start.dtype != torch.int32 or entry_start.dim() != 1 or entry_start.numel() < 2:
+        raise ValueError("unpack_particles: entry_start must be an int32 tensor [B+1]")
+    if not isinstance(pos, torch.Tensor) or pos.dim() != 2:
+        raise ValueError("unpack_particles: a ragged batch holds its particles as [P,D]")
+    es = [int(x) for x in entry_start.cpu().numpy()]
+    if es[0] < 0 or es[-1] > pos.shape[0] or any(b < a for a, b in zip(es, es[1:])):
+        raise ValueError("unpack_particles: entry_start %s does not describe %d rows" % (es, pos.shape[0]))
+    return [pos[a:b] for a, b in zip(es, es[1:])]
+
+
+def advect_particles(pos, vel, dt, bnd=1, vel_scale=1.0, out=None, entry_start=None):
     """One RK4 trace of the particles ``pos`` [B,N,D] (cell units, xyz order) through ``vel`` [B,(Z,)Y,X,D] (MAC face values, times
     ``vel_scale``), then clamped to [bnd, extent - bnd - 2^-10] per axis -- modelled on mantaflow's ``pp.advectInGrid(IntRK4,
     deleteInObstacle=False)`` (scene/liquid3_vis.py:134), NOT bit-identical to it; include/deepfluids_hip.h holds the definition that
-    is tested.  Returns the new positions (``out`` if given; it may be ``pos`` itself)."""
+    is tested.  Returns the new positions (``out`` if given; it may be ``pos`` itself).
+    ``entry_start`` [B+1] int32 (``pack_particles``): ``pos`` is a ragged batch [P,D]; unused rows are neither read nor written."""
     with torch.no_grad():
+        if entry_start is not None:
+            p, es = _ragged_arg(pos, entry_start, "advect_particles")
+            v = _liquid_vel(vel, p.shape[0], p.shape[-1], "advect_particles")
+            if int(bnd) != bnd or bnd < 0:
+                raise ValueError("advect_particles: bnd must be an integer >= 0, got %r" % (bnd,))
+            if out is None:
+                out = torch.empty_like(pos)
+            elif tuple(out.shape) != tuple(pos.shape) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+                raise ValueError("advect_particles: out must be a contiguous float32 GPU tensor of the positions' shape")
+            call("df_particles_advect%dd_ragged" % p.shape[-1], _ptr(p), _ptr(out), _ptr(v), _ptr(es), p.shape[0], p.shape[1],
+                 *(list(v.shape[1:-1]) + [float(dt), float(vel_scale), int(bnd), _stream()]))
+            return out
         p = _particle_pos(pos, "advect_particles")
         v = _prep(vel.detach(), "vel")
         B, N, nd = p.shape
@@ -2532,20 +2598,29 @@ def advect_particles(pos, vel, dt, bnd=1, vel_scale=1.0, out=None):
         return out
 
 
-def particle_cells(pos, shape):
+def particle_cells(pos, shape, entry_start=None):
     """The cell index of mantaflow's ``gridParticleIndex``: ``(sorted_pos [B,N,D], cell_start [B*ncell + 1] int32, order [B*N] int64)``
     for positions ``pos`` [B,N,D] on a grid ``shape`` [(Z,)Y,X].  Keys (batch entry, cell) come from a HIP kernel, the stable sort and
     the ranges from torch, the permutation of the positions from a HIP kernel again: ``sorted_pos.view(-1, D) == pos.view(-1, D)[order]``
-    and the particles of key c are rows ``cell_start[c] .. cell_start[c+1] - 1``, in their original index order."""
+    and the particles of key c are rows ``cell_start[c] .. cell_start[c+1] - 1``, in their original index order.
+    ``entry_start`` [B+1] int32: ``pos`` is a ragged batch [P,D] (and so is ``sorted_pos``).  Unused rows get the key B*ncell and sort
+    behind every cell; the stable sort keeps the entries contiguous and in order, so ``entry_start`` describes ``sorted_pos`` too, and
+    ``cell_start[-1]`` is the live total."""
     with torch.no_grad():
-        p = _particle_pos(pos, "particle_cells")
+        if entry_start is not None:
+            p, es = _ragged_arg(pos, entry_start, "particle_cells")
+        else:
+            p = _particle_pos(pos, "particle_cells")
         B, N, nd = p.shape
         shape = _grid_shape(shape, nd, "particle_cells")
         ncell = int(np.prod(shape))
         keys = torch.empty((B * N,), dtype=torch.int32, device=p.device)
-        call("df_particles_cell_keys%dd" % nd, _ptr(p), _ptr(keys), B, N, *(list(shape) + [_stream()]))
+        if entry_start is not None:
+            call("df_particles_cell_keys%dd_ragged" % nd, _ptr(p), _ptr(keys), _ptr(es), B, N, *(list(shape) + [_stream()]))
+        else:
+            call("df_particles_cell_keys%dd" % nd, _ptr(p), _ptr(keys), B, N, *(list(shape) + [_stream()]))
         skeys, order = torch.sort(keys, stable=True)
-        spos = torch.empty_like(p)
+        spos = torch.empty_like(p if entry_start is None else pos)
         call("df_particles_gather", _ptr(p), _ptr(order), _ptr(spos), B * N, nd, _stream())
         edges = torch.arange(B * ncell + 1, dtype=torch.int32, device=p.device)
         cell_start = torch.searchsorted(skeys, edges, out_int32=True)
@@ -2588,7 +2663,8 @@ def _levelset_averaged(spos, cell_start, out, tmp, B, N, shape, radius_factor, s
     return out
 
 
-def particle_levelset_averaged(pos, shape, radius_factor=1.0, smooth=1, smooth_neg=1, bound_value=1.0, bnd=1, out=None, cells=None):
+def particle_levelset_averaged(pos, shape, radius_factor=1.0, smooth=1, smooth_neg=1, bound_value=1.0, bnd=1, out=None, cells=None,
+                               entry_start=None):
     """The averaged surface level set of the particles ``pos`` [B,N,D] on a grid ``shape`` -- modelled on mantaflow's
     ``averagedParticleLevelset(pp, pindex, flags, gpi, phi, radius_factor, smooth, smooth_neg)`` followed by ``phi.setBound(bound_value,
     bnd)`` (scene/liquid_pos_size.py:254-295), restated from memory and NOT bit-identical to it; include/deepfluids_hip.h holds the
@@ -2597,7 +2673,8 @@ def particle_levelset_averaged(pos, shape, radius_factor=1.0, smooth=1, smooth_n
     sum(w) > 1e-6, else R.  Then ``smooth`` passes of the (2D+1)-point average on every cell off the outermost layer, ``smooth_neg``
     passes of the same average kept only where it is smaller, and the ``bnd``-wide band set to ``bound_value`` (``bnd=0``: no band).
     ``cells=(sorted_pos, cell_start)`` of ``particle_cells`` reuses a sort already done (``pos`` is then only read for its shape).  The
-    sums run in ascending cell order and, inside a cell, in sorted order: deterministic, no atomics."""
+    sums run in ascending cell order and, inside a cell, in sorted order: deterministic, no atomics.
+    ``entry_start`` [B+1] int32: ``pos`` (and ``cells[0]``) is a ragged batch [P,D]; the kernels are driven by ``cell_start`` alone."""
     with torch.no_grad():
         smooth, smooth_neg = int(smooth), int(smooth_neg)
         if smooth < 0 or smooth_neg < 0:
@@ -2606,7 +2683,10 @@ def particle_levelset_averaged(pos, shape, radius_factor=1.0, smooth=1, smooth_n
             raise ValueError("particle_levelset_averaged: bnd must be an integer >= 0, got %r" % (bnd,))
         if not 0.0 <= radius_factor <= 1024.0:
             raise ValueError("particle_levelset_averaged: radius_factor must lie in [0, 1024], got %r" % (radius_factor,))
-        p = _particle_pos(pos, "particle_levelset_averaged")
+        if entry_start is not None:
+            p, _ = _ragged_arg(pos, entry_start, "particle_levelset_averaged")
+        else:
+            p = _particle_pos(pos, "particle_levelset_averaged")
         B, N, nd = p.shape
         shape = _grid_shape(shape, nd, "particle_levelset_averaged")
         if out is None:
@@ -2614,10 +2694,11 @@ def particle_levelset_averaged(pos, shape, radius_factor=1.0, smooth=1, smooth_n
         elif tuple(out.shape) != (B,) + shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
             raise ValueError("particle_levelset_averaged: out must be a contiguous float32 GPU tensor %s" % ((B,) + shape,))
         if cells is None:
-            spos, cell_start, _ = particle_cells(p, shape)
+            spos, cell_start, _ = particle_cells(pos if entry_start is not None else p, shape, entry_start=entry_start)
         else:
             spos, cell_start = cells
-            spos = _particle_pos(spos, "particle_levelset_averaged")
+            spos = _ragged_arg(spos, entry_start, "particle_levelset_averaged")[0] if entry_start is not None else \
+                _particle_pos(spos, "particle_levelset_averaged")
             if tuple(spos.shape) != tuple(p.shape):
                 raise ValueError("particle_levelset_averaged: cells hold positions %s for positions %s" % (tuple(spos.shape), tuple(p.shape)))
             if (cell_start.dtype != torch.int32 or not cell_start.is_cuda or not cell_start.is_contiguous()
@@ -3014,12 +3095,19 @@ def _diffuse(v, al, out, ws, nbytes, nd, dims, dims4, bnd, acc, max_iter, check_
     return out, iters.clone().reshape(B, nd)
 
 
-def flip_update(pos, pvel, vel, vel_old, flip_ratio=DEFAULT_FLIP_RATIO, out=None):
+def flip_update(pos, pvel, vel, vel_old, flip_ratio=DEFAULT_FLIP_RATIO, out=None, entry_start=None):
     """mantaflow's ``flipVelocityUpdate``: with ``u(.)`` the MAC sample of ``advect_particles``, ``un = u(vel, p)``,
-    ``d = un - u(vel_old, p)``, ``pvel = flip_ratio * (pvel + d) + (1 - flip_ratio) * un``.  ``out`` may be ``pvel``."""
+    ``d = un - u(vel_old, p)``, ``pvel = flip_ratio * (pvel + d) + (1 - flip_ratio) * un``.  ``out`` may be ``pvel``.
+    ``entry_start`` [B+1] int32: ``pos``, ``pvel`` are a ragged batch [P,D]; unused rows are neither read nor written."""
     with torch.no_grad():
-        p = _particle_pos(pos, "flip_update")
-        u = _particle_pos(pvel, "flip_update")
+        if entry_start is not None:
+            p, es = _ragged_arg(pos, entry_start, "flip_update")
+            if not isinstance(pvel, torch.Tensor) or tuple(pvel.shape) != tuple(pos.shape):
+                raise ValueError("flip_update: velocities %s for positions %s" % (tuple(getattr(pvel, "shape", ())), tuple(pos.shape)))
+            u = _prep(pvel.detach(), "pvel").view(p.shape)
+        else:
+            p = _particle_pos(pos, "flip_update")
+            u = _particle_pos(pvel, "flip_update")
         B, N, nd = p.shape
         if tuple(u.shape) != tuple(p.shape):
             raise ValueError("flip_update: velocities %s for positions %s" % (tuple(u.shape), tuple(p.shape)))
@@ -3030,19 +3118,135 @@ def flip_update(pos, pvel, vel, vel_old, flip_ratio=DEFAULT_FLIP_RATIO, out=None
         if not 0.0 <= flip_ratio <= 1.0:
             raise ValueError("flip_update: flip_ratio must lie in [0, 1], got %r" % (flip_ratio,))
         if out is None:
-            out = torch.empty_like(u)
-        elif tuple(out.shape) != tuple(u.shape) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+            out = torch.empty_like(pvel if entry_start is not None else u)
+        elif tuple(out.shape) != tuple(pvel.shape if entry_start is not None else u.shape) or out.dtype != torch.float32 or not out.is_cuda \
+                or not out.is_contiguous():
             raise ValueError("flip_update: out must be a contiguous float32 GPU tensor of the velocities' shape")
+        if entry_start is not None:
+            call("df_flip_update%dd_ragged" % nd, _ptr(p), _ptr(u), _ptr(out), _ptr(v), _ptr(vo), _ptr(es), B, N,
+                 *(list(v.shape[1:-1]) + [float(flip_ratio), _stream()]))
+            return out
         call("df_flip_update%dd" % nd, _ptr(p), _ptr(u), _ptr(out), _ptr(v), _ptr(vo), B, N, *(list(v.shape[1:-1]) + [float(flip_ratio), _stream()]))
         return out
 
 
-def sample_velocity(vel, pos):
+def sample_velocity(vel, pos, entry_start=None):
     """``u(vel, p)`` at the particles (mantaflow's ``mapGridToPartsVec3`` of a MAC grid): the FLIP update with ratio 0 from zero particle
-    velocities, which is ``0 * (0 + 0) + 1 * u`` -- the sample's own bits."""
+    velocities, which is ``0 * (0 + 0) + 1 * u`` -- the sample's own bits.  ``entry_start``: ``pos`` is a ragged batch [P,D]; unused
+    rows come back 0."""
     with torch.no_grad():
+        if entry_start is not None:
+            _ragged_arg(pos, entry_start, "sample_velocity")
+            return flip_update(pos, torch.zeros_like(pos), vel, vel, flip_ratio=0.0, out=torch.zeros_like(pos), entry_start=entry_start)
         p = _particle_pos(pos, "sample_velocity")
         return flip_update(p, torch.zeros_like(p), vel, vel, flip_ratio=0.0)
+
+
+def extrapolate_levelset(phi, distance=4, inside=True, out=None):
+    """mantaflow's ``extrapolateLsSimple(phi, distance, inside)``, restated from memory; the definition that is tested is the one in
+    include/deepfluids_hip.h (tests/liquid_resample_ref.py), NOT mantaflow.  Over the cells off the outermost layer of ``phi``
+    [B,(Z,)Y,X]: mark 1 where phi > 0 (``inside``) or phi < 0, mark 2 on unmarked cells with a face neighbour marked 1, and for d = 2 ..
+    ``distance`` an unmarked cell with n > 0 face neighbours marked d takes mark d + 1 and phi = (their sum, x-, x+, y-, y+[, z-, z+]) / n
+    - 1 (``inside``) or + 1.  Cells never reached and the outermost layer keep their bits; ``distance <= 1`` returns the input's bits.
+    One launch for the marks and one per layer, in place on the result.  ``out`` may be ``phi``.  With ``inside`` this makes phi
+    decrease with depth below the surface, which ``resample_particles`` relies on."""
+    with torch.no_grad():
+        distance = int(distance)
+        if not 0 <= distance <= 254:
+            raise ValueError("extrapolate_levelset: distance must be in 0..254, got %r" % (distance,))
+        if not isinstance(phi, torch.Tensor) or phi.dim() not in (3, 4):
+            raise ValueError("extrapolate_levelset expects phi [B,(Z,)Y,X], got %s" % (tuple(phi.shape) if isinstance(phi, torch.Tensor) else type(phi),))
+        ph = _prep(phi.detach(), "phi")
+        nd = ph.dim() - 1
+        if out is None:
+            out = ph.clone()
+        else:
+            if tuple(out.shape) != tuple(ph.shape) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+                raise ValueError("extrapolate_levelset: out must be a contiguous float32 GPU tensor of phi's shape")
+            if out.data_ptr() != ph.data_ptr():
+                out.copy_(ph)
+        if distance <= 1:
+            return out
+        dims = list(ph.shape)
+        mark = _u8(tuple(ph.shape), ph)
+        call("df_levelset_extrapolate_marks%dd" % nd, _ptr(out), _ptr(mark), *(dims + [1 if inside else 0, _stream()]))
+        for d in range(2, distance + 1):
+            call("df_levelset_extrapolate_layer%dd" % nd, _ptr(out), _ptr(mark), *(dims + [1 if inside else 0, d, _stream()]))
+        return out
+
+
+def _resample_launch(sp, su, cell_start, ph, fl, v, B, N, shape, bnd, min_particles, max_particles, radius_factor, seed, step):
+    """the launches of ``resample_particles`` on checked arguments: ``(pos, pvel, entry_start, cell_start, keep, kept, seeds)``; the
+    wanted total is ``cell_start[-1]``, still on the device"""
+    nd = len(shape)
+    ncell = int(np.prod(shape))
+    keep = torch.zeros((B * N,), dtype=torch.uint8, device=v.device)
+    counts = torch.empty((2, B * ncell), dtype=torch.int32, device=v.device)
+    kept, seeds = counts[0], counts[1]
+    call("df_resample_count%dd" % nd, _ptr(sp), _ptr(cell_start), _ptr(ph), _ptr(fl), _ptr(keep), _ptr(kept), _ptr(seeds), B, N,
+         *(list(shape) + [bnd, min_particles, max_particles, float(radius_factor), _stream()]))
+    new_start = torch.zeros((B * ncell + 1,), dtype=torch.int32, device=v.device)
+    torch.cumsum(kept + seeds, 0, dtype=torch.int32, out=new_start[1:])
+    pos_out, pvel_out = torch.empty_like(sp), torch.empty_like(su)
+    call("df_resample_scatter%dd" % nd, _ptr(sp), _ptr(su), _ptr(cell_start), _ptr(keep), _ptr(seeds), _ptr(new_start), _ptr(v), _ptr(pos_out),
+         _ptr(pvel_out), B, N, *(list(shape) + [min_particles, int(seed) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF, _stream()]))
+    return pos_out, pvel_out, new_start[::ncell].contiguous(), new_start, keep, kept, seeds
+
+
+def _resample_counts_arg(min_particles, max_particles, who):
+    min_particles = int(min_particles)
+    max_particles = 2 * min_particles if max_particles is None else int(max_particles)
+    if not 1 <= min_particles <= 4096:
+        raise ValueError("%s: min_particles must be in 1..4096, got %r" % (who, min_particles))
+    if max_particles < min_particles or max_particles > 8192:
+        raise ValueError("%s: max_particles must be in min_particles..8192 (max < min is refused), got %r for min_particles %r" %
+                         (who, max_particles, min_particles))
+    return min_particles, max_particles
+
+
+def resample_particles(spos, spvel, cell_start, entry_start, phi, flags, vel, min_particles, max_particles=None, radius_factor=1.0, seed=123,
+                       step=0, bnd=1, details=False):
+    """mantaflow's ``adjustNumber(pp, vel, flags, minParticles, maxParticles, phi, radiusFactor)`` after ``pVel.setSource(vel,
+    isMAC=True)``, restated from memory; the definition that is tested is the one in include/deepfluids_hip.h
+    (tests/liquid_resample_ref.py), NOT mantaflow.  On a SORTED ragged batch (``particle_cells(.., entry_start=)``; ``spvel`` permuted
+    alike) with ``phi`` the extrapolated level set (``extrapolate_levelset``), ``flags`` of ``liquid_flags`` and the MAC velocity ``vel``:
+    a particle is dropped where the interpolated phi is > 0, or where its cell already kept more than ``max_particles`` (default ``2 *
+    min_particles``) and it is not at the surface (phi <= -2R, R the level sets' radius); a liquid cell below the surface with fewer
+    than ``min_particles`` kept is filled up with seeds at hashed positions (``seed``, ``step``) strictly inside the cell, carrying
+    ``u(vel, p)``.  Returns ``(pos [P,D], pvel [P,D], entry_start [B+1], cell_start [B*ncell+1])``, again sorted by cell; rows from
+    ``entry_start[B]`` on are unused.  Raises when the result needs more than P rows, naming the capacity needed (nothing is written
+    past row P - 1; this reads one word back from the device).  ``details``: also ``(keep [P] uint8, kept, seeds [B*ncell] int32)``."""
+    with torch.no_grad():
+        min_particles, max_particles = _resample_counts_arg(min_particles, max_particles, "resample_particles")
+        if not 0.0 <= radius_factor <= 1024.0:
+            raise ValueError("resample_particles: radius_factor must lie in [0, 1024], got %r" % (radius_factor,))
+        bnd = _liquid_bnd(bnd, "resample_particles")
+        p, es = _ragged_arg(spos, entry_start, "resample_particles")
+        if not isinstance(spvel, torch.Tensor) or tuple(spvel.shape) != tuple(spos.shape):
+            raise ValueError("resample_particles: velocities %s for positions %s" % (tuple(getattr(spvel, "shape", ())), tuple(spos.shape)))
+        u = _prep(spvel.detach(), "spvel")
+        B, N, nd = p.shape
+        v = _liquid_vel(vel, B, nd, "resample_particles")
+        shape = tuple(v.shape[1:-1])
+        ph = _gf_phi_arg(phi, v, "resample_particles")
+        fl = _liquid_flags_arg(flags, v, "resample_particles")
+        ncell = int(np.prod(shape))
+        if cell_start.dtype != torch.int32 or not cell_start.is_cuda or not cell_start.is_contiguous() or cell_start.numel() != B * ncell + 1:
+            raise ValueError("resample_particles: cell_start must be the int32 GPU tensor [B*ncell + 1] of particle_cells")
+        pos_out, pvel_out, new_es, new_start, keep, kept, seeds = _resample_launch(
+            p.view(-1, nd), u, cell_start, ph, fl, v, B, N, shape, bnd, min_particles, max_particles, radius_factor, seed, step)
+        _resample_check(new_start, B * N, B, "resample_particles")
+        if details:
+            return pos_out, pvel_out, new_es, new_start, (keep, kept, seeds)
+        return pos_out, pvel_out, new_es, new_start
+
+
+def _resample_check(new_start, P, B, who):
+    """refuse a resampled state that did not fit: ``new_start[-1]`` is the total the scan wanted"""
+    total = _read_word(new_start[-1:])
+    if total > P:
+        raise _lib.DeepFluidsHipError("%s: the resampled batch holds %d particles but the storage has P = %d rows; it needs a capacity of at "
+                                      "least %d (a multiple of B = %d)" % (who, total, P, -(-total // B) * B, B))
 
 
 def _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws, visc=None, gf=None):
@@ -3084,6 +3288,103 @@ def _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_
     return spos, su, vel, iters
 
 
+class Resample(object):
+    """The settings of ``resample=`` on ``liquid_step`` / ``simulate_liquid``: ``min_particles`` per deep liquid cell, ``max_particles``
+    (None: ``2 * min_particles``, as the scripts call adjustNumber), the ``seed`` of the seed positions' hash, and the ``capacity`` P of the
+    ragged storage (None: twice the initial live total, rounded up to a multiple of B).  ``step`` is the counter fed to the hash; every
+    step taken with this object advances it by one, so chained ``liquid_step`` calls and ``simulate_liquid`` seed alike."""
+
+    def __init__(self, min_particles, max_particles=None, seed=123, capacity=None, step=0):
+        self.min_particles, self.max_particles = _resample_counts_arg(min_particles, max_particles, "Resample")
+        self.seed, self.step = int(seed), int(step)
+        if capacity is not None and (int(capacity) != capacity or capacity < 1):
+            raise ValueError("Resample: capacity must be a positive integer, got %r" % (capacity,))
+        self.capacity = None if capacity is None else int(capacity)
+
+
+def _resample_arg(resample, who):
+    if resample is not None and not isinstance(resample, Resample):
+        raise ValueError("%s: resample must be None or an ops.Resample, got %r" % (who, type(resample)))
+    return resample
+
+
+def _ragged_state(pos, pvel, vel, entry_start, rs, who):
+    """the ragged state ``(pos [P,D], pvel [P,D], entry_start, vel)`` a step with ``resample`` runs on: a dense [B,N,D] input is packed
+    (entry b in rows b*N ..), a ragged one is moved into storage of ``rs.capacity`` rows if it has another size"""
+    if entry_start is None:
+        p, u, v = _liquid_state(pos, pvel, vel, who)
+        B, N, nd = p.shape
+        live = B * N
+        es = torch.arange(B + 1, dtype=torch.int32, device=p.device) * N
+        p, u = p.reshape(-1, nd), u.reshape(-1, nd)
+    else:
+        p3, es = _ragged_arg(pos, entry_start, who)
+        if not isinstance(pvel, torch.Tensor) or tuple(pvel.shape) != tuple(pos.shape):
+            raise ValueError("%s: particle velocities %s for positions %s" % (who, tuple(getattr(pvel, "shape", ())), tuple(pos.shape)))
+        B, nd = p3.shape[0], p3.shape[-1]
+        p, u = p3.view(-1, nd), _prep(pvel.detach(), "pvel")
+        v = _liquid_vel(vel, B, nd, who)
+        live = None
+    P = rs.capacity
+    if P is None:
+        if live is None:
+            P = p.shape[0]                                   # a ragged state already has its storage
+        else:
+            P = -(-2 * live // B) * B
+    if P % B:
+        raise ValueError("%s: the capacity %d is not a multiple of B = %d" % (who, P, B))
+    if P != p.shape[0]:
+        if live is None:
+            live = _read_word(es[-1:])
+        if P < live:
+            raise ValueError("%s: the capacity %d does not hold the %d particles" % (who, P, live))
+        np_, nu = torch.zeros((P, nd), dtype=torch.float32, device=p.device), torch.zeros((P, nd), dtype=torch.float32, device=p.device)
+        np_[:live], nu[:live] = p[:live], u[:live]
+        p, u = np_, nu
+    return p, u, es, v
+
+
+def _liquid_step_resample(p, u, es, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws, visc, gf, rs, radius_factor, phis, step):
+    """``_liquid_step`` on a ragged state with the script's extrapolateLsSimple and adjustNumber: ``phis`` two phi buffers, ``gf`` as in
+    ``_liquid_step`` (only its clamp is read: phi is computed whenever the step resamples); returns (pos, pvel, vel, iters[, diters],
+    entry_start, cell_start).  The wanted total is ``cell_start[-1]``, still on the device: the caller checks it."""
+    nd = p.shape[-1]
+    shape = tuple(v.shape[1:-1])
+    B = es.numel() - 1
+    N = p.shape[0] // B
+    moved = advect_particles(p, v, dt, bnd=bnd, entry_start=es)
+    spos, cell_start, order = particle_cells(moved, shape, entry_start=es)
+    su = torch.empty_like(u)
+    call("df_particles_gather", _ptr(u), _ptr(order), _ptr(su), B * N, nd, _stream())
+    vel, weight, known = particles_to_grid(spos.view(B, N, nd), su.view(B, N, nd), cell_start, shape)
+    vel_old = vel
+    vel, _ = extrapolate_mac(vel, known, 2, bnd=bnd)
+    flags, touch = liquid_flags(cell_start, shape, B, N, bnd=bnd)
+    phi = _levelset_averaged(spos, cell_start, phis[0], phis[1], B, N, shape, radius_factor, 1, 1, 1.0, bnd)
+    extrapolate_levelset(phi, 4, True, out=phi)
+    diters = None
+    if visc is not None:
+        liquid_forces(vel, flags, (0.0,) * nd, bnd=bnd, out=vel)
+        dims, dims4 = _pressure_dims(vel, nd)
+        _, diters = _diffuse(vel, visc[0], vel, visc[1], visc[1].numel() * 4, nd, dims, dims4, bnd, float(accuracy),
+                             default_diffusion_max_iter(shape), DEFAULT_CHECK_EVERY if check_every is None else int(check_every))
+    liquid_forces(vel, flags, force, bnd=bnd, out=vel)
+    if gf is None:
+        _, _, iters = solve_pressure_liquid(vel, flags, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=vel, workspace=pws)
+    else:
+        _, _, iters = solve_pressure_liquid(vel, flags, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=vel,
+                                            workspace=pws, phi=phi, gf_clamp=gf[1])
+    # pVel.setSource(vel, isMAC=True) + adjustNumber against the projected velocity, then extrapolateMACSimple and the FLIP update on
+    # old and new particles alike
+    npos, npvel, nes, ncs = _resample_launch(spos, su, cell_start, phi, flags, vel, B, N, shape, bnd, rs.min_particles, rs.max_particles,
+                                             radius_factor, rs.seed, step)[:4]
+    vel, _ = extrapolate_mac(vel, touch, 4, bnd=bnd)
+    flip_update(npos, npvel, vel, vel_old, flip_ratio=flip_ratio, out=npvel, entry_start=nes)
+    if diters is not None:
+        return npos, npvel, vel, iters, diters, nes, ncs
+    return npos, npvel, vel, iters, nes, ncs
+
+
 def _liquid_state(pos, pvel, vel, who):
     p = _particle_pos(pos, who)
     u = _particle_pos(pvel, who)
@@ -3112,7 +3413,7 @@ def _ghost_fluid_arg(ghost_fluid, radius_factor, gf_clamp, v, who):
 
 
 def liquid_step(pos, pvel, vel, dt, force=None, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, flip_ratio=DEFAULT_FLIP_RATIO,
-                open_bound=False, viscosity_alpha=None, ghost_fluid=False, radius_factor=1.0, gf_clamp=1e-4):
+                open_bound=False, viscosity_alpha=None, ghost_fluid=False, radius_factor=1.0, gf_clamp=1e-4, resample=None, entry_start=None):
     """One frame of the reference's liquid scenes (scene/liquid_pos_size.py:254-295) on particles ``pos``, ``pvel`` [B,N,D] and the MAC
     velocity ``vel`` [B,(Z,)Y,X,D], in the script's order: trace the particles through ``vel`` (RK4), sort them by cell, map their
     velocities to the grid, extrapolate 2 layers from the faces that received weight, mark the liquid cells, add gravity (``force``,
@@ -3120,7 +3421,7 @@ def liquid_step(pos, pvel, vel, dt, force=None, bnd=1, accuracy=1e-4, max_iter=N
     with p = 0 in the air cells, extrapolate 4 layers from the faces of liquid cells, update the particle velocities (FLIP,
     ``flip_ratio``).  Returns ``(pos, pvel, vel, iterations)``: the particles come back SORTED by cell, so the step permutes them
     (``pos`` and ``pvel`` alike); ``vel`` is the frame the script saves.  Left out, as named in include/deepfluids_hip.h:
-    adjustNumber, extrapolateLsSimple, open sides (``open_bound=True`` is refused), obstacles, MIC(0).
+    adjustNumber and extrapolateLsSimple unless ``resample`` is set, open sides (``open_bound=True`` is refused), obstacles, MIC(0).
     ``ghost_fluid=True``: right after the liquid cells are marked, the averaged level set of the step's own sorted particles
     (``particle_levelset_averaged`` with ``radius_factor``, smooth 1, smooth_neg 1, the ``bnd`` band set to 1.0 -- the script's order) is
     computed and handed to the solve (``solve_pressure_liquid(phi=..., gf_clamp=...)``): the velocity is projected against a surface
@@ -3128,11 +3429,37 @@ def liquid_step(pos, pvel, vel, dt, force=None, bnd=1, accuracy=1e-4, max_iter=N
     ``viscosity_alpha`` (a number or B numbers, ``diffusion_alpha``): the viscous step of scene/liquid3_vis.py:256-296 -- after the
     liquid cells are marked the wall faces are zeroed (setWallBcs, a zero-force ``liquid_forces`` pass) and the velocity is diffused
     (``diffuse_velocity`` at the step's ``accuracy`` and its own default iteration cap), then gravity and the rest as above; the
-    result is then ``(pos, pvel, vel, iterations, diffusion_iterations [B, D])``.  With ``None`` nothing of this is launched."""
+    result is then ``(pos, pvel, vel, iterations, diffusion_iterations [B, D])``.  With ``None`` nothing of this is launched.
+    ``resample`` (an ``ops.Resample``): the step also runs the script's ``extrapolateLsSimple(phi, 4, inside=True)`` and ``pVel.setSource``
+    + ``adjustNumber``.  The state is then ragged: a dense [B,N,D] input is packed into storage of ``resample.capacity`` rows, or pass
+    ``pos``, ``pvel`` [P,D] with ``entry_start`` [B+1] as a step returned them.  Order: flags; the averaged level set (computed whenever
+    ``resample`` is set, shared with ``ghost_fluid``, which then sees the EXTRAPOLATED phi, as in the script); ``extrapolate_levelset``;
+    forces and the solve; ``resample_particles`` against the projected velocity (``resample.step`` feeds the hash and advances);
+    the 4-layer extrapolation; the FLIP update on old and new particles alike.  The result is ``(pos [P,D], pvel [P,D], vel,
+    iterations[, diffusion_iterations], entry_start)``; a state that does not fit the capacity raises before the step returns.  With
+    ``None`` nothing of this is launched and every result keeps its bits."""
     if open_bound:
         raise NotImplementedError("liquid_step: open sides (resetOutflow) are not implemented for the liquid solver")
     if ghost_fluid:
         _gf_clamp_arg(gf_clamp, "liquid_step")
+    rs = _resample_arg(resample, "liquid_step")
+    if rs is None and entry_start is not None:
+        raise ValueError("liquid_step: entry_start (a ragged state) needs resample=")
+    if rs is not None:
+        if not 0.0 <= radius_factor <= 1024.0:
+            raise ValueError("liquid_step: radius_factor must lie in [0, 1024], got %r" % (radius_factor,))
+        with torch.no_grad():
+            p, u, es, v = _ragged_state(pos, pvel, vel, entry_start, rs, "liquid_step")
+            bnd = _liquid_bnd(bnd, "liquid_step")
+            force = default_gravity_force(v.shape[1:-1], dt) if force is None else force
+            visc = _viscosity_arg(viscosity_alpha, v, "liquid_step")
+            gf = _ghost_fluid_arg(ghost_fluid, radius_factor, gf_clamp, v, "liquid_step")
+            phis = gf[2:] if gf is not None else (_empty(tuple(v.shape[:-1]), v), _empty(tuple(v.shape[:-1]), v))
+            out = _liquid_step_resample(p, u, es, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio,
+                                        pressure_workspace(v, gf is not None), visc, gf, rs, float(radius_factor), phis, rs.step)
+            rs.step += 1
+            _resample_check(out[-1], p.shape[0], es.numel() - 1, "liquid_step")
+            return out[:-1]
     with torch.no_grad():
         p, u, v = _liquid_state(pos, pvel, vel, "liquid_step")
         bnd = _liquid_bnd(bnd, "liquid_step")
@@ -3140,6 +3467,31 @@ def liquid_step(pos, pvel, vel, dt, force=None, bnd=1, accuracy=1e-4, max_iter=N
         visc = _viscosity_arg(viscosity_alpha, v, "liquid_step")
         gf = _ghost_fluid_arg(ghost_fluid, radius_factor, gf_clamp, v, "liquid_step")
         return _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pressure_workspace(v, gf is not None), visc, gf)
+
+
+def _liquid_frames_resample(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats, viscosity_alpha,
+                            keep_every, ghost_fluid, radius_factor, gf_clamp, rs, entry_start):
+    p, u, es, v = _ragged_state(pos0, pvel0, vel0, entry_start, rs, "simulate_liquid")
+    bnd = _liquid_bnd(bnd, "simulate_liquid")
+    force = default_gravity_force(v.shape[1:-1], dt) if force is None else force
+    gf = _ghost_fluid_arg(ghost_fluid, radius_factor, gf_clamp, v, "simulate_liquid")
+    phis = gf[2:] if gf is not None else (_empty(tuple(v.shape[:-1]), v), _empty(tuple(v.shape[:-1]), v))
+    pws = pressure_workspace(v, gf is not None)
+    visc = _viscosity_arg(viscosity_alpha, v, "simulate_liquid")
+    B = es.numel() - 1
+    for t in range(int(steps)):
+        out = _liquid_step_resample(p, u, es, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws, visc, gf, rs,
+                                    float(radius_factor), phis, rs.step)
+        rs.step += 1
+        p, u, v, iters, es = out[0], out[1], out[2], out[3], out[-2]
+        if stats is not None:
+            stats.append(iters)
+        if t % keep_every == 0 or t == int(steps) - 1:
+            # a state that did not fit is refused at every kept frame and after the last step; between them a step that follows an
+            # overflow reads clamped ranges only, and its result is never handed out
+            _resample_check(out[-1], p.shape[0], B, "simulate_liquid")
+        if t % keep_every == 0:
+            yield p, u, v, es
 
 
 def _liquid_frames(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats, viscosity_alpha=None,
@@ -3160,13 +3512,15 @@ def _liquid_frames(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter,
 
 def simulate_liquid(pos0, pvel0, vel0, steps, dt=0.5, force=None, bnd=1, accuracy=1e-4, max_iter=None, check_every=None,
                     flip_ratio=DEFAULT_FLIP_RATIO, stack=True, stats=None, open_bound=False, viscosity_alpha=None, keep_every=1,
-                    ghost_fluid=False, radius_factor=1.0, gf_clamp=1e-4):
+                    ghost_fluid=False, radius_factor=1.0, gf_clamp=1e-4, resample=None, entry_start=None):
     """``steps`` chained ``liquid_step`` frames from ``(pos0, pvel0, vel0)`` (left untouched).  With ``stack`` returns
     ``(pos, pvel, vels)``, ``vels`` [steps,B,(Z,)Y,X,D] the velocity after each step; without it a generator of ``(pos, pvel, vel)`` per
     step.  ``stats``: a list that receives the iteration counts [B] of every step's solve.  ``viscosity_alpha``: as in ``liquid_step``.
     ``keep_every=k``: only the steps 0, k, 2k, ... (0-based) are yielded or stacked (``vels`` [ceil(steps/k),...]; a scene whose frame
     is ``k`` solver steps) -- every step still runs and reports to ``stats``, and with ``stack`` the returned particles are those after
-    the LAST step.  ``ghost_fluid``, ``radius_factor``, ``gf_clamp``: as in ``liquid_step``."""
+    the LAST step.  ``ghost_fluid``, ``radius_factor``, ``gf_clamp``: as in ``liquid_step``.  ``resample`` (and ``entry_start`` for a
+    ragged start): as in ``liquid_step``; the state is ragged, the result is ``(pos [P,D], pvel [P,D], vels, entry_start)`` or a generator
+    of ``(pos, pvel, vel, entry_start)``, and a state that does not fit the capacity raises at the next kept frame at the latest."""
     if open_bound:
         raise NotImplementedError("simulate_liquid: open sides (resetOutflow) are not implemented for the liquid solver")
     keep_every = int(keep_every)
@@ -3174,6 +3528,23 @@ def simulate_liquid(pos0, pvel0, vel0, steps, dt=0.5, force=None, bnd=1, accurac
         raise ValueError("simulate_liquid: keep_every must be >= 1, got %r" % (keep_every,))
     if ghost_fluid:
         _gf_clamp_arg(gf_clamp, "simulate_liquid")
+    rs = _resample_arg(resample, "simulate_liquid")
+    if rs is None and entry_start is not None:
+        raise ValueError("simulate_liquid: entry_start (a ragged state) needs resample=")
+    if rs is not None:
+        if not 0.0 <= radius_factor <= 1024.0:
+            raise ValueError("simulate_liquid: radius_factor must lie in [0, 1024], got %r" % (radius_factor,))
+        with torch.no_grad():
+            gen = _liquid_frames_resample(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats,
+                                          viscosity_alpha, keep_every, ghost_fluid, radius_factor, gf_clamp, rs, entry_start)
+            if not stack:
+                return _no_grad_iter(gen)
+            kept = (int(steps) + keep_every - 1) // keep_every
+            vels = torch.empty((kept,) + tuple(vel0.shape), dtype=torch.float32, device=vel0.device)
+            p, u, es = pos0, pvel0, entry_start
+            for t, (p, u, v, es) in enumerate(gen):
+                vels[t].copy_(v)
+            return p, u, vels, es
     with torch.no_grad():
         gen = _liquid_frames(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats, viscosity_alpha,
                              keep_every, ghost_fluid, radius_factor, gf_clamp)

@@ -853,8 +853,8 @@ int df_wall_buoyancy3d_open_dev(const float* vel, const float* density, float* o
  * memory, and parity is with the NumPy restatement of THIS definition (tests/liquid_ref.py), NOT with mantaflow.
  * In this block p = 0 sits at the centres of the air cells, a first-order surface; the averaged level set, phi.setBound and the
  * ghost-fluid surface treatment (solvePressure(phi=)) are the opt-in block at the end of this header.
- * Left out: adjustNumber resampling (N is constant); extrapolateLsSimple; resetOutflow and open sides; obstacles inside the liquid; the
- * MIC(0) preconditioner; per-entry particle counts (one call, one N).
+ * Left out of this block: resetOutflow and open sides; obstacles inside the liquid; the MIC(0) preconditioner.  adjustNumber resampling,
+ * extrapolateLsSimple and per-entry particle counts (here one call takes one N) are the opt-in block at the end of this header.
  *
  * Layouts, bnd, "interior", e_a, u(p) and the per-axis weights (n; s0, s1) are those of the blocks above.  pos, pvel [B,N,D] fp32 SORTED
  * by key (df_particles_gather with the order of the key sort, for both); vel, weight [B,(Z,)Y,X,D] fp32; marks [B,(Z,)Y,X,D] uint8;
@@ -963,7 +963,8 @@ int df_diffuse_finish3d(void* ws, int64_t ws_bytes, float* out, int64_t B, int64
  * and solvePressure(flags, vel, pressure, phi=phi), the two calls every liquid loop of the reference makes (scene/liquid_pos_size.py:254-295,
  * scene/liquid3_d_r.py, scene/liquid3_vis.py).  mantaflow cannot be run beside this library: both are restated from memory, the
  * definitions below are this library's own, and parity is with the NumPy restatement of THESE definitions (tests/liquid_gf_ref.py), NOT
- * with mantaflow.  Still left out: adjustNumber, extrapolateLsSimple, resetOutflow and open sides, obstacles inside the liquid, MIC(0).
+ * with mantaflow.  Still left out: resetOutflow and open sides, obstacles inside the liquid, MIC(0); adjustNumber and extrapolateLsSimple
+ * are the block after this one.
  * DF_VERSION is NOT raised by this block (it has stayed 207 through every solver block of this header): a client cannot tell from
  * df_version() whether these symbols exist and has to look them up (dlsym), as for the smoke and liquid blocks above.
  *
@@ -1026,6 +1027,85 @@ int df_pressure_correct2d_gf(const float* vel, const float* pressure, float* out
                              int64_t X, int bnd, float gf_clamp, df_stream_t stream);
 int df_pressure_correct3d_gf(const float* vel, const float* pressure, float* out, const uint8_t* flags, const float* phi, int64_t B, int64_t Z,
                              int64_t Y, int64_t X, int bnd, float gf_clamp, df_stream_t stream);
+
+/* ---- the liquid solver's resampling: ragged particle batches, extrapolateLsSimple(phi, distance, inside) and adjustNumber(pp, vel, flags,
+ * minParticles, maxParticles, phi, radiusFactor), the last calls of the reference's liquid loops (scene/liquid_pos_size.py,
+ * scene/liquid3_d_r.py, scene/liquid3_vis.py) that this library did not have.  mantaflow cannot be run beside this library: all of it is
+ * restated from memory, the definitions below are this library's own, and parity is with the NumPy restatement of THESE definitions
+ * (tests/liquid_resample_ref.py), NOT with mantaflow.  Opt-in: nothing above calls any of it.  The step that uses it runs, per frame: trace,
+ * keys, sort, p2g, 2 layers, flags, the averaged level set with its band, the extrapolation (4, inside), forces, the solve (the ghost-fluid
+ * one sees the extrapolated phi), the resampling against the projected velocity, 4 layers, the FLIP update on old and new particles.  DF_VERSION is NOT raised.
+ *
+ *   ragged batches   pos, pvel [P,D] fp32 with P = B*N rows (N is only the capacity per entry that makes P a multiple of B);
+ *            entry_start [B+1] int32 in DEVICE memory, non-decreasing.  Rows entry_start[b] .. entry_start[b+1] - 1 belong to entry b: the
+ *            entry of row i is (the number of b in 0..B with entry_start[b] <= i) - 1, found by bisection; rows from entry_start[B] on
+ *            (and below entry_start[0]) are unused.  df_particles_advect*_ragged, df_particles_cell_keys*_ragged and
+ *            df_flip_update*_ragged are the entry points above with that entry in place of i / N: an unused row is neither read nor
+ *            written by the trace and the FLIP update, and gets the key B*ncell, which sorts behind every cell.  The stable sort keeps the
+ *            entries contiguous and in order, and the ranges over keys 0 .. B*ncell hold the live total in their last element, so every
+ *            entry point driven by cell_start (p2g, flags, both level sets) takes a ragged batch as it is, with N = P / B.
+ *            Bit rule: with entry_start[b] = b*N the ragged forms return the bits of the dense ones.  Whatever entry_start holds, the
+ *            entry found lies in 0..B-1: it changes numbers, never addresses.
+ *   extrapolation    of phi [B,(Z,)Y,X] over the cells off the outermost layer of the grid (index 1 .. extent - 2 on every axis); the
+ *            outermost layer is never marked, read as a source or written.  df_levelset_extrapolate_marks*: mark 1 where phi > 0
+ *            (inside = 1) or phi < 0 (inside = 0); mark 2 on an unmarked cell with a face neighbour marked 1; else 0.
+ *            df_levelset_extrapolate_layer*, ONE layer per call, layer = 2, 3, ..., IN PLACE: a cell with mark 0 and n > 0 face
+ *            neighbours marked `layer` becomes phi = (the sum of those neighbours' phi, from 0, in the order x-, x+, y-, y+[, z-, z+])
+ *            / (float)n + direction, direction = -1 for inside = 1 and +1 otherwise, and takes mark layer + 1.  A launch writes cells
+ *            marked 0 only and reads phi of cells marked `layer` only, so it is race free in place.  extrapolateLsSimple(distance) is the
+ *            marks and the layers 2 .. distance; distance <= 1 changes nothing.  The marks handed to a layer call must be those of
+ *            df_levelset_extrapolate_marks* (and the layers before it) on the same phi with the SAME `inside`; the library cannot check that.
+ *   resampling       of SORTED ragged particles.  R = (0.5 * sqrt(D)) * (radius_factor + 0.01), surface = -2 * R.
+ *            df_resample_count*: for every (entry, cell) its range of cell_start is walked in sorted order with a counter k from 0; for
+ *            a particle p, phiv = the D-linear interpolation of the entry's cell-centred phi at p (weights (n; s0, s1) of q_a = p_a - 0.5,
+ *            along x, then y[, then z], as u(p) combines them).  The particle is dropped if phiv > 0, else if k > max_particles and
+ *            phiv <= surface; else it is kept and k += 1.  keep[row] = 1 or 0, kept[cell] = k, seeds[cell] = min_particles - k if the cell
+ *            is interior and liquid by flags (df_liquid_flags*), phi[cell] <= surface and k < min_particles; else 0.
+ *            The caller scans kept + seeds into new_start [B*ncell + 1] int32 (exclusive; the last element is the wanted total);
+ *            new_entry_start[b] = new_start[b*ncell].
+ *            df_resample_scatter*: for every (entry, cell) the kept particles of its range (position and velocity bits) go to rows
+ *            new_start[cell] + 0, 1, ... in order, then seed m = 0 .. seeds - 1 follows: its coordinate a is
+ *            float(c_a) + float(h >> 8) * 2^-24 with h the integer mix of the lattice noise above applied to
+ *            seed ^ (step * 0x8DA6B343) ^ ((entry*ncell + cell) * 0xD8163841) ^ ((m*D + a) * 0xCB1AB31F), a 24-bit uniform in [0, 1).
+ *            That sum can round up to float(c_a + 1); it is then replaced by the largest float below float(c_a + 1) (its bit pattern
+ *            minus one), so a seed lies in [c_a, c_a + 1) and keeps its cell's key.  A seed's velocity is u(vel, p) of its entry.  The
+ *            output is sorted by cell with new_start as its cell_start.  No row >= P is read or written: when the wanted total exceeds
+ *            P the tail is left out, and the caller, who holds the total in new_start, has to refuse the result.
+ * Every index read from device memory (cell_start, new_start, seeds, entry_start) is clamped before use; a flags byte is believed only
+ * where the cell is interior by its index.  No atomics, no floating-point sums whose order depends on scheduling.
+ * Errors, on the host and before any launch: those of the blocks above, and DF_EINVAL for a null entry_start (N > 0), inside outside 0..1,
+ * layer outside 2..254, marks that overlap phi, min_particles outside 1..4096, max_particles outside min_particles..8192, scatter outputs
+ * that overlap an input or each other; DF_ESHAPE when B*ncell*min_particles + P does not fit an int32. */
+int df_particles_advect2d_ragged(const float* pos_in, float* pos_out, const float* vel, const int32_t* entry_start, int64_t B, int64_t N,
+                                 int64_t Y, int64_t X, float dt, float vel_scale, int bnd, df_stream_t stream);
+int df_particles_advect3d_ragged(const float* pos_in, float* pos_out, const float* vel, const int32_t* entry_start, int64_t B, int64_t N,
+                                 int64_t Z, int64_t Y, int64_t X, float dt, float vel_scale, int bnd, df_stream_t stream);
+int df_particles_cell_keys2d_ragged(const float* pos, int32_t* keys, const int32_t* entry_start, int64_t B, int64_t N, int64_t Y, int64_t X,
+                                    df_stream_t stream);
+int df_particles_cell_keys3d_ragged(const float* pos, int32_t* keys, const int32_t* entry_start, int64_t B, int64_t N, int64_t Z, int64_t Y,
+                                    int64_t X, df_stream_t stream);
+int df_flip_update2d_ragged(const float* pos, const float* pvel_in, float* pvel_out, const float* vel, const float* vel_old,
+                            const int32_t* entry_start, int64_t B, int64_t N, int64_t Y, int64_t X, float flip_ratio, df_stream_t stream);
+int df_flip_update3d_ragged(const float* pos, const float* pvel_in, float* pvel_out, const float* vel, const float* vel_old,
+                            const int32_t* entry_start, int64_t B, int64_t N, int64_t Z, int64_t Y, int64_t X, float flip_ratio,
+                            df_stream_t stream);
+int df_levelset_extrapolate_marks2d(const float* phi, uint8_t* mark, int64_t B, int64_t Y, int64_t X, int inside, df_stream_t stream);
+int df_levelset_extrapolate_marks3d(const float* phi, uint8_t* mark, int64_t B, int64_t Z, int64_t Y, int64_t X, int inside, df_stream_t stream);
+int df_levelset_extrapolate_layer2d(float* phi, uint8_t* mark, int64_t B, int64_t Y, int64_t X, int inside, int layer, df_stream_t stream);
+int df_levelset_extrapolate_layer3d(float* phi, uint8_t* mark, int64_t B, int64_t Z, int64_t Y, int64_t X, int inside, int layer,
+                                    df_stream_t stream);
+int df_resample_count2d(const float* pos_sorted, const int32_t* cell_start, const float* phi, const uint8_t* flags, uint8_t* keep, int32_t* kept,
+                        int32_t* seeds, int64_t B, int64_t N, int64_t Y, int64_t X, int bnd, int min_particles, int max_particles,
+                        float radius_factor, df_stream_t stream);
+int df_resample_count3d(const float* pos_sorted, const int32_t* cell_start, const float* phi, const uint8_t* flags, uint8_t* keep, int32_t* kept,
+                        int32_t* seeds, int64_t B, int64_t N, int64_t Z, int64_t Y, int64_t X, int bnd, int min_particles, int max_particles,
+                        float radius_factor, df_stream_t stream);
+int df_resample_scatter2d(const float* pos_sorted, const float* pvel_sorted, const int32_t* cell_start, const uint8_t* keep, const int32_t* seeds,
+                          const int32_t* new_start, const float* vel, float* pos_out, float* pvel_out, int64_t B, int64_t N, int64_t Y,
+                          int64_t X, int min_particles, uint32_t seed, uint32_t step, df_stream_t stream);
+int df_resample_scatter3d(const float* pos_sorted, const float* pvel_sorted, const int32_t* cell_start, const uint8_t* keep, const int32_t* seeds,
+                          const int32_t* new_start, const float* vel, float* pos_out, float* pvel_out, int64_t B, int64_t N, int64_t Z,
+                          int64_t Y, int64_t X, int min_particles, uint32_t seed, uint32_t step, df_stream_t stream);
 
 #ifdef __cplusplus
 }

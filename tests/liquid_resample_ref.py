@@ -1,0 +1,445 @@
+"""NumPy restatement of the liquid solver's resampling block as include/deepfluids_hip.h declares it (ragged particle batches, the
+level-set extrapolation, the count and scatter passes of the resampling), written from that definition and parametrised by dtype:
+float64 is the reference, float32 -- the same operations in the same order -- is the twin, which the GPU must match bit for bit (nothing
+here passes through a solve).  The definitions are this project's own, restated from memory of mantaflow's extrapolateLsSimple and
+adjustNumber; parity is with THIS file, NOT with mantaflow.  Also the inputs the host and the GPU tests share.  Plain helper, no fixtures.
+
+Layout: a ragged batch is pos, pvel [P,D] (x, y[, z]) with entry_start [B+1]; velocity [B,(Z,)Y,X,D]; phi [B,(Z,)Y,X]; cell (i,j,k) =
+[..,k,j,i]."""
+import numpy as np
+
+import liquid_ref as ref
+import particles_ref as pref
+from smoke_ref import interior_mask
+
+_type = ref._type
+_ax = ref._ax
+
+
+# ---- ragged batches -----------------------------------------------------------------------------------------------------------------------------
+def pack(parts, capacity=None):
+    B = len(parts)
+    D = parts[0].shape[-1]
+    counts = [len(p) for p in parts]
+    total = sum(counts)
+    P = -(-total // B) * B if capacity is None else capacity
+    assert P >= total and P % B == 0
+    pos = np.zeros((P, D), parts[0].dtype)
+    if total:
+        pos[:total] = np.concatenate(parts, axis=0)
+    return pos, np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+
+
+def entries(entry_start, P):
+    """[P]: the entry of every row, (the number of starts <= row) - 1; -1 for an unused row"""
+    es = np.asarray(entry_start, np.int64)
+    B = len(es) - 1
+    e = np.searchsorted(es, np.arange(P), side="right") - 1
+    return np.where(e == B, -1, e)
+
+
+def trace(pos, vel, entry_start, dt, bnd=1, vel_scale=1.0, dtype=np.float64):
+    """pref.trace per entry on its own rows; unused rows come back as they are"""
+    dtype = _type(dtype)
+    out = np.asarray(pos).astype(dtype).copy()
+    e = entries(entry_start, len(out))
+    for b in range(len(entry_start) - 1):
+        rows = np.flatnonzero(e == b)
+        if len(rows):
+            out[rows] = pref.trace(out[rows][None], np.asarray(vel)[b:b + 1], dt, bnd, vel_scale, dtype)[0]
+    return out
+
+
+def keys(pos, entry_start, shape):
+    p = np.asarray(pos, np.float32)
+    B = len(entry_start) - 1
+    ncell = int(np.prod(shape))
+    e = entries(entry_start, len(p))
+    k = np.full(len(p), B * ncell, np.int64)
+    live = e >= 0
+    with np.errstate(invalid="ignore"):
+        k[live] = pref.cell_keys(p[live][None], shape).astype(np.int64) + e[live] * ncell
+    return k.astype(np.int32)
+
+
+def sort(pos, pvel, entry_start, shape):
+    """(pos_sorted, pvel_sorted, cell_start [B*ncell + 1], order): the keys of the fp32 positions, sorted stably; the arrays keep their dtype"""
+    B = len(entry_start) - 1
+    order, cell_start = pref.cell_ranges(keys(pos, entry_start, shape), B * int(np.prod(shape)))
+    return pos[order], (None if pvel is None else pvel[order]), cell_start, order
+
+
+def flip_update(pos, pvel, vel, vel_old, entry_start, flip_ratio=0.97, dtype=np.float64):
+    dtype = _type(dtype)
+    out = np.asarray(pvel).astype(dtype).copy()
+    e = entries(entry_start, len(out))
+    for b in range(len(entry_start) - 1):
+        rows = np.flatnonzero(e == b)
+        if len(rows):
+            out[rows] = ref.flip_update(np.asarray(pos)[rows][None], out[rows][None], np.asarray(vel)[b:b + 1], np.asarray(vel_old)[b:b + 1],
+                                        flip_ratio, dtype)[0]
+    return out
+
+
+# ---- the level-set extrapolation ------------------------------------------------------------------------------------------------------------------
+DIRS = ((0, 1), (0, -1), (1, 1), (1, -1), (2, 1), (2, -1))           # (axis, roll shift): x-, x+, y-, y+, z-, z+
+
+
+def extrapolate_marks(phi, inside=True):
+    ph = np.asarray(phi)
+    shape = ph.shape[1:]
+    nd = len(shape)
+    inner = np.broadcast_to(interior_mask(shape, 1)[None], ph.shape)
+    with np.errstate(invalid="ignore"):
+        src = inner & ((ph > 0) if inside else (ph < 0))
+    near = np.zeros(ph.shape, bool)
+    for a, sh in DIRS[:2 * nd]:
+        near |= np.roll(src, sh, axis=_ax(nd, a))                      # the wrap lands on the outermost layer only, which `inner` masks
+    return np.where(src, 1, np.where(inner & near, 2, 0)).astype(np.uint8)
+
+
+def extrapolate_levelset(phi, distance=4, inside=True, dtype=np.float64, marks=False):
+    dtype = _type(dtype)
+    ph = np.asarray(phi).astype(dtype).copy()
+    if distance <= 1:
+        return (ph, np.zeros(ph.shape, np.uint8)) if marks else ph
+    shape = ph.shape[1:]
+    nd = len(shape)
+    inner = np.broadcast_to(interior_mask(shape, 1)[None], ph.shape)
+    m = extrapolate_marks(ph, inside)
+    direction = dtype(-1) if inside else dtype(1)
+    for d in range(2, int(distance) + 1):
+        s = np.zeros(ph.shape, dtype)
+        cnt = np.zeros(ph.shape, np.int64)
+        for a, sh in DIRS[:2 * nd]:
+            ok = np.roll(m, sh, axis=_ax(nd, a)) == d
+            with np.errstate(invalid="ignore"):
+                s = np.where(ok, s + np.roll(ph, sh, axis=_ax(nd, a)), s).astype(dtype)
+            cnt = cnt + ok
+        fill = inner & (m == 0) & (cnt > 0)
+        with np.errstate(all="ignore"):
+            ph = np.where(fill, (s / np.maximum(cnt, 1).astype(dtype)).astype(dtype) + direction, ph).astype(dtype)
+        m = np.where(fill, d + 1, m).astype(np.uint8)
+    return (ph, m) if marks else ph
+
+
+# ---- the resampling -------------------------------------------------------------------------------------------------------------------------------
+def mix4(seed, a, b, c):
+    M = 0xFFFFFFFF
+    h = (seed ^ (a * 0x8DA6B343) ^ (b * 0xD8163841) ^ (c * 0xCB1AB31F)) & M
+    h ^= h >> 16
+    h = (h * 0x7FEB352D) & M
+    h ^= h >> 15
+    h = (h * 0x846CA68B) & M
+    h ^= h >> 16
+    return h
+
+
+def phi_sample(phi_e, p, dtype):
+    """the D-linear interpolation of one entry's cell-centred phi (already of ``dtype``) at p [n,D]"""
+    D = p.shape[-1]
+    ext = phi_e.shape[::-1]
+    w = [pref.axis_weights(p[:, a] - dtype(0.5), ext[a], dtype) for a in range(D)]
+
+    def at(off):
+        return phi_e[tuple(w[c][0] + off[c] for c in reversed(range(D)))]
+
+    def along_x(rest):
+        return w[0][1] * at((0,) + rest) + w[0][2] * at((1,) + rest)
+
+    with np.errstate(invalid="ignore"):
+        if D == 2:
+            return (w[1][1] * along_x((0,)) + w[1][2] * along_x((1,))).astype(dtype)
+        r0 = w[1][1] * along_x((0, 0)) + w[1][2] * along_x((1, 0))
+        r1 = w[1][1] * along_x((0, 1)) + w[1][2] * along_x((1, 1))
+        return (w[2][1] * r0 + w[2][2] * r1).astype(dtype)
+
+
+def surface_of(D, radius_factor, dtype):
+    dtype = _type(dtype)
+    return dtype(-2) * pref.radius_of(D, radius_factor, dtype)
+
+
+def resample(spos, spvel, cell_start, phi, liquid, vel, min_particles, max_particles=None, radius_factor=1.0, seed=123, step=0,
+             dtype=np.float64):
+    """The count pass, the scan and the scatter pass on SORTED ragged particles.  ``liquid`` [B,..] bool: interior and liquid by the
+    flags.  Returns a dict: pos, pvel [total,D] (no capacity here), entry_start, cell_start (the new ranges), keep [P], kept, seeds
+    [B*ncell], phiv [P] (NaN on rows no cell holds), seeded [total] bool."""
+    dtype = _type(dtype)
+    maxp = 2 * min_particles if max_particles is None else max_particles
+    p = np.asarray(spos).astype(dtype)
+    u = np.asarray(spvel).astype(dtype)
+    ph = np.asarray(phi).astype(dtype)
+    v = np.asarray(vel).astype(dtype)
+    P, D = p.shape
+    B = ph.shape[0]
+    shape = ph.shape[1:]
+    ncell = int(np.prod(shape))
+    X, Y = shape[-1], shape[-2]
+    surface = surface_of(D, radius_factor, dtype)
+    cs = np.clip(np.asarray(cell_start, np.int64), 0, P)
+    phiv = np.full(P, np.nan, dtype)
+    for b in range(B):
+        s, e = cs[b * ncell], cs[(b + 1) * ncell]
+        if e > s:
+            phiv[s:e] = phi_sample(ph[b], p[s:e], dtype)
+    keep = np.zeros(P, np.uint8)
+    kept = np.zeros(B * ncell, np.int32)
+    for c in range(B * ncell):
+        k = 0
+        for r in range(cs[c], cs[c + 1]):
+            drop = phiv[r] > 0 or (k > maxp and phiv[r] <= surface)
+            keep[r] = 0 if drop else 1
+            k += 0 if drop else 1
+        kept[c] = k
+    with np.errstate(invalid="ignore"):
+        deep = np.asarray(liquid, bool).reshape(-1) & (ph.reshape(-1) <= surface)
+    seeds = np.where(deep & (kept < min_particles), min_particles - kept, 0).astype(np.int32)
+    new_start = np.concatenate([[0], np.cumsum(kept.astype(np.int64) + seeds)])
+    total = int(new_start[-1])
+    pos_out = np.zeros((total, D), dtype)
+    pvel_out = np.zeros((total, D), dtype)
+    seeded = np.zeros(total, bool)
+    for c in range(B * ncell):
+        rows = np.arange(cs[c], cs[c + 1])
+        rows = rows[keep[rows] == 1]
+        dst = new_start[c]
+        pos_out[dst:dst + len(rows)] = p[rows]
+        pvel_out[dst:dst + len(rows)] = u[rows]
+        dst += len(rows)
+        ns = int(seeds[c])
+        if ns == 0:
+            continue
+        b, local = divmod(c, ncell)
+        cell = (local % X, (local // X) % Y, local // (X * Y))
+        q = np.zeros((ns, D), dtype)
+        for m in range(ns):
+            for a in range(D):
+                h = mix4(seed & 0xFFFFFFFF, step & 0xFFFFFFFF, c, m * D + a)
+                lo, up = dtype(cell[a]), dtype(cell[a] + 1)
+                val = lo + dtype(h >> 8) * dtype(2.0 ** -24)
+                q[m, a] = val if val < up else np.nextafter(up, dtype(0))
+        pos_out[dst:dst + ns] = q
+        pvel_out[dst:dst + ns] = pref.mac_sample(v[b:b + 1], q[None], 1.0, dtype)[0]
+        seeded[dst:dst + ns] = True
+    return dict(pos=pos_out, pvel=pvel_out, entry_start=new_start[::ncell].astype(np.int32), cell_start=new_start.astype(np.int32), keep=keep,
+                kept=kept, seeds=seeds, phiv=phiv, seeded=seeded, total=total)
+
+
+def check_invariants(r, phi, liquid, min_particles, max_particles, radius_factor=1.0):
+    """the properties of a resampled state ``r`` (of ``resample``) that hold whatever the input: asserts"""
+    ph = np.asarray(phi)
+    B = ph.shape[0]
+    shape = ph.shape[1:]
+    D = len(shape)
+    ncell = int(np.prod(shape))
+    dtype = r["pos"].dtype.type
+    surface = surface_of(D, radius_factor, dtype)
+    counts = np.diff(r["cell_start"].astype(np.int64))
+    with np.errstate(invalid="ignore"):
+        deep = np.asarray(liquid, bool).reshape(-1) & (ph.astype(dtype).reshape(-1) <= surface)
+    assert (counts[deep] >= min_particles).all()                       # a deep liquid cell ends with >= min_particles
+    kept_rows = r["keep"] == 1
+    assert not (r["phiv"][kept_rows] > 0).any()                         # no kept particle has phiv > 0
+    # a cell keeps <= max_particles + 1 particles that are not at the surface
+    cs = r["old_cell_start"]
+    for c in np.flatnonzero(r["kept"] > max_particles):
+        rows = np.arange(cs[c], cs[c + 1])
+        rows = rows[kept_rows[rows]]
+        assert (r["phiv"][rows] <= surface).sum() <= max_particles + 1, c
+    # seeds lie inside their cell, and the output is sorted by cell with new_start as its ranges
+    es = r["entry_start"]
+    k = keys(r["pos"].astype(np.float32), np.concatenate([es[:-1], [r["total"]]]), shape).astype(np.int64)
+    assert (np.diff(k) >= 0).all()
+    np.testing.assert_array_equal(np.searchsorted(k, np.arange(B * ncell + 1)), r["cell_start"])
+    assert np.isfinite(r["pos"][r["seeded"]]).all()
+
+
+# ---- inputs the host and the GPU tests share ------------------------------------------------------------------------------------------------
+SHAPES = [(12, 10), (8, 10, 12)]          # [(Z,)Y,X]
+B = 3
+BND = 1
+
+
+def velocity(shape, seed, scale=0.6):
+    rng = np.random.RandomState(seed)
+    D = len(shape)
+    return (scale * rng.standard_normal((B,) + tuple(shape) + (D,))).astype(np.float32)
+
+
+def ragged_case(shape, N, seed):
+    """counts (N, 0, N // 3): (pos [P,D] with NaN in the unused rows, pvel alike, entry_start, the per-entry lists)"""
+    rng = np.random.RandomState(seed)
+    D = len(shape)
+    lo, hi = pref.clamp_bounds(shape, BND, np.float32)
+    counts = (N, 0, N // 3)
+    parts = [(lo + rng.uniform(0, 1, size=(n, D)) * (hi - lo)).astype(np.float32) for n in counts]
+    vels = [rng.standard_normal((n, D)).astype(np.float32) for n in counts]
+    P = B * N
+    pos, es = pack(parts, P)
+    pvel, _ = pack(vels, P)
+    pos[es[-1]:] = np.nan
+    pvel[es[-1]:] = np.nan
+    return pos, pvel, es, parts, vels
+
+
+def pocket_phi(shape, seed):
+    """phi [B,..] float32: a smooth surface with liquid below, an isolated positive pocket inside the liquid of entry 0, noise; entry 1 is
+    all negative (nothing to mark with inside=True)"""
+    rng = np.random.RandomState(seed)
+    D = len(shape)
+    yc = pref._centre(shape, 1, np.float64)
+    xc = pref._centre(shape, 0, np.float64)
+    base = np.broadcast_to(yc - 0.55 * shape[-2] + 0.8 * np.sin(xc * 0.9), shape)
+    phi = np.stack([base + 0.05 * rng.standard_normal(shape) for _ in range(B)])
+    pocket = (slice(2, 4),) * D
+    phi[0][pocket] = 0.3
+    phi[1] = -np.abs(phi[1]) - 0.01
+    return phi.astype(np.float32)
+
+
+MIN_P = 2                                  # max_particles = 4
+
+
+def resample_state(shape, seed=5):
+    """A sorted ragged state that holds at once: a deep cell with max + 3 particles, a surface cell with max + 3 (all kept), particles at
+    phiv > 0, a deep liquid cell with one particle, a deep cell emptied by the drops, an entry with no particles (entry 1, which is liquid by the
+    flags below the surface all the same and so is filled from nothing), and deep cells in the last interior column along x that get seeds.  phi is a flat surface at y = ys, so phiv is known: phi = y - ys.
+    Returns a dict of fp32 arrays: pos, pvel (sorted), cell_start, entry_start, phi, liquid, vel, and ``cells``: name -> flat key."""
+    rng = np.random.RandomState(seed)
+    D = len(shape)
+    X, Y = shape[-1], shape[-2]
+    ncell = int(np.prod(shape))
+    ys = Y - 3.0                                                        # the surface: cells with centre <= ys - 2R are deep
+    yc = pref._centre(shape, 1, np.float32)
+    phi = np.broadcast_to(yc - np.float32(ys), shape).astype(np.float32)
+    phi = np.stack([phi, phi, phi])
+    maxp = 2 * MIN_P
+    mid = (shape[0] // 2,) if D == 3 else ()
+
+    def key(b, i, j):
+        k = mid[0] if D == 3 else 0
+        return b * ncell + (k * Y + j) * X + i
+
+    def inside(i, j, n, ylo=0.05, yhi=0.95, lo=0.05, hi=0.95):
+        q = np.empty((n, D), np.float32)
+        q[:, 0] = i + rng.uniform(lo, hi, n)
+        q[:, 1] = j + rng.uniform(ylo, yhi, n)
+        if D == 3:
+            q[:, 2] = mid[0] + rng.uniform(lo, hi, n)
+        return q
+
+    jsurf = int(ys) - 1                                                 # a liquid row whose particles have -2R < phiv <= 0
+    e0 = [inside(2, 1, maxp + 3),                                       # deep, crowded
+          inside(3, jsurf, maxp + 3, 0.6, 0.95),                        # at the surface, crowded: all kept
+          inside(4, int(ys) + 1, 3),                                    # phiv > 0: dropped
+          inside(5, 1, 1),                                              # deep, one particle
+          inside(X - 2, 1, 1),                                          # deep, last interior column: seeds at the round-up end
+          inside(X - 2, 2, MIN_P)]
+    # a deep cell emptied by the drops cannot exist under a flat phi (deep means phiv <= surface < 0); bend phi up in the cell above one
+    # cell of entry 2 instead: its centre stays deep while its particles, near its upper side, see phiv > 0
+    e2 = [inside(6, 2, 2, 0.9, 0.98, 0.3, 0.7), inside(2, 1, 3)]
+    phi[2][mid + (3, 6)] = 40.0
+    parts = [np.concatenate(e0), np.zeros((0, D), np.float32), np.concatenate(e2)]
+    total = sum(len(q) for q in parts)
+    P = -(-(total + B * ncell * MIN_P) // B) * B                        # room for every cell's seeds
+    pos, es = pack(parts, P)
+    pos[es[-1]:] = np.nan
+    pvel = np.where(np.isnan(pos), np.nan, rng.standard_normal(pos.shape)).astype(np.float32)
+    spos, spvel, cell_start, _ = sort(pos, pvel, es, shape)
+    liquid = ref.liquid_mask(cell_start, B, shape, BND)
+    # the cells that must be seeded are liquid by the flags even with few particles; mark the whole region below the surface liquid,
+    # as a solver's flags would after a step (interior cells only)
+    liquid = liquid | (np.broadcast_to(yc <= ys, (B,) + tuple(shape)) & interior_mask(shape, BND)[None])
+    cells = dict(deep_crowded=key(0, 2, 1), surface_crowded=key(0, 3, jsurf), outside=key(0, 4, int(ys) + 1), deep_single=key(0, 5, 1),
+                 last_column=key(0, X - 2, 1), emptied=key(2, 6, 2))
+    return dict(pos=spos, pvel=spvel, cell_start=cell_start, entry_start=es, phi=phi, liquid=liquid, vel=velocity(shape, seed + 1), cells=cells)
+
+
+# ---- the step with resample -------------------------------------------------------------------------------------------------------------------------
+def step(pos, pvel, entry_start, vel, dt, min_particles, max_particles=None, seed=123, step_no=0, force=None, bnd=1, accuracy=1e-4,
+         max_iter=None, flip_ratio=0.97, radius_factor=1.0, ghost_fluid=False, gf_clamp=1e-4, alpha=None, dtype=np.float64):
+    """One step on a ragged state (pos, pvel [P,D], entry_start) in the script's order: trace, sort, particles to grid, 2 layers, flags,
+    the averaged level set with the bnd band, its extrapolation (4, inside), [the viscous pass,] forces, the solve (with ghost_fluid it
+    sees the extrapolated phi), the resampling against the projected velocity, 4 layers, the FLIP update on old and new particles alike.
+    The positions are traced in ``dtype`` and the keys are taken of their fp32 rounding.  Returns a dict: pos, pvel [total,D],
+    entry_start, cell_start (the new ranges), vel, iters, phi, liquid, and ``resampled``: the dict of ``resample`` with the old ranges."""
+    import diffuse_ref as dref
+    import liquid_gf_ref as gref
+    dtype = _type(dtype)
+    shape = vel.shape[1:-1]
+    B = len(entry_start) - 1
+    D = pos.shape[-1]
+    P = len(pos)
+    N = P // B
+    used = (entries(entry_start, P) >= 0)[:, None]
+    p = np.where(used, np.asarray(pos), 0).astype(dtype)                # unused rows hold no meaning: zeros here, never read through a range
+    u = np.where(used, np.asarray(pvel), 0).astype(dtype)
+    force = ref.default_force(shape, dt) if force is None else force
+    p = trace(p, vel, entry_start, dt, bnd, 1.0, dtype)
+    p, u, cell_start, _ = sort(p, u, entry_start, shape)
+    p3, u3 = p.reshape(B, N, D), u.reshape(B, N, D)
+    v, w, known = ref.p2g(p3, u3, cell_start, shape, dtype)
+    v_old = v.copy()
+    v, _ = ref.extrapolate(v, known, 2, bnd, dtype)
+    liquid = ref.liquid_mask(cell_start, B, shape, bnd)
+    _, touch = ref.flags_of(liquid)
+    phi = gref.levelset_averaged_sorted(p3, cell_start, shape, radius_factor, 1, 1, 1.0, bnd, dtype)
+    phi = extrapolate_levelset(phi, 4, True, dtype)
+    diters = None
+    if alpha is not None:
+        v = ref.forces(v, liquid, (0.0,) * len(shape), bnd, dtype)
+        v, diters, _, _ = dref.cg(v, alpha, bnd, accuracy, dref.default_max_iter(shape), dtype)
+    v = ref.forces(v, liquid, force, bnd, dtype)
+    if ghost_fluid:
+        v, pr, iters = gref.solve_pressure(v, liquid, phi, bnd, accuracy, max_iter, gf_clamp, dtype)
+    else:
+        v, pr, iters = ref.solve_pressure(v, liquid, bnd, accuracy, max_iter, dtype)
+    r = resample(p, u, cell_start, phi, liquid, v, min_particles, max_particles, radius_factor, seed, step_no, dtype)
+    r["old_cell_start"] = cell_start
+    v, _ = ref.extrapolate(v, touch, 4, bnd, dtype)
+    es = np.concatenate([r["entry_start"][:-1], [r["total"]]]).astype(np.int32)
+    un = flip_update(r["pos"], r["pvel"], v, v_old, es, flip_ratio, dtype)
+    return dict(pos=r["pos"], pvel=un, entry_start=es, cell_start=r["cell_start"], vel=v, iters=iters, diters=diters, phi=phi, liquid=liquid,
+                resampled=r, total=r["total"])
+
+
+def padded(a, B, capacity=None):
+    """rows appended (zeros) up to ``capacity``, or to the next multiple of B"""
+    P = -(-len(a) // B) * B if capacity is None else capacity
+    out = np.zeros((P,) + a.shape[1:], a.dtype)
+    out[:len(a)] = a
+    return out
+
+
+STEP_MIN_P = {2: 5, 3: 9}       # above the 2^D particles per cell the scenes are seeded with, so that deep cells are filled up
+STEP_DT = 0.5
+STEP_ACC = 1e-6
+STEP_T = 3
+#             name              shape         ghost_fluid  viscosity alpha
+STEP_CASES = [("dam2d", (12, 10), False, None), ("dam2d-gf", (12, 10), True, None), ("dam2d-gf-visc", (12, 10), True, (0.5, 2.0, 0.0)),
+              ("drop3d", (8, 10, 12), False, None), ("drop3d-gf", (8, 10, 12), True, None)]
+
+
+def step_scene(shape, seed=123):
+    """(parts: B lists of positions [N_b,D] float32 with different counts, vel0 [B,..,D]): 2-D a dam break (a column of liquid against the
+    left wall, one width per entry), 3-D a drop over a basin (one drop position per entry; the drop moves down)"""
+    from deep_fluids_amd import ops
+    D = len(shape)
+    ext = np.array(shape[::-1], np.float64)
+    parts, vel = [], []
+    for n in range(B):
+        if D == 2:
+            hi = np.array([3.0 + n, 0.7 * ext[1]])
+            phi = ops.box_levelset(shape, np.zeros(D), hi)
+            vel.append(np.zeros(tuple(shape) + (D,), np.float32))
+        else:
+            hi = ext.copy()
+            hi[1] = 0.3 * ext[1]
+            c = 0.5 * ext
+            c[0] = np.floor((0.3 + 0.15 * n) * ext[0]) + 0.5
+            c[1] = np.floor(0.65 * ext[1]) + 0.5
+            phi = np.minimum(ops.box_levelset(shape, np.zeros(D), hi), ops.sphere_levelset(shape, c, (0.13 + 0.02 * n) * ext[0]))
+            vel.append(ref.initial_velocity(shape, [(c, (0.13 + 0.02 * n) * ext[0] + 1.0)]))
+        parts.append(ops.seed_particles(phi, seed=seed + n))
+    return parts, np.stack(vel)
