@@ -11,6 +11,7 @@ TF-1 style hidden state (``slim`` variables inside ``tf.variable_scope``) is rep
 name-keyed registry: ``variable_scope(name, reuse)`` + ``get_variables(scope)``; variable names
 follow slim: ``<scope>/<layer>/weights`` ``[k,(k,)k,Cin,Cout]`` / ``[in,out]`` and ``.../biases``.
 """
+import collections
 import contextlib
 import ctypes
 import contextlib as _contextlib
@@ -2309,50 +2310,30 @@ def solve_pressure(vel, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, o
         osd = open_sides(open_bound, nd)
         if int(bnd) != bnd or bnd < 1:
             raise ValueError("solve_pressure: bnd must be an integer >= 1, got %r" % (bnd,))
-        if not accuracy >= 0:
-            raise ValueError("solve_pressure: accuracy must be >= 0, got %r" % (accuracy,))
-        dims, dims4 = _pressure_dims(v, nd)
-        if max_iter is None:
-            max_iter = default_max_iter(dims[1:])
-        check_every = DEFAULT_CHECK_EVERY if check_every is None else int(check_every)
-        if max_iter < 0 or check_every < 1:
-            raise ValueError("solve_pressure: max_iter must be >= 0 and check_every >= 1, got %r, %r" % (max_iter, check_every))
+        s = _solve_begin("solve_pressure", v, nd, accuracy, max_iter, check_every, workspace if workspace is not None else pressure_workspace(v))
         out = _smoke_out(out, v, "solve_pressure")
-        ws = workspace if workspace is not None else pressure_workspace(v)
-        if ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous():
-            raise ValueError("solve_pressure: workspace must be a contiguous float32 GPU tensor (pressure_workspace)")
-        nbytes = ws.numel() * 4
-        sfx = "%dd" % nd
+        dims, ws, nbytes, bnd = list(v.shape[:-1]), s.ws, s.nbytes, int(bnd)
         pressure = _empty(dims, v)
-        words = torch.empty((1 + dims[0],), dtype=torch.int32, device=v.device)
-        count, iters = words[:1], words[1:]
-        bnd, acc, max_iter = int(bnd), float(accuracy), int(max_iter)
         # with obstacles: the `_flags` twin of every launch, the flags pointer right after the array arguments
         flags = None if obstacle is None else _obstacle_arg(obstacle, dims, bnd, "solve_pressure")     # held until the last launch
         fl = [] if flags is None else [_ptr(flags)]
-        sfx += "_flags" if fl else ""
+        sfx = "%dd" % nd + ("_flags" if fl else "")
         call("df_pressure_init" + sfx, _ptr(v), _ptr(pressure), _ptr(ws), nbytes, *(fl + dims + [bnd, _stream()]))
         # open sides: only the direction launch (n_c) and the correction differ; their `_open` twins take a nullable flags pointer
         fo = [_ptr(flags) if fl else None]
-        k = 0
-        while True:
-            if osd:
-                call("df_pressure_cg_direction%dd_open" % nd, _ptr(ws), nbytes, *(fo + dims + [bnd, osd, k, acc, max_iter, _stream()]))
-            else:
-                call("df_pressure_cg_direction" + sfx, _ptr(ws), nbytes, *(fl + dims + [bnd, k, acc, max_iter, _stream()]))
-            if k % check_every == check_every - 1 or k >= max_iter:
-                call("df_pressure_status", _ptr(ws), nbytes, *(dims4 + [k, _ptr(count), None, _stream()]))
-                if _read_word(count) == 0:
-                    break
-            call("df_pressure_cg_update" + sfx, _ptr(pressure), _ptr(ws), nbytes, *(fl + dims + [bnd, k, _stream()]))
-            k += 1
-        call("df_pressure_status", _ptr(ws), nbytes, *(dims4 + [k, None, _ptr(iters), _stream()]))
+        if osd:
+            def direction(k):
+                call("df_pressure_cg_direction%dd_open" % nd, _ptr(ws), nbytes, *(fo + dims + [bnd, osd, k, s.acc, s.max_iter, _stream()]))
+        else:
+            def direction(k):
+                call("df_pressure_cg_direction" + sfx, _ptr(ws), nbytes, *(fl + dims + [bnd, k, s.acc, s.max_iter, _stream()]))
+        iters = _cg_loop(direction, lambda k: call("df_pressure_cg_update" + sfx, _ptr(pressure), _ptr(ws), nbytes, *(fl + dims + [bnd, k, _stream()])), s)
         if osd:
             call("df_pressure_correct%dd_open" % nd, _ptr(v), _ptr(pressure), _ptr(out), *(fo + dims + [bnd, osd, _stream()]))
             _fill_open(out, nd, bnd, osd)
         else:
             call("df_pressure_correct" + sfx, _ptr(v), _ptr(pressure), _ptr(out), *(fl + dims + [bnd, _stream()]))
-        return out, pressure, iters.clone()
+        return out, pressure, iters
 
 
 def default_buoyancy_force(shape, dt, gravity=-4e-3):
@@ -2370,33 +2351,47 @@ def buoyancy_forces(shape, dt, gravities):
     return torch.tensor([default_buoyancy_force(shape, dt, float(g)) for g in gravities], dtype=torch.float32).reshape(-1, len(shape))
 
 
-class _SmokeBuffers(object):
-    """Everything a smoke step needs besides its inputs, allocated once for a shape."""
+class _SmokeSettings(object):
+    """What a smoke step needs besides ``d``, ``v`` (the checked inputs), prepared once per ``smoke_step`` call or ``simulate_smoke``
+    sequence of ``steps`` (``who``): the open sides, the force, the source as the sequence forms hold it, the buffers allocated once for
+    the shape, the obstacle packed into flags, the velocity stamp, and the scalars of the call."""
 
-    def __init__(self, density, vel, order, source):
-        self.adv = advect_workspace(density, order, source)
-        self.fwd = torch.empty((vel.numel(),), dtype=torch.float32, device=vel.device) if order == 2 else None
-        self.pws = pressure_workspace(vel)
+    def __init__(self, who, density, vel, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, obstacle, open_bound,
+                 inflow_velocity):
+        d, v, nd = _advect_dims(density, vel)
+        self.d, self.v = d, v
+        self.osd = open_sides(open_bound, nd)
+        self.force = default_buoyancy_force(d.shape[1:], dt) if force is None else force
+        self.mask = mask = _source_arg(source, d)
+        if steps is not None and isinstance(mask, SphereSource) and mask.centers.dim() == 3 and mask.centers.shape[0] < int(steps):
+            raise ValueError("%s: %d frames of source centres for %d steps" % (who, mask.centers.shape[0], int(steps)))
+        self.adv = advect_workspace(d, order, mask is not None)
+        self.fwd = torch.empty((v.numel(),), dtype=torch.float32, device=v.device) if order == 2 else None
+        self.pws = pressure_workspace(v)
+        self.flags = _obstacle_arg(obstacle, d.shape, bnd, who) if obstacle is not None else None
+        self.vstamp = _inflow_velocity_arg(inflow_velocity, v, nd)
+        self.dt, self.order, self.clamp_mode, self.bnd = dt, order, clamp_mode, bnd
+        self.accuracy, self.max_iter, self.check_every = accuracy, max_iter, check_every
 
 
-def _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags=None, osd=0, time=0.0,
-                vstamp=None, v_stamped=None):
-    if vstamp is None:
-        advect(d, v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, source=mask, out=d_out, workspace=buf.adv, obstacle=flags, time=time)
+def _smoke_step(cfg, d, v, d_out, v_out, mask, time=0.0, v_stamped=None):
+    dt, bnd, flags, osd = cfg.dt, cfg.bnd, cfg.flags, cfg.osd
+    how = dict(order=cfg.order, clamp_mode=cfg.clamp_mode, bnd=bnd, obstacle=flags)
+    if cfg.vstamp is None:
+        advect(d, v, dt, source=mask, out=d_out, workspace=cfg.adv, time=time, **how)
     else:
         # the script's order: density inflow, velocity stamp (into ``v_stamped``, which may be ``v``), then both advections through it
         n = d.numel()
         if mask is not None:
-            stamped = buf.adv[:n].view(d.shape)
+            stamped = cfg.adv[:n].view(d.shape)
             _stamp(d, mask, 1.0, stamped, time, bnd)
             d = stamped
-        v = stamp_velocity(v, vstamp[0], vstamp[1], out=v_stamped)
-        advect(d, v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, out=d_out, workspace=buf.adv[n:] if mask is not None else buf.adv,
-               obstacle=flags)
-    advect_velocity(v, dt, order=order, clamp_mode=clamp_mode, bnd=bnd, out=v_out, workspace=buf.fwd, obstacle=flags, open_bound=osd)
-    wall_buoyancy(v_out, d_out, force, bnd=bnd, out=v_out, obstacle=flags, open_bound=osd)
-    _, _, iters = solve_pressure(v_out, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=v_out, workspace=buf.pws,
-                                 obstacle=flags, open_bound=osd)
+        v = stamp_velocity(v, cfg.vstamp[0], cfg.vstamp[1], out=v_stamped)
+        advect(d, v, dt, out=d_out, workspace=cfg.adv[n:] if mask is not None else cfg.adv, **how)
+    advect_velocity(v, dt, out=v_out, workspace=cfg.fwd, open_bound=osd, **how)
+    wall_buoyancy(v_out, d_out, cfg.force, bnd=bnd, out=v_out, obstacle=flags, open_bound=osd)
+    _, _, iters = solve_pressure(v_out, bnd=bnd, accuracy=cfg.accuracy, max_iter=cfg.max_iter, check_every=cfg.check_every, out=v_out,
+                                 workspace=cfg.pws, obstacle=flags, open_bound=osd)
     return iters
 
 
@@ -2413,15 +2408,10 @@ def smoke_step(density, vel, dt, source=None, force=None, order=2, clamp_mode=2,
     [B,D] or [D] values ``stamp_velocity`` writes) and ``force`` a tensor [B,D] it is the loop of scene/smoke3_vel_buo.py:222-232: density
     inflow, velocity stamp, both advections through the STAMPED velocity, walls, buoyancy, projection.  ``vel`` itself is never written."""
     with torch.no_grad():
-        d, v, nd = _advect_dims(density, vel)
-        osd = open_sides(open_bound, nd)
-        force = default_buoyancy_force(d.shape[1:], dt) if force is None else force
-        mask = _source_arg(source, d)
-        buf = _SmokeBuffers(d, v, order, mask is not None)
-        flags = _obstacle_arg(obstacle, d.shape, bnd, "smoke_step") if obstacle is not None else None
-        d_out, v_out = torch.empty_like(d), torch.empty_like(v)
-        _smoke_step(d, v, d_out, v_out, buf, dt, mask, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags, osd, time,
-                    _inflow_velocity_arg(inflow_velocity, v, nd))
+        cfg = _SmokeSettings("smoke_step", density, vel, None, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, obstacle,
+                             open_bound, inflow_velocity)
+        d_out, v_out = torch.empty_like(cfg.d), torch.empty_like(cfg.v)
+        _smoke_step(cfg, cfg.d, cfg.v, d_out, v_out, cfg.mask, time)
         return d_out, v_out
 
 
@@ -2435,25 +2425,16 @@ def _inflow_velocity_arg(inflow_velocity, v, nd):
     return shape, _entry_rows(values, v, nd, "inflow_velocity: values")
 
 
-def _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, stats, obstacle=None,
-                  open_bound=None, inflow_velocity=None):
-    d, v, nd = _advect_dims(density0, vel0)
-    osd = open_sides(open_bound, nd)
-    force = default_buoyancy_force(d.shape[1:], dt) if force is None else force
-    mask = _source_arg(source, d)
-    if isinstance(mask, SphereSource) and mask.centers.dim() == 3 and mask.centers.shape[0] < int(steps):
-        raise ValueError("simulate_smoke: %d frames of source centres for %d steps" % (mask.centers.shape[0], int(steps)))
-    buf = _SmokeBuffers(d, v, order, mask is not None)
-    flags = _obstacle_arg(obstacle, d.shape, bnd, "simulate_smoke") if obstacle is not None else None      # once per sequence
-    vstamp = _inflow_velocity_arg(inflow_velocity, v, nd)
-    if isinstance(force, torch.Tensor):
-        force = _entry_rows(force, v, nd, "simulate_smoke: force")                                         # on the device, once
-    d, v = d.clone(), v.clone()
+def _smoke_frames(steps, stats, settings):
+    cfg = settings()
+    nd, mask = cfg.v.dim() - 2, cfg.mask
+    if isinstance(cfg.force, torch.Tensor):
+        cfg.force = _entry_rows(cfg.force, cfg.v, nd, "simulate_smoke: force")                             # on the device, once
+    d, v = cfg.d.clone(), cfg.v.clone()
     d2, v2 = torch.empty_like(d), torch.empty_like(v)
     for t in range(int(steps)):
         # the working copy ``v`` is stamped in place (v_stamped=v): the caller's vel0 is never written
-        iters = _smoke_step(d, v, d2, v2, buf, dt, _source_frame(mask, t), force, order, clamp_mode, bnd, accuracy, max_iter, check_every, flags,
-                            osd, _source_time(mask, t, dt), vstamp, v)
+        iters = _smoke_step(cfg, d, v, d2, v2, _source_frame(mask, t), _source_time(mask, t, cfg.dt), v)
         if stats is not None:
             stats.append(iters)
         d, d2, v, v2 = d2, d, v2, v
@@ -2470,8 +2451,8 @@ def simulate_smoke(density0, vel0, steps, dt=0.5, source=None, force=None, order
     source is evaluated at ``t * dt`` in step t; ``inflow_velocity`` and a ``force`` tensor [B,D]: as for ``smoke_step`` (the stamp goes
     into the sequence's own working buffer)."""
     with torch.no_grad():
-        gen = _smoke_frames(density0, vel0, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, stats, obstacle,
-                            open_bound, inflow_velocity)
+        gen = _smoke_frames(steps, stats, lambda: _SmokeSettings("simulate_smoke", density0, vel0, steps, dt, source, force, order, clamp_mode, bnd,
+                                                                 accuracy, max_iter, check_every, obstacle, open_bound, inflow_velocity))
         if not stack:
             return _no_grad_iter(gen)
         vels = torch.empty((int(steps),) + tuple(vel0.shape), dtype=torch.float32, device=vel0.device)
@@ -2645,15 +2626,18 @@ def particle_levelset(pos, shape, radius_factor=1.0, out=None):
         return out
 
 
-def _levelset_averaged(spos, cell_start, out, tmp, B, N, shape, radius_factor, smooth, smooth_neg, bound_value, bnd):
-    """the launches of ``particle_levelset_averaged`` on sorted particles; ``tmp`` is a second buffer of ``out``'s shape (None without
-    smoothing passes).  The passes alternate between the two buffers and end in ``out``; the band is fused into the last one."""
+def _levelset_averaged(spos, cell_start, out, tmp, radius_factor, smooth, smooth_neg, bound_value, bnd):
+    """the launches of ``particle_levelset_averaged`` on sorted particles, into ``out`` [B,(Z,)Y,X]; ``tmp`` is a second buffer of its
+    shape (None without smoothing passes).  The passes alternate between the two buffers and end in ``out``; the band is fused into the
+    last one."""
+    dims = list(out.shape)
+    B, shape = dims[0], dims[1:]
     nd = len(shape)
-    dims = [B] + list(shape)
+    N = spos.numel() // (B * nd)
     passes = [1] * smooth + [2] * smooth_neg
     bufs = (out, tmp) if len(passes) % 2 == 0 else (tmp, out)
     cur = bufs[0]
-    call("df_particle_levelset_averaged%dd" % nd, _ptr(spos), _ptr(cell_start), _ptr(cur), B, N, *(list(shape) + [float(radius_factor), _stream()]))
+    call("df_particle_levelset_averaged%dd" % nd, _ptr(spos), _ptr(cell_start), _ptr(cur), B, N, *(shape + [float(radius_factor), _stream()]))
     for n, mode in enumerate(passes):
         nxt = bufs[(n + 1) % 2]
         call("df_levelset_smooth%dd" % nd, _ptr(cur), _ptr(nxt), *(dims + [mode, bnd if n == len(passes) - 1 else 0, float(bound_value), _stream()]))
@@ -2705,7 +2689,7 @@ def particle_levelset_averaged(pos, shape, radius_factor=1.0, smooth=1, smooth_n
                     or cell_start.numel() != B * int(np.prod(shape)) + 1):
                 raise ValueError("particle_levelset_averaged: cells[1] must be the int32 GPU tensor [B*ncell + 1] of particle_cells")
         tmp = torch.empty_like(out) if smooth + smooth_neg else None
-        return _levelset_averaged(spos, cell_start, out, tmp, B, N, shape, radius_factor, smooth, smooth_neg, bound_value, int(bnd))
+        return _levelset_averaged(spos, cell_start, out, tmp, radius_factor, smooth, smooth_neg, bound_value, int(bnd))
 
 
 def liquid_sequence(pos0, vels, dt, bnd=1, vel_scale=1.0, radius_factor=1.0, images=False):
@@ -2918,17 +2902,42 @@ def default_gravity_force(shape, dt, gravity=-1e-3):
     return tuple(f)
 
 
-def _cg_loop(direction, update, ws, nbytes, dims4, count, max_iter, check_every):
-    """the host loop of a solve: ``direction(k)`` and ``update(k)`` launch one iteration's two kernels; returns the last k"""
+_Solve = collections.namedtuple("_Solve", "ws nbytes status4 count iters acc max_iter check_every")
+
+
+def _solve_begin(who, v, nd, accuracy, max_iter, check_every, ws, diffusion=False):
+    """The head every solve shares: the iteration controls checked and defaulted, the workspace ``ws`` checked, and the words the host
+    reads -- the number of systems still iterating and their iteration counts.  A system is a batch entry, or, for a ``diffusion``, an
+    (entry, component) pair: ``df_pressure_status`` then runs over the B*D pairs."""
+    if not accuracy >= 0:
+        raise ValueError("%s: accuracy must be >= 0, got %r" % (who, accuracy))
+    dims, dims4 = _pressure_dims(v, nd)
+    if max_iter is None:
+        max_iter = (default_diffusion_max_iter if diffusion else default_max_iter)(dims[1:])
+    check_every = DEFAULT_CHECK_EVERY if check_every is None else int(check_every)
+    if max_iter < 0 or check_every < 1:
+        raise ValueError("%s: max_iter must be >= 0 and check_every >= 1, got %r, %r" % (who, max_iter, check_every))
+    if ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous():
+        raise ValueError("%s: workspace must be a contiguous float32 GPU tensor (%s_workspace)" % (who, "diffusion" if diffusion else "pressure"))
+    systems = dims[0] * (nd if diffusion else 1)
+    words = torch.empty((1 + systems,), dtype=torch.int32, device=v.device)
+    return _Solve(ws, ws.numel() * 4, [systems] + dims4[1:], words[:1], words[1:], float(accuracy), int(max_iter), check_every)
+
+
+def _cg_loop(direction, update, s):
+    """the host loop of a solve and its end: ``direction(k)`` and ``update(k)`` launch one iteration's two kernels, the host reads one
+    word every ``check_every`` iterations; returns the iteration counts of the systems (a copy)"""
     k = 0
     while True:
         direction(k)
-        if k % check_every == check_every - 1 or k >= max_iter:
-            call("df_pressure_status", _ptr(ws), nbytes, *(dims4 + [k, _ptr(count), None, _stream()]))
-            if _read_word(count) == 0:
-                return k
+        if k % s.check_every == s.check_every - 1 or k >= s.max_iter:
+            call("df_pressure_status", _ptr(s.ws), s.nbytes, *(s.status4 + [k, _ptr(s.count), None, _stream()]))
+            if _read_word(s.count) == 0:
+                break
         update(k)
         k += 1
+    call("df_pressure_status", _ptr(s.ws), s.nbytes, *(s.status4 + [k, None, _ptr(s.iters), _stream()]))
+    return s.iters.clone()
 
 
 def _gf_phi_arg(phi, vel, who):
@@ -2972,39 +2981,21 @@ def solve_pressure_liquid(vel, flags, bnd=1, accuracy=1e-4, max_iter=None, check
             phi = _gf_phi_arg(phi, vel, "solve_pressure_liquid")
         v, nd = _smoke_vel(vel, "solve_pressure_liquid")
         bnd = _liquid_bnd(bnd, "solve_pressure_liquid")
-        if not accuracy >= 0:
-            raise ValueError("solve_pressure_liquid: accuracy must be >= 0, got %r" % (accuracy,))
         fl = _liquid_flags_arg(flags, v, "solve_pressure_liquid")
-        dims, dims4 = _pressure_dims(v, nd)
-        if max_iter is None:
-            max_iter = default_max_iter(dims[1:])
-        check_every = DEFAULT_CHECK_EVERY if check_every is None else int(check_every)
-        if max_iter < 0 or check_every < 1:
-            raise ValueError("solve_pressure_liquid: max_iter must be >= 0 and check_every >= 1, got %r, %r" % (max_iter, check_every))
+        s = _solve_begin("solve_pressure_liquid", v, nd, accuracy, max_iter, check_every,
+                         workspace if workspace is not None else pressure_workspace(v, ghost_fluid=gf))
         out = _smoke_out(out, v, "solve_pressure_liquid")
-        ws = workspace if workspace is not None else pressure_workspace(v, ghost_fluid=gf)
-        if ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous():
-            raise ValueError("solve_pressure_liquid: workspace must be a contiguous float32 GPU tensor (pressure_workspace)")
-        nbytes = ws.numel() * 4
+        dims, ws, nbytes = list(v.shape[:-1]), s.ws, s.nbytes
         pressure = _empty(dims, v)
-        words = torch.empty((1 + dims[0],), dtype=torch.int32, device=v.device)
-        count, iters = words[:1], words[1:]
-        acc, max_iter = float(accuracy), int(max_iter)
-        if gf:
-            call("df_pressure_init%dd_gf" % nd, _ptr(v), _ptr(pressure), _ptr(ws), nbytes, _ptr(fl), _ptr(phi), *(dims + [bnd, gfc, _stream()]))
-            k = _cg_loop(lambda k: call("df_pressure_cg_direction%dd_gf" % nd, _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, acc, max_iter, _stream()])),
-                         lambda k: call("df_pressure_cg_update%dd_gf" % nd, _ptr(pressure), _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, _stream()])),
-                         ws, nbytes, dims4, count, max_iter, check_every)
-            call("df_pressure_status", _ptr(ws), nbytes, *(dims4 + [k, None, _ptr(iters), _stream()]))
-            call("df_pressure_correct%dd_gf" % nd, _ptr(v), _ptr(pressure), _ptr(out), _ptr(fl), _ptr(phi), *(dims + [bnd, gfc, _stream()]))
-            return out, pressure, iters.clone()
-        call("df_pressure_init%dd_flags" % nd, _ptr(v), _ptr(pressure), _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, _stream()]))
-        k = _cg_loop(lambda k: call("df_pressure_cg_direction%dd_liquid" % nd, _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, acc, max_iter, _stream()])),
-                     lambda k: call("df_pressure_cg_update%dd_flags" % nd, _ptr(pressure), _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, _stream()])),
-                     ws, nbytes, dims4, count, max_iter, check_every)
-        call("df_pressure_status", _ptr(ws), nbytes, *(dims4 + [k, None, _ptr(iters), _stream()]))
-        call("df_pressure_correct%dd_liquid" % nd, _ptr(v), _ptr(pressure), _ptr(out), _ptr(fl), *(dims + [bnd, _stream()]))
-        return out, pressure, iters.clone()
+        # the entry points' twins: `_gf` throughout with phi, which init and correct take after the flags, with the clamp after bnd
+        sfx, twin = "%dd_" % nd, ("gf", "gf") if gf else ("flags", "liquid")
+        surface = [_ptr(fl)] + ([_ptr(phi)] if gf else []) + dims + [bnd] + ([gfc] if gf else [])
+        call("df_pressure_init" + sfx + twin[0], _ptr(v), _ptr(pressure), _ptr(ws), nbytes, *(surface + [_stream()]))
+        iters = _cg_loop(
+            lambda k: call("df_pressure_cg_direction" + sfx + twin[1], _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, s.acc, s.max_iter, _stream()])),
+            lambda k: call("df_pressure_cg_update" + sfx + twin[0], _ptr(pressure), _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, _stream()])), s)
+        call("df_pressure_correct" + sfx + twin[1], _ptr(v), _ptr(pressure), _ptr(out), *(surface + [_stream()]))
+        return out, pressure, iters
 
 
 # ---- implicit velocity diffusion: cgSolveDiffusion of the viscous liquid scene (scene/liquid3_vis.py:277-281), the definition of
@@ -3058,41 +3049,25 @@ def diffuse_velocity(vel, alpha, bnd=1, accuracy=1e-4, max_iter=None, check_ever
             raise ValueError("diffuse_velocity: vel must be a contiguous float32 GPU tensor [B,(Z,)Y,X,D]")
         v, nd = _smoke_vel(vel, "diffuse_velocity")
         bnd = _liquid_bnd(bnd, "diffuse_velocity")
-        if not accuracy >= 0:
-            raise ValueError("diffuse_velocity: accuracy must be >= 0, got %r" % (accuracy,))
-        dims, dims4 = _pressure_dims(v, nd)
-        B = dims[0]
-        a32 = _diffusion_alpha_arg(alpha, B, "diffuse_velocity")
-        if max_iter is None:
-            max_iter = default_diffusion_max_iter(dims[1:])
-        check_every = DEFAULT_CHECK_EVERY if check_every is None else int(check_every)
-        if max_iter < 0 or check_every < 1:
-            raise ValueError("diffuse_velocity: max_iter must be >= 0 and check_every >= 1, got %r, %r" % (max_iter, check_every))
+        a32 = _diffusion_alpha_arg(alpha, v.shape[0], "diffuse_velocity")
+        s = _solve_begin("diffuse_velocity", v, nd, accuracy, max_iter, check_every, workspace if workspace is not None else diffusion_workspace(v),
+                         diffusion=True)
         out = _smoke_out(out, v, "diffuse_velocity")
-        ws = workspace if workspace is not None else diffusion_workspace(v)
-        if ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous():
-            raise ValueError("diffuse_velocity: workspace must be a contiguous float32 GPU tensor (diffusion_workspace)")
-        nbytes = ws.numel() * 4
-        need = query("df_diffuse_workspace_bytes", *([int(x) for x in dims4] + [nd]))
-        if need < 0 or nbytes < need:
+        need = query("df_diffuse_workspace_bytes", *([int(x) for x in _pressure_dims(v, nd)[1]] + [nd]))
+        if need < 0 or s.nbytes < need:
             raise ValueError("diffuse_velocity: unsupported extents %s or a workspace of %d bytes where %d are needed (diffusion_workspace)"
-                             % (tuple(v.shape), nbytes, need))
-        return _diffuse(v, torch.from_numpy(a32).to(v.device), out, ws, nbytes, nd, dims, dims4, bnd, float(accuracy), int(max_iter), check_every)
+                             % (tuple(v.shape), s.nbytes, need))
+        return _diffuse(v, torch.from_numpy(a32).to(v.device), out, bnd, s)
 
 
-def _diffuse(v, al, out, ws, nbytes, nd, dims, dims4, bnd, acc, max_iter, check_every):
-    """the launches of ``diffuse_velocity``; ``al`` [B] float32 on the device"""
-    B = dims[0]
-    pairs4 = [B * nd] + dims4[1:]                            # df_pressure_status over the B*D pairs
-    words = torch.empty((1 + B * nd,), dtype=torch.int32, device=v.device)
-    count, iters = words[:1], words[1:]
+def _diffuse(v, al, out, bnd, s):
+    """the launches of ``diffuse_velocity``; ``al`` [B] float32 on the device, ``s`` the ``_solve_begin`` of a diffusion"""
+    nd, dims, ws, nbytes = v.dim() - 2, list(v.shape[:-1]), s.ws, s.nbytes
     call("df_diffuse_init%dd" % nd, _ptr(v), _ptr(al), _ptr(ws), nbytes, *(dims + [bnd, _stream()]))
-    k = _cg_loop(lambda k: call("df_diffuse_cg_direction%dd" % nd, _ptr(al), _ptr(ws), nbytes, *(dims + [bnd, k, acc, max_iter, _stream()])),
-                 lambda k: call("df_diffuse_cg_update%dd" % nd, _ptr(ws), nbytes, *(dims + [bnd, k, _stream()])),
-                 ws, nbytes, pairs4, count, max_iter, check_every)
-    call("df_pressure_status", _ptr(ws), nbytes, *(pairs4 + [k, None, _ptr(iters), _stream()]))
+    iters = _cg_loop(lambda k: call("df_diffuse_cg_direction%dd" % nd, _ptr(al), _ptr(ws), nbytes, *(dims + [bnd, k, s.acc, s.max_iter, _stream()])),
+                     lambda k: call("df_diffuse_cg_update%dd" % nd, _ptr(ws), nbytes, *(dims + [bnd, k, _stream()])), s)
     call("df_diffuse_finish%dd" % nd, _ptr(ws), nbytes, _ptr(out), *(dims + [bnd, _stream()]))
-    return out, iters.clone().reshape(B, nd)
+    return out, iters.reshape(dims[0], nd)
 
 
 def flip_update(pos, pvel, vel, vel_old, flip_ratio=DEFAULT_FLIP_RATIO, out=None, entry_start=None):
@@ -3175,22 +3150,27 @@ def extrapolate_levelset(phi, distance=4, inside=True, out=None):
         return out
 
 
-def _resample_launch(sp, su, cell_start, ph, fl, v, B, N, shape, bnd, min_particles, max_particles, radius_factor, seed, step):
-    """the launches of ``resample_particles`` on checked arguments: ``(pos, pvel, entry_start, cell_start, keep, kept, seeds)``; the
-    wanted total is ``cell_start[-1]``, still on the device"""
-    nd = len(shape)
+_Resampled = collections.namedtuple("_Resampled", "pos pvel entry_start cell_start keep kept seeds")
+
+
+def _resample_launch(sp, su, cell_start, ph, fl, v, bnd, radius_factor, rs):
+    """the launches of ``resample_particles`` on checked arguments, ``rs`` a ``Resample`` (its counts, seed and step); the wanted total is
+    the result's ``cell_start[-1]``, still on the device"""
+    shape = tuple(v.shape[1:-1])
+    nd, B = len(shape), v.shape[0]
+    N = sp.shape[0] // B
     ncell = int(np.prod(shape))
     keep = torch.zeros((B * N,), dtype=torch.uint8, device=v.device)
     counts = torch.empty((2, B * ncell), dtype=torch.int32, device=v.device)
     kept, seeds = counts[0], counts[1]
     call("df_resample_count%dd" % nd, _ptr(sp), _ptr(cell_start), _ptr(ph), _ptr(fl), _ptr(keep), _ptr(kept), _ptr(seeds), B, N,
-         *(list(shape) + [bnd, min_particles, max_particles, float(radius_factor), _stream()]))
+         *(list(shape) + [bnd, rs.min_particles, rs.max_particles, float(radius_factor), _stream()]))
     new_start = torch.zeros((B * ncell + 1,), dtype=torch.int32, device=v.device)
     torch.cumsum(kept + seeds, 0, dtype=torch.int32, out=new_start[1:])
     pos_out, pvel_out = torch.empty_like(sp), torch.empty_like(su)
     call("df_resample_scatter%dd" % nd, _ptr(sp), _ptr(su), _ptr(cell_start), _ptr(keep), _ptr(seeds), _ptr(new_start), _ptr(v), _ptr(pos_out),
-         _ptr(pvel_out), B, N, *(list(shape) + [min_particles, int(seed) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF, _stream()]))
-    return pos_out, pvel_out, new_start[::ncell].contiguous(), new_start, keep, kept, seeds
+         _ptr(pvel_out), B, N, *(list(shape) + [rs.min_particles, rs.seed & 0xFFFFFFFF, rs.step & 0xFFFFFFFF, _stream()]))
+    return _Resampled(pos_out, pvel_out, new_start[::ncell].contiguous(), new_start, keep, kept, seeds)
 
 
 def _resample_counts_arg(min_particles, max_particles, who):
@@ -3233,12 +3213,11 @@ def resample_particles(spos, spvel, cell_start, entry_start, phi, flags, vel, mi
         ncell = int(np.prod(shape))
         if cell_start.dtype != torch.int32 or not cell_start.is_cuda or not cell_start.is_contiguous() or cell_start.numel() != B * ncell + 1:
             raise ValueError("resample_particles: cell_start must be the int32 GPU tensor [B*ncell + 1] of particle_cells")
-        pos_out, pvel_out, new_es, new_start, keep, kept, seeds = _resample_launch(
-            p.view(-1, nd), u, cell_start, ph, fl, v, B, N, shape, bnd, min_particles, max_particles, radius_factor, seed, step)
-        _resample_check(new_start, B * N, B, "resample_particles")
+        new = _resample_launch(p.view(-1, nd), u, cell_start, ph, fl, v, bnd, radius_factor, Resample(min_particles, max_particles, seed, step=step))
+        _resample_check(new.cell_start, B * N, B, "resample_particles")
         if details:
-            return pos_out, pvel_out, new_es, new_start, (keep, kept, seeds)
-        return pos_out, pvel_out, new_es, new_start
+            return new.pos, new.pvel, new.entry_start, new.cell_start, (new.keep, new.kept, new.seeds)
+        return new.pos, new.pvel, new.entry_start, new.cell_start
 
 
 def _resample_check(new_start, P, B, who):
@@ -3247,45 +3226,6 @@ def _resample_check(new_start, P, B, who):
     if total > P:
         raise _lib.DeepFluidsHipError("%s: the resampled batch holds %d particles but the storage has P = %d rows; it needs a capacity of at "
                                       "least %d (a multiple of B = %d)" % (who, total, P, -(-total // B) * B, B))
-
-
-def _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws, visc=None, gf=None):
-    """``visc``: None, or (alpha [B] float32 on the device, the diffusion workspace): the viscous step of scene/liquid3_vis.py:256-296;
-    the iteration counts [B, D] of its diffusion are then returned as a fifth element.  ``gf``: None, or (radius_factor, gf_clamp, two
-    phi buffers): the averaged level set of the step's sorted particles right after the flags, handed to the solve"""
-    nd = p.shape[-1]
-    shape = tuple(v.shape[1:-1])
-    B, N = p.shape[0], p.shape[1]
-    moved = advect_particles(p, v, dt, bnd=bnd)
-    spos, cell_start, order = particle_cells(moved, shape)
-    su = torch.empty_like(u)
-    call("df_particles_gather", _ptr(u), _ptr(order), _ptr(su), B * N, nd, _stream())
-    vel, weight, known = particles_to_grid(spos, su, cell_start, shape)
-    vel_old = vel                                            # extrapolate_mac leaves its input untouched
-    vel, _ = extrapolate_mac(vel, known, 2, bnd=bnd)
-    flags, touch = liquid_flags(cell_start, shape, B, N, bnd=bnd)
-    phi = None
-    if gf is not None:
-        # averagedParticleLevelset(.., radius_factor, 1, 1) and phi.setBound(1, bWidth), from the sort above: no second sort
-        phi = _levelset_averaged(spos, cell_start, gf[2], gf[3], B, N, shape, gf[0], 1, 1, 1.0, bnd)
-    if visc is not None:
-        # setWallBcs as a zero-force pass (+ 0.0 leaves a value's bits but for -0), then cgSolveDiffusion: the step's accuracy, the
-        # iteration cap of cgSolveDiffusion's own default (max_iter is the pressure solve's)
-        liquid_forces(vel, flags, (0.0,) * nd, bnd=bnd, out=vel)
-        dims, dims4 = _pressure_dims(vel, nd)
-        _, diters = _diffuse(vel, visc[0], vel, visc[1], visc[1].numel() * 4, nd, dims, dims4, bnd, float(accuracy),
-                             default_diffusion_max_iter(shape), DEFAULT_CHECK_EVERY if check_every is None else int(check_every))
-    liquid_forces(vel, flags, force, bnd=bnd, out=vel)
-    if phi is None:
-        _, _, iters = solve_pressure_liquid(vel, flags, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=vel, workspace=pws)
-    else:
-        _, _, iters = solve_pressure_liquid(vel, flags, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=vel,
-                                            workspace=pws, phi=phi, gf_clamp=gf[1])
-    vel, _ = extrapolate_mac(vel, touch, 4, bnd=bnd)
-    flip_update(spos, su, vel, vel_old, flip_ratio=flip_ratio, out=su)
-    if visc is not None:
-        return spos, su, vel, iters, diters
-    return spos, su, vel, iters
 
 
 class Resample(object):
@@ -3302,18 +3242,63 @@ class Resample(object):
         self.capacity = None if capacity is None else int(capacity)
 
 
-def _resample_arg(resample, who):
-    if resample is not None and not isinstance(resample, Resample):
-        raise ValueError("%s: resample must be None or an ops.Resample, got %r" % (who, type(resample)))
-    return resample
+class _LiquidSettings(object):
+    """What a liquid step needs besides its state, built once per ``liquid_step`` call or ``simulate_liquid`` sequence (``who``).  The
+    constructor keeps the call's scalars and refuses what can be refused before any tensor is touched; ``prepare(vel)`` then allocates
+    what the options need and nothing else: the device ``alpha`` and the diffusion workspace (``viscosity_alpha``), the two phi buffers
+    (``ghost_fluid`` or ``resample``), the pressure workspace (ghost-fluid-sized only with ``ghost_fluid``).  ``rs`` is the ``Resample``."""
+
+    def __init__(self, who, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, open_bound, viscosity_alpha, ghost_fluid, radius_factor,
+                 gf_clamp, resample, entry_start):
+        if open_bound:
+            raise NotImplementedError("%s: open sides (resetOutflow) are not implemented for the liquid solver" % who)
+        if ghost_fluid:
+            _gf_clamp_arg(gf_clamp, who)
+        if resample is not None and not isinstance(resample, Resample):
+            raise ValueError("%s: resample must be None or an ops.Resample, got %r" % (who, type(resample)))
+        if resample is None and entry_start is not None:
+            raise ValueError("%s: entry_start (a ragged state) needs resample=" % who)
+        if (resample is not None or ghost_fluid) and not 0.0 <= radius_factor <= 1024.0:
+            raise ValueError("%s: radius_factor must lie in [0, 1024], got %r" % (who, radius_factor))
+        self.who, self.rs, self.dt, self.force, self.bnd = who, resample, dt, force, bnd
+        self.accuracy, self.max_iter, self.check_every, self.flip_ratio = accuracy, max_iter, check_every, flip_ratio
+        self.viscosity_alpha, self.ghost_fluid, self.radius_factor, self.gf_clamp = viscosity_alpha, bool(ghost_fluid), radius_factor, gf_clamp
+
+    def prepare(self, v):
+        self.bnd = _liquid_bnd(self.bnd, self.who)
+        if self.force is None:
+            self.force = default_gravity_force(v.shape[1:-1], self.dt)
+        self.phi = self.phi_tmp = self.alpha = self.dws = None
+        if self.ghost_fluid or self.rs is not None:
+            self.phi = _empty(tuple(v.shape[:-1]), v)
+            self.phi_tmp = torch.empty_like(self.phi)
+        self.pws = pressure_workspace(v, self.ghost_fluid)
+        if self.viscosity_alpha is not None:
+            self.alpha = torch.from_numpy(_diffusion_alpha_arg(self.viscosity_alpha, v.shape[0], self.who)).to(v.device)
+            self.dws = diffusion_workspace(v)
+
+    def frame(self, r, counts=False):
+        """the public tuple of a ``_LiquidResult``: ``(pos, pvel, vel[, iterations[, diffusion_iterations]][, entry_start])``"""
+        out = (r.pos, r.pvel, r.vel)
+        if counts:
+            out += (r.iters,) if r.diters is None else (r.iters, r.diters)
+        return out if self.rs is None else out + (r.entry_start,)
 
 
-def _ragged_state(pos, pvel, vel, entry_start, rs, who):
-    """the ragged state ``(pos [P,D], pvel [P,D], entry_start, vel)`` a step with ``resample`` runs on: a dense [B,N,D] input is packed
-    (entry b in rows b*N ..), a ragged one is moved into storage of ``rs.capacity`` rows if it has another size"""
+def _liquid_state(pos, pvel, vel, entry_start, cfg):
+    """the checked state ``(pos, pvel, vel, entry_start)`` a step runs on: dense [B,N,D] with ``entry_start`` None, or, with ``resample``,
+    ragged [P,D] -- a dense input is packed (entry b in rows b*N ..), a ragged one is moved into storage of ``capacity`` rows if it has
+    another size"""
+    who, rs = cfg.who, cfg.rs
     if entry_start is None:
-        p, u, v = _liquid_state(pos, pvel, vel, who)
+        p = _particle_pos(pos, who)
+        u = _particle_pos(pvel, who)
+        if tuple(u.shape) != tuple(p.shape):
+            raise ValueError("%s: particle velocities %s for positions %s" % (who, tuple(u.shape), tuple(p.shape)))
         B, N, nd = p.shape
+        v = _liquid_vel(vel, B, nd, who)
+        if rs is None:
+            return p, u, v, None
         live = B * N
         es = torch.arange(B + 1, dtype=torch.int32, device=p.device) * N
         p, u = p.reshape(-1, nd), u.reshape(-1, nd)
@@ -3341,75 +3326,58 @@ def _ragged_state(pos, pvel, vel, entry_start, rs, who):
         np_, nu = torch.zeros((P, nd), dtype=torch.float32, device=p.device), torch.zeros((P, nd), dtype=torch.float32, device=p.device)
         np_[:live], nu[:live] = p[:live], u[:live]
         p, u = np_, nu
-    return p, u, es, v
+    return p, u, v, es
 
 
-def _liquid_step_resample(p, u, es, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws, visc, gf, rs, radius_factor, phis, step):
-    """``_liquid_step`` on a ragged state with the script's extrapolateLsSimple and adjustNumber: ``phis`` two phi buffers, ``gf`` as in
-    ``_liquid_step`` (only its clamp is read: phi is computed whenever the step resamples); returns (pos, pvel, vel, iters[, diters],
-    entry_start, cell_start).  The wanted total is ``cell_start[-1]``, still on the device: the caller checks it."""
-    nd = p.shape[-1]
+_LiquidResult = collections.namedtuple("_LiquidResult", "pos pvel vel iters diters entry_start cell_start")
+
+
+def _liquid_step(p, u, v, es, cfg):
+    """One step on the dense state ``p``, ``u`` [B,N,D] (``es`` None: the dense kernels) or on the ragged one [P,D] with its
+    ``entry_start`` ``es`` (``cfg.rs`` set: the script's extrapolateLsSimple and adjustNumber run too), ``cfg`` a prepared
+    ``_LiquidSettings``.  Fields of the result that do not apply are None: ``diters`` [B, D] without ``viscosity_alpha``; ``entry_start``
+    and ``cell_start`` without ``resample`` -- the total the resampling wanted is ``cell_start[-1]``, still on the device: the caller
+    checks it."""
+    nd, bnd, rs = p.shape[-1], cfg.bnd, cfg.rs
     shape = tuple(v.shape[1:-1])
-    B = es.numel() - 1
-    N = p.shape[0] // B
-    moved = advect_particles(p, v, dt, bnd=bnd, entry_start=es)
+    B = v.shape[0]
+    N = p.numel() // (B * nd)
+    moved = advect_particles(p, v, cfg.dt, bnd=bnd, entry_start=es)
     spos, cell_start, order = particle_cells(moved, shape, entry_start=es)
     su = torch.empty_like(u)
     call("df_particles_gather", _ptr(u), _ptr(order), _ptr(su), B * N, nd, _stream())
     vel, weight, known = particles_to_grid(spos.view(B, N, nd), su.view(B, N, nd), cell_start, shape)
-    vel_old = vel
+    vel_old = vel                                            # extrapolate_mac leaves its input untouched
     vel, _ = extrapolate_mac(vel, known, 2, bnd=bnd)
     flags, touch = liquid_flags(cell_start, shape, B, N, bnd=bnd)
-    phi = _levelset_averaged(spos, cell_start, phis[0], phis[1], B, N, shape, radius_factor, 1, 1, 1.0, bnd)
-    extrapolate_levelset(phi, 4, True, out=phi)
+    phi = None
+    if cfg.phi is not None:
+        # averagedParticleLevelset(.., radius_factor, 1, 1) and phi.setBound(1, bWidth), from the sort above: no second sort; computed
+        # whenever the step resamples, and then extrapolated before the solve sees it
+        phi = _levelset_averaged(spos, cell_start, cfg.phi, cfg.phi_tmp, cfg.radius_factor, 1, 1, 1.0, bnd)
+        if rs is not None:
+            extrapolate_levelset(phi, 4, True, out=phi)
     diters = None
-    if visc is not None:
+    if cfg.alpha is not None:
+        # the viscous step of scene/liquid3_vis.py:256-296: setWallBcs as a zero-force pass (+ 0.0 leaves a value's bits but for -0),
+        # then cgSolveDiffusion: the step's accuracy, the iteration cap of cgSolveDiffusion's own default (max_iter is the pressure solve's)
         liquid_forces(vel, flags, (0.0,) * nd, bnd=bnd, out=vel)
-        dims, dims4 = _pressure_dims(vel, nd)
-        _, diters = _diffuse(vel, visc[0], vel, visc[1], visc[1].numel() * 4, nd, dims, dims4, bnd, float(accuracy),
-                             default_diffusion_max_iter(shape), DEFAULT_CHECK_EVERY if check_every is None else int(check_every))
-    liquid_forces(vel, flags, force, bnd=bnd, out=vel)
-    if gf is None:
-        _, _, iters = solve_pressure_liquid(vel, flags, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=vel, workspace=pws)
-    else:
-        _, _, iters = solve_pressure_liquid(vel, flags, bnd=bnd, accuracy=accuracy, max_iter=max_iter, check_every=check_every, out=vel,
-                                            workspace=pws, phi=phi, gf_clamp=gf[1])
-    # pVel.setSource(vel, isMAC=True) + adjustNumber against the projected velocity, then extrapolateMACSimple and the FLIP update on
-    # old and new particles alike
-    npos, npvel, nes, ncs = _resample_launch(spos, su, cell_start, phi, flags, vel, B, N, shape, bnd, rs.min_particles, rs.max_particles,
-                                             radius_factor, rs.seed, step)[:4]
+        _, diters = _diffuse(vel, cfg.alpha, vel, bnd, _solve_begin(cfg.who, vel, nd, cfg.accuracy, None, cfg.check_every, cfg.dws, diffusion=True))
+    liquid_forces(vel, flags, cfg.force, bnd=bnd, out=vel)
+    surface = dict(phi=phi, gf_clamp=cfg.gf_clamp) if cfg.ghost_fluid else dict()
+    _, _, iters = solve_pressure_liquid(vel, flags, bnd=bnd, accuracy=cfg.accuracy, max_iter=cfg.max_iter, check_every=cfg.check_every, out=vel,
+                                        workspace=cfg.pws, **surface)
+    if rs is not None:
+        # pVel.setSource(vel, isMAC=True) + adjustNumber against the projected velocity, then extrapolateMACSimple and the FLIP update on
+        # old and new particles alike
+        new = _resample_launch(spos, su, cell_start, phi, flags, vel, bnd, cfg.radius_factor, rs)
+        spos, su, es, cell_start = new.pos, new.pvel, new.entry_start, new.cell_start
     vel, _ = extrapolate_mac(vel, touch, 4, bnd=bnd)
-    flip_update(npos, npvel, vel, vel_old, flip_ratio=flip_ratio, out=npvel, entry_start=nes)
-    if diters is not None:
-        return npos, npvel, vel, iters, diters, nes, ncs
-    return npos, npvel, vel, iters, nes, ncs
-
-
-def _liquid_state(pos, pvel, vel, who):
-    p = _particle_pos(pos, who)
-    u = _particle_pos(pvel, who)
-    if tuple(u.shape) != tuple(p.shape):
-        raise ValueError("%s: particle velocities %s for positions %s" % (who, tuple(u.shape), tuple(p.shape)))
-    v = _liquid_vel(vel, p.shape[0], p.shape[-1], who)
-    return p, u, v
-
-
-def _viscosity_arg(viscosity_alpha, v, who):
-    """None, or (alpha [B] float32 on the device, the diffusion workspace) for ``_liquid_step``"""
-    if viscosity_alpha is None:
-        return None
-    a32 = _diffusion_alpha_arg(viscosity_alpha, v.shape[0], who)
-    return torch.from_numpy(a32).to(v.device), diffusion_workspace(v)
-
-
-def _ghost_fluid_arg(ghost_fluid, radius_factor, gf_clamp, v, who):
-    """None, or (radius_factor, gf_clamp, two phi buffers) for ``_liquid_step``"""
-    if not ghost_fluid:
-        return None
-    if not 0.0 <= radius_factor <= 1024.0:
-        raise ValueError("%s: radius_factor must lie in [0, 1024], got %r" % (who, radius_factor))
-    phi = _empty(tuple(v.shape[:-1]), v)
-    return float(radius_factor), _gf_clamp_arg(gf_clamp, who), phi, torch.empty_like(phi)
+    flip_update(spos, su, vel, vel_old, flip_ratio=cfg.flip_ratio, out=su, entry_start=es)
+    if rs is None:
+        return _LiquidResult(spos, su, vel, iters, diters, None, None)
+    rs.step += 1
+    return _LiquidResult(spos, su, vel, iters, diters, es, cell_start)
 
 
 def liquid_step(pos, pvel, vel, dt, force=None, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, flip_ratio=DEFAULT_FLIP_RATIO,
@@ -3438,76 +3406,32 @@ def liquid_step(pos, pvel, vel, dt, force=None, bnd=1, accuracy=1e-4, max_iter=N
     the 4-layer extrapolation; the FLIP update on old and new particles alike.  The result is ``(pos [P,D], pvel [P,D], vel,
     iterations[, diffusion_iterations], entry_start)``; a state that does not fit the capacity raises before the step returns.  With
     ``None`` nothing of this is launched and every result keeps its bits."""
-    if open_bound:
-        raise NotImplementedError("liquid_step: open sides (resetOutflow) are not implemented for the liquid solver")
-    if ghost_fluid:
-        _gf_clamp_arg(gf_clamp, "liquid_step")
-    rs = _resample_arg(resample, "liquid_step")
-    if rs is None and entry_start is not None:
-        raise ValueError("liquid_step: entry_start (a ragged state) needs resample=")
-    if rs is not None:
-        if not 0.0 <= radius_factor <= 1024.0:
-            raise ValueError("liquid_step: radius_factor must lie in [0, 1024], got %r" % (radius_factor,))
-        with torch.no_grad():
-            p, u, es, v = _ragged_state(pos, pvel, vel, entry_start, rs, "liquid_step")
-            bnd = _liquid_bnd(bnd, "liquid_step")
-            force = default_gravity_force(v.shape[1:-1], dt) if force is None else force
-            visc = _viscosity_arg(viscosity_alpha, v, "liquid_step")
-            gf = _ghost_fluid_arg(ghost_fluid, radius_factor, gf_clamp, v, "liquid_step")
-            phis = gf[2:] if gf is not None else (_empty(tuple(v.shape[:-1]), v), _empty(tuple(v.shape[:-1]), v))
-            out = _liquid_step_resample(p, u, es, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio,
-                                        pressure_workspace(v, gf is not None), visc, gf, rs, float(radius_factor), phis, rs.step)
-            rs.step += 1
-            _resample_check(out[-1], p.shape[0], es.numel() - 1, "liquid_step")
-            return out[:-1]
+    cfg = _LiquidSettings("liquid_step", dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, open_bound, viscosity_alpha, ghost_fluid,
+                          radius_factor, gf_clamp, resample, entry_start)
     with torch.no_grad():
-        p, u, v = _liquid_state(pos, pvel, vel, "liquid_step")
-        bnd = _liquid_bnd(bnd, "liquid_step")
-        force = default_gravity_force(v.shape[1:-1], dt) if force is None else force
-        visc = _viscosity_arg(viscosity_alpha, v, "liquid_step")
-        gf = _ghost_fluid_arg(ghost_fluid, radius_factor, gf_clamp, v, "liquid_step")
-        return _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pressure_workspace(v, gf is not None), visc, gf)
+        p, u, v, es = _liquid_state(pos, pvel, vel, entry_start, cfg)
+        cfg.prepare(v)
+        r = _liquid_step(p, u, v, es, cfg)
+        if cfg.rs is not None:
+            _resample_check(r.cell_start, p.shape[0], v.shape[0], "liquid_step")
+        return cfg.frame(r, counts=True)
 
 
-def _liquid_frames_resample(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats, viscosity_alpha,
-                            keep_every, ghost_fluid, radius_factor, gf_clamp, rs, entry_start):
-    p, u, es, v = _ragged_state(pos0, pvel0, vel0, entry_start, rs, "simulate_liquid")
-    bnd = _liquid_bnd(bnd, "simulate_liquid")
-    force = default_gravity_force(v.shape[1:-1], dt) if force is None else force
-    gf = _ghost_fluid_arg(ghost_fluid, radius_factor, gf_clamp, v, "simulate_liquid")
-    phis = gf[2:] if gf is not None else (_empty(tuple(v.shape[:-1]), v), _empty(tuple(v.shape[:-1]), v))
-    pws = pressure_workspace(v, gf is not None)
-    visc = _viscosity_arg(viscosity_alpha, v, "simulate_liquid")
-    B = es.numel() - 1
+def _liquid_frames(pos0, pvel0, vel0, entry_start, steps, keep_every, stats, cfg):
+    """the kept steps' ``_LiquidResult`` of ``steps`` chained steps"""
+    p, u, v, es = _liquid_state(pos0, pvel0, vel0, entry_start, cfg)
+    cfg.prepare(v)
     for t in range(int(steps)):
-        out = _liquid_step_resample(p, u, es, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws, visc, gf, rs,
-                                    float(radius_factor), phis, rs.step)
-        rs.step += 1
-        p, u, v, iters, es = out[0], out[1], out[2], out[3], out[-2]
+        r = _liquid_step(p, u, v, es, cfg)
+        p, u, v, es = r.pos, r.pvel, r.vel, r.entry_start
         if stats is not None:
-            stats.append(iters)
-        if t % keep_every == 0 or t == int(steps) - 1:
+            stats.append(r.iters)
+        if cfg.rs is not None and (t % keep_every == 0 or t == int(steps) - 1):
             # a state that did not fit is refused at every kept frame and after the last step; between them a step that follows an
             # overflow reads clamped ranges only, and its result is never handed out
-            _resample_check(out[-1], p.shape[0], B, "simulate_liquid")
+            _resample_check(r.cell_start, p.shape[0], v.shape[0], cfg.who)
         if t % keep_every == 0:
-            yield p, u, v, es
-
-
-def _liquid_frames(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats, viscosity_alpha=None,
-                   keep_every=1, ghost_fluid=False, radius_factor=1.0, gf_clamp=1e-4):
-    p, u, v = _liquid_state(pos0, pvel0, vel0, "simulate_liquid")
-    bnd = _liquid_bnd(bnd, "simulate_liquid")
-    force = default_gravity_force(v.shape[1:-1], dt) if force is None else force
-    gf = _ghost_fluid_arg(ghost_fluid, radius_factor, gf_clamp, v, "simulate_liquid")
-    pws = pressure_workspace(v, gf is not None)
-    visc = _viscosity_arg(viscosity_alpha, v, "simulate_liquid")
-    for t in range(int(steps)):
-        p, u, v, iters = _liquid_step(p, u, v, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, pws, visc, gf)[:4]
-        if stats is not None:
-            stats.append(iters)
-        if t % keep_every == 0:
-            yield p, u, v
+            yield r
 
 
 def simulate_liquid(pos0, pvel0, vel0, steps, dt=0.5, force=None, bnd=1, accuracy=1e-4, max_iter=None, check_every=None,
@@ -3521,41 +3445,21 @@ def simulate_liquid(pos0, pvel0, vel0, steps, dt=0.5, force=None, bnd=1, accurac
     the LAST step.  ``ghost_fluid``, ``radius_factor``, ``gf_clamp``: as in ``liquid_step``.  ``resample`` (and ``entry_start`` for a
     ragged start): as in ``liquid_step``; the state is ragged, the result is ``(pos [P,D], pvel [P,D], vels, entry_start)`` or a generator
     of ``(pos, pvel, vel, entry_start)``, and a state that does not fit the capacity raises at the next kept frame at the latest."""
-    if open_bound:
-        raise NotImplementedError("simulate_liquid: open sides (resetOutflow) are not implemented for the liquid solver")
     keep_every = int(keep_every)
     if keep_every < 1:
         raise ValueError("simulate_liquid: keep_every must be >= 1, got %r" % (keep_every,))
-    if ghost_fluid:
-        _gf_clamp_arg(gf_clamp, "simulate_liquid")
-    rs = _resample_arg(resample, "simulate_liquid")
-    if rs is None and entry_start is not None:
-        raise ValueError("simulate_liquid: entry_start (a ragged state) needs resample=")
-    if rs is not None:
-        if not 0.0 <= radius_factor <= 1024.0:
-            raise ValueError("simulate_liquid: radius_factor must lie in [0, 1024], got %r" % (radius_factor,))
-        with torch.no_grad():
-            gen = _liquid_frames_resample(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats,
-                                          viscosity_alpha, keep_every, ghost_fluid, radius_factor, gf_clamp, rs, entry_start)
-            if not stack:
-                return _no_grad_iter(gen)
-            kept = (int(steps) + keep_every - 1) // keep_every
-            vels = torch.empty((kept,) + tuple(vel0.shape), dtype=torch.float32, device=vel0.device)
-            p, u, es = pos0, pvel0, entry_start
-            for t, (p, u, v, es) in enumerate(gen):
-                vels[t].copy_(v)
-            return p, u, vels, es
+    cfg = _LiquidSettings("simulate_liquid", dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, open_bound, viscosity_alpha, ghost_fluid,
+                          radius_factor, gf_clamp, resample, entry_start)
     with torch.no_grad():
-        gen = _liquid_frames(pos0, pvel0, vel0, steps, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, stats, viscosity_alpha,
-                             keep_every, ghost_fluid, radius_factor, gf_clamp)
+        gen = _liquid_frames(pos0, pvel0, vel0, entry_start, steps, keep_every, stats, cfg)
         if not stack:
-            return _no_grad_iter(gen)
+            return _no_grad_iter(cfg.frame(r) for r in gen)
         kept = (int(steps) + keep_every - 1) // keep_every
         vels = torch.empty((kept,) + tuple(vel0.shape), dtype=torch.float32, device=vel0.device)
-        p, u = pos0, pvel0
-        for t, (p, u, v) in enumerate(gen):
-            vels[t].copy_(v)
-        return p, u, vels
+        last = _LiquidResult(pos0, pvel0, vels, None, None, entry_start, None)                            # steps == 0: the inputs
+        for t, last in enumerate(gen):
+            vels[t].copy_(last.vel)
+        return cfg.frame(last._replace(vel=vels))
 
 
 def liquid_initial_state(shape, phi0, vel_spheres=(), discretization=2, randomness=0.05, seed=123, bnd=1, device="cuda"):

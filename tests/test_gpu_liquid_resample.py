@@ -311,9 +311,34 @@ def test_three_chained_steps_with_resample(case):
             ops.liquid_step(dp, du, dv, rr.STEP_DT, resample=ops.Resample(minp, capacity=rr.B * n), **kw)
 
 
+def _composed_dense_step(ops, p, u, v, shape, ghost_fluid=False, viscosity_alpha=None):
+    """the dense step put together from the public functions, in the order the ``liquid_step`` docstring gives"""
+    B, n, D = p.shape
+    moved = ops.advect_particles(p, v, rr.STEP_DT, bnd=rr.BND)
+    spos, cell_start, order = ops.particle_cells(moved, shape)
+    su = torch.empty_like(u)
+    ops.call("df_particles_gather", ops._ptr(u), ops._ptr(order), ops._ptr(su), B * n, D, ops._stream())
+    vel_old, _, known = ops.particles_to_grid(spos, su, cell_start, shape)
+    vel, _ = ops.extrapolate_mac(vel_old, known, 2, bnd=rr.BND)
+    flags, touch = ops.liquid_flags(cell_start, shape, B, n, bnd=rr.BND)
+    solve = dict()
+    if ghost_fluid:
+        solve = dict(phi=ops.particle_levelset_averaged(spos, shape, 1.0, 1, 1, 1.0, rr.BND, cells=(spos, cell_start)), gf_clamp=1e-4)
+    diters = ()
+    if viscosity_alpha is not None:
+        vel = ops.liquid_forces(vel, flags, (0.0,) * D, bnd=rr.BND)
+        vel, it = ops.diffuse_velocity(vel, viscosity_alpha, bnd=rr.BND, accuracy=1e-4, max_iter=ops.default_diffusion_max_iter(shape))
+        diters = (it,)
+    vel = ops.liquid_forces(vel, flags, ops.default_gravity_force(shape, rr.STEP_DT), bnd=rr.BND)
+    vel, _, iters = ops.solve_pressure_liquid(vel, flags, bnd=rr.BND, **solve)
+    vel, _ = ops.extrapolate_mac(vel, touch, 4, bnd=rr.BND)
+    return (spos, ops.flip_update(spos, su, vel, vel_old), vel, iters) + diters
+
+
 @pytest.mark.parametrize("shape", rr.SHAPES)
 def test_resample_none_keeps_the_dense_step(shape):
-    """the off switch: with resample=None the step and the simulation return the bits of the dense path, taken in the same run"""
+    """the off switch: with resample=None the step and the simulation return the bits of the dense step as its docstring composes it
+    from the public functions, taken in the same run"""
     from deep_fluids_amd import ops
     parts, vel0 = rr.step_scene(shape)
     n = min(len(q) for q in parts)
@@ -324,9 +349,7 @@ def test_resample_none_keeps_the_dense_step(shape):
     try:
         ops.call = lambda name, *a: (names.append(name), real(name, *a))[1]
         for kw in (dict(), dict(ghost_fluid=True), dict(viscosity_alpha=0.3)):
-            want = ops._liquid_step(p, u, v, rr.STEP_DT, ops.default_gravity_force(shape, rr.STEP_DT), rr.BND, 1e-4, None, None, ops.DEFAULT_FLIP_RATIO,
-                                    ops.pressure_workspace(v, bool(kw.get("ghost_fluid"))), ops._viscosity_arg(kw.get("viscosity_alpha"), v, "t"),
-                                    ops._ghost_fluid_arg(kw.get("ghost_fluid"), 1.0, 1e-4, v, "t"))
+            want = _composed_dense_step(ops, p, u, v, shape, **kw)
             got = ops.liquid_step(p, u, v, rr.STEP_DT, resample=None, **kw)
             assert len(got) == len(want) and all(torch.equal(a, b) for a, b in zip(got, want))
             sim = ops.simulate_liquid(p, u, v, 2, dt=rr.STEP_DT, resample=None, **kw)
