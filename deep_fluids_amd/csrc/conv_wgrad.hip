@@ -2443,6 +2443,7 @@ __global__ __launch_bounds__(kThreads) void wgrad_up_reduce_kernel(const float* 
 
 struct Plan {
   int nrows, npairs, nranges, ppr, Cinp, Coutp, taps, ndzdy, nqi, nqj, nsub;
+  int maxr;      // upper bound of nranges: min(npairs, the range count asked for)
   int64_t partial_elems, bpartial_elems;
 };
 
@@ -2479,6 +2480,7 @@ Plan make_plan(int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t 
   if (algo == 3 && p.nsub > 1 && heur > 128 / p.nsub) heur = 128 / p.nsub < fill ? fill : 128 / p.nsub;
   const int maxr = (ranges > 0 && ranges <= kMaxRanges) ? ranges : heur;
   int nr = p.npairs >= maxr ? maxr : p.npairs;
+  p.maxr = nr;
   p.ppr = (p.npairs + nr - 1) / nr;
   p.nranges = (p.npairs + p.ppr - 1) / p.ppr;
   const int slots = algo == 0 ? p.taps : p.ndzdy * 4;             // the Winograd kernels write 4 xi_x slots per group
@@ -2486,6 +2488,10 @@ Plan make_plan(int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t 
   p.bpartial_elems = static_cast<int64_t>(p.nranges) * p.nsub * p.Coutp;
   return p;
 }
+// Floats of the partial sums as the *_workspace_bytes queries count them: with maxr ranges instead of nranges.  nranges =
+// ceil(npairs / ceil(npairs / maxr)) can shrink when the batch grows (65 row pairs over at most 64 ranges: 33 ranges of 2), maxr cannot,
+// so a workspace sized for the largest batch a caller runs is enough for every smaller one.  (Both buffers are nranges equal slices.)
+inline int64_t plan_bound_elems(const Plan& p) { return (p.partial_elems + p.bpartial_elems) / p.nranges * p.maxr; }
 
 // ---- row lengths without an (x,y,z) Winograd instantiation (W = 28, 14: levels of cfg4's 112-wide grid) ----------------------------------
 // gW of a SAME conv does not change when both operands get zero columns appended (the added gradient columns are zero, and the added input
@@ -2542,7 +2548,7 @@ int64_t df_conv_wgrad_workspace_bytes(int64_t B, int64_t D, int64_t H, int64_t W
   for (int algo = 0; algo <= 3; ++algo) {       // the launch may fall back (operand alignment), so size for the largest
     if ((algo == 1 && !wx_ok(W, Cin, Cout)) || (algo == 2 && !wxy_ok(H, W, Cin, Cout)) || (algo == 3 && !wxyz_ok(D, H, W, Cin, Cout, kz))) continue;
     const Plan p = make_plan(B, D, H, W, Cin, Cout, kz, algo);
-    const int64_t n = (p.partial_elems + p.bpartial_elems) * static_cast<int64_t>(sizeof(float));
+    const int64_t n = plan_bound_elems(p) * static_cast<int64_t>(sizeof(float));
     if (n > best) best = n;
   }
   return best + zero_row_bytes(W, Cin, Cout);
@@ -2693,7 +2699,8 @@ static int conv_wgrad_impl(const float* x, const float* gy, float* gw, float* gb
     const dim3 gridf((unsigned)(p.nranges * 16), grid.y, grid.z);       // all 16 (xi_z, xi_y) types of a range, adjacent
     // the default (req 0) at the 128 -> 128, W = 64 | 32 levels: the staged form (operands fetched and combined once per workgroup,
     // same partials bit for bit); req 4 keeps wgrad_wxyz_fused_kernel, the comparison and the form of every other shape
-    const bool staged = req == 0 && Cin == 128 && Cout == 128 && (W == 64 || W == 32);
+    // (its 16-byte row loads need 16-byte aligned operands; the register-ring kernel reads 8 bytes per lane and gives the same bits)
+    const bool staged = req == 0 && Cin == 128 && Cout == 128 && (W == 64 || W == 32) && df::aligned16(x) && df::aligned16(gy);
     if (staged) {
       if (W == 64) hipLaunchKernelGGL((wgrad_wxyz_staged_kernel<8>), gridf, dim3(kThreads), 0, s, aa);
       else hipLaunchKernelGGL((wgrad_wxyz_staged_kernel<4>), gridf, dim3(kThreads), 0, s, aa);
@@ -2825,7 +2832,7 @@ static bool s2_wgrad_ok(int64_t Wo, int64_t Cin, int64_t Cout) {
 int64_t df_conv_s2_wgrad_workspace_bytes(int64_t B, int64_t Do, int64_t Ho, int64_t Wo, int64_t Cin, int64_t Cout, int kz) {
   if (B <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || !s2_wgrad_ok(Wo, Cin, Cout)) return 0;
   const Plan p = make_plan(B, Do, Ho, Wo, Cin, Cout, kz);
-  return (p.partial_elems + p.bpartial_elems) * static_cast<int64_t>(sizeof(float)) + zero_row_bytes(2 * Wo, Cin, Cout);
+  return plan_bound_elems(p) * static_cast<int64_t>(sizeof(float)) + zero_row_bytes(2 * Wo, Cin, Cout);
 }
 int df_conv_s2_wgrad(const float* x, const float* gy, float* gw, float* gb, int64_t B, int64_t Do, int64_t Ho, int64_t Wo, int64_t Cin,
                      int64_t Cout, int kz, void* workspace, int64_t workspace_bytes, df_stream_t stream) {
@@ -2888,6 +2895,7 @@ static Plan make_up_plan(int64_t B, int64_t Dc, int64_t Hc, int64_t Wc, int64_t 
   // 32 | 8 (class, dz/dy) combos per range: 64 ranges x 32 combos = 2048 workgroups = 8 whole rounds of 256 CUs, and the
   // partial buffer (96 | 24 slots per range) stays 4x smaller than with 256 ranges
   const int nr = p.npairs >= 64 ? 64 : p.npairs;
+  p.maxr = nr;
   p.ppr = (p.npairs + nr - 1) / nr;
   p.nranges = (p.npairs + p.ppr - 1) / p.ppr;
   p.taps = p.ndzdy * 3;                                  // partial slots per range
@@ -2923,12 +2931,12 @@ int64_t df_upconv_wgrad_workspace_bytes(int64_t B, int64_t Dc, int64_t Hc, int64
   if (wxyz_ok(2 * Dc, 2 * Hc, 2 * Wc, Cin, Cout, kz)) {      // sized for either form (the choice depends on a debug switch)
     const Plan q = make_plan(B, 2 * Dc, 2 * Hc, 2 * Wc, Cin, Cout, kz, 3, up_wxyz_ranges(B, Dc, Hc, Cin, Cout));
     const Plan p = make_up_plan(B, Dc, Hc, Wc, Cin, Cout, kz);
-    const int64_t nq = (q.partial_elems + q.bpartial_elems) * static_cast<int64_t>(sizeof(float)) + zero_row_bytes(2 * Wc, Cin, Cout);
-    const int64_t np = (p.partial_elems + p.bpartial_elems) * static_cast<int64_t>(sizeof(float)) + zero_row_bytes(Wc, Cin, Cout);
+    const int64_t nq = plan_bound_elems(q) * static_cast<int64_t>(sizeof(float)) + zero_row_bytes(2 * Wc, Cin, Cout);
+    const int64_t np = plan_bound_elems(p) * static_cast<int64_t>(sizeof(float)) + zero_row_bytes(Wc, Cin, Cout);
     return nq > np ? nq : np;
   }
   const Plan p = make_up_plan(B, Dc, Hc, Wc, Cin, Cout, kz);
-  return (p.partial_elems + p.bpartial_elems) * static_cast<int64_t>(sizeof(float)) + zero_row_bytes(Wc, Cin, Cout);
+  return plan_bound_elems(p) * static_cast<int64_t>(sizeof(float)) + zero_row_bytes(Wc, Cin, Cout);
 }
 
 static int upconv_wgrad_impl(const float* xc, const float* gy, float* gw, float* gb, int64_t B, int64_t Dc, int64_t Hc,
@@ -2997,19 +3005,25 @@ static int upconv_wgrad_impl(const float* xc, const float* gy, float* gw, float*
   dim3 grid((unsigned)(p.nranges * p.ndzdy), (unsigned)ceil_div(Cin, 128), (unsigned)ceil_div(Cout, 128));
   const int wp8 = a.Wp / 8;
   const bool exact = (Wc % 8) == 0;
-  const bool aligned8 = ((reinterpret_cast<uintptr_t>(xc) | reinterpret_cast<uintptr_t>(gy)) & 7u) == 0;
+  // every kernel below but wgrad_kernel<*, *, 0> reads 8 bytes per lane from both operands: a pointer that is only 4-byte aligned
+  // takes the scalar loads of that kernel, as in conv_wgrad_impl (channel counts are even here)
+  const bool xvec = (reinterpret_cast<uintptr_t>(xc) & 7u) == 0, gvec = (reinterpret_cast<uintptr_t>(gy) & 7u) == 0;
+  const bool aligned8 = xvec && gvec;
   const dim3 grid2((unsigned)(p.nranges * (p.ndzdy / 2)), grid.y, grid.z);     // one workgroup per x-parity class PAIR
-  if (prec == 1 && wgrad_bf16x3_ok(Wc, Cin, Cout)) launch_wgrad_bf16x3(Wc, grid, s, a);
+  if (prec == 1 && aligned8 && wgrad_bf16x3_ok(Wc, Cin, Cout)) launch_wgrad_bf16x3(Wc, grid, s, a);
   else if (aligned8 && exact && wp8 == 4 && Cin == 128 && Cout == 128 && req != 1) hipLaunchKernelGGL((wgrad_up2_kernel<4, 128>), grid2, dim3(kThreads), 0, s, a);
   else if (aligned8 && exact && wp8 == 6 && Cin == 128 && Cout == 128 && req != 1) hipLaunchKernelGGL((wgrad_up2_kernel<6, 128>), grid2, dim3(kThreads), 0, s, a);      // 2-D 128x96: coarse W = 48 | 24
   else if (aligned8 && exact && wp8 == 3 && Cin == 128 && Cout == 128 && req != 1) hipLaunchKernelGGL((wgrad_up2_kernel<3, 128>), grid2, dim3(kThreads), 0, s, a);
   else if (aligned8 && exact && wp8 == 2 && req != 1) hipLaunchKernelGGL((wgrad_up2_kernel<2, 0>), grid2, dim3(kThreads), 0, s, a);
   else if (aligned8 && exact && wp8 == 1 && req != 1) hipLaunchKernelGGL((wgrad_up2_kernel<1, 0>), grid2, dim3(kThreads), 0, s, a);
-  else if (exact && wp8 == 8) hipLaunchKernelGGL((wgrad_kernel<true, true, 8>), grid, dim3(kThreads), 0, s, a);
-  else if (exact && wp8 == 4) hipLaunchKernelGGL((wgrad_kernel<true, true, 4>), grid, dim3(kThreads), 0, s, a);
-  else if (exact && wp8 == 2) hipLaunchKernelGGL((wgrad_kernel<true, true, 2>), grid, dim3(kThreads), 0, s, a);
-  else if (exact && wp8 == 7) hipLaunchKernelGGL((wgrad_kernel<true, true, 7>), grid, dim3(kThreads), 0, s, a);
-  else hipLaunchKernelGGL((wgrad_kernel<true, true, 0>), grid, dim3(kThreads), 0, s, a);
+  else if (aligned8 && exact && wp8 == 8) hipLaunchKernelGGL((wgrad_kernel<true, true, 8>), grid, dim3(kThreads), 0, s, a);
+  else if (aligned8 && exact && wp8 == 4) hipLaunchKernelGGL((wgrad_kernel<true, true, 4>), grid, dim3(kThreads), 0, s, a);
+  else if (aligned8 && exact && wp8 == 2) hipLaunchKernelGGL((wgrad_kernel<true, true, 2>), grid, dim3(kThreads), 0, s, a);
+  else if (aligned8 && exact && wp8 == 7) hipLaunchKernelGGL((wgrad_kernel<true, true, 7>), grid, dim3(kThreads), 0, s, a);
+  else if (aligned8) hipLaunchKernelGGL((wgrad_kernel<true, true, 0>), grid, dim3(kThreads), 0, s, a);
+  else if (xvec) hipLaunchKernelGGL((wgrad_kernel<true, false, 0>), grid, dim3(kThreads), 0, s, a);
+  else if (gvec) hipLaunchKernelGGL((wgrad_kernel<false, true, 0>), grid, dim3(kThreads), 0, s, a);
+  else hipLaunchKernelGGL((wgrad_kernel<false, false, 0>), grid, dim3(kThreads), 0, s, a);
   const int64_t total = static_cast<int64_t>(kz * 9) * Cin * Cout;
   const int64_t rg = ceil_div(total, 32);
   hipLaunchKernelGGL(wgrad_up_reduce_kernel, dim3((unsigned)rg), dim3(kThreads), 0, s, a.partial, a.bpartial, gw, gb,

@@ -459,7 +459,12 @@ int df_conv_wgrad_algo(const float* x, const float* gy, float* gw, float* gb, in
  * visible so that a silent fall-back to a slower form shows up in the caller's log (bench.py `dispatch`):
  *   0 direct MFMA | 1 Winograd in x | 2 Winograd in (x,y) | 3 Winograd in (x,y,z) | 10 thin layer (Cin or Cout <= 4) on the matrix
  *   cores | 11 thin layer on the vector ALU; negative = invalid arguments.  df_upconv_wgrad_form: 3 = 27-point Winograd-(x,y,z)
- *   form on the coarse input, 0 = parity-class kernels.  (No reference counterpart: TF picks cuDNN algorithms internally.) */
+ *   form on the coarse input, 0 = parity-class kernels.  (No reference counterpart: TF picks cuDNN algorithms internally.)
+ * Both queries see no pointers and keep assuming 16-byte aligned operands.  The launch itself looks at x and gy: the thin matrix-core
+ * form (10 -> 11), the zero-padded rows, the staged default of the 128 -> 128 levels (-> the register-ring kernel of algo 4, same bits)
+ * and the 27-point up-sampling form (3 -> 0) need 16 bytes; every 8-byte kernel (Winograd forms, bf16x3, parity-class pairs, exact-row
+ * direct kernels) needs 8; an operand that is only 4-byte aligned takes the direct kernel with scalar loads (form 0).  Every fallback
+ * returns the same gradient up to fp32 summation order. */
 int df_conv_wgrad_form(int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int kz, int algo);
 int df_upconv_wgrad_form(int64_t B, int64_t Dc, int64_t Hc, int64_t Wc, int64_t Cin, int64_t Cout, int kz, int algo);
 

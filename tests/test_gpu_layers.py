@@ -548,9 +548,14 @@ def test_upconv_block_bf16x3_mode(ops, bf16x3):
         ins.append(x); x = orc.lrelu(orc.conv_same(x, w.astype(np.float64), b.astype(np.float64))); outs.append(x)
     assert rel_linf(host(y), x + x0) < 1e-4
     dx = go.astype(np.float64)
+    dws, dbs = [None] * n, [None] * n
     for i in reversed(range(n)):
-        dx, _, _ = orc.conv_same_bwd(ins[i], ws[i].astype(np.float64), dx * np.where(outs[i] > 0, 1.0, 0.2))
+        dx, dws[i], dbs[i] = orc.conv_same_bwd(ins[i], ws[i].astype(np.float64), dx * np.where(outs[i] > 0, 1.0, 0.2))
     assert rel_linf(host(xt.grad), orc.upscale_nn_bwd(dx + go)) < 1e-4
+    for i in range(n):      # the weight and bias gradients of both convs (the first one is the up-sampling-aware weight gradient)
+        ew, eb = rel_linf(host(args[2 * i].grad), dws[i]), rel_linf(host(args[2 * i + 1].grad), dbs[i])
+        print("conv %d: dw %.3e (< 1e-4)  db %.3e (< %.0e)" % (i, ew, eb, TOL))
+        assert ew < 1e-4 and eb < TOL, (i, ew, eb)
 
 
 def test_conv_wgrad_range_override_is_bounds_checked(ops):
