@@ -20,6 +20,9 @@
 // W = 64 | 32, wgrad_wxyz_staged_kernel: there the WORKGROUP fetches each raw row once with 16-byte loads, applies the (xi_z, xi_y)
 // combination once and keeps the combined operands of a tile-row pair in LDS, from where the four quadrant waves read them
 // (ds_read_b64) -- half the operand requests per MFMA, the same partials bit for bit (algo 4 = the register-ring kernel it replaced).
+#include <type_traits>
+#include <utility>
+
 #include "df_common.hpp"
 
 namespace {
@@ -39,10 +42,6 @@ inline int64_t zero_row_bytes(int64_t W, int64_t Cin, int64_t Cout) {
   return Wp * (Cin > 2 * Cout ? Cin : 2 * Cout) * 4 + 64;
 }
 constexpr int kSmallStreams = 2048;  // wave streams of the small-N kernel
-
-#ifdef DF_TUNING
-int g_wgrad_dbg = 0;      // df_debug_set_wgrad (include/deepfluids_hip_debug.h)
-#endif
 
 struct WgradArgs {
   const float* x;
@@ -1106,7 +1105,7 @@ __device__ __forceinline__ int wxyz_wg(int nwg) {
 }
 
 // the work of ONE workgroup: voxel range `range`, transform point (xi_z, xi_y) number `sel` of the (GZ, GY) class
-template <int WP8, int CS, bool GZ, bool GY, bool UP, int DBG>
+template <int WP8, int CS, bool GZ, bool GY, bool UP>
 __device__ __forceinline__ void wgrad_wxyz_body(const WxyzArgs& aa, int range, int sel, float* lds) {      // lds: kWxyzLds floats when CS == 64
   const WgradArgs& a = aa.w;
   const int tid = threadIdx.x;
@@ -1127,8 +1126,8 @@ __device__ __forceinline__ void wgrad_wxyz_body(const WxyzArgs& aa, int range, i
   const int ppe = (a.pairs_per_range + a.nsub - 1) / a.nsub;
   // [r5] 64 -> 64 layers: the nsub = 4 waves that split a range take INTERLEAVED tile-row pairs (pair = first + sub + nsub i), not contiguous
   // sub-ranges: at any time they stream neighbouring rows and share the y-halo rows of x through the L1 -- 5.84 -> 5.68 ms at 128^3 x 4
-  // (tools/r05_wgrad64_probe.py; tuning variant 16 = the contiguous split of rounds 3-4).  Same partial slots, fixed summation order.
-  constexpr bool IL = (CS == 64) != ((DBG & 16) != 0);
+  // (tools/archive/r05_wgrad64_probe.py, against the contiguous split of rounds 3-4).  Same partial slots, fixed summation order.
+  constexpr bool IL = CS == 64;
   const int pstep = IL ? a.nsub : 1;
   const int p0 = range * a.pairs_per_range + (IL ? sub : sub * ppe);
   int p1 = IL ? (range + 1) * a.pairs_per_range : p0 + ppe;
@@ -1149,7 +1148,7 @@ __device__ __forceinline__ void wgrad_wxyz_body(const WxyzArgs& aa, int range, i
   struct Row { const float* x[2][2]; const float* g[2][2]; };      // [plane a|b][row a|b]
   auto row_setup = [&](int pair) -> Row {
     Row rw;
-    const int trow = (DBG & 8) ? 2 * (pair & 3) + half : 2 * pair + half;      // (tuning library, DBG 8: every range reads the same 8 tile rows -- an L2-resident working set)
+    const int trow = 2 * pair + half;
     const bool ok = pair < p1 && trow < aa.ntrows;
     const int yt = trow % aa.Ht;
     const int t = trow / aa.Ht;
@@ -1175,10 +1174,6 @@ __device__ __forceinline__ void wgrad_wxyz_body(const WxyzArgs& aa, int range, i
         const bool need = (pz == 0 || GZ) && (py == 0 || GY);
         rw.g[pz][py] = (need && ok && co_ok0) ? a.g + ((bbase + gz) * a.H + gy) * a.W * a.Cout + coa : zb;
       }
-    }
-    if (DBG & 1) {        // (tuning library) latency experiment: every operand load reads the cached zero row
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { rw.x[q >> 1][q & 1] = zb; rw.g[q >> 1][q & 1] = zb; }
     }
     return rw;
   };
@@ -1221,12 +1216,10 @@ __device__ __forceinline__ void wgrad_wxyz_body(const WxyzArgs& aa, int range, i
     if (GZ && GY) gr[1][1][slot] = ld(lr.g[1][1], pos, gs);
   };
   auto xcomb = [&](int slot) -> f32x2 {
-    if (DBG & 2) return xr[0][0][slot];      // (tuning library) no (z, y) combination
     const f32x2 ta = pkfma(xr[0][1][slot], sy2, xr[0][0][slot]), tb = pkfma(xr[1][1][slot], sy2, xr[1][0][slot]);
     return pkfma(tb, sz2, ta);
   };
   auto gcomb = [&](int slot) -> f32x2 {
-    if (DBG & 2) return gr[0][0][slot];
     if (GZ && GY) {
       const f32x2 ta = pkfma(gr[0][1][slot], sgy2, gr[0][0][slot]), tb = pkfma(gr[1][1][slot], sgy2, gr[1][0][slot]);
       return pkfma(tb, sgz2, ta);
@@ -1248,10 +1241,9 @@ __device__ __forceinline__ void wgrad_wxyz_body(const WxyzArgs& aa, int range, i
     f32x2 dm = xc[(u + 7) & 7], d0 = xc[u], d1 = xc[(u + 1) & 7], d2 = xc[(u + 2) & 7];
     if (x == 0) dm = f32x2{0.f, 0.f};
     if (x == Wc - 2) d2 = f32x2{0.f, 0.f};
-    const f32x2 v0 = (DBG & 4) ? dm : wpk_sub(dm, d1), v1 = (DBG & 4) ? d0 : wpk_add(d0, d1), v2 = (DBG & 4) ? d1 : wpk_sub(d1, d0),
-                v3 = (DBG & 4) ? d2 : wpk_sub(d0, d2);      // (DBG & 4, tuning library: no x transform)
-    const f32x2 m1 = (DBG & 4) ? g0 : wpk_add(g0, g1), m2 = (DBG & 4) ? g1 : wpk_sub(g0, g1);
-    if (!(DBG & 4)) bsum = wpk_add(bsum, m1);
+    const f32x2 v0 = wpk_sub(dm, d1), v1 = wpk_add(d0, d1), v2 = wpk_sub(d1, d0), v3 = wpk_sub(d0, d2);
+    const f32x2 m1 = wpk_add(g0, g1), m2 = wpk_sub(g0, g1);
+    bsum = wpk_add(bsum, m1);
     __builtin_amdgcn_sched_barrier(0);
     load_pos(lr, (u + 6) & 7, lpos);
     load_pos(lr, (u + 7) & 7, lpos + 1);
@@ -1352,18 +1344,10 @@ __device__ __forceinline__ void wgrad_wxyz_body(const WxyzArgs& aa, int range, i
   }
 }
 
-template <int WP8, int CS, bool GZ, bool GY, bool UP = false, int DBG = 0>
-__global__ __launch_bounds__(kThreads, 1) void wgrad_wxyz_kernel(const WxyzArgs aa) {
-  constexpr int NT = ((UP && GZ) ? 1 : 2) * ((UP && GY) ? 1 : 2);      // workgroup types of this launch
-  __shared__ float sLds[CS == 64 ? kWxyzLds : 1];
-  const int wg = wxyz_wg(aa.w.nranges * NT);
-  wgrad_wxyz_body<WP8, CS, GZ, GY, UP, DBG>(aa, wg / NT, wg % NT, sLds);
-}
-
 // All 16 (xi_z, xi_y) types of a voxel range in ONE launch, adjacent in the grid: they run at the same time on the same XCD, so the
 // rows of x and g a range streams are fetched from the fabric once and the other 15 readers hit that XCD's L2 (four launches by
 // (GZ, GY) class re-read both tensors from HBM four times, and an HBM miss outlasts the 6-position register prefetch).
-template <int WP8, int CS, int DBG = 0>
+template <int WP8, int CS>
 __global__ __launch_bounds__(kThreads, 1) void wgrad_wxyz_fused_kernel(const WxyzArgs aa) {
   const int wg = wxyz_wg(aa.w.nranges * 16);
   const int range = wg >> 4, type = wg & 15;
@@ -1371,10 +1355,10 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad_wxyz_fused_kernel(const Wxy
   const bool gz = xiz == 1 || xiz == 2, gy = xiy == 1 || xiy == 2;
   const int sel = (gz ? xiz - 1 : xiz / 3) * 2 + (gy ? xiy - 1 : xiy / 3);
   __shared__ float sLds[CS == 64 ? kWxyzLds : 1];
-  if (gz && gy) wgrad_wxyz_body<WP8, CS, true, true, false, DBG>(aa, range, sel, sLds);
-  else if (gz) wgrad_wxyz_body<WP8, CS, true, false, false, DBG>(aa, range, sel, sLds);
-  else if (gy) wgrad_wxyz_body<WP8, CS, false, true, false, DBG>(aa, range, sel, sLds);
-  else wgrad_wxyz_body<WP8, CS, false, false, false, DBG>(aa, range, sel, sLds);
+  if (gz && gy) wgrad_wxyz_body<WP8, CS, true, true, false>(aa, range, sel, sLds);
+  else if (gz) wgrad_wxyz_body<WP8, CS, true, false, false>(aa, range, sel, sLds);
+  else if (gy) wgrad_wxyz_body<WP8, CS, false, true, false>(aa, range, sel, sLds);
+  else wgrad_wxyz_body<WP8, CS, false, false, false>(aa, range, sel, sLds);
 }
 
 // The up-sampling-aware form has 9 live (xi_z, xi_y) types (xi in {0, 1, 3} per axis): one launch as well (four launches by class
@@ -1387,10 +1371,10 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad_wxyz_up_fused_kernel(const 
   const bool gz = zi == 1, gy = yi == 1;
   const int selz = zi == 2 ? 1 : 0, sely = yi == 2 ? 1 : 0;
   __shared__ float sLds[CS == 64 ? kWxyzLds : 1];
-  if (gz && gy) wgrad_wxyz_body<WP8, CS, true, true, true, 0>(aa, range, 0, sLds);
-  else if (gz) wgrad_wxyz_body<WP8, CS, true, false, true, 0>(aa, range, sely, sLds);
-  else if (gy) wgrad_wxyz_body<WP8, CS, false, true, true, 0>(aa, range, selz, sLds);
-  else wgrad_wxyz_body<WP8, CS, false, false, true, 0>(aa, range, selz * 2 + sely, sLds);
+  if (gz && gy) wgrad_wxyz_body<WP8, CS, true, true, true>(aa, range, 0, sLds);
+  else if (gz) wgrad_wxyz_body<WP8, CS, true, false, true>(aa, range, sely, sLds);
+  else if (gy) wgrad_wxyz_body<WP8, CS, false, true, true>(aa, range, selz, sLds);
+  else wgrad_wxyz_body<WP8, CS, false, false, true>(aa, range, selz * 2 + sely, sLds);
 }
 
 // ---- staged (x,y,z) weight gradient: one pre-combined operand stream per workgroup -------------------------------------------------
@@ -1695,18 +1679,64 @@ __global__ __launch_bounds__(kThreads) void wgrad_wxyz_reduce_kernel(const float
   if (gb && static_cast<int>(blockIdx.x) * 32 < Cout) bias_reduce_cols(bpartial, gb, nranges, Cout, Coutp, &sV[0][0][0], blockIdx.x);
 }
 
-// the Winograd-in-x variant exists for the fully unrolled row lengths below (even channel counts: float2 operand loads)
-inline bool wx_ok(int64_t W, int64_t Cin, int64_t Cout) {
-  return (W == 16 || W == 32 || W == 64 || W == 56 || W == 112 || W == 128 || W == 96 || W == 48) && Cin % 2 == 0 && Cout % 2 == 0 && Cin >= 32 && Cout >= 32;
+// ---- the instantiated template arguments of every kernel family, each set named ONCE --------------------------------------------------
+// A family's predicate is "the value is in its list" and its launch is with_value on the same list, so the library holds exactly the
+// instantiations listed here and no call can reach one that a predicate did not admit.
+template <int... V> using Ints = std::integer_sequence<int, V...>;
+constexpr int wc(int wp8, int cs) { return wp8 * 1000 + cs; }      // a (WP8, CS) pair as one list value
+// run-time value -> compile-time one: calls f(std::integral_constant<int, V>) for the V of the list that equals v; false (and no call)
+// when the list does not hold v
+template <int... V, typename F>
+inline bool with_value(Ints<V...>, int64_t v, F&& f) { return ((v == V && (f(std::integral_constant<int, V>{}), true)) || ...); }
+template <typename L> inline bool in_list(L list, int64_t v) { return with_value(list, v, [](auto) {}); }
+
+constexpr Ints<8, 16, 4, 14, 12, 7, 2, 3, 6> kDirectWp8{};      // wgrad_kernel<true, true, WP8>; <*, *, 0> takes every other row and alignment
+constexpr Ints<8, 4, 2, 7> kUpDirectWp8{};                      // ... the ones the class-strided views of the up-sampling form use
+constexpr Ints<1, 2, 4, 8> kS2Wp8{};                            // wgrad_s2_kernel<WP8>
+constexpr Ints<wc(4, 128), wc(6, 128), wc(3, 128), wc(2, 0), wc(1, 0)> kUp2{};      // wgrad_up2_kernel<WP8, CS>; 6 | 3: 2-D 128x96, coarse W = 48 | 24
+// wgrad_wx_kernel<WP8, CS>: CS = 128 only where listed (128 -> 128 at W = 128 runs <16, 0>)
+constexpr Ints<wc(8, 128), wc(8, 0), wc(16, 0), wc(12, 0), wc(6, 0), wc(14, 0), wc(7, 0), wc(4, 128), wc(4, 0), wc(2, 128), wc(2, 0)> kWx{};
+// wgrad_wxy_kernel<WP8, CS, true | false>: 16: AE3 128^3 (cfg5); 12 | 6: 2-D 128x96 (cfg1/cfg2) and its 64x48 level; 14 | 7: cfg4 row lengths
+constexpr Ints<wc(8, 128), wc(8, 0), wc(16, 0), wc(12, 128), wc(12, 0), wc(6, 128), wc(6, 0), wc(14, 0), wc(7, 0), wc(4, 128), wc(4, 0),
+               wc(2, 128), wc(2, 0)> kWxy{};
+// wgrad_wxyz_fused_kernel / wgrad_wxyz_up_fused_kernel<WP8, CS>: the 128 -> 128 layers at W = 64 | 32 | 16 (cfg3), 112 | 56 (cfg4), 128, and
+// the 64 -> 64 layers of the auto-encoder (cfg5, F = 64) at W = 128 | 64 | 32 | 16
+constexpr Ints<wc(8, 128), wc(4, 128), wc(2, 128), wc(14, 128), wc(16, 128), wc(7, 128), wc(16, 64), wc(8, 64), wc(4, 64), wc(2, 64)> kWxyz{};
+constexpr Ints<8, 4> kWxyzStagedWp8{};                          // wgrad_wxyz_staged_kernel<WP8> (128 -> 128)
+// wgrad_bf16x3_kernel<W16>.  W = 112 (cfg4) is NOT listed: its 28-step unrolled variant spilt 720 B of scratch per lane and ran 148 ms per
+// launch on MI355X; those rows take the fp32 Winograd weight gradients instead (more accurate, ~40x faster)
+constexpr Ints<1, 2, 4, 6> kBf16x3W16{};
+constexpr Ints<31, 32, 33, 34, 11, 12, 13, 14> kSmallN{};       // wgrad_small_n_kernel<KZ, CO> as KZ * 10 + CO
+// wgrad_thin_mfma_kernel<CT, NJ, SWAP, NP> as ((CT * 10 + NJ) * 10 + SWAP) * 10 + NP: CT 1..4 for 128 wide channels in one pass, every
+// (NJ, SWAP, NP) for three thin channels (others fall back to the generic kernels)
+constexpr Ints<1401, 2401, 3401, 4401, 3402, 3201, 3202, 3411, 3412, 3211, 3212> kThin{};
+
+inline bool c128(int64_t Cin, int64_t Cout) { return Cin == 128 && Cout == 128; }
+// the (WP8, CS) entry of `list` for rows of W: CS = 128 where the 128 -> 128 layers have their own variant, else CS = 0; 0 = none
+template <typename L> inline int wc_of(L list, int64_t W, int64_t Cin, int64_t Cout) {
+  if (W % 8 != 0 || W / 8 >= 1000) return 0;
+  const int wp8 = (int)(W / 8);
+  return c128(Cin, Cout) && in_list(list, wc(wp8, 128)) ? wc(wp8, 128) : in_list(list, wc(wp8, 0)) ? wc(wp8, 0) : 0;
 }
-inline bool wxy_ok(int64_t H, int64_t W, int64_t Cin, int64_t Cout) { return wx_ok(W, Cin, Cout) && H % 2 == 0 && H >= 4; }
-// (x,y,z): instantiated for the 128 -> 128 layers at W = 64 | 32 | 16 (cfg3), 112 | 56 (cfg4), 128, and for the 64 -> 64 layers of the
-// auto-encoder (cfg5, F = 64) at W = 128 | 64 | 32 | 16
+// the entry of kWxyz: CS = the channel count of the 128 -> 128 | 64 -> 64 layers; 0 = none
+inline int wxyz_key(int64_t W, int64_t Cin, int64_t Cout) {
+  if (W % 8 != 0 || W / 8 >= 1000 || Cin != Cout || !(Cin == 128 || Cin == 64)) return 0;
+  return in_list(kWxyz, wc((int)(W / 8), (int)Cin)) ? wc((int)(W / 8), (int)Cin) : 0;
+}
+
+// the Winograd-in-x variant exists for the fully unrolled row lengths of kWx (even channel counts: float2 operand loads)
+inline bool wx_ok(int64_t W, int64_t Cin, int64_t Cout) {
+  return wc_of(kWx, W, Cin, Cout) != 0 && Cin % 2 == 0 && Cout % 2 == 0 && Cin >= 32 && Cout >= 32;
+}
+inline bool wxy_ok(int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
+  return wx_ok(W, Cin, Cout) && wc_of(kWxy, W, Cin, Cout) != 0 && H % 2 == 0 && H >= 4;
+}
 inline bool wxyz_ok(int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int kz) {
-  if (!(kz == 3 && wxy_ok(H, W, Cin, Cout) && D % 2 == 0 && D >= 4)) return false;
-  if (Cin == 128 && Cout == 128) return W == 64 || W == 32 || W == 16 || W == 112 || W == 56 || W == 128;
-  if (Cin == 64 && Cout == 64) return W == 128 || W == 64 || W == 32 || W == 16;
-  return false;
+  return kz == 3 && wxy_ok(H, W, Cin, Cout) && D % 2 == 0 && D >= 4 && wxyz_key(W, Cin, Cout) != 0;
+}
+// does form `algo` (0 direct | 1 Winograd in x | 2 in (x,y) | 3 in (x,y,z)) exist for this shape?
+inline bool form_exists(int algo, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int kz) {
+  return algo == 0 || (algo == 1 && wx_ok(W, Cin, Cout)) || (algo == 2 && wxy_ok(H, W, Cin, Cout)) || (algo == 3 && wxyz_ok(D, H, W, Cin, Cout, kz));
 }
 // `req` = the caller's algorithm request (the `algo` argument of df_conv_wgrad_algo, low 3 bits): 0: best available,
 // 1: always the direct kernel, 2: at most Winograd-in-x, 3: (x,y) wherever it exists, 4: (x,y,z) wherever it exists.
@@ -1910,18 +1940,7 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad_bf16x3_kernel(const WgradAr
 }
 
 inline bool wgrad_bf16x3_ok(int64_t W, int64_t Cin, int64_t Cout) {
-  // W = 112 (cfg4) is NOT listed: its 28-step unrolled variant spilt 720 B of scratch per lane and ran 148 ms per launch on
-  // MI355X; those rows take the fp32 Winograd weight gradients instead (more accurate, ~40x faster)
-  return (W == 16 || W == 32 || W == 64 || W == 96) && Cin % 2 == 0 && Cout % 2 == 0 && Cin >= 16 && Cout >= 16;
-}
-template <typename A>
-inline void launch_wgrad_bf16x3(int64_t W, dim3 grid, hipStream_t s, const A& a) {
-  switch (W / 16) {
-    case 1: hipLaunchKernelGGL((wgrad_bf16x3_kernel<1>), grid, dim3(kThreads), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((wgrad_bf16x3_kernel<2>), grid, dim3(kThreads), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((wgrad_bf16x3_kernel<4>), grid, dim3(kThreads), 0, s, a); break;
-    default: hipLaunchKernelGGL((wgrad_bf16x3_kernel<6>), grid, dim3(kThreads), 0, s, a); break;
-  }
+  return W % 16 == 0 && in_list(kBf16x3W16, W / 16) && Cin % 2 == 0 && Cout % 2 == 0 && Cin >= 16 && Cout >= 16;
 }
 
 // gw[tap][ci][co] = sum_range partial[range][tap][ci][co]  (fixed order);  gb likewise
@@ -2356,11 +2375,15 @@ inline bool thin_mfma_ok(int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cwi
   return kz == 3 && (Cwide == 128 || Cwide == 64) && Cthin >= 1 && Cthin <= 4 && W % 16 == 0 && (W * Cthin) % 16 == 0 && W * Cthin <= 480 &&
          B * D * H >= 4 && B * D * H * W * Cwide * 4 < (1LL << 44);
 }
-// instantiated combinations (others fall back to the generic kernels)
-inline bool thin_mfma_inst(int64_t W, int64_t Cwide, int64_t Cthin, bool swap) {
-  const bool two = W * Cthin > 256;
-  if (!swap && Cwide == 128 && !two) return true;                 // CT 1..4
-  return Cthin == 3;                                              // every (NJ, SWAP, NP) for three thin channels
+// a thin layer: F -> 1..4 (wide = x, thin = gy) or 1..4 -> F (SWAP: wide = gy, thin = x)
+struct ThinShape { bool swap; int64_t Cw, Ct; };
+inline ThinShape thin_shape(int64_t Cin, int64_t Cout) {
+  const bool swap = Cin <= 4 && Cout >= 64;
+  return {swap, swap ? Cout : Cin, swap ? Cin : Cout};
+}
+// the entry of kThin for a shape thin_mfma_ok admits (two 64-lane passes per thin row above 256 floats)
+inline int thin_key(int64_t W, const ThinShape& t) {
+  return (int)(((t.Ct * 10 + t.Cw / 32) * 10 + (t.swap ? 1 : 0)) * 10 + (W * t.Ct > 256 ? 2 : 1));
 }
 // streams (waves) of the matrix-core thin weight gradient and its workspace floats
 static int thin_wgrad_streams(int64_t B, int64_t D, int64_t H) {
@@ -2521,48 +2544,158 @@ __global__ __launch_bounds__(kThreads) void pad_rows_kernel(const f32x4* __restr
   dst[i] = xx < W ? src[(row * W + xx) * C4 + (r - xx * C4)] : f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
-}  // namespace
+// ---- up-sampling-aware form: plans --------------------------------------------------------------------------------------------------------
+Plan make_up_plan(int64_t B, int64_t Dc, int64_t Hc, int64_t Wc, int64_t Cin, int64_t Cout, int kz) {
+  Plan p = make_plan(B, Dc, Hc, Wc, Cin, Cout, kz);
+  p.ndzdy = kz == 3 ? 32 : 8;
+  // 32 | 8 (class, dz/dy) combos per range: 64 ranges x 32 combos = 2048 workgroups = 8 whole rounds of 256 CUs, and the
+  // partial buffer (96 | 24 slots per range) stays 4x smaller than with 256 ranges
+  const int nr = p.npairs >= 64 ? 64 : p.npairs;
+  p.maxr = nr;
+  p.ppr = (p.npairs + nr - 1) / nr;
+  p.nranges = (p.npairs + p.ppr - 1) / p.ppr;
+  p.taps = p.ndzdy * 3;                                  // partial slots per range
+  p.partial_elems = static_cast<int64_t>(p.nranges) * p.nsub * p.taps * p.Cinp * p.Coutp;
+  p.bpartial_elems = static_cast<int64_t>(p.nranges) * p.nsub * (kz == 3 ? 8 : 4) * p.Coutp;
+  return p;
+}
+// the 27-point Winograd-(x,y,z) form of the up-sampling-aware weight gradient (fine extents 2Dc x 2Hc x 2Wc): exists, and `req` runs it
+inline bool up_wxyz_exists(int64_t Dc, int64_t Hc, int64_t Wc, int64_t Cin, int64_t Cout, int kz) { return wxyz_ok(2 * Dc, 2 * Hc, 2 * Wc, Cin, Cout, kz); }
+inline bool up_wxyz_ok(int req, int64_t B, int64_t Dc, int64_t Hc, int64_t Wc, int64_t Cin, int64_t Cout, int kz) {
+  // at every size ([r3] batch 2 | 4 | 16, fine 16x24x16: parity-class 0.216 | 0.315 | 0.443 ms, 27-point 0.048 | 0.058 | 0.132; fine 32x48x32:
+  // 0.442 | 0.597 | 1.484 vs 0.129 | 0.222 | 0.787): the parity-class form pays a fixed-cost reduce of its 32-combo partials
+  (void)B;
+  return up_wxyz_exists(Dc, Hc, Wc, Cin, Cout, kz) && req != 1 && req != 2 && req != 3;
+}
+// partial ranges of the 27-point (x,y,z) form: 9 workgroup types per range in one launch -- 28 ranges (252 workgroups: one round of
+// the 256 CUs) below 4096 tile-row pairs, 113 (1017: four rounds) above
+// (64 -> 64: the spare waves split each range four ways -- 28 ranges are already 112 partials)
+inline int up_wxyz_ranges(int64_t B, int64_t Dc, int64_t Hc, int64_t Cin, int64_t Cout) {
+  return ((B * Dc * Hc + 1) / 2 < 4096 || (Cin <= 64 && Cout <= 64)) ? 28 : 113;
+}
+inline Plan make_up_wxyz_plan(int64_t B, int64_t Dc, int64_t Hc, int64_t Wc, int64_t Cin, int64_t Cout, int kz) {
+  return make_plan(B, 2 * Dc, 2 * Hc, 2 * Wc, Cin, Cout, kz, 3, up_wxyz_ranges(B, Dc, Hc, Cin, Cout));
+}
 
-extern "C" {
+// ---- the argument block of the streaming kernels ------------------------------------------------------------------------------------------
+// Partial sums, bias partials and the zeroed row lie in the workspace in that order.  D, H, W: the extents of x; Wp: the row length the
+// kernel unrolls; up = 1: x is the COARSE input of the parity-class kernels and g has twice its extents.  Returns the zero row, which the
+// caller clears ahead of the launch.
+float* fill_args(WgradArgs& a, const Plan& p, const float* x, const float* g, bool want_bias, void* workspace, int64_t B, int64_t D, int64_t H,
+                 int64_t W, int64_t Cin, int64_t Cout, int kz, int64_t Wp, int up) {
+  a.x = x; a.g = g;
+  a.partial = static_cast<float*>(workspace);
+  a.bpartial = a.partial + p.partial_elems;
+  float* zeros = a.bpartial + p.bpartial_elems;
+  a.zeros = zeros;
+  a.B = (int)B; a.D = (int)D; a.H = (int)H; a.W = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout;
+  a.Cinp = p.Cinp; a.Coutp = p.Coutp;
+  a.Wp = (int)Wp;
+  a.nrows = p.nrows; a.npairs = p.npairs; a.nranges = p.nranges; a.pairs_per_range = p.ppr;
+  a.ndzdy = p.ndzdy; a.want_bias = want_bias;
+  a.nqi = p.nqi; a.nqj = p.nqj; a.nsub = p.nsub;
+  a.up = up; a.gD = up && kz == 3 ? 2 * a.D : a.D; a.gH = up ? 2 * a.H : a.H; a.gW = up ? 2 * a.W : a.W;      // (kz == 1: D == 1)
+  return zeros;
+}
 
-#ifdef DF_TUNING
-void df_debug_set_wgrad(int v) { g_wgrad_dbg = v; }
-#endif
+// ---- which kernel a call runs -------------------------------------------------------------------------------------------------------------
+enum Family { kFamDirect, kFamWx, kFamWxy, kFamXyzFused, kFamXyzStaged, kFamBf16x3, kFamThin, kFamSmallN, kFamUp2 };
+struct Choice {
+  Family fam;
+  int key;            // the instantiation: its entry in the family's list (direct: WP8, 0 = the generic row loop <xvec, gvec, 0>)
+  bool xvec, gvec;    // direct: 8-byte loads of x / gy (even channel count, 8-byte aligned pointer)
+  int64_t Wp;         // > 0: x and gy are first copied into zero-padded rows of Wp; fam and key are those of the padded shape
+  int algo;           // what make_plan needs: 0 direct | 1 Winograd in x | 2 in (x,y) | 3 in (x,y,z)
+};
+inline int align_of(const void* p) {
+  const uintptr_t u = reinterpret_cast<uintptr_t>(p);
+  return u % 16 == 0 ? 16 : u % 8 == 0 ? 8 : 4;
+}
+// the thin-layer shapes the matrix-core form covers (whether instantiated or not: the workspace query counts them all)
+inline bool thin_candidate(int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int kz) {
+  const ThinShape t = thin_shape(Cin, Cout);
+  return (t.swap || small_n_ok(Cin, Cout)) && thin_mfma_ok(B, D, H, W, t.Cw, t.Ct, kz);
+}
 
-int64_t df_conv_wgrad_workspace_bytes(int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int kz) {
-  if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
-  if (small_n_ok(Cin, Cout)) {
-    const SmallPlan sp = make_small_plan(B, D, H, Cin, Cout, kz);
-    int64_t fl = sp.partial_elems;
-    if (thin_mfma_ok(B, D, H, W, Cin, Cout, kz)) {
-      const int64_t t = thin_wgrad_ws_floats(B, D, H, Cin, Cout, false);
-      if (t > fl) fl = t;
-    }
-    return fl * static_cast<int64_t>(sizeof(float)) + kZeroBytes;
+// df_conv_wgrad* without the matrix-core thin form.  x_align, g_align: 16 | 8 | 4 bytes.
+Choice choose_conv_generic(int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int kz, int req, int prec, int x_align,
+                           int g_align) {
+  const bool a16 = x_align >= 16 && g_align >= 16;
+  if (small_n_ok(Cin, Cout)) return {kFamSmallN, kz * 10 + (int)Cout, false, false, 0, 0};
+  // (both precision modes: where the (x,y,z) form exists the bf16x3 mode keeps it -- see below -- so rows that reach an instantiated
+  //  length by zero padding take it too instead of the direct kernel; df_conv_wgrad_form reports 3 for them in both modes)
+  if (const int64_t Wp = a16 ? wxyz_padded_w(req, D, H, W, Cin, Cout, kz) : 0) {      // (pad_rows_kernel copies 16 bytes per lane)
+    Choice c = choose_conv_generic(B, D, H, Wp, Cin, Cout, kz, req, prec, 16, 16);
+    c.Wp = Wp;
+    return c;
   }
-  if (const int64_t Wp = wxyz_padded_w(0, D, H, W, Cin, Cout, kz))      // zero-padded rows + the workspace of the padded shape
-    return df_conv_wgrad_workspace_bytes(B, D, H, Wp, Cin, Cout, kz) + 256 + wxyz_pad_bytes(B, D, H, Wp, Cin, Cout);
-  int64_t best = 0;
-  if (Cin <= 4 && Cout >= 64 && thin_mfma_ok(B, D, H, W, Cout, Cin, kz))
-    best = thin_wgrad_ws_floats(B, D, H, Cout, Cin, true) * static_cast<int64_t>(sizeof(float));
-  for (int algo = 0; algo <= 3; ++algo) {       // the launch may fall back (operand alignment), so size for the largest
-    if ((algo == 1 && !wx_ok(W, Cin, Cout)) || (algo == 2 && !wxy_ok(H, W, Cin, Cout)) || (algo == 3 && !wxyz_ok(D, H, W, Cin, Cout, kz))) continue;
-    const Plan p = make_plan(B, D, H, W, Cin, Cout, kz, algo);
-    const int64_t n = plan_bound_elems(p) * static_cast<int64_t>(sizeof(float));
-    if (n > best) best = n;
+  const bool xvec = Cin % 2 == 0 && x_align >= 8, gvec = Cout % 2 == 0 && g_align >= 8;
+  // bf16x3 mode: rows without a bf16x3 variant (W = 56 | 28 | ... of cfg4) take the fp32 Winograd forms, not the 2.6x slower direct kernel
+  // ... and where the fp32 (x,y,z) Winograd form exists it is FASTER than the split-operand kernel (cfg3 top level 14.2 vs 15.2 ms, one level
+  // down 1.76 vs 2.03) and exact: the opt-in precision mode keeps it
+  if (prec == 1 && xvec && gvec && wgrad_bf16x3_ok(W, Cin, Cout) && !((req == 0 || req == 4) && wxyz_ok(D, H, W, Cin, Cout, kz) && a16))
+    return {kFamBf16x3, (int)(W / 16), true, true, 0, 0};
+  const int algo = xvec && gvec ? wgrad_algo(req, B * D * H, D, H, W, Cin, Cout, kz) : 0;
+  if (algo == 3) {
+    // the default (req 0) at the 128 -> 128, W = 64 | 32 levels: the staged form (operands fetched and combined once per workgroup,
+    // same partials bit for bit); req 4 keeps wgrad_wxyz_fused_kernel, the comparison and the form of every other shape
+    // (its 16-byte row loads need 16-byte aligned operands; the register-ring kernel reads 8 bytes per lane and gives the same bits)
+    if (req == 0 && c128(Cin, Cout) && in_list(kWxyzStagedWp8, W / 8) && a16) return {kFamXyzStaged, (int)(W / 8), true, true, 0, 3};
+    return {kFamXyzFused, wxyz_key(W, Cin, Cout), true, true, 0, 3};
   }
-  return best + zero_row_bytes(W, Cin, Cout);
+  if (algo == 2) return {kFamWxy, wc_of(kWxy, W, Cin, Cout), true, true, 0, 2};
+  if (algo == 1) return {kFamWx, wc_of(kWx, W, Cin, Cout), true, true, 0, 1};
+  const bool unrolled = xvec && gvec && W % 8 == 0 && in_list(kDirectWp8, W / 8);
+  return {kFamDirect, unrolled ? (int)(W / 8) : 0, xvec, gvec, 0, 0};
+}
+// df_conv_wgrad*: the matrix-core form of the thin layers where it is instantiated (16-byte raw buffer loads), else the above
+Choice choose_conv(int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int kz, int req, int prec, int x_align, int g_align) {
+  if (req != 1 && prec == 0 && x_align >= 16 && g_align >= 16 && thin_candidate(B, D, H, W, Cin, Cout, kz) &&
+      in_list(kThin, thin_key(W, thin_shape(Cin, Cout))))
+    return {kFamThin, thin_key(W, thin_shape(Cin, Cout)), false, false, 0, 0};
+  return choose_conv_generic(B, D, H, W, Cin, Cout, kz, req, prec, x_align, g_align);
+}
+// df_upconv_wgrad* (even channel counts)
+Choice choose_up(int64_t B, int64_t Dc, int64_t Hc, int64_t Wc, int64_t Cin, int64_t Cout, int kz, int req, int prec, int x_align, int g_align) {
+  // (the 27-point fp32 form beats the bf16x3 parity-class kernel too -- 5.8 vs 7.0 ms at the cfg3 top level -- so both precision modes take it)
+  if (up_wxyz_ok(req, B, Dc, Hc, Wc, Cin, Cout, kz) && x_align >= 16 && g_align >= 16)
+    return {kFamXyzFused, wxyz_key(2 * Wc, Cin, Cout), true, true, 0, 3};
+  // every kernel below but wgrad_kernel<*, *, 0> reads 8 bytes per lane from both operands: a pointer that is only 4-byte aligned
+  // takes the scalar loads of that kernel, as in choose_conv_generic
+  const bool xvec = x_align >= 8, gvec = g_align >= 8, aligned8 = xvec && gvec;
+  if (prec == 1 && aligned8 && wgrad_bf16x3_ok(Wc, Cin, Cout)) return {kFamBf16x3, (int)(Wc / 16), true, true, 0, 0};
+  if (const int up2 = aligned8 && req != 1 ? wc_of(kUp2, Wc, Cin, Cout) : 0) return {kFamUp2, up2, true, true, 0, 0};
+  const bool unrolled = aligned8 && Wc % 8 == 0 && in_list(kUpDirectWp8, Wc / 8);
+  return {kFamDirect, unrolled ? (int)(Wc / 8) : 0, xvec, gvec, 0, 0};
+}
+
+// Launch from a list: runs the launch statement with K = the compile-time copy of `key`; an error if the list does not hold `key` (a choice
+// function and a list disagree), so no instantiation is ever reached by default.
+#define DF_LAUNCH_FROM(list, key, what, ...)                                                              \
+  DF_REQUIRE(with_value(list, key, [&](auto k_) { constexpr int K = decltype(k_)::value; __VA_ARGS__; }), \
+             DF_EINVAL, "%s: no kernel instantiation for the form chosen", what)
+// the kernels both entry points share: wgrad_bf16x3_kernel; wgrad_kernel, the unrolled variant of c.key or the generic row loop with
+// 8-byte | scalar loads per operand
+int launch_direct_or_bf16x3(const Choice& c, dim3 grid, hipStream_t s, const WgradArgs& a, const char* what) {
+  if (c.fam == kFamBf16x3) DF_LAUNCH_FROM(kBf16x3W16, c.key, what, hipLaunchKernelGGL((wgrad_bf16x3_kernel<K>), grid, dim3(kThreads), 0, s, a));
+  else if (c.key) DF_LAUNCH_FROM(kDirectWp8, c.key, what, hipLaunchKernelGGL((wgrad_kernel<true, true, K>), grid, dim3(kThreads), 0, s, a));
+  else if (c.xvec && c.gvec) hipLaunchKernelGGL((wgrad_kernel<true, true, 0>), grid, dim3(kThreads), 0, s, a);
+  else if (c.xvec) hipLaunchKernelGGL((wgrad_kernel<true, false, 0>), grid, dim3(kThreads), 0, s, a);
+  else if (c.gvec) hipLaunchKernelGGL((wgrad_kernel<false, true, 0>), grid, dim3(kThreads), 0, s, a);
+  else hipLaunchKernelGGL((wgrad_kernel<false, false, 0>), grid, dim3(kThreads), 0, s, a);
+  return DF_OK;
 }
 
 // "not applicable, take the generic path": a value no hipError_t (> 0) and no DF_E* code (-1..-4) can take, so a real launch
 // failure of the thin kernel is never mistaken for the fall-back signal
 constexpr int kThinNotApplicable = -1000;
-static int launch_thin_wgrad(const float* wide, const float* thin, float* gw, float* gb, int64_t B, int64_t D, int64_t H, int64_t W,
-                             int64_t Cw, int64_t Ct, bool swap, void* workspace, df_stream_t stream) {
+int launch_thin_wgrad(const float* x, const float* gy, float* gw, float* gb, int64_t B, int64_t D, int64_t H, int64_t W, const ThinShape& t,
+                      int key, void* workspace, df_stream_t stream) {
+  const int64_t Cw = t.Cw, Ct = t.Ct;
   ThinWgradArgs ta;
   const int ns = thin_wgrad_streams(B, D, H);
   const int nrows = (int)(B * D * H);
-  ta.x = wide; ta.g = thin; ta.partial = static_cast<float*>(workspace);
+  ta.x = t.swap ? gy : x; ta.g = t.swap ? x : gy; ta.partial = static_cast<float*>(workspace);
   ta.bpartial = ta.partial + static_cast<int64_t>(ns) * 27 * Ct * Cw;
   ta.B = (int)B; ta.D = (int)D; ta.H = (int)H; ta.W = (int)W;
   ta.nrows = nrows; ta.nstreams = ns; ta.rows_per = (nrows + ns - 1) / ns;
@@ -2574,29 +2707,43 @@ static int launch_thin_wgrad(const float* wide, const float* thin, float* gw, fl
   hipStream_t s = df::as_stream(stream);
   const size_t lds = static_cast<size_t>(4) * 19 * ta.RS * sizeof(float);
   const dim3 grid((unsigned)(ns / 4));
-  const bool two = W * Ct > 256;
-#define DF_WT(CT, NJ, SW, NP)                                                                                                         \
-  do {                                                                                                                                \
-    if (lds > 65536) {                                                                                                                \
-      if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_thin_mfma_kernel<CT, NJ, SW, NP>),                  \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))                                   \
-        return df::fail((int)e, "df_conv_wgrad: LDS opt-in: %s", hipGetErrorString(e));                                               \
-    }                                                                                                                                 \
-    hipLaunchKernelGGL((wgrad_thin_mfma_kernel<CT, NJ, SW, NP>), grid, dim3(kThreads), lds, s, ta);                                   \
-  } while (0)
-  if (!swap && Cw == 128 && !two) {
-    if (Ct == 1) DF_WT(1, 4, false, 1); else if (Ct == 2) DF_WT(2, 4, false, 1); else if (Ct == 3) DF_WT(3, 4, false, 1); else DF_WT(4, 4, false, 1);
-  } else if (!swap && Cw == 128) DF_WT(3, 4, false, 2);
-  else if (!swap && !two) DF_WT(3, 2, false, 1);
-  else if (!swap) DF_WT(3, 2, false, 2);
-  else if (Cw == 128 && !two) DF_WT(3, 4, true, 1);
-  else if (Cw == 128) DF_WT(3, 4, true, 2);
-  else if (!two) DF_WT(3, 2, true, 1);
-  else DF_WT(3, 2, true, 2);
-#undef DF_WT
+  hipError_t e = hipSuccess;
+  const bool found = with_value(kThin, key, [&](auto k) {
+    constexpr int K = decltype(k)::value, CT = K / 1000, NJ = K / 100 % 10, NP = K % 10;
+    constexpr bool SWAP = K / 10 % 10 != 0;
+    if (lds > 65536)
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_thin_mfma_kernel<CT, NJ, SWAP, NP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) hipLaunchKernelGGL((wgrad_thin_mfma_kernel<CT, NJ, SWAP, NP>), grid, dim3(kThreads), lds, s, ta);
+  });
+  if (!found) return kThinNotApplicable;
+  if (e != hipSuccess) return df::fail((int)e, "df_conv_wgrad: LDS opt-in: %s", hipGetErrorString(e));
   hipLaunchKernelGGL(wgrad_thin_reduce_kernel, dim3((unsigned)(27 * Ct * (Cw / 32))), dim3(kThreads), 0, s, ta.partial, ta.bpartial, gw, gb,
-                     ns, (int)(27 * Ct), (int)Ct, (int)Cw, swap ? 1 : 0);
+                     ns, (int)(27 * Ct), (int)Ct, (int)Cw, t.swap ? 1 : 0);
   return df::launched("df_conv_wgrad(thin mfma)");
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t df_conv_wgrad_workspace_bytes(int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int kz) {
+  if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
+  // room for every form a launch may fall back to (operand alignment, the thin kernel's own limits): the largest
+  const ThinShape t = thin_shape(Cin, Cout);
+  const int64_t thin = thin_candidate(B, D, H, W, Cin, Cout, kz) ? thin_wgrad_ws_floats(B, D, H, t.Cw, t.Ct, t.swap) : 0;
+  if (small_n_ok(Cin, Cout)) {
+    const int64_t fl = make_small_plan(B, D, H, Cin, Cout, kz).partial_elems;
+    return (thin > fl ? thin : fl) * static_cast<int64_t>(sizeof(float)) + kZeroBytes;
+  }
+  if (const int64_t Wp = wxyz_padded_w(0, D, H, W, Cin, Cout, kz))      // zero-padded rows + the workspace of the padded shape
+    return df_conv_wgrad_workspace_bytes(B, D, H, Wp, Cin, Cout, kz) + 256 + wxyz_pad_bytes(B, D, H, Wp, Cin, Cout);
+  int64_t best = thin * static_cast<int64_t>(sizeof(float));
+  for (int algo = 0; algo <= 3; ++algo) {
+    if (!form_exists(algo, D, H, W, Cin, Cout, kz)) continue;
+    const int64_t n = plan_bound_elems(make_plan(B, D, H, W, Cin, Cout, kz, algo)) * static_cast<int64_t>(sizeof(float));
+    if (n > best) best = n;
+  }
+  return best + zero_row_bytes(W, Cin, Cout);
 }
 
 static int conv_wgrad_impl(const float* x, const float* gy, float* gw, float* gb, int64_t B, int64_t D, int64_t H, int64_t W,
@@ -2612,17 +2759,14 @@ static int conv_wgrad_impl(const float* x, const float* gy, float* gw, float* gb
   DF_REQUIRE(df::aligned16(workspace), DF_EALIGN, "df_conv_wgrad: workspace must be 16-byte aligned");
   DF_REQUIRE(workspace_bytes >= df_conv_wgrad_workspace_bytes(B, D, H, W, Cin, Cout, kz), DF_EWORKSPACE,
              "df_conv_wgrad: workspace too small");
-  {
-    // matrix-core form of the thin layers: F -> 1..4 (wide = x, thin = gy) or 1..4 -> F (SWAP: wide = gy, thin = x)
-    const bool swap = Cin <= 4 && Cout >= 64;
-    const int64_t Cw = swap ? Cout : Cin, Ct = swap ? Cin : Cout;
-    if ((swap || small_n_ok(Cin, Cout)) && req != 1 && prec == 0 && thin_mfma_ok(B, D, H, W, Cw, Ct, kz) &&
-        thin_mfma_inst(W, Cw, Ct, swap) && df::aligned16(x) && df::aligned16(gy)) {
-      const int rc = launch_thin_wgrad(swap ? gy : x, swap ? x : gy, gw, gb, B, D, H, W, Cw, Ct, swap, workspace, stream);
-      if (rc != kThinNotApplicable) return rc;      // shape outside the kernel's 32-bit stream offsets -> generic path below
-    }
+  hipStream_t s = df::as_stream(stream);
+  Choice c = choose_conv(B, D, H, W, Cin, Cout, kz, req, prec, align_of(x), align_of(gy));
+  if (c.fam == kFamThin) {
+    const int rc = launch_thin_wgrad(x, gy, gw, gb, B, D, H, W, thin_shape(Cin, Cout), c.key, workspace, stream);
+    if (rc != kThinNotApplicable) return rc;      // shape outside the kernel's 32-bit stream offsets -> generic path below
+    c = choose_conv_generic(B, D, H, W, Cin, Cout, kz, req, prec, align_of(x), align_of(gy));
   }
-  if (small_n_ok(Cin, Cout)) {
+  if (c.fam == kFamSmallN) {
     const SmallPlan sp = make_small_plan(B, D, H, Cin, Cout, kz);
     SmallWgradArgs sa;
     sa.x = x; sa.g = gy; sa.partial = static_cast<float*>(workspace);
@@ -2632,26 +2776,19 @@ static int conv_wgrad_impl(const float* x, const float* gy, float* gw, float* gb
     sa.B = (int)B; sa.D = (int)D; sa.H = (int)H; sa.W = (int)W; sa.Cin = (int)Cin; sa.Cout = (int)Cout;
     sa.Wp = (int)(ceil_div(W + 1, 8) * 8);
     sa.nrows = sp.nrows; sa.nstreams = sp.nstreams; sa.rows_per = sp.rows_per; sa.ncib = sp.ncib;
-    hipStream_t s = df::as_stream(stream);
     if (hipError_t e = df::zero_async(zeros, kZeroBytes, s)) return df::fail((int)e, "df_conv_wgrad: memset: %s", hipGetErrorString(e));
-    dim3 grid((unsigned)(sp.nstreams * sp.ncib / 4));
-#define DF_WS(KZ, CO) hipLaunchKernelGGL((wgrad_small_n_kernel<KZ, CO>), grid, dim3(kThreads), 0, s, sa)
-    if (kz == 3) { if (Cout == 1) DF_WS(3, 1); else if (Cout == 2) DF_WS(3, 2); else if (Cout == 3) DF_WS(3, 3); else DF_WS(3, 4); }
-    else { if (Cout == 1) DF_WS(1, 1); else if (Cout == 2) DF_WS(1, 2); else if (Cout == 3) DF_WS(1, 3); else DF_WS(1, 4); }
-#undef DF_WS
+    const dim3 grid((unsigned)(sp.nstreams * sp.ncib / 4));
+    DF_LAUNCH_FROM(kSmallN, c.key, "df_conv_wgrad(small-N)", hipLaunchKernelGGL((wgrad_small_n_kernel<K / 10, K % 10>), grid, dim3(kThreads), 0, s, sa));
     const int64_t per = static_cast<int64_t>(sp.taps) * Cin * sp.CO;
     int64_t rg = ceil_div(per, 32);
     hipLaunchKernelGGL(wgrad_small_reduce_kernel, dim3((unsigned)rg), dim3(kThreads), 0, s, sa.partial, sa.bpartial, gw,
                        gb, sp.nstreams, per, sp.CO, (int)Cout);
     return df::launched("df_conv_wgrad(small-N)");
   }
-  // (both precision modes: where the (x,y,z) form exists the bf16x3 mode keeps it -- see use_bf16x3 below -- so rows that reach an
-  //  instantiated length by zero padding take it too instead of the direct kernel; df_conv_wgrad_form reports 3 for them in both modes)
-  if (const int64_t Wp = df::aligned16(x) && df::aligned16(gy) ? wxyz_padded_w(req, D, H, W, Cin, Cout, kz) : 0) {
+  if (const int64_t Wp = c.Wp) {
     const int64_t inner = up256(df_conv_wgrad_workspace_bytes(B, D, H, Wp, Cin, Cout, kz));
     float* xp = reinterpret_cast<float*>(static_cast<char*>(workspace) + inner);
     float* gp = reinterpret_cast<float*>(reinterpret_cast<char*>(xp) + up256(B * D * H * Wp * Cin * 4));
-    hipStream_t s = df::as_stream(stream);
     const int64_t rows = B * D * H;
     hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)ceil_div(rows * Wp * (Cin / 4), kThreads)), dim3(kThreads), 0, s,
                        reinterpret_cast<const f32x4*>(x), reinterpret_cast<f32x4*>(xp), rows, (int)W, (int)Wp, (int)(Cin / 4));
@@ -2660,151 +2797,51 @@ static int conv_wgrad_impl(const float* x, const float* gy, float* gw, float* gb
     if (int e = df::launched("df_conv_wgrad(pad rows)")) return e;
     return conv_wgrad_impl(xp, gp, gw, gb, B, D, H, Wp, Cin, Cout, kz, workspace, inner, stream, prec, algo_arg);
   }
-  const bool xvec = (Cin % 2 == 0) && ((reinterpret_cast<uintptr_t>(x) & 7u) == 0);
-  const bool gvec = (Cout % 2 == 0) && ((reinterpret_cast<uintptr_t>(gy) & 7u) == 0);
-  // bf16x3 mode: rows without a bf16x3 variant (W = 56 | 28 | ... of cfg4) take the fp32 Winograd forms, not the 2.6x slower direct kernel
-  // ... and where the fp32 (x,y,z) Winograd form exists it is FASTER than the split-operand kernel (cfg3 top level 14.2 vs 15.2 ms, one level
-  // down 1.76 vs 2.03) and exact: the opt-in precision mode keeps it
-  const bool use_bf16x3 = prec == 1 && xvec && gvec && wgrad_bf16x3_ok(W, Cin, Cout) &&
-                          !((req == 0 || req == 4) && wxyz_ok(D, H, W, Cin, Cout, kz) && df::aligned16(x) && df::aligned16(gy));
-  const int algo = (!use_bf16x3 && xvec && gvec) ? wgrad_algo(req, B * D * H, D, H, W, Cin, Cout, kz) : 0;
-  const Plan p = make_plan(B, D, H, W, Cin, Cout, kz, algo, req_ranges);
+  const Plan p = make_plan(B, D, H, W, Cin, Cout, kz, c.algo, req_ranges);
   // a caller-chosen number of partial ranges may need more room than df_conv_wgrad_workspace_bytes (sized for the defaults) promises
   DF_REQUIRE(workspace_bytes >= (p.partial_elems + p.bpartial_elems) * static_cast<int64_t>(sizeof(float)) + zero_row_bytes(W, Cin, Cout),
              DF_EWORKSPACE, "df_conv_wgrad: workspace too small for %d partial ranges", p.nranges);
   WgradArgs a;
-  a.x = x; a.g = gy;
-  a.partial = static_cast<float*>(workspace);
-  a.bpartial = a.partial + p.partial_elems;
-  float* zeros = a.bpartial + p.bpartial_elems;
-  a.zeros = zeros;
-  a.B = (int)B; a.D = (int)D; a.H = (int)H; a.W = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout;
-  a.Cinp = p.Cinp; a.Coutp = p.Coutp;
-  a.Wp = (int)(ceil_div(W, 8) * 8);
-  a.nrows = p.nrows; a.npairs = p.npairs; a.nranges = p.nranges; a.pairs_per_range = p.ppr;
-  a.ndzdy = p.ndzdy; a.want_bias = gb != nullptr;
-  a.nqi = p.nqi; a.nqj = p.nqj; a.nsub = p.nsub;
-  a.up = 0; a.gD = a.D; a.gH = a.H; a.gW = a.W;
-  hipStream_t s = df::as_stream(stream);
+  float* zeros = fill_args(a, p, x, gy, gb != nullptr, workspace, B, D, H, W, Cin, Cout, kz, ceil_div(W, 8) * 8, 0);
   if (hipError_t e = df::zero_async(zeros, zero_row_bytes(W, Cin, Cout), s)) return df::fail((int)e, "df_conv_wgrad: memset: %s", hipGetErrorString(e));
-  dim3 grid((unsigned)(p.nranges * p.ndzdy), (unsigned)ceil_div(Cin, 128), (unsigned)ceil_div(Cout, 128));
-  if (use_bf16x3) {
-    launch_wgrad_bf16x3(W, grid, s, a);
-  } else if (algo == 3) {
+  const dim3 grid((unsigned)(p.nranges * p.ndzdy), (unsigned)ceil_div(Cin, 128), (unsigned)ceil_div(Cout, 128));
+  if (c.fam == kFamXyzFused || c.fam == kFamXyzStaged) {
     WxyzArgs aa;
     aa.w = a; aa.Ht = (int)(H / 2); aa.Dt = (int)(D / 2); aa.ntrows = p.nrows;
-#ifdef DF_TUNING
-    const dim3 gridq((unsigned)(p.nranges * 4), grid.y, grid.z);      // 4 workgroup types per launch
-#endif
     const dim3 gridf((unsigned)(p.nranges * 16), grid.y, grid.z);       // all 16 (xi_z, xi_y) types of a range, adjacent
-    // the default (req 0) at the 128 -> 128, W = 64 | 32 levels: the staged form (operands fetched and combined once per workgroup,
-    // same partials bit for bit); req 4 keeps wgrad_wxyz_fused_kernel, the comparison and the form of every other shape
-    // (its 16-byte row loads need 16-byte aligned operands; the register-ring kernel reads 8 bytes per lane and gives the same bits)
-    const bool staged = req == 0 && Cin == 128 && Cout == 128 && (W == 64 || W == 32) && df::aligned16(x) && df::aligned16(gy);
-    if (staged) {
-      if (W == 64) hipLaunchKernelGGL((wgrad_wxyz_staged_kernel<8>), gridf, dim3(kThreads), 0, s, aa);
-      else hipLaunchKernelGGL((wgrad_wxyz_staged_kernel<4>), gridf, dim3(kThreads), 0, s, aa);
-    } else {
-#define DF_WXYZ(WP) hipLaunchKernelGGL((wgrad_wxyz_fused_kernel<WP, 128>), gridf, dim3(kThreads), 0, s, aa)
-#ifdef DF_TUNING
-    // experiments of tools/wgrad_diag.py (W = 64 rows): four launches by (GZ, GY) class (the round-1 form) with DBGV variants
-#define DF_WXYZ_DBG(DBGV)                                                                                              \
-  do {                                                                                                                 \
-    hipLaunchKernelGGL((wgrad_wxyz_kernel<8, 128, true, true, false, DBGV>), gridq, dim3(kThreads), 0, s, aa);         \
-    hipLaunchKernelGGL((wgrad_wxyz_kernel<8, 128, true, false, false, DBGV>), gridq, dim3(kThreads), 0, s, aa);        \
-    hipLaunchKernelGGL((wgrad_wxyz_kernel<8, 128, false, true, false, DBGV>), gridq, dim3(kThreads), 0, s, aa);        \
-    hipLaunchKernelGGL((wgrad_wxyz_kernel<8, 128, false, false, false, DBGV>), gridq, dim3(kThreads), 0, s, aa);       \
-  } while (0)
-    if (W == 64 && g_wgrad_dbg == 1) DF_WXYZ_DBG(1); else if (W == 64 && g_wgrad_dbg == 2) DF_WXYZ_DBG(2);
-    else if (W == 64 && g_wgrad_dbg == 3) DF_WXYZ_DBG(3); else if (W == 64 && g_wgrad_dbg == 6) DF_WXYZ_DBG(6);
-    else if (W == 64 && g_wgrad_dbg == 7) DF_WXYZ_DBG(7); else if (W == 64 && g_wgrad_dbg == 8) DF_WXYZ_DBG(0);
-    else if (W == 64 && g_wgrad_dbg == 9) hipLaunchKernelGGL((wgrad_wxyz_fused_kernel<8, 128, 1>), gridf, dim3(kThreads), 0, s, aa);
-    else if (W == 64 && g_wgrad_dbg == 10) hipLaunchKernelGGL((wgrad_wxyz_fused_kernel<8, 128, 8>), gridf, dim3(kThreads), 0, s, aa);
+    if (c.fam == kFamXyzStaged)
+      DF_LAUNCH_FROM(kWxyzStagedWp8, c.key, "df_conv_wgrad(winograd-xyz)", hipLaunchKernelGGL((wgrad_wxyz_staged_kernel<K>), gridf, dim3(kThreads), 0, s, aa));
     else
-#undef DF_WXYZ_DBG
-#endif
-#define DF_WXYZ64(WP) hipLaunchKernelGGL((wgrad_wxyz_fused_kernel<WP, 64>), gridf, dim3(kThreads), 0, s, aa)
-#ifdef DF_TUNING
-    if (Cin == 64 && W == 128 && g_wgrad_dbg == 16) hipLaunchKernelGGL((wgrad_wxyz_fused_kernel<16, 64, 16>), gridf, dim3(kThreads), 0, s, aa);
-    else if (Cin == 64 && W == 64 && g_wgrad_dbg == 16) hipLaunchKernelGGL((wgrad_wxyz_fused_kernel<8, 64, 16>), gridf, dim3(kThreads), 0, s, aa);
-    else
-#endif
-    if (Cin == 64) { if (W == 128) DF_WXYZ64(16); else if (W == 64) DF_WXYZ64(8); else if (W == 32) DF_WXYZ64(4); else DF_WXYZ64(2); }
-    else
-    if (W == 64) DF_WXYZ(8); else if (W == 32) DF_WXYZ(4); else if (W == 16) DF_WXYZ(2); else if (W == 112) DF_WXYZ(14); else if (W == 128) DF_WXYZ(16); else DF_WXYZ(7);
-#undef DF_WXYZ
-#undef DF_WXYZ64
-    }
+      DF_LAUNCH_FROM(kWxyz, c.key, "df_conv_wgrad(winograd-xyz)", hipLaunchKernelGGL((wgrad_wxyz_fused_kernel<K / 1000, K % 1000>), gridf, dim3(kThreads), 0, s, aa));
     const int64_t rgx = ceil_div(Cin * Cout, 32);
     hipLaunchKernelGGL(wgrad_wxyz_reduce_kernel, dim3((unsigned)rgx), dim3(kThreads), 0, s, a.partial, a.bpartial, gw, gb,
                        Cin == 64 ? p.nranges : p.nranges * p.nsub, (int)Cin, (int)Cout, p.Cinp, p.Coutp, 0);      // (64 -> 64: summed in the workgroup)
     return df::launched("df_conv_wgrad(winograd-xyz)");
-  } else if (algo == 2) {
+  }
+  if (c.fam == kFamWxy) {
     WxyArgs aa;
     aa.w = a; aa.Ht = (int)(H / 2); aa.ntrows = p.nrows;
-    const bool c128 = Cin == 128 && Cout == 128;
     aa.w.ndzdy = p.ndzdy / 2;                         // workgroup types per launch: (dz) x 2 xi_y
     const dim3 gridh((unsigned)(p.nranges * aa.w.ndzdy), grid.y, grid.z);
-#define DF_WXY(WP, CSV)                                                                                  \
-  do {                                                                                                   \
-    hipLaunchKernelGGL((wgrad_wxy_kernel<WP, CSV, true>), gridh, dim3(kThreads), 0, s, aa);              \
-    hipLaunchKernelGGL((wgrad_wxy_kernel<WP, CSV, false>), gridh, dim3(kThreads), 0, s, aa);             \
-  } while (0)
-    if (W == 64 && c128) DF_WXY(8, 128);
-    else if (W == 64) DF_WXY(8, 0);
-    else if (W == 128) DF_WXY(16, 0);      // AE3 128^3 (cfg5)
-    else if (W == 96 && c128) DF_WXY(12, 128);      // 2-D 128x96 (cfg1/cfg2) and its 64x48 level
-    else if (W == 96) DF_WXY(12, 0);
-    else if (W == 48 && c128) DF_WXY(6, 128);
-    else if (W == 48) DF_WXY(6, 0);
-    else if (W == 112) DF_WXY(14, 0);      // cfg4 row lengths
-    else if (W == 56) DF_WXY(7, 0);
-    else if (W == 32 && c128) DF_WXY(4, 128);
-    else if (W == 32) DF_WXY(4, 0);
-    else if (c128) DF_WXY(2, 128);
-    else DF_WXY(2, 0);
-#undef DF_WXY
+    DF_LAUNCH_FROM(kWxy, c.key, "df_conv_wgrad(winograd-xy)",      // the xi_y pair with, then without the bias sum
+                   hipLaunchKernelGGL((wgrad_wxy_kernel<K / 1000, K % 1000, true>), gridh, dim3(kThreads), 0, s, aa);
+                   hipLaunchKernelGGL((wgrad_wxy_kernel<K / 1000, K % 1000, false>), gridh, dim3(kThreads), 0, s, aa));
     const int ndz = kz == 3 ? 3 : 1;
     const int64_t tot = static_cast<int64_t>(ndz) * Cin * Cout;
     const int64_t rgx = ceil_div(tot, 32);
     hipLaunchKernelGGL(wgrad_wxy_reduce_kernel, dim3((unsigned)rgx), dim3(kThreads), 0, s, a.partial, a.bpartial, gw, gb,
                        p.nranges * p.nsub, ndz, (int)Cin, (int)Cout, p.Cinp, p.Coutp);
     return df::launched("df_conv_wgrad(winograd-xy)");
-  } else if (algo == 1) {
-    const bool c128 = Cin == 128 && Cout == 128;
-    if (W == 64 && c128) hipLaunchKernelGGL((wgrad_wx_kernel<8, 128>), grid, dim3(kThreads), 0, s, a);
-    else if (W == 64) hipLaunchKernelGGL((wgrad_wx_kernel<8, 0>), grid, dim3(kThreads), 0, s, a);
-    else if (W == 128) hipLaunchKernelGGL((wgrad_wx_kernel<16, 0>), grid, dim3(kThreads), 0, s, a);
-    else if (W == 96) hipLaunchKernelGGL((wgrad_wx_kernel<12, 0>), grid, dim3(kThreads), 0, s, a);
-    else if (W == 48) hipLaunchKernelGGL((wgrad_wx_kernel<6, 0>), grid, dim3(kThreads), 0, s, a);
-    else if (W == 112) hipLaunchKernelGGL((wgrad_wx_kernel<14, 0>), grid, dim3(kThreads), 0, s, a);
-    else if (W == 56) hipLaunchKernelGGL((wgrad_wx_kernel<7, 0>), grid, dim3(kThreads), 0, s, a);
-    else if (W == 32 && c128) hipLaunchKernelGGL((wgrad_wx_kernel<4, 128>), grid, dim3(kThreads), 0, s, a);
-    else if (W == 32) hipLaunchKernelGGL((wgrad_wx_kernel<4, 0>), grid, dim3(kThreads), 0, s, a);
-    else if (c128) hipLaunchKernelGGL((wgrad_wx_kernel<2, 128>), grid, dim3(kThreads), 0, s, a);
-    else hipLaunchKernelGGL((wgrad_wx_kernel<2, 0>), grid, dim3(kThreads), 0, s, a);
+  }
+  if (c.fam == kFamWx) {
+    DF_LAUNCH_FROM(kWx, c.key, "df_conv_wgrad(winograd-x)", hipLaunchKernelGGL((wgrad_wx_kernel<K / 1000, K % 1000>), grid, dim3(kThreads), 0, s, a));
     const int64_t tot = static_cast<int64_t>(p.ndzdy) * Cin * Cout;
     const int64_t rgx = ceil_div(tot, 32) + (gb ? ceil_div(Cout, 32) : 0);      // 32 elements per workgroup + the bias workgroups
     hipLaunchKernelGGL(wgrad_wx_reduce_kernel, dim3((unsigned)rgx), dim3(kThreads), 0, s, a.partial, a.bpartial, gw, gb,
                        p.nranges * p.nsub, p.ndzdy, (int)Cin, (int)Cout, p.Cinp, p.Coutp);
     return df::launched("df_conv_wgrad(winograd-x)");
-  } else {
-  const int wp8 = a.Wp / 8;
-  const bool exact = (W % 8) == 0;
-  if (xvec && gvec && exact && wp8 == 8) hipLaunchKernelGGL((wgrad_kernel<true, true, 8>), grid, dim3(kThreads), 0, s, a);
-  else if (xvec && gvec && exact && wp8 == 16) hipLaunchKernelGGL((wgrad_kernel<true, true, 16>), grid, dim3(kThreads), 0, s, a);
-  else if (xvec && gvec && exact && wp8 == 4) hipLaunchKernelGGL((wgrad_kernel<true, true, 4>), grid, dim3(kThreads), 0, s, a);
-  else if (xvec && gvec && exact && wp8 == 14) hipLaunchKernelGGL((wgrad_kernel<true, true, 14>), grid, dim3(kThreads), 0, s, a);
-  else if (xvec && gvec && exact && wp8 == 12) hipLaunchKernelGGL((wgrad_kernel<true, true, 12>), grid, dim3(kThreads), 0, s, a);
-  else if (xvec && gvec && exact && wp8 == 7) hipLaunchKernelGGL((wgrad_kernel<true, true, 7>), grid, dim3(kThreads), 0, s, a);
-  else if (xvec && gvec && exact && wp8 == 2) hipLaunchKernelGGL((wgrad_kernel<true, true, 2>), grid, dim3(kThreads), 0, s, a);
-  else if (xvec && gvec && exact && wp8 == 3) hipLaunchKernelGGL((wgrad_kernel<true, true, 3>), grid, dim3(kThreads), 0, s, a);
-  else if (xvec && gvec && exact && wp8 == 6) hipLaunchKernelGGL((wgrad_kernel<true, true, 6>), grid, dim3(kThreads), 0, s, a);
-  else if (xvec && gvec) hipLaunchKernelGGL((wgrad_kernel<true, true, 0>), grid, dim3(kThreads), 0, s, a);
-  else if (xvec) hipLaunchKernelGGL((wgrad_kernel<true, false, 0>), grid, dim3(kThreads), 0, s, a);
-  else if (gvec) hipLaunchKernelGGL((wgrad_kernel<false, true, 0>), grid, dim3(kThreads), 0, s, a);
-  else hipLaunchKernelGGL((wgrad_kernel<false, false, 0>), grid, dim3(kThreads), 0, s, a);
   }
+  if (int e = launch_direct_or_bf16x3(c, grid, s, a, "df_conv_wgrad")) return e;
   const int64_t total = static_cast<int64_t>(p.taps) * Cin * Cout;
   const int64_t rg = ceil_div(total, 32) + (gb ? ceil_div(Cout, 32) : 0);      // 32 elements per workgroup + the bias workgroups
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rg), dim3(kThreads), 0, s, a.partial, a.bpartial, gw, gb,
@@ -2825,9 +2862,20 @@ int df_conv_wgrad_bf16x3(const float* x, const float* gy, float* gw, float* gb, 
   return conv_wgrad_impl(x, gy, gw, gb, B, D, H, W, Cin, Cout, kz, workspace, workspace_bytes, stream, 1, 0);
 }
 
+// Which kernel family a df_conv_wgrad_algo call with these arguments runs (16-byte aligned operands assumed): the silent size-based
+// choices made visible to the caller.  0 direct MFMA | 1 Winograd in x | 2 Winograd in (x,y) | 3 Winograd in (x,y,z) |
+// 10 thin layer on the matrix cores | 11 thin layer on the vector ALU (general-shape fallback); < 0: invalid arguments.
+static int form_of(const Choice& c) {
+  return c.fam == kFamWx ? 1 : c.fam == kFamWxy ? 2 : (c.fam == kFamXyzFused || c.fam == kFamXyzStaged) ? 3 : c.fam == kFamThin ? 10 : c.fam == kFamSmallN ? 11 : 0;
+}
+int df_conv_wgrad_form(int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int kz, int algo) {
+  if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (kz != 1 && kz != 3) || algo < 0 || (algo & 7) > 4) return DF_EINVAL;
+  return form_of(choose_conv(B, D, H, W, Cin, Cout, kz, algo & 7, 0, 16, 16));
+}
+
 // ---- stride-2 weight gradient (see wgrad_s2_kernel) ---------------------------------------------------------------------------------
 static bool s2_wgrad_ok(int64_t Wo, int64_t Cin, int64_t Cout) {
-  return (Wo == 8 || Wo == 16 || Wo == 32 || Wo == 64) && Cin % 2 == 0 && Cout % 2 == 0 && Cin >= 32 && Cout >= 32;
+  return Wo % 8 == 0 && in_list(kS2Wp8, Wo / 8) && Cin % 2 == 0 && Cout % 2 == 0 && Cin >= 32 && Cout >= 32;
 }
 int64_t df_conv_s2_wgrad_workspace_bytes(int64_t B, int64_t Do, int64_t Ho, int64_t Wo, int64_t Cin, int64_t Cout, int kz) {
   if (B <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || !s2_wgrad_ok(Wo, Cin, Cout)) return 0;
@@ -2843,30 +2891,16 @@ int df_conv_s2_wgrad(const float* x, const float* gy, float* gw, float* gb, int6
   DF_REQUIRE(s2_wgrad_ok(Wo, Cin, Cout), DF_ESHAPE,
              "df_conv_s2_wgrad: output rows of 8 | 16 | 32 | 64 voxels and even channel counts >= 32 only (other shapes: df_dilate2_odd + df_conv_wgrad)");
   DF_REQUIRE(B * Do * Ho < (1LL << 30) && 8 * B * Do * Ho * Wo * Cin < (1LL << 40), DF_ESHAPE, "df_conv_s2_wgrad: tensor too large");
-  DF_REQUIRE(df::aligned16(workspace) && (reinterpret_cast<uintptr_t>(x) & 7u) == 0 && (reinterpret_cast<uintptr_t>(gy) & 7u) == 0, DF_EALIGN,
+  DF_REQUIRE(df::aligned16(workspace) && align_of(x) >= 8 && align_of(gy) >= 8, DF_EALIGN,
              "df_conv_s2_wgrad: workspace must be 16-byte, x and gy 8-byte aligned");
   DF_REQUIRE(workspace_bytes >= df_conv_s2_wgrad_workspace_bytes(B, Do, Ho, Wo, Cin, Cout, kz), DF_EWORKSPACE, "df_conv_s2_wgrad: workspace too small");
   const Plan p = make_plan(B, Do, Ho, Wo, Cin, Cout, kz);
   WgradArgs a;
-  a.x = x; a.g = gy;
-  a.partial = static_cast<float*>(workspace);
-  a.bpartial = a.partial + p.partial_elems;
-  float* zeros = a.bpartial + p.bpartial_elems;
-  a.zeros = zeros;
-  a.B = (int)B; a.D = (int)Do; a.H = (int)Ho; a.W = (int)Wo; a.Cin = (int)Cin; a.Cout = (int)Cout;
-  a.Cinp = p.Cinp; a.Coutp = p.Coutp;
-  a.Wp = (int)Wo;
-  a.nrows = p.nrows; a.npairs = p.npairs; a.nranges = p.nranges; a.pairs_per_range = p.ppr;
-  a.ndzdy = p.ndzdy; a.want_bias = gb != nullptr;
-  a.nqi = p.nqi; a.nqj = p.nqj; a.nsub = p.nsub;
-  a.up = 0; a.gD = a.D; a.gH = a.H; a.gW = a.W;
+  float* zeros = fill_args(a, p, x, gy, gb != nullptr, workspace, B, Do, Ho, Wo, Cin, Cout, kz, Wo, 0);
   hipStream_t s = df::as_stream(stream);
   if (hipError_t e = df::zero_async(zeros, zero_row_bytes(2 * Wo, Cin, Cout), s)) return df::fail((int)e, "df_conv_s2_wgrad: memset: %s", hipGetErrorString(e));
-  dim3 grid((unsigned)(p.nranges * p.ndzdy), (unsigned)ceil_div(Cin, 128), (unsigned)ceil_div(Cout, 128));
-  if (Wo == 64) hipLaunchKernelGGL((wgrad_s2_kernel<8>), grid, dim3(kThreads), 0, s, a);
-  else if (Wo == 32) hipLaunchKernelGGL((wgrad_s2_kernel<4>), grid, dim3(kThreads), 0, s, a);
-  else if (Wo == 16) hipLaunchKernelGGL((wgrad_s2_kernel<2>), grid, dim3(kThreads), 0, s, a);
-  else hipLaunchKernelGGL((wgrad_s2_kernel<1>), grid, dim3(kThreads), 0, s, a);
+  const dim3 grid((unsigned)(p.nranges * p.ndzdy), (unsigned)ceil_div(Cin, 128), (unsigned)ceil_div(Cout, 128));
+  DF_LAUNCH_FROM(kS2Wp8, Wo / 8, "df_conv_s2_wgrad", hipLaunchKernelGGL((wgrad_s2_kernel<K>), grid, dim3(kThreads), 0, s, a));
   const int64_t total = static_cast<int64_t>(p.taps) * Cin * Cout;
   const int64_t rg = ceil_div(total, 32) + (gb ? ceil_div(Cout, 32) : 0);
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rg), dim3(kThreads), 0, s, a.partial, a.bpartial, gw, gb,
@@ -2874,69 +2908,24 @@ int df_conv_s2_wgrad(const float* x, const float* gy, float* gw, float* gb, int6
   return df::launched("df_conv_s2_wgrad");
 }
 
-// Which kernel family a df_conv_wgrad_algo call with these arguments runs (16-byte aligned operands assumed): the silent size-based
-// choices made visible to the caller.  0 direct MFMA | 1 Winograd in x | 2 Winograd in (x,y) | 3 Winograd in (x,y,z) |
-// 10 thin layer on the matrix cores | 11 thin layer on the vector ALU (general-shape fallback); < 0: invalid arguments.
-int df_conv_wgrad_form(int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int kz, int algo) {
-  if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (kz != 1 && kz != 3) || algo < 0 || (algo & 7) > 4) return DF_EINVAL;
-  const int req = algo & 7;
-  const bool swap = Cin <= 4 && Cout >= 64;
-  const int64_t Cw = swap ? Cout : Cin, Ct = swap ? Cin : Cout;
-  if ((swap || small_n_ok(Cin, Cout)) && req != 1 && thin_mfma_ok(B, D, H, W, Cw, Ct, kz) && thin_mfma_inst(W, Cw, Ct, swap)) return 10;
-  if (small_n_ok(Cin, Cout)) return 11;
-  if (Cin % 2 || Cout % 2) return 0;
-  if (wxyz_padded_w(req, D, H, W, Cin, Cout, kz)) return 3;      // (x,y,z) on zero-padded rows
-  return wgrad_algo(req, B * D * H, D, H, W, Cin, Cout, kz);
-}
-
-static Plan make_up_plan(int64_t B, int64_t Dc, int64_t Hc, int64_t Wc, int64_t Cin, int64_t Cout, int kz) {
-  Plan p = make_plan(B, Dc, Hc, Wc, Cin, Cout, kz);
-  p.ndzdy = kz == 3 ? 32 : 8;
-  // 32 | 8 (class, dz/dy) combos per range: 64 ranges x 32 combos = 2048 workgroups = 8 whole rounds of 256 CUs, and the
-  // partial buffer (96 | 24 slots per range) stays 4x smaller than with 256 ranges
-  const int nr = p.npairs >= 64 ? 64 : p.npairs;
-  p.maxr = nr;
-  p.ppr = (p.npairs + nr - 1) / nr;
-  p.nranges = (p.npairs + p.ppr - 1) / p.ppr;
-  p.taps = p.ndzdy * 3;                                  // partial slots per range
-  p.partial_elems = static_cast<int64_t>(p.nranges) * p.nsub * p.taps * p.Cinp * p.Coutp;
-  p.bpartial_elems = static_cast<int64_t>(p.nranges) * p.nsub * (kz == 3 ? 8 : 4) * p.Coutp;
-  return p;
-}
-
-// the 27-point Winograd-(x,y,z) form of the up-sampling-aware weight gradient (fine extents 2Dc x 2Hc x 2Wc)
-static bool up_wxyz_ok(int req, int64_t B, int64_t Dc, int64_t Hc, int64_t Wc, int64_t Cin, int64_t Cout, int kz) {
-  // at every size ([r3] batch 2 | 4 | 16, fine 16x24x16: parity-class 0.216 | 0.315 | 0.443 ms, 27-point 0.048 | 0.058 | 0.132; fine 32x48x32:
-  // 0.442 | 0.597 | 1.484 vs 0.129 | 0.222 | 0.787): the parity-class form pays a fixed-cost reduce of its 32-combo partials
-  (void)B;
-  return wxyz_ok(2 * Dc, 2 * Hc, 2 * Wc, Cin, Cout, kz) && req != 1 && req != 2 && req != 3;
-}
-
-// partial ranges of the 27-point (x,y,z) form: 9 workgroup types per range in one launch -- 28 ranges (252 workgroups: one round of
-// the 256 CUs) below 4096 tile-row pairs, 113 (1017: four rounds) above
-// (64 -> 64: the spare waves split each range four ways -- 28 ranges are already 112 partials)
-static int up_wxyz_ranges(int64_t B, int64_t Dc, int64_t Hc, int64_t Cin = 128, int64_t Cout = 128) {
-  return ((B * Dc * Hc + 1) / 2 < 4096 || (Cin <= 64 && Cout <= 64)) ? 28 : 113;
-}
-
-// The same for df_upconv_wgrad_algo: 3 = the 27-point Winograd-(x,y,z) form on the coarse input, 0 = the three-product parity-class
+// ---- up-sampling-aware weight gradient ----------------------------------------------------------------------------------------------------
+// The form query of df_upconv_wgrad_algo: 3 = the 27-point Winograd-(x,y,z) form on the coarse input, 0 = the three-product parity-class
 // kernel (algo 0 | 2) or the generic direct kernel on class-strided views (algo 1).
 int df_upconv_wgrad_form(int64_t B, int64_t Dc, int64_t Hc, int64_t Wc, int64_t Cin, int64_t Cout, int kz, int algo) {
   if (B <= 0 || Dc <= 0 || Hc <= 0 || Wc <= 0 || Cin <= 0 || Cout <= 0 || (kz != 1 && kz != 3) || algo < 0 || algo > 4) return DF_EINVAL;
-  return up_wxyz_ok(algo, B, Dc, Hc, Wc, Cin, Cout, kz) ? 3 : 0;
+  return form_of(choose_up(B, Dc, Hc, Wc, Cin, Cout, kz, algo, 0, 16, 16));
 }
 
 int64_t df_upconv_wgrad_workspace_bytes(int64_t B, int64_t Dc, int64_t Hc, int64_t Wc, int64_t Cin, int64_t Cout, int kz) {
   if (B <= 0 || Dc <= 0 || Hc <= 0 || Wc <= 0 || Cin <= 0 || Cout <= 0) return 0;
-  if (wxyz_ok(2 * Dc, 2 * Hc, 2 * Wc, Cin, Cout, kz)) {      // sized for either form (the choice depends on a debug switch)
-    const Plan q = make_plan(B, 2 * Dc, 2 * Hc, 2 * Wc, Cin, Cout, kz, 3, up_wxyz_ranges(B, Dc, Hc, Cin, Cout));
-    const Plan p = make_up_plan(B, Dc, Hc, Wc, Cin, Cout, kz);
-    const int64_t nq = plan_bound_elems(q) * static_cast<int64_t>(sizeof(float)) + zero_row_bytes(2 * Wc, Cin, Cout);
-    const int64_t np = plan_bound_elems(p) * static_cast<int64_t>(sizeof(float)) + zero_row_bytes(Wc, Cin, Cout);
-    return nq > np ? nq : np;
-  }
   const Plan p = make_up_plan(B, Dc, Hc, Wc, Cin, Cout, kz);
-  return plan_bound_elems(p) * static_cast<int64_t>(sizeof(float)) + zero_row_bytes(Wc, Cin, Cout);
+  int64_t best = plan_bound_elems(p) * static_cast<int64_t>(sizeof(float)) + zero_row_bytes(Wc, Cin, Cout);
+  if (up_wxyz_exists(Dc, Hc, Wc, Cin, Cout, kz)) {      // sized for either form (the choice depends on the request and the alignment)
+    const Plan q = make_up_wxyz_plan(B, Dc, Hc, Wc, Cin, Cout, kz);
+    const int64_t nq = plan_bound_elems(q) * static_cast<int64_t>(sizeof(float)) + zero_row_bytes(2 * Wc, Cin, Cout);
+    if (nq > best) best = nq;
+  }
+  return best;
 }
 
 static int upconv_wgrad_impl(const float* xc, const float* gy, float* gw, float* gb, int64_t B, int64_t Dc, int64_t Hc,
@@ -2951,36 +2940,19 @@ static int upconv_wgrad_impl(const float* xc, const float* gy, float* gw, float*
   DF_REQUIRE(df::aligned16(workspace), DF_EALIGN, "df_upconv_wgrad: workspace must be 16-byte aligned");
   DF_REQUIRE(workspace_bytes >= df_upconv_wgrad_workspace_bytes(B, Dc, Hc, Wc, Cin, Cout, kz), DF_EWORKSPACE,
              "df_upconv_wgrad: workspace too small");
-  // (the 27-point fp32 form beats the bf16x3 parity-class kernel too -- 5.8 vs 7.0 ms at the cfg3 top level -- so both precision modes take it)
-  if (up_wxyz_ok(req, B, Dc, Hc, Wc, Cin, Cout, kz) && df::aligned16(xc) && df::aligned16(gy)) {
+  hipStream_t s = df::as_stream(stream);
+  const Choice c = choose_up(B, Dc, Hc, Wc, Cin, Cout, kz, req, prec, align_of(xc), align_of(gy));
+  if (c.fam == kFamXyzFused) {
     const int64_t D = 2 * Dc, H = 2 * Hc, W = 2 * Wc;
-    const Plan p = make_plan(B, D, H, W, Cin, Cout, kz, 3, up_wxyz_ranges(B, Dc, Hc, Cin, Cout));
+    const Plan p = make_up_wxyz_plan(B, Dc, Hc, Wc, Cin, Cout, kz);
     WxyzArgs aa;
     WgradArgs& a = aa.w;
-    a.x = xc; a.g = gy;
-    a.partial = static_cast<float*>(workspace);
-    a.bpartial = a.partial + p.partial_elems;
-    float* zeros = a.bpartial + p.bpartial_elems;
-    a.zeros = zeros;
-    a.B = (int)B; a.D = (int)D; a.H = (int)H; a.W = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout;
-    a.Cinp = p.Cinp; a.Coutp = p.Coutp;
-    a.Wp = (int)W;
-    a.nrows = p.nrows; a.npairs = p.npairs; a.nranges = p.nranges; a.pairs_per_range = p.ppr;
-    a.ndzdy = p.ndzdy; a.want_bias = gb != nullptr;
-    a.nqi = p.nqi; a.nqj = p.nqj; a.nsub = p.nsub;
-    a.up = 0; a.gD = a.D; a.gH = a.H; a.gW = a.W;
+    float* zeros = fill_args(a, p, xc, gy, gb != nullptr, workspace, B, D, H, W, Cin, Cout, kz, W, 0);
     aa.Ht = (int)Hc; aa.Dt = (int)Dc; aa.ntrows = p.nrows;
-    hipStream_t s = df::as_stream(stream);
     if (hipError_t e = df::zero_async(zeros, zero_row_bytes(W, Cin, Cout), s)) return df::fail((int)e, "df_upconv_wgrad: memset: %s", hipGetErrorString(e));
-    const unsigned gy_ = (unsigned)ceil_div(Cin, 128), gz_ = (unsigned)ceil_div(Cout, 128);
-    const dim3 gridu((unsigned)(p.nranges * 9), gy_, gz_);          // all 9 live (xi_z, xi_y) types of a range, adjacent
-#define DF_UWXYZ(WP) hipLaunchKernelGGL((wgrad_wxyz_up_fused_kernel<WP, 128>), gridu, dim3(kThreads), 0, s, aa)
-#define DF_UWXYZ64(WP) hipLaunchKernelGGL((wgrad_wxyz_up_fused_kernel<WP, 64>), gridu, dim3(kThreads), 0, s, aa)
-    if (Cin == 64) { if (W == 128) DF_UWXYZ64(16); else if (W == 64) DF_UWXYZ64(8); else if (W == 32) DF_UWXYZ64(4); else DF_UWXYZ64(2); }
-    else
-    if (W == 64) DF_UWXYZ(8); else if (W == 32) DF_UWXYZ(4); else if (W == 16) DF_UWXYZ(2); else if (W == 112) DF_UWXYZ(14); else if (W == 128) DF_UWXYZ(16); else DF_UWXYZ(7);
-#undef DF_UWXYZ
-#undef DF_UWXYZ64
+    const dim3 gridu((unsigned)(p.nranges * 9), (unsigned)ceil_div(Cin, 128), (unsigned)ceil_div(Cout, 128));      // all 9 live (xi_z, xi_y) types of a range, adjacent
+    DF_LAUNCH_FROM(kWxyz, c.key, "df_upconv_wgrad(winograd-xyz, 27-point)",
+                   hipLaunchKernelGGL((wgrad_wxyz_up_fused_kernel<K / 1000, K % 1000>), gridu, dim3(kThreads), 0, s, aa));
     const int64_t rgx = ceil_div(Cin * Cout, 32);
     hipLaunchKernelGGL(wgrad_wxyz_reduce_kernel, dim3((unsigned)rgx), dim3(kThreads), 0, s, a.partial, a.bpartial, gw, gb,
                        Cin == 64 ? p.nranges : p.nranges * p.nsub, (int)Cin, (int)Cout, p.Cinp, p.Coutp, 1);
@@ -2988,42 +2960,12 @@ static int upconv_wgrad_impl(const float* xc, const float* gy, float* gw, float*
   }
   const Plan p = make_up_plan(B, Dc, Hc, Wc, Cin, Cout, kz);
   WgradArgs a;
-  a.x = xc; a.g = gy;
-  a.partial = static_cast<float*>(workspace);
-  a.bpartial = a.partial + p.partial_elems;
-  float* zeros = a.bpartial + p.bpartial_elems;
-  a.zeros = zeros;
-  a.B = (int)B; a.D = (int)Dc; a.H = (int)Hc; a.W = (int)Wc; a.Cin = (int)Cin; a.Cout = (int)Cout;
-  a.Cinp = p.Cinp; a.Coutp = p.Coutp;
-  a.Wp = (int)(ceil_div(Wc, 8) * 8);
-  a.nrows = p.nrows; a.npairs = p.npairs; a.nranges = p.nranges; a.pairs_per_range = p.ppr;
-  a.ndzdy = p.ndzdy; a.want_bias = gb != nullptr;
-  a.nqi = p.nqi; a.nqj = p.nqj; a.nsub = p.nsub;
-  a.up = 1; a.gD = kz == 3 ? 2 * a.D : 1; a.gH = 2 * a.H; a.gW = 2 * a.W;
-  hipStream_t s = df::as_stream(stream);
+  float* zeros = fill_args(a, p, xc, gy, gb != nullptr, workspace, B, Dc, Hc, Wc, Cin, Cout, kz, ceil_div(Wc, 8) * 8, 1);
   if (hipError_t e = df::zero_async(zeros, zero_row_bytes(Wc, Cin, Cout), s)) return df::fail((int)e, "df_upconv_wgrad: memset: %s", hipGetErrorString(e));
-  dim3 grid((unsigned)(p.nranges * p.ndzdy), (unsigned)ceil_div(Cin, 128), (unsigned)ceil_div(Cout, 128));
-  const int wp8 = a.Wp / 8;
-  const bool exact = (Wc % 8) == 0;
-  // every kernel below but wgrad_kernel<*, *, 0> reads 8 bytes per lane from both operands: a pointer that is only 4-byte aligned
-  // takes the scalar loads of that kernel, as in conv_wgrad_impl (channel counts are even here)
-  const bool xvec = (reinterpret_cast<uintptr_t>(xc) & 7u) == 0, gvec = (reinterpret_cast<uintptr_t>(gy) & 7u) == 0;
-  const bool aligned8 = xvec && gvec;
+  const dim3 grid((unsigned)(p.nranges * p.ndzdy), (unsigned)ceil_div(Cin, 128), (unsigned)ceil_div(Cout, 128));
   const dim3 grid2((unsigned)(p.nranges * (p.ndzdy / 2)), grid.y, grid.z);     // one workgroup per x-parity class PAIR
-  if (prec == 1 && aligned8 && wgrad_bf16x3_ok(Wc, Cin, Cout)) launch_wgrad_bf16x3(Wc, grid, s, a);
-  else if (aligned8 && exact && wp8 == 4 && Cin == 128 && Cout == 128 && req != 1) hipLaunchKernelGGL((wgrad_up2_kernel<4, 128>), grid2, dim3(kThreads), 0, s, a);
-  else if (aligned8 && exact && wp8 == 6 && Cin == 128 && Cout == 128 && req != 1) hipLaunchKernelGGL((wgrad_up2_kernel<6, 128>), grid2, dim3(kThreads), 0, s, a);      // 2-D 128x96: coarse W = 48 | 24
-  else if (aligned8 && exact && wp8 == 3 && Cin == 128 && Cout == 128 && req != 1) hipLaunchKernelGGL((wgrad_up2_kernel<3, 128>), grid2, dim3(kThreads), 0, s, a);
-  else if (aligned8 && exact && wp8 == 2 && req != 1) hipLaunchKernelGGL((wgrad_up2_kernel<2, 0>), grid2, dim3(kThreads), 0, s, a);
-  else if (aligned8 && exact && wp8 == 1 && req != 1) hipLaunchKernelGGL((wgrad_up2_kernel<1, 0>), grid2, dim3(kThreads), 0, s, a);
-  else if (aligned8 && exact && wp8 == 8) hipLaunchKernelGGL((wgrad_kernel<true, true, 8>), grid, dim3(kThreads), 0, s, a);
-  else if (aligned8 && exact && wp8 == 4) hipLaunchKernelGGL((wgrad_kernel<true, true, 4>), grid, dim3(kThreads), 0, s, a);
-  else if (aligned8 && exact && wp8 == 2) hipLaunchKernelGGL((wgrad_kernel<true, true, 2>), grid, dim3(kThreads), 0, s, a);
-  else if (aligned8 && exact && wp8 == 7) hipLaunchKernelGGL((wgrad_kernel<true, true, 7>), grid, dim3(kThreads), 0, s, a);
-  else if (aligned8) hipLaunchKernelGGL((wgrad_kernel<true, true, 0>), grid, dim3(kThreads), 0, s, a);
-  else if (xvec) hipLaunchKernelGGL((wgrad_kernel<true, false, 0>), grid, dim3(kThreads), 0, s, a);
-  else if (gvec) hipLaunchKernelGGL((wgrad_kernel<false, true, 0>), grid, dim3(kThreads), 0, s, a);
-  else hipLaunchKernelGGL((wgrad_kernel<false, false, 0>), grid, dim3(kThreads), 0, s, a);
+  if (c.fam == kFamUp2) DF_LAUNCH_FROM(kUp2, c.key, "df_upconv_wgrad", hipLaunchKernelGGL((wgrad_up2_kernel<K / 1000, K % 1000>), grid2, dim3(kThreads), 0, s, a));
+  else if (int e = launch_direct_or_bf16x3(c, grid, s, a, "df_upconv_wgrad")) return e;
   const int64_t total = static_cast<int64_t>(kz * 9) * Cin * Cout;
   const int64_t rg = ceil_div(total, 32);
   hipLaunchKernelGGL(wgrad_up_reduce_kernel, dim3((unsigned)rg), dim3(kThreads), 0, s, a.partial, a.bpartial, gw, gb,
@@ -3046,3 +2988,4 @@ int df_upconv_wgrad_bf16x3(const float* xc, const float* gy, float* gw, float* g
 }
 
 }  // extern "C"
+

@@ -1,7 +1,7 @@
 """No GPU: the case table of the weight-gradient edge tests (tests/wgrad_cases.py) against the host side of csrc/conv_wgrad.hip -- the form
-queries, the workspace queries, and the symbol table of the release library.  The table's "reaches" column is established by reading
-the dispatcher; what keeps it honest here is that it must name EVERY weight-gradient kernel instantiation the library holds, and nothing
-else: a new instantiation without a row fails test_every_instantiation_has_a_row."""
+queries, the workspace queries, and the symbol table of the release library.  The table's "reaches" column is observed by
+tests/test_wgrad_launches_host.py; what keeps it complete here is that it must name EVERY weight-gradient kernel instantiation the library
+holds, and nothing else: a new instantiation without a row fails test_every_instantiation_has_a_row."""
 import re
 import subprocess
 

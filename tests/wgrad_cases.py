@@ -10,11 +10,11 @@ A row:  (id, entry, shape, Cin, Cout, kz, algo, bias, xoff, goff, form, reaches,
   form     what df_conv_wgrad_form / df_upconv_wgrad_form answers for (shape, channels, kz, algo or 0).  The queries see no pointers and
            no precision mode, so for offset rows and bf16x3 rows this is the answer for aligned fp32 operands, not the kernel that runs.
            None for "s2" (no query).
-  reaches  the kernel instantiations the call launches, or "EALIGN" where the entry point must refuse the pointers.  ESTABLISHED BY READING
-           the dispatcher, not observed at run time: nothing in the library reports which kernel ran.  What the tests can observe backs
-           it indirectly -- the form query, bit-equality with a twin where two rows name the same kernel, bit-INEQUALITY between the
-           split-operand bf16x3 kernel and the fp32 kernels -- and the host test keeps the column complete: the set of names here equals
-           the set of weight-gradient instantiations in the release library's symbol table.
+  reaches  the kernel instantiations the call launches (in launch order, without the *_reduce_kernel and pad_rows_kernel launches), or
+           "EALIGN" where the entry point must refuse the pointers.  OBSERVED, without a GPU: tests/test_wgrad_launches_host.py runs every
+           row through tests/wgrad_launch_recorder.cpp, a program that links the release library, answers the HIP runtime calls of the
+           host path itself and names each launched kernel from the library's symbol table.  tests/test_wgrad_cases_host.py keeps the
+           column complete: the set of names here equals the set of weight-gradient instantiations in that symbol table.
   twin     for offset rows: (id of the aligned row with the same arguments, "bits" | "tol").  "bits": the offset call runs the same
            kernel, or one documented to give the same partial sums bit for bit (staged -> register-ring (x,y,z) kernel); "tol": another
            kernel, both within the tolerance of the oracle.
@@ -41,7 +41,7 @@ def WXY(wp, cs):      # two launches: the xi_y pair with and without the bias su
 
 
 def XYZ(wp, cs):
-    return ["wgrad_wxyz_fused_kernel<%d,%d,0>" % (wp, cs)]
+    return ["wgrad_wxyz_fused_kernel<%d,%d>" % (wp, cs)]
 
 
 def STG(wp):

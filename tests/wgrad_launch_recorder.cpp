@@ -1,0 +1,177 @@
+// Launch recorder of tests/test_wgrad_launches_host.py: calls the weight-gradient entry points of libdeepfluids_hip.so WITHOUT a GPU and
+// prints what they would have launched.  No HIP header, no device: this executable itself defines every HIP runtime call the host path of
+// csrc/conv_wgrad.hip makes (df_common.hpp, core.hip), and a symbol defined in the executable wins over the shared runtime's when the
+// library's calls are bound.  A launch arrives as hipLaunchKernel(kernel handle, grid, block, argument pointers, LDS bytes, stream);
+// handle - load base of the library = the symbol's value in the library's `nm -C` listing, which names the instantiation.
+//
+//   wgrad_launch_recorder <symbols> <rows>
+//     symbols  lines "<hex value> <demangled name>" (the library's nm -C listing, address and name columns)
+//     rows     lines "id entry B D H W Cin Cout kz algo bias xoff goff"; entry as in tests/wgrad_cases.py, algo -1 = the entry point
+//              without an algo argument
+//   per row:   "row <id>", one line per runtime call in order --
+//              "  launch <kernel> grid x y z block x lds <bytes> args <hex bytes>" | "  funcattr <kernel> <attribute> <value>" --
+//              then "end <id> rc <return code> ws <the workspace bytes the entry point's query asked for, and the call got>"
+// Operands sit at fixed fake addresses (never dereferenced on the host) plus the row's payload offsets; the LDS opt-in query is answered
+// with 160 KB (an unpartitioned MI355X).
+#include <dlfcn.h>
+
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <string>
+
+#include "deepfluids_hip.h"
+
+namespace {
+
+struct dim3 { unsigned x, y, z; };      // layout of HIP's dim3
+
+std::map<uintptr_t, std::string> g_names;      // symbol value -> demangled name
+dim3 g_grid, g_block;
+size_t g_lds;
+void* g_stream;
+
+std::string kernel_name(const void* f) {
+  Dl_info di;
+  if (!dladdr(f, &di) || !di.dli_fbase) return "?";
+  const auto it = g_names.find(reinterpret_cast<uintptr_t>(f) - reinterpret_cast<uintptr_t>(di.dli_fbase));
+  return it == g_names.end() ? "?" : it->second;
+}
+
+// Argument bytes of each kernel the weight-gradient host code launches: the sizes of its parameters in order.  The kernels that take one
+// argument struct list its size WITHOUT tail padding (WxyzArgs: 140 of 144, SmallWgradArgs: 84 of 88), which is not initialised.
+struct Layout { const char* prefix; int n; int size[12]; };
+const Layout kLayouts[] = {
+    {"(anonymous namespace)::wgrad_kernel<", 1, {128}},
+    {"(anonymous namespace)::wgrad_s2_kernel<", 1, {128}},
+    {"(anonymous namespace)::wgrad_up2_kernel<", 1, {128}},
+    {"(anonymous namespace)::wgrad_wx_kernel<", 1, {128}},
+    {"(anonymous namespace)::wgrad_bf16x3_kernel<", 1, {128}},
+    {"(anonymous namespace)::wgrad_wxy_kernel<", 1, {136}},
+    {"(anonymous namespace)::wgrad_wxyz_kernel<", 1, {140}},
+    {"(anonymous namespace)::wgrad_wxyz_fused_kernel<", 1, {140}},
+    {"(anonymous namespace)::wgrad_wxyz_up_fused_kernel<", 1, {140}},
+    {"(anonymous namespace)::wgrad_wxyz_staged_kernel<", 1, {140}},
+    {"(anonymous namespace)::wgrad_small_n_kernel<", 1, {84}},
+    {"(anonymous namespace)::wgrad_thin_mfma_kernel<", 1, {72}},
+    {"(anonymous namespace)::wgrad_reduce_kernel(", 10, {8, 8, 8, 8, 4, 4, 4, 4, 4, 4}},
+    {"(anonymous namespace)::wgrad_wx_reduce_kernel(", 10, {8, 8, 8, 8, 4, 4, 4, 4, 4, 4}},
+    {"(anonymous namespace)::wgrad_wxy_reduce_kernel(", 10, {8, 8, 8, 8, 4, 4, 4, 4, 4, 4}},
+    {"(anonymous namespace)::wgrad_wxyz_reduce_kernel(", 10, {8, 8, 8, 8, 4, 4, 4, 4, 4, 4}},
+    {"(anonymous namespace)::wgrad_up_reduce_kernel(", 10, {8, 8, 8, 8, 4, 4, 4, 4, 4, 4}},
+    {"(anonymous namespace)::wgrad_small_reduce_kernel(", 8, {8, 8, 8, 8, 4, 8, 4, 4}},
+    {"(anonymous namespace)::wgrad_thin_reduce_kernel(", 9, {8, 8, 8, 8, 4, 4, 4, 4, 4}},
+    {"(anonymous namespace)::pad_rows_kernel(", 6, {8, 8, 8, 4, 4, 4}},
+    {"df::zero_words_kernel(", 2, {8, 8}},
+};
+
+}  // namespace
+
+extern "C" {
+
+int __hipPushCallConfiguration(dim3 grid, dim3 block, size_t lds, void* stream) {
+  g_grid = grid; g_block = block; g_lds = lds; g_stream = stream;
+  return 0;
+}
+int __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* lds, void** stream) {
+  *grid = g_grid; *block = g_block; *lds = g_lds; *stream = g_stream;
+  return 0;
+}
+int hipLaunchKernel(const void* f, dim3 grid, dim3 block, void** args, size_t lds, void* stream) {
+  (void)stream;
+  const std::string name = kernel_name(f);
+  printf("  launch %s grid %u %u %u block %u lds %zu args ", name.c_str(), grid.x, grid.y, grid.z, block.x, lds);
+  const Layout* lay = nullptr;
+  for (const Layout& l : kLayouts)
+    if (name.compare(0, strlen(l.prefix), l.prefix) == 0) lay = &l;
+  if (!lay) { printf("?\n"); return 0; }
+  for (int i = 0; i < lay->n; ++i) {
+    const unsigned char* p = static_cast<const unsigned char*>(args[i]);
+    for (int b = 0; b < lay->size[i]; ++b) printf("%02x", p[b]);
+    if (i + 1 < lay->n) printf(".");
+  }
+  printf("\n");
+  return 0;
+}
+int hipGetLastError(void) { return 0; }
+int hipPeekAtLastError(void) { return 0; }
+const char* hipGetErrorString(int) { return "no error (launch recorder)"; }
+int hipFuncSetAttribute(const void* f, int attr, int value) {
+  printf("  funcattr %s %d %d\n", kernel_name(f).c_str(), attr, value);
+  return 0;
+}
+int hipGetDevice(int* dev) { *dev = 0; return 0; }
+int hipDeviceGetAttribute(int* v, int attr, int dev) {
+  (void)attr; (void)dev;
+  *v = 160 * 1024;
+  return 0;
+}
+int hipMemsetAsync(void* p, int value, size_t bytes, void* stream) {
+  (void)stream;
+  printf("  memset %p %d %zu\n", p, value, bytes);
+  return 0;
+}
+
+}  // extern "C"
+
+int main(int argc, char** argv) {
+  if (argc != 3) { fprintf(stderr, "usage: %s <symbols> <rows>\n", argv[0]); return 2; }
+  FILE* fs = fopen(argv[1], "r");
+  FILE* fr = fopen(argv[2], "r");
+  if (!fs || !fr) { fprintf(stderr, "cannot open %s\n", fs ? argv[2] : argv[1]); return 2; }
+  char line[4096];
+  while (fgets(line, sizeof line, fs)) {
+    char* end = nullptr;
+    const uintptr_t v = strtoull(line, &end, 16);
+    if (end == line || *end != ' ') continue;
+    std::string name(end + 1);
+    while (!name.empty() && (name.back() == '\n' || name.back() == ' ')) name.pop_back();
+    if (name.compare(0, 5, "void ") == 0) name.erase(0, 5);      // (function templates are listed with their return type)
+    g_names[v] = name;
+  }
+  fclose(fs);
+  float* const X = reinterpret_cast<float*>(0x100000000000ull);
+  float* const G = reinterpret_cast<float*>(0x200000000000ull);
+  float* const GW = reinterpret_cast<float*>(0x300000000000ull);
+  float* const GB = reinterpret_cast<float*>(0x400000000000ull);
+  void* const WS = reinterpret_cast<void*>(0x500000000000ull);
+  char id[128], entry[32];
+  long long B, D, H, W, Cin, Cout;
+  int kz, algo, bias, xoff, goff;
+  while (fgets(line, sizeof line, fr)) {
+    if (sscanf(line, "%127s %31s %lld %lld %lld %lld %lld %lld %d %d %d %d %d", id, entry, &B, &D, &H, &W, &Cin, &Cout, &kz, &algo, &bias,
+               &xoff, &goff) != 13)
+      continue;
+    const float* x = X + xoff;
+    const float* g = G + goff;
+    float* gb = bias ? GB : nullptr;
+    const std::string e(entry);
+    int64_t ws = 0;
+    int rc = -1000;
+    printf("row %s", id);
+    fflush(stdout);
+    if (e == "conv" || e == "conv_bf16x3") {
+      ws = df_conv_wgrad_workspace_bytes(B, D, H, W, Cin, Cout, kz);
+      printf("\n");
+      if (e == "conv_bf16x3") rc = df_conv_wgrad_bf16x3(x, g, GW, gb, B, D, H, W, Cin, Cout, kz, WS, ws, nullptr);
+      else if (algo < 0) rc = df_conv_wgrad(x, g, GW, gb, B, D, H, W, Cin, Cout, kz, WS, ws, nullptr);
+      else rc = df_conv_wgrad_algo(x, g, GW, gb, B, D, H, W, Cin, Cout, kz, WS, ws, algo, nullptr);
+    } else if (e == "up" || e == "up_bf16x3") {
+      ws = df_upconv_wgrad_workspace_bytes(B, D, H, W, Cin, Cout, kz);
+      printf("\n");
+      if (e == "up_bf16x3") rc = df_upconv_wgrad_bf16x3(x, g, GW, gb, B, D, H, W, Cin, Cout, kz, WS, ws, nullptr);
+      else if (algo < 0) rc = df_upconv_wgrad(x, g, GW, gb, B, D, H, W, Cin, Cout, kz, WS, ws, nullptr);
+      else rc = df_upconv_wgrad_algo(x, g, GW, gb, B, D, H, W, Cin, Cout, kz, WS, ws, algo, nullptr);
+    } else if (e == "s2") {
+      ws = df_conv_s2_wgrad_workspace_bytes(B, D, H, W, Cin, Cout, kz);
+      printf("\n");
+      rc = df_conv_s2_wgrad(x, g, GW, gb, B, D, H, W, Cin, Cout, kz, WS, ws, nullptr);
+    } else {
+      printf("\n");
+    }
+    printf("end %s rc %d ws %lld\n", id, rc, static_cast<long long>(ws));
+  }
+  fclose(fr);
+  return 0;
+}

@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# ARCHIVED: needs the tuning library as of the parent of the change that removed df_debug_set_wgrad (variant 16 no longer exists).
 """Round 5: 64 -> 64 (x,y,z)-Winograd weight gradient (cfg5 / every AE run): interleaved tile-row pairs per wave (production since round 5) vs contiguous
 sub-ranges (tuning variant 16, rounds 3-4) -- timing and agreement with the direct kernel."""
 import ctypes
@@ -7,7 +8,7 @@ import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from deep_fluids_amd import _lib as _libmod  # noqa: E402
 _libmod.use_tuning_library()

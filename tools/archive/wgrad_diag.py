@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# ARCHIVED: needs the tuning library as of the parent of the change that removed df_debug_set_wgrad and the DBG kernel variants.
 """Where the time of the (x,y,z) Winograd weight gradient goes (tuning library, results wrong by construction for dbg != 0):
 dbg 0 = production (one fused launch), 8 = four launches by (GZ, GY) class (the round-1 form), 9 = fused + cached loads (L1 hits),
 10 = fused + every range reads the same 8 tile rows (L2-resident working set, L1 misses as in production: the bound of any L2 prefetch);
