@@ -14,7 +14,6 @@ follow slim: ``<scope>/<layer>/weights`` ``[k,(k,)k,Cin,Cout]`` / ``[in,out]`` a
 import collections
 import contextlib
 import ctypes
-import contextlib as _contextlib
 import math
 import os as _os
 import threading as _threading
@@ -351,40 +350,74 @@ def _use_wino(cin, cout, dims, kz):
     return 2 if (CONV_ALGO == "winograd" or (dims[2] >= 16 and dims[3] >= 24)) else 0
 
 
-def _pack(w, taps, cin, cout, mode, dims=None, fp32=False, family=None):
-    """Packed MFMA operand of w for the stride-1 conv on `dims` (mode 0: forward, mode 1: dgrad).  ``fp32=True`` forces the exact-fp32
-    operand format whatever CONV_PRECISION says (kernels that have no bf16x3 variant: the stride-2 forward).  ``family="f222"``: the
-    F(2,3)^3 operand whatever WINO3D_FAMILY says (the 27-point forms)."""
-    algo = _use_wino(cin, cout, dims, 3 if taps == 27 else 1) if dims is not None else 0
-    if algo:
-        fn = ("df_wino43" if (family or WINO3D_FAMILY) == "f224" else "df_wino") if algo == 3 else (
-            "df_wino2d43" if (family or _w2fam(mode)) == "f24" else "df_wino2d")
-        wp = torch.empty(query(fn + "_packed_elems", cin, cout, mode), dtype=torch.float32, device=w.device)
-        call(fn + "_pack_weights", _ptr(w), _ptr(wp), cin, cout, mode, _stream())
-        return wp
-    sfx = "" if fp32 else _sfx(cin, cout)
-    n = query("df_conv_packed_elems" + sfx, taps, cin, cout, mode)
-    wp = torch.empty(n, dtype=torch.float32, device=w.device)
-    call("df_conv_pack_weights" + sfx, _ptr(w), _ptr(wp), taps, cin, cout, mode, _stream())
-    return wp
-
-
 # Sign-bit masks (conv_wino.hip): the forward convs of a fused generator block whose outputs only serve, in the backward pass, as the
 # lrelu mask of the next layer's dgrad also emit that mask as bit words (1/32 of the bytes); the masked dgrad then reads the words
 # instead of the fp32 activation.  Same arithmetic, bit-identical results; only the 3-D Winograd kernels have the path.
 SIGN_BIT_MASKS = _os.environ.get("DF_SIGN_BIT_MASKS", "1") != "0"
 
 
-def _bits_kind(cin, cout, dims, kz):
-    """Which sign-word layout a forward conv (cin -> cout on `dims`) can emit for the masked dgrad of the layer above: 0 none, 3 the 3-D Winograd
-    kernels' bytes (both 3-D families read and write them), 2 the words of the 2-D F(2,3) x F(4,3) kernel -- only where the dgrads run on that
-    kernel too (WINO2D_FAMILY "f24": forward and dgrad share the thread <-> output mapping the words are indexed by)."""
-    if not SIGN_BIT_MASKS:
-        return 0
-    algo = _use_wino(cin, cout, dims, kz)
+# The kernel of one stride-1 3x3(x3) conv under the current options:
+#   kind   "wino43" | "wino" | "wino2d43" | "wino2d" | "direct";
+#   fn     C-ABI prefix of its `*_packed_elems` / `*_pack_weights` pair;
+#   sfx    "_bf16x3" where the direct kernel runs in that mode, else "";
+#   form   its DISPATCH_COUNTS label (the thin case -- Cin or Cout <= 4 -- is a label of the direct kernel);
+#   bits   the sign-word layout its forward can emit for the masked dgrad of the layer above: 0 none, 3 the 3-D Winograd kernels' bytes (both
+#          3-D families read and write them), 2 the words of the 2-D F(2,3) x F(4,3) kernel -- only where the dgrads run on that kernel too
+#          (WINO2D_FAMILY "f24": forward and dgrad share the thread <-> output mapping the words are indexed by).
+_ConvKernel = collections.namedtuple("_ConvKernel", "kind fn sfx form bits")
+
+
+def _conv_kernel(cin, cout, dims, kz, mode, family=None):
+    """Which kernel a stride-1 conv cin -> cout on `dims` takes (mode 0 forward, 1 dgrad: the same layer with the two channel counts either way
+    round -- every rule is symmetric in them).  Decided here and nowhere else: packing, launch, dispatch label and sign words are all read
+    off the answer.  ``family`` ("f222" /
+    "f22") overrides WINO3D_FAMILY / WINO2D_FAMILY: the 27-point and 9-point up-sampling forms exist in those families only.  ``dims=None``
+    (an operand for a kernel outside this choice: the stride-2 forward): the direct kernel's format.  Evaluated per call, never kept: an
+    `options` block may change the answer at any time."""
+    algo = _use_wino(cin, cout, dims, kz) if dims is not None else 0
     if algo == 3:
-        return 3
-    return 2 if (algo == 2 and _w2fam(0) == "f24" and _w2fam(1) == "f24") else 0
+        return _KERNELS["wino43" if (family or WINO3D_FAMILY) == "f224" else "wino", 3 if SIGN_BIT_MASKS else 0]
+    if algo == 2:
+        bits = 2 if (SIGN_BIT_MASKS and _w2fam(0) == "f24" and _w2fam(1) == "f24") else 0
+        return _KERNELS["wino2d43" if (family or _w2fam(mode)) == "f24" else "wino2d", bits]
+    if min(cin, cout) <= 4:
+        return _KERNELS["thin-valu-forced" if THIN_VALU_ONLY else "thin", 0]
+    return _KERNELS["direct-mfma" + _sfx(cin, cout), 0]
+
+
+# every possible answer, built once (the choice runs several times per conv and step: a lookup, not a construction)
+_KERNELS = {(kind, bits): _ConvKernel(kind, fn, "", form, bits) for bits in (0, 2, 3) for kind, fn, form in (
+    ("wino43", "df_wino43", "winograd-f2x2x4"), ("wino", "df_wino", "winograd-f2x2x2"), ("wino2d43", "df_wino2d43", "winograd-f2x4"),
+    ("wino2d", "df_wino2d", "winograd-f2x2"))}
+_KERNELS.update({(form, 0): _ConvKernel("direct", "df_conv", sfx, form, 0) for form, sfx in (
+    ("thin", ""), ("thin-valu-forced", ""), ("direct-mfma", ""), ("direct-mfma_bf16x3", "_bf16x3"))})
+
+
+def _pack(w, taps, cin, cout, mode, dims=None, fp32=False, family=None):
+    """Packed MFMA operand of w for the stride-1 conv on `dims` (mode 0: forward, mode 1: dgrad).  ``fp32=True`` forces the exact-fp32
+    operand format whatever CONV_PRECISION says (kernels that have no bf16x3 variant: the stride-2 forward).  ``family="f222"``: the
+    F(2,3)^3 operand whatever WINO3D_FAMILY says (the 27-point forms)."""
+    k = _conv_kernel(cin, cout, dims, 3 if taps == 27 else 1, mode, family)
+    if k.kind != "direct":
+        wp = torch.empty(query(k.fn + "_packed_elems", cin, cout, mode), dtype=torch.float32, device=w.device)
+        call(k.fn + "_pack_weights", _ptr(w), _ptr(wp), cin, cout, mode, _stream())
+        return wp
+    sfx = "" if fp32 else k.sfx
+    wp = torch.empty(query(k.fn + "_packed_elems" + sfx, taps, cin, cout, mode), dtype=torch.float32, device=w.device)
+    call(k.fn + "_pack_weights" + sfx, _ptr(w), _ptr(wp), taps, cin, cout, mode, _stream())
+    return wp
+
+
+def _upconv_pack(w, cin, cout, kz, mode, sfx=""):
+    """Packed operand of the parity-class kernels (df_upconv_*): mode 0 forward, 1 dgrad, 2 the stride-2 conv's dgrad."""
+    wp = torch.empty(query("df_upconv_packed_elems" + sfx, cin, cout, kz, mode), dtype=torch.float32, device=w.device)
+    call("df_upconv_pack_weights" + sfx, _ptr(w), _ptr(wp), cin, cout, kz, mode, _stream())
+    return wp
+
+
+def _bits_kind(cin, cout, dims, kz):
+    """Which sign-word layout a forward conv (cin -> cout on `dims`) can emit for the masked dgrad of the layer above (`_ConvKernel.bits`)."""
+    return _conv_kernel(cin, cout, dims, kz, 0).bits
 
 
 def _new_bits(dims, c, like, kind=3):
@@ -429,48 +462,68 @@ SIGN_BITS_FETCH = None
 
 
 def _conv_raw(x, wp, bias, residual, mask_src, dims, cin, cout, kz, flags, leak, sign_bits=None, mask_bits=None):
-    """`wp` must come from ``_pack(..., dims)`` with the same dims AND mode (the two agree on the algorithm and the family: every forward
-    call carries DF_CONV_BIAS, no dgrad call does -- that is how the pack mode is recognised here)."""
+    """`wp` must come from ``_pack(..., dims)`` with the same dims AND mode: both ask `_conv_kernel` (every forward call carries DF_CONV_BIAS,
+    no dgrad call does -- that is how the pack mode is recognised here)."""
     mode = 0 if (flags & DF_CONV_BIAS) else 1
     B, D, H, W = dims
     y = torch.empty((B, D, H, W, cout), dtype=torch.float32, device=x.device)
-    algo = _use_wino(cin, cout, dims, kz)
+    k = _conv_kernel(cin, cout, dims, kz, mode)
     if DISPATCH_COUNTS is not None:
-        thin = min(cin, cout) <= 4
-        _count("conv", ("winograd-f2x2x4" if WINO3D_FAMILY == "f224" else "winograd-f2x2x2") if algo == 3 else
-               ("winograd-f2x4" if _w2fam(mode) == "f24" else "winograd-f2x2") if algo == 2 else
-               ("thin" + ("-valu-forced" if THIN_VALU_ONLY else "")) if thin else ("direct-mfma" + _sfx(cin, cout)), dims, cin, cout)
-    if algo == 3 and WINO3D_FAMILY == "f224":
+        _count("conv", k.form, dims, cin, cout)
+    words = sign_bits is not None or mask_bits is not None
+    if k.kind == "wino43":
         call("df_wino43_conv", _ptr(x), _ptr(wp), _ptr(bias), _ptr(residual), _ptr(mask_src), _ptr(mask_bits), _ptr(y), None, _ptr(sign_bits),
              B, D, H, W, cin, cout, flags, float(leak), _stream())
-        return y
-    if algo == 3:
-        if sign_bits is not None or mask_bits is not None:
-            call("df_wino_conv_fwd_bits", _ptr(x), _ptr(wp), _ptr(bias), _ptr(mask_bits), _ptr(y), _ptr(sign_bits), B, D, H, W, cin, cout,
-                 flags, float(leak), _stream())
-            return y
+    elif k.kind == "wino" and words:
+        call("df_wino_conv_fwd_bits", _ptr(x), _ptr(wp), _ptr(bias), _ptr(mask_bits), _ptr(y), _ptr(sign_bits), B, D, H, W, cin, cout,
+             flags, float(leak), _stream())
+    elif k.kind == "wino":
         call("df_wino_conv_fwd", _ptr(x), _ptr(wp), _ptr(bias), _ptr(residual), _ptr(mask_src), _ptr(y), B, D, H, W, cin, cout,
              flags, float(leak), _stream())
-        return y
-    if (sign_bits is not None or mask_bits is not None) and not (algo == 2 and _w2fam(mode) == "f24"):
-        raise _lib.DeepFluidsHipError("sign-bit masks exist for the 3-D Winograd kernels and the 2-D F(2,3) x F(4,3) kernel only")
-    if algo == 2 and _w2fam(mode) == "f24" and (sign_bits is not None or mask_bits is not None):
+    elif k.kind == "wino2d43" and words:
         call("df_wino2d43_conv_bits", _ptr(x), _ptr(wp), _ptr(bias), _ptr(mask_bits), _ptr(y), _ptr(sign_bits), B, H, W, cin, cout, flags, float(leak),
              _stream())
-        return y
-    if algo == 2 and _w2fam(mode) == "f24":
+    elif words:
+        raise _lib.DeepFluidsHipError("sign-bit masks exist for the 3-D Winograd kernels and the 2-D F(2,3) x F(4,3) kernel only")
+    elif k.kind == "wino2d43":
         call("df_wino2d43_conv", _ptr(x), _ptr(wp), _ptr(bias), _ptr(residual), _ptr(mask_src), _ptr(y), B, H, W, cin, cout, flags, float(leak),
              _stream())
-        return y
-    if algo == 2:
+    elif k.kind == "wino2d":
         call("df_wino2d_conv_fwd", _ptr(x), _ptr(wp), _ptr(bias), _ptr(residual), _ptr(mask_src), _ptr(y), B, H, W, cin, cout,
              flags, float(leak), _stream())
-        return y
-    if THIN_VALU_ONLY:
-        flags |= _lib.DF_CONV_VALU_ONLY
-    call("df_conv_fwd" + _sfx(cin, cout), _ptr(x), _ptr(wp), _ptr(bias), _ptr(residual), _ptr(mask_src), _ptr(y), B, D, H, W,
-         cin, cout, kz, flags, float(leak), _stream())
+    else:
+        if THIN_VALU_ONLY:
+            flags |= _lib.DF_CONV_VALU_ONLY
+        call("df_conv_fwd" + k.sfx, _ptr(x), _ptr(wp), _ptr(bias), _ptr(residual), _ptr(mask_src), _ptr(y), B, D, H, W,
+             cin, cout, kz, flags, float(leak), _stream())
     return y
+
+
+def _geom(x, ws, who):
+    """``(kz, taps, dims)`` of the k=3 convs with weights `ws` applied in a row to the channels-last `x` ([B, (D,) H, W, C]); raises where a
+    weight is not [3, (3,) 3, Cin, Cout] with Cin the channel count that reaches it.  `who` names the caller in the error."""
+    nd = x.dim() - 2
+    c = x.shape[-1]
+    for w in ws:
+        if tuple(w.shape[:-2]) != (3,) * nd or w.shape[-2] != c:
+            raise ValueError("%s: weights %s do not match input %s (k=3 only)" % (who, tuple(w.shape), tuple(x.shape[:-1]) + (c,)))
+        c = w.shape[-1]
+    dims = (x.shape[0], x.shape[1] if nd == 3 else 1, x.shape[-3], x.shape[-2])
+    return (3, 27, dims) if nd == 3 else (1, 9, dims)
+
+
+def _conv_bwd_prologue(gy, y, leak, w, bptr):
+    """What the backward of a single conv starts with: the gradient through the fused lrelu (if any) and the outputs of the weight / bias
+    gradient kernels -> ``(dp, gw, rw, gb, rb)`` (rw, rb: what backward returns for them, see `_grad_out`)."""
+    gy = _prep(gy, "grad")
+    if leak is not None:
+        dp = torch.empty_like(gy)
+        call("df_lrelu_bwd", _ptr(gy), _ptr(y), _ptr(dp), float(leak), gy.numel(), _stream())
+    else:
+        dp = gy
+    gw, rw = _grad_out(w.data_ptr(), w.shape, w.device)
+    gb, rb = _grad_out(bptr, (w.shape[-1],), w.device)
+    return dp, gw, rw, gb, rb
 
 
 class _ConvSame3(torch.autograd.Function):
@@ -479,13 +532,8 @@ class _ConvSame3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, leak):
         x = _prep(x, "x"); w = _prep(w, "weights"); b = _prep(b, "biases")
-        nd = x.dim() - 2
-        kz = 3 if nd == 3 else 1
-        taps = 27 if nd == 3 else 9
+        kz, taps, dims = _geom(x, [w], "conv")
         cin, cout = w.shape[-2], w.shape[-1]
-        if tuple(w.shape[:-2]) != (3,) * nd or x.shape[-1] != cin:
-            raise ValueError("conv: weights %s do not match input %s (k=3 only)" % (tuple(w.shape), tuple(x.shape)))
-        dims = (x.shape[0], x.shape[1] if nd == 3 else 1, x.shape[-3], x.shape[-2])
         wp = _pack(w, taps, cin, cout, 0, dims)
         flags = DF_CONV_BIAS | (DF_CONV_LRELU if leak is not None else 0)
         y = _conv_raw(x, wp, b, None, None, dims, cin, cout, kz, flags, leak if leak is not None else 0.0)
@@ -503,14 +551,7 @@ class _ConvSame3(torch.autograd.Function):
         x, w, y = ctx.saved_tensors
         dims, cin, cout, kz, taps = ctx.geom
         B, D, H, W = dims
-        gy = _prep(gy, "grad")
-        if ctx.leak is not None:
-            dp = torch.empty_like(gy)
-            call("df_lrelu_bwd", _ptr(gy), _ptr(y), _ptr(dp), float(ctx.leak), gy.numel(), _stream())
-        else:
-            dp = gy
-        gw, rw = _grad_out(w.data_ptr(), w.shape, x.device)
-        gb, rb = _grad_out(ctx.bptr, (cout,), x.device)
+        dp, gw, rw, gb, rb = _conv_bwd_prologue(gy, y, ctx.leak, w, ctx.bptr)
         _wgrad(x, dp, gw, gb, B, D, H, W, cin, cout, kz, _sfx(cin, cout))
         gx = None
         if ctx.needs_input_grad[0]:
@@ -519,55 +560,78 @@ class _ConvSame3(torch.autograd.Function):
         return gx, rw, rb, None
 
 
-class _GenBlock(torch.autograd.Function):
-    """One generator block as a single autograd node: n x [conv k3 s1 + bias + lrelu] and the residual add of the
-    block input (model.py:24-40 / 66-82).  Forward = the same kernels as the layer-by-layer path; the hand-written
-    reverse chain uses the fused epilogues of ``df_conv_fwd``: each dgrad multiplies by the lrelu slope of the layer
-    below (DF_CONV_MASK) and the first layer's dgrad adds the skip gradient (DF_CONV_RESIDUAL), which removes three
-    element-wise passes and one gradient-accumulation pass over the block's activations per block."""
+# The per-layer steps the fused nodes (_ConvStack, _UpGenBlock) share.
+def _layer_fwd(x, w, b, dims, kz, taps, leak, want_bits):
+    """conv k3 s1 + bias + lrelu -> (activation, its sign words or None).  `want_bits`: the activation only serves as the lrelu mask of the
+    dgrad of the layer above -- emit the mask as sign words too, where this layer's kernel can."""
+    cin, cout = w.shape[-2], w.shape[-1]
+    wp = _pack(w, taps, cin, cout, 0, dims)
+    bk = _bits_kind(cin, cout, dims, kz) if want_bits else 0
+    sb = _new_bits(dims, cout, x, bk) if bk else None
+    y = _conv_raw(x, wp, b, None, None, dims, cin, cout, kz, DF_CONV_BIAS | DF_CONV_LRELU, leak, sign_bits=sb)
+    return y.view(x.shape[:-1] + (cout,)), sb
+
+
+def _layer_wgrad(lane, x, dp, w, bptr, dims, kz):
+    """Weight and bias gradient of the layer with input `x` and masked output gradient `dp`, on the lane -> what backward returns for (w, b)."""
+    cin, cout = w.shape[-2], w.shape[-1]
+    B, D, H, W = dims
+    gw, rw = _grad_out(w.data_ptr(), w.shape, dp.device)
+    gb, rb = _grad_out(bptr, (cout,), dp.device)
+    lane.run(lambda: _wgrad(x, dp, gw, gb, B, D, H, W, cin, cout, kz, _sfx(cin, cout)), dp, gw, gb)
+    return rw, rb
+
+
+def _layer_dgrad_masked(dp, w, dims, kz, taps, leak, act, bits):
+    """dgrad of a layer times the lrelu slope of the layer below -- from that layer's sign words `bits` if its forward emitted them, else from
+    its fp32 activation `act`: directly the next dp."""
+    cin, cout = w.shape[-2], w.shape[-1]
+    wpd = _pack(w, taps, cin, cout, 1, dims)
+    return _conv_raw(dp, wpd, None, None, None if bits is not None else act, dims, cout, cin, kz, DF_CONV_MASK, leak, mask_bits=bits).view(act.shape)
+
+
+class _ConvStack(torch.autograd.Function):
+    """n x [conv k3 s1 + bias + lrelu] in a row as ONE autograd node, with (``skip``) or without the residual add of the input at the end:
+    a generator block (model.py:24-40 / 66-82) or the per-level conv stack of the encoder (model.py:131-136 / 167-172; its first conv may
+    change the channel count).  Forward = the same kernels as the layer-by-layer path; the hand-written reverse chain uses the fused
+    epilogues of the conv kernels: each dgrad multiplies by the lrelu slope of the layer below (DF_CONV_MASK; sign words where the Winograd
+    forward emits them) and with ``skip`` the first layer's dgrad adds the skip gradient (DF_CONV_RESIDUAL) -- per block three element-wise
+    passes and one gradient-accumulation pass over the activations less; only the LAST layer's element-wise lrelu-backward pass remains."""
 
     @staticmethod
-    def forward(ctx, x0, leak, *wb):
+    def forward(ctx, x0, leak, skip, *wb):
+        who = "gen_block" if skip else "conv_chain"
         x0 = _prep(x0, "x")
         n = len(wb) // 2
-        nd = x0.dim() - 2
-        kz = 3 if nd == 3 else 1
-        taps = 27 if nd == 3 else 9
-        dims = (x0.shape[0], x0.shape[1] if nd == 3 else 1, x0.shape[-3], x0.shape[-2])
+        ws = [_prep(w, "weights") for w in wb[0::2]]
+        bs = [_prep(b, "biases") for b in wb[1::2]]
+        kz, taps, dims = _geom(x0, ws, who)
         xs = [x0]
         bits = []
-        x = x0
         for i in range(n):
-            w = _prep(wb[2 * i], "weights"); b = _prep(wb[2 * i + 1], "biases")
-            cin, cout = w.shape[-2], w.shape[-1]
-            if tuple(w.shape[:-2]) != (3,) * nd or x.shape[-1] != cin:
-                raise ValueError("gen_block: weights %s do not match input %s" % (tuple(w.shape), tuple(x.shape)))
-            wp = _pack(w, taps, cin, cout, 0, dims)
             # outputs of convs 1 .. n-1 are the masks of the dgrads of convs 2 .. n
-            bk = _bits_kind(cin, cout, dims, kz) if i < n - 1 else 0
-            sb = _new_bits(dims, cout, x0, bk) if bk else None
-            bits.append(sb)
-            x = _conv_raw(x, wp, b, None, None, dims, cin, cout, kz, DF_CONV_BIAS | DF_CONV_LRELU, leak, sign_bits=sb).view(
-                x0.shape[:-1] + (cout,))
+            x, sb = _layer_fwd(xs[i], ws[i], bs[i], dims, kz, taps, leak, i < n - 1)
             xs.append(x)
-        if x.shape != x0.shape:
-            raise ValueError("gen_block: residual add needs Cout == Cin of the block")
-        y = torch.empty_like(x)
-        call("df_add", _ptr(x), _ptr(x0), _ptr(y), x.numel(), _stream())
+            bits.append(sb)
+        y = xs[n]
+        if skip:
+            if y.shape != x0.shape:
+                raise ValueError("gen_block: residual add needs Cout == Cin of the block")
+            y = torch.empty_like(y)
+            call("df_add", _ptr(xs[n]), _ptr(x0), _ptr(y), y.numel(), _stream())
         if ACTIVATION_FETCH is not None:
             ACTIVATION_FETCH.extend(xs[1:])
-        ctx.save_for_backward(*(xs + [wb[2 * i] for i in range(n)]))
-        ctx.geom = (n, dims, kz, taps, float(leak))
+        ctx.save_for_backward(*(xs + list(wb[0::2])))
+        ctx.geom = (n, dims, kz, taps, float(leak), skip)
         ctx.bits = bits
-        ctx.bptrs = [wb[2 * i + 1].data_ptr() for i in range(n)]
+        ctx.bptrs = [b.data_ptr() for b in wb[1::2]]
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        n, dims, kz, taps, leak = ctx.geom
+        n, dims, kz, taps, leak, skip = ctx.geom
         saved = ctx.saved_tensors
         xs, ws = saved[:n + 1], saved[n + 1:]
-        B, D, H, W = dims
         dy = _prep(dy, "grad")
         dp = torch.empty_like(dy)
         call("df_lrelu_bwd", _ptr(dy), _ptr(xs[n]), _ptr(dp), leak, dy.numel(), _stream())
@@ -576,199 +640,134 @@ class _GenBlock(torch.autograd.Function):
         lane = _WgradLane(dims, dy, taps)
         for i in range(n, 0, -1):
             w = ws[i - 1]
-            cin, cout = w.shape[-2], w.shape[-1]
-            gw, rw = _grad_out(w.data_ptr(), w.shape, dy.device)
-            gb, rb = _grad_out(ctx.bptrs[i - 1], (cout,), dy.device)
-            lane.run(lambda: _wgrad(xs[i - 1], dp, gw, gb, B, D, H, W, cin, cout, kz, _sfx(cin, cout)), dp, gw, gb)
-            grads[2 * (i - 1)] = rw; grads[2 * (i - 1) + 1] = rb
-            wpd = _pack(w, taps, cin, cout, 1, dims)
-            if i > 1:      # dgrad, times the lrelu slope of the layer below: directly the next dp
-                mb = ctx.bits[i - 2]      # sign bits of conv i-1's output, if its forward emitted them
-                dp = _conv_raw(dp, wpd, None, None, None if mb is not None else xs[i - 1], dims, cout, cin, kz, DF_CONV_MASK, leak,
-                               mask_bits=mb).view(xs[i - 1].shape)
-            elif ctx.needs_input_grad[0]:   # dgrad of the first layer + the skip gradient
-                dx0 = _conv_raw(dp, wpd, None, dy, None, dims, cout, cin, kz, DF_CONV_RESIDUAL, 0.0).view(xs[0].shape)
-        lane.join()
-        return (dx0, None) + tuple(grads)
-
-
-class _ConvChain(torch.autograd.Function):
-    """n x [conv k3 s1 + bias + lrelu] in a row as ONE autograd node -- the per-level conv stack of the encoder (model.py:131-136 / 167-172;
-    the first conv may change the channel count).  Same forward kernels as the layer-by-layer path; the reverse chain applies the lrelu
-    slope of the layer below in each dgrad's epilogue (DF_CONV_MASK, sign bits where the 3-D Winograd forward emits them) exactly as
-    _GenBlock does, so only the LAST layer's element-wise lrelu-backward pass remains (its gradient arrives from the concat)."""
-
-    @staticmethod
-    def forward(ctx, x0, leak, *wb):
-        x0 = _prep(x0, "x")
-        n = len(wb) // 2
-        nd = x0.dim() - 2
-        kz = 3 if nd == 3 else 1
-        taps = 27 if nd == 3 else 9
-        dims = (x0.shape[0], x0.shape[1] if nd == 3 else 1, x0.shape[-3], x0.shape[-2])
-        xs = [x0]
-        bits = []
-        x = x0
-        for i in range(n):
-            w = _prep(wb[2 * i], "weights"); b = _prep(wb[2 * i + 1], "biases")
-            cin, cout = w.shape[-2], w.shape[-1]
-            if tuple(w.shape[:-2]) != (3,) * nd or x.shape[-1] != cin:
-                raise ValueError("conv_chain: weights %s do not match input %s" % (tuple(w.shape), tuple(x.shape)))
-            wp = _pack(w, taps, cin, cout, 0, dims)
-            bk = _bits_kind(cin, cout, dims, kz) if i < n - 1 else 0
-            sb = _new_bits(dims, cout, x0, bk) if bk else None
-            bits.append(sb)
-            x = _conv_raw(x, wp, b, None, None, dims, cin, cout, kz, DF_CONV_BIAS | DF_CONV_LRELU, leak, sign_bits=sb).view(
-                x0.shape[:-1] + (cout,))
-            xs.append(x)
-        if ACTIVATION_FETCH is not None:
-            ACTIVATION_FETCH.extend(xs[1:])
-        ctx.save_for_backward(*(xs + [wb[2 * i] for i in range(n)]))
-        ctx.geom = (n, dims, kz, taps, float(leak))
-        ctx.bits = bits
-        ctx.bptrs = [wb[2 * i + 1].data_ptr() for i in range(n)]
-        return x
-
-    @staticmethod
-    def backward(ctx, dy):
-        n, dims, kz, taps, leak = ctx.geom
-        saved = ctx.saved_tensors
-        xs, ws = saved[:n + 1], saved[n + 1:]
-        B, D, H, W = dims
-        dy = _prep(dy, "grad")
-        dp = torch.empty_like(dy)
-        call("df_lrelu_bwd", _ptr(dy), _ptr(xs[n]), _ptr(dp), leak, dy.numel(), _stream())
-        grads = [None] * (2 * n)
-        dx0 = None
-        lane = _WgradLane(dims, dy, taps)
-        for i in range(n, 0, -1):
-            w = ws[i - 1]
-            cin, cout = w.shape[-2], w.shape[-1]
-            gw, rw = _grad_out(w.data_ptr(), w.shape, dy.device)
-            gb, rb = _grad_out(ctx.bptrs[i - 1], (cout,), dy.device)
-            lane.run(lambda: _wgrad(xs[i - 1], dp, gw, gb, B, D, H, W, cin, cout, kz, _sfx(cin, cout)), dp, gw, gb)
-            grads[2 * (i - 1)] = rw; grads[2 * (i - 1) + 1] = rb
-            if i > 1 or ctx.needs_input_grad[0]:
+            grads[2 * i - 2], grads[2 * i - 1] = _layer_wgrad(lane, xs[i - 1], dp, w, ctx.bptrs[i - 1], dims, kz)
+            if i > 1:
+                dp = _layer_dgrad_masked(dp, w, dims, kz, taps, leak, xs[i - 1], ctx.bits[i - 2])
+            elif ctx.needs_input_grad[0]:   # dgrad of the first layer, + the skip gradient in its epilogue
+                cin, cout = w.shape[-2], w.shape[-1]
                 wpd = _pack(w, taps, cin, cout, 1, dims)
-                if i > 1:      # dgrad, times the lrelu slope of the layer below: directly the next dp
-                    mb = ctx.bits[i - 2]
-                    dp = _conv_raw(dp, wpd, None, None, None if mb is not None else xs[i - 1], dims, cout, cin, kz, DF_CONV_MASK, leak,
-                                   mask_bits=mb).view(xs[i - 1].shape)
-                else:
-                    dx0 = _conv_raw(dp, wpd, None, None, None, dims, cout, cin, kz, 0, 0.0).view(xs[0].shape)
+                dx0 = _conv_raw(dp, wpd, None, dy if skip else None, None, dims, cout, cin, kz, DF_CONV_RESIDUAL if skip else 0, 0.0).view(xs[0].shape)
         lane.join()
-        return (dx0, None) + tuple(grads)
+        return (dx0, None, None) + tuple(grads)
+
+
+class _GenBlock(object):
+    """One generator block as a single autograd node: ``_GenBlock.apply(x, leak, w1, b1, ..., wn, bn)`` = `_ConvStack` with the skip."""
+
+    @staticmethod
+    def apply(x, leak, *wb):
+        return _ConvStack.apply(x, leak, True, *wb)
+
+
+class _ConvChain(object):
+    """The encoder's per-level conv stack as a single autograd node: `_ConvStack` without the skip."""
+
+    @staticmethod
+    def apply(x, leak, *wb):
+        return _ConvStack.apply(x, leak, False, *wb)
+
+
+_UP_FORMS = {"wino": "winograd-27pt", "wino2d": "winograd2d-9pt"}      # DISPATCH_COUNTS labels of the up-sampling-aware Winograd forms, by kernel kind
+
+
+def _fused_tail(k, x, w, b, xc, fdims, taps, leak):
+    """The last conv of an up-sampling block on kernel `k` with the block-end skip add fused into its epilogue: ``y = lrelu(conv(x)) +
+    upscale(xc)`` -> ``(activation, y, tail_bits)``, or None where `k` has no such epilogue (the caller then runs conv and add apart).
+    With sign-bit masks on and nobody fetching activations, of the conv's own activation only the sign words are kept (``tail_bits``: all
+    the backward tail needs of it) and the activation is None; otherwise (3-D only) the fp32 activation is a second output."""
+    is3d = k.kind in ("wino43", "wino")
+    words = bool(k.bits) and ACTIVATION_FETCH is None
+    if not (is3d or words):
+        return None
+    cin, cout = w.shape[-2], w.shape[-1]
+    B, D, H, W = fdims
+    wp = _pack(w, taps, cin, cout, 0, fdims)
+    _count("conv", k.form + ("+addup+signwords" if words else "+addup"), fdims, cin, cout)
+    tail_bits = _new_bits(fdims, cout, xc, k.bits) if words else None
+    act = None if words else torch.empty_like(x)
+    y = torch.empty_like(x)
+    if k.kind == "wino43":
+        call("df_wino43_conv", _ptr(x), _ptr(wp), _ptr(b), _ptr(xc), None, None, _ptr(act), _ptr(y), _ptr(tail_bits), B, D, H, W, cin, cout,
+             DF_CONV_BIAS | DF_CONV_LRELU | _lib.DF_CONV_ADDUP, float(leak), _stream())
+    elif k.kind == "wino" and words:
+        call("df_wino_conv_fwd_addup_bits", _ptr(x), _ptr(wp), _ptr(b), _ptr(xc), _ptr(y), _ptr(tail_bits), B, D, H, W, cin, cout, float(leak), _stream())
+    elif k.kind == "wino":
+        call("df_wino_conv_fwd_addup", _ptr(x), _ptr(wp), _ptr(b), _ptr(xc), _ptr(act), _ptr(y), B, D, H, W, cin, cout, float(leak), _stream())
+    else:
+        call("df_wino2d43_conv_addup_bits", _ptr(x), _ptr(wp), _ptr(b), _ptr(xc), _ptr(y), _ptr(tail_bits), B, H, W, cin, cout, float(leak), _stream())
+    if words and is3d and SIGN_BITS_FETCH is not None:
+        SIGN_BITS_FETCH.append((tail_bits, fdims, cout))
+    return act, y, tail_bits
 
 
 class _UpGenBlock(torch.autograd.Function):
     """``x0 = upscale(xc, 2)`` followed by one generator block (model.py:36-40 / 78-82) as a single autograd node that
-    never materialises ``x0``: the block's first conv runs as parity-class 2x2(x2)-tap convs on the coarse input
-    (``df_upconv_*``: 3.4x fewer FLOPs forward, dgrad and 2.25x fewer in wgrad), the block-end residual add reads the
-    coarse tensor (``df_add_up2x``) and the skip gradient is the 2x2(x2) sum-pool of dy (``df_upsample2x_bwd``)."""
+    never materialises ``x0``: the block's first conv runs on the coarse input -- as the up-sampling-aware form of the fine grid's
+    Winograd kernel (27 of the 64 / 9 of the 16 products: F(2,3)^3 / F(2,3)^2 only) or as parity-class 2x2(x2)-tap convs
+    (``df_upconv_*``: 3.4x fewer FLOPs forward, dgrad and 2.25x fewer in wgrad) --, the block-end residual add reads the coarse tensor
+    (the last conv's epilogue, or ``df_add_up2x``) and the skip gradient is the 2x2(x2) sum-pool of dy."""
 
     @staticmethod
     def forward(ctx, xc, leak, *wb):
         xc = _prep(xc, "x")
         n = len(wb) // 2
-        nd = xc.dim() - 2
-        is3d = nd == 3
-        kz = 3 if is3d else 1
-        taps = 27 if is3d else 9
-        cdims = (xc.shape[0], xc.shape[1] if is3d else 1, xc.shape[-3], xc.shape[-2])
-        fdims = (cdims[0], 2 * cdims[1] if is3d else 1, 2 * cdims[2], 2 * cdims[3])
+        ws = [_prep(w, "weights") for w in wb[0::2]]
+        bs = [_prep(b, "biases") for b in wb[1::2]]
         C = int(xc.shape[-1])
+        kz, taps, cdims = _geom(xc, ws, "up_gen_block")
+        for w in ws:
+            if w.shape[-1] != C:
+                raise ValueError("up_gen_block: weights %s do not match %d channels" % (tuple(w.shape), C))
+        is3d = kz == 3
+        fdims = (cdims[0], 2 * cdims[1] if is3d else 1, 2 * cdims[2], 2 * cdims[3])
         fshape = (xc.shape[0],) + tuple(2 * int(d) for d in xc.shape[1:-1]) + (C,)
+        Bc, Dc, Hc, Wc = cdims
+        fam = "f222" if is3d else "f22"       # the up-sampling-aware forms exist in these families only
+        first = _conv_kernel(C, C, fdims, kz, 0, family=fam)
+        last = _conv_kernel(C, C, fdims, kz, 0)
         xs = []
         bits = []
         y = None
         tail_bits = None
         for i in range(n):
-            w = _prep(wb[2 * i], "weights"); b = _prep(wb[2 * i + 1], "biases")
-            cin, cout = w.shape[-2], w.shape[-1]
-            if tuple(w.shape[:-2]) != (3,) * nd or cin != C or cout != C:
-                raise ValueError("up_gen_block: weights %s do not match %d channels" % (tuple(w.shape), C))
             # (2-D: the block's first conv runs the 9-point F(2,3)^2 form, which has no sign words -- the dgrad above it reads its fp32 activation)
-            bk = _bits_kind(cin, cout, fdims, kz) if (i < n - 1 and (is3d or i > 0)) else 0
-            sb = _new_bits(fdims, cout, xc, bk) if bk else None
-            bits.append(sb)
-            if DISPATCH_COUNTS is not None and i == 0:
-                _count("upconv", "winograd-27pt" if (is3d and _use_wino(cin, cout, fdims, kz) == 3) else
-                       "winograd2d-9pt" if (not is3d and _use_wino(cin, cout, fdims, kz) == 2) else "parity-class" + _sfx(cin, cout), fdims, cin, cout)
-            if i == 0 and is3d and _use_wino(cin, cout, fdims, kz) == 3:
-                # 27-point up-sampling-aware Winograd form (conv_wino.hip, UP variant): the F(2,3)^3 operand of a plain conv
-                wp = _pack(w, taps, cin, cout, 0, fdims, family="f222")
+            want_bits = i < n - 1 and (is3d or i > 0)
+            if i == 0:
+                sb = _new_bits(fdims, C, xc, first.bits) if (want_bits and first.bits) else None
+                _count("upconv", _UP_FORMS.get(first.kind, "parity-class" + first.sfx), fdims, C, C)
                 x = torch.empty(fshape, dtype=torch.float32, device=xc.device)
-                if sb is not None:
-                    call("df_wino_upconv_fwd_bits", _ptr(xc), _ptr(wp), _ptr(b), _ptr(x), _ptr(sb), cdims[0], cdims[1], cdims[2], cdims[3],
-                         cin, cout, float(leak), _stream())
-                else:
-                    call("df_wino_upconv_fwd", _ptr(xc), _ptr(wp), _ptr(b), _ptr(x), cdims[0], cdims[1], cdims[2], cdims[3], cin, cout,
-                         DF_CONV_BIAS | DF_CONV_LRELU, float(leak), _stream())
-            elif i == 0 and not is3d and _use_wino(cin, cout, fdims, kz) == 2:
-                # 2-D twin: 9 of the 16 Winograd products (conv_wino2d.hip, UP variant)
-                wp = _pack(w, taps, cin, cout, 0, fdims, family="f22")
-                x = torch.empty(fshape, dtype=torch.float32, device=xc.device)
-                call("df_wino2d_upconv_fwd", _ptr(xc), _ptr(wp), _ptr(b), _ptr(x), cdims[0], cdims[2], cdims[3], cin, cout,
-                     DF_CONV_BIAS | DF_CONV_LRELU, float(leak), _stream())
-            elif i == 0:
-                sfx = _sfx(cin, cout)
-                wp = torch.empty(query("df_upconv_packed_elems" + sfx, cin, cout, kz, 0), dtype=torch.float32,
-                                 device=xc.device)
-                call("df_upconv_pack_weights" + sfx, _ptr(w), _ptr(wp), cin, cout, kz, 0, _stream())
-                x = torch.empty(fshape, dtype=torch.float32, device=xc.device)
-                call("df_upconv_fwd" + sfx, _ptr(xc), _ptr(wp), _ptr(b), _ptr(x), cdims[0], cdims[1], cdims[2], cdims[3], cin, cout,
-                     kz, DF_CONV_BIAS | DF_CONV_LRELU, float(leak), _stream())
-            else:
-                wp = _pack(w, taps, cin, cout, 0, fdims)
-                if i == n - 1 and is3d and _use_wino(cin, cout, fdims, kz) == 3 and SIGN_BIT_MASKS and ACTIVATION_FETCH is None:
-                    # block-end skip add fused into the last conv's epilogue, and of the conv's own activation only the sign bits are
-                    # kept (all the backward tail needs of it): y = lrelu(conv(x)) + upscale(xc), tail_bits = (lrelu(conv(x)) > 0)
-                    f224 = WINO3D_FAMILY == "f224"
-                    _count("conv", "winograd-%s+addup+signwords" % ("f2x2x4" if f224 else "f2x2x2"), fdims, cin, cout)
-                    tail_bits = _new_bits(fdims, cout, xc)
-                    y = torch.empty(fshape, dtype=torch.float32, device=xc.device)
-                    if f224:
-                        call("df_wino43_conv", _ptr(x), _ptr(wp), _ptr(b), _ptr(xc), None, None, None, _ptr(y), _ptr(tail_bits), fdims[0], fdims[1],
-                             fdims[2], fdims[3], cin, cout, DF_CONV_BIAS | DF_CONV_LRELU | _lib.DF_CONV_ADDUP, float(leak), _stream())
-                    else:
-                        call("df_wino_conv_fwd_addup_bits", _ptr(x), _ptr(wp), _ptr(b), _ptr(xc), _ptr(y), _ptr(tail_bits), fdims[0], fdims[1],
-                             fdims[2], fdims[3], cin, cout, float(leak), _stream())
-                    if SIGN_BITS_FETCH is not None:
-                        SIGN_BITS_FETCH.append((tail_bits, fdims, cout))
-                    x = None
-                elif i == n - 1 and is3d and _use_wino(cin, cout, fdims, kz) == 3:
-                    # (fp32 masks: the activation is a second output)
-                    f224 = WINO3D_FAMILY == "f224"
-                    _count("conv", "winograd-%s+addup" % ("f2x2x4" if f224 else "f2x2x2"), fdims, cin, cout)
-                    x_in, x = x, torch.empty(fshape, dtype=torch.float32, device=xc.device)
-                    y = torch.empty(fshape, dtype=torch.float32, device=xc.device)
-                    if f224:
-                        call("df_wino43_conv", _ptr(x_in), _ptr(wp), _ptr(b), _ptr(xc), None, None, _ptr(x), _ptr(y), None, fdims[0], fdims[1],
-                             fdims[2], fdims[3], cin, cout, DF_CONV_BIAS | DF_CONV_LRELU | _lib.DF_CONV_ADDUP, float(leak), _stream())
-                    else:
-                        call("df_wino_conv_fwd_addup", _ptr(x_in), _ptr(wp), _ptr(b), _ptr(xc), _ptr(x), _ptr(y), fdims[0], fdims[1],
-                             fdims[2], fdims[3], cin, cout, float(leak), _stream())
-                elif i == n - 1 and not is3d and _bits_kind(cin, cout, fdims, kz) == 2 and ACTIVATION_FETCH is None:
-                    # the 2-D twin of the fused block tail: y = lrelu(conv(x)) + upscale(xc) from the conv's epilogue, only the sign words of its activation kept
-                    _count("conv", "winograd-f2x4+addup+signwords", fdims, cin, cout)
-                    tail_bits = _new_bits(fdims, cout, xc, 2)
-                    y = torch.empty(fshape, dtype=torch.float32, device=xc.device)
-                    call("df_wino2d43_conv_addup_bits", _ptr(x), _ptr(wp), _ptr(b), _ptr(xc), _ptr(y), _ptr(tail_bits), fdims[0], fdims[2], fdims[3], cin, cout,
+                if first.kind == "direct":
+                    wp = _upconv_pack(ws[0], C, C, kz, 0, first.sfx)
+                    call("df_upconv_fwd" + first.sfx, _ptr(xc), _ptr(wp), _ptr(bs[0]), _ptr(x), Bc, Dc, Hc, Wc, C, C, kz, DF_CONV_BIAS | DF_CONV_LRELU,
                          float(leak), _stream())
-                    x = None
                 else:
-                    x = _conv_raw(x, wp, b, None, None, fdims, cin, cout, kz, DF_CONV_BIAS | DF_CONV_LRELU, leak, sign_bits=sb).view(fshape)
+                    wp = _pack(ws[0], taps, C, C, 0, fdims, family=fam)      # the operand of a plain conv of that family
+                    if first.kind == "wino2d":      # 9 of the 16 Winograd products (conv_wino2d.hip, UP variant)
+                        call("df_wino2d_upconv_fwd", _ptr(xc), _ptr(wp), _ptr(bs[0]), _ptr(x), Bc, Hc, Wc, C, C, DF_CONV_BIAS | DF_CONV_LRELU, float(leak),
+                             _stream())
+                    elif sb is not None:            # 27-point form (conv_wino.hip, UP variant)
+                        call("df_wino_upconv_fwd_bits", _ptr(xc), _ptr(wp), _ptr(bs[0]), _ptr(x), _ptr(sb), Bc, Dc, Hc, Wc, C, C, float(leak), _stream())
+                    else:
+                        call("df_wino_upconv_fwd", _ptr(xc), _ptr(wp), _ptr(bs[0]), _ptr(x), Bc, Dc, Hc, Wc, C, C, DF_CONV_BIAS | DF_CONV_LRELU,
+                             float(leak), _stream())
+            else:
+                tail = _fused_tail(last, x, ws[i], bs[i], xc, fdims, taps, leak) if i == n - 1 else None
+                if tail is not None:
+                    (x, y, tail_bits), sb = tail, None
+                else:
+                    x, sb = _layer_fwd(x, ws[i], bs[i], fdims, kz, taps, leak, want_bits)
+            bits.append(sb)
             xs.append(x)
         if y is None:
             y = torch.empty_like(x)
-            call("df_add_up2x", _ptr(x), _ptr(xc), _ptr(y), cdims[0], cdims[1], cdims[2], cdims[3], C, int(is3d), _stream())
+            call("df_add_up2x", _ptr(x), _ptr(xc), _ptr(y), Bc, Dc, Hc, Wc, C, int(is3d), _stream())
         if ACTIVATION_FETCH is not None:
             ACTIVATION_FETCH.extend(xs)
-        ctx.save_for_backward(*([xc] + xs + [wb[2 * i] for i in range(n)]))
+        ctx.save_for_backward(*([xc] + xs + list(wb[0::2])))
         ctx.geom = (n, cdims, fdims, kz, taps, float(leak), C, is3d)
         ctx.bits = bits
         ctx.tail_bits = tail_bits
-        ctx.bptrs = [wb[2 * i + 1].data_ptr() for i in range(n)]
+        ctx.bptrs = [b.data_ptr() for b in wb[1::2]]
         return y
 
     @staticmethod
@@ -776,7 +775,7 @@ class _UpGenBlock(torch.autograd.Function):
         n, cdims, fdims, kz, taps, leak, C, is3d = ctx.geom
         saved = ctx.saved_tensors
         xc, xs, ws = saved[0], saved[1:n + 1], saved[n + 1:]
-        B, D, H, W = fdims
+        Bc, Dc, Hc, Wc = cdims
         dy = _prep(dy, "grad")
         dp = torch.empty_like(dy)
         dxc = None
@@ -785,88 +784,70 @@ class _UpGenBlock(torch.autograd.Function):
             # level instead of 12.9; the pooled skip gradient comes with it (dropped below if xc needs no gradient)
             dxc = torch.empty_like(xc)
             if is3d:
-                call("df_lrelu_bits_bwd_pool2x", _ptr(dy), _ptr(ctx.tail_bits), _ptr(dp), _ptr(dxc), leak, cdims[0], cdims[1], cdims[2], cdims[3],
-                     C, _stream())
+                call("df_lrelu_bits_bwd_pool2x", _ptr(dy), _ptr(ctx.tail_bits), _ptr(dp), _ptr(dxc), leak, Bc, Dc, Hc, Wc, C, _stream())
             else:
-                call("df_lrelu_words2d_bwd_pool2x", _ptr(dy), _ptr(ctx.tail_bits), _ptr(dp), _ptr(dxc), leak, cdims[0], cdims[2], cdims[3], C, _stream())
+                call("df_lrelu_words2d_bwd_pool2x", _ptr(dy), _ptr(ctx.tail_bits), _ptr(dp), _ptr(dxc), leak, Bc, Hc, Wc, C, _stream())
         elif ctx.needs_input_grad[0]:
             # both consumers of dy in one pass: the masked gradient entering the last conv and the skip path's 2x2(x2) sum-pool
             dxc = torch.empty_like(xc)
-            call("df_lrelu_bwd_pool2x", _ptr(dy), _ptr(xs[n - 1]), _ptr(dp), _ptr(dxc), leak, cdims[0], cdims[1], cdims[2], cdims[3], C,
-                 int(is3d), _stream())
+            call("df_lrelu_bwd_pool2x", _ptr(dy), _ptr(xs[n - 1]), _ptr(dp), _ptr(dxc), leak, Bc, Dc, Hc, Wc, C, int(is3d), _stream())
         else:
             call("df_lrelu_bwd", _ptr(dy), _ptr(xs[n - 1]), _ptr(dp), leak, dy.numel(), _stream())
         grads = [None] * (2 * n)
         lane = _WgradLane(fdims, dy, taps)
-        for i in range(n, 0, -1):
-            w = ws[i - 1]
-            gw, rw = _grad_out(w.data_ptr(), w.shape, dy.device)
-            gb, rb = _grad_out(ctx.bptrs[i - 1], (C,), dy.device)
-            if i > 1:
-                lane.run(lambda: _wgrad(xs[i - 2], dp, gw, gb, B, D, H, W, C, C, kz, _sfx(C, C)), dp, gw, gb)
-                wpd = _pack(w, taps, C, C, 1, fdims)
-                mb = ctx.bits[i - 2]      # sign bits of conv i-1's output (xs[i-2]), if its forward emitted them
-                dp = _conv_raw(dp, wpd, None, None, None if mb is not None else xs[i - 2], fdims, C, C, kz, DF_CONV_MASK, leak,
-                               mask_bits=mb).view(dy.shape)
-            else:
-                nbytes = query("df_upconv_wgrad_workspace_bytes", cdims[0], cdims[1], cdims[2], cdims[3], C, C, kz)
-                wsb = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dy.device)
+        for i in range(n, 1, -1):      # sign bits of conv i-1's output (xs[i-2]), if its forward emitted them
+            grads[2 * i - 2], grads[2 * i - 1] = _layer_wgrad(lane, xs[i - 2], dp, ws[i - 1], ctx.bptrs[i - 1], fdims, kz)
+            dp = _layer_dgrad_masked(dp, ws[i - 1], fdims, kz, taps, leak, xs[i - 2], ctx.bits[i - 2])
+        # the first conv, on the coarse input
+        w = ws[0]
+        sfx = _sfx(C, C)
+        gw, grads[0] = _grad_out(w.data_ptr(), w.shape, dy.device)
+        gb, grads[1] = _grad_out(ctx.bptrs[0], (C,), dy.device)
+        nbytes = query("df_upconv_wgrad_workspace_bytes", Bc, Dc, Hc, Wc, C, C, kz)
+        wsb = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dy.device)
 
-                def up_wgrad():
-                    if _sfx(C, C):
-                        call("df_upconv_wgrad" + _sfx(C, C), _ptr(xc), _ptr(dp), _ptr(gw), _ptr(gb), cdims[0], cdims[1], cdims[2],
-                             cdims[3], C, C, kz, _ptr(wsb), nbytes, _stream())
-                    else:
-                        if DISPATCH_COUNTS is not None:
-                            f = query("df_upconv_wgrad_form", cdims[0], cdims[1], cdims[2], cdims[3], C, C, kz, int(WGRAD_ALGO))
-                            _count("upconv-wgrad", "winograd-xyz-27pt" if f == 3 else "parity-class", fdims, C, C)
-                        call("df_upconv_wgrad_algo", _ptr(xc), _ptr(dp), _ptr(gw), _ptr(gb), cdims[0], cdims[1], cdims[2],
-                             cdims[3], C, C, kz, _ptr(wsb), nbytes, int(WGRAD_ALGO), _stream())
-                lane.run(up_wgrad, dp, gw, gb, wsb)
-                if ctx.needs_input_grad[0]:
-                    if DISPATCH_COUNTS is not None:
-                        _count("upconv-dgrad", "winograd-27pt-pooled" if (is3d and _use_wino(C, C, fdims, kz) == 3) else
-                               "winograd2d-9pt-pooled" if (not is3d and _use_wino(C, C, fdims, kz) == 2) else "parity-class" + _sfx(C, C), fdims, C, C)
-                    # dxc holds the skip path's sum-pool of dy (df_lrelu_bwd_pool2x above); += the conv path per parity class
-                    if is3d and _use_wino(C, C, fdims, kz) == 3:
-                        # pooled-output Winograd form (conv_wino.hip, POOL variant): 27 of the 64 products, coarse stores
-                        wpd = _pack(w, taps, C, C, 1, fdims, family="f222")
-                        call("df_wino_upconv_dgrad", _ptr(dp), _ptr(wpd), _ptr(dxc), cdims[0], cdims[1], cdims[2], cdims[3], C, C,
-                             _stream())
-                    elif not is3d and _use_wino(C, C, fdims, kz) == 2:
-                        wpd = _pack(w, taps, C, C, 1, fdims, family="f22")
-                        call("df_wino2d_upconv_dgrad", _ptr(dp), _ptr(wpd), _ptr(dxc), cdims[0], cdims[2], cdims[3], C, C, _stream())
-                    else:
-                        sfx = _sfx(C, C)
-                        wpd = torch.empty(query("df_upconv_packed_elems" + sfx, C, C, kz, 1), dtype=torch.float32,
-                                          device=dy.device)
-                        call("df_upconv_pack_weights" + sfx, _ptr(w), _ptr(wpd), C, C, kz, 1, _stream())
-                        call("df_upconv_dgrad" + sfx, _ptr(dp), _ptr(wpd), _ptr(dxc), cdims[0], cdims[1], cdims[2], cdims[3], C, C,
-                             kz, _stream())
-            grads[2 * (i - 1)] = rw; grads[2 * (i - 1) + 1] = rb
+        def up_wgrad():
+            if sfx:
+                call("df_upconv_wgrad" + sfx, _ptr(xc), _ptr(dp), _ptr(gw), _ptr(gb), Bc, Dc, Hc, Wc, C, C, kz, _ptr(wsb), nbytes, _stream())
+            else:
+                if DISPATCH_COUNTS is not None:
+                    f = query("df_upconv_wgrad_form", Bc, Dc, Hc, Wc, C, C, kz, int(WGRAD_ALGO))
+                    _count("upconv-wgrad", "winograd-xyz-27pt" if f == 3 else "parity-class", fdims, C, C)
+                call("df_upconv_wgrad_algo", _ptr(xc), _ptr(dp), _ptr(gw), _ptr(gb), Bc, Dc, Hc, Wc, C, C, kz, _ptr(wsb), nbytes, int(WGRAD_ALGO),
+                     _stream())
+        lane.run(up_wgrad, dp, gw, gb, wsb)
+        if ctx.needs_input_grad[0]:
+            # dxc holds the skip path's sum-pool of dy (the prologue above); += the conv path
+            fam = "f222" if is3d else "f22"
+            first = _conv_kernel(C, C, fdims, kz, 1, family=fam)
+            _count("upconv-dgrad", _UP_FORMS[first.kind] + "-pooled" if first.kind in _UP_FORMS else "parity-class" + first.sfx, fdims, C, C)
+            if first.kind == "direct":      # per parity class
+                wpd = _upconv_pack(w, C, C, kz, 1, first.sfx)
+                call("df_upconv_dgrad" + first.sfx, _ptr(dp), _ptr(wpd), _ptr(dxc), Bc, Dc, Hc, Wc, C, C, kz, _stream())
+            else:
+                wpd = _pack(w, taps, C, C, 1, fdims, family=fam)
+                if first.kind == "wino":    # pooled-output Winograd form (conv_wino.hip, POOL variant): 27 of the 64 products, coarse stores
+                    call("df_wino_upconv_dgrad", _ptr(dp), _ptr(wpd), _ptr(dxc), Bc, Dc, Hc, Wc, C, C, _stream())
+                else:
+                    call("df_wino2d_upconv_dgrad", _ptr(dp), _ptr(wpd), _ptr(dxc), Bc, Hc, Wc, C, C, _stream())
         lane.join()
         return (dxc if ctx.needs_input_grad[0] else None, None) + tuple(grads)
 
 
 class _ConvSame3S2(torch.autograd.Function):
     """k=3, stride-2, TF-'SAME' conv on even extents (pad 0 before / 1 after): the encoder's
-    down-sampling layers (model.py:141-143, 177-179).  Forward is a dedicated MFMA kernel; the backward re-uses the
-    stride-1 dgrad / wgrad kernels on the zero-inserted gradient (out[2o+1] = g[o]), which reproduces the stride-2
-    adjoints exactly (at 4x / 8x the minimal FLOPs -- four layers of the auto-encoder only)."""
+    down-sampling layers (model.py:141-143, 177-179).  Forward is a dedicated MFMA kernel; the backward has native forms on the output
+    grid and, for the shapes those are not instantiated for, re-uses the stride-1 dgrad / wgrad kernels on the zero-inserted gradient
+    (out[2o+1] = g[o]), which reproduces the stride-2 adjoints exactly (at 4x / 8x the minimal FLOPs)."""
 
     @staticmethod
     def forward(ctx, x, w, b, leak):
         x = _prep(x, "x"); w = _prep(w, "weights"); b = _prep(b, "biases")
-        nd = x.dim() - 2
-        kz = 3 if nd == 3 else 1
-        taps = 27 if nd == 3 else 9
+        kz, taps, idims = _geom(x, [w], "conv")
         cin, cout = w.shape[-2], w.shape[-1]
-        if tuple(w.shape[:-2]) != (3,) * nd or x.shape[-1] != cin:
-            raise ValueError("conv: weights %s do not match input %s (k=3 only)" % (tuple(w.shape), tuple(x.shape)))
         if any(int(d) % 2 for d in x.shape[1:-1]):
             raise NotImplementedError("stride-2 conv: even spatial extents only (the encoder asserts them, model.py:125,161)")
-        idims = (x.shape[0], x.shape[1] if nd == 3 else 1, x.shape[-3], x.shape[-2])
-        odims = (idims[0], idims[1] // 2 if nd == 3 else 1, idims[2] // 2, idims[3] // 2)
+        odims = (idims[0], idims[1] // 2 if kz == 3 else 1, idims[2] // 2, idims[3] // 2)
         wp = _pack(w, taps, cin, cout, 0, fp32=True)       # df_conv_s2_fwd has no bf16x3 variant: always the fp32 operand
         flags = DF_CONV_BIAS | (DF_CONV_LRELU if leak is not None else 0)
         y = torch.empty(odims + (cout,), dtype=torch.float32, device=x.device)
@@ -886,15 +867,14 @@ class _ConvSame3S2(torch.autograd.Function):
         x, w, y = ctx.saved_tensors
         idims, odims, cin, cout, kz, taps = ctx.geom
         B, D, H, W = idims
-        gy = _prep(gy, "grad")
-        if ctx.leak is not None:
-            dp = torch.empty_like(gy)
-            call("df_lrelu_bwd", _ptr(gy), _ptr(y), _ptr(dp), float(ctx.leak), gy.numel(), _stream())
-        else:
-            dp = gy
-        gw, rw = _grad_out(w.data_ptr(), w.shape, x.device)
-        gb, rb = _grad_out(ctx.bptr, (cout,), x.device)
-        up = None
+        dp, gw, rw, gb, rb = _conv_bwd_prologue(gy, y, ctx.leak, w, ctx.bptr)
+        up = []
+
+        def zero_inserted():      # out[2o+1] = g[o] on the input grid: built once, where it is first needed
+            if not up:
+                up.append(torch.empty((B, D, H, W, cout), dtype=torch.float32, device=x.device))
+                call("df_dilate2_odd", _ptr(dp), _ptr(up[0]), odims[0], odims[1], odims[2], odims[3], cout, int(kz == 3), _stream())
+            return up[0]
         nbytes = query("df_conv_s2_wgrad_workspace_bytes", odims[0], odims[1], odims[2], odims[3], cin, cout, kz)
         if nbytes > 0 and WGRAD_ALGO == 0:
             # native form on the output grid: x[2o + t] * g[o] (conv_wgrad.hip::wgrad_s2_kernel) -- no zero-inserted gradient
@@ -903,18 +883,15 @@ class _ConvSame3S2(torch.autograd.Function):
             call("df_conv_s2_wgrad", _ptr(x), _ptr(dp), _ptr(gw), _ptr(gb), odims[0], odims[1], odims[2], odims[3], cin, cout, kz, _ptr(ws),
                  nbytes, _stream())
         else:
-            # shapes the native kernel is not instantiated for: the stride-1 kernels on the zero-inserted gradient (out[2o+1] = g[o])
-            up = torch.empty((B, D, H, W, cout), dtype=torch.float32, device=x.device)
-            call("df_dilate2_odd", _ptr(dp), _ptr(up), odims[0], odims[1], odims[2], odims[3], cout, int(kz == 3), _stream())
-            _wgrad(x, up, gw, gb, B, D, H, W, cin, cout, kz)
+            # shapes the native kernel is not instantiated for: the stride-1 kernels on the zero-inserted gradient
+            _wgrad(x, zero_inserted(), gw, gb, B, D, H, W, cin, cout, kz)
         gx = None
         if ctx.needs_input_grad[0]:
             if cin > 4 and cout > 4:
                 # adjoint as 8 (4) parity-class 2x2(x2)-tap convs from the coarse gradient straight to the fine grid: the
                 # up-sampling-aware forward kernel with the stride-2 dgrad operand (pack mode 2) -- 3.4x fewer FLOPs than the
                 # stride-1 dgrad on the zero-inserted gradient, which stays as the thin-channel fallback below
-                wpd = torch.empty(query("df_upconv_packed_elems", cin, cout, kz, 2), dtype=torch.float32, device=x.device)
-                call("df_upconv_pack_weights", _ptr(w), _ptr(wpd), cin, cout, kz, 2, _stream())
+                wpd = _upconv_pack(w, cin, cout, kz, 2)
                 gx = torch.empty((B, D, H, W, cin), dtype=torch.float32, device=x.device)
                 # [r5] df_conv_s2_dgrad: the same parity classes, each on a kernel specialised on its LIVE taps (27 of the 64 the generic
                 # 2x2x2-tap parity-class kernel df_upconv_fwd multiplies -- half of the mode-2 operand is structural zeros)
@@ -924,12 +901,11 @@ class _ConvSame3S2(torch.autograd.Function):
                 call("df_conv_s2_dgrad", _ptr(dp), _ptr(wpd), _ptr(gx), odims[0], odims[1], odims[2], odims[3], cin, cout, kz, _stream())
                 gx = gx.view(x.shape)
             else:
-                if up is None:
-                    up = torch.empty((B, D, H, W, cout), dtype=torch.float32, device=x.device)
-                    call("df_dilate2_odd", _ptr(dp), _ptr(up), odims[0], odims[1], odims[2], odims[3], cout, int(kz == 3), _stream())
+                g = zero_inserted()
                 wpd = _pack(w, taps, cin, cout, 1, idims)
-                gx = _conv_raw(up, wpd, None, None, None, idims, cout, cin, kz, 0, 0.0).view(x.shape)
+                gx = _conv_raw(g, wpd, None, None, None, idims, cout, cin, kz, 0, 0.0).view(x.shape)
         return gx, rw, rb, None
+
 
 
 class _Concat2(torch.autograd.Function):
@@ -1362,7 +1338,7 @@ _OPTION_CHOICES = {"conv_precision": ("fp32", "bf16x3"), "conv_algo": ("auto", "
 _OPTION_LOCK = _threading.RLock()
 
 
-@_contextlib.contextmanager
+@contextlib.contextmanager
 def options(**kw):
     """``with ops.options(conv_precision="bf16x3", conv_algo="direct", wgrad_algo=1, activation_fetch=[]): ...``
     Keys: conv_precision, conv_algo, wino3d_family ("f224" | "f222"), wino2d_family ("auto" | "f24" | "f22"), wgrad_algo, thin_valu_only, sign_bit_masks, fused_blocks, dispatch_counts (a dict to count into),
@@ -1385,35 +1361,29 @@ def options(**kw):
                 g[_OPTION_ATTRS[k]] = v
 
 
+def _stack_variables(names, nd, cin, filters, device):
+    """The slim variables ``names`` of a row of k=3 convs cin -> filters -> ... -> filters: [w1, b1, w2, b2, ...]."""
+    wb = []
+    for name in names:
+        wb.append(get_variable(name + "/weights", (3,) * nd + (int(cin), int(filters)), "xavier", device))
+        wb.append(get_variable(name + "/biases", (int(filters),), "zeros", device))
+        cin = filters
+    return wb
+
+
 def gen_block(x, filters, names, nd, leak=0.2):
     """``num_conv`` x conv(k=3,s=1,act=lrelu) + ``x += x0`` (model.py:24-40 / 66-82) with slim variables ``names``."""
-    wb = []
-    cin = int(x.shape[-1])
-    for name in names:
-        wb.append(get_variable(name + "/weights", (3,) * nd + (cin, int(filters)), "xavier", x.device))
-        wb.append(get_variable(name + "/biases", (int(filters),), "zeros", x.device))
-        cin = int(filters)
-    return _GenBlock.apply(x, leak, *wb)
+    return _GenBlock.apply(x, leak, *_stack_variables(names, nd, x.shape[-1], filters, x.device))
 
 
 def conv_chain(x, filters, names, nd, leak=0.2):
     """``len(names)`` x conv(k=3,s=1,act=lrelu) (the encoder's per-level stack, model.py:131-136 / 167-172) as one autograd node."""
-    wb = []
-    cin = int(x.shape[-1])
-    for name in names:
-        wb.append(get_variable(name + "/weights", (3,) * nd + (cin, int(filters)), "xavier", x.device))
-        wb.append(get_variable(name + "/biases", (int(filters),), "zeros", x.device))
-        cin = int(filters)
-    return _ConvChain.apply(x, leak, *wb)
+    return _ConvChain.apply(x, leak, *_stack_variables(names, nd, x.shape[-1], filters, x.device))
 
 
 def up_gen_block(xc, filters, names, nd, leak=0.2):
     """``upscale(xc, 2)`` + one generator block on the up-sampled tensor (model.py:36-40 / 78-82), fused."""
-    wb = []
-    for name in names:
-        wb.append(get_variable(name + "/weights", (3,) * nd + (int(filters), int(filters)), "xavier", xc.device))
-        wb.append(get_variable(name + "/biases", (int(filters),), "zeros", xc.device))
-    return _UpGenBlock.apply(xc, leak, *wb)
+    return _UpGenBlock.apply(xc, leak, *_stack_variables(names, nd, filters, filters, xc.device))
 
 
 def nchw_to_nhwc(x):
