@@ -43,6 +43,26 @@ __device__ __forceinline__ int xcd_tile(int bid, int ntiles) {
   return (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + idx;
 }
 
+// Grid of the persistent 3-D Winograd kernels (conv_wino.hip: WinoArgs, conv_wino43.hip: W43Args): one workgroup per CU (a workgroup owns a
+// CU's whole register file and most of its LDS), fewer when there are fewer (tile block, cout slice) items.  Sets a.spx = cout slices per XCD.
+template <class Args>
+inline int64_t wino_grid(Args& a, int64_t ntb) {
+  int64_t grid = df::kCUs;
+  a.spx = 1;
+  if (8 % a.ncs == 0) {      // the slice count divides the 8 XCDs: an XCD only ever sees spx slices (their weights stay L2-resident)
+    a.spx = a.ncs % 2 == 0 ? 2 : 1;
+    const int xpg = a.ncs / a.spx, ngroups = 8 / xpg;
+    const int64_t need = df::ceil_div(ntb, ngroups) * a.spx * 8;      // workers that get at least one tile block
+    if (need < grid) grid = need;
+    if ((grid >> 3) % a.spx) grid = ((grid >> 3) / a.spx + 1) * a.spx * 8;
+    if (grid > df::kCUs) grid = df::kCUs;
+  } else {
+    grid = (grid / a.ncs) * a.ncs;
+    if (ntb * a.ncs < grid) grid = ntb * a.ncs;
+  }
+  return grid;
+}
+
 // VALU kernels for the generator's last layer (conv_small.hip); return DF_OK or an error
 int launch_small_n(const ConvArgs& a, int kz, hipStream_t s);   // Cout <= 4  (128 -> 3 | 1)
 int launch_small_k(const ConvArgs& a, int kz, hipStream_t s);   // Cin  <= 4  (dgrad of the last layer; 3 -> F)

@@ -22,20 +22,19 @@
 //   * epilogue: inverse transform in y,x in registers, the four xi_z partial planes are combined through the idle LDS
 //     buffer, then bias / lrelu / residual / lrelu-mask as in conv.hip.  The dgrad is the same kernel on mode-1 weights.
 //
-// Compile-time switches of wino3d_kernel.  The release library instantiates DBG = 0, PREC = 0, XS = 0 only (FL = the epilogue, MODE = 0 plain |
-// 3 up-sampling-aware forward with the coarse halo block staged (round 5; MODE 1 = its round-2 form staging the fine positions, tuning library
-// only) | 2 pooled adjoint); everything else exists in the -DDF_TUNING library for tools/r05_breakdown_probe.py, r05_upc_check.py and
-// tools/archive/wino_diag.py, wino_probe.py, wino_xblk_probe.py:
-//   DBG bits (diagnosis: results wrong by construction unless noted)   1 no input transform | 2 no raw LDS reads | 4 no staging | 8 no weight loads |
-//     16 per-phase cycle counters (correct results) | 64 staging loads kept alive, no LDS writes | 128 staged zeros (LDS writes only) |
-//     256 staging loads read an always-cached address | 384 ... confined to a 1 MB L2-resident window | 512 no output stores |
-//     262144 / 524288 weight loads of the z-row-1 waves / of all waves through a zero-length descriptor |
-//     1048576 / 2097152 (correct results) staging loads one per MFMA row during k-step 1 / 0 instead of one burst |
-//     4194304 staging loads fully coalesced (1 KiB contiguous per wave instruction), still L1-missing
-//   XS bits (round-4 probe, correct results unless noted): 1 LDS-DMA staging from the x-blocked copy | 2 waves 4-7 issue | 4 in front of k-step 0's
-//     MFMAs | 8 unrolled issue | 16 at the start of k-step 0 | 32 two weight register sets | 64 "weights" from LDS (timing only) | 128 three buffers
-//   PREC 1: bf16x3 in the Winograd domain (round 3).   The switches of rounds 1-3 whose experiments were negative (cache policies, chunk-pair
-//   permutation, split staging, reload orders, full barriers, setprio) were removed in round 4; their numbers are in profiles/LAB_NOTES.md.
+// wino3d_kernel<FL, MODE>: FL = the epilogue (compile-time flags, -1 = run-time a.flags), MODE = 0 plain | 2 pooled adjoint | 3 up-sampling-aware
+// forward with the coarse halo block staged.  The library instantiates the 12 pairs listed in wino_launch below, nothing else.
+//
+// Until commit 2f63d5b this kernel also carried the experiments of rounds 2-5 as template switches DBG / PREC / XS of a tuning build, with entry
+// points to select them: DBG = timing variants that drop the transform / the LDS reads / the staging / the weight loads, per-phase cycle
+// counters, spread and coalesced staging loads; XS (round 4) = staging by LDS-DMA from an x-blocked copy of the input, three buffers, two weight
+// register sets -- no-go; PREC 1 (round 3) = bf16x3 in the Winograd domain; MODE 1 (round 2) = the up-sampling-aware forward staging the fine
+// positions, replaced by MODE 3.  Their numbers are in profiles/LAB_NOTES.md, r03_probes.md, r04_probes.md and r05_probes.md; the probes under
+// tools/archive/ that drove them need that commit.  The switches are now the constants DBG = PREC = XS = 0 inside the kernel: nothing can
+// select a variant any more, the epilogue and most of the main loop are free of them, but the staging lambdas, the PREC staging plan and the
+// branches of the main loop that call them are still in the text as dead code.  Deleting those changes which variables the main-loop lambda
+// captures, and with it the register allocation and instruction order of all 12 instantiations (LAB_NOTES.md, "Winograd 3-D convs: experiment
+// switches"): they go when that can be done without touching the emitted code, or with a measurement.
 #include <type_traits>
 #include "df_common.hpp"
 #include "conv_args.hpp"
@@ -45,11 +44,6 @@ namespace {
 using df::ceil_div;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kT = 512;                   // 8 waves: (xi_z, tile z-row)
 constexpr int kPackT = 256;
@@ -80,13 +74,11 @@ constexpr int kNoPrimary = 256;            // with DF_CONV_ADDUP + kSignBits: y 
                                            // the backward pass needs of it (df_wino_conv_fwd_addup_bits / df_lrelu_bits_bwd_pool2x)
 constexpr int kBitBytesPerBlock = 1024;    // 8 waves x 2 cout blocks x 64 lanes, per (tile block, cout slice)
 constexpr int kZeroFloats = 1024;         // zeroed tail of the packed weights: SAME padding reads it, one 64-byte step per chunk
-// PREC = 1 ("bf16x3" in the Winograd domain, see wino3d_kernel): LDS holds the z-TRANSFORMED input of a chunk, position-major with the 16
-// channels of a position contiguous: [plane = (z-row, xi_z)][y 0..9][x 0..9 of pitch 12][16 channels + 4 pad floats]
-constexpr int BPOS = 80;                  // bytes per position (16 channels + pad: 5 sixteen-byte slots, odd -> conflict-free ds_read_b128)
-constexpr int BPY = 12;                   // positions per row (pitch)
-constexpr int BPLANE = (9 * BPY + 10) * BPOS;      // bytes per plane (the last row needs 10 positions only)
-constexpr int BBUF = 8 * BPLANE;          // bytes per LDS buffer (75520)
-constexpr int BCOL = 400;                 // staging threads: one (y, x, channel quad) z-column of the halo block each
+// (types and LDS layout constants of the dead PREC = 1 paths, see the header comment)
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+constexpr int BPOS = 80, BPY = 12, BPLANE = (9 * BPY + 10) * BPOS, BBUF = 8 * BPLANE, BCOL = 400;
 
 struct WinoArgs {
   const float* x;
@@ -103,8 +95,8 @@ struct WinoArgs {
   int nbz, nby, nbx, ntb, ncs;
   int flags;
   float leak;
-  int spx;
-  int Wb;              // XS != 0: x-blocks of 4 per row of the x-blocked copy (2 nbx + 1); a.x then points to that copy
+  int spx;             // cout slices per XCD (wino_grid)
+  int Wb;              // (never set: read by the dead XS paths only)
 };
 
 // ---- weight transform + packing ------------------------------------------------------------------------------------------
@@ -159,56 +151,6 @@ __global__ __launch_bounds__(kPackT) void wino_pack_kernel(const float* __restri
     wp[total + i] = 0.f;
 }
 
-// "bf16x3" operand: the same transform, every U split into two bf16 words (hi = rne(U), lo = rne(U - hi)) and laid out for
-// v_mfma_f32_16x16x16_bf16: Ub[cs][xz][k16][xy][xx][nb][lane = (k % 16) / 4 * 16 + n % 16][hi(k % 4 = 0..3) | lo(0..3)] -- one 16-byte load per
-// lane gives the B operand (hi and lo) of a (transform point, cout 16-block) for the 16 input channels of a chunk.
-__global__ __launch_bounds__(kPackT) void wino_pack_bf16x3_kernel(const float* __restrict__ w, __bf16* __restrict__ wp, int cin, int cout,
-                                                                  int mode, int64_t total) {
-  const int K = mode == 0 ? cin : cout, N = mode == 0 ? cout : cin;
-  const int64_t nfil = static_cast<int64_t>(K) * N;
-  for (int64_t f = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; f < nfil; f += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-    const int n = static_cast<int>(f % N), k = static_cast<int>(f / N);
-    double g[27];
-#pragma unroll
-    for (int tap = 0; tap < 27; ++tap)
-      g[tap] = static_cast<double>(mode == 0 ? w[(static_cast<int64_t>(tap) * cin + k) * cout + n]
-                                             : w[(static_cast<int64_t>(26 - tap) * cin + n) * cout + k]);
-    double gx[9][4];
-#pragma unroll
-    for (int r = 0; r < 9; ++r) {
-      const double a = g[r * 3], b = g[r * 3 + 1], c = g[r * 3 + 2];
-      gx[r][0] = a; gx[r][1] = 0.5 * (a + b + c); gx[r][2] = 0.5 * (a - b + c); gx[r][3] = c;
-    }
-    const int cs = n >> 5, nb = (n >> 4) & 1, j = n & 15, k16 = k >> 4, kq = (k >> 2) & 3, e = k & 3;
-#pragma unroll
-    for (int xz = 0; xz < 4; ++xz) {
-      double gz[3][4];
-#pragma unroll
-      for (int ty = 0; ty < 3; ++ty)
-#pragma unroll
-        for (int xx = 0; xx < 4; ++xx) {
-          const double a = gx[ty][xx], b = gx[3 + ty][xx], c = gx[6 + ty][xx];
-          gz[ty][xx] = xz == 0 ? a : xz == 3 ? c : xz == 1 ? 0.5 * (a + b + c) : 0.5 * (a - b + c);
-        }
-#pragma unroll
-      for (int xy = 0; xy < 4; ++xy)
-#pragma unroll
-        for (int xx = 0; xx < 4; ++xx) {
-          const double a = gz[0][xx], b = gz[1][xx], c = gz[2][xx];
-          const float u = static_cast<float>(xy == 0 ? a : xy == 3 ? c : xy == 1 ? 0.5 * (a + b + c) : 0.5 * (a - b + c));
-          const __bf16 h = static_cast<__bf16>(u);
-          const __bf16 l = static_cast<__bf16>(u - static_cast<float>(h));
-          const int64_t rec = ((((((static_cast<int64_t>(cs) * 4 + xz) * (K / 16) + k16) * 4 + xy) * 4 + xx) * 2 + nb) * 64 + kq * 16 + j) * 8;
-          wp[rec + e] = h;
-          wp[rec + 4 + e] = l;
-        }
-    }
-  }
-  float* wz = reinterpret_cast<float*>(wp);
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < kZeroFloats; i += static_cast<int64_t>(gridDim.x) * blockDim.x)
-    wz[total + i] = 0.f;
-}
-
 // ---- packed-fp32 helpers (VOP3P): one instruction = two lanes of the separable B^T transform --------------------------------
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
   f32x2 d;
@@ -252,8 +194,6 @@ __device__ __forceinline__ f32x2 pk_x3(f32x2 p, f32x2 q) {
   return d;
 }
 
-__device__ unsigned long long g_wino_prof[32];
-
 struct BlockInfo {
   const float* xb;     // &x[b][0][0][0][0]
   int hoff;            // element offset of the block's halo origin (z0-1, y0-1, x0-1) inside the batch volume (may be < 0)
@@ -274,44 +214,16 @@ __device__ __forceinline__ f32x4 buf_load16(__amdgpu_buffer_rsrc_t r, unsigned v
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // FL >= 0: the epilogue flags are the compile-time constant FL (no per-element flag tests); FL < 0: run-time a.flags
-// UP: the input is the COARSE tensor of an up-sampling-aware conv (x = nearest_up2x(xc) is never materialised): the staging reads
+// UPC (MODE 3): the input is the COARSE tensor of an up-sampling-aware conv (x = nearest_up2x(xc) is never materialised): the staging reads
 // xc[g >> 1] for fine halo coordinate g, and because every 2x2x2 tile then sees each coarse value twice, the transform points with
 // index 2 in any axis are identically zero (B^T d = (c-1 - c0, 2 c0, 0, c0 - c1)): only 27 of the 64 points are multiplied
 // (no wave takes xi_z = 2 and the xi_y|xi_x = 2 MFMAs are skipped) -- the 27-product form of the parity-class convolution.
 // POOL (MODE 2): the adjoint case -- the output is the 2x2x2 sum-pool of the convolution (d/d(xc) of the up-sampling-aware conv: x is
 // the fine gradient, y the COARSE tensor [B, D/2, H/2, W/2, Cout], accumulated into).  The pooled inverse transform is
 // (A^T row 0 + row 1) = (1, 2, 0, -1) per axis, so the same 27 points are the only ones needed and a tile block writes 32 voxels, not 256.
-//
-// PREC = 1 -- "bf16x3" IN THE WINOGRAD DOMAIN (opt-in precision mode, ops.CONV_PRECISION = "bf16x3"; the default stays exact fp32).
-// Same decomposition, staging loads, weights-from-L2 stream and epilogue; the 64 GEMMs run on the bf16 matrix pipe with both operands split
-// into bf16 (hi, lo) words AFTER the fp32 transforms, three v_mfma_f32_16x16x16_bf16 per product block (lo*hi + hi*lo + hi*hi, fp32
-// accumulate; tools/ubench/mfma_bf16_overlap.hip: 16.5 cycles each and -- unlike the fp32 MFMA -- plain VALU work hides beside them):
-//   * the staging threads apply the z part of B^T once per chunk (a thread owns a z-column of the halo block: 6 loads -> the 8 (z-row, xi_z)
-//     planes) and store 16 bytes = 4 channels of a position at a time: LDS = [plane][y][x][16 channels], 75.5 KB per buffer;
-//   * a k-step is (chunk of 16 channels, xi_y): lane = (tile, channel quad) reads 2 rows x 4 positions of its plane as ds_read_b128 (its 4
-//     channels at once), applies the y and x parts (32 plain v_add/v_sub: v_pk_* cost 15 cycles beside a bf16 MFMA) and splits the 4 points
-//     x 4 channels into packed bf16 hi / lo (v_cvt_pk_bf16_f32; 48 ops) = the A operands of 4 points, K = 16;
-//   * weights: U pre-split by wino_pack_bf16x3_kernel, one 16-byte load per lane = (hi, lo) of a (point, cout block): 8 loads per k-step.
-// The fp32 values that are split are bit-identical to the PREC = 0 kernel's operands; per-product error 2^-17 (16 significand bits).
-//
-// XS != 0 -- STAGING BY LDS-DMA FROM AN X-BLOCKED COPY OF THE INPUT (round 4).  a.x = G[b][z][y][xb][c][4], element i of granule (xb, c) =
-// x[b][z][y][4 xb - 1 + i][c] (zero outside the row: the SAME padding in x is part of the layout).  The 10 halo positions x0-1 .. x0+8 of a
-// tile block (x0 = 8 bx) are the first 10 of the 12 floats of granules xb = 2 bx .. 2 bx + 2, and the 16 channels of a chunk of one granule
-// column are 256 contiguous bytes: a halo ROW of a chunk is three such pieces = one `buffer_load_dwordx4 ... lds` of 51 lanes (lane =
-// (piece g, channel c | pad)), global -> LDS with no staging registers, no ds_write, no transpose, two full 128-byte lines per piece
-// instead of a 64-byte piece of every 512-byte voxel record.  LDS = [plane hz][row hy][piece g][17 slots: 16 channels + 1 pad][4 x]:
-// piece pitch 68 dwords, row pitch 204 -- the wave-wide ds_read2_b64 of the A path (lane = (tile, channel); the two x pairs of a tile row
-// sit in one or two pieces) stay bank-conflict free.  The row's address is scalar (SALU); a row outside the tensor reads through a
-// zero-length descriptor (zeros = SAME padding in y, z).  60 DMA instructions per chunk.
-// XS & 2: only waves 4-7 (one per SIMD) issue them -- the other wave of every SIMD never has a staging load in its in-order vmcnt queue and
-// keeps the matrix pipe busy while its partner waits for HBM.  XS & 4: issued in front of k-step 0's MFMAs instead of behind them.
-template <int DBG, int FL = -1, int MODE = 0, int PREC = 0, int XS = 0>
+template <int FL, int MODE>
 __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
-#ifndef DF_TUNING
-  // The release translation unit can only instantiate the production combination: every DBG / XS / PREC experiment path below is dead code
-  // there BY CONSTRUCTION (tests/test_cabi.py lists the instantiations the shipped library holds; DESIGN.md section 4 names them).
-  static_assert(DBG == 0 && PREC == 0 && XS == 0 && MODE != 1, "wino3d_kernel: experiment variants exist in the -DDF_TUNING library only");
-#endif
+  constexpr int DBG = 0, PREC = 0, XS = 0;      // the former template switches (header comment): every branch on them below is dead
   constexpr bool UPC = MODE == 3;                    // UP with the coarse halo block staged as such (see UPY / UCP above)
   constexpr bool UP = MODE == 1 || UPC, POOL = MODE == 2, P27 = MODE != 0;
   constexpr bool BX = PREC == 1;
@@ -321,10 +233,6 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
   constexpr int PZk = UPC ? UPZ : PZ, CPk = UPC ? UCP : CP;      // pitches INSIDE a buffer; the buffer stride below keeps the plain size (the
                                                                 // epilogue's 32 KB exchange area lives in the idle buffer)
   constexpr int NL = UPC ? NLU : NLOAD;              // staging pieces per thread and chunk
-#ifndef DF_KEEPQ      // (-DDF_KEEPQ=1: keep the whole weight quad of a 27-point row live up to its reload -- the cure of the "dead xi_x = 2 word" hazard
-#define DF_KEEPQ 0    //  that round 5 used before all transform temporaries were register PAIRS; costs 8 VGPRs, not needed any more)
-#endif
-  constexpr bool KEEPQ = DF_KEEPQ != 0;
   constexpr int XROWB = 51 * 16, XROWS = 60;        // XS: bytes per LDS row (3 pieces x 17 slots x 16 B), halo rows per chunk (6 planes x 10)
   constexpr int BUFk = XB ? XROWS * XROWB / 4 : CKW * CP;
   constexpr int BUFF = BX ? BBUF / 4 : BUFk;      // floats per LDS buffer
@@ -334,9 +242,7 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
   constexpr int NSB = TRI ? 3 : 2;
   __shared__ __attribute__((aligned(16))) float sIn[NSB * BUFF];
   __shared__ float sBias[32];        // this worker's cout slice of the bias (the slice is fixed for the worker's whole life)
-  // lrelu-mask operands of a tile block's outputs, fetched by LDS-DMA loads (no registers); PREC = 1: behind the epilogue's exchange area in
-  // the idle input buffer (32 + 32 of its 75.5 KB)
-  __shared__ float sMs[BX ? 4 : 16 * kT];
+  __shared__ float sMs[16 * kT];     // lrelu-mask operands of a tile block's outputs, fetched by LDS-DMA loads (no registers)
 
   const int eflags = FL >= 0 ? FL : a.flags;
   const int tid = threadIdx.x;
@@ -386,7 +292,7 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
     const int bz = t2 % a.nbz;
     bi.b = t2 / a.nbz;
     bi.z0 = bz * 4; bi.y0 = by * 8; bi.x0 = bx * 8;
-    bi.xb = a.x + static_cast<int64_t>(bi.b) * (XB ? a.D * a.H * a.Wb * 4 : UP ? (a.D >> 1) * (a.H >> 1) * (a.W >> 1) : a.D * a.H * a.W) * a.Cin;
+    bi.xb = a.x + static_cast<int64_t>(bi.b) * (UPC ? (a.D >> 1) * (a.H >> 1) * (a.W >> 1) : a.D * a.H * a.W) * a.Cin;
     bi.hoff = (((bi.z0 - 1) * a.H + (bi.y0 - 1)) * a.W + (bi.x0 - 1)) * a.Cin;
     return bi;
   };
@@ -414,7 +320,7 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
   }
   // pass `it` of the staging is taken by every wave, except the coarse block's second pass (64 pieces: wave 0) -- wave-uniform
   auto stage_pass = [&](int) -> bool { return !UPC || wave < UWIN * 4 / 64; };      // MODE 3: waves 0-5 stage (wave-uniform)
-  const unsigned vol_bytes = static_cast<unsigned>(XB ? a.D * a.H * a.Wb * 4 : UP ? (a.D >> 1) * (a.H >> 1) * (a.W >> 1) : a.D * a.H * a.W) * a.Cin * 4u;
+  const unsigned vol_bytes = static_cast<unsigned>(UPC ? (a.D >> 1) * (a.H >> 1) * (a.W >> 1) : a.D * a.H * a.W) * a.Cin * 4u;
   auto set_offs = [&](const BlockInfo& bi) {
     // [r6] opaque thread id: LLVM otherwise hoists the five pieces' (hz, hy, hx, roff) out of the block loop -- 20 registers that it then spills
     // (37-56 spilled VGPRs in the plain instantiations, 15 in the pooled adjoint), and the reloads sit in the main loop behind `s_waitcnt vmcnt(0)`
@@ -428,9 +334,8 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
         const int px = (w & 3) + 2 * it, py = (w >> 2) % 6, pz = w / 24;
         const int Dc = a.D >> 1, Hc = a.H >> 1, Wc = a.W >> 1;
         const int cz = (bi.z0 >> 1) - 1 + pz, cy = (bi.y0 >> 1) - 1 + py, cx = (bi.x0 >> 1) - 1 + px;
-        bool ok = static_cast<unsigned>(cz) < static_cast<unsigned>(Dc) && static_cast<unsigned>(cy) < static_cast<unsigned>(Hc) &&
+        const bool ok = static_cast<unsigned>(cz) < static_cast<unsigned>(Dc) && static_cast<unsigned>(cy) < static_cast<unsigned>(Hc) &&
                   static_cast<unsigned>(cx) < static_cast<unsigned>(Wc);      // fine g in range <=> coarse g >> 1 in range (even extents)
-        if (DBG & 4) ok = false;
         so[it] = ok ? static_cast<unsigned>(((cz * Hc + cy) * Wc + cx) * a.Cin + q4 * 4) * 4u : 0x80000000u;
         continue;
       }
@@ -439,16 +344,9 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
       const int hx = hv % HX, hy = (hv / HX) % HY, hz = hv / (HX * HY);
       const int roff = ((hz * a.H + hy) * a.W + hx) * a.Cin + q4 * 4;
       const int gz = bi.z0 - 1 + hz, gy = bi.y0 - 1 + hy, gx = bi.x0 - 1 + hx;
-      bool ok = static_cast<unsigned>(gz) < static_cast<unsigned>(a.D) && static_cast<unsigned>(gy) < static_cast<unsigned>(a.H) &&
+      const bool ok = static_cast<unsigned>(gz) < static_cast<unsigned>(a.D) && static_cast<unsigned>(gy) < static_cast<unsigned>(a.H) &&
                 static_cast<unsigned>(gx) < static_cast<unsigned>(a.W);
-      if (DBG & 4) ok = false;
-      if (UP) {
-        const int Hc = a.H >> 1, Wc = a.W >> 1;
-        so[it] = ok ? static_cast<unsigned>((((gz >> 1) * Hc + (gy >> 1)) * Wc + (gx >> 1)) * a.Cin + q4 * 4) * 4u : 0x80000000u;
-      } else {
-        so[it] = ok ? static_cast<unsigned>(bi.hoff + roff) * 4u : 0x80000000u;
-        if ((DBG & 384) == 384 && ok) so[it] &= 0xFFFC0u;      // (experiment 384: every staging load inside one 1 MB window -- L2 hits, L1 misses)
-      }
+      so[it] = ok ? static_cast<unsigned>(bi.hoff + roff) * 4u : 0x80000000u;
     }
   };
   auto stage_load = [&](int it, __amdgpu_buffer_rsrc_t srd, unsigned chunkbytes) -> f32x4 {
@@ -467,8 +365,7 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
   };
   // all pieces of a thread; MODE 3: the three loaded voxels (c0, c1, c2) x 4 channels -> the window (c0, c1, c2, -) of each channel
   auto stage_store_all = [&](int bufbytes, const auto& v) {
-    if constexpr (XB) {      // (x-blocked LDS-DMA staging: nothing passes through registers)
-    } else if constexpr (UPC) {
+    if constexpr (UPC) {
       if (!stage_pass(0)) return;
       char* d = sInB + (ldst[0] + bufbytes);
 #pragma unroll
@@ -527,20 +424,6 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
         for (int r = XASYM ? wave - 4 : wave; r < XROWS; r += XASYM ? 4 : 8) one_row(r);
       }
     }
-  };
-
-  // (experiment XS & 256, with three buffers: piece j of the wave is issued behind MFMA row j of k-step 0 instead of all 8 in one burst)
-  auto issue_piece = [&](int j, int bufbytes, const BlockInfo& bi, unsigned chunkbytes) {
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    const __amdgpu_buffer_rsrc_t dsrd = make_srd(bi.xb, vol_bytes);
-    const int rowb = a.Wb * a.Cin * 16;
-    const int base = (((bi.z0 - 1) * a.H + (bi.y0 - 1)) * a.Wb + (bi.x0 >> 2)) * a.Cin * 16 + static_cast<int>(chunkbytes);
-    const int r0 = wave + 8 * j, r = r0 < XROWS ? r0 : XROWS - 1;
-    const int hz = r / 10, hy = r - hz * 10;
-    const bool ok = static_cast<unsigned>(bi.z0 - 1 + hz) < static_cast<unsigned>(a.D) && static_cast<unsigned>(bi.y0 - 1 + hy) < static_cast<unsigned>(a.H);
-    const unsigned soff = static_cast<unsigned>(base + (hz * a.H + hy) * rowb);
-    const unsigned vo = xvoff | (ok ? 0u : 0x80000000u);      // (lanes >= 51 carry the out-of-range bit in xvoff already ... but they must not WRITE: exec mask)
-    if (lane < 51) __builtin_amdgcn_raw_ptr_buffer_load_lds(dsrd, (lds_ptr)(sInB + bufbytes + r * XROWB), 16, vo, soff, 0, 0);
   };
 
   // ---- PREC = 1 staging plan: thread p < 400 owns the z-column (hy, hx, channel quad) of the halo block -------------------------
@@ -697,9 +580,7 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
   constexpr int NBQ = (XS & 32) ? 2 : 1;
   f32x4 bq[NBQ][2][4];     // [k-step parity][cout 16-block][xi_y] = (xi_x 0..3)
   const unsigned laneb = static_cast<unsigned>(lane) * 16u;
-  // (experiments 262144 / 524288, timing only: the weight loads of the tile z-row 1 waves / of every wave go through a zero-length descriptor
-  //  -- same instructions, no cache traffic: what the DUPLICATE weight stream of the two z-row waves costs the CU's vector-memory path)
-  const __amdgpu_buffer_rsrc_t wsrd = make_srd(a.wp, ((DBG & 524288) || ((DBG & 262144) && th == 1)) ? 0u : static_cast<unsigned>(a.Cin) * a.Cout * 256u);
+  const __amdgpu_buffer_rsrc_t wsrd = make_srd(a.wp, static_cast<unsigned>(a.Cin) * a.Cout * 256u);
   const unsigned wbase_b = static_cast<unsigned>((cs * 4 + mz) * nk4) * 8192u + static_cast<unsigned>(hnb) * 4096u;
   auto issue_b = [&](int nb, int k4) {
     const int kl = k4 < nk4 ? k4 : 0;        // wraps to the first k-step of the next tile block
@@ -791,7 +672,6 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
 
   int pb = 0;          // buffer parity of the block's chunk 0
   for (int it = 0; it < niter; ++it) {
-    const unsigned long long tp0 = (DBG & 16) ? __builtin_readcyclecounter() : 0ull;
     const BlockInfo nxt = decode(seq(it + 1 < niter ? it + 1 : it));
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb)
@@ -814,8 +694,6 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
       }
     }
 
-    const unsigned long long tp1 = (DBG & 16) ? __builtin_readcyclecounter() : 0ull;
-    unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // The 16 lrelu-mask operands of this lane's outputs go global -> LDS by DMA loads (in registers hipcc spills each one to scratch
     // behind its own vmcnt(0): 14 serial HBM round trips).  Issued at the top of the epilogue and read back after the first combine
     // (issuing them inside the last chunk costs more than it hides: +20 % kernel time); every thread reads only what it requested.
@@ -826,13 +704,12 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
       const __amdgpu_buffer_rsrc_t msrd = make_srd(a.mask_src + static_cast<int64_t>(cur.b) * a.D * a.H * a.W * a.Cout,
                                                    static_cast<unsigned>(a.D) * a.H * a.W * a.Cout * 4u);
       const unsigned mv = static_cast<unsigned>(((oz0 * a.H + oy0) * a.W + ox0) * a.Cout + n0 + tl) * 4u;
-      float* const sM = BX ? sIn + ((nchunk - 1 + pb) & 1) * BUFF + 8192 : sMs;
 #pragma unroll
       for (int n2 = 0; n2 < 2; ++n2)
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
           const unsigned so_ = static_cast<unsigned>(n2 * 16 + (s >> 2) * sD + ((s >> 1) & 1) * sH + (s & 1) * sW) * 4u;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(msrd, (lds_ptr)(sM + (n2 * 8 + s) * kT + wave * 64), 4, mv, so_, 0, 0);
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(msrd, (lds_ptr)(sMs + (n2 * 8 + s) * kT + wave * 64), 4, mv, so_, 0, 0);
         }
     };
     auto main_loop = [&](auto half_c, auto lw_c) {
@@ -842,29 +719,16 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
     //  the weights arrive through an LDS ring would give them; the ring's own fill traffic is not modelled)
     constexpr bool LW = decltype(lw_c)::value;
     for (int chunk = 0; chunk < nchunk; ++chunk) {
-      const int bo = TRI ? ((chunk + pb) % 3) * BUFk * 4 : ((chunk + pb) & 1) * BUFk * 4;      // byte offsets of this / the next chunk's buffer
-      const int bn = TRI ? ((chunk + 1 + pb) % 3) * BUFk * 4 : BUFk * 4 - bo;
-      const int bn2 = ((chunk + 2 + pb) % 3) * BUFk * 4;                                       // TRI: where the pieces of chunk + 2 go
+      const int bo = ((chunk + pb) & 1) * BUFF * 4, bn = BUFF * 4 - bo;      // byte offsets of this / the next chunk's buffer
       const bool lastc = chunk + 1 == nchunk;
-      if constexpr (!XB) {
-        if (lastc) set_offs(nxt);                    // the last chunk stages the next tile block's first chunk
-      }
+      if (lastc) set_offs(nxt);                    // the last chunk stages the next tile block's first chunk
       const __amdgpu_buffer_rsrc_t ssrd = make_srd(lastc ? nxt.xb : cur.xb, vol_bytes);
-      const unsigned schunk = XB ? static_cast<unsigned>(lastc ? 0 : chunk + 1) * 256u : static_cast<unsigned>(lastc ? 0 : chunk + 1) * (CKW * 4u);
-      f32x4 stg[XB ? 1 : NLOAD];
+      const unsigned schunk = static_cast<unsigned>(lastc ? 0 : chunk + 1) * (CKW * 4u);
+      f32x4 stg[NLOAD];
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
         // -- A operands of this k-step (its raw inputs were requested during the previous one) --
-        const unsigned long long q0 = (DBG & 16) ? __builtin_readcyclecounter() : 0ull;
-        if (DBG & 16) asm volatile("s_waitcnt lgkmcnt(0)");
-        const unsigned long long q1 = (DBG & 16) ? __builtin_readcyclecounter() : 0ull;
-        if (XB && TRI && !(XS & 256) && ks == 0 && !(DBG & 4)) {
-          const int cc = chunk + 2;
-          issue_dma(bn2, cc < nchunk ? cur : nxt, static_cast<unsigned>(cc < nchunk ? cc : cc - nchunk) * 256u);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if (XB && !TRI && (XS & 16) && ks == 0 && !(DBG & 4)) { issue_dma(bn, lastc ? nxt : cur, schunk); __builtin_amdgcn_sched_barrier(0); }
-        if (!(DBG & 1)) transform();
+        transform();
         __builtin_amdgcn_sched_barrier(0);
         if (!XB && ks == (SPREAD1 ? 3 : 2) && !(DBG & 4) && !(DBG & 64)) {
           stage_store_all(bn, stg);
@@ -887,14 +751,8 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
         // already waited for at the LDS writes of ks == 2, and __syncthreads()' vmcnt(0) drained the weight loads in flight (this and the
         // two epilogue barriers: 16.21 -> 16.05 ms per top-level launch, round 3)
         if (ks == 3) lds_barrier();
-        if (!(DBG & 2)) {                                                    // raw inputs of the next k-step
-          if constexpr (XB) raw_read_x(ks < 3 ? bo + (ks + 1) * 64 : bn); else raw_read(ks < 3 ? bo + (ks + 1) * 16 * CPk : bn);
-        }
+        raw_read(ks < 3 ? bo + (ks + 1) * 16 * CPk : bn);      // raw inputs of the next k-step
         __builtin_amdgcn_sched_barrier(0);
-        if (XB && !TRI && (XS & 20) == 4 && ks == 0 && !(DBG & 4)) { issue_dma(bn, lastc ? nxt : cur, schunk); __builtin_amdgcn_sched_barrier(0); }
-        const unsigned long long q2 = (DBG & 16) ? __builtin_readcyclecounter() : 0ull;
-        if (DBG & 16) asm volatile("s_waitcnt vmcnt(4)");
-        const unsigned long long q3 = (DBG & 16) ? __builtin_readcyclecounter() : 0ull;
         // [r3] a xi_y row's weight registers are reloaded right after its 4 MFMAs, not after the cout block's 16: every weight load is in
         // flight up to 12 MFMAs longer before the next k-step needs it (16.52 -> 16.27 ms per top-level launch; tuning variant 196608 = the
         // old order)
@@ -911,16 +769,8 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
           if (!P27 || ((i >> 2) != 2 && (i & 3) != 2))
             acc[0][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A2[i >> 1][i & 1], bq[ks & (NBQ - 1)][0][i >> 2][i & 3], acc[0][i], 0, 0, 0);
           if ((i & 3) == 3) {
-            // 27-point modes never read the xi_x = 2 word of a weight quad: without this use of the WHOLE quad the register allocator hands that
-            // dead register to an A operand, whose write then has to wait (s_waitcnt vmcnt) for the quad's load issued a moment ago
-            if (P27 && KEEPQ) asm volatile("" :: "v"(bq[ks & (NBQ - 1)][0][i >> 2]));
             __builtin_amdgcn_sched_barrier(0);
             reload_row(0, i >> 2);
-            if (XB && TRI && (XS & 256) && ks == 0 && !(DBG & 4)) {
-              const int cc = chunk + 2;
-              issue_piece(i >> 2, bn2, cc < nchunk ? cur : nxt, static_cast<unsigned>(cc < nchunk ? cc : cc - nchunk) * 256u);
-            }
-            if (!XB && SPREAD && ks == (SPREAD1 ? 1 : 0) && !(DBG & 4)) stg[i >> 2] = stage_load(i >> 2, ssrd, schunk);      // pieces 0..3
             __builtin_amdgcn_sched_barrier(0);
           }
         }
@@ -932,14 +782,8 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
             if (!P27 || ((i >> 2) != 2 && (i & 3) != 2))
               acc[1][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A2[i >> 1][i & 1], bq[ks & (NBQ - 1)][1][i >> 2][i & 3], acc[1][i], 0, 0, 0);
             if ((i & 3) == 3) {
-              if (P27 && KEEPQ) asm volatile("" :: "v"(bq[ks & (NBQ - 1)][1][i >> 2]));
               __builtin_amdgcn_sched_barrier(0);
               reload_row(1, i >> 2);
-              if (XB && TRI && (XS & 256) && ks == 0 && !(DBG & 4)) {
-                const int cc = chunk + 2;
-                issue_piece(4 + (i >> 2), bn2, cc < nchunk ? cur : nxt, static_cast<unsigned>(cc < nchunk ? cc : cc - nchunk) * 256u);
-              }
-              if (!XB && SPREAD && ks == (SPREAD1 ? 1 : 0) && !(DBG & 4) && (i >> 2) == 1) stg[4] = stage_load(4, ssrd, schunk);      // piece 4
               __builtin_amdgcn_sched_barrier(0);
             }
           }
@@ -950,13 +794,9 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
                                          // the first wait that covers them is the one for the NEXT weight batch (1.5 k-steps away)
 #pragma unroll
           for (int it = 0; it < NL; ++it)
-            if (stage_pass(it)) stg[it] = (DBG & 384) == 128 ? f32x4{0.f, 0.f, 0.f, 0.f} : stage_load(it, ssrd, schunk);
+            if (stage_pass(it)) stg[it] = stage_load(it, ssrd, schunk);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (DBG & 16) {
-          const unsigned long long q4 = __builtin_readcyclecounter();
-          ph[0] += q1 - q0; ph[1] += q2 - q1; ph[2] += q3 - q2; ph[3] += q4 - q3;
-        }
       }
     }
     };
@@ -1044,7 +884,6 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
       }
     }
 
-    const unsigned long long tp2 = (DBG & 16) ? __builtin_readcyclecounter() : 0ull;
     // ---- epilogue: inverse transform in x, y per accumulator element; z across the waves through the idle LDS buffer ---------
     // (the buffer of the last chunk is free since that chunk's barrier; the other one holds the next block's chunk 0)
     if constexpr (POOL) {
@@ -1076,8 +915,7 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
         lds_barrier();
       }
     } else {
-      const int lb = TRI ? ((nchunk - 1 + pb) % 3) * BUFF : ((nchunk - 1 + pb) & 1) * BUFF;
-      const float* const sM = BX ? sIn + lb + 8192 : sMs;
+      const int lb = ((nchunk - 1 + pb) & 1) * BUFF;
       f32x4* sO = reinterpret_cast<f32x4*>(sIn + lb);      // [xi_z][tz][e][lane] float4 = (oy0ox0, oy0ox1, oy1ox0, oy1ox1)
       // this wave combines accumulator element e = xi_z of its own z-row:  tile (ty = lane>>4, tx = e), cout = lane & 15
       const int oz0 = cur.z0 + 2 * th, oy0 = cur.y0 + 2 * kq, ox0 = cur.x0 + 2 * xz;
@@ -1114,11 +952,8 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
             sO[((mz * 2 + mth) * 4 + e) * 64 + lane] = f32x4{o01[0], o01[1], o23[0], o23[1]};
           }
         };
-        const unsigned long long e0 = (DBG & 16) ? __builtin_readcyclecounter() : 0ull;
         if (!half) emit(acc[nb]);
         else if (nb == hnb) emit(acc[0]);
-        if (DBG & 16) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const unsigned long long e1 = (DBG & 16) ? __builtin_readcyclecounter() : 0ull;
         if (nb == 0 && full && (eflags & DF_CONV_RESIDUAL)) {
 #pragma unroll
           for (int n2 = 0; n2 < 2; ++n2)
@@ -1127,7 +962,6 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
               rres[n2][s] = a.residual[obase + n2 * 16 + (s >> 2) * sD + ((s >> 1) & 1) * sH + (s & 1) * sW];
         }
         if (full_bar) __syncthreads(); else lds_barrier();      // (the combine below reads LDS only; the residual loads are waited for at their use)
-        const unsigned long long e2 = (DBG & 16) ? __builtin_readcyclecounter() : 0ull;
         const f32x4 m0 = sO[((0 * 2 + th) * 4 + xz) * 64 + lane], m1 = sO[((1 * 2 + th) * 4 + xz) * 64 + lane];
         const f32x4 m3 = sO[((3 * 2 + th) * 4 + xz) * 64 + lane];
         f32x4 lo = m0 + m1, hi = m1 - m3;
@@ -1145,7 +979,7 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
         // Full blocks of the variants without a per-output operand (bias / lrelu / sign bits only: the 27-point up-sampling-aware forward and the plain
         // forward): the stores go through the 4 x 4 lane-quad transpose of conv_wino43.hip -- 2 float4 stores per lane and cout block instead of 8 scalar
         // ones; bias, lrelu and the sign bits stay in the accumulator layout (the sign-byte layout is unchanged).  Bit-identical.
-        const bool wide = full && !(eflags & (DF_CONV_RESIDUAL | DF_CONV_MASK | DF_CONV_ADDUP)) && !NOY && !(DBG & 512);
+        const bool wide = full && !(eflags & (DF_CONV_RESIDUAL | DF_CONV_MASK | DF_CONV_ADDUP)) && !NOY;
         if (wide) {
           f32x4 vz[2];
 #pragma unroll
@@ -1178,12 +1012,11 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
           const bool mpos = !MB || ((mbyte >> s) & 1u) != 0u;
           if (full) {
             if (eflags & DF_CONV_RESIDUAL) v += rres[nb][s];
-            if (eflags & DF_CONV_MASK) v = (MB ? mpos : sM[(nb * 8 + s) * kT + tid] > 0.f) ? v : a.leak * v;
+            if (eflags & DF_CONV_MASK) v = (MB ? mpos : sMs[(nb * 8 + s) * kT + tid] > 0.f) ? v : a.leak * v;
             // wave-uniform base (batch volume + this output's scalar offset) + 32-bit lane offset: no 64-bit address per output
             char* yb = reinterpret_cast<char*>(a.y + static_cast<int64_t>(cur.b) * a.D * a.H * a.W * a.Cout +
                                                ((s >> 2) * sD + ((s >> 1) & 1) * sH + (s & 1) * sW) + nb * 16);
-            if (DBG & 512) asm volatile("" :: "v"(v));      // (experiment: no stores)
-            else if (!NOY) *reinterpret_cast<float*>(yb + lane_off) = v;
+            if (!NOY) *reinterpret_cast<float*>(yb + lane_off) = v;
             if (eflags & DF_CONV_ADDUP) {
               char* yb2 = reinterpret_cast<char*>(a.y2 + static_cast<int64_t>(cur.b) * a.D * a.H * a.W * a.Cout +
                                                   ((s >> 2) * sD + ((s >> 1) & 1) * sH + (s & 1) * sW) + nb * 16);
@@ -1197,20 +1030,10 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
           }
         }
         if (SB) a.bits_out[wbase + nb * 64] = static_cast<unsigned char>(sbyte);
-        const unsigned long long e3 = (DBG & 16) ? __builtin_readcyclecounter() : 0ull;
         if (full_bar) __syncthreads(); else lds_barrier();      // (the output stores drain behind the next cout block's exchange / the next tile block)
-        if (DBG & 16) {
-          const unsigned long long e4 = __builtin_readcyclecounter();
-          ph[4 + 0] += e1 - e0; ph[4 + 1] += e2 - e1; ph[4 + 2] += e3 - e2; ph[4 + 3] += e4 - e3;
-        }
       }
     }
-    if ((DBG & 16) && blockIdx.x == 8 && tid == 0) {
-      const unsigned long long tp3 = __builtin_readcyclecounter();
-      g_wino_prof[0] += tp1 - tp0; g_wino_prof[1] += tp2 - tp1; g_wino_prof[2] += tp3 - tp2; g_wino_prof[3] += 1;
-      for (int i = 0; i < 8; ++i) g_wino_prof[4 + i] += ph[i];
-    }
-    pb = TRI ? (pb + nchunk) % 3 : (pb + nchunk) & 1;
+    pb = (pb + nchunk) & 1;
     cur = nxt;
   }
 }
@@ -1260,152 +1083,96 @@ __global__ __launch_bounds__(256) void lrelu_bits_bwd_pool_kernel(const float4* 
   gpool[i] = acc;
 }
 
-// NDHWC -> the x-blocked layout of the XS staging (see wino3d_kernel): G[b][z][y][xb][c][0..3] = x[b][z][y][4 xb - 1 + i][c], zero outside.
-// One thread = one 16-byte granule; the lanes of a wave are consecutive channels: four 256-byte reads, one 1 KiB write.
-__global__ __launch_bounds__(256) void to_xblk_kernel(const float* __restrict__ x, f32x4* __restrict__ g, int64_t ngran, int W, int Wb, int C) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (i >= ngran) return;
-  const int c = static_cast<int>(i % C);
-  const int64_t r = i / C;
-  const int xb = static_cast<int>(r % Wb);
-  const int64_t row = r / Wb;
-  const float* src = x + (row * W) * C + c;
-  f32x4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int xs = 4 * xb - 1 + e;
-    v[e] = (xs >= 0 && xs < W) ? src[static_cast<int64_t>(xs) * C] : 0.f;
+// ---- host side: one argument check, one launch -------------------------------------------------------------------------------------
+// The operands of a launch as the kernel sees them: the pointer fields of WinoArgs in its order.  Bit i of the masks below = field i.
+struct WinoOps {
+  const float *x, *wp, *bias, *residual, *mask_src;
+  float *y, *y2;
+  void* bits_out;
+  const void* bits_in;
+};
+enum : unsigned { kX = 1, kWp = 2, kBias = 4, kResidual = 8, kMaskSrc = 16, kY = 32, kY2 = 64, kBitsOut = 128, kBitsIn = 256 };
+
+// What differs between the argument checks of the seven entry points (everything else is wino_check itself):
+struct WinoEntry {
+  const char* name;
+  unsigned need;          // operands that must not be null
+  unsigned aligned;       // operands that must be 16-byte aligned: x, the packed weights, the bit words, and y where every instantiation
+                          // the entry point reaches may store it 16 bytes at a time (a null operand counts as aligned)
+  bool coarse;            // B, D, H, W are the COARSE extents of an up-sampling form: the kernel runs on twice each
+  bool up_fwd_volume;     // the 2 GiB bound is on 8 v Cout and v Cin (v = coarse volume: y is fine, x coarse), not on the kernel's volume x max(Cin, Cout)
+  bool even;              // extents must be even (the output of a 2x up-sampling block)
+  bool flags_first;       // the flag / operand check comes before the volume bound, not behind it
+};
+//                                  name                            need                                          aligned                          coarse upvol  even   flags first
+constexpr WinoEntry kFwd =        {"df_wino_conv_fwd",            kX | kWp | kY,                                  kX | kWp | kY,                     false, false, false, false};
+constexpr WinoEntry kFwdBits =    {"df_wino_conv_fwd_bits",       kX | kWp | kY,                                  kX | kWp | kY | kBitsIn | kBitsOut, false, false, false, false};
+constexpr WinoEntry kAddup =      {"df_wino_conv_fwd_addup",      kX | kWp | kBias | kResidual | kY | kY2,        kX | kWp,                          false, false, true,  false};
+constexpr WinoEntry kAddupBits =  {"df_wino_conv_fwd_addup_bits", kX | kWp | kBias | kResidual | kY2 | kBitsOut,  kX | kWp | kBitsOut,               false, false, true,  false};
+constexpr WinoEntry kUpFwd =      {"df_wino_upconv_fwd",          kX | kWp | kY,                                  kX | kWp | kY,                     true,  true,  false, true};
+constexpr WinoEntry kUpFwdBits =  {"df_wino_upconv_fwd_bits",     kX | kWp | kY | kBias | kBitsOut,               kX | kWp | kY | kBitsOut,          true,  true,  false, false};
+constexpr WinoEntry kUpDgrad =    {"df_wino_upconv_dgrad",        kX | kWp | kY,                                  kX | kWp,                          true,  false, false, false};
+
+// B, D, H, W, Cin, Cout as the entry point received them; flags_ok = the entry point's own rule for its flags and their operands
+int wino_check(const WinoEntry& e, const WinoOps& o, int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, bool flags_ok,
+               const char* flags_rule) {
+  const void* const p[9] = {o.x, o.wp, o.bias, o.residual, o.mask_src, o.y, o.y2, o.bits_out, o.bits_in};
+  bool present = true, aligned = true;
+  for (int i = 0; i < 9; ++i) {
+    if ((e.need >> i) & 1u) present = present && p[i] != nullptr;
+    if ((e.aligned >> i) & 1u) aligned = aligned && df::aligned16(p[i]);
   }
-  __builtin_nontemporal_store(v, g + i);
+  DF_REQUIRE(present, DF_EINVAL, "%s: null pointer", e.name);
+  DF_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, DF_EINVAL, "%s: non-positive extent", e.name);
+  DF_REQUIRE(!e.even || (D % 2 == 0 && H % 2 == 0 && W % 2 == 0), DF_EINVAL, "%s: extents must be even (the output of a 2x up-sampling block)", e.name);
+  DF_REQUIRE(Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0, DF_ESHAPE, "%s: Cin, Cout must be multiples of 32", e.name);
+  if (e.flags_first) DF_REQUIRE(flags_ok, DF_EINVAL, "%s: %s", e.name, flags_rule);
+  // (staging goes through 32-bit byte offsets into one batch volume, with 0x80000000 as the out-of-range sentinel)
+  const int64_t v = D * H * W, cmax = Cin > Cout ? Cin : Cout;
+  const bool fits = e.up_fwd_volume ? 8 * v * Cout <= (1LL << 29) && v * Cin <= (1LL << 29) : (e.coarse ? 8 : 1) * v * cmax <= (1LL << 29);
+  DF_REQUIRE(fits && Cin * Cout <= (1LL << 24), DF_ESHAPE, "%s: one batch volume must stay below 2 GiB, Cin * Cout below 16 Mi", e.name);
+  if (!e.flags_first) DF_REQUIRE(flags_ok, DF_EINVAL, "%s: %s", e.name, flags_rule);
+  DF_REQUIRE(aligned, DF_EALIGN, "%s: x, the packed weights, the bit words and a y stored 16 bytes at a time must be 16-byte aligned", e.name);
+  return DF_OK;
 }
 
-#ifdef DF_TUNING      // instrumented kernel variants + knobs of the tuning library only (include/deepfluids_hip_debug.h)
-int g_wino_dbg = 0;
-int g_wino_spx = 0;     // slices per XCD override
-#else
-constexpr int g_wino_spx = 0;
-#endif
+// D, H, W = the OUTPUT extents of the underlying convolution, Cin / Cout = the kernel's; (fl, mode) must be one of the pairs listed here
+int wino_launch(const char* name, int fl, int mode, const WinoOps& o, int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
+                int flags, float leak, df_stream_t stream) {
+  WinoArgs a;
+  a.x = o.x; a.wp = reinterpret_cast<const f32x4*>(o.wp); a.zeros = o.wp + 64 * Cin * Cout;
+  a.bias = o.bias; a.residual = o.residual; a.mask_src = o.mask_src; a.y = o.y; a.y2 = o.y2;
+  a.bits_out = static_cast<unsigned char*>(o.bits_out); a.bits_in = static_cast<const unsigned char*>(o.bits_in);
+  a.B = (int)B; a.D = (int)D; a.H = (int)H; a.W = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout;
+  a.nbz = (int)ceil_div(D, 4); a.nby = (int)ceil_div(H, 8); a.nbx = (int)ceil_div(W, 8);
+  const int64_t ntb = B * a.nbz * a.nby * a.nbx;
+  a.ncs = (int)(Cout / 32);
+  DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "%s: too many workgroups", name);
+  a.ntb = (int)ntb;
+  a.flags = flags; a.leak = leak;
+  const dim3 grid((unsigned)dfconv::wino_grid(a, ntb));
+  hipStream_t s = df::as_stream(stream);
+#define DF_WINO(F, M) \
+  if (fl == (F) && mode == (M)) { hipLaunchKernelGGL((wino3d_kernel<F, M>), grid, dim3(kT), 0, s, a); return df::launched(name); }
+  DF_WINO(-1, 0)
+  DF_WINO(0, 0)
+  DF_WINO(DF_CONV_RESIDUAL, 0)
+  DF_WINO(DF_CONV_MASK, 0)
+  DF_WINO(DF_CONV_MASK | kMaskBits, 0)
+  DF_WINO(DF_CONV_BIAS | DF_CONV_LRELU, 0)
+  DF_WINO(DF_CONV_BIAS | DF_CONV_LRELU | kSignBits, 0)
+  DF_WINO(DF_CONV_BIAS | DF_CONV_LRELU | DF_CONV_ADDUP, 0)
+  DF_WINO(DF_CONV_BIAS | DF_CONV_LRELU | DF_CONV_ADDUP | kSignBits | kNoPrimary, 0)
+  DF_WINO(0, 2)
+  DF_WINO(DF_CONV_BIAS | DF_CONV_LRELU, 3)
+  DF_WINO(DF_CONV_BIAS | DF_CONV_LRELU | kSignBits, 3)
+#undef DF_WINO
+  return df::fail(DF_EINVAL, "%s: wino3d_kernel<%d, %d> is not instantiated", name, fl, mode);
+}
+
 }  // namespace
 
 extern "C" {
-
-#ifdef DF_TUNING
-void df_debug_set_wino(int v) { g_wino_dbg = v & 0x3ffffff; g_wino_spx = v >> 26; }
-int df_debug_wino_prof(unsigned long long* out, int reset) {
-  if (reset) { unsigned long long z[32] = {0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_wino_prof), z, sizeof(z)); }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wino_prof), 32 * sizeof(unsigned long long));
-}
-#endif
-
-#ifdef DF_TUNING
-static int64_t wino_grid(WinoArgs& a, int64_t ntb);
-// Round-4 probe: df_wino_conv_fwd (flags = DF_CONV_BIAS | DF_CONV_LRELU) with the input staged by LDS-DMA from an x-blocked copy `xg`
-// ([B, D, H, 2 ceil(W/8) + 1, Cin, 4] floats, written here by to_xblk_kernel unless variant & 256).  variant & 15 = XS of wino3d_kernel:
-// 1 all waves issue the DMA pieces behind k-step 0's MFMAs | 3 waves 4-7 only | 5 / 7 the same in front of the MFMAs;
-// variant & 16: DBG 4 (no staging at all, timing only).
-int64_t df_debug_wino_xblk_elems(int64_t B, int64_t D, int64_t H, int64_t W, int64_t C) { return B * D * H * (2 * ceil_div(W, 8) + 1) * C * 4; }
-int df_debug_wino_conv_fwd_xblk(const float* x, float* xg, const float* wp, const float* bias, float* y, int64_t B, int64_t D, int64_t H, int64_t W,
-                                int64_t Cin, int64_t Cout, float leak, int variant, df_stream_t stream) {
-  DF_REQUIRE(x && xg && wp && bias && y, DF_EINVAL, "df_debug_wino_conv_fwd_xblk: null pointer");
-  DF_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0, DF_ESHAPE, "df_debug_wino_conv_fwd_xblk: shape");
-  WinoArgs a;
-  a.x = xg; a.wp = reinterpret_cast<const f32x4*>(wp); a.zeros = wp + 64 * Cin * Cout;
-  a.bias = bias; a.residual = nullptr; a.mask_src = nullptr; a.y = y; a.y2 = nullptr; a.bits_out = nullptr; a.bits_in = nullptr;
-  a.B = (int)B; a.D = (int)D; a.H = (int)H; a.W = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout;
-  a.nbz = (int)ceil_div(D, 4); a.nby = (int)ceil_div(H, 8); a.nbx = (int)ceil_div(W, 8);
-  a.Wb = 2 * a.nbx + 1;
-  DF_REQUIRE(D * H * a.Wb * 4 * Cin <= (1LL << 29), DF_ESHAPE, "df_debug_wino_conv_fwd_xblk: one batch volume of the copy must stay below 2 GiB");
-  const int64_t ntb = B * a.nbz * a.nby * a.nbx;
-  a.ncs = (int)(Cout / 32);
-  a.ntb = (int)ntb;
-  a.flags = DF_CONV_BIAS | DF_CONV_LRELU; a.leak = leak;
-  hipStream_t s = df::as_stream(stream);
-  if (!(variant & 256)) {
-    const int64_t ngran = B * D * H * a.Wb * Cin;
-    hipLaunchKernelGGL(to_xblk_kernel, dim3((unsigned)ceil_div(ngran, 256)), dim3(256), 0, s, x, reinterpret_cast<f32x4*>(xg), ngran, (int)W, a.Wb, (int)Cin);
-  }
-  const int64_t grid = wino_grid(a, ntb);
-  constexpr int F = DF_CONV_BIAS | DF_CONV_LRELU;
-  switch (variant & 127) {
-    case 1: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 1>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 3: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 3>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 5: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 5>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 7: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 7>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 9: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 9>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 11: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 11>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 13: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 13>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 15: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 15>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 17: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 17>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 25: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 25>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 27: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 27>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 32 + 1: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 33>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 32 + 9: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 41>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 32 + 11: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 43>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 32 + 13: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 45>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 32 + 17: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 49>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 32 + 31: hipLaunchKernelGGL((wino3d_kernel<4, F, 0, 0, 33>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 3 + 64: hipLaunchKernelGGL((wino3d_kernel<4, F, 0, 0, 3>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 104: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 256 + 128 + 64 + 1>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;           // three buffers + LDS "weights", pieces spread over k-step 0
-    case 106: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 256 + 128 + 1>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;                // three buffers, global weights, pieces spread
-    case 98: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 128 + 64 + 1>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;                 // three buffers + LDS "weights"
-    case 102: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 128 + 1>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;                     // three buffers, global weights
-    case 64 + 32 + 1: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 64 + 1>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;            // all waves stage, LDS "weights"
-    case 64 + 32 + 17: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 64 + 17>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;
-    case 64 + 32 + 4: hipLaunchKernelGGL((wino3d_kernel<4, F, 0, 0, 64 + 3>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;            // no staging, LDS "weights"
-    case 64 + 32 + 3: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 64 + 3>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;            // waves 4-7 stage (behind the MFMAs, rolled) and take LDS "weights"
-    case 64 + 32 + 19: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 64 + 19>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;          // ... pieces at the start of k-step 0
-    case 64 + 32 + 7: hipLaunchKernelGGL((wino3d_kernel<0, F, 0, 0, 64 + 7>), dim3((unsigned)grid), dim3(kT), 0, s, a); break;            // ... in front of the MFMAs
-    default: return df::fail(DF_EINVAL, "df_debug_wino_conv_fwd_xblk: unknown variant");
-  }
-  return df::launched("df_debug_wino_conv_fwd_xblk");
-}
-// The "bf16x3 in the Winograd domain" experiment (wino3d_kernel PREC = 1), tuning library only: same arguments as df_wino_pack_weights /
-// df_wino_conv_fwd.  df_debug_set_wino: 0 production order | 32 xi_x-major MFMA order | diagnosis variants (results wrong by construction)
-// 1 no transform | 2 no LDS operand reads | 4 no staging | 8 no weight loads and sums | 16 staged chunk stored one k-step later |
-// 64 staging loads ahead of the k-step's MFMAs.
-int df_debug_wino_pack_weights_bf16x3(const float* w, float* wp, int64_t cin, int64_t cout, int mode, df_stream_t stream) {
-  DF_REQUIRE(w && wp, DF_EINVAL, "df_debug_wino_pack_weights_bf16x3: null pointer");
-  DF_REQUIRE(cin > 0 && cout > 0 && cin % 32 == 0 && cout % 32 == 0 && (mode == 0 || mode == 1), DF_ESHAPE,
-             "df_debug_wino_pack_weights_bf16x3: cin, cout must be multiples of 32; mode 0|1");
-  const int64_t total = 64 * cin * cout;      // in fp32 units: (hi, lo) bf16 = 4 bytes per transformed weight
-  int64_t g = ceil_div(cin * cout, 64);
-  if (g > 4096) g = 4096;
-  hipLaunchKernelGGL(wino_pack_bf16x3_kernel, dim3((unsigned)g), dim3(64), 0, df::as_stream(stream), w, reinterpret_cast<__bf16*>(wp), (int)cin,
-                     (int)cout, mode, total);
-  return df::launched("df_debug_wino_pack_weights_bf16x3");
-}
-int df_debug_wino_conv_fwd_bf16x3(const float* x, const float* wp, const float* bias, const float* residual, const float* mask_src, float* y,
-                                  int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int flags, float leak,
-                                  df_stream_t stream) {
-  DF_REQUIRE(x && wp && y, DF_EINVAL, "df_debug_wino_conv_fwd_bf16x3: null pointer");
-  DF_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0, DF_ESHAPE,
-             "df_debug_wino_conv_fwd_bf16x3: positive extents, Cin, Cout multiples of 32");
-  DF_REQUIRE(D * H * W * (Cin > Cout ? Cin : Cout) <= (1LL << 29) && Cin * Cout <= (1LL << 24), DF_ESHAPE,
-             "df_debug_wino_conv_fwd_bf16x3: one batch volume must stay below 2 GiB");
-  DF_REQUIRE(!(flags & DF_CONV_ADDUP) && (!(flags & DF_CONV_BIAS) || bias) && (!(flags & DF_CONV_RESIDUAL) || residual) &&
-                 (!(flags & DF_CONV_MASK) || mask_src), DF_EINVAL, "df_debug_wino_conv_fwd_bf16x3: flag without its operand");
-  DF_REQUIRE(df::aligned16(wp) && df::aligned16(x), DF_EALIGN, "df_debug_wino_conv_fwd_bf16x3: x and packed weights must be 16-byte aligned");
-  WinoArgs a;
-  a.x = x; a.wp = reinterpret_cast<const f32x4*>(wp); a.zeros = wp + 64 * Cin * Cout;
-  a.bias = bias; a.residual = residual; a.mask_src = mask_src; a.y = y; a.y2 = nullptr; a.bits_out = nullptr; a.bits_in = nullptr;
-  a.B = (int)B; a.D = (int)D; a.H = (int)H; a.W = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout;
-  a.nbz = (int)ceil_div(D, 4); a.nby = (int)ceil_div(H, 8); a.nbx = (int)ceil_div(W, 8);
-  const int64_t ntb = B * a.nbz * a.nby * a.nbx;
-  a.ncs = (int)(Cout / 32);
-  DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "df_debug_wino_conv_fwd_bf16x3: too many workgroups");
-  a.ntb = (int)ntb;
-  a.flags = flags; a.leak = leak;
-  const int64_t grid = wino_grid(a, ntb);
-#define DF_WB(V) case V: hipLaunchKernelGGL((wino3d_kernel<V, DF_CONV_BIAS | DF_CONV_LRELU, 0, 1>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break
-  switch (g_wino_dbg) {
-    case 0: hipLaunchKernelGGL((wino3d_kernel<0, -1, 0, 1>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    DF_WB(1); DF_WB(2); DF_WB(3); DF_WB(4); DF_WB(8); DF_WB(12); DF_WB(7); DF_WB(15); DF_WB(11); DF_WB(16); DF_WB(32); DF_WB(64);
-    default: return df::fail(DF_EINVAL, "df_debug_wino_conv_fwd_bf16x3: unknown debug variant");
-  }
-#undef DF_WB
-  return df::launched("df_debug_wino_conv_fwd_bf16x3");
-}
-#endif
 
 int64_t df_wino_packed_elems(int64_t cin, int64_t cout, int mode) {
   (void)mode;
@@ -1424,274 +1191,74 @@ int df_wino_pack_weights(const float* w, float* wp, int64_t cin, int64_t cout, i
   return df::launched("df_wino_pack_weights");
 }
 
-static int64_t wino_grid(WinoArgs& a, int64_t ntb) {
-  // persistent workers: one workgroup per CU (a workgroup owns a CU's whole register file and most of its LDS)
-  int64_t grid = df::kCUs;
-  a.spx = 1;
-  if (8 % a.ncs == 0) {
-    a.spx = (g_wino_spx > 0 && a.ncs % g_wino_spx == 0) ? g_wino_spx : (a.ncs % 2 == 0 ? 2 : 1);
-    const int xpg = a.ncs / a.spx, ngroups = 8 / xpg;
-    const int64_t need = ceil_div(ntb, ngroups) * a.spx * 8;      // workers that get at least one tile block
-    if (need < grid) grid = need;
-    if ((grid >> 3) % a.spx) grid = ((grid >> 3) / a.spx + 1) * a.spx * 8;
-    if (grid > df::kCUs) grid = df::kCUs;
-  } else {
-    grid = (grid / a.ncs) * a.ncs;
-    if (ntb * a.ncs < grid) grid = ntb * a.ncs;
-  }
-  return grid;
-}
-
-int df_wino_conv_fwd(const float* x, const float* wp, const float* bias, const float* residual, const float* mask_src,
-                     float* y, int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int flags, float leak,
-                     df_stream_t stream) {
-  DF_REQUIRE(x && wp && y, DF_EINVAL, "df_wino_conv_fwd: null pointer");
-  DF_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, DF_EINVAL, "df_wino_conv_fwd: non-positive extent");
-  DF_REQUIRE(Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0, DF_ESHAPE,
-             "df_wino_conv_fwd: Cin, Cout must be multiples of 32 (use df_conv_fwd otherwise)");
-  // (staging goes through 32-bit byte offsets into one batch volume, with 0x80000000 as the out-of-range sentinel)
-  DF_REQUIRE(D * H * W * (Cin > Cout ? Cin : Cout) <= (1LL << 29) && Cin * Cout <= (1LL << 24), DF_ESHAPE,
-             "df_wino_conv_fwd: one batch volume must stay below 2 GiB (use df_conv_fwd)");
-  DF_REQUIRE(!(flags & DF_CONV_ADDUP), DF_EINVAL, "df_wino_conv_fwd: DF_CONV_ADDUP needs df_wino_conv_fwd_addup");
-  DF_REQUIRE(!(flags & DF_CONV_BIAS) || bias, DF_EINVAL, "df_wino_conv_fwd: DF_CONV_BIAS without bias");
-  DF_REQUIRE(!(flags & DF_CONV_RESIDUAL) || residual, DF_EINVAL, "df_wino_conv_fwd: DF_CONV_RESIDUAL without residual");
-  DF_REQUIRE(!(flags & DF_CONV_MASK) || mask_src, DF_EINVAL, "df_wino_conv_fwd: DF_CONV_MASK without mask_src");
-  DF_REQUIRE(df::aligned16(wp) && df::aligned16(x) && df::aligned16(y), DF_EALIGN, "df_wino_conv_fwd: x, y and packed weights must be 16-byte aligned");
-  WinoArgs a;
-  a.x = x; a.wp = reinterpret_cast<const f32x4*>(wp); a.zeros = wp + 64 * Cin * Cout;
-  a.bias = bias; a.residual = residual; a.mask_src = mask_src; a.y = y; a.y2 = nullptr; a.bits_out = nullptr; a.bits_in = nullptr;
-  a.B = (int)B; a.D = (int)D; a.H = (int)H; a.W = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout;
-  a.nbz = (int)ceil_div(D, 4); a.nby = (int)ceil_div(H, 8); a.nbx = (int)ceil_div(W, 8);
-  const int64_t ntb = B * a.nbz * a.nby * a.nbx;
-  a.ncs = (int)(Cout / 32);
-  DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "df_wino_conv_fwd: too many workgroups");
-  a.ntb = (int)ntb;
-  a.flags = flags; a.leak = leak;
-  const int64_t grid = wino_grid(a, ntb);
-#ifdef DF_TUNING
-  const int variant = g_wino_dbg >> 2;
-#else
-  constexpr int variant = 0;
-#endif
-  switch (variant) {
-    case 0:
-      if (flags == (DF_CONV_BIAS | DF_CONV_LRELU)) hipLaunchKernelGGL((wino3d_kernel<0, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a);
-      else if (flags == DF_CONV_MASK) hipLaunchKernelGGL((wino3d_kernel<0, DF_CONV_MASK>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a);
-      else if (flags == DF_CONV_RESIDUAL) hipLaunchKernelGGL((wino3d_kernel<0, DF_CONV_RESIDUAL>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a);
-      else if (flags == 0) hipLaunchKernelGGL((wino3d_kernel<0, 0>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a);
-      else hipLaunchKernelGGL((wino3d_kernel<0, -1>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a);
-      break;
-#ifdef DF_TUNING
-    case 1: hipLaunchKernelGGL((wino3d_kernel<1, -1>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 2: hipLaunchKernelGGL((wino3d_kernel<2, -1>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 3: hipLaunchKernelGGL((wino3d_kernel<3, -1>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 7: hipLaunchKernelGGL((wino3d_kernel<7, -1>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 272: hipLaunchKernelGGL((wino3d_kernel<272, -1>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 16:      // cycle profile (df_debug_wino_prof) of the SPECIALISED epilogues where they exist
-      if (flags == (DF_CONV_BIAS | DF_CONV_LRELU)) hipLaunchKernelGGL((wino3d_kernel<16, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a);
-      else if (flags == DF_CONV_MASK) hipLaunchKernelGGL((wino3d_kernel<16, DF_CONV_MASK>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a);
-      else hipLaunchKernelGGL((wino3d_kernel<16, -1>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a);
-      break;
-    // diagnosis variants (results are wrong by construction, timing only): 4 no staging at all | 8 no weight loads | 64 staging loads
-    // kept alive but not written to LDS | 128 staging loads replaced by zeros | 256 staging loads read an always-cached address
-    case 4: hipLaunchKernelGGL((wino3d_kernel<4, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 8: hipLaunchKernelGGL((wino3d_kernel<8, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 12: hipLaunchKernelGGL((wino3d_kernel<12, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 64: hipLaunchKernelGGL((wino3d_kernel<64, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 128: hipLaunchKernelGGL((wino3d_kernel<128, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 256: hipLaunchKernelGGL((wino3d_kernel<256, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 512: hipLaunchKernelGGL((wino3d_kernel<512, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 9: hipLaunchKernelGGL((wino3d_kernel<9, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 384: hipLaunchKernelGGL((wino3d_kernel<384, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;      // staging loads confined to a 1 MB window (L2-resident, L1 misses)
-    case 100: hipLaunchKernelGGL((wino3d_kernel<0, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;      // production kernel, compile-time flags (baseline of the experiments)
-    case 4194304: hipLaunchKernelGGL((wino3d_kernel<4194304, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 1048576: hipLaunchKernelGGL((wino3d_kernel<1048576, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 2097152: hipLaunchKernelGGL((wino3d_kernel<2097152, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 262144: hipLaunchKernelGGL((wino3d_kernel<262144, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case 524288: hipLaunchKernelGGL((wino3d_kernel<524288, DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-    case (262144 | 4): hipLaunchKernelGGL((wino3d_kernel<(262144 | 4), DF_CONV_BIAS | DF_CONV_LRELU>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); break;
-#endif
-    default: return df::fail(DF_EINVAL, "df_wino_conv_fwd: unknown debug variant");
-  }
-  return df::launched("df_wino_conv_fwd");
-}
-
-int df_wino_upconv_fwd(const float* xc, const float* wp, const float* bias, float* y, int64_t B, int64_t Dc, int64_t Hc,
-                       int64_t Wc, int64_t Cin, int64_t Cout, int flags, float leak, df_stream_t stream) {
-  DF_REQUIRE(xc && wp && y, DF_EINVAL, "df_wino_upconv_fwd: null pointer");
-  DF_REQUIRE(B > 0 && Dc > 0 && Hc > 0 && Wc > 0, DF_EINVAL, "df_wino_upconv_fwd: non-positive extent");
-  DF_REQUIRE(Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0, DF_ESHAPE,
-             "df_wino_upconv_fwd: Cin, Cout must be multiples of 32 (use df_upconv_fwd otherwise)");
-  DF_REQUIRE(flags == (DF_CONV_BIAS | DF_CONV_LRELU) && bias, DF_EINVAL, "df_wino_upconv_fwd: flags must be DF_CONV_BIAS | DF_CONV_LRELU");
-  DF_REQUIRE(8 * Dc * Hc * Wc * Cout <= (1LL << 29) && Dc * Hc * Wc * Cin <= (1LL << 29) && Cin * Cout <= (1LL << 24), DF_ESHAPE,
-             "df_wino_upconv_fwd: one batch volume must stay below 2 GiB (use df_upconv_fwd)");
-  DF_REQUIRE(df::aligned16(wp) && df::aligned16(xc) && df::aligned16(y), DF_EALIGN, "df_wino_upconv_fwd: xc, y and packed weights must be 16-byte aligned");
-  WinoArgs a;
-  a.x = xc; a.wp = reinterpret_cast<const f32x4*>(wp); a.zeros = wp + 64 * Cin * Cout;
-  a.bias = bias; a.residual = nullptr; a.mask_src = nullptr; a.y = y; a.y2 = nullptr; a.bits_out = nullptr; a.bits_in = nullptr;
-  a.B = (int)B; a.D = (int)(2 * Dc); a.H = (int)(2 * Hc); a.W = (int)(2 * Wc); a.Cin = (int)Cin; a.Cout = (int)Cout;      // OUTPUT (fine) extents
-  a.nbz = (int)ceil_div(a.D, 4); a.nby = (int)ceil_div(a.H, 8); a.nbx = (int)ceil_div(a.W, 8);
-  const int64_t ntb = B * a.nbz * a.nby * a.nbx;
-  a.ncs = (int)(Cout / 32);
-  DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "df_wino_upconv_fwd: too many workgroups");
-  a.ntb = (int)ntb;
-  a.flags = flags; a.leak = leak;
-  const int64_t grid = wino_grid(a, ntb);
-#ifdef DF_TUNING      // round-5 breakdown of the 27-point form (tools/r05_breakdown_probe.py; results wrong by construction, timing only)
-#define DF_WU(V) case V: hipLaunchKernelGGL((wino3d_kernel<V, DF_CONV_BIAS | DF_CONV_LRELU, 3>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); return df::launched("df_wino_upconv_fwd")
-#define DF_WU1(V) case 1000 + V: hipLaunchKernelGGL((wino3d_kernel<V, DF_CONV_BIAS | DF_CONV_LRELU, 1>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); return df::launched("df_wino_upconv_fwd")
-  switch (g_wino_dbg >> 2) {      // V: coarse-block staging (MODE 3, production); 1000 + V: the fine-grid staging of rounds 2-4 (MODE 1)
-    DF_WU(1); DF_WU(2); DF_WU(3); DF_WU(4); DF_WU(7); DF_WU(8); DF_WU(64); DF_WU(128); DF_WU(512);
-    DF_WU1(0); DF_WU1(1); DF_WU1(2); DF_WU1(3); DF_WU1(4); DF_WU1(7); DF_WU1(8); DF_WU1(64); DF_WU1(128); DF_WU1(512);
-    default: break;
-  }
-#undef DF_WU
-#undef DF_WU1
-#endif
-  hipLaunchKernelGGL((wino3d_kernel<0, DF_CONV_BIAS | DF_CONV_LRELU, 3>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a);
-  return df::launched("df_wino_upconv_fwd");
-}
-
 int64_t df_wino_signbits_bytes(int64_t B, int64_t D, int64_t H, int64_t W, int64_t C) {
   if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 32) return 0;
   return B * ceil_div(D, 4) * ceil_div(H, 8) * ceil_div(W, 8) * (C / 32) * kBitBytesPerBlock;
 }
 
+int df_wino_conv_fwd(const float* x, const float* wp, const float* bias, const float* residual, const float* mask_src,
+                     float* y, int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int flags, float leak,
+                     df_stream_t stream) {
+  const WinoOps o = {x, wp, bias, residual, mask_src, y, nullptr, nullptr, nullptr};
+  const bool ok = !(flags & DF_CONV_ADDUP) && (!(flags & DF_CONV_BIAS) || bias) && (!(flags & DF_CONV_RESIDUAL) || residual) &&
+                  (!(flags & DF_CONV_MASK) || mask_src);
+  if (const int rc = wino_check(kFwd, o, B, D, H, W, Cin, Cout, ok,
+                                "DF_CONV_BIAS / RESIDUAL / MASK need bias / residual / mask_src; DF_CONV_ADDUP needs df_wino_conv_fwd_addup"))
+    return rc;
+  // the flag combinations with an epilogue of their own; every other one runs the kernel that tests a.flags per element
+  const bool special = flags == (DF_CONV_BIAS | DF_CONV_LRELU) || flags == DF_CONV_MASK || flags == DF_CONV_RESIDUAL || flags == 0;
+  return wino_launch(kFwd.name, special ? flags : -1, 0, o, B, D, H, W, Cin, Cout, flags, leak, stream);
+}
+
 int df_wino_conv_fwd_bits(const float* x, const float* wp, const float* bias, const void* mask_bits, float* y, void* sign_bits, int64_t B,
                           int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int flags, float leak, df_stream_t stream) {
-  DF_REQUIRE(x && wp && y, DF_EINVAL, "df_wino_conv_fwd_bits: null pointer");
-  DF_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, DF_EINVAL, "df_wino_conv_fwd_bits: non-positive extent");
-  DF_REQUIRE(Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0, DF_ESHAPE, "df_wino_conv_fwd_bits: Cin, Cout must be multiples of 32");
-  DF_REQUIRE(D * H * W * (Cin > Cout ? Cin : Cout) <= (1LL << 29) && Cin * Cout <= (1LL << 24), DF_ESHAPE,
-             "df_wino_conv_fwd_bits: one batch volume must stay below 2 GiB");
+  const WinoOps o = {x, wp, bias, nullptr, nullptr, y, nullptr, sign_bits, mask_bits};
   const bool fwd = flags == (DF_CONV_BIAS | DF_CONV_LRELU) && bias && sign_bits && !mask_bits;
   const bool dgr = flags == DF_CONV_MASK && mask_bits && !sign_bits;
-  DF_REQUIRE(fwd || dgr, DF_EINVAL, "df_wino_conv_fwd_bits: either (BIAS|LRELU, bias, sign_bits out) or (MASK, mask_bits in)");
-  DF_REQUIRE(df::aligned16(wp) && df::aligned16(x) && df::aligned16(y) && df::aligned16(mask_bits) && df::aligned16(sign_bits), DF_EALIGN,
-             "df_wino_conv_fwd_bits: x, y, packed weights and bit words must be 16-byte aligned");
-  WinoArgs a;
-  a.x = x; a.wp = reinterpret_cast<const f32x4*>(wp); a.zeros = wp + 64 * Cin * Cout;
-  a.bias = bias; a.residual = nullptr; a.mask_src = nullptr; a.y = y; a.y2 = nullptr;
-  a.bits_out = static_cast<unsigned char*>(sign_bits); a.bits_in = static_cast<const unsigned char*>(mask_bits);
-  a.B = (int)B; a.D = (int)D; a.H = (int)H; a.W = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout;
-  a.nbz = (int)ceil_div(D, 4); a.nby = (int)ceil_div(H, 8); a.nbx = (int)ceil_div(W, 8);
-  const int64_t ntb = B * a.nbz * a.nby * a.nbx;
-  a.ncs = (int)(Cout / 32);
-  DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "df_wino_conv_fwd_bits: too many workgroups");
-  a.ntb = (int)ntb;
-  a.flags = flags; a.leak = leak;
-  const int64_t grid = wino_grid(a, ntb);
-  if (fwd) hipLaunchKernelGGL((wino3d_kernel<0, DF_CONV_BIAS | DF_CONV_LRELU | kSignBits>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a);
-  else hipLaunchKernelGGL((wino3d_kernel<0, DF_CONV_MASK | kMaskBits>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a);
-  return df::launched("df_wino_conv_fwd_bits");
-}
-
-int df_wino_upconv_fwd_bits(const float* xc, const float* wp, const float* bias, float* y, void* sign_bits, int64_t B, int64_t Dc,
-                            int64_t Hc, int64_t Wc, int64_t Cin, int64_t Cout, float leak, df_stream_t stream) {
-  DF_REQUIRE(xc && wp && y && bias && sign_bits, DF_EINVAL, "df_wino_upconv_fwd_bits: null pointer");
-  DF_REQUIRE(B > 0 && Dc > 0 && Hc > 0 && Wc > 0, DF_EINVAL, "df_wino_upconv_fwd_bits: non-positive extent");
-  DF_REQUIRE(Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0, DF_ESHAPE, "df_wino_upconv_fwd_bits: Cin, Cout must be multiples of 32");
-  DF_REQUIRE(8 * Dc * Hc * Wc * Cout <= (1LL << 29) && Dc * Hc * Wc * Cin <= (1LL << 29) && Cin * Cout <= (1LL << 24), DF_ESHAPE,
-             "df_wino_upconv_fwd_bits: one batch volume must stay below 2 GiB");
-  DF_REQUIRE(df::aligned16(wp) && df::aligned16(xc) && df::aligned16(y) && df::aligned16(sign_bits), DF_EALIGN,
-             "df_wino_upconv_fwd_bits: xc, y, packed weights and bit words must be 16-byte aligned");
-  WinoArgs a;
-  a.x = xc; a.wp = reinterpret_cast<const f32x4*>(wp); a.zeros = wp + 64 * Cin * Cout;
-  a.bias = bias; a.residual = nullptr; a.mask_src = nullptr; a.y = y; a.y2 = nullptr;
-  a.bits_out = static_cast<unsigned char*>(sign_bits); a.bits_in = nullptr;
-  a.B = (int)B; a.D = (int)(2 * Dc); a.H = (int)(2 * Hc); a.W = (int)(2 * Wc); a.Cin = (int)Cin; a.Cout = (int)Cout;
-  a.nbz = (int)ceil_div(a.D, 4); a.nby = (int)ceil_div(a.H, 8); a.nbx = (int)ceil_div(a.W, 8);
-  const int64_t ntb = B * a.nbz * a.nby * a.nbx;
-  a.ncs = (int)(Cout / 32);
-  DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "df_wino_upconv_fwd_bits: too many workgroups");
-  a.ntb = (int)ntb;
-  a.flags = DF_CONV_BIAS | DF_CONV_LRELU; a.leak = leak;
-  const int64_t grid = wino_grid(a, ntb);
-  hipLaunchKernelGGL((wino3d_kernel<0, DF_CONV_BIAS | DF_CONV_LRELU | kSignBits, 3>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a);
-  return df::launched("df_wino_upconv_fwd_bits");
-}
-
-int df_wino_upconv_dgrad(const float* g, const float* wp, float* acc, int64_t B, int64_t Dc, int64_t Hc, int64_t Wc, int64_t Cin,
-                         int64_t Cout, df_stream_t stream) {
-  DF_REQUIRE(g && wp && acc, DF_EINVAL, "df_wino_upconv_dgrad: null pointer");
-  DF_REQUIRE(B > 0 && Dc > 0 && Hc > 0 && Wc > 0, DF_EINVAL, "df_wino_upconv_dgrad: non-positive extent");
-  DF_REQUIRE(Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0, DF_ESHAPE,
-             "df_wino_upconv_dgrad: Cin, Cout must be multiples of 32 (use df_upconv_dgrad otherwise)");
-  DF_REQUIRE(8 * Dc * Hc * Wc * (Cin > Cout ? Cin : Cout) <= (1LL << 29) && Cin * Cout <= (1LL << 24), DF_ESHAPE,
-             "df_wino_upconv_dgrad: one batch volume must stay below 2 GiB (use df_upconv_dgrad)");
-  DF_REQUIRE(df::aligned16(wp) && df::aligned16(g), DF_EALIGN, "df_wino_upconv_dgrad: g and packed weights must be 16-byte aligned");
-  WinoArgs a;      // the adjoint conv reads g (Cout channels, fine grid) and produces Cin channels
-  a.x = g; a.wp = reinterpret_cast<const f32x4*>(wp); a.zeros = wp + 64 * Cin * Cout;
-  a.bias = nullptr; a.residual = nullptr; a.mask_src = nullptr; a.y = acc; a.y2 = nullptr; a.bits_out = nullptr; a.bits_in = nullptr;
-  a.B = (int)B; a.D = (int)(2 * Dc); a.H = (int)(2 * Hc); a.W = (int)(2 * Wc); a.Cin = (int)Cout; a.Cout = (int)Cin;
-  a.nbz = (int)ceil_div(a.D, 4); a.nby = (int)ceil_div(a.H, 8); a.nbx = (int)ceil_div(a.W, 8);
-  const int64_t ntb = B * a.nbz * a.nby * a.nbx;
-  a.ncs = (int)(Cin / 32);
-  DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "df_wino_upconv_dgrad: too many workgroups");
-  a.ntb = (int)ntb;
-  a.flags = 0; a.leak = 0.f;
-  const int64_t grid = wino_grid(a, ntb);
-#ifdef DF_TUNING
-#define DF_WP(V) case V: hipLaunchKernelGGL((wino3d_kernel<V, 0, 2>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a); return df::launched("df_wino_upconv_dgrad")
-  switch (g_wino_dbg >> 2) {
-    DF_WP(1); DF_WP(2); DF_WP(3); DF_WP(4); DF_WP(7); DF_WP(8); DF_WP(64); DF_WP(128);
-    default: break;
-  }
-#undef DF_WP
-#endif
-  hipLaunchKernelGGL((wino3d_kernel<0, 0, 2>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a);
-  return df::launched("df_wino_upconv_dgrad");
+  if (const int rc = wino_check(kFwdBits, o, B, D, H, W, Cin, Cout, fwd || dgr, "either (BIAS|LRELU, bias, sign_bits out) or (MASK, mask_bits in)"))
+    return rc;
+  return wino_launch(kFwdBits.name, fwd ? flags | kSignBits : flags | kMaskBits, 0, o, B, D, H, W, Cin, Cout, flags, leak, stream);
 }
 
 int df_wino_conv_fwd_addup(const float* x, const float* wp, const float* bias, const float* xc, float* y, float* y2, int64_t B,
                            int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, float leak, df_stream_t stream) {
-  DF_REQUIRE(x && wp && bias && xc && y && y2, DF_EINVAL, "df_wino_conv_fwd_addup: null pointer");
-  DF_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && D % 2 == 0 && H % 2 == 0 && W % 2 == 0, DF_EINVAL,
-             "df_wino_conv_fwd_addup: extents must be positive and even (the output of a 2x up-sampling block)");
-  DF_REQUIRE(Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0, DF_ESHAPE, "df_wino_conv_fwd_addup: Cin, Cout must be multiples of 32");
-  DF_REQUIRE(D * H * W * (Cin > Cout ? Cin : Cout) <= (1LL << 29) && Cin * Cout <= (1LL << 24), DF_ESHAPE,
-             "df_wino_conv_fwd_addup: one batch volume must stay below 2 GiB");
-  DF_REQUIRE(df::aligned16(wp) && df::aligned16(x), DF_EALIGN, "df_wino_conv_fwd_addup: x and packed weights must be 16-byte aligned");
-  WinoArgs a;
-  a.x = x; a.wp = reinterpret_cast<const f32x4*>(wp); a.zeros = wp + 64 * Cin * Cout;
-  a.bias = bias; a.residual = xc; a.mask_src = nullptr; a.y = y; a.y2 = y2; a.bits_out = nullptr; a.bits_in = nullptr;
-  a.B = (int)B; a.D = (int)D; a.H = (int)H; a.W = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout;
-  a.nbz = (int)ceil_div(D, 4); a.nby = (int)ceil_div(H, 8); a.nbx = (int)ceil_div(W, 8);
-  const int64_t ntb = B * a.nbz * a.nby * a.nbx;
-  a.ncs = (int)(Cout / 32);
-  DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "df_wino_conv_fwd_addup: too many workgroups");
-  a.ntb = (int)ntb;
-  a.flags = DF_CONV_BIAS | DF_CONV_LRELU | DF_CONV_ADDUP; a.leak = leak;
-  const int64_t grid = wino_grid(a, ntb);
-  hipLaunchKernelGGL((wino3d_kernel<0, DF_CONV_BIAS | DF_CONV_LRELU | DF_CONV_ADDUP>), dim3((unsigned)grid), dim3(kT), 0, df::as_stream(stream), a);
-  return df::launched("df_wino_conv_fwd_addup");
+  const WinoOps o = {x, wp, bias, xc, nullptr, y, y2, nullptr, nullptr};
+  if (const int rc = wino_check(kAddup, o, B, D, H, W, Cin, Cout, true, "")) return rc;
+  constexpr int F = DF_CONV_BIAS | DF_CONV_LRELU | DF_CONV_ADDUP;
+  return wino_launch(kAddup.name, F, 0, o, B, D, H, W, Cin, Cout, F, leak, stream);
 }
 
 int df_wino_conv_fwd_addup_bits(const float* x, const float* wp, const float* bias, const float* xc, float* y2, void* sign_bits,
                                 int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, float leak, df_stream_t stream) {
-  DF_REQUIRE(x && wp && bias && xc && y2 && sign_bits, DF_EINVAL, "df_wino_conv_fwd_addup_bits: null pointer");
-  DF_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && D % 2 == 0 && H % 2 == 0 && W % 2 == 0, DF_EINVAL,
-             "df_wino_conv_fwd_addup_bits: extents must be positive and even (the output of a 2x up-sampling block)");
-  DF_REQUIRE(Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0, DF_ESHAPE, "df_wino_conv_fwd_addup_bits: Cin, Cout must be multiples of 32");
-  DF_REQUIRE(D * H * W * (Cin > Cout ? Cin : Cout) <= (1LL << 29) && Cin * Cout <= (1LL << 24), DF_ESHAPE,
-             "df_wino_conv_fwd_addup_bits: one batch volume must stay below 2 GiB");
-  DF_REQUIRE(df::aligned16(wp) && df::aligned16(x) && df::aligned16(sign_bits), DF_EALIGN,
-             "df_wino_conv_fwd_addup_bits: x, packed weights and bit words must be 16-byte aligned");
-  WinoArgs a;
-  a.x = x; a.wp = reinterpret_cast<const f32x4*>(wp); a.zeros = wp + 64 * Cin * Cout;
-  a.bias = bias; a.residual = xc; a.mask_src = nullptr; a.y = nullptr; a.y2 = y2;
-  a.bits_out = static_cast<unsigned char*>(sign_bits); a.bits_in = nullptr;
-  a.B = (int)B; a.D = (int)D; a.H = (int)H; a.W = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout;
-  a.nbz = (int)ceil_div(D, 4); a.nby = (int)ceil_div(H, 8); a.nbx = (int)ceil_div(W, 8);
-  const int64_t ntb = B * a.nbz * a.nby * a.nbx;
-  a.ncs = (int)(Cout / 32);
-  DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "df_wino_conv_fwd_addup_bits: too many workgroups");
-  a.ntb = (int)ntb;
-  a.flags = DF_CONV_BIAS | DF_CONV_LRELU | DF_CONV_ADDUP; a.leak = leak;
-  const int64_t grid = wino_grid(a, ntb);
-  hipLaunchKernelGGL((wino3d_kernel<0, DF_CONV_BIAS | DF_CONV_LRELU | DF_CONV_ADDUP | kSignBits | kNoPrimary>), dim3((unsigned)grid), dim3(kT), 0,
-                     df::as_stream(stream), a);
-  return df::launched("df_wino_conv_fwd_addup_bits");
+  const WinoOps o = {x, wp, bias, xc, nullptr, nullptr, y2, sign_bits, nullptr};
+  if (const int rc = wino_check(kAddupBits, o, B, D, H, W, Cin, Cout, true, "")) return rc;
+  constexpr int F = DF_CONV_BIAS | DF_CONV_LRELU | DF_CONV_ADDUP;
+  return wino_launch(kAddupBits.name, F | kSignBits | kNoPrimary, 0, o, B, D, H, W, Cin, Cout, F, leak, stream);
+}
+
+int df_wino_upconv_fwd(const float* xc, const float* wp, const float* bias, float* y, int64_t B, int64_t Dc, int64_t Hc,
+                       int64_t Wc, int64_t Cin, int64_t Cout, int flags, float leak, df_stream_t stream) {
+  const WinoOps o = {xc, wp, bias, nullptr, nullptr, y, nullptr, nullptr, nullptr};
+  if (const int rc = wino_check(kUpFwd, o, B, Dc, Hc, Wc, Cin, Cout, flags == (DF_CONV_BIAS | DF_CONV_LRELU) && bias,
+                                "flags must be DF_CONV_BIAS | DF_CONV_LRELU, with bias"))
+    return rc;
+  return wino_launch(kUpFwd.name, flags, 3, o, B, 2 * Dc, 2 * Hc, 2 * Wc, Cin, Cout, flags, leak, stream);
+}
+
+int df_wino_upconv_fwd_bits(const float* xc, const float* wp, const float* bias, float* y, void* sign_bits, int64_t B, int64_t Dc,
+                            int64_t Hc, int64_t Wc, int64_t Cin, int64_t Cout, float leak, df_stream_t stream) {
+  const WinoOps o = {xc, wp, bias, nullptr, nullptr, y, nullptr, sign_bits, nullptr};
+  if (const int rc = wino_check(kUpFwdBits, o, B, Dc, Hc, Wc, Cin, Cout, true, "")) return rc;
+  constexpr int F = DF_CONV_BIAS | DF_CONV_LRELU;
+  return wino_launch(kUpFwdBits.name, F | kSignBits, 3, o, B, 2 * Dc, 2 * Hc, 2 * Wc, Cin, Cout, F, leak, stream);
+}
+
+int df_wino_upconv_dgrad(const float* g, const float* wp, float* acc, int64_t B, int64_t Dc, int64_t Hc, int64_t Wc, int64_t Cin,
+                         int64_t Cout, df_stream_t stream) {
+  const WinoOps o = {g, wp, nullptr, nullptr, nullptr, acc, nullptr, nullptr, nullptr};
+  if (const int rc = wino_check(kUpDgrad, o, B, Dc, Hc, Wc, Cin, Cout, true, "")) return rc;
+  // the adjoint conv reads g (Cout channels, fine grid) and produces Cin channels: the kernel's Cin / Cout are the entry point's Cout / Cin
+  return wino_launch(kUpDgrad.name, 0, 2, o, B, 2 * Dc, 2 * Hc, 2 * Wc, Cout, Cin, 0, 0.f, stream);
 }
 
 int df_lrelu_bits_bwd_pool2x(const float* gy, const void* mask_bits, float* gx, float* gpool, float leak, int64_t B, int64_t Dc, int64_t Hc,

@@ -152,14 +152,10 @@ __device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
 }
 
 // FL >= 0: the epilogue flags are the compile-time constant FL; FL < 0: run-time a.flags (public DF_CONV_* bits only)
-// DBG (probe build -DDF_W43_PROBE only, results wrong by construction): 1 no input transform, 2 no LDS operand reads, 4 no staging,
-// 8 no weight reloads, 64 staging loads kept but nothing written to LDS, 128 staged zeros (z transform + LDS writes, no loads)
-// -- tools/r06_wino43_probe.py's time breakdown
-template <int FL, int DBG = 0>
+// (Until commit 2f63d5b a DBG argument and a -DDF_W43_PROBE build held the timing variants of tools/archive/r06_wino43_probe.py -- no transform /
+//  LDS reads / staging / weight reloads -- and probe macros a second weight register set and other slice counts per XCD: profiles/r06_probes.md.)
+template <int FL>
 __global__ __launch_bounds__(kT, 1) void wino43_kernel(const W43Args a) {
-#ifndef DF_W43_PROBE
-  static_assert(DBG == 0, "wino43_kernel: probe variants exist in the -DDF_W43_PROBE build only");
-#endif
   __shared__ __attribute__((aligned(16))) float sIn[2 * BUFF];
   __shared__ __attribute__((aligned(16))) float sXc[8192];      // second exchange area (32 KB): the (y, x)-complete partials per xi_z
   __shared__ float sBias[32];
@@ -295,11 +291,7 @@ __global__ __launch_bounds__(kT, 1) void wino43_kernel(const W43Args a) {
 
   // ---- B operand: three float4 per lane and cout block = its 12 points --------------------------------------------------------------------
   const int nk4 = a.Cin >> 2;
-#ifndef W43_NBQ
-#define W43_NBQ 1      // 2: two weight register sets (even / odd k-steps), every reload two k-steps ahead
-#endif
-  constexpr int NBQ = W43_NBQ;
-  f32x4 bq[NBQ][2][3];
+  f32x4 bq[2][3];          // [cout 16-block] = its 12 points
   const unsigned laneb = static_cast<unsigned>(lane) * 48u;
   const __amdgpu_buffer_rsrc_t wsrd = make_srd(a.wp, static_cast<unsigned>(a.Cin) * a.Cout * (kPts * 4u));
   const unsigned wbase_b = static_cast<unsigned>(((cs * 4 + mz) * 2 + yh) * nk4) * 6144u;
@@ -307,7 +299,7 @@ __global__ __launch_bounds__(kT, 1) void wino43_kernel(const W43Args a) {
     const int kl = k4 < nk4 ? k4 : 0;
     const unsigned sb = wbase_b + static_cast<unsigned>(kl) * 6144u + nb * 3072u;
 #pragma unroll
-    for (int q = 0; q < 3; ++q) bq[k4 & (NBQ - 1)][nb][q] = buf_load16(wsrd, laneb + q * 16u, sb);
+    for (int q = 0; q < 3; ++q) bq[nb][q] = buf_load16(wsrd, laneb + q * 16u, sb);
   };
 
   f32x4 acc[2][12];
@@ -330,14 +322,7 @@ __global__ __launch_bounds__(kT, 1) void wino43_kernel(const W43Args a) {
 #pragma unroll
       for (int i = 0; i < 12; ++i) acc[nb][i] = f32x4{0.f, 0.f, 0.f, 0.f};
     raw_read(pb * BUFF * 4);
-    if (DBG & 1) {
-#pragma unroll
-      for (int i = 0; i < 12; ++i) Av[i] = ra[i % 9][0] + static_cast<float>(i);
-    }
-    if (itb == 0) {
-      issue_b(0, 0); issue_b(1, 0);
-      if (NBQ == 2) { issue_b(0, 1); issue_b(1, 1); }
-    }      // (later blocks: the last k-step of the previous block reloaded k-step 0's weights)
+    if (itb == 0) { issue_b(0, 0); issue_b(1, 0); }      // (later blocks: the last k-step of the previous block reloaded k-step 0's weights)
 
     for (int chunk = 0; chunk < nchunk; ++chunk) {
       const int bo = ((chunk + pb) & 1) * BUFF * 4, bn = BUFF * 4 - bo;
@@ -347,41 +332,27 @@ __global__ __launch_bounds__(kT, 1) void wino43_kernel(const W43Args a) {
       f32x4 stg[6];
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        if (!(DBG & 1)) transform();
+        transform();
         __builtin_amdgcn_sched_barrier(0);
-        if (ks == 2 && !(DBG & 4) && stager) {
-          if (DBG & 64) {      // (probe: the loads stay alive, nothing is written)
-#pragma unroll
-            for (int z = 0; z < 6; ++z) asm volatile("" :: "v"(stg[z]));
-          } else {
-            stage_store(bn, stg);
-          }
-        }
+        if (ks == 2 && stager) stage_store(bn, stg);
         if (ks == 3) lds_barrier();
-        if (!(DBG & 2)) raw_read(ks < 3 ? bo + (ks + 1) * 16 * CP : bn);
+        raw_read(ks < 3 ? bo + (ks + 1) * 16 * CP : bn);
         __builtin_amdgcn_sched_barrier(0);
-        const int k4n = chunk * 4 + ks + NBQ;
-        const unsigned sbn = wbase_b + static_cast<unsigned>(k4n < nk4 ? k4n : k4n - nk4) * 6144u;      // wraps to the next block's first k-step(s)
+        const int k4n = chunk * 4 + ks + 1;
+        const unsigned sbn = wbase_b + static_cast<unsigned>(k4n < nk4 ? k4n : k4n - nk4) * 6144u;      // wraps to the next block's first k-step
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
 #pragma unroll
           for (int i = 0; i < 12; ++i) {
-            acc[nb][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(Av[i], bq[ks & (NBQ - 1)][nb][i >> 2][i & 3], acc[nb][i], 0, 0, 0);
+            acc[nb][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(Av[i], bq[nb][i >> 2][i & 3], acc[nb][i], 0, 0, 0);
             if ((i & 3) == 3) {      // this quad's four products are issued: reload it with the next k-step's weights
               __builtin_amdgcn_sched_barrier(0);
-              if (!(DBG & 8)) bq[ks & (NBQ - 1)][nb][i >> 2] = buf_load16(wsrd, laneb + (i >> 2) * 16u, sbn + nb * 3072u);
+              bq[nb][i >> 2] = buf_load16(wsrd, laneb + (i >> 2) * 16u, sbn + nb * 3072u);
               __builtin_amdgcn_sched_barrier(0);
             }
           }
         }
-        if (ks == 0 && !(DBG & 4) && stager) {      // the next chunk's z columns, behind a weight batch
-          if (DBG & 128) {      // (probe: staged zeros -- the z transform and the LDS writes without the loads)
-#pragma unroll
-            for (int z = 0; z < 6; ++z) stg[z] = f32x4{0.f, 0.f, 0.f, 0.f};
-          } else {
-            stage_load(lastc ? nxt : cur, schunk, stg);
-          }
-        }
+        if (ks == 0 && stager) stage_load(lastc ? nxt : cur, schunk, stg);      // the next chunk's z columns, behind a weight batch
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -527,26 +498,6 @@ __global__ __launch_bounds__(kT, 1) void wino43_kernel(const W43Args a) {
   }
 }
 
-int64_t w43_grid(W43Args& a, int64_t ntb) {
-  int64_t grid = df::kCUs;
-  a.spx = 1;
-  if (8 % a.ncs == 0) {
-#ifndef W43_SPX
-#define W43_SPX 2      // cout slices per XCD (probe builds: 1 | 2 | 4)
-#endif
-    a.spx = a.ncs % W43_SPX == 0 ? W43_SPX : (a.ncs % 2 == 0 ? 2 : 1);
-    const int xpg = a.ncs / a.spx, ngroups = 8 / xpg;
-    const int64_t need = ceil_div(ntb, ngroups) * a.spx * 8;
-    if (need < grid) grid = need;
-    if ((grid >> 3) % a.spx) grid = ((grid >> 3) / a.spx + 1) * a.spx * 8;
-    if (grid > df::kCUs) grid = df::kCUs;
-  } else {
-    grid = (grid / a.ncs) * a.ncs;
-    if (ntb * a.ncs < grid) grid = ntb * a.ncs;
-  }
-  return grid;
-}
-
 }  // namespace
 
 extern "C" {
@@ -595,7 +546,7 @@ int df_wino43_conv(const float* x, const float* wp, const float* bias, const flo
   DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "df_wino43_conv: too many workgroups");
   a.ntb = (int)ntb;
   a.flags = flags; a.leak = leak;
-  const int64_t grid = w43_grid(a, ntb);
+  const int64_t grid = dfconv::wino_grid(a, ntb);
   hipStream_t s = df::as_stream(stream);
   const int f = flags | (sign_bits ? kSignBits : 0) | (mask_bits ? kMaskBits : 0) | (!y ? kNoPrimary : 0);
 #define DF_W43(F) hipLaunchKernelGGL((wino43_kernel<F>), dim3((unsigned)grid), dim3(kT), 0, s, a)
@@ -615,24 +566,5 @@ int df_wino43_conv(const float* x, const float* wp, const float* bias, const flo
 #undef DF_W43
   return df::launched("df_wino43_conv");
 }
-
-#ifdef DF_W43_PROBE
-// probe build: df_wino43_conv(BIAS | LRELU) with a DBG variant (results wrong by construction unless dbg == 0)
-int df_wino43_probe(const float* x, const float* wp, const float* bias, float* y, int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin,
-                    int64_t Cout, float leak, int dbg, df_stream_t stream) {
-  W43Args a;
-  a.x = x; a.wp = wp; a.bias = bias; a.residual = nullptr; a.mask_src = nullptr; a.y = y; a.y2 = nullptr; a.bits_out = nullptr; a.bits_in = nullptr;
-  a.B = (int)B; a.D = (int)D; a.H = (int)H; a.W = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout;
-  a.nbz = (int)ceil_div(D, 4); a.nby = (int)ceil_div(H, 8); a.nbx = (int)ceil_div(W, 8);
-  const int64_t ntb = B * a.nbz * a.nby * a.nbx;
-  a.ncs = (int)(Cout / 32); a.ntb = (int)ntb; a.flags = 9; a.leak = leak;
-  const int64_t grid = w43_grid(a, ntb);
-  hipStream_t s = df::as_stream(stream);
-#define DF_P(V) case V: hipLaunchKernelGGL((wino43_kernel<9, V>), dim3((unsigned)grid), dim3(kT), 0, s, a); break
-  switch (dbg) { DF_P(0); DF_P(1); DF_P(2); DF_P(3); DF_P(4); DF_P(8); DF_P(7); DF_P(15); DF_P(12); DF_P(64); DF_P(128); default: return DF_EINVAL; }
-#undef DF_P
-  return df::launched("df_wino43_probe");
-}
-#endif
 
 }  // extern "C"

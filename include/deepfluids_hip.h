@@ -18,7 +18,7 @@
  *     aborts; a message for the calling thread's last failure is kept in df_last_error();
  *   - re-entrant; no global state besides read-only kernel handles: algorithm choices are call arguments
  *     (`algo`, DF_CONV_VALU_ONLY), never process-wide switches.  (Tuning builds, `make tuning` with -DDF_TUNING, add
- *     the instrumented kernels and knobs declared in deepfluids_hip_debug.h to a SEPARATE library; the release
+ *     the launch knobs and timing variants declared in deepfluids_hip_debug.h to a SEPARATE library; the release
  *     library exports exactly what this header declares.)
  */
 #ifndef DEEPFLUIDS_HIP_H

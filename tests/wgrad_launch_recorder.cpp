@@ -1,5 +1,5 @@
-// Launch recorder of tests/test_wgrad_launches_host.py: calls the weight-gradient entry points of libdeepfluids_hip.so WITHOUT a GPU and
-// prints what they would have launched.  No HIP header, no device: this executable itself defines every HIP runtime call the host path of
+// Launch recorder of tests/test_wgrad_launches_host.py and tests/test_wino_launches_host.py: calls the weight-gradient and the 3-D Winograd
+// entry points of libdeepfluids_hip.so WITHOUT a GPU and prints what they would have launched.  No HIP header, no device: this executable itself defines every HIP runtime call the host path of
 // csrc/conv_wgrad.hip makes (df_common.hpp, core.hip), and a symbol defined in the executable wins over the shared runtime's when the
 // library's calls are bound.  A launch arrives as hipLaunchKernel(kernel handle, grid, block, argument pointers, LDS bytes, stream);
 // handle - load base of the library = the symbol's value in the library's `nm -C` listing, which names the instantiation.
@@ -8,6 +8,10 @@
 //     symbols  lines "<hex value> <demangled name>" (the library's nm -C listing, address and name columns)
 //     rows     lines "id entry B D H W Cin Cout kz algo bias xoff goff"; entry as in tests/wgrad_cases.py, algo -1 = the entry point
 //              without an algo argument
+//              | "id entry B D H W Cin Cout flags present misaligned" with entry = wino_fwd | wino_fwd_bits | wino_fwd_addup | wino_fwd_addup_bits |
+//              wino_upconv_fwd | wino_upconv_fwd_bits | wino_upconv_dgrad | wino43; present / misaligned = bit masks over the operand slots
+//              x 1, wp 2, bias 4, residual (xc of the add-up forms) 8, mask_src 16, mask_bits 32, y (acc) 64, y2 128, sign_bits 256: a slot
+//              not present is passed as NULL, a misaligned one 4 bytes behind its address; leak = 0.2
 //   per row:   "row <id>", one line per runtime call in order --
 //              "  launch <kernel> grid x y z block x lds <bytes> args <hex bytes>" | "  funcattr <kernel> <attribute> <value>" --
 //              then "end <id> rc <return code> ws <the workspace bytes the entry point's query asked for, and the call got>"
@@ -64,6 +68,9 @@ const Layout kLayouts[] = {
     {"(anonymous namespace)::wgrad_thin_reduce_kernel(", 9, {8, 8, 8, 8, 4, 4, 4, 4, 4}},
     {"(anonymous namespace)::pad_rows_kernel(", 6, {8, 8, 8, 4, 4, 4}},
     {"df::zero_words_kernel(", 2, {8, 8}},
+    // WinoArgs up to and including spx (the experiment field that once followed it was never set by these entry points); W43Args whole
+    {"(anonymous namespace)::wino3d_kernel<", 1, {136}},
+    {"(anonymous namespace)::wino43_kernel<", 1, {128}},
 };
 
 }  // namespace
@@ -115,6 +122,26 @@ int hipMemsetAsync(void* p, int value, size_t bytes, void* stream) {
 
 }  // extern "C"
 
+// one row of tests/test_wino_launches_host.py: operand slot i sits at (i + 1) << 44
+static int wino_row(const std::string& e, long long B, long long D, long long H, long long W, long long Cin, long long Cout, int flags,
+                    int present, int mis) {
+  auto slot = [&](int i) -> char* {
+    if (!((present >> i) & 1)) return nullptr;
+    return reinterpret_cast<char*>((static_cast<uintptr_t>(i + 1) << 44) + (((mis >> i) & 1) ? 4 : 0));
+  };
+  auto f = [&](int i) { return reinterpret_cast<float*>(slot(i)); };
+  const float leak = 0.2f;
+  if (e == "wino_fwd") return df_wino_conv_fwd(f(0), f(1), f(2), f(3), f(4), f(6), B, D, H, W, Cin, Cout, flags, leak, nullptr);
+  if (e == "wino_fwd_bits") return df_wino_conv_fwd_bits(f(0), f(1), f(2), slot(5), f(6), slot(8), B, D, H, W, Cin, Cout, flags, leak, nullptr);
+  if (e == "wino_fwd_addup") return df_wino_conv_fwd_addup(f(0), f(1), f(2), f(3), f(6), f(7), B, D, H, W, Cin, Cout, leak, nullptr);
+  if (e == "wino_fwd_addup_bits") return df_wino_conv_fwd_addup_bits(f(0), f(1), f(2), f(3), f(7), slot(8), B, D, H, W, Cin, Cout, leak, nullptr);
+  if (e == "wino_upconv_fwd") return df_wino_upconv_fwd(f(0), f(1), f(2), f(6), B, D, H, W, Cin, Cout, flags, leak, nullptr);
+  if (e == "wino_upconv_fwd_bits") return df_wino_upconv_fwd_bits(f(0), f(1), f(2), f(6), slot(8), B, D, H, W, Cin, Cout, leak, nullptr);
+  if (e == "wino_upconv_dgrad") return df_wino_upconv_dgrad(f(0), f(1), f(6), B, D, H, W, Cin, Cout, nullptr);
+  if (e == "wino43") return df_wino43_conv(f(0), f(1), f(2), f(3), f(4), slot(5), f(6), f(7), slot(8), B, D, H, W, Cin, Cout, flags, leak, nullptr);
+  return -1000;
+}
+
 int main(int argc, char** argv) {
   if (argc != 3) { fprintf(stderr, "usage: %s <symbols> <rows>\n", argv[0]); return 2; }
   FILE* fs = fopen(argv[1], "r");
@@ -140,6 +167,13 @@ int main(int argc, char** argv) {
   long long B, D, H, W, Cin, Cout;
   int kz, algo, bias, xoff, goff;
   while (fgets(line, sizeof line, fr)) {
+    int flags, present, mis;
+    if (sscanf(line, "%127s %31s %lld %lld %lld %lld %lld %lld %d %d %d", id, entry, &B, &D, &H, &W, &Cin, &Cout, &flags, &present, &mis) == 11 &&
+        strncmp(entry, "wino", 4) == 0) {
+      printf("row %s\n", id);
+      printf("end %s rc %d ws 0\n", id, wino_row(entry, B, D, H, W, Cin, Cout, flags, present, mis));
+      continue;
+    }
     if (sscanf(line, "%127s %31s %lld %lld %lld %lld %lld %lld %d %d %d %d %d", id, entry, &B, &D, &H, &W, &Cin, &Cout, &kz, &algo, &bias,
                &xoff, &goff) != 13)
       continue;
