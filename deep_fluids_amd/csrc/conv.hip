@@ -477,10 +477,15 @@ int df_conv_pack_weights(const float* w, float* wp, int64_t taps, int64_t cin, i
   return df::launched("df_conv_pack_weights");
 }
 
+// A flag bit that the entry point's comment in the header does not list is DF_EINVAL (as df_wino43_conv decides it): it would be
+// accepted today and silently do nothing.
+constexpr int kEpilogueFlags = DF_CONV_BIAS | DF_CONV_LRELU | DF_CONV_RESIDUAL | DF_CONV_MASK;
+
 static int conv_common(const char* fn, const float* x, const float* wp, const float* bias, const float* residual,
                        const float* mask_src, float* y, int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin,
-                       int64_t Cout, int kz, int stride, int flags, float leak, df_stream_t stream, int prec = 0) {
+                       int64_t Cout, int kz, int stride, int flags, int allowed, float leak, df_stream_t stream, int prec = 0) {
   DF_REQUIRE(x && wp && y, DF_EINVAL, "%s: null pointer", fn);
+  DF_REQUIRE(!(flags & ~allowed), DF_EINVAL, "%s: flags 0x%x hold a bit this entry point does not take (0x%x)", fn, flags, allowed);
   DF_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, DF_EINVAL, "%s: non-positive extent", fn);
   DF_REQUIRE(kz == 1 || kz == 3, DF_ESHAPE, "%s: kz must be 1 (2-D) or 3 (3-D)", fn);
   DF_REQUIRE(kz == 3 || D == 1, DF_ESHAPE, "%s: D must be 1 when kz == 1", fn);
@@ -505,6 +510,7 @@ static int conv_common(const char* fn, const float* x, const float* wp, const fl
   hipStream_t s = df::as_stream(stream);
   if (prec == 1) {
     DF_REQUIRE(stride == 1 && bf16x3_supported(a), DF_ESHAPE, "%s: bf16x3 needs stride 1, Cin %% 4 == 0, channels >= 16", fn);
+    DF_REQUIRE(df::aligned16(x), DF_EALIGN, "%s: x must be 16-byte aligned", fn);
     a.Kpad = (int)bf16x3_kpad(Cin);
     return launch_bf16x3(a, kz, 3, s);
   }
@@ -530,15 +536,15 @@ static int conv_common(const char* fn, const float* x, const float* wp, const fl
 int df_conv_fwd(const float* x, const float* wp, const float* bias, const float* residual, const float* mask_src,
                 float* y, int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int kz, int flags,
                 float leak, df_stream_t stream) {
-  return conv_common("df_conv_fwd", x, wp, bias, residual, mask_src, y, B, D, H, W, Cin, Cout, kz, 1, flags, leak,
-                     stream);
+  return conv_common("df_conv_fwd", x, wp, bias, residual, mask_src, y, B, D, H, W, Cin, Cout, kz, 1, flags,
+                     kEpilogueFlags | DF_CONV_VALU_ONLY, leak, stream);
 }
 
 int df_conv_s2_fwd(const float* x, const float* wp, const float* bias, float* y, int64_t B, int64_t Do, int64_t Ho,
                    int64_t Wo, int64_t Cin, int64_t Cout, int kz, int flags, float leak, df_stream_t stream) {
-  DF_REQUIRE(!(flags & (DF_CONV_RESIDUAL | DF_CONV_MASK)), DF_EINVAL, "df_conv_s2_fwd: only BIAS / LRELU epilogues");
-  return conv_common("df_conv_s2_fwd", x, wp, bias, nullptr, nullptr, y, B, Do, Ho, Wo, Cin, Cout, kz, 2, flags, leak,
-                     stream);
+  DF_REQUIRE(!(flags & ~(DF_CONV_BIAS | DF_CONV_LRELU)), DF_EINVAL, "df_conv_s2_fwd: only BIAS / LRELU epilogues (flags 0x%x)", flags);
+  return conv_common("df_conv_s2_fwd", x, wp, bias, nullptr, nullptr, y, B, Do, Ho, Wo, Cin, Cout, kz, 2, flags,
+                     DF_CONV_BIAS | DF_CONV_LRELU, leak, stream);
 }
 
 int64_t df_upconv_packed_elems(int64_t cin, int64_t cout, int kz, int mode) {
@@ -577,7 +583,7 @@ static int upconv_fwd_impl(const float* xc, const float* wp, const float* bias, 
   DF_REQUIRE(kz == 1 || kz == 3, DF_ESHAPE, "df_upconv_fwd: kz must be 1 (2-D) or 3 (3-D)");
   DF_REQUIRE(kz == 3 || Dc == 1, DF_ESHAPE, "df_upconv_fwd: Dc must be 1 when kz == 1");
   DF_REQUIRE(Cin > 4 && Cout > 4, DF_ESHAPE, "df_upconv_fwd: MFMA path only (channels > 4)");
-  DF_REQUIRE(!(flags & (DF_CONV_RESIDUAL | DF_CONV_MASK)), DF_EINVAL, "df_upconv_fwd: only BIAS / LRELU epilogues");
+  DF_REQUIRE(!(flags & ~(DF_CONV_BIAS | DF_CONV_LRELU)), DF_EINVAL, "df_upconv_fwd: only BIAS / LRELU epilogues (flags 0x%x)", flags);
   DF_REQUIRE(!(flags & DF_CONV_BIAS) || bias, DF_EINVAL, "df_upconv_fwd: DF_CONV_BIAS without bias");
   DF_REQUIRE(df::aligned16(wp), DF_EALIGN, "df_upconv_fwd: packed weights must be 16-byte aligned");
   ConvArgs a;
@@ -595,6 +601,7 @@ static int upconv_fwd_impl(const float* xc, const float* wp, const float* bias, 
   a.nclass = kz == 3 ? 8 : 4;
   if (prec == 1) {
     DF_REQUIRE(bf16x3_supported(a), DF_ESHAPE, "df_upconv_fwd_bf16x3: Cin %% 4 == 0, channels >= 16");
+    DF_REQUIRE(df::aligned16(xc), DF_EALIGN, "df_upconv_fwd_bf16x3: xc must be 16-byte aligned");
     a.Kpad = (int)bf16x3_kpad(Cin);
   }
   a.wclass = static_cast<int64_t>(kz == 3 ? 8 : 4) * a.Kpad * a.Npad / 4;
@@ -689,6 +696,7 @@ static int upconv_dgrad_impl(const float* g, const float* wp, float* acc, int64_
     a.nclass = 1; a.wclass = 0;
     if (prec == 1) {
       DF_REQUIRE(bf16x3_supported(a), DF_ESHAPE, "df_upconv_dgrad_bf16x3: channels %% 4 == 0, >= 16");
+      DF_REQUIRE(df::aligned16(g), DF_EALIGN, "df_upconv_dgrad_bf16x3: g must be 16-byte aligned");      // (class 0: nothing launched yet)
       if (int e = launch_bf16x3(a, kz, 2, s)) return e;
     } else if (int e = upconv_launch(a, kz, s)) {
       return e;
@@ -723,8 +731,8 @@ int df_conv_pack_weights_bf16x3(const float* w, float* wp, int64_t taps, int64_t
 int df_conv_fwd_bf16x3(const float* x, const float* wp, const float* bias, const float* residual, const float* mask_src,
                        float* y, int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int kz, int flags,
                        float leak, df_stream_t stream) {
-  return conv_common("df_conv_fwd_bf16x3", x, wp, bias, residual, mask_src, y, B, D, H, W, Cin, Cout, kz, 1, flags, leak,
-                     stream, 1);
+  return conv_common("df_conv_fwd_bf16x3", x, wp, bias, residual, mask_src, y, B, D, H, W, Cin, Cout, kz, 1, flags, kEpilogueFlags,
+                     leak, stream, 1);
 }
 int64_t df_upconv_packed_elems_bf16x3(int64_t cin, int64_t cout, int kz, int mode) {
   const int64_t K = mode == 0 ? cin : cout, N = mode == 0 ? cout : cin;

@@ -313,8 +313,9 @@ int launch_t(ConvArgs a, hipStream_t s) {
 
 }  // namespace
 
+// channel counts only (DF_ESHAPE); the callers check the 16-byte alignment of x themselves (DF_EALIGN)
 bool bf16x3_supported(const ConvArgs& a) {
-  return a.Cin % 4 == 0 && a.Cin >= 16 && a.Cout >= 16 && df::aligned16(a.x);
+  return a.Cin % 4 == 0 && a.Cin >= 16 && a.Cout >= 16;
 }
 
 int64_t bf16x3_kpad(int64_t K) { return ceil_div(K, CKB) * CKB; }

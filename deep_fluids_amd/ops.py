@@ -492,7 +492,7 @@ def _conv_raw(x, wp, bias, residual, mask_src, dims, cin, cout, kz, flags, leak,
         call("df_wino2d_conv_fwd", _ptr(x), _ptr(wp), _ptr(bias), _ptr(residual), _ptr(mask_src), _ptr(y), B, H, W, cin, cout,
              flags, float(leak), _stream())
     else:
-        if THIN_VALU_ONLY:
+        if THIN_VALU_ONLY and not k.sfx:      # (df_conv_fwd_bf16x3 has no thin layers and refuses the flag)
             flags |= _lib.DF_CONV_VALU_ONLY
         call("df_conv_fwd" + k.sfx, _ptr(x), _ptr(wp), _ptr(bias), _ptr(residual), _ptr(mask_src), _ptr(y), B, D, H, W,
              cin, cout, kz, flags, float(leak), _stream())

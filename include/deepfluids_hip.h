@@ -40,7 +40,9 @@ enum {
   DF_EWORKSPACE = -4 /* workspace too small */
 };
 
-/* flags for df_conv_fwd */
+/* flags for df_conv_fwd.  Every conv entry point that takes `flags` names the bits it accepts in its comment; any other bit
+ * (DF_CONV_ADDUP outside the add-up forms, DF_CONV_VALU_ONLY where the entry point has no thin-layer kernels, an undefined bit) is
+ * DF_EINVAL, as is a flag whose operand is NULL. */
 enum {
   DF_CONV_LRELU = 1,      /* y = max(v, leak*v)            ops.py:9-10 fused into the conv epilogue   */
   DF_CONV_RESIDUAL = 2,   /* y += residual (after act)      model.py:35,40,77,82                       */
@@ -243,13 +245,18 @@ int df_store_scalars(float* dst, int64_t n, float v0, float v1, float v2, float 
 /* slim.conv2d / conv3d, k=3, stride 1, padding SAME, channels-last (ops.py:12-16; model.py:26,42,68,84).
  * Weights are given in TF layout [kz,ky,kx,Cin,Cout] (2-D: kz = 1) and are re-packed once per update into
  * the MFMA operand order by df_conv_pack_weights:
- *   mode 0: forward operand;  mode 1: dgrad operand (taps mirrored, Cin/Cout swapped). */
+ *   mode 0: forward operand;  mode 1: dgrad operand (taps mirrored, Cin/Cout swapped).
+ * Packed size, in floats: taps * Kpad * Npad with K = cin, N = cout (mode 0) or K = cout, N = cin (modes 1, 2); Kpad = K rounded up to
+ * 16 (the *_bf16x3 packs: 32), Npad = N rounded up to its N tile (32 up to N = 32, 64 up to 64, 128 above).  The up-sampling packs
+ * (df_upconv_packed_elems) hold 4 classes x 4 taps (2-D) or 8 x 8 (3-D) of that. */
 int64_t df_conv_packed_elems(int64_t taps, int64_t cin, int64_t cout, int mode);
 int df_conv_pack_weights(const float* w, float* wp, int64_t taps, int64_t cin, int64_t cout, int mode,
                          df_stream_t stream);
 /* y[B,D,H,W,Cout] = epilogue( conv_same(x[B,D,H,W,Cin], w) ).  D = 1 and kz = 1 for 2-D.
  * `wp` packed with mode 0 (forward) or mode 1 (then x is dL/dy and y is dL/dx: the dgrad).
- * flags: DF_CONV_*; bias / residual / mask_src are used only when their flag is set. */
+ * flags: DF_CONV_BIAS | LRELU | RESIDUAL | MASK | VALU_ONLY; bias / residual / mask_src are used only when their flag is set.
+ * Alignment: wp 16 bytes (DF_EALIGN); x, y, bias, residual, mask_src 4 bytes (the kernels that read or write them through
+ * 16-byte types run only where they are 16-byte aligned; the general kernels take their place otherwise). */
 int df_conv_fwd(const float* x, const float* wp, const float* bias, const float* residual, const float* mask_src,
                 float* y, int64_t B, int64_t D, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int kz, int flags,
                 float leak, df_stream_t stream);
@@ -281,6 +288,7 @@ int df_conv_s2_dgrad_form(const float* gy, int64_t Cin, int64_t Cout);
  * WITHOUT materialising the up-sampled tensor as 8 (3-D) / 4 (2-D) parity-class convs with 2x2x2 / 2x2 pre-summed taps
  * on the coarse grid (27/8 = 3.4x fewer FLOPs; identical up to fp32 summation order).
  *   xc [B,Dc|1,Hc,Wc,Cin] (coarse)  ->  y [B,2Dc|1,2Hc,2Wc,Cout] (fine).  Weights: TF layout [kz,3,3,Cin,Cout].
+ *   df_upconv_fwd flags: DF_CONV_BIAS | DF_CONV_LRELU only; channel counts > 4 (DF_ESHAPE), also for df_upconv_dgrad.
  * Pack modes: 0 forward operand; 1 operand of df_upconv_dgrad; 2 DGRAD OPERAND OF THE STRIDE-2 CONV (df_conv_s2_fwd): the adjoint of
  *   y[o] = sum_t x[2o+t] w[t] is dx[2m] = g[m-1] w[2] + g[m] w[0], dx[2m+1] = g[m] w[1] per axis, i.e. the same parity-class / offset
  *   structure; run it as  df_upconv_fwd(g [B,Do,Ho,Wo,Cout], wp(mode 2), NULL, dx [B,2Do,2Ho,2Wo,Cin], B, Do, Ho, Wo, Cin := Cout,
@@ -417,7 +425,9 @@ int df_wino2d_upconv_dgrad(const float* g, const float* wp, float* acc, int64_t 
 /* ---- opt-in "bf16x3" precision mode (conv_bf16.hip) ---------------------------------------------------------------------
  * fp32 operands are split a = hi + lo into two bf16 words and a*b ~= hi*hi + hi*lo + lo*hi runs on the bf16 matrix pipe
  * (3 x v_mfma_f32_32x32x16_bf16, fp32 accumulate): 16 significand bits per operand, ~5x the fp32 MFMA rate.  Same arguments
- * as the fp32 twins; weights must be packed by the matching *_bf16x3 pack call.  Needs Cin % 4 == 0, channels >= 16. */
+ * as the fp32 twins; weights must be packed by the matching *_bf16x3 pack call.  Needs Cin % 4 == 0, channels >= 16 (DF_ESHAPE)
+ * and the input tensor (x / xc / g) 16-byte aligned (DF_EALIGN: this mode has no scalar-load kernel).  flags: those of the fp32 twin
+ * without DF_CONV_VALU_ONLY (no thin layers here). */
 int64_t df_conv_packed_elems_bf16x3(int64_t taps, int64_t cin, int64_t cout, int mode);   /* in 4-byte units */
 int df_conv_pack_weights_bf16x3(const float* w, float* wp, int64_t taps, int64_t cin, int64_t cout, int mode,
                                 df_stream_t stream);

@@ -1,4 +1,5 @@
-// Launch recorder of tests/test_wgrad_launches_host.py and tests/test_wino_launches_host.py: calls the weight-gradient and the 3-D Winograd
+// Launch recorder of tests/test_wgrad_launches_host.py, tests/test_wino_launches_host.py and tests/test_conv_cases_host.py: calls the
+// weight-gradient, the 3-D Winograd and the direct conv (forward / input-gradient)
 // entry points of libdeepfluids_hip.so WITHOUT a GPU and prints what they would have launched.  No HIP header, no device: this executable itself defines every HIP runtime call the host path of
 // csrc/conv_wgrad.hip makes (df_common.hpp, core.hip), and a symbol defined in the executable wins over the shared runtime's when the
 // library's calls are bound.  A launch arrives as hipLaunchKernel(kernel handle, grid, block, argument pointers, LDS bytes, stream);
@@ -12,6 +13,10 @@
 //              wino_upconv_fwd | wino_upconv_fwd_bits | wino_upconv_dgrad | wino43; present / misaligned = bit masks over the operand slots
 //              x 1, wp 2, bias 4, residual (xc of the add-up forms) 8, mask_src 16, mask_bits 32, y (acc) 64, y2 128, sign_bits 256: a slot
 //              not present is passed as NULL, a misaligned one 4 bytes behind its address; leak = 0.2
+//              | "id entry B D H W Cin Cout kz flags present ox owp obias ores omask oy" with entry = dc_fwd | dc_fwd_bf16x3 | dc_s2_fwd |
+//              dc_s2_dgrad | dc_up_fwd | dc_up_fwd_bf16x3 | dc_up_dgrad | dc_up_dgrad_bf16x3 (tests/conv_cases.py): present = bit mask over
+//              the slots x (gy / g of the dgrads) 1, wp 2, bias 4, residual 8, mask_src 16, y (gx / acc) 32; o* = the slot's payload offset
+//              in floats; leak = 0.2
 //   per row:   "row <id>", one line per runtime call in order --
 //              "  launch <kernel> grid x y z block x lds <bytes> args <hex bytes>" | "  funcattr <kernel> <attribute> <value>" --
 //              then "end <id> rc <return code> ws <the workspace bytes the entry point's query asked for, and the call got>"
@@ -45,7 +50,8 @@ std::string kernel_name(const void* f) {
 
 // Argument bytes of each kernel the weight-gradient host code launches: the sizes of its parameters in order.  The kernels that take one
 // argument struct list its size WITHOUT tail padding (WxyzArgs: 140 of 144, SmallWgradArgs: 84 of 88), which is not initialised.
-struct Layout { const char* prefix; int n; int size[12]; };
+// hole_at / hole_len: padding bytes inside the one argument struct (never initialised by the host code), printed as 00.
+struct Layout { const char* prefix; int n; int size[12]; int hole_at, hole_len; };
 const Layout kLayouts[] = {
     {"(anonymous namespace)::wgrad_kernel<", 1, {128}},
     {"(anonymous namespace)::wgrad_s2_kernel<", 1, {128}},
@@ -71,6 +77,18 @@ const Layout kLayouts[] = {
     // WinoArgs up to and including spx (the experiment field that once followed it was never set by these entry points); W43Args whole
     {"(anonymous namespace)::wino3d_kernel<", 1, {136}},
     {"(anonymous namespace)::wino43_kernel<", 1, {128}},
+    // the direct convs: ConvArgs whole (200 bytes, 4 of padding in front of wclass); ThinKArgs without its tail padding (84 of 88); ThinNArgs
+    {"(anonymous namespace)::conv_mfma_kernel<", 1, {200}, 156, 4},
+    {"(anonymous namespace)::conv_tiny2d_kernel(", 1, {200}, 156, 4},
+    {"dfconv::(anonymous namespace)::conv_bf16x3_kernel<", 1, {200}, 156, 4},
+    {"dfconv::(anonymous namespace)::conv_small_n_kernel<", 1, {200}, 156, 4},
+    {"dfconv::(anonymous namespace)::conv_small_k_kernel<", 2, {200, 4}, 156, 4},
+    {"dfconv::(anonymous namespace)::conv_thin_k_mfma_kernel<", 1, {84}},
+    {"dfconv::(anonymous namespace)::conv_thin_n_mfma_kernel<", 1, {72}},
+    {"(anonymous namespace)::pack_kernel(", 8, {8, 8, 4, 4, 4, 4, 4, 4}},
+    {"(anonymous namespace)::upconv_pack_kernel(", 8, {8, 8, 4, 4, 4, 4, 4, 4}},
+    {"dfconv::(anonymous namespace)::pack_bf16x3_kernel(", 8, {8, 8, 4, 4, 4, 4, 4, 4}},
+    {"dfconv::(anonymous namespace)::upconv_pack_bf16x3_kernel(", 8, {8, 8, 4, 4, 4, 4, 4, 4}},
 };
 
 }  // namespace
@@ -95,7 +113,7 @@ int hipLaunchKernel(const void* f, dim3 grid, dim3 block, void** args, size_t ld
   if (!lay) { printf("?\n"); return 0; }
   for (int i = 0; i < lay->n; ++i) {
     const unsigned char* p = static_cast<const unsigned char*>(args[i]);
-    for (int b = 0; b < lay->size[i]; ++b) printf("%02x", p[b]);
+    for (int b = 0; b < lay->size[i]; ++b) printf("%02x", i == 0 && b >= lay->hole_at && b < lay->hole_at + lay->hole_len ? 0 : p[b]);
     if (i + 1 < lay->n) printf(".");
   }
   printf("\n");
@@ -142,6 +160,25 @@ static int wino_row(const std::string& e, long long B, long long D, long long H,
   return -1000;
 }
 
+// one row of tests/conv_cases.py: operand slot i sits at (i + 1) << 44, plus the row's offset in floats
+static int dc_row(const std::string& e, long long B, long long D, long long H, long long W, long long Cin, long long Cout, int kz, int flags,
+                  int present, const int* off) {
+  auto f = [&](int i) -> float* {
+    if (!((present >> i) & 1)) return nullptr;
+    return reinterpret_cast<float*>(static_cast<uintptr_t>(i + 1) << 44) + off[i];
+  };
+  const float leak = 0.2f;
+  if (e == "dc_fwd") return df_conv_fwd(f(0), f(1), f(2), f(3), f(4), f(5), B, D, H, W, Cin, Cout, kz, flags, leak, nullptr);
+  if (e == "dc_fwd_bf16x3") return df_conv_fwd_bf16x3(f(0), f(1), f(2), f(3), f(4), f(5), B, D, H, W, Cin, Cout, kz, flags, leak, nullptr);
+  if (e == "dc_s2_fwd") return df_conv_s2_fwd(f(0), f(1), f(2), f(5), B, D, H, W, Cin, Cout, kz, flags, leak, nullptr);
+  if (e == "dc_s2_dgrad") return df_conv_s2_dgrad(f(0), f(1), f(5), B, D, H, W, Cin, Cout, kz, nullptr);
+  if (e == "dc_up_fwd") return df_upconv_fwd(f(0), f(1), f(2), f(5), B, D, H, W, Cin, Cout, kz, flags, leak, nullptr);
+  if (e == "dc_up_fwd_bf16x3") return df_upconv_fwd_bf16x3(f(0), f(1), f(2), f(5), B, D, H, W, Cin, Cout, kz, flags, leak, nullptr);
+  if (e == "dc_up_dgrad") return df_upconv_dgrad(f(0), f(1), f(5), B, D, H, W, Cin, Cout, kz, nullptr);
+  if (e == "dc_up_dgrad_bf16x3") return df_upconv_dgrad_bf16x3(f(0), f(1), f(5), B, D, H, W, Cin, Cout, kz, nullptr);
+  return -1000;
+}
+
 int main(int argc, char** argv) {
   if (argc != 3) { fprintf(stderr, "usage: %s <symbols> <rows>\n", argv[0]); return 2; }
   FILE* fs = fopen(argv[1], "r");
@@ -168,6 +205,13 @@ int main(int argc, char** argv) {
   int kz, algo, bias, xoff, goff;
   while (fgets(line, sizeof line, fr)) {
     int flags, present, mis;
+    int off[6];
+    if (sscanf(line, "%127s %31s %lld %lld %lld %lld %lld %lld %d %d %d %d %d %d %d %d %d", id, entry, &B, &D, &H, &W, &Cin, &Cout, &kz, &flags,
+               &present, &off[0], &off[1], &off[2], &off[3], &off[4], &off[5]) == 17 && strncmp(entry, "dc_", 3) == 0) {
+      printf("row %s\n", id);
+      printf("end %s rc %d ws 0\n", id, dc_row(entry, B, D, H, W, Cin, Cout, kz, flags, present, off));
+      continue;
+    }
     if (sscanf(line, "%127s %31s %lld %lld %lld %lld %lld %lld %d %d %d", id, entry, &B, &D, &H, &W, &Cin, &Cout, &flags, &present, &mis) == 11 &&
         strncmp(entry, "wino", 4) == 0) {
       printf("row %s\n", id);
