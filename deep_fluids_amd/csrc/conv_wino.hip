@@ -25,16 +25,10 @@
 // wino3d_kernel<FL, MODE>: FL = the epilogue (compile-time flags, -1 = run-time a.flags), MODE = 0 plain | 2 pooled adjoint | 3 up-sampling-aware
 // forward with the coarse halo block staged.  The library instantiates the 12 pairs listed in wino_launch below, nothing else.
 //
-// Until commit 2f63d5b this kernel also carried the experiments of rounds 2-5 as template switches DBG / PREC / XS of a tuning build, with entry
-// points to select them: DBG = timing variants that drop the transform / the LDS reads / the staging / the weight loads, per-phase cycle
-// counters, spread and coalesced staging loads; XS (round 4) = staging by LDS-DMA from an x-blocked copy of the input, three buffers, two weight
-// register sets -- no-go; PREC 1 (round 3) = bf16x3 in the Winograd domain; MODE 1 (round 2) = the up-sampling-aware forward staging the fine
-// positions, replaced by MODE 3.  Their numbers are in profiles/LAB_NOTES.md, r03_probes.md, r04_probes.md and r05_probes.md; the probes under
-// tools/archive/ that drove them need that commit.  The switches are now the constants DBG = PREC = XS = 0 inside the kernel: nothing can
-// select a variant any more, the epilogue and most of the main loop are free of them, but the staging lambdas, the PREC staging plan and the
-// branches of the main loop that call them are still in the text as dead code.  Deleting those changes which variables the main-loop lambda
-// captures, and with it the register allocation and instruction order of all 12 instantiations (LAB_NOTES.md, "Winograd 3-D convs: experiment
-// switches"): they go when that can be done without touching the emitted code, or with a measurement.
+// The kernel is one fp32 path: a chunk is staged by buffer loads (offsets: set_offs) and stage_store_all into one of two alternating LDS buffers,
+// raw_read + transform make the A operands of a k-step, reload_row fetches a xi_y row's weights behind its MFMAs.  (History: until commit
+// 2f63d5b it also carried the experiments of rounds 2-5 as template switches DBG / PREC / XS; what they were, their numbers and how they
+// were removed is in profiles/LAB_NOTES.md, "Winograd 3-D convs: experiment switches ..." and "wino3d_kernel: the dead DBG / PREC / XS paths".)
 #include <type_traits>
 #include "df_common.hpp"
 #include "conv_args.hpp"
@@ -74,11 +68,6 @@ constexpr int kNoPrimary = 256;            // with DF_CONV_ADDUP + kSignBits: y 
                                            // the backward pass needs of it (df_wino_conv_fwd_addup_bits / df_lrelu_bits_bwd_pool2x)
 constexpr int kBitBytesPerBlock = 1024;    // 8 waves x 2 cout blocks x 64 lanes, per (tile block, cout slice)
 constexpr int kZeroFloats = 1024;         // zeroed tail of the packed weights: SAME padding reads it, one 64-byte step per chunk
-// (types and LDS layout constants of the dead PREC = 1 paths, see the header comment)
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-constexpr int BPOS = 80, BPY = 12, BPLANE = (9 * BPY + 10) * BPOS, BBUF = 8 * BPLANE, BCOL = 400;
 
 struct WinoArgs {
   const float* x;
@@ -96,7 +85,7 @@ struct WinoArgs {
   int flags;
   float leak;
   int spx;             // cout slices per XCD (wino_grid)
-  int Wb;              // (never set: read by the dead XS paths only)
+  int reserved = 0;    // padding that keeps the argument block at its size: always zero, never read
 };
 
 // ---- weight transform + packing ------------------------------------------------------------------------------------------
@@ -223,24 +212,13 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // (A^T row 0 + row 1) = (1, 2, 0, -1) per axis, so the same 27 points are the only ones needed and a tile block writes 32 voxels, not 256.
 template <int FL, int MODE>
 __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
-  constexpr int DBG = 0, PREC = 0, XS = 0;      // the former template switches (header comment): every branch on them below is dead
   constexpr bool UPC = MODE == 3;                    // UP with the coarse halo block staged as such (see UPY / UCP above)
-  constexpr bool UP = MODE == 1 || UPC, POOL = MODE == 2, P27 = MODE != 0;
-  constexpr bool BX = PREC == 1;
-  constexpr bool XB = XS != 0, XASYM = (XS & 2) != 0;
-  static_assert(!XB || (!UP && !BX), "x-blocked staging: plain / pooled fp32 modes only");
-  static_assert(!UPC || !BX, "coarse staging: fp32 mode only");
+  constexpr bool POOL = MODE == 2, P27 = MODE != 0;
   constexpr int PZk = UPC ? UPZ : PZ, CPk = UPC ? UCP : CP;      // pitches INSIDE a buffer; the buffer stride below keeps the plain size (the
                                                                 // epilogue's 32 KB exchange area lives in the idle buffer)
   constexpr int NL = UPC ? NLU : NLOAD;              // staging pieces per thread and chunk
-  constexpr int XROWB = 51 * 16, XROWS = 60;        // XS: bytes per LDS row (3 pieces x 17 slots x 16 B), halo rows per chunk (6 planes x 10)
-  constexpr int BUFk = XB ? XROWS * XROWB / 4 : CKW * CP;
-  constexpr int BUFF = BX ? BBUF / 4 : BUFk;      // floats per LDS buffer
-  // (experiment XS & 128: THREE staging buffers -- the pieces of chunk c + 2 are issued at the start of chunk c and waited for at the end of
-  //  chunk c + 1: ~7 k-steps of slack instead of 2-3)
-  constexpr bool TRI = (XS & 128) != 0;
-  constexpr int NSB = TRI ? 3 : 2;
-  __shared__ __attribute__((aligned(16))) float sIn[NSB * BUFF];
+  constexpr int BUFF = CKW * CP;                     // floats per LDS buffer
+  __shared__ __attribute__((aligned(16))) float sIn[2 * BUFF];
   __shared__ float sBias[32];        // this worker's cout slice of the bias (the slice is fixed for the worker's whole life)
   __shared__ float sMs[16 * kT];     // lrelu-mask operands of a tile block's outputs, fetched by LDS-DMA loads (no registers)
 
@@ -297,7 +275,6 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
     return bi;
   };
 
-  const __amdgpu_buffer_rsrc_t wsrd_dbg = make_srd(a.wp, 4096u);
   // ---- staging plan (per thread: 5 float4 pieces of the 600-voxel x 16-channel halo block) ---------------------------------
   // so[it] = byte offset of piece `it` inside the batch volume, or an out-of-range offset for halo voxels outside the tensor:
   // the buffer load's range check then returns the zeros of the SAME padding.  Set once per tile block; a staging pass adds
@@ -349,15 +326,6 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
       so[it] = ok ? static_cast<unsigned>(bi.hoff + roff) * 4u : 0x80000000u;
     }
   };
-  auto stage_load = [&](int it, __amdgpu_buffer_rsrc_t srd, unsigned chunkbytes) -> f32x4 {
-    if ((DBG & 384) == 256) return buf_load16(wsrd_dbg, static_cast<unsigned>(lane) * 16u, 0u);      // always-cached address (latency experiment)
-    if (DBG & 4194304) {      // (experiment, timing only: FULLY COALESCED staging loads -- lane i reads 16 B at base + 16 i, 1 KiB contiguous per wave
-                              //  instruction, 8 full lines -- that miss L1: the base walks the tensor with the real offsets' block / chunk part)
-      const unsigned basev = (so[it] == 0x80000000u ? 0u : so[it]) & 0x7FFFFC00u;
-      return buf_load16(srd, __builtin_amdgcn_readfirstlane(basev) + static_cast<unsigned>(lane) * 16u, chunkbytes & ~1023u);
-    }
-    return buf_load16(srd, so[it], chunkbytes);
-  };
   char* sInB = reinterpret_cast<char*>(sIn);
   auto stage_store = [&](int it, int bufbytes, const f32x4& v) {
     float* d = reinterpret_cast<float*>(sInB + (ldst[it] + bufbytes));
@@ -381,93 +349,6 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
     } else {
 #pragma unroll
       for (int it = 0; it < NLOAD; ++it) stage_store(it, bufbytes, v[it]);
-    }
-  };
-
-  // ---- XS staging: DMA instruction = halo row r = hz * 10 + hy; lane = (piece g, slot c), 51 of 64 lanes active -------------------------
-  const bool xissuer = XB && (!XASYM || wave >= 4);
-  const int xg = lane / 17, xc = lane - xg * 17;
-  const unsigned xvoff = (lane < 51 && xc < 16) ? static_cast<unsigned>((xg * a.Cin + xc) * 16) : 0x80000000u;      // pad slot: zeros
-  auto issue_dma = [&](int bufbytes, const BlockInfo& bi, unsigned chunkbytes) {      // chunkbytes = chunk * 256 (16 channels x 16 B)
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    if (!xissuer) return;
-    const __amdgpu_buffer_rsrc_t dsrd = make_srd(bi.xb, vol_bytes);
-    const int rowb = a.Wb * a.Cin * 16;                                             // bytes per (z, y) row of the copy
-    const int base = (((bi.z0 - 1) * a.H + (bi.y0 - 1)) * a.Wb + (bi.x0 >> 2)) * a.Cin * 16 + static_cast<int>(chunkbytes);
-    // a rolled loop of scalar row arithmetic (nothing of it lives in registers across the main loop); a row outside the tensor reads
-    // through the out-of-range lane offset (zeros = the SAME padding in y, z)
-    auto one_row = [&](int r) {
-      const int hz = r / 10, hy = r - hz * 10;
-      const bool ok = static_cast<unsigned>(bi.z0 - 1 + hz) < static_cast<unsigned>(a.D) &&
-                      static_cast<unsigned>(bi.y0 - 1 + hy) < static_cast<unsigned>(a.H);
-      // branch-free: a row outside the tensor keeps its (meaningless, never dereferenced) scalar offset and gets the out-of-range bit in
-      // the LANE offset -- the range check looks at the lane offset only
-      const unsigned soff = static_cast<unsigned>(base + (hz * a.H + hy) * rowb);
-      const unsigned vo = xvoff | (ok ? 0u : 0x80000000u);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(dsrd, (lds_ptr)(sInB + bufbytes + r * XROWB), 16, vo, soff, 0, 0);
-    };
-    if (lane < 51) {
-      if constexpr (TRI) {        // exactly 8 pieces per wave (the surplus one of waves 4-7 repeats row 59): the chunk-end wait counts on it
-        static_assert(!TRI || !XASYM, "three staging buffers: symmetric issue only");
-#pragma unroll 1
-        for (int j = 0; j < 8; ++j) { const int r0 = wave + 8 * j; one_row(r0 < XROWS ? r0 : XROWS - 1); }
-      } else if constexpr ((XS & 8) != 0) {      // unrolled: the compiler counts the pieces in its vmcnt waits (a rolled loop makes it assume none were issued)
-        int w0 = XASYM ? wave - 4 : wave;
-#pragma unroll
-        for (int j = 0; j < (XASYM ? 15 : 8); ++j) {
-          asm volatile("" : "+s"(w0));      // opaque: the row arithmetic is redone per piece instead of living in SGPRs across the main loop
-          const int r0 = w0 + (XASYM ? 4 : 8) * j;
-          one_row(r0 < XROWS ? r0 : XROWS - 1);      // (the surplus piece of waves 4-7 repeats row 59: same bytes, same place)
-        }
-      } else {
-#pragma unroll 1
-        for (int r = XASYM ? wave - 4 : wave; r < XROWS; r += XASYM ? 4 : 8) one_row(r);
-      }
-    }
-  };
-
-  // ---- PREC = 1 staging plan: thread p < 400 owns the z-column (hy, hx, channel quad) of the halo block -------------------------
-  unsigned soz[6];
-  const int colp = tid < BCOL ? tid : BCOL - 1;
-  const int chy = colp / 40, chx = (colp >> 2) % 10, cq4 = colp & 3;
-  const int ldsz = (chy * BPY + chx) * BPOS + cq4 * 16;      // bytes, plane 0 of buffer 0
-  auto set_offs_b = [&](const BlockInfo& bi) {
-    const int gy = bi.y0 - 1 + chy, gx = bi.x0 - 1 + chx;
-    const bool okyx = tid < BCOL && static_cast<unsigned>(gy) < static_cast<unsigned>(a.H) && static_cast<unsigned>(gx) < static_cast<unsigned>(a.W);
-#pragma unroll
-    for (int z = 0; z < 6; ++z) {
-      const int gz = bi.z0 - 1 + z;
-      const bool ok = okyx && static_cast<unsigned>(gz) < static_cast<unsigned>(a.D);
-      if (UP) {
-        const int Hc = a.H >> 1, Wc = a.W >> 1;
-        soz[z] = ok ? static_cast<unsigned>((((gz >> 1) * Hc + (gy >> 1)) * Wc + (gx >> 1)) * a.Cin + cq4 * 4) * 4u : 0x80000000u;
-      } else {
-        soz[z] = ok ? static_cast<unsigned>(bi.hoff + ((z * a.H + chy) * a.W + chx) * a.Cin + cq4 * 4) * 4u : 0x80000000u;
-      }
-    }
-  };
-  auto vsub4 = [](const f32x4& p, const f32x4& q) -> f32x4 {      // plain v_sub_f32 x 4 (hipcc would form v_pk_add_f32)
-    f32x4 d;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { float t; asm("v_sub_f32 %0, %1, %2" : "=v"(t) : "v"(p[e]), "v"(q[e])); d[e] = t; }
-    return d;
-  };
-  auto vadd4 = [](const f32x4& p, const f32x4& q) -> f32x4 {
-    f32x4 d;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { float t; asm("v_add_f32 %0, %1, %2" : "=v"(t) : "v"(p[e]), "v"(q[e])); d[e] = t; }
-    return d;
-  };
-  auto stage_store_b = [&](int bufbytes, const f32x4 (&pl)[6]) {      // z part of B^T (same operations as the PREC = 0 lanes apply) + 8 stores
-    if (tid < BCOL) {
-      char* d = sInB + (bufbytes + ldsz);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        *reinterpret_cast<f32x4*>(d + (t * 4 + 0) * BPLANE) = vsub4(pl[2 * t], pl[2 * t + 2]);
-        *reinterpret_cast<f32x4*>(d + (t * 4 + 1) * BPLANE) = vadd4(pl[2 * t + 1], pl[2 * t + 2]);
-        if (!P27) *reinterpret_cast<f32x4*>(d + (t * 4 + 2) * BPLANE) = vsub4(pl[2 * t + 2], pl[2 * t + 1]);
-        *reinterpret_cast<f32x4*>(d + (t * 4 + 3) * BPLANE) = vsub4(pl[2 * t + 1], pl[2 * t + 3]);
-      }
     }
   };
 
@@ -498,9 +379,6 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
   f32x2 T[8], U[8];        // after the z / y transform
   f32x2 A2[8];             // A operands of a k-step: A2[xi_y*2 + h] = (xi_x = 2h, 2h+1)
   const int offAb = offA * 4, offBb = offB * 4;      // bytes (multiples of 8)
-  // XS: x pair h of this lane's tile = floats 2 tx + 2 h, + 1 of the row = piece (tx + h) >> 1, element 2 ((tx + h) & 1)
-  const int xrowA = ((2 * mth + za) * 10 + 2 * ty) * XROWB + kq * 16, xrowB = ((2 * mth + zb) * 10 + 2 * ty) * XROWB + kq * 16;
-  const int xp0 = (tx >> 1) * (17 * 16) + (tx & 1) * 8, xp1 = ((tx + 1) >> 1) * (17 * 16) + ((tx + 1) & 1) * 8;
   auto raw_read_up = [&](int idxbytes) {      // idxbytes: LDS byte offset of channel plane 4 ks (+ buffer)
     int ia = idxbytes + uoffA, ib = idxbytes + uoffB;
     asm volatile("" : "+v"(ia), "+v"(ib));
@@ -510,18 +388,6 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
     for (int r = 0; r < 3; ++r) {
       ua[r] = *reinterpret_cast<const f32x4*>(sInB + ia + r * UPY * 4);
       ub[r] = *reinterpret_cast<const f32x4*>(sInB + ib + r * UPY * 4);
-    }
-  };
-  auto raw_read_x = [&](int idxbytes) {   // idxbytes: buffer + 64 ks (the k-step's 4 channels are slots 4 ks .. 4 ks + 3)
-    int ia0 = idxbytes + xrowA + xp0, ia1 = idxbytes + xrowA + xp1, ib0 = idxbytes + xrowB + xp0, ib1 = idxbytes + xrowB + xp1;
-    asm volatile("" : "+v"(ia0), "+v"(ia1), "+v"(ib0), "+v"(ib1));
-    __builtin_assume((ia0 & 7) == 0); __builtin_assume((ia1 & 7) == 0); __builtin_assume((ib0 & 7) == 0); __builtin_assume((ib1 & 7) == 0);
-#pragma unroll
-    for (int y = 0; y < 4; ++y) {
-      ra[y * 2 + 0] = *reinterpret_cast<const f32x2*>(sInB + ia0 + y * XROWB);
-      ra[y * 2 + 1] = *reinterpret_cast<const f32x2*>(sInB + ia1 + y * XROWB);
-      rb[y * 2 + 0] = *reinterpret_cast<const f32x2*>(sInB + ib0 + y * XROWB);
-      rb[y * 2 + 1] = *reinterpret_cast<const f32x2*>(sInB + ib1 + y * XROWB);
     }
   };
   auto raw_read = [&](int idxbytes) {   // idxbytes: LDS byte offset of plane 4 ks (+ buffer), without this lane's offset
@@ -574,98 +440,28 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
 
   // ---- B operand ------------------------------------------------------------------------------------------------------------
   const int nk4 = a.Cin >> 2;
-  // XS & 32: TWO weight register sets (even / odd k-steps): a row is reloaded right behind its MFMAs with the weights of k-step + 2, i.e.
-  // every weight load has two k-steps (~3000 cycles) to come back instead of one -- the staging pieces' HBM misses sit in front of the
-  // weight loads in the CU's in-order vector-memory return path (the DMA staging freed the registers for it)
-  constexpr int NBQ = (XS & 32) ? 2 : 1;
-  f32x4 bq[NBQ][2][4];     // [k-step parity][cout 16-block][xi_y] = (xi_x 0..3)
+  f32x4 bq[2][4];          // [cout 16-block][xi_y] = (xi_x 0..3)
   const unsigned laneb = static_cast<unsigned>(lane) * 16u;
   const __amdgpu_buffer_rsrc_t wsrd = make_srd(a.wp, static_cast<unsigned>(a.Cin) * a.Cout * 256u);
   const unsigned wbase_b = static_cast<unsigned>((cs * 4 + mz) * nk4) * 8192u + static_cast<unsigned>(hnb) * 4096u;
-  auto issue_b = [&](int nb, int k4) {
+  auto issue_bq = [&](int nb, int k4) {
     const int kl = k4 < nk4 ? k4 : 0;        // wraps to the first k-step of the next tile block
     const unsigned sb = wbase_b + static_cast<unsigned>(kl) * 8192u + nb * 4096u;      // wave-uniform
 #pragma unroll
-    for (int q = 0; q < 4; ++q) bq[0][nb][q] = buf_load16(wsrd, laneb + q * 1024u, sb);
-  };
-  auto issue_b1 = [&](int nb) {      // NBQ == 2: k-step 1 into the odd set
-#pragma unroll
-    for (int q = 0; q < 4; ++q) bq[NBQ - 1][nb][q] = buf_load16(wsrd, laneb + q * 1024u, wbase_b + 8192u + nb * 4096u);
-  };
-
-  // ---- PREC = 1: A operands of a k-step = (chunk, xi_y = j); B operands ------------------------------------------------------------
-  const int aoffB = (mth * 4 + mz) * BPLANE + ((2 * ty) * BPY + 2 * tx) * BPOS + kq * 16;      // this lane's tile, its plane, its channel quad
-  f32x4 rwa[4], rwb[4];      // the two rows of the y combination: 4 positions x 4 channels each
-  u32x2 Ah[4], Al[4];        // [xi_x]: packed bf16 (hi | lo) of the lane's 4 channels
-  auto raw_read_b = [&](int bufbytes, int j) {
-    const int rA = j == 0 ? 0 : j == 2 ? 2 : 1, rB = j == 0 ? 2 : j == 1 ? 2 : j == 2 ? 1 : 3;      // U = row rA -+ row rB
-    int ia = bufbytes + aoffB;
-    asm volatile("" : "+v"(ia));
-    __builtin_assume((ia & 15) == 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      rwa[i] = *reinterpret_cast<const f32x4*>(sInB + ia + (rA * BPY + i) * BPOS);
-      rwb[i] = *reinterpret_cast<const f32x4*>(sInB + ia + (rB * BPY + i) * BPOS);
-    }
-  };
-  auto split2 = [](float v0, float v1, unsigned& hi, unsigned& lo) {
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi) : "v"(v0), "v"(v1));
-    const float h0 = __builtin_bit_cast(float, hi << 16), h1 = __builtin_bit_cast(float, hi & 0xffff0000u);
-    float l0, l1;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(l0) : "v"(v0), "v"(h0));
-    asm("v_sub_f32 %0, %1, %2" : "=v"(l1) : "v"(v1), "v"(h1));
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo) : "v"(l0), "v"(l1));
-  };
-  auto transform_b = [&](int j) {
-    f32x4 Uy[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) Uy[i] = j == 1 ? vadd4(rwa[i], rwb[i]) : vsub4(rwa[i], rwb[i]);
-#pragma unroll
-    for (int xx = 0; xx < 4; ++xx) {
-      if (P27 && xx == 2) continue;
-      const f32x4 v = xx == 0 ? vsub4(Uy[0], Uy[2]) : xx == 1 ? vadd4(Uy[1], Uy[2]) : xx == 2 ? vsub4(Uy[2], Uy[1]) : vsub4(Uy[1], Uy[3]);
-      unsigned h01, l01, h23, l23;
-      split2(v[0], v[1], h01, l01);
-      split2(v[2], v[3], h23, l23);
-      Ah[xx] = u32x2{h01, h23};
-      Al[xx] = u32x2{l01, l23};
-    }
-  };
-  u32x4 bw[2][4];            // [cout 16-block][xi_x] = (hi k0k1, hi k2k3, lo k0k1, lo k2k3)
-  const unsigned wbaseB = static_cast<unsigned>((cs * 4 + mz) * (a.Cin >> 4)) * 32768u + static_cast<unsigned>(hnb) * 1024u;
-  auto issue_bw = [&](int nb, int k16, int j) {      // record (k16, xi_y = j): 4 xi_x x 2 cout blocks x 1 KB
-    const unsigned sb = wbaseB + static_cast<unsigned>(k16 * 4 + j) * 8192u + nb * 1024u;      // wave-uniform
-#pragma unroll
-    for (int xx = 0; xx < 4; ++xx)
-      if (!(P27 && xx == 2)) bw[nb][xx] = __builtin_bit_cast(u32x4, buf_load16(wsrd, laneb, sb + xx * 2048u));
+    for (int q = 0; q < 4; ++q) bq[nb][q] = buf_load16(wsrd, laneb + q * 1024u, sb);
   };
 
   f32x4 acc[2][16];
   const int nchunk = a.Cin / CKW;
-  // (experiments 1048576 / 2097152: the 5 staging loads of a thread are not issued as one burst behind k-step 0's MFMAs -- all 8 waves at the same
-  //  moment: 40 instructions of 16 lines each into the CU's vector-memory path -- but ONE per MFMA row, behind that row's weight reload, during
-  //  k-step 1 (stores just before the chunk barrier) / during k-step 0 (stores in k-step 2 as in production))
-  constexpr bool SPREAD1 = (DBG & 1048576) != 0, SPREAD0 = (DBG & 2097152) != 0, SPREAD = SPREAD1 || SPREAD0;
 
   // ---- prologue: first block's chunk 0 -> buffer 0 ------------------------------------------------------------------------------
   BlockInfo cur = decode(seq(0));
-  if constexpr (BX) {
-    set_offs_b(cur);
-    const __amdgpu_buffer_rsrc_t srd0 = make_srd(cur.xb, vol_bytes);
-    f32x4 stz[6];
-#pragma unroll
-    for (int z = 0; z < 6; ++z) stz[z] = buf_load16(srd0, soz[z], 0u);
-    stage_store_b(0, stz);
-  } else if constexpr (XB) {
-    issue_dma(0, cur, 0u);
-    if constexpr (TRI) { issue_dma(BUFk * 4, cur, 256u); asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else {
+  {
     set_offs(cur);
     const __amdgpu_buffer_rsrc_t srd0 = make_srd(cur.xb, vol_bytes);
     f32x4 stg[NLOAD];
 #pragma unroll
-    for (int it = 0; it < NL; ++it) if (stage_pass(it)) stg[it] = stage_load(it, srd0, 0u);
+    for (int it = 0; it < NL; ++it) if (stage_pass(it)) stg[it] = buf_load16(srd0, so[it], 0u);
     stage_store_all(0, stg);
   }
   __syncthreads();
@@ -678,20 +474,13 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[nb][i] = f32x4{0.f, 0.f, 0.f, 0.f};
     // first raw inputs of this block (and, for the worker's first block, the weights of k-step 0)
-    if constexpr (BX) {
-      raw_read_b(pb * BBUF, 0);
-      issue_bw(0, 0, 0);
-      if (!half) issue_bw(1, 0, 0);
-    } else {
-      if constexpr (XB) raw_read_x(pb * BUFk * 4); else raw_read(pb * BUFk * 4);      // (TRI: pb = chunk counter mod 3)
-      // [r3] the weights of k-step 0 are the same for every tile block of the worker and the last k-step of a block has already reloaded
-      // them (issue_b / reload_row wrap around): they stay in their registers across the epilogue (16.13 -> 16.05 ms per top-level
-      // launch; tuning variant 65536 = reloaded at every block start)
-      if (it == 0) {
-        issue_b(0, 0);
-        if (!half) issue_b(1, 0);
-        if (NBQ == 2) { issue_b1(0); if (!half) issue_b1(1); }
-      }
+    raw_read(pb * BUFF * 4);
+    // [r3] the weights of k-step 0 are the same for every tile block of the worker and the last k-step of a block has already reloaded
+    // them (issue_bq / reload_row wrap around): they stay in their registers across the epilogue (16.13 -> 16.05 ms per top-level
+    // launch; tuning variant 65536 = reloaded at every block start)
+    if (it == 0) {
+      issue_bq(0, 0);
+      if (!half) issue_bq(1, 0);
     }
 
     // The 16 lrelu-mask operands of this lane's outputs go global -> LDS by DMA loads (in registers hipcc spills each one to scratch
@@ -712,12 +501,8 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
           __builtin_amdgcn_raw_ptr_buffer_load_lds(msrd, (lds_ptr)(sMs + (n2 * 8 + s) * kT + wave * 64), 4, mv, so_, 0, 0);
         }
     };
-    auto main_loop = [&](auto half_c, auto lw_c) {
+    auto main_loop = [&](auto half_c) {
     constexpr bool HALF = decltype(half_c)::value;      // this wave owns one 16-cout block only (acc[0], weights of block hnb)
-    // (experiment XS & 64, timing only: this copy of the loop -- taken by waves 4-7 -- reads its "weights" from LDS (whatever is there) instead of
-    //  global memory: the vmcnt queue of the waves that stage (4-7 with XS & 2) then holds the staging pieces only -- what a design in which
-    //  the weights arrive through an LDS ring would give them; the ring's own fill traffic is not modelled)
-    constexpr bool LW = decltype(lw_c)::value;
     for (int chunk = 0; chunk < nchunk; ++chunk) {
       const int bo = ((chunk + pb) & 1) * BUFF * 4, bn = BUFF * 4 - bo;      // byte offsets of this / the next chunk's buffer
       const bool lastc = chunk + 1 == nchunk;
@@ -730,22 +515,8 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
         // -- A operands of this k-step (its raw inputs were requested during the previous one) --
         transform();
         __builtin_amdgcn_sched_barrier(0);
-        if (!XB && ks == (SPREAD1 ? 3 : 2) && !(DBG & 4) && !(DBG & 64)) {
+        if (ks == 2) {
           stage_store_all(bn, stg);
-        }
-        // XS: the DMA pieces of the next chunk have landed once at most the 8 (4) weight reloads of k-step 2 are outstanding behind them
-        if (XB && ks == 3) {      // (every wave: one that issued no pieces has only those reloads outstanding and does not wait)
-          constexpr int NWL = (LW ? 0 : (P27 ? 3 : 4) * (HALF ? 1 : 2) * NBQ) + (TRI ? 8 : 0);      // loads issued behind the pieces that must have landed
-          if constexpr (NWL == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          else if constexpr (NWL == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-          else if constexpr (NWL == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-          else if constexpr (NWL == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-          else if constexpr (NWL == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-          else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        }
-        if (ks == 2 && (DBG & 64)) {       // keep the loads alive without the LDS writes
-#pragma unroll
-          for (int it = 0; it < NL; ++it) if (stage_pass(it)) asm volatile("" :: "v"(stg[it]));
         }
         // next chunk staged by everyone; everyone is done reading the planes it overwrote.  [r3] An LDS-only barrier: the staged data was
         // already waited for at the LDS writes of ks == 2, and __syncthreads()' vmcnt(0) drained the weight loads in flight (this and the
@@ -757,17 +528,16 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
         // flight up to 12 MFMAs longer before the next k-step needs it (16.52 -> 16.27 ms per top-level launch; tuning variant 196608 = the
         // old order)
         auto reload_row = [&](int nb, int q) {
-          if ((DBG & 8) || (P27 && q == 2)) return;
-          const int k4 = chunk * 4 + ks + NBQ;
+          if (P27 && q == 2) return;
+          const int k4 = chunk * 4 + ks + 1;
           const int kl = k4 < nk4 ? k4 : k4 - nk4;      // wraps to the first k-step(s) of the next tile block
           const unsigned sb = wbase_b + static_cast<unsigned>(kl) * 8192u + nb * 4096u;
-          if constexpr (LW) bq[ks & (NBQ - 1)][nb][q] = *reinterpret_cast<const f32x4*>(sInB + bo + (nb * 4 + q) * 1024 + lane * 16);
-          else bq[ks & (NBQ - 1)][nb][q] = buf_load16(wsrd, laneb + q * 1024u, sb);
+          bq[nb][q] = buf_load16(wsrd, laneb + q * 1024u, sb);
         };
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           if (!P27 || ((i >> 2) != 2 && (i & 3) != 2))
-            acc[0][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A2[i >> 1][i & 1], bq[ks & (NBQ - 1)][0][i >> 2][i & 3], acc[0][i], 0, 0, 0);
+            acc[0][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A2[i >> 1][i & 1], bq[0][i >> 2][i & 3], acc[0][i], 0, 0, 0);
           if ((i & 3) == 3) {
             __builtin_amdgcn_sched_barrier(0);
             reload_row(0, i >> 2);
@@ -780,7 +550,7 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             if (!P27 || ((i >> 2) != 2 && (i & 3) != 2))
-              acc[1][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A2[i >> 1][i & 1], bq[ks & (NBQ - 1)][1][i >> 2][i & 3], acc[1][i], 0, 0, 0);
+              acc[1][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(A2[i >> 1][i & 1], bq[1][i >> 2][i & 3], acc[1][i], 0, 0, 0);
             if ((i & 3) == 3) {
               __builtin_amdgcn_sched_barrier(0);
               reload_row(1, i >> 2);
@@ -789,100 +559,17 @@ __global__ __launch_bounds__(kT, 1) void wino3d_kernel(const WinoArgs a) {
           }
           __builtin_amdgcn_sched_barrier(0);
         }
-        if (XB && !TRI && !(XS & 20) && ks == 0 && !(DBG & 4)) issue_dma(bn, lastc ? nxt : cur, schunk);
-        if (!XB && !SPREAD && ks == 0 && !(DBG & 4)) {     // staging loads of the next chunk, right behind a weight batch: vmcnt retires in order, so
+        if (ks == 0) {     // staging loads of the next chunk, right behind a weight batch: vmcnt retires in order, so
                                          // the first wait that covers them is the one for the NEXT weight batch (1.5 k-steps away)
 #pragma unroll
           for (int it = 0; it < NL; ++it)
-            if (stage_pass(it)) stg[it] = stage_load(it, ssrd, schunk);
+            if (stage_pass(it)) stg[it] = buf_load16(ssrd, so[it], schunk);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
     }
     };
-    // PREC = 1: k-step = (chunk, xi_y); the 27-point modes skip xi_y = 2 (and the xi_x = 2 products)
-    auto main_loop_b = [&](auto half_c) {
-      constexpr bool HALF = decltype(half_c)::value;
-      constexpr int NST = P27 ? 3 : 4;
-      for (int chunk = 0; chunk < nchunk; ++chunk) {
-        const int bo = ((chunk + pb) & 1) * BBUF, bn = BBUF - bo;
-        const bool lastc = chunk + 1 == nchunk;
-        if (lastc) set_offs_b(nxt);
-        const __amdgpu_buffer_rsrc_t ssrd = make_srd(lastc ? nxt.xb : cur.xb, vol_bytes);
-        const unsigned schunk = static_cast<unsigned>(lastc ? 0 : chunk + 1) * (CKW * 4u);
-        const int cnext = lastc ? 0 : chunk + 1;      // (the weights of the next tile block's first k-step)
-        f32x4 stz[6];
-#pragma unroll
-        for (int st = 0; st < NST; ++st) {
-          const int j = P27 && st == 2 ? 3 : st;                                   // xi_y of this k-step
-          const int jn = st + 1 < NST ? (P27 && st + 1 == 2 ? 3 : st + 1) : 0;     // ... and of the next one
-          const int kn = st + 1 < NST ? chunk : cnext;
-          if (!(DBG & 1)) transform_b(j);
-          __builtin_amdgcn_sched_barrier(0);
-          constexpr int STS = (DBG & 16) ? NST - 1 : NST - 2;      // (experiment 16: store the staged chunk one k-step later)
-          if (st == STS && !(DBG & 4)) stage_store_b(bn, stz);
-          if (st == NST - 1) __syncthreads();
-          if (!(DBG & 2)) raw_read_b(st + 1 < NST ? bo : bn, jn);
-          __builtin_amdgcn_sched_barrier(0);
-          auto mfma_nb = [&](int nb) {
-            if (DBG & 32) {      // (experiment 32: xi_x-major -- a point's three products back to back, its weight registers reloaded at once)
-#pragma unroll
-              for (int xx = 0; xx < 4; ++xx)
-                if (!(P27 && xx == 2)) {
-#pragma unroll
-                  for (int t = 0; t < 3; ++t) {
-                    const u32x2 av = t == 0 ? Al[xx] : Ah[xx];
-                    const u32x2 bv = t == 1 ? u32x2{bw[nb][xx][2], bw[nb][xx][3]} : u32x2{bw[nb][xx][0], bw[nb][xx][1]};
-                    acc[nb][j * 4 + xx] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, av), __builtin_bit_cast(s16x4, bv),
-                                                                                    acc[nb][j * 4 + xx], 0, 0, 0);
-                  }
-                  __builtin_amdgcn_sched_barrier(0);
-                  if (!(DBG & 8)) {
-                    const unsigned sb = wbaseB + static_cast<unsigned>(kn * 4 + jn) * 8192u + nb * 1024u;
-                    bw[nb][xx] = __builtin_bit_cast(u32x4, buf_load16(wsrd, laneb, sb + xx * 2048u));
-                  }
-                  __builtin_amdgcn_sched_barrier(0);
-                }
-            } else {
-#pragma unroll
-              for (int t = 0; t < 3; ++t)
-#pragma unroll
-                for (int xx = 0; xx < 4; ++xx)
-                  if (!(P27 && xx == 2)) {
-                    const u32x2 av = t == 0 ? Al[xx] : Ah[xx];
-                    const u32x2 bv = t == 1 ? u32x2{bw[nb][xx][2], bw[nb][xx][3]} : u32x2{bw[nb][xx][0], bw[nb][xx][1]};
-                    acc[nb][j * 4 + xx] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, av), __builtin_bit_cast(s16x4, bv),
-                                                                                    acc[nb][j * 4 + xx], 0, 0, 0);
-                  }
-              __builtin_amdgcn_sched_barrier(0);
-              if (!(DBG & 8)) issue_bw(nb, kn, jn);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-          };
-          if (st == 0 && (DBG & 64)) {      // (experiment 64: staging loads ahead of the k-step's MFMAs)
-#pragma unroll
-            for (int z = 0; z < 6; ++z) stz[z] = buf_load16(ssrd, soz[z], schunk);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-          mfma_nb(0);
-          if (!HALF) mfma_nb(1);
-          if (st == 0 && !(DBG & 4) && !(DBG & 64)) {      // staging loads of the next chunk, right behind a weight batch (see the PREC = 0 loop)
-#pragma unroll
-            for (int z = 0; z < 6; ++z) stz[z] = buf_load16(ssrd, soz[z], schunk);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    };
-    if constexpr (BX) {
-      if (half) main_loop_b(std::true_type{}); else main_loop_b(std::false_type{});
-    } else {
-      if constexpr ((XS & 64) != 0) {
-        main_loop(std::false_type{}, std::true_type{});      // (every wave: a single copy of the loop -- two copies in one kernel spill 150-250 B)
-      } else {
-        if (half) main_loop(std::true_type{}, std::false_type{}); else main_loop(std::false_type{}, std::false_type{});
-      }
-    }
+    if (half) main_loop(std::true_type{}); else main_loop(std::false_type{});
 
     // ---- epilogue: inverse transform in x, y per accumulator element; z across the waves through the idle LDS buffer ---------
     // (the buffer of the last chunk is free since that chunk's barrier; the other one holds the next block's chunk 0)
