@@ -242,6 +242,17 @@ SIGNATURES = {
     "df_resample_count3d": (I32, [P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I32, I32, I32, F32, P]),
     "df_resample_scatter2d": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I32, U32, U32, P]),
     "df_resample_scatter3d": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I32, U32, U32, P]),
+    "df_mg_hierarchy_bytes": (I64, [I32, I64, I64, I64, I64]),
+    "df_mg_levels": (I32, [I32, I64, I64, I64]),
+    "df_mg_sweeps": (I32, [I32]),
+    "df_mg_omega": (F32, []),
+    "df_mg_cycle_launches": (I32, [I32, I64, I64, I64]),
+    "df_mg_level_offset": (I64, [I32, I64, I64, I64, I64, I32, I32]),
+    "df_mg_build": (I32, [P, I64, P, I32, I64, I64, I64, I64, I32, I32, P]),
+    "df_mg_apply": (I32, [P, I64, P, I32, I64, I64, I64, I64, F32, P]),
+    "df_pressure_mg_precondition": (I32, [P, I64, P, I64, I32, I64, I64, I64, I64, F32, I64, P]),
+    "df_pressure_cg_direction_mg": (I32, [P, I64, P, I64, P, I32, I64, I64, I64, I64, I32, I32, I64, F32, I64, P]),
+    "df_pressure_cg_update_mg": (I32, [P, P, I64, P, I32, I64, I64, I64, I64, I32, I64, P]),
 }
 
 DF_CONV_LRELU, DF_CONV_RESIDUAL, DF_CONV_MASK, DF_CONV_BIAS, DF_CONV_ADDUP, DF_CONV_VALU_ONLY = 1, 2, 4, 8, 16, 32

@@ -1,0 +1,667 @@
+// Multigrid V-cycle preconditioner of the smoke pressure solve, written for gfx950 from the definition in include/deepfluids_hip.h
+// ("multigrid preconditioner"); tests/smoke_mg_ref.py restates it, and its fp32 twin gives the bits of these kernels: every pass is a
+// pointwise stencil, the sums run in a fixed order, nothing is contracted (-ffp-contract=off) and nothing is reduced across cells.
+//
+//   hierarchy      one float32 block per hierarchy: per level the face weights w_a[c] (face between c and c - e_a), dir, diag, the
+//                  level's right-hand side (level 0: z) and two x buffers, each [B, cells of the level].  Level 0 is the solve's own grid
+//                  (band included); its weights are written once by mg_level0_kernel from the flags byte / the index tests / open_sides,
+//                  so every level runs the same kernels.  Level l + 1 is the Galerkin product with piecewise-constant aggregates of 2^D
+//                  children: one thread per coarse cell gathers, no atomics.  The counts are small integers: exact in float32.
+//   V-cycle        four launches per level of more than 1024 cells (and level 0), one thread per cell (restriction: per coarse cell); the
+//                  smaller levels all run in ONE launch, mg_small_kernel, one workgroup per batch entry walking them down and up with the
+//                  same cell functions (without it a cycle is launch-bound on exactly the jobs that are launch-bound today).  Jacobi
+//                  sweeps ping-pong between the two x buffers so that no thread reads a word another thread of the pass writes:
+//     presmooth2   two damped-Jacobi sweeps from x = 0 in one launch: the first is (omega r) / diag pointwise, so the second takes its
+//                  neighbours' values from r directly.
+//     restrict     residual of the children computed on the fly and summed in ascending x, then y, then z.
+//     correct_sweep  x + alpha e[parent] formed on the fly at the cell and its neighbours, then one sweep.
+//     sweep        one sweep; on level 0 it writes z and the workgroup's r.z partial (the `rr` partials of the solve's workspace).
+//                  The coarsest level (every extent <= 2) runs presmooth2 and six sweeps (inside mg_small_kernel).
+//   iteration      cg_direction_mg / cg_update_mg: the solve's two kernels for the preconditioned recurrence, as cg_direction_gf /
+//                  cg_update_gf have it: `rr` holds r.z, p = z + beta p.  update writes r and the max|r| partials; z comes from the
+//                  cycle that runs after it.  Every V-cycle kernel returns at once for an entry whose CgState::active is 0.
+//   The levels are L2 resident at the sizes this is used for; the arrays are planar and every access of a pass is coalesced along x.
+#include "smoke_common.hpp"
+
+namespace {
+
+using df::ceil_div;
+using dfadv::apart;
+using dfadv::hi_bit;
+using dfadv::lo_bit;
+
+constexpr int kMaxLevels = 26;                          // extents < 2^24
+constexpr float kOmega = 2.0f / 3.0f;
+constexpr int kNu = 2;                                  // pre- and post-sweeps; mg_presmooth2 fuses exactly two
+constexpr int kCoarsestSweeps = 8;
+constexpr int kSmallCells = 1024;                       // levels (above level 0) of at most this many cells run in the one-workgroup kernel
+constexpr int kSmallLevels = 12;                        // 1024 cells halve to nothing in at most 11 steps
+static_assert(kNu == 2 && kCoarsestSweeps % 2 == 0, "the fused pre-sweep and the ping-pong of the coarsest level");
+
+struct MgLevel {   // one level, all B entries; every array [B, n]
+  float *w[3], *dir, *diag, *r, *xa, *xb;
+  int64_t n;
+  int nblk, Z, Y, X;
+};
+
+struct MgPlan {
+  int levels, D;
+  int64_t B, floats;
+  MgLevel lev[kMaxLevels];
+  int64_t off[kMaxLevels][8];                           // float offsets of w[0..2], dir, diag, r, xa, xb inside the block (-1: none)
+};
+
+struct MgSmall {   // the levels of the one-workgroup kernel, finest first
+  int count;
+  MgLevel lev[kSmallLevels];
+};
+
+struct MgCell {
+  int e, j;
+  int64_t cell;
+  int p[3];
+  bool in;
+};
+
+template <int D>
+__device__ __forceinline__ void mcoords(const MgLevel& L, int64_t cell, int* p) {
+  const int64_t row = cell / L.X;
+  p[0] = static_cast<int>(cell - row * L.X);
+  p[1] = static_cast<int>(row % L.Y);
+  p[2] = D == 3 ? static_cast<int>(row / L.Y) : 0;
+}
+
+template <int D>
+__device__ __forceinline__ MgCell mdecode(const MgLevel& L) {
+  MgCell c;
+  c.e = static_cast<int>(blockIdx.x / static_cast<unsigned>(L.nblk));
+  c.j = static_cast<int>(blockIdx.x - static_cast<unsigned>(c.e) * static_cast<unsigned>(L.nblk));
+  c.cell = static_cast<int64_t>(c.j) * kThreads + threadIdx.x;
+  mcoords<D>(L, c.cell, c.p);
+  c.in = c.cell < L.n;
+  return c;
+}
+
+__device__ __forceinline__ bool mg_idle(const CgState* __restrict__ st, int e) { return st && !st[e].active; }
+
+// (A x)[c] = diag[c] x[c] - sum, the sum from 0 in the order x-, x+, y-, y+[, z-, z+] over the neighbours inside the grid, each term
+// w * x.  `x(k, a, s)`: the value at cell k, which is c displaced by s along axis a.
+template <int D, class F>
+__device__ __forceinline__ float mg_Ax(const MgLevel& L, int64_t eo, const int* p, int64_t c, float xc, F x) {
+  const int64_t st[3] = {1, L.X, static_cast<int64_t>(L.X) * L.Y};
+  const int ext[3] = {L.X, L.Y, L.Z};
+  float sum = 0.0f;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    if (p[a] > 0) sum += L.w[a][eo + c] * x(c - st[a], a, -1);
+    if (p[a] + 1 < ext[a]) sum += L.w[a][eo + c + st[a]] * x(c + st[a], a, 1);
+  }
+  return L.diag[eo + c] * xc - sum;
+}
+
+// one damped-Jacobi sweep at c: x + (omega (r - A x)) / diag, 0 on an inactive cell
+template <int D, class F>
+__device__ __forceinline__ float mg_jacobi(const MgLevel& L, int64_t eo, const int* p, int64_t c, float rc, float xc, F x) {
+  const float dg = L.diag[eo + c];
+  if (!(dg > 0.0f)) return 0.0f;
+  const float t = rc - mg_Ax<D>(L, eo, p, c, xc, x);
+  return xc + (kOmega * t) / dg;
+}
+
+// ---- the hierarchy -------------------------------------------------------------------------------------------------------------------------
+// level 0 from the solve's own tests: a cell is fluid as pdecode has it (interior by its index, and the flags byte's bit 0 where there are
+// flags); w_a = 1 between two fluid cells; dir = the open neighbours of a fluid cell (what OPEN adds to n_c in cg_direction_kernel)
+template <int D>
+__global__ __launch_bounds__(kThreads) void mg_level0_kernel(MgLevel L, const uint8_t* __restrict__ flags, int bnd, int os) {
+  const MgCell c = mdecode<D>(L);
+  if (!c.in) return;
+  const int64_t g = static_cast<int64_t>(c.e) * L.n + c.cell;
+  const int ext[3] = {L.X, L.Y, L.Z};
+  bool interior = true;
+#pragma unroll
+  for (int a = 0; a < D; ++a) interior = interior && c.p[a] >= bnd && c.p[a] < ext[a] - bnd;
+  const unsigned fl = (flags && interior) ? flags[g] : 0u;   // a flags byte is only believed where the cell is interior by its index
+  const bool fluid = flags ? (fl & kFluid) != 0u : interior;
+  int cnt = 0, dir = 0;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    const bool lo = fluid && (flags ? (fl & lo_bit(a)) != 0u : c.p[a] > bnd);
+    const bool hi = fluid && (flags ? (fl & hi_bit(a)) != 0u : c.p[a] + 1 < ext[a] - bnd);
+    L.w[a][g] = lo ? 1.0f : 0.0f;
+    cnt += (lo ? 1 : 0) + (hi ? 1 : 0);
+    if (fluid) dir += ((c.p[a] == bnd && ((os >> (2 * a)) & 1)) ? 1 : 0) + ((c.p[a] + 1 == ext[a] - bnd && ((os >> (2 * a + 1)) & 1)) ? 1 : 0);
+  }
+  L.dir[g] = static_cast<float>(dir);
+  L.diag[g] = static_cast<float>(cnt + dir);
+}
+
+// the fine faces of axis a with i_a = ia and the other coordinates inside aggregate P, summed in ascending x, then y, then z
+template <int D>
+__device__ __forceinline__ float mg_face_sum(const MgLevel& F, int64_t eo, const int* P, int a, int ia) {
+  const int ext[3] = {F.X, F.Y, F.Z};
+  float s = 0.0f;
+  for (int dz = 0; dz < (D == 3 ? 2 : 1); ++dz)
+    for (int dy = 0; dy < 2; ++dy)
+      for (int dx = 0; dx < 2; ++dx) {
+        const int d[3] = {dx, dy, dz};
+        if (d[a] != 0) continue;
+        int q[3] = {2 * P[0] + dx, 2 * P[1] + dy, 2 * P[2] + dz};
+        q[a] = ia;
+        if (q[0] >= ext[0] || q[1] >= ext[1] || q[2] >= ext[2]) continue;
+        s += F.w[a][eo + (static_cast<int64_t>(q[2]) * F.Y + q[1]) * F.X + q[0]];
+      }
+  return s;
+}
+
+// one thread = one coarse cell: its D low-face weights, dir, and diag (the high-face weights are summed again here, not read from the
+// thread that owns them: all of it is exact)
+template <int D>
+__global__ __launch_bounds__(kThreads) void mg_coarsen_kernel(MgLevel F, MgLevel C) {
+  const MgCell c = mdecode<D>(C);
+  if (!c.in) return;
+  const int64_t eoF = static_cast<int64_t>(c.e) * F.n, g = static_cast<int64_t>(c.e) * C.n + c.cell;
+  const int ext[3] = {F.X, F.Y, F.Z};
+  float tot = 0.0f;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    const float lo = mg_face_sum<D>(F, eoF, c.p, a, 2 * c.p[a]);     // i_a = 0 holds no face: its weights are 0 on every level
+    const float hi = 2 * c.p[a] + 2 < ext[a] ? mg_face_sum<D>(F, eoF, c.p, a, 2 * c.p[a] + 2) : 0.0f;
+    C.w[a][g] = lo;
+    tot += lo + hi;
+  }
+  float dir = 0.0f;
+  for (int dz = 0; dz < (D == 3 ? 2 : 1); ++dz)
+    for (int dy = 0; dy < 2; ++dy)
+      for (int dx = 0; dx < 2; ++dx) {
+        const int q[3] = {2 * c.p[0] + dx, 2 * c.p[1] + dy, 2 * c.p[2] + dz};
+        if (q[0] >= ext[0] || q[1] >= ext[1] || q[2] >= ext[2]) continue;
+        dir += F.dir[eoF + (static_cast<int64_t>(q[2]) * F.Y + q[1]) * F.X + q[0]];
+      }
+  C.dir[g] = dir;
+  C.diag[g] = tot + dir;
+}
+
+// ---- the V-cycle ---------------------------------------------------------------------------------------------------------------------------
+// The four passes at one cell (e: batch entry, p: the cell's coordinates); the kernels below run them one cell per thread, and
+// mg_small_kernel runs them level after level inside one workgroup.  No __restrict__ here: in mg_small_kernel a pass reads what the
+// pass before it wrote.
+template <int D>
+__device__ __forceinline__ void mg_presmooth2_at(const MgLevel& L, const float* r, float* xout, int e, int64_t cell, const int* p) {
+  const int64_t eo = static_cast<int64_t>(e) * L.n;
+  const float* re = r + eo;
+  const float* dg = L.diag + eo;
+  auto x1 = [&](int64_t k, int, int) { return dg[k] > 0.0f ? (kOmega * re[k]) / dg[k] : 0.0f; };
+  xout[eo + cell] = mg_jacobi<D>(L, eo, p, cell, re[cell], x1(cell, 0, 0), x1);
+}
+
+// at coarse cell `cell` of C: r_coarse = the sum over the children of r - A x (0 on an inactive child)
+template <int D>
+__device__ __forceinline__ void mg_restrict_at(const MgLevel& F, const MgLevel& C, const float* r, const float* x, int e, int64_t cell,
+                                               const int* p) {
+  const int64_t eo = static_cast<int64_t>(e) * F.n;
+  const float* xe = x + eo;
+  const int ext[3] = {F.X, F.Y, F.Z};
+  auto xv = [&](int64_t k, int, int) { return xe[k]; };
+  float s = 0.0f;
+  for (int dz = 0; dz < (D == 3 ? 2 : 1); ++dz)
+    for (int dy = 0; dy < 2; ++dy)
+      for (int dx = 0; dx < 2; ++dx) {
+        const int q[3] = {2 * p[0] + dx, 2 * p[1] + dy, 2 * p[2] + dz};
+        if (q[0] >= ext[0] || q[1] >= ext[1] || q[2] >= ext[2]) continue;
+        const int64_t k = (static_cast<int64_t>(q[2]) * F.Y + q[1]) * F.X + q[0];
+        if (F.diag[eo + k] > 0.0f) s += r[eo + k] - mg_Ax<D>(F, eo, q, k, xe[k], xv);
+      }
+  C.r[static_cast<int64_t>(e) * C.n + cell] = s;
+}
+
+template <int D>
+__device__ __forceinline__ void mg_correct_sweep_at(const MgLevel& F, const MgLevel& C, const float* r, const float* xin, const float* ec,
+                                                    float* xout, float alpha, int e, int64_t cell, const int* p) {
+  const int64_t eo = static_cast<int64_t>(e) * F.n;
+  const float* xe = xin + eo;
+  const float* ee = ec + static_cast<int64_t>(e) * C.n;
+  const float* dg = F.diag + eo;
+  auto xc = [&](int64_t k, int a, int s) {
+    if (!(dg[k] > 0.0f)) return 0.0f;
+    int q[3] = {p[0], p[1], p[2]};
+    q[a] += s;
+    return xe[k] + alpha * ee[(static_cast<int64_t>(q[2] >> 1) * C.Y + (q[1] >> 1)) * C.X + (q[0] >> 1)];
+  };
+  xout[eo + cell] = mg_jacobi<D>(F, eo, p, cell, r[eo + cell], xc(cell, 0, 0), xc);
+}
+
+// one sweep; returns r * x' of the cell
+template <int D>
+__device__ __forceinline__ float mg_sweep_at(const MgLevel& L, const float* r, const float* xin, float* xout, int e, int64_t cell, const int* p) {
+  const int64_t eo = static_cast<int64_t>(e) * L.n;
+  const float* xe = xin + eo;
+  auto xv = [&](int64_t k, int, int) { return xe[k]; };
+  const float rc = r[eo + cell];
+  const float z = mg_jacobi<D>(L, eo, p, cell, rc, xe[cell], xv);
+  xout[eo + cell] = z;
+  return rc * z;
+}
+
+template <int D>
+__global__ __launch_bounds__(kThreads) void mg_presmooth2_kernel(MgLevel L, const float* __restrict__ r, float* __restrict__ xout,
+                                                                 const CgState* __restrict__ st) {
+  const MgCell c = mdecode<D>(L);
+  if (mg_idle(st, c.e) || !c.in) return;
+  mg_presmooth2_at<D>(L, r, xout, c.e, c.cell, c.p);
+}
+
+// one thread = one coarse cell
+template <int D>
+__global__ __launch_bounds__(kThreads) void mg_restrict_kernel(MgLevel F, MgLevel C, const float* __restrict__ r, const float* __restrict__ x,
+                                                               const CgState* __restrict__ st) {
+  const MgCell c = mdecode<D>(C);
+  if (mg_idle(st, c.e) || !c.in) return;
+  mg_restrict_at<D>(F, C, r, x, c.e, c.cell, c.p);
+}
+
+template <int D>
+__global__ __launch_bounds__(kThreads) void mg_correct_sweep_kernel(MgLevel F, MgLevel C, const float* __restrict__ r,
+                                                                    const float* __restrict__ xin, const float* __restrict__ ec,
+                                                                    float* __restrict__ xout, float alpha, const CgState* __restrict__ st) {
+  const MgCell c = mdecode<D>(F);
+  if (mg_idle(st, c.e) || !c.in) return;
+  mg_correct_sweep_at<D>(F, C, r, xin, ec, xout, alpha, c.e, c.cell, c.p);
+}
+
+// FINAL (level 0): xout is z, and the workgroup's r.z partial goes to rr_part (if there is one)
+template <int D, bool FINAL>
+__global__ __launch_bounds__(kThreads) void mg_sweep_kernel(MgLevel L, const float* __restrict__ r, const float* __restrict__ xin,
+                                                            float* __restrict__ xout, float* __restrict__ rr_part,
+                                                            const CgState* __restrict__ st) {
+  __shared__ float lds[4];
+  const MgCell c = mdecode<D>(L);
+  if (mg_idle(st, c.e)) return;
+  float rz = 0.0f;
+  if (c.in) rz = mg_sweep_at<D>(L, r, xin, xout, c.e, c.cell, c.p);
+  if (FINAL) {
+    rz = block_reduce<false>(rz, lds);
+    if (rr_part && threadIdx.x == 0) rr_part[static_cast<int64_t>(c.e) * L.nblk + c.j] = rz;
+  }
+}
+
+// Every level of at most kSmallCells cells, down and up, in ONE launch: one workgroup per batch entry walks the levels, the threads stride
+// over a level's cells, and a barrier stands between two passes.  The same cell functions in the same order as the per-level kernels,
+// so the same bits.  The levels' arrays (a few KiB) stay in global memory: what one pass writes the next reads after __syncthreads(),
+// which orders the global accesses of a workgroup (all of its waves share one CU's L1).  The finest of these levels takes its
+// right-hand side from lev.r (the restriction above it wrote it) and leaves its result in lev.xa.
+#define MG_EACH(L, body)                                                             \
+  for (int64_t cell = threadIdx.x; cell < (L).n; cell += kThreads) {                 \
+    int p[3];                                                                        \
+    mcoords<D>((L), cell, p);                                                        \
+    body;                                                                            \
+  }                                                                                  \
+  __syncthreads();
+
+template <int D>
+__global__ __launch_bounds__(kThreads) void mg_small_kernel(MgSmall S, float alpha, const CgState* __restrict__ st) {
+  const int e = static_cast<int>(blockIdx.x);
+  if (mg_idle(st, e)) return;
+  const int last = S.count - 1;
+  for (int l = 0; l < last; ++l) {
+    const MgLevel& L = S.lev[l];
+    const MgLevel& C = S.lev[l + 1];
+    MG_EACH(L, mg_presmooth2_at<D>(L, L.r, L.xa, e, cell, p))
+    MG_EACH(C, mg_restrict_at<D>(L, C, L.r, L.xa, e, cell, p))
+  }
+  {
+    const MgLevel& L = S.lev[last];
+    MG_EACH(L, mg_presmooth2_at<D>(L, L.r, L.xa, e, cell, p))
+    float *from = L.xa, *to = L.xb;
+    for (int i = 2; i < kCoarsestSweeps; ++i) {         // an even number of them: the result is in xa again
+      MG_EACH(L, mg_sweep_at<D>(L, L.r, from, to, e, cell, p))
+      float* t = from; from = to; to = t;
+    }
+  }
+  for (int l = last - 1; l >= 0; --l) {
+    const MgLevel& L = S.lev[l];
+    const MgLevel& C = S.lev[l + 1];
+    MG_EACH(L, mg_correct_sweep_at<D>(L, C, L.r, L.xa, C.xa, L.xb, alpha, e, cell, p))
+    MG_EACH(L, mg_sweep_at<D>(L, L.r, L.xb, L.xa, e, cell, p))
+  }
+}
+#undef MG_EACH
+
+// ---- the preconditioned iteration ------------------------------------------------------------------------------------------------------------
+// cg_direction_kernel of smoke.hip with z in the place of r in the direction and r.z in the place of r.r (as cg_direction_gf): the same
+// matrix, read from the flags byte / the index tests
+template <int D, bool MASKED, bool OPEN>
+__global__ __launch_bounds__(kThreads) void cg_direction_mg(PWs w, const float* __restrict__ zz, const uint8_t* __restrict__ flags, PDims d,
+                                                            int par, int first, float accuracy, int max_iter, int os) {
+  __shared__ float lds[4];
+  const PCell c = pdecode<D, MASKED>(d, flags);
+  const bool writer = c.j == 0 && threadIdx.x == 0;
+  CgState s;
+  if (first) s = CgState{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1, 0, 0};
+  else s = w.state[par][c.e];
+  if (!s.active) {                                      // frozen: carry the record over, touch nothing else
+    if (writer) w.state[par ^ 1][c.e] = s;
+    return;
+  }
+  const int64_t po = static_cast<int64_t>(c.e) * d.nblk;
+  const float rz = entry_reduce<false>(w.rr_part + po, d.nblk, lds);
+  const float mx = entry_reduce<true>(w.mx_part + po, d.nblk, lds);
+  const bool act = mx > accuracy && rz > 0.0f && s.iters < max_iter;
+  const float beta = first ? 0.0f : rz / s.rr;          // s.rr > 0: the entry was active
+  if (writer) w.state[par ^ 1][c.e] = CgState{rz, mx, s.alpha, act ? beta : s.beta, s.pq, act ? 1 : 0, s.iters + (act ? 1 : 0), 0};
+  if (!act) return;
+  float pq = 0.0f;
+  if (c.interior) {
+    const int64_t eo = static_cast<int64_t>(c.e) * d.n;
+    const float* __restrict__ z = zz + eo;
+    const float* __restrict__ po_ = w.p[par] + eo;
+    const int64_t st[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
+    const int ext[3] = {d.X, d.Y, d.Z};
+    const float pc = z[c.cell] + beta * po_[c.cell];
+    float sum = 0.0f;
+    int cnt = 0;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+      const bool lo = MASKED ? (c.fl & lo_bit(a)) != 0u : c.p[a] > d.bnd;
+      const bool hi = MASKED ? (c.fl & hi_bit(a)) != 0u : c.p[a] + 1 < ext[a] - d.bnd;
+      if (lo) { const int64_t nb = c.cell - st[a]; sum += z[nb] + beta * po_[nb]; ++cnt; }
+      if (hi) { const int64_t nb = c.cell + st[a]; sum += z[nb] + beta * po_[nb]; ++cnt; }
+    }
+    if (OPEN) {
+#pragma unroll
+      for (int a = 0; a < D; ++a)
+        cnt += ((c.p[a] == d.bnd && ((os >> (2 * a)) & 1)) ? 1 : 0) + ((c.p[a] + 1 == ext[a] - d.bnd && ((os >> (2 * a + 1)) & 1)) ? 1 : 0);
+    }
+    const float qv = static_cast<float>(cnt) * pc - sum;
+    w.p[par ^ 1][eo + c.cell] = pc;
+    w.q[eo + c.cell] = qv;
+    pq = pc * qv;
+  }
+  pq = block_reduce<false>(pq, lds);
+  if (threadIdx.x == 0) w.pq_part[po + c.j] = pq;
+}
+
+// cg_update_kernel with alpha = r.z / p.q; it writes r and the max|r| partials, z and the r.z partials come from the cycle after it
+template <int D, bool MASKED>
+__global__ __launch_bounds__(kThreads) void cg_update_mg(float* __restrict__ x, PWs w, const uint8_t* __restrict__ flags, PDims d, int par) {
+  __shared__ float lds[4];
+  const PCell c = pdecode<D, MASKED>(d, flags);
+  CgState* s = w.state[par ^ 1] + c.e;                  // what direction(k) has just written
+  if (!s->active) return;
+  const float rz_old = s->rr;
+  const int64_t po = static_cast<int64_t>(c.e) * d.nblk;
+  const float pq = entry_reduce<false>(w.pq_part + po, d.nblk, lds);
+  const float alpha = pq > 0.0f ? rz_old / pq : 0.0f;
+  if (c.j == 0 && threadIdx.x == 0) { s->alpha = alpha; s->pq = pq; }   // words no workgroup of this launch reads
+  float mx = 0.0f;
+  if (c.interior) {
+    const int64_t g = static_cast<int64_t>(c.e) * d.n + c.cell;
+    x[g] = x[g] + alpha * w.p[par ^ 1][g];
+    const float rn = w.r[g] - alpha * w.q[g];
+    w.r[g] = rn;
+    mx = fabsf(rn);
+  }
+  mx = block_reduce<true>(mx, lds);
+  if (threadIdx.x == 0) w.mx_part[po + c.j] = mx;
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------------------
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+// the extents the solves accept (check_dims / pplan of smoke.hip), without a boundary width
+int mg_dims(const char* fn, int dim, int64_t B, int64_t Z, int64_t Y, int64_t X) {
+  DF_REQUIRE(dim == 2 || dim == 3, DF_EINVAL, "%s: dim must be 2 or 3 (got %d)", fn, dim);
+  DF_REQUIRE(B > 0 && Z > 0 && Y > 0 && X > 0, DF_EINVAL, "%s: non-positive extent", fn);
+  DF_REQUIRE(dim == 3 || Z == 1, DF_EINVAL, "%s: a 2-D grid has Z = 1", fn);
+  DF_REQUIRE(B < (1 << 24) && Z < (1 << 24) && Y < (1 << 24) && X < (1 << 24), DF_ESHAPE, "%s: extent too large", fn);
+  DF_REQUIRE(X >= 4 && Y >= 4 && (dim == 2 || Z >= 4), DF_ESHAPE, "%s: every extent must be >= 4", fn);
+  DF_REQUIRE(Z * Y * X < (1ll << 40) / B, DF_ESHAPE, "%s: extent too large", fn);
+  DF_REQUIRE(ceil_div(Z * Y * X, kThreads) * B < (1ll << 31), DF_ESHAPE, "%s: extent too large", fn);
+  return DF_OK;
+}
+
+// the levels and the layout of the block: level after level, per level D weights, dir, diag, r (level 0: z), xa, xb, each B * n floats
+int mg_plan(const char* fn, int dim, int64_t B, int64_t Z, int64_t Y, int64_t X, void* h, MgPlan* p) {
+  if (int e = mg_dims(fn, dim, B, Z, Y, X)) return e;
+  p->D = dim;
+  p->B = B;
+  float* f = static_cast<float*>(h);
+  int64_t off = 0;
+  int l = 0;
+  for (;; ++l) {
+    MgLevel& L = p->lev[l];
+    L.Z = (int)Z; L.Y = (int)Y; L.X = (int)X;
+    L.n = Z * Y * X;
+    L.nblk = (int)ceil_div(L.n, kThreads);
+    const int64_t N = B * L.n;
+    float** arr[8] = {&L.w[0], &L.w[1], &L.w[2], &L.dir, &L.diag, &L.r, &L.xa, &L.xb};
+    for (int i = 0; i < 8; ++i) {
+      const bool none = i == 2 && dim == 2;
+      p->off[l][i] = none ? -1 : off;
+      *arr[i] = (f && !none) ? f + off : nullptr;
+      if (!none) off += N;
+    }
+    if (X <= 2 && Y <= 2 && Z <= 2) break;
+    X = (X + 1) / 2; Y = (Y + 1) / 2; Z = (Z + 1) / 2;
+  }
+  p->levels = l + 1;
+  p->floats = off;
+  return DF_OK;
+}
+
+int mg_block(const char* fn, int dim, int64_t B, int64_t Z, int64_t Y, int64_t X, void* h, int64_t h_bytes, MgPlan* p) {
+  DF_REQUIRE(h, DF_EINVAL, "%s: null hierarchy", fn);
+  DF_REQUIRE(aligned4(h), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  if (int e = mg_plan(fn, dim, B, Z, Y, X, h, p)) return e;
+  DF_REQUIRE(h_bytes >= 4 * p->floats, DF_EWORKSPACE, "%s: hierarchy of %lld bytes, %lld needed", fn, (long long)h_bytes,
+             (long long)(4 * p->floats));
+  return DF_OK;
+}
+
+// the first level (above level 0) of at most kSmallCells cells; the coarsest has at most 8, and at most kSmallLevels follow the first
+int mg_first_small(const MgPlan& p) {
+  int l = 1;
+  while (p.lev[l].n > kSmallCells) ++l;
+  return l;
+}
+
+unsigned mg_grid(const MgPlan& p, int l) { return static_cast<unsigned>(p.B * p.lev[l].nblk); }
+
+template <int D>
+int mg_build(const char* fn, MgPlan& p, const uint8_t* flags, int bnd, int os, hipStream_t s) {
+  hipLaunchKernelGGL((mg_level0_kernel<D>), dim3(mg_grid(p, 0)), dim3(kThreads), 0, s, p.lev[0], flags, bnd, os);
+  for (int l = 1; l < p.levels; ++l)
+    hipLaunchKernelGGL((mg_coarsen_kernel<D>), dim3(mg_grid(p, l)), dim3(kThreads), 0, s, p.lev[l - 1], p.lev[l]);
+  return df::launched(fn);
+}
+
+// z = M r into lev[0].r; `st`: the state records of a solve (null: every entry runs), `rr_part`: where the r.z partials go (or null)
+template <int D>
+int mg_vcycle(const char* fn, MgPlan& p, const float* r0, float alpha, const CgState* st, float* rr_part, hipStream_t s) {
+  const int last = p.levels - 1;                        // >= 1: every extent of level 0 is >= 4
+  const int fs = mg_first_small(p);                     // levels fs..last run in mg_small_kernel; 1 <= fs <= last
+  const dim3 blk(kThreads);
+  for (int l = 0; l < fs; ++l) {
+    MgLevel& L = p.lev[l];
+    const float* r = l == 0 ? r0 : L.r;
+    hipLaunchKernelGGL((mg_presmooth2_kernel<D>), dim3(mg_grid(p, l)), blk, 0, s, L, r, L.xa, st);
+    hipLaunchKernelGGL((mg_restrict_kernel<D>), dim3(mg_grid(p, l + 1)), blk, 0, s, L, p.lev[l + 1], r, L.xa, st);
+  }
+  {
+    MgSmall S;
+    S.count = last - fs + 1;
+    for (int l = fs; l <= last; ++l) S.lev[l - fs] = p.lev[l];
+    hipLaunchKernelGGL((mg_small_kernel<D>), dim3(static_cast<unsigned>(p.B)), blk, 0, s, S, alpha, st);
+  }
+  for (int l = fs - 1; l >= 0; --l) {
+    MgLevel& L = p.lev[l];
+    const float* r = l == 0 ? r0 : L.r;
+    hipLaunchKernelGGL((mg_correct_sweep_kernel<D>), dim3(mg_grid(p, l)), blk, 0, s, L, p.lev[l + 1], r, L.xa, p.lev[l + 1].xa, L.xb, alpha, st);
+    if (l == 0) hipLaunchKernelGGL((mg_sweep_kernel<D, true>), dim3(mg_grid(p, 0)), blk, 0, s, L, r, L.xb, L.r, rr_part, st);
+    else hipLaunchKernelGGL((mg_sweep_kernel<D, false>), dim3(mg_grid(p, l)), blk, 0, s, L, r, L.xb, L.xa, nullptr, st);
+  }
+  return df::launched(fn);
+}
+
+int mg_alpha_ok(const char* fn, float alpha) {
+  DF_REQUIRE(alpha >= 1.0f && alpha < 2.0f, DF_EINVAL, "%s: alpha must lie in [1, 2) (got %g)", fn, (double)alpha);
+  return DF_OK;
+}
+
+// the workspace of the plain solve beside a hierarchy
+int mg_ws(const char* fn, void* ws, int64_t ws_bytes, const MgPlan& p, const void* h, PDims* d) {
+  const MgLevel& L = p.lev[0];
+  *d = PDims{L.n, L.nblk, (int)p.B, L.Z, L.Y, L.X, 0};
+  DF_REQUIRE(ws, DF_EINVAL, "%s: null workspace", fn);
+  DF_REQUIRE(aligned4(ws), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  const int64_t need = 4 * ws_floats(p.B, L.n, L.nblk);
+  DF_REQUIRE(ws_bytes >= need, DF_EWORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes, (long long)need);
+  DF_REQUIRE(!h || apart(ws, need, h, 4 * p.floats), DF_EINVAL, "%s: the workspace overlaps the hierarchy", fn);
+  return DF_OK;
+}
+
+int mg_open_ok(const char* fn, int dim, int open_sides) {
+  DF_REQUIRE(open_sides >= 0 && open_sides <= 63, DF_EINVAL, "%s: open_sides must be in 0..63 (got %d)", fn, open_sides);
+  DF_REQUIRE(dim == 3 || open_sides < 16, DF_EINVAL, "%s: open_sides %d opens a z side of a 2-D grid", fn, open_sides);
+  return DF_OK;
+}
+
+int mg_bnd_ok(const char* fn, int dim, int64_t Z, int64_t Y, int64_t X, int bnd) {
+  DF_REQUIRE(bnd >= 1, DF_EINVAL, "%s: boundary width must be >= 1 (got %d)", fn, bnd);
+  const int64_t need = 2 * static_cast<int64_t>(bnd) + 2;
+  DF_REQUIRE(X >= need && Y >= need && (dim == 2 || Z >= need), DF_ESHAPE, "%s: every extent must be >= 2*bnd + 2 = %lld", fn, (long long)need);
+  return DF_OK;
+}
+
+template <int D>
+int direction_mg(const char* fn, PWs w, const float* z, const uint8_t* flags, PDims d, int64_t k, float accuracy, int max_iter, int os,
+                 hipStream_t s) {
+  const dim3 grid(static_cast<unsigned>(static_cast<int64_t>(d.nblk) * d.B)), blk(kThreads);
+  const int par = (int)(k & 1), first = k == 0 ? 1 : 0;
+  if (flags && os) hipLaunchKernelGGL((cg_direction_mg<D, true, true>), grid, blk, 0, s, w, z, flags, d, par, first, accuracy, max_iter, os);
+  else if (flags) hipLaunchKernelGGL((cg_direction_mg<D, true, false>), grid, blk, 0, s, w, z, flags, d, par, first, accuracy, max_iter, os);
+  else if (os) hipLaunchKernelGGL((cg_direction_mg<D, false, true>), grid, blk, 0, s, w, z, flags, d, par, first, accuracy, max_iter, os);
+  else hipLaunchKernelGGL((cg_direction_mg<D, false, false>), grid, blk, 0, s, w, z, flags, d, par, first, accuracy, max_iter, os);
+  return df::launched(fn);
+}
+
+template <int D>
+int update_mg(const char* fn, float* pressure, PWs w, const uint8_t* flags, PDims d, int64_t k, hipStream_t s) {
+  const dim3 grid(static_cast<unsigned>(static_cast<int64_t>(d.nblk) * d.B)), blk(kThreads);
+  if (flags) hipLaunchKernelGGL((cg_update_mg<D, true>), grid, blk, 0, s, pressure, w, flags, d, (int)(k & 1));
+  else hipLaunchKernelGGL((cg_update_mg<D, false>), grid, blk, 0, s, pressure, w, flags, d, (int)(k & 1));
+  return df::launched(fn);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t df_mg_hierarchy_bytes(int dim, int64_t B, int64_t Z, int64_t Y, int64_t X) {
+  MgPlan p;
+  if (mg_plan("df_mg_hierarchy_bytes", dim, B, Z, Y, X, nullptr, &p)) return -1;
+  return 4 * p.floats;
+}
+
+int df_mg_sweeps(int coarsest) { return coarsest == 0 ? kNu : coarsest == 1 ? kCoarsestSweeps : -1; }
+
+float df_mg_omega(void) { return kOmega; }
+
+int df_mg_cycle_launches(int dim, int64_t Z, int64_t Y, int64_t X) {
+  MgPlan p;
+  if (mg_plan("df_mg_cycle_launches", dim, 1, Z, Y, X, nullptr, &p)) return -1;
+  return 4 * mg_first_small(p) + 1;
+}
+
+int df_mg_levels(int dim, int64_t Z, int64_t Y, int64_t X) {
+  MgPlan p;
+  if (mg_plan("df_mg_levels", dim, 1, Z, Y, X, nullptr, &p)) return -1;
+  return p.levels;
+}
+
+int64_t df_mg_level_offset(int dim, int64_t B, int64_t Z, int64_t Y, int64_t X, int level, int array) {
+  MgPlan p;
+  if (mg_plan("df_mg_level_offset", dim, B, Z, Y, X, nullptr, &p)) return -1;
+  if (level < 0 || level >= p.levels || array < 0 || array >= dim + 5) return -1;
+  return p.off[level][array < dim ? array : array + (3 - dim)];
+}
+
+int df_mg_build(void* hierarchy, int64_t hierarchy_bytes, const uint8_t* flags, int dim, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                int open_sides, df_stream_t stream) {
+  const char* fn = "df_mg_build";
+  MgPlan p;
+  if (int e = mg_block(fn, dim, B, Z, Y, X, hierarchy, hierarchy_bytes, &p)) return e;
+  if (int e = mg_bnd_ok(fn, dim, Z, Y, X, bnd)) return e;
+  if (int e = mg_open_ok(fn, dim, open_sides)) return e;
+  DF_REQUIRE(!flags || apart(flags, B * Z * Y * X, hierarchy, 4 * p.floats), DF_EINVAL, "%s: the flags overlap the hierarchy", fn);
+  return dim == 2 ? mg_build<2>(fn, p, flags, bnd, open_sides, df::as_stream(stream)) : mg_build<3>(fn, p, flags, bnd, open_sides, df::as_stream(stream));
+}
+
+int df_mg_apply(void* hierarchy, int64_t hierarchy_bytes, const float* r, int dim, int64_t B, int64_t Z, int64_t Y, int64_t X, float alpha,
+                df_stream_t stream) {
+  const char* fn = "df_mg_apply";
+  MgPlan p;
+  if (int e = mg_block(fn, dim, B, Z, Y, X, hierarchy, hierarchy_bytes, &p)) return e;
+  if (int e = mg_alpha_ok(fn, alpha)) return e;
+  DF_REQUIRE(r, DF_EINVAL, "%s: null r", fn);
+  DF_REQUIRE(aligned4(r), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  DF_REQUIRE(apart(r, 4 * B * Z * Y * X, hierarchy, 4 * p.floats), DF_EINVAL, "%s: r overlaps the hierarchy", fn);
+  return dim == 2 ? mg_vcycle<2>(fn, p, r, alpha, nullptr, nullptr, df::as_stream(stream))
+                  : mg_vcycle<3>(fn, p, r, alpha, nullptr, nullptr, df::as_stream(stream));
+}
+
+int df_pressure_mg_precondition(void* hierarchy, int64_t hierarchy_bytes, void* ws, int64_t ws_bytes, int dim, int64_t B, int64_t Z, int64_t Y,
+                                int64_t X, float alpha, int64_t k, df_stream_t stream) {
+  const char* fn = "df_pressure_mg_precondition";
+  MgPlan p;
+  PDims d;
+  if (int e = mg_block(fn, dim, B, Z, Y, X, hierarchy, hierarchy_bytes, &p)) return e;
+  if (int e = mg_alpha_ok(fn, alpha)) return e;
+  if (int e = mg_ws(fn, ws, ws_bytes, p, hierarchy, &d)) return e;
+  DF_REQUIRE(k >= -1, DF_EINVAL, "%s: iteration %lld", fn, (long long)k);
+  const PWs w = carve(ws, B, d.n, d.nblk);
+  const CgState* st = k < 0 ? nullptr : w.state[(k & 1) ^ 1];   // the record direction(k) wrote and update(k) read
+  return dim == 2 ? mg_vcycle<2>(fn, p, w.r, alpha, st, w.rr_part, df::as_stream(stream))
+                  : mg_vcycle<3>(fn, p, w.r, alpha, st, w.rr_part, df::as_stream(stream));
+}
+
+int df_pressure_cg_direction_mg(void* ws, int64_t ws_bytes, void* hierarchy, int64_t hierarchy_bytes, const uint8_t* flags, int dim, int64_t B,
+                                int64_t Z, int64_t Y, int64_t X, int bnd, int open_sides, int64_t k, float accuracy, int64_t max_iter,
+                                df_stream_t stream) {
+  const char* fn = "df_pressure_cg_direction_mg";
+  MgPlan p;
+  PDims d;
+  if (int e = mg_block(fn, dim, B, Z, Y, X, hierarchy, hierarchy_bytes, &p)) return e;
+  if (int e = mg_bnd_ok(fn, dim, Z, Y, X, bnd)) return e;
+  if (int e = mg_open_ok(fn, dim, open_sides)) return e;
+  if (int e = mg_ws(fn, ws, ws_bytes, p, hierarchy, &d)) return e;
+  d.bnd = bnd;
+  DF_REQUIRE(k >= 0 && max_iter >= 0 && max_iter < (1ll << 31), DF_EINVAL, "%s: iteration %lld of at most %lld", fn, (long long)k,
+             (long long)max_iter);
+  DF_REQUIRE(accuracy >= 0.0f, DF_EINVAL, "%s: accuracy must be >= 0", fn);
+  DF_REQUIRE(!flags || apart(flags, B * d.n, ws, 4 * ws_floats(B, d.n, d.nblk)), DF_EINVAL, "%s: the workspace overlaps the flags", fn);
+  const PWs w = carve(ws, B, d.n, d.nblk);
+  return dim == 2 ? direction_mg<2>(fn, w, p.lev[0].r, flags, d, k, accuracy, (int)max_iter, open_sides, df::as_stream(stream))
+                  : direction_mg<3>(fn, w, p.lev[0].r, flags, d, k, accuracy, (int)max_iter, open_sides, df::as_stream(stream));
+}
+
+int df_pressure_cg_update_mg(float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int dim, int64_t B, int64_t Z, int64_t Y,
+                             int64_t X, int bnd, int64_t k, df_stream_t stream) {
+  const char* fn = "df_pressure_cg_update_mg";
+  DF_REQUIRE(pressure, DF_EINVAL, "%s: null pressure", fn);
+  MgPlan p;
+  PDims d;
+  if (int e = mg_plan(fn, dim, B, Z, Y, X, nullptr, &p)) return e;
+  if (int e = mg_bnd_ok(fn, dim, Z, Y, X, bnd)) return e;
+  if (int e = mg_ws(fn, ws, ws_bytes, p, nullptr, &d)) return e;
+  d.bnd = bnd;
+  DF_REQUIRE(k >= 0, DF_EINVAL, "%s: iteration %lld", fn, (long long)k);
+  const int64_t need = 4 * ws_floats(B, d.n, d.nblk);
+  DF_REQUIRE(aligned4(pressure), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
+  DF_REQUIRE(apart(pressure, 4 * B * d.n, ws, need), DF_EINVAL, "%s: the workspace overlaps the pressure", fn);
+  DF_REQUIRE(!flags || (apart(flags, B * d.n, ws, need) && apart(flags, B * d.n, pressure, 4 * B * d.n)), DF_EINVAL,
+             "%s: the flags overlap the workspace or the pressure", fn);
+  const PWs w = carve(ws, B, d.n, d.nblk);
+  return dim == 2 ? update_mg<2>(fn, pressure, w, flags, d, k, df::as_stream(stream)) : update_mg<3>(fn, pressure, w, flags, d, k, df::as_stream(stream));
+}
+
+}  // extern "C"

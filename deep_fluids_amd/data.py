@@ -295,13 +295,14 @@ def generate_smoke_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="sr
                            min_src_x_pos=0.2, max_src_x_pos=0.8, src_y_pos=0.1, num_src_radius=5, min_src_radius=0.04, max_src_radius=0.12,
                            num_frames=200, min_frames=0, max_frames=None, num_simulations=None, resolution_x=96, resolution_y=128,
                            buoyancy=-4e-3, bWidth=1, open_bound=False, time_step=0.5, adv_order=2, clamp_mode=2, scenes_per_batch=None,
-                           accuracy=1e-4, device="cuda"):
+                           accuracy=1e-4, device="cuda", preconditioner=None):
     """Simulate the reference's default 2-D training set (scene/smoke_pos_size.py:111-254, ``smoke_pos21_size5_f200``) on the GPU and
     write it in the reference's on-disk format: ``args.txt`` with every argument of the scene script, ``v/%d_%d_%d.npz`` (x [Y,X,2]
     float32 velocity after frame t, y = [p0, p1, t]) and ``v_range.txt``.  The keyword arguments are the script's, with its defaults.
     Every scene is one batch entry of ``ops.simulate_smoke`` (``scenes_per_batch`` splits the set into chunks; an entry's result does
     not depend on the rest of its batch).  The step is this library's restatement (include/deepfluids_hip.h), not mantaflow's: plain CG
-    in place of MIC(0)-preconditioned CG.  ``open_bound``: a string of the open sides, ``'xXyY'`` being what the script's
+    in place of MIC(0)-preconditioned CG (``preconditioner="mg"``: multigrid-preconditioned, see ``ops.solve_pressure``; the files and
+    the ``args.txt`` keys are the same).  ``open_bound``: a string of the open sides, ``'xXyY'`` being what the script's
     ``--open_bound True`` opens, simulated with this library's open-side rules and zero-gradient fill (tests/smoke_open_ref.py), not
     mantaflow's outflow.  The bare ``True`` is still refused: it would promise the script's mantaflow outflow, which is not restated;
     name the sides.  Returns the number of files written."""
@@ -341,7 +342,7 @@ def generate_smoke_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="sr
         d0 = torch.zeros((len(part), Y, X), dtype=torch.float32, device=device)
         v0 = torch.zeros((len(part), Y, X, 2), dtype=torch.float32, device=device)
         frames = ops.simulate_smoke(d0, v0, num_frames, dt=time_step, source=mask, force=force, order=adv_order, clamp_mode=clamp_mode,
-                                    bnd=bWidth, accuracy=accuracy, stack=False, open_bound=sides)
+                                    bnd=bWidth, accuracy=accuracy, stack=False, open_bound=sides, preconditioner=preconditioner)
         for t, (_, v) in enumerate(frames):
             vh = v.cpu().numpy()
             v_range = [min(v_range[0], float(vh.min())), max(v_range[1], float(vh.max()))]
@@ -553,7 +554,7 @@ def generate_smoke3_obs_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p
                                 max_buoyancy=-16e-3, num_buoyancy=4, src_x_pos=0.5, src_y_pos=0.13, src_z_pos=0.5, src_radius=0.12,
                                 min_frames=0, max_frames=None, num_frames=150, num_simulations=None, resolution_x=64, resolution_y=96,
                                 resolution_z=64, bWidth=1, open_bound=False, time_step=0.5, adv_order=2, clamp_mode=2, scenes_per_batch=None,
-                                accuracy=1e-4, device="cuda"):
+                                accuracy=1e-4, device="cuda", preconditioner=None):
     """Simulate the reference's 3-D obstacle training set (scene/smoke3_obs_buo.py:126-294, ``smoke3_obs11_buo4_f150``) on the GPU and
     write it in the reference's on-disk format: ``args.txt`` with every argument of the scene script, ``v/%d_%d_%d.npz`` (x [Z,Y,X,3]
     float32 velocity after frame t, y = [p0, p1, t]) and ``v_range.txt``.  The keyword arguments are the script's, with its defaults
@@ -604,7 +605,7 @@ def generate_smoke3_obs_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p
             v0 = torch.zeros((len(part),) + shape + (3,), dtype=torch.float32, device=device)
             frames = ops.simulate_smoke(d0, v0, num_frames, dt=time_step, source=source, force=force, order=adv_order, clamp_mode=clamp_mode,
                                         bnd=bWidth, accuracy=accuracy, stack=False, obstacle=ops.obstacle_flags(obs, bWidth),
-                                        open_bound=sides)
+                                        open_bound=sides, preconditioner=preconditioner)
             for t, (_, v) in enumerate(frames):
                 vh = v.cpu().numpy()
                 v_range = [min(v_range[0], float(vh.min())), max(v_range[1], float(vh.max()))]
@@ -637,7 +638,7 @@ def smooth_source_paths(num_scenes, num_frames, lo, hi, seed=123, modes=3):
 
 
 def _simulate_moving_source(root, args, positions, name, src_y_pos, src_radius, num_frames, resolution, buoyancy, bWidth, open_bound,
-                            time_step, adv_order, clamp_mode, scenes_per_batch, accuracy, device):
+                            time_step, adv_order, clamp_mode, scenes_per_batch, accuracy, device, preconditioner=None):
     """what the two generators below share: args.txt, the frames of every scene (scenes are batch entries), v_range.txt, n.npz"""
     from . import ops
     os.makedirs(os.path.join(root, "v"), exist_ok=True)
@@ -660,7 +661,7 @@ def _simulate_moving_source(root, args, positions, name, src_y_pos, src_radius, 
         d0 = torch.zeros((len(part),) + shape, dtype=torch.float32, device=device)
         v0 = torch.zeros((len(part),) + shape + (3,), dtype=torch.float32, device=device)
         frames = ops.simulate_smoke(d0, v0, T, dt=time_step, source=src, force=force, order=adv_order, clamp_mode=clamp_mode, bnd=bWidth,
-                                    accuracy=accuracy, stack=False, open_bound=sides)
+                                    accuracy=accuracy, stack=False, open_bound=sides, preconditioner=preconditioner)
         for t, (_, v) in enumerate(frames):
             vh = v.cpu().numpy()
             v_range = [min(v_range[0], float(vh.min())), max(v_range[1], float(vh.max()))]
@@ -679,7 +680,8 @@ def _simulate_moving_source(root, args, positions, name, src_y_pos, src_radius, 
 def generate_smoke3_rot_dataset(root, num_param=1, path_format="%d.npz", p0="frames", min_src_pos=0.1, max_src_pos=0.9, src_y_pos=0.1,
                                 src_radius=0.08, circle_radius=0.25, circle_period=100, min_frames=0, max_frames=None, num_frames=500,
                                 num_simulations=None, num_dof=2, resolution_x=48, resolution_y=72, resolution_z=48, buoyancy=-4e-3, bWidth=1,
-                                open_bound="xXyYzZ", time_step=0.5, adv_order=2, clamp_mode=2, accuracy=1e-4, device="cuda"):
+                                open_bound="xXyYzZ", time_step=0.5, adv_order=2, clamp_mode=2, accuracy=1e-4, device="cuda",
+                                preconditioner=None):
     """Simulate the reference's rotating-source set (scene/smoke3_rot.py, ``smoke3_rot_f500``) on the GPU and write it as that script
     does: ``args.txt`` with every argument of the script, ``v/%d.npz`` (x [Z,Y,X,3] float32 velocity after frame t, y [2, num_frames] =
     the last ``num_frames`` source positions (px; pz) as fractions of the grid, oldest first, padded in front with -1), ``n.npz`` (nx,
@@ -703,14 +705,15 @@ def generate_smoke3_rot_dataset(root, num_param=1, path_format="%d.npz", p0="fra
                          axis=-1)[None]
     return _simulate_moving_source(root, args, positions, lambda i, t: path_format % t, src_y_pos, src_radius, num_frames,
                                    (resolution_x, resolution_y, resolution_z), buoyancy, bWidth, open_bound, time_step, adv_order, clamp_mode,
-                                   None, accuracy, device)
+                                   None, accuracy, device, preconditioner)
 
 
 def generate_smoke3_mov_dataset(root, num_param=2, path_format="%d_%d.npz", p0="scenes", p1="frames", min_src_pos=0.1, max_src_pos=0.9,
                                 src_y_pos=0.1, src_radius=0.08, min_scenes=0, max_scenes=None, num_scenes=200, min_frames=0, max_frames=None,
                                 num_frames=400, num_simulations=None, num_dof=2, resolution_x=48, resolution_y=72, resolution_z=48,
                                 buoyancy=-4e-3, bWidth=1, open_bound="xXyYzZ", time_step=0.5, adv_order=2, clamp_mode=2, nscale=0.01,
-                                nrepeat=1000, nseed=123, positions=None, scenes_per_batch=None, accuracy=1e-4, device="cuda"):
+                                nrepeat=1000, nseed=123, positions=None, scenes_per_batch=None, accuracy=1e-4, device="cuda",
+                                preconditioner=None):
     """Simulate the reference's moving-source set (scene/smoke3_mov.py, ``smoke3_mov200_f400``) on the GPU and write it as that script
     does: ``args.txt`` with every argument of the script, ``v/%d_%d.npz`` (scene, frame: x [Z,Y,X,3] float32 velocity after frame t, y
     [2, num_frames] = the last ``num_frames`` source positions (px; pz), oldest first, padded in front with -1), ``n.npz`` (nx, nz
@@ -740,7 +743,7 @@ def generate_smoke3_mov_dataset(root, num_param=2, path_format="%d_%d.npz", p0="
             ("nrepeat", nrepeat), ("nseed", nseed)]
     return _simulate_moving_source(root, args, positions, lambda i, t: path_format % (i, t), src_y_pos, src_radius, num_frames,
                                    (resolution_x, resolution_y, resolution_z), buoyancy, bWidth, open_bound, time_step, adv_order, clamp_mode,
-                                   scenes_per_batch, accuracy, device)
+                                   scenes_per_batch, accuracy, device, preconditioner)
 
 
 # ---- the noise-inflow scene (scene/smoke3_vel_buo.py): a cylinder source, a noise-modulated density inflow, an inflow velocity stamped
@@ -768,7 +771,7 @@ def generate_smoke3_vel_buo_dataset(root, num_param=3, path_format="%d_%d_%d.npz
                                     src_y_pos=0.25, src_z_pos=0.5, src_radius=0.14, src_height=0.04, min_frames=0, max_frames=None,
                                     num_frames=250, num_simulations=None, resolution_x=112, resolution_y=64, resolution_z=32, bWidth=1,
                                     open_bound="XyY", time_step=0.5, adv_order=2, clamp_mode=2, scenes_per_batch=None, accuracy=1e-4,
-                                    device="cuda", nseed=123):
+                                    device="cuda", nseed=123, preconditioner=None):
     """Simulate the reference's inflow / buoyancy set (scene/smoke3_vel_buo.py:127-308, ``smoke3_vel5_buo3_f250``) on the GPU and write it
     as that script does: ``args.txt`` with every argument of the script in its order, ``v/%d_%d_%d.npz`` (x [Z,Y,X,3] float32 velocity
     after frame t, y = [inflow, buoyancy, t]) and ``v_range.txt``.  The keyword arguments are the script's, with its defaults
@@ -808,7 +811,8 @@ def generate_smoke3_vel_buo_dataset(root, num_param=3, path_format="%d_%d_%d.npz
         d0 = torch.zeros((len(part),) + shape, dtype=torch.float32, device=device)
         v0 = torch.zeros((len(part),) + shape + (3,), dtype=torch.float32, device=device)
         frames = ops.simulate_smoke(d0, v0, num_frames, dt=time_step, source=inflow, force=force, order=adv_order, clamp_mode=clamp_mode,
-                                    bnd=bWidth, accuracy=accuracy, stack=False, open_bound=sides, inflow_velocity=(inflow.shape, values))
+                                    bnd=bWidth, accuracy=accuracy, stack=False, open_bound=sides, inflow_velocity=(inflow.shape, values),
+                                    preconditioner=preconditioner)
         for t, (_, v) in enumerate(frames):
             vh = v.cpu().numpy()
             v_range = [min(v_range[0], float(vh.min())), max(v_range[1], float(vh.max()))]

@@ -2262,7 +2262,131 @@ def default_max_iter(shape):
     return int(10 * max(shape)) * (1 if len(shape) == 3 else 4)
 
 
-def solve_pressure(vel, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, out=None, workspace=None, obstacle=None, open_bound=None):
+# ---- multigrid preconditioner of the smoke pressure solve: the V-cycle defined in include/deepfluids_hip.h ----
+DEFAULT_MG_ALPHA = 1.8        # the over-correction of the coarse-grid step; the table it was chosen from is in profiles/smoke_mg.md
+DEFAULT_MG_CHECK_EVERY = 4    # a preconditioned solve takes 6-12 iterations: a look every 16 would launch up to 10 idle cycles after the last
+
+
+class MultigridHierarchy(object):
+    """What ``multigrid_hierarchy`` returns: one float32 GPU block that holds, per batch entry and level, the face weights, ``dir``,
+    ``diag``, the level's right-hand side and x scratch, and ``z`` -- and the geometry it was built for (``shape`` [(Z,)Y,X], ``batch``,
+    ``bnd``, ``open_sides`` bits).  Reusable across solves of the same geometry; a solve writes its scratch, so one hierarchy serves one
+    stream at a time."""
+
+    def __init__(self, block, shape, batch, bnd, osd, alpha):
+        self.block, self.shape, self.batch, self.bnd, self.open_sides, self.alpha = block, tuple(shape), int(batch), int(bnd), int(osd), float(alpha)
+        self.dim = len(self.shape)
+        self.dims4 = [self.batch] + ([1] if self.dim == 2 else []) + list(self.shape)
+        self.nbytes = block.numel() * 4
+        self.levels = query("df_mg_levels", self.dim, *self.dims4[1:])
+
+    @property
+    def device(self):
+        return self.block.device
+
+    def level_shape(self, level):
+        s = self.shape
+        for _ in range(level):
+            s = tuple((n + 1) // 2 for n in s)
+        return s
+
+    def _array(self, level, array):
+        off = query("df_mg_level_offset", self.dim, *(self.dims4 + [int(level), int(array)]))
+        if off < 0:
+            raise ValueError("MultigridHierarchy: no array %d on level %d of %d" % (array, level, self.levels))
+        shape = (self.batch,) + self.level_shape(level)
+        return self.block[off:off + int(np.prod(shape))].view(shape)
+
+    def weights(self, level):
+        """``(w, dir, diag)`` of a level: ``w`` a tuple of D tensors [B,(Z,)Y,X of the level] (axis x, y[, z]); views of the block"""
+        return tuple(self._array(level, a) for a in range(self.dim)), self._array(level, self.dim), self._array(level, self.dim + 1)
+
+    @property
+    def z(self):
+        return self._array(0, self.dim + 2)
+
+
+def multigrid_hierarchy(vel_or_shape, bnd=1, obstacle=None, open_bound=None, batch=None, alpha=DEFAULT_MG_ALPHA, device=None):
+    """The multigrid hierarchy of the smoke pressure matrix (include/deepfluids_hip.h, "multigrid preconditioner") for a velocity
+    [B,(Z,)Y,X,D] or a grid shape [(Z,)Y,X] with ``batch`` entries (default: those of a per-entry ``obstacle``, else 1): level 0 is the matrix ``solve_pressure`` uses for ``bnd``,
+    ``obstacle`` (a mask or flags, per entry or shared) and ``open_bound``; the coarser levels are its Galerkin products over aggregates of
+    2^D cells.  Build it once per geometry and pass it as ``preconditioner=``; the solve it is passed to must use the same ``obstacle``,
+    which cannot be checked there.  ``alpha`` in [1, 2) scales the coarse-grid correction."""
+    with torch.no_grad():
+        if isinstance(vel_or_shape, torch.Tensor):
+            v, nd = _smoke_vel(vel_or_shape, "multigrid_hierarchy")
+            shape, B, device = tuple(v.shape[1:-1]), v.shape[0], v.device
+            if batch is not None and int(batch) != B:
+                raise ValueError("multigrid_hierarchy: batch=%r beside a velocity of %d entries" % (batch, B))
+        else:
+            shape = tuple(int(n) for n in vel_or_shape)
+            nd = len(shape)
+            if batch is None:                                  # a per-entry obstacle says how many entries there are
+                batch = obstacle.shape[0] if isinstance(obstacle, torch.Tensor) and obstacle.dim() == nd + 1 else 1
+            B = int(batch)
+            if nd not in (2, 3) or B < 1:
+                raise ValueError("multigrid_hierarchy expects a velocity or a grid shape [(Z,)Y,X] and batch >= 1, got %r, batch=%r" % (vel_or_shape, batch))
+            if device is None:
+                device = obstacle.device if isinstance(obstacle, torch.Tensor) and obstacle.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        if int(bnd) != bnd or bnd < 1:
+            raise ValueError("multigrid_hierarchy: bnd must be an integer >= 1, got %r" % (bnd,))
+        if not 1.0 <= alpha < 2.0:
+            raise ValueError("multigrid_hierarchy: alpha must lie in [1, 2), got %r" % (alpha,))
+        osd = open_sides(open_bound, nd)
+        dims = [B] + list(shape)
+        flags = None if obstacle is None else _obstacle_arg(obstacle, dims, int(bnd), "multigrid_hierarchy")
+        if flags is not None and flags.device != torch.device(device):
+            raise ValueError("multigrid_hierarchy: the obstacle is on %s, the hierarchy on %s" % (flags.device, device))
+        dims4 = [B] + ([1] if nd == 2 else []) + list(shape)
+        nbytes = query("df_mg_hierarchy_bytes", nd, *dims4)
+        if nbytes < 0:
+            raise ValueError("multigrid_hierarchy: unsupported extents %s" % (tuple(dims),))
+        h = MultigridHierarchy(torch.empty((nbytes // 4,), dtype=torch.float32, device=device), shape, B, bnd, osd, alpha)
+        call("df_mg_build", _ptr(h.block), h.nbytes, _ptr(flags), nd, *(dims4 + [int(bnd), osd, _stream()]))
+        return h
+
+
+def multigrid_apply(hierarchy, r):
+    """``z = M r``: one V-cycle of ``hierarchy`` on ``r`` [B,(Z,)Y,X] (float32, on the hierarchy's device).  Returns ``hierarchy.z``, a
+    view of the hierarchy's block that the next cycle overwrites.  The bare op; ``solve_pressure(preconditioner=...)`` is its user."""
+    with torch.no_grad():
+        if not isinstance(hierarchy, MultigridHierarchy):
+            raise ValueError("multigrid_apply expects the hierarchy of multigrid_hierarchy, got %r" % (type(hierarchy),))
+        want = (hierarchy.batch,) + hierarchy.shape
+        if (not isinstance(r, torch.Tensor) or r.dtype != torch.float32 or tuple(r.shape) != want or r.device != hierarchy.device
+                or not r.is_contiguous()):
+            raise ValueError("multigrid_apply: r must be a contiguous float32 tensor %s on %s" % (want, hierarchy.device))
+        call("df_mg_apply", _ptr(hierarchy.block), hierarchy.nbytes, _ptr(r.detach()), hierarchy.dim, *(hierarchy.dims4 + [hierarchy.alpha, _stream()]))
+        return hierarchy.z
+
+
+def _preconditioner_arg(preconditioner, who):
+    """``None``, ``"mg"`` or a ``MultigridHierarchy``; checked before anything touches a GPU"""
+    if preconditioner is None or isinstance(preconditioner, MultigridHierarchy) or (isinstance(preconditioner, str) and preconditioner == "mg"):
+        return preconditioner
+    raise ValueError("%s: preconditioner must be None, 'mg' or the hierarchy of multigrid_hierarchy, got %r" % (who, preconditioner))
+
+
+def _no_preconditioner(preconditioner, who):
+    if preconditioner is not None:
+        raise ValueError("%s: there is no preconditioner for this system (got preconditioner=%r); the multigrid preconditioner serves the "
+                         "smoke projections (solve_pressure, smoke_step, simulate_smoke) only" % (who, preconditioner))
+
+
+def _hierarchy_for(preconditioner, v, bnd, flags, osd, who):
+    """the hierarchy a solve on ``v`` uses: built here for ``"mg"``, or the caller's, which must fit the call"""
+    if not isinstance(preconditioner, MultigridHierarchy):
+        return multigrid_hierarchy(v, bnd, flags, osd)
+    h = preconditioner
+    if h.shape != tuple(v.shape[1:-1]) or h.batch != v.shape[0] or h.bnd != int(bnd) or h.device != v.device or h.open_sides != osd:
+        raise ValueError("%s: the hierarchy was built for shape %s, batch %d, bnd %d, open sides %d on %s; the call has shape %s, batch %d, "
+                         "bnd %d, open sides %d on %s" % (who, h.shape, h.batch, h.bnd, h.open_sides, h.device, tuple(v.shape[1:-1]),
+                                                          v.shape[0], int(bnd), osd, v.device))
+    return h
+
+
+def solve_pressure(vel, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, out=None, workspace=None, obstacle=None, open_bound=None,
+                   preconditioner=None):
     """Make ``vel`` [B,(Z,)Y,X,D] divergence free inside a closed box: plain conjugate gradients on the Neumann Laplacian of the interior
     cells from p = 0, every batch entry on its own until its ``max|r| <= accuracy`` or ``max_iter`` iterations (default
     ``int(10*max(extent))``, times 4 in 2-D), then ``vel -= grad p`` with the wall faces 0.  The wall faces of ``vel`` must be 0 already
@@ -2274,12 +2398,21 @@ def solve_pressure(vel, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, o
     its own singular system), the solid faces of ``vel`` must be 0 already and stay 0, and the pressure is 0 outside the fluid.
     ``open_bound``: the open sides (see ``open_sides``); p = 0 in open cells (Dirichlet), so a fluid region that touches one is a
     non-singular system, the faces between fluid and open cells are corrected too (every fluid cell ends divergence free -- mantaflow,
-    as far as can be recalled, leaves those faces alone), and the open cells are filled (zero gradient) before returning."""
+    as far as can be recalled, leaves those faces alone), and the open cells are filled (zero gradient) before returning.
+    ``preconditioner``: ``"mg"`` or the hierarchy of ``multigrid_hierarchy`` for this geometry makes it multigrid-preconditioned
+    conjugate gradients (one V-cycle per iteration, include/deepfluids_hip.h); it stops on the same unscaled ``max|r|``, so the fields
+    agree with the plain solve's to the accuracy and not beyond; ``check_every`` then defaults to 4.  A hierarchy passed in is checked
+    for shape, batch, ``bnd``, open sides and device; it must also have been built for the SAME ``obstacle``, which is NOT checked (a
+    hierarchy of another obstacle is still a symmetric preconditioner of the wrong matrix: the result stays within the accuracy, the
+    solve only takes more iterations).  With ``None`` nothing of it is allocated or launched."""
+    pre = _preconditioner_arg(preconditioner, "solve_pressure")
     with torch.no_grad():
         v, nd = _smoke_vel(vel, "solve_pressure")
         osd = open_sides(open_bound, nd)
         if int(bnd) != bnd or bnd < 1:
             raise ValueError("solve_pressure: bnd must be an integer >= 1, got %r" % (bnd,))
+        if pre is not None and check_every is None:
+            check_every = DEFAULT_MG_CHECK_EVERY
         s = _solve_begin("solve_pressure", v, nd, accuracy, max_iter, check_every, workspace if workspace is not None else pressure_workspace(v))
         out = _smoke_out(out, v, "solve_pressure")
         dims, ws, nbytes, bnd = list(v.shape[:-1]), s.ws, s.nbytes, int(bnd)
@@ -2291,13 +2424,28 @@ def solve_pressure(vel, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, o
         call("df_pressure_init" + sfx, _ptr(v), _ptr(pressure), _ptr(ws), nbytes, *(fl + dims + [bnd, _stream()]))
         # open sides: only the direction launch (n_c) and the correction differ; their `_open` twins take a nullable flags pointer
         fo = [_ptr(flags) if fl else None]
-        if osd:
+        if pre is not None:
+            # the preconditioned recurrence: z = M r after the init and after every update, r.z in the place of r.r
+            h = _hierarchy_for(pre, v, bnd, flags, osd, "solve_pressure")
+            mg, hb = [nd] + s.status4, [_ptr(h.block), h.nbytes]
+
+            def direction(k):
+                call("df_pressure_cg_direction_mg", _ptr(ws), nbytes, *(hb + fo + mg + [bnd, osd, k, s.acc, s.max_iter, _stream()]))
+
+            def update(k):
+                call("df_pressure_cg_update_mg", _ptr(pressure), _ptr(ws), nbytes, *(fo + mg + [bnd, k, _stream()]))
+                call("df_pressure_mg_precondition", *(hb + [_ptr(ws), nbytes] + mg + [h.alpha, k, _stream()]))
+            call("df_pressure_mg_precondition", *(hb + [_ptr(ws), nbytes] + mg + [h.alpha, -1, _stream()]))
+        elif osd:
             def direction(k):
                 call("df_pressure_cg_direction%dd_open" % nd, _ptr(ws), nbytes, *(fo + dims + [bnd, osd, k, s.acc, s.max_iter, _stream()]))
         else:
             def direction(k):
                 call("df_pressure_cg_direction" + sfx, _ptr(ws), nbytes, *(fl + dims + [bnd, k, s.acc, s.max_iter, _stream()]))
-        iters = _cg_loop(direction, lambda k: call("df_pressure_cg_update" + sfx, _ptr(pressure), _ptr(ws), nbytes, *(fl + dims + [bnd, k, _stream()])), s)
+        if pre is None:
+            def update(k):
+                call("df_pressure_cg_update" + sfx, _ptr(pressure), _ptr(ws), nbytes, *(fl + dims + [bnd, k, _stream()]))
+        iters = _cg_loop(direction, update, s)
         if osd:
             call("df_pressure_correct%dd_open" % nd, _ptr(v), _ptr(pressure), _ptr(out), *(fo + dims + [bnd, osd, _stream()]))
             _fill_open(out, nd, bnd, osd)
@@ -2327,7 +2475,8 @@ class _SmokeSettings(object):
     the shape, the obstacle packed into flags, the velocity stamp, and the scalars of the call."""
 
     def __init__(self, who, density, vel, steps, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, obstacle, open_bound,
-                 inflow_velocity):
+                 inflow_velocity, preconditioner=None):
+        pre = _preconditioner_arg(preconditioner, who)
         d, v, nd = _advect_dims(density, vel)
         self.d, self.v = d, v
         self.osd = open_sides(open_bound, nd)
@@ -2342,6 +2491,8 @@ class _SmokeSettings(object):
         self.vstamp = _inflow_velocity_arg(inflow_velocity, v, nd)
         self.dt, self.order, self.clamp_mode, self.bnd = dt, order, clamp_mode, bnd
         self.accuracy, self.max_iter, self.check_every = accuracy, max_iter, check_every
+        # the multigrid hierarchy, built once per sequence (None: nothing is allocated)
+        self.pre = None if pre is None else _hierarchy_for(pre, v, bnd, self.flags, self.osd, who)
 
 
 def _smoke_step(cfg, d, v, d_out, v_out, mask, time=0.0, v_stamped=None):
@@ -2361,12 +2512,12 @@ def _smoke_step(cfg, d, v, d_out, v_out, mask, time=0.0, v_stamped=None):
     advect_velocity(v, dt, out=v_out, workspace=cfg.fwd, open_bound=osd, **how)
     wall_buoyancy(v_out, d_out, cfg.force, bnd=bnd, out=v_out, obstacle=flags, open_bound=osd)
     _, _, iters = solve_pressure(v_out, bnd=bnd, accuracy=cfg.accuracy, max_iter=cfg.max_iter, check_every=cfg.check_every, out=v_out,
-                                 workspace=cfg.pws, obstacle=flags, open_bound=osd)
+                                 workspace=cfg.pws, obstacle=flags, open_bound=osd, preconditioner=cfg.pre)
     return iters
 
 
 def smoke_step(density, vel, dt, source=None, force=None, order=2, clamp_mode=2, bnd=1, accuracy=1e-4, max_iter=None, check_every=None,
-               obstacle=None, open_bound=None, time=0.0, inflow_velocity=None):
+               obstacle=None, open_bound=None, time=0.0, inflow_velocity=None, preconditioner=None):
     """One frame of the reference's smoke scene (scene/smoke_pos_size.py:187-195) on ``density`` [B,(Z,)Y,X] and the MAC velocity ``vel``
     [B,(Z,)Y,X,D] of a closed box: stamp ``source`` (a mask) with 1, advect the density and the velocity through the OLD velocity, zero
     the wall faces, add buoyancy (``force``; default ``default_buoyancy_force``), project.  Returns new ``(density, vel)``.
@@ -2376,10 +2527,11 @@ def smoke_step(density, vel, dt, source=None, force=None, order=2, clamp_mode=2,
     steps treat those sides as open; the density needs nothing, its band is 0 after every advection (``resetOutflow``).
     With a ``NoiseInflow`` source (evaluated at solver time ``time``), ``inflow_velocity=(shape, values)`` (a ``CylinderShape`` and the
     [B,D] or [D] values ``stamp_velocity`` writes) and ``force`` a tensor [B,D] it is the loop of scene/smoke3_vel_buo.py:222-232: density
-    inflow, velocity stamp, both advections through the STAMPED velocity, walls, buoyancy, projection.  ``vel`` itself is never written."""
+    inflow, velocity stamp, both advections through the STAMPED velocity, walls, buoyancy, projection.  ``vel`` itself is never written.
+    ``preconditioner``: as for ``solve_pressure``."""
     with torch.no_grad():
         cfg = _SmokeSettings("smoke_step", density, vel, None, dt, source, force, order, clamp_mode, bnd, accuracy, max_iter, check_every, obstacle,
-                             open_bound, inflow_velocity)
+                             open_bound, inflow_velocity, preconditioner)
         d_out, v_out = torch.empty_like(cfg.d), torch.empty_like(cfg.v)
         _smoke_step(cfg, cfg.d, cfg.v, d_out, v_out, cfg.mask, time)
         return d_out, v_out
@@ -2412,17 +2564,20 @@ def _smoke_frames(steps, stats, settings):
 
 
 def simulate_smoke(density0, vel0, steps, dt=0.5, source=None, force=None, order=2, clamp_mode=2, bnd=1, accuracy=1e-4, max_iter=None,
-                   check_every=None, stack=True, stats=None, obstacle=None, open_bound=None, inflow_velocity=None):
+                   check_every=None, stack=True, stats=None, obstacle=None, open_bound=None, inflow_velocity=None, preconditioner=None):
     """``steps`` chained ``smoke_step`` frames from ``(density0, vel0)`` (left untouched); every buffer is allocated once.  With
     ``stack`` returns ``(density, vels)``, ``vels`` [steps,B,(Z,)Y,X,D] the velocity after each step; without it returns a generator of
     ``(density, vel)`` per step -- views of buffers the next step overwrites, so copy what is to be kept.  ``stats``: a list that
     receives the iteration counts [B] of every step's solve.  ``obstacle``: as for ``smoke_step``, packed into flags once.  ``source``
     may be a ``SphereSource`` [B,D] or [T,B,D] (step t stamps ``centers[t]``); ``open_bound``: as for ``smoke_step``.  A ``NoiseInflow``
     source is evaluated at ``t * dt`` in step t; ``inflow_velocity`` and a ``force`` tensor [B,D]: as for ``smoke_step`` (the stamp goes
-    into the sequence's own working buffer)."""
+    into the sequence's own working buffer).  ``preconditioner``: as for ``solve_pressure``; ``"mg"`` builds the hierarchy once for the
+    sequence."""
+    _preconditioner_arg(preconditioner, "simulate_smoke")
     with torch.no_grad():
         gen = _smoke_frames(steps, stats, lambda: _SmokeSettings("simulate_smoke", density0, vel0, steps, dt, source, force, order, clamp_mode, bnd,
-                                                                 accuracy, max_iter, check_every, obstacle, open_bound, inflow_velocity))
+                                                                 accuracy, max_iter, check_every, obstacle, open_bound, inflow_velocity,
+                                                                 preconditioner))
         if not stack:
             return _no_grad_iter(gen)
         vels = torch.empty((int(steps),) + tuple(vel0.shape), dtype=torch.float32, device=vel0.device)
@@ -2929,7 +3084,7 @@ def _gf_clamp_arg(gf_clamp, who):
 
 
 def solve_pressure_liquid(vel, flags, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, out=None, workspace=None, phi=None,
-                          gf_clamp=1e-4):
+                          gf_clamp=1e-4, preconditioner=None):
     """The free-surface projection: ``solve_pressure`` with rows for the liquid cells of ``flags`` (``liquid_flags``) only and p = 0 in
     the air cells -- n_c counts every neighbour that is interior by its index, the neighbour sums run over the liquid ones.  Faces
     between two interior cells of which at least one is liquid are corrected with p as the array holds it (0 in air), other interior
@@ -2943,7 +3098,9 @@ def solve_pressure_liquid(vel, flags, bnd=1, accuracy=1e-4, max_iter=None, check
     > -1e-4, else clamped to [``gf_clamp``, 1]): the row of i gets p_i / theta for that neighbour, and the face is corrected with
     p_i / theta.  The solve is then Jacobi-preconditioned CG (the clamp puts diagonals up to 1 / gf_clamp beside diagonals of 4-6),
     stopping on the UNscaled residual as before, and needs ``pressure_workspace(vel, ghost_fluid=True)``.  With ``phi=None`` nothing of
-    this is launched."""
+    this is launched.  The multigrid preconditioner of ``solve_pressure`` is deliberately out of scope for the free-surface and
+    ghost-fluid systems: any ``preconditioner`` but ``None`` is refused."""
+    _no_preconditioner(preconditioner, "solve_pressure_liquid")
     with torch.no_grad():
         gf = phi is not None
         if gf:
@@ -3006,14 +3163,16 @@ def _diffusion_alpha_arg(alpha, B, who):
     return a32
 
 
-def diffuse_velocity(vel, alpha, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, out=None, workspace=None):
+def diffuse_velocity(vel, alpha, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, out=None, workspace=None, preconditioner=None):
     """mantaflow's ``cgSolveDiffusion(flags, vel, alpha)`` as include/deepfluids_hip.h restates it: every component of ``vel``
     [B,(Z,)Y,X,D] is diffused implicitly, ``(I - alpha * Laplacian) x = u`` on the cells interior by index with the ``bnd`` band as
     Dirichlet data (copied through bit for bit), by plain conjugate gradients from ``x = u``.  ``alpha``: a number or B numbers on the
     host (``diffusion_alpha``), finite and >= 0.  Every (entry, component) pair is its own system and stops on its own at
     ``max|r| <= accuracy`` or after ``max_iter`` iterations (default ``default_diffusion_max_iter``); the host reads one word every
     ``check_every`` iterations, as in ``solve_pressure``.  ``alpha = 0`` returns the input's bits.  No preconditioner, no obstacles.
-    Returns ``(vel_out, iterations)``, ``iterations`` int32 [B, D].  ``out`` may be ``vel``."""
+    Returns ``(vel_out, iterations)``, ``iterations`` int32 [B, D].  ``out`` may be ``vel``.  The multigrid preconditioner of
+    ``solve_pressure`` is deliberately out of scope for the diffusion system: any ``preconditioner`` but ``None`` is refused."""
+    _no_preconditioner(preconditioner, "diffuse_velocity")
     with torch.no_grad():
         if not isinstance(vel, torch.Tensor) or vel.dtype != torch.float32 or not vel.is_cuda or not vel.is_contiguous():
             raise ValueError("diffuse_velocity: vel must be a contiguous float32 GPU tensor [B,(Z,)Y,X,D]")
@@ -3351,7 +3510,8 @@ def _liquid_step(p, u, v, es, cfg):
 
 
 def liquid_step(pos, pvel, vel, dt, force=None, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, flip_ratio=DEFAULT_FLIP_RATIO,
-                open_bound=False, viscosity_alpha=None, ghost_fluid=False, radius_factor=1.0, gf_clamp=1e-4, resample=None, entry_start=None):
+                open_bound=False, viscosity_alpha=None, ghost_fluid=False, radius_factor=1.0, gf_clamp=1e-4, resample=None, entry_start=None,
+                preconditioner=None):
     """One frame of the reference's liquid scenes (scene/liquid_pos_size.py:254-295) on particles ``pos``, ``pvel`` [B,N,D] and the MAC
     velocity ``vel`` [B,(Z,)Y,X,D], in the script's order: trace the particles through ``vel`` (RK4), sort them by cell, map their
     velocities to the grid, extrapolate 2 layers from the faces that received weight, mark the liquid cells, add gravity (``force``,
@@ -3375,7 +3535,9 @@ def liquid_step(pos, pvel, vel, dt, force=None, bnd=1, accuracy=1e-4, max_iter=N
     forces and the solve; ``resample_particles`` against the projected velocity (``resample.step`` feeds the hash and advances);
     the 4-layer extrapolation; the FLIP update on old and new particles alike.  The result is ``(pos [P,D], pvel [P,D], vel,
     iterations[, diffusion_iterations], entry_start)``; a state that does not fit the capacity raises before the step returns.  With
-    ``None`` nothing of this is launched and every result keeps its bits."""
+    ``None`` nothing of this is launched and every result keeps its bits.  The liquid systems are out of the multigrid preconditioner's
+    scope: any ``preconditioner`` but ``None`` is refused."""
+    _no_preconditioner(preconditioner, "liquid_step")
     cfg = _LiquidSettings("liquid_step", dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, open_bound, viscosity_alpha, ghost_fluid,
                           radius_factor, gf_clamp, resample, entry_start)
     with torch.no_grad():
@@ -3406,7 +3568,7 @@ def _liquid_frames(pos0, pvel0, vel0, entry_start, steps, keep_every, stats, cfg
 
 def simulate_liquid(pos0, pvel0, vel0, steps, dt=0.5, force=None, bnd=1, accuracy=1e-4, max_iter=None, check_every=None,
                     flip_ratio=DEFAULT_FLIP_RATIO, stack=True, stats=None, open_bound=False, viscosity_alpha=None, keep_every=1,
-                    ghost_fluid=False, radius_factor=1.0, gf_clamp=1e-4, resample=None, entry_start=None):
+                    ghost_fluid=False, radius_factor=1.0, gf_clamp=1e-4, resample=None, entry_start=None, preconditioner=None):
     """``steps`` chained ``liquid_step`` frames from ``(pos0, pvel0, vel0)`` (left untouched).  With ``stack`` returns
     ``(pos, pvel, vels)``, ``vels`` [steps,B,(Z,)Y,X,D] the velocity after each step; without it a generator of ``(pos, pvel, vel)`` per
     step.  ``stats``: a list that receives the iteration counts [B] of every step's solve.  ``viscosity_alpha``: as in ``liquid_step``.
@@ -3414,7 +3576,9 @@ def simulate_liquid(pos0, pvel0, vel0, steps, dt=0.5, force=None, bnd=1, accurac
     is ``k`` solver steps) -- every step still runs and reports to ``stats``, and with ``stack`` the returned particles are those after
     the LAST step.  ``ghost_fluid``, ``radius_factor``, ``gf_clamp``: as in ``liquid_step``.  ``resample`` (and ``entry_start`` for a
     ragged start): as in ``liquid_step``; the state is ragged, the result is ``(pos [P,D], pvel [P,D], vels, entry_start)`` or a generator
-    of ``(pos, pvel, vel, entry_start)``, and a state that does not fit the capacity raises at the next kept frame at the latest."""
+    of ``(pos, pvel, vel, entry_start)``, and a state that does not fit the capacity raises at the next kept frame at the latest.  Any
+    ``preconditioner`` but ``None`` is refused (out of the multigrid preconditioner's scope)."""
+    _no_preconditioner(preconditioner, "simulate_liquid")
     keep_every = int(keep_every)
     if keep_every < 1:
         raise ValueError("simulate_liquid: keep_every must be >= 1, got %r" % (keep_every,))

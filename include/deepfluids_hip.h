@@ -1122,6 +1122,72 @@ int df_resample_scatter3d(const float* pos_sorted, const float* pvel_sorted, con
                           const int32_t* new_start, const float* vel, float* pos_out, float* pvel_out, int64_t B, int64_t N, int64_t Z,
                           int64_t Y, int64_t X, int min_particles, uint32_t seed, uint32_t step, df_stream_t stream);
 
+/* ---- multigrid preconditioner of the smoke pressure solve (opt-in; the plain solve above is untouched) -------------------------------
+ * A V-cycle z = M r for the matrices of the plain, `_flags` and `_open` smoke solves, and the two kernels of the preconditioned
+ * recurrence.  The definition below is this library's own (as the projection's is) and it is the one that is tested:
+ * tests/smoke_mg_ref.py restates it in fp64 and as an op-for-op fp32 twin whose bits the kernels give.  The free-surface, ghost-fluid
+ * and diffusion systems are out of scope.  DF_VERSION is NOT raised by this block either (tests pin 207): look the symbols up.
+ *
+ * Level 0 is the solve's own grid, band included, and the solve's own matrix, stored as face weights: w_a[c] for the face between c and
+ *   c - e_a, 1 if both cells are fluid, else 0 (a neighbour outside the grid has no face); dir[c] = the number of open neighbours of a
+ *   fluid cell (what open sides add to n_c), 0 elsewhere; diag[c] = the sum of the 2D incident w, plus dir[c].
+ * Coarser levels: extents ceil(extent / 2) per axis, until every extent is <= 2.  Aggregate I holds the children 2I and 2I + 1 along each
+ *   axis, where they exist.  The weights are the Galerkin product with piecewise-constant interpolation: w_a^c[I] = the sum of w_a[i]
+ *   over the fine faces with i_a = 2 I_a and the other coordinates inside the aggregate (faces inside an aggregate vanish), dir^c[I] = the
+ *   sum of dir over the children, diag^c = the sum of the incident w^c plus dir^c.  The children are summed in ascending x, then y, then
+ *   z.  All of it is float32 and exact (small integers).  A cell with diag = 0 is inactive on its level: its value is 0 and its residual
+ *   is 0.  There are no cell types above level 0: obstacles, walls, open sides, odd extents, split regions and enclosed cells are all
+ *   carried by the weights.
+ * (A x)[c] = diag[c] * x[c] - sum, the sum taken from 0 in the order x-, x+, y-, y+[, z-, z+] over the neighbours inside the grid, each
+ *   term w * x[neighbour] with the weight of the face between them.
+ * One damped-Jacobi sweep: x'[c] = x[c] + (omega * (r[c] - (A x)[c])) / diag[c] on active cells, omega = float(2) / float(3).
+ * V-cycle on level l, from x = 0:  two sweeps, the first of them as x[c] = (omega * r[c]) / diag[c];  the residual r - A x;
+ *   r^c[I] = the sum of the children's residuals from 0 in the order above;  e = the V-cycle of level l + 1 on r^c;
+ *   x[c] += alpha * e[parent(c)] on active cells;  two sweeps.  The coarsest level runs eight sweeps, the first as above.  z is x of level
+ *   0.  alpha in [1, 2) over-corrects for the piecewise-constant interpolation.  All arithmetic fp32, no fused multiply-add, in the order
+ *   written; no reductions across cells, no atomics; an entry's result does not depend on the rest of the batch.
+ * Because the coarse operators are Galerkin and the smoother is symmetric, M is symmetric positive semidefinite for every geometry.
+ * The iteration is the preconditioned one in the form of the `_gf` entry points: CgState::rr and the `rr` partials hold r.z,
+ *   p = z + beta * p; it stops on the UNscaled max|r| exactly as the plain solve does (accuracy, max_iter, the iteration counts and the
+ *   frozen-entry rule are unchanged).  Every V-cycle kernel returns at once for an entry that is no longer active.
+ *
+ *   df_mg_hierarchy_bytes(dim, B, Z, Y, X)   the bytes of a hierarchy block (weights, per-level scratch and z); -1 for bad extents.
+ *                                            dim = 2 takes Z = 1.  Extents as the solves accept them (every extent >= 4).
+ *   df_mg_levels(dim, Z, Y, X)               the number of levels; -1 for bad extents
+ *   df_mg_sweeps(coarsest)                   the scheme's sweep counts: 0 -> the pre- / post-sweeps (2), 1 -> the coarsest level's (8); else -1
+ *   df_mg_omega()                            the damping as the kernels hold it, float(2) / float(3)
+ *   df_mg_cycle_launches(dim, Z, Y, X)       kernel launches of one V-cycle: four per level of more than 1024 cells (and level 0), one for
+ *                                            all smaller levels together (one workgroup per entry walks them, same arithmetic); -1 for
+ *                                            bad extents
+ *   df_mg_level_offset(.., level, array)     the float offset inside the block of an array [B, cells of the level]: array 0..dim-1 = w_a,
+ *                                            dim = dir, dim + 1 = diag, dim + 2 = the level's right-hand side (level 0: z), dim + 3 and
+ *                                            dim + 4 = the two x buffers; -1 if there is none
+ *   df_mg_build          writes every level's weights from flags (nullable: no obstacles; df_obstacle_flags*), bnd and open_sides
+ *   df_mg_apply          z = M r for r [B,(Z,)Y,X]; z is array dim + 2 of level 0.  Nothing of the block is read before it is written.
+ *   df_pressure_mg_precondition   the same on the r of a solve's workspace (df_pressure_workspace_bytes), and the r.z partials.  k = -1:
+ *                        after df_pressure_init*, before direction 0; k >= 0: after update k, skipping the entries update k skipped
+ *   df_pressure_cg_direction_mg / df_pressure_cg_update_mg   df_pressure_cg_direction* / _update* for the preconditioned recurrence
+ *                        (flags nullable, open_sides may be 0); update writes r and the max|r| partials, z comes from the cycle after it
+ * Errors, on the host and before any launch: DF_EINVAL (null pointer, dim, alpha outside [1, 2), open_sides, overlapping arrays, k),
+ * DF_ESHAPE (extents), DF_EALIGN, DF_EWORKSPACE (a hierarchy or a workspace too small). */
+int64_t df_mg_hierarchy_bytes(int dim, int64_t B, int64_t Z, int64_t Y, int64_t X);
+int df_mg_levels(int dim, int64_t Z, int64_t Y, int64_t X);
+int df_mg_sweeps(int coarsest);
+float df_mg_omega(void);
+int df_mg_cycle_launches(int dim, int64_t Z, int64_t Y, int64_t X);
+int64_t df_mg_level_offset(int dim, int64_t B, int64_t Z, int64_t Y, int64_t X, int level, int array);
+int df_mg_build(void* hierarchy, int64_t hierarchy_bytes, const uint8_t* flags, int dim, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                int open_sides, df_stream_t stream);
+int df_mg_apply(void* hierarchy, int64_t hierarchy_bytes, const float* r, int dim, int64_t B, int64_t Z, int64_t Y, int64_t X, float alpha,
+                df_stream_t stream);
+int df_pressure_mg_precondition(void* hierarchy, int64_t hierarchy_bytes, void* ws, int64_t ws_bytes, int dim, int64_t B, int64_t Z, int64_t Y,
+                                int64_t X, float alpha, int64_t k, df_stream_t stream);
+int df_pressure_cg_direction_mg(void* ws, int64_t ws_bytes, void* hierarchy, int64_t hierarchy_bytes, const uint8_t* flags, int dim, int64_t B,
+                                int64_t Z, int64_t Y, int64_t X, int bnd, int open_sides, int64_t k, float accuracy, int64_t max_iter,
+                                df_stream_t stream);
+int df_pressure_cg_update_mg(float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int dim, int64_t B, int64_t Z, int64_t Y,
+                             int64_t X, int bnd, int64_t k, df_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
