@@ -63,6 +63,16 @@ inline int64_t wino_grid(Args& a, int64_t ntb) {
   return grid;
 }
 
+// The generic mapping above (and its twins wino2d_grid of conv_wino2d.hip and w2_grid of conv_wino2d43.hip) gives every cout slice the same
+// number of workers out of the one-workgroup-per-CU grid: (kCUs / ncs) * ncs workgroups, which is an EMPTY grid from kCUs + 1 slices on.  Every
+// Winograd conv entry point of the four files refuses such a call here (ncs = the kernel's cout slices of 32 channels), before it computes a grid.
+constexpr int kWinoMaxSlices = df::kCUs;
+inline int wino_slices_check(const char* name, int64_t ncs) {
+  DF_REQUIRE(ncs <= kWinoMaxSlices, DF_ESHAPE, "%s: %lld cout slices of 32 channels, the persistent grid serves at most %d (%d output channels)", name,
+             static_cast<long long>(ncs), kWinoMaxSlices, 32 * kWinoMaxSlices);
+  return DF_OK;
+}
+
 // VALU kernels for the generator's last layer (conv_small.hip); return DF_OK or an error
 int launch_small_n(const ConvArgs& a, int kz, hipStream_t s);   // Cout <= 4  (128 -> 3 | 1)
 int launch_small_k(const ConvArgs& a, int kz, hipStream_t s);   // Cin  <= 4  (dgrad of the last layer; 3 -> F)

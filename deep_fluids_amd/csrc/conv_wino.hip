@@ -834,6 +834,7 @@ int wino_launch(const char* name, int fl, int mode, const WinoOps& o, int64_t B,
   a.nbz = (int)ceil_div(D, 4); a.nby = (int)ceil_div(H, 8); a.nbx = (int)ceil_div(W, 8);
   const int64_t ntb = B * a.nbz * a.nby * a.nbx;
   a.ncs = (int)(Cout / 32);
+  if (const int rc = dfconv::wino_slices_check(name, Cout / 32)) return rc;
   DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "%s: too many workgroups", name);
   a.ntb = (int)ntb;
   a.flags = flags; a.leak = leak;

@@ -452,6 +452,7 @@ int df_wino2d_conv_fwd(const float* x, const float* wp, const float* bias, const
   a.nby = (int)ceil_div(H, 16); a.nbx = (int)ceil_div(W, 32);
   const int64_t ntb = B * a.nby * a.nbx;
   a.ncs = (int)(Cout / 32);
+  if (const int rc = dfconv::wino_slices_check("df_wino2d_conv_fwd", Cout / 32)) return rc;
   DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "df_wino2d_conv_fwd: too many workgroups");
   a.ntb = (int)ntb;
   a.flags = flags; a.leak = leak;
@@ -475,6 +476,7 @@ static int wino2d_up_common(const char* fn, Wino2dArgs& a, const float* wp, int6
   a.nby = (int)ceil_div(a.H, 16); a.nbx = (int)ceil_div(a.W, 32);
   const int64_t ntb = B * a.nby * a.nbx;
   a.ncs = (int)(N / 32);
+  if (const int rc = dfconv::wino_slices_check(fn, N / 32)) return rc;
   DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "%s: too many workgroups", fn);
   a.ntb = (int)ntb;
   return DF_OK;

@@ -556,6 +556,7 @@ static int w2_conv(const char* fn, const float* x, const float* wp, const float*
   a.nby = (int)ceil_div(H, 16); a.nbx = (int)ceil_div(W, 32);
   const int64_t ntb = B * a.nby * a.nbx;
   a.ncs = (int)(Cout / 32);
+  if (const int rc = dfconv::wino_slices_check(fn, Cout / 32)) return rc;
   DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "%s: too many workgroups", fn);
   a.ntb = (int)ntb;
   a.flags = flags; a.leak = leak;
@@ -606,6 +607,7 @@ int df_wino2d43_conv_addup_bits(const float* x, const float* wp, const float* bi
   a.nby = (int)ceil_div(H, 16); a.nbx = (int)ceil_div(W, 32);
   const int64_t ntb = B * a.nby * a.nbx;
   a.ncs = (int)(Cout / 32);
+  if (const int rc = dfconv::wino_slices_check(fn, Cout / 32)) return rc;
   DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "%s: too many workgroups", fn);
   a.ntb = (int)ntb;
   a.flags = DF_CONV_BIAS | DF_CONV_LRELU | DF_CONV_ADDUP; a.leak = leak;

@@ -543,6 +543,7 @@ int df_wino43_conv(const float* x, const float* wp, const float* bias, const flo
   a.nbz = (int)ceil_div(D, 4); a.nby = (int)ceil_div(H, 8); a.nbx = (int)ceil_div(W, 8);
   const int64_t ntb = B * a.nbz * a.nby * a.nbx;
   a.ncs = (int)(Cout / 32);
+  if (const int rc = dfconv::wino_slices_check("df_wino43_conv", Cout / 32)) return rc;
   DF_REQUIRE(ntb * a.ncs < (1LL << 31), DF_ESHAPE, "df_wino43_conv: too many workgroups");
   a.ntb = (int)ntb;
   a.flags = flags; a.leak = leak;

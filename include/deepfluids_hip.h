@@ -316,7 +316,8 @@ int df_add_up2x(const float* a, const float* bc, float* y, int64_t B, int64_t D,
 
 /* ---- Winograd F(2x2x2, 3x3x3) form of the 3-D stride-1 convolution (conv_wino.hip) ------------------------------------
  * Same result as df_conv_fwd with kz = 3 up to fp32 rounding order (all arithmetic fp32, 3.4x fewer matrix-core FLOPs);
- * same epilogue flags.  Needs Cin % 32 == 0, Cout % 32 == 0 and D*H*W*max(Cin,Cout) <= 2^29 (one batch volume below 2 GiB).  Weights: TF layout [3,3,3,Cin,Cout], transformed and
+ * same epilogue flags.  Needs Cin % 32 == 0, Cout % 32 == 0, D*H*W*max(Cin,Cout) <= 2^29 (one batch volume below 2 GiB), Cin*Cout <= 2^24 and at
+ * most 256 cout slices of 32 channels (Cout <= 8192; df_wino_upconv_dgrad: Cin <= 8192, its kernel's output channels), else DF_ESHAPE.  Weights: TF layout [3,3,3,Cin,Cout], transformed and
  * packed once per update by df_wino_pack_weights (mode 0: forward operand, mode 1: dgrad operand). */
 int64_t df_wino_packed_elems(int64_t cin, int64_t cout, int mode);
 int df_wino_pack_weights(const float* w, float* wp, int64_t cin, int64_t cout, int mode, df_stream_t stream);
@@ -345,6 +346,7 @@ int df_wino_conv_fwd_addup(const float* x, const float* wp, const float* bias, c
 /* ---- round 6: F(2,3) x F(2,3) x F(4,3) Winograd family (conv_wino43.hip) -------------------------------------------------------------
  * The same convolution as df_wino_conv_fwd* (slim.conv3d k=3 s=1 SAME, model.py:66-70; dgrad = mode-1 operand) with a 2 x 2 x 4 output
  * tile: 6 matrix multiply-adds per output voxel and (cin, cout) pair instead of 8, about one bit of fp32 accuracy less.
+ * Shape limits as df_wino_conv_fwd, with Cin*Cout <= 2^22; Cout <= 8192 (256 cout slices) as there.
  * ONE entry point covers every fused epilogue of the F(2,3)^3 family; the sign words it writes / reads have the SAME layout
  * (df_wino_signbits_bytes, df_lrelu_bits_bwd_pool2x), so the two families can be mixed layer by layer:
  *   flags        DF_CONV_BIAS | LRELU | RESIDUAL (fine tensor `residual`) | MASK | ADDUP (`residual` = the COARSE tensor, y2 = y + up2x)
@@ -359,7 +361,7 @@ int df_wino43_conv(const float* x, const float* wp, const float* bias, const flo
 
 /* The 2-D twin (conv_wino2d43.hip): slim.conv2d k=3 s=1 SAME (ops.py:12-13; model.py:24-28) as Winograd F(2,3) x F(4,3) -- 3 matrix multiply-adds
  * per output pixel and (cin, cout) pair instead of the 4 of df_wino2d_conv_fwd; same arguments, flags (BIAS | LRELU | RESIDUAL | MASK with an
- * fp32 mask_src) and error convention as df_wino2d_conv_fwd; mode 1 of the pack = the dgrad operand. */
+ * fp32 mask_src), shape limits (Cout <= 8192 among them) and error convention as df_wino2d_conv_fwd; mode 1 of the pack = the dgrad operand. */
 int64_t df_wino2d43_packed_elems(int64_t cin, int64_t cout, int mode);
 int df_wino2d43_pack_weights(const float* w, float* wp, int64_t cin, int64_t cout, int mode, df_stream_t stream);
 int df_wino2d43_conv(const float* x, const float* wp, const float* bias, const float* residual, const float* mask_src, float* y, int64_t B,
@@ -406,7 +408,8 @@ int df_lrelu_bits_bwd_pool2x(const float* gy, const void* mask_bits, float* gx, 
                              int64_t Wc, int64_t C, df_stream_t stream);
 
 /* 2-D twin: Winograd F(2x2, 3x3) form of the stride-1 3x3 convolution (conv_wino2d.hip): 2.25x fewer matrix-core FLOPs than df_conv_fwd
- * with kz = 1, fp32 throughout, same epilogue flags.  Needs Cin % 32 == 0, Cout % 32 == 0, H*W*max(Cin,Cout) <= 2^29. */
+ * with kz = 1, fp32 throughout, same epilogue flags.  Needs Cin % 32 == 0, Cout % 32 == 0, H*W*max(Cin,Cout) <= 2^29, Cin*Cout <= 2^24 and at most
+ * 256 cout slices of 32 channels (Cout <= 8192; df_wino2d_upconv_dgrad: Cin <= 8192, its kernel's output channels), else DF_ESHAPE. */
 
 int64_t df_wino2d_packed_elems(int64_t cin, int64_t cout, int mode);
 int df_wino2d_pack_weights(const float* w, float* wp, int64_t cin, int64_t cout, int mode, df_stream_t stream);

@@ -1,7 +1,8 @@
 """No GPU: what the seven df_wino_* entry points and df_wino43_conv accept, reject and launch.  tests/wgrad_launch_recorder.cpp links the
 release library, defines the HIP runtime calls itself and prints every launch; the expected values -- return code, instantiation, grid,
 block, LDS bytes, argument bytes -- are tests/golden/wino_launches.json, recorded with this recorder from the last commit whose
-conv_wino.hip still held one argument fill per entry point (2f63d5b).  `python tests/test_wino_launches_host.py <library> <json>`
+conv_wino.hip still held one argument fill per entry point (2f63d5b); the cout-slices rows, which the parent of their commit answered with
+an empty grid, from the commit that added the limit.  `python tests/test_wino_launches_host.py <library> <json>`
 records such a file from any build of the library."""
 import json
 import os
@@ -133,6 +134,10 @@ def _rows():
         cc = 2048 if entry == "wino43" else 4096      # Cin Cout <= 2^22 | 2^24
         add("cincout-at", entry, small, cc, cc)
         add("cincout-over", entry, small, cc, cc + 32)
+        # ---- at most 256 cout slices: beyond them the persistent grid would be empty (the dgrad's slices are the entry point's Cin) ----
+        dg = entry == "wino_upconv_dgrad"
+        add("cout-slices-at", entry, small, 8192 if dg else 32, 32 if dg else 8192)
+        add("cout-slices-over", entry, small, 8224 if dg else 32, 32 if dg else 8224)
         # ---- tile blocks x cout slices < 2^31 ----
         add("workgroups-at", entry, ((1 << 31) - 1, 2 if up else 4, 4, 4), 32, 32)      # one tile block per batch entry, one slice
         add("workgroups-over", entry, (1 << 31, 2 if up else 4, 4, 4), 32, 32)

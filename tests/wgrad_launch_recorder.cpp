@@ -1,5 +1,5 @@
-// Launch recorder of tests/test_wgrad_launches_host.py, tests/test_wino_launches_host.py and tests/test_conv_cases_host.py: calls the
-// weight-gradient, the 3-D Winograd and the direct conv (forward / input-gradient)
+// Launch recorder of tests/test_wgrad_launches_host.py, tests/test_wino_launches_host.py, tests/test_conv_cases_host.py and
+// tests/test_wino_cases_host.py: calls the weight-gradient, the 3-D and 2-D Winograd and the direct conv (forward / input-gradient)
 // entry points of libdeepfluids_hip.so WITHOUT a GPU and prints what they would have launched.  No HIP header, no device: this executable itself defines every HIP runtime call the host path of
 // csrc/conv_wgrad.hip makes (df_common.hpp, core.hip), and a symbol defined in the executable wins over the shared runtime's when the
 // library's calls are bound.  A launch arrives as hipLaunchKernel(kernel handle, grid, block, argument pointers, LDS bytes, stream);
@@ -10,9 +10,14 @@
 //     rows     lines "id entry B D H W Cin Cout kz algo bias xoff goff"; entry as in tests/wgrad_cases.py, algo -1 = the entry point
 //              without an algo argument
 //              | "id entry B D H W Cin Cout flags present misaligned" with entry = wino_fwd | wino_fwd_bits | wino_fwd_addup | wino_fwd_addup_bits |
-//              wino_upconv_fwd | wino_upconv_fwd_bits | wino_upconv_dgrad | wino43; present / misaligned = bit masks over the operand slots
-//              x 1, wp 2, bias 4, residual (xc of the add-up forms) 8, mask_src 16, mask_bits 32, y (acc) 64, y2 128, sign_bits 256: a slot
-//              not present is passed as NULL, a misaligned one 4 bytes behind its address; leak = 0.2
+//              wino_upconv_fwd | wino_upconv_fwd_bits | wino_upconv_dgrad | wino43 | wino_bits_bwd (df_lrelu_bits_bwd_pool2x: C = Cin); present /
+//              misaligned = bit masks over the operand slots x (gy) 1, wp 2, bias 4, residual (xc of the add-up forms) 8, mask_src 16,
+//              mask_bits 32, y (acc, gx) 64, y2 (gpool) 128, sign_bits 256: a slot not present is passed as NULL, a misaligned one 4 bytes behind
+//              its address; leak = 0.2
+//              | "id entry B H W Cin Cout flags present misaligned" (tests/wino_cases.py, tests/test_wino_cases_host.py), the same slots, with entry =
+//              w2_fwd df_wino2d_conv_fwd | w2_up_fwd | w2_up_dgrad | w2_43 df_wino2d43_conv | w2_43_bits | w2_43_addup_bits | w2_words_bwd
+//              df_lrelu_words2d_bwd_pool2x (C = Cin) | w2_pack df_wino2d_pack_weights | w2_43_pack (w = slot x, mode = flags) | the queries
+//              w2_packed_elems | w2_43_packed_elems (mode = flags) | w2_43_signbits_bytes (C = Cin), whose value is printed as ws
 //              | "id entry B D H W Cin Cout kz flags present ox owp obias ores omask oy" with entry = dc_fwd | dc_fwd_bf16x3 | dc_s2_fwd |
 //              dc_s2_dgrad | dc_up_fwd | dc_up_fwd_bf16x3 | dc_up_dgrad | dc_up_dgrad_bf16x3 (tests/conv_cases.py): present = bit mask over
 //              the slots x (gy / g of the dgrads) 1, wp 2, bias 4, residual 8, mask_src 16, y (gx / acc) 32; o* = the slot's payload offset
@@ -51,7 +56,7 @@ std::string kernel_name(const void* f) {
 // Argument bytes of each kernel the weight-gradient host code launches: the sizes of its parameters in order.  The kernels that take one
 // argument struct list its size WITHOUT tail padding (WxyzArgs: 140 of 144, SmallWgradArgs: 84 of 88), which is not initialised.
 // hole_at / hole_len: padding bytes inside the one argument struct (never initialised by the host code), printed as 00.
-struct Layout { const char* prefix; int n; int size[12]; int hole_at, hole_len; };
+struct Layout { const char* prefix; int n; int size[14]; int hole_at, hole_len; };
 const Layout kLayouts[] = {
     {"(anonymous namespace)::wgrad_kernel<", 1, {128}},
     {"(anonymous namespace)::wgrad_s2_kernel<", 1, {128}},
@@ -77,6 +82,13 @@ const Layout kLayouts[] = {
     // WinoArgs up to and including spx (the experiment field that once followed it was never set by these entry points); W43Args whole
     {"(anonymous namespace)::wino3d_kernel<", 1, {136}},
     {"(anonymous namespace)::wino43_kernel<", 1, {128}},
+    // the 2-D Winograd families: Wino2dArgs and W2Args whole
+    {"(anonymous namespace)::wino2d_kernel<", 1, {96}},
+    {"(anonymous namespace)::wino2d43_kernel<", 1, {120}},
+    {"(anonymous namespace)::wino2d_pack_kernel(", 6, {8, 8, 4, 4, 4, 8}},
+    {"(anonymous namespace)::wino2d43_pack_kernel(", 5, {8, 8, 4, 4, 4}},
+    {"(anonymous namespace)::lrelu_words2d_bwd_pool_kernel(", 11, {8, 8, 8, 8, 4, 4, 4, 4, 4, 4, 4}},
+    {"(anonymous namespace)::lrelu_bits_bwd_pool_kernel(", 14, {8, 8, 8, 8, 4, 8, 4, 4, 4, 4, 4, 4, 4, 4}},
     // the direct convs: ConvArgs whole (200 bytes, 4 of padding in front of wclass); ThinKArgs without its tail padding (84 of 88); ThinNArgs
     {"(anonymous namespace)::conv_mfma_kernel<", 1, {200}, 156, 4},
     {"(anonymous namespace)::conv_tiny2d_kernel(", 1, {200}, 156, 4},
@@ -157,6 +169,31 @@ static int wino_row(const std::string& e, long long B, long long D, long long H,
   if (e == "wino_upconv_fwd_bits") return df_wino_upconv_fwd_bits(f(0), f(1), f(2), f(6), slot(8), B, D, H, W, Cin, Cout, leak, nullptr);
   if (e == "wino_upconv_dgrad") return df_wino_upconv_dgrad(f(0), f(1), f(6), B, D, H, W, Cin, Cout, nullptr);
   if (e == "wino43") return df_wino43_conv(f(0), f(1), f(2), f(3), f(4), slot(5), f(6), f(7), slot(8), B, D, H, W, Cin, Cout, flags, leak, nullptr);
+  if (e == "wino_bits_bwd") return df_lrelu_bits_bwd_pool2x(f(0), slot(5), f(6), f(7), leak, B, D, H, W, Cin, nullptr);
+  return -1000;
+}
+
+// one row of the 2-D entry points (tests/wino_cases.py, tests/test_wino_cases_host.py): the slots and addresses of wino_row; *value = a query's answer
+static int wino2d_row(const std::string& e, long long B, long long H, long long W, long long Cin, long long Cout, int flags, int present, int mis,
+                      long long* value) {
+  auto slot = [&](int i) -> char* {
+    if (!((present >> i) & 1)) return nullptr;
+    return reinterpret_cast<char*>((static_cast<uintptr_t>(i + 1) << 44) + (((mis >> i) & 1) ? 4 : 0));
+  };
+  auto f = [&](int i) { return reinterpret_cast<float*>(slot(i)); };
+  const float leak = 0.2f;
+  if (e == "w2_fwd") return df_wino2d_conv_fwd(f(0), f(1), f(2), f(3), f(4), f(6), B, H, W, Cin, Cout, flags, leak, nullptr);
+  if (e == "w2_up_fwd") return df_wino2d_upconv_fwd(f(0), f(1), f(2), f(6), B, H, W, Cin, Cout, flags, leak, nullptr);
+  if (e == "w2_up_dgrad") return df_wino2d_upconv_dgrad(f(0), f(1), f(6), B, H, W, Cin, Cout, nullptr);
+  if (e == "w2_43") return df_wino2d43_conv(f(0), f(1), f(2), f(3), f(4), f(6), B, H, W, Cin, Cout, flags, leak, nullptr);
+  if (e == "w2_43_bits") return df_wino2d43_conv_bits(f(0), f(1), f(2), slot(5), f(6), slot(8), B, H, W, Cin, Cout, flags, leak, nullptr);
+  if (e == "w2_43_addup_bits") return df_wino2d43_conv_addup_bits(f(0), f(1), f(2), f(3), f(7), slot(8), B, H, W, Cin, Cout, leak, nullptr);
+  if (e == "w2_words_bwd") return df_lrelu_words2d_bwd_pool2x(f(0), slot(5), f(6), f(7), leak, B, H, W, Cin, nullptr);
+  if (e == "w2_pack") return df_wino2d_pack_weights(f(0), f(1), Cin, Cout, flags, nullptr);
+  if (e == "w2_43_pack") return df_wino2d43_pack_weights(f(0), f(1), Cin, Cout, flags, nullptr);
+  if (e == "w2_packed_elems") { *value = df_wino2d_packed_elems(Cin, Cout, flags); return 0; }
+  if (e == "w2_43_packed_elems") { *value = df_wino2d43_packed_elems(Cin, Cout, flags); return 0; }
+  if (e == "w2_43_signbits_bytes") { *value = df_wino2d43_signbits_bytes(B, H, W, Cin); return 0; }
   return -1000;
 }
 
@@ -216,6 +253,14 @@ int main(int argc, char** argv) {
         strncmp(entry, "wino", 4) == 0) {
       printf("row %s\n", id);
       printf("end %s rc %d ws 0\n", id, wino_row(entry, B, D, H, W, Cin, Cout, flags, present, mis));
+      continue;
+    }
+    if (sscanf(line, "%127s %31s %lld %lld %lld %lld %lld %d %d %d", id, entry, &B, &H, &W, &Cin, &Cout, &flags, &present, &mis) == 10 &&
+        strncmp(entry, "w2_", 3) == 0) {
+      long long value = 0;
+      printf("row %s\n", id);
+      const int rc2 = wino2d_row(entry, B, H, W, Cin, Cout, flags, present, mis, &value);
+      printf("end %s rc %d ws %lld\n", id, rc2, value);
       continue;
     }
     if (sscanf(line, "%127s %31s %lld %lld %lld %lld %lld %lld %d %d %d %d %d", id, entry, &B, &D, &H, &W, &Cin, &Cout, &kz, &algo, &bias,
