@@ -253,6 +253,9 @@ SIGNATURES = {
     "df_pressure_mg_precondition": (I32, [P, I64, P, I64, I32, I64, I64, I64, I64, F32, I64, P]),
     "df_pressure_cg_direction_mg": (I32, [P, I64, P, I64, P, I32, I64, I64, I64, I64, I32, I32, I64, F32, I64, P]),
     "df_pressure_cg_update_mg": (I32, [P, P, I64, P, I32, I64, I64, I64, I64, I32, I64, P]),
+    "df_mesh_capacity_bound": (I64, [I64, I64, I64, I64, I32, I32, I32]),
+    "df_mesh_count": (I32, [P, P, P, P, I64, I64, I64, I64, I32, I32, F32, P]),
+    "df_mesh_emit": (I32, [P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I32, I32, F32, P]),
 }
 
 DF_CONV_LRELU, DF_CONV_RESIDUAL, DF_CONV_MASK, DF_CONV_BIAS, DF_CONV_ADDUP, DF_CONV_VALU_ONLY = 1, 2, 4, 8, 16, 32

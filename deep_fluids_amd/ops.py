@@ -2600,8 +2600,8 @@ def _no_grad_iter(gen):
 # ---- a liquid carried through a velocity field (the advect() mode of the reference's liquid scene scripts, scene/liquid3_vis.py:47-148,
 #      scene/liquid_pos_size.py:47-132): marker particles traced with RK4, a union level set rebuilt from them.  Inference only, no
 #      autograd.  The step is defined in include/deepfluids_hip.h; mantaflow, which the reference calls for it, cannot be run here, so
-#      bit parity with it is not claimed.  Left out: extrapolateMACSimple, markFluidCells, resetOutflow, adjustNumber resampling,
-#      meshing; the frame loop uses the union form (the one the 2-D script carries commented out), the averaged form with phi.setBound
+#      bit parity with it is not claimed.  Left out: extrapolateMACSimple, markFluidCells, resetOutflow, adjustNumber resampling;
+#      meshing is ``extract_surface`` below (this project's own marching tetrahedra); the frame loop uses the union form (the one the 2-D script carries commented out), the averaged form with phi.setBound
 #      is ``particle_levelset_averaged`` ----
 def _particle_pos(pos, who):
     p = _prep(pos.detach(), "pos")
@@ -2817,12 +2817,14 @@ def particle_levelset_averaged(pos, shape, radius_factor=1.0, smooth=1, smooth_n
         return _levelset_averaged(spos, cell_start, out, tmp, radius_factor, smooth, smooth_neg, bound_value, int(bnd))
 
 
-def liquid_sequence(pos0, vels, dt, bnd=1, vel_scale=1.0, radius_factor=1.0, images=False):
+def liquid_sequence(pos0, vels, dt, bnd=1, vel_scale=1.0, radius_factor=1.0, images=False, on_frame=None):
     """The frame loop of the liquid scenes' ``advect()`` (scene/liquid3_vis.py:100-148) over ``vels`` [T,B,(Z,)Y,X,D] (a tensor or a
     sequence of T tensors): per frame build the level set of the current particles, optionally render it with ``density_image`` (the
     ``l_adv`` frame: clipped where the reference's cast wraps), then trace the particles through the frame's velocity.  ``pos0`` is left
     untouched.  Returns ``(final positions [B,N,D], last phi [B,(Z,)Y,X])`` -- the last phi is the level set of the positions BEFORE the
-    last trace, as in the reference's loop -- and with ``images`` also the uint8 frames [T,B,Y,X], copied to the host once."""
+    last trace, as in the reference's loop -- and with ``images`` also the uint8 frames [T,B,Y,X], copied to the host once.
+    ``on_frame(t, phi)``: called for every frame with the level set just built, before the trace; phi is the loop's one buffer, to be
+    read (``extract_surface``) and not kept or written.  Without it the loop allocates and launches what it always did."""
     with torch.no_grad():
         T = len(vels)
         if T < 1:
@@ -2835,6 +2837,8 @@ def liquid_sequence(pos0, vels, dt, bnd=1, vel_scale=1.0, radius_factor=1.0, ima
             particle_levelset(cur, shape, radius_factor, out=phi)
             if images:
                 density_image(phi, out=imgs[t])
+            if on_frame is not None:
+                on_frame(t, phi)
             advect_particles(cur, vels[t], dt, bnd=bnd, vel_scale=vel_scale, out=cur)
         if images:
             return cur, phi, imgs.cpu().numpy()
@@ -3617,6 +3621,118 @@ def liquid_initial_state(shape, phi0, vel_spheres=(), discretization=2, randomne
     p = torch.from_numpy(pos[None]).to(device)
     v = torch.from_numpy(vel[None]).to(device)
     return p, sample_velocity(v, p), v
+
+
+# ---- the surface of a 3-D level set as a triangle mesh (what the reference's 3-D liquid scripts get from phi.createMesh + mesh.save,
+#      scene/liquid3_vis.py:136-143).  Marching tetrahedra on the Kuhn split of the cubes between cell centres: the definition is this
+#      project's own (include/deepfluids_hip.h, "liquid surface meshes"), tested against tests/liquid_mesh_ref.py; no parity with
+#      mantaflow's marching-cubes mesh is claimed.  Left out: 2-D contours, smoothMesh / subdivideMesh (smooth phi with
+#      ``particle_levelset_averaged`` instead), .bobj.gz, rendering ----
+class SurfaceMesh(object):
+    """The result of ``extract_surface``: ``vertices`` [V,3] float32 (xyz, grid units, a cell centre at +0.5), ``faces`` [T,3] int32 holding
+    vertex rows LOCAL to their batch entry, ``normals`` [V,3] or None, and ``vertex_start``, ``face_start`` [B+1] int32: entry b owns the
+    vertex rows ``vertex_start[b] .. vertex_start[b+1] - 1`` and the face rows ``face_start[b] .. face_start[b+1] - 1`` (a ragged batch in
+    the ``entry_start`` style).  All on the device of phi."""
+
+    def __init__(self, vertices, faces, normals, vertex_start, face_start):
+        self.vertices, self.faces, self.normals = vertices, faces, normals
+        self.vertex_start, self.face_start = vertex_start, face_start
+        self._starts = None
+
+    @property
+    def batch(self):
+        return self.vertex_start.numel() - 1
+
+    def entry(self, i):
+        """``(vertices [V_i,3], faces [T_i,3], normals [V_i,3] | None)`` of batch entry ``i``, views of the batch's arrays; the first
+        call copies the 2 (B + 1) starts to the host."""
+        if self._starts is None:
+            self._starts = (self.vertex_start.cpu().numpy().astype(np.int64), self.face_start.cpu().numpy().astype(np.int64))
+        vs, fs = self._starts
+        if not 0 <= int(i) < len(vs) - 1:
+            raise IndexError("SurfaceMesh.entry: %r is not one of the %d batch entries" % (i, len(vs) - 1))
+        i = int(i)
+        v = slice(int(vs[i]), int(vs[i + 1]))
+        return self.vertices[v], self.faces[int(fs[i]):int(fs[i + 1])], None if self.normals is None else self.normals[v]
+
+
+def _mesh_args(phi, bnd, closed, closed_value, capacity):
+    """the checks of ``extract_surface`` that need no device: ``(bnd, closed, closed_value, (vertex rows, face rows) | None)``"""
+    who = "extract_surface"
+    if not isinstance(phi, torch.Tensor):
+        raise TypeError("%s: phi must be a torch.Tensor on the MI355X (got %r)" % (who, type(phi)))
+    if phi.dim() != 4:
+        raise ValueError("%s expects a 3-D level set phi [B,Z,Y,X], got %s (2-D contours are not built)" % (who, tuple(phi.shape)))
+    if phi.dtype != torch.float32:
+        raise TypeError("%s: phi must be float32, got %s" % (who, phi.dtype))
+    if not phi.is_contiguous():
+        raise ValueError("%s: phi must be contiguous (strides %s for shape %s)" % (who, tuple(phi.stride()), tuple(phi.shape)))
+    B, Z, Y, X = (int(n) for n in phi.shape)
+    if B < 1 or min(Z, Y, X) < 2:
+        raise ValueError("%s: every extent of phi [B,Z,Y,X] must be >= 2 (and B >= 1), got %s" % (who, tuple(phi.shape)))
+    if isinstance(bnd, bool) or int(bnd) != bnd or bnd < 0:
+        raise ValueError("%s: bnd must be an integer >= 0, got %r" % (who, bnd))
+    bnd, closed = int(bnd), bool(closed)
+    if closed and bnd < 1:
+        raise ValueError("%s: closed=True needs bnd >= 1 (the capped layer is the outer layer of the box one wider than bnd)" % who)
+    if min(Z, Y, X) - 1 - 2 * (bnd - 1 if closed else bnd) < 1:
+        raise ValueError("%s: bnd = %d is too wide for a grid %s: the meshed box has no cube" % (who, bnd, (Z, Y, X)))
+    closed_value = float(closed_value)
+    if closed and not (closed_value > 0.0 and math.isfinite(closed_value)):
+        raise ValueError("%s: closed_value must be finite and > 0 (an outside value), got %r" % (who, closed_value))
+    if 12 * B * Z * Y * X >= 2 ** 31:
+        raise ValueError("%s: %d samples: 12 triangles per sample do not fit an int32 offset" % (who, B * Z * Y * X))
+    if capacity is not None:
+        cap = (capacity, capacity) if isinstance(capacity, (int, np.integer)) else tuple(capacity)
+        if len(cap) != 2 or any(isinstance(c, bool) or int(c) != c or c < 0 or c > (2 ** 31 - 1) // 3 for c in cap):
+            raise ValueError("%s: capacity must be a row count >= 0 or a pair (vertex rows, face rows), got %r" % (who, capacity))
+        capacity = (int(cap[0]), int(cap[1]))
+    return bnd, closed, closed_value, capacity
+
+
+def _mesh_fit(V, T, capacity, who="extract_surface"):
+    """refuse a mesh that does not fit ``capacity = (vertex rows, face rows)``, naming the capacity needed"""
+    if capacity is not None and (V > capacity[0] or T > capacity[1]):
+        raise _lib.DeepFluidsHipError("%s: the mesh holds %d vertices and %d faces but capacity gives %d vertex rows and %d face rows; it "
+                                      "needs capacity=(%d, %d)" % (who, V, T, capacity[0], capacity[1], V, T))
+
+
+def extract_surface(phi, bnd=0, closed=False, closed_value=0.5, normals=False, capacity=None):
+    """The surface phi = 0 of a 3-D level set ``phi`` [B,Z,Y,X] (float32, contiguous, negative inside) as an indexed triangle mesh, one
+    per batch entry: a ``SurfaceMesh``.  Marching tetrahedra on the Kuhn split of the cubes between cell centres, as
+    include/deepfluids_hip.h defines it -- this project's own definition, not mantaflow's ``phi.createMesh`` (marching cubes); the
+    kernels give the bits of tests/liquid_mesh_ref.py's fp32 twin, order included.  A vertex sits on every grid edge (axis, face
+    diagonal or cube diagonal, always towards +) whose ends differ in sign, an exact zero counting as outside; triangles are wound with
+    their normal out of the liquid.
+    ``bnd``: leave out the ``bnd`` outermost samples per side.  ``closed`` (needs ``bnd >= 1``): mesh one layer more and read that outer
+    layer as ``max(phi, closed_value)``, which caps a liquid that rests against a wall: every mesh is then a closed surface.
+    ``normals``: also the normalised gradient of phi at the vertices.
+    Two launches and two scans: count, ``torch.cumsum`` twice, emit.  The host reads the two totals between them -- ONE
+    synchronisation -- and allocates exactly; with ``capacity`` (rows, or ``(vertex rows, face rows)``) the arrays are views of buffers
+    of that size instead, and a mesh that does not fit raises, naming the capacity needed, before anything is emitted."""
+    bnd, closed, closed_value, capacity = _mesh_args(phi, bnd, closed, closed_value, capacity)
+    with torch.no_grad():
+        ph = _prep(phi.detach(), "phi")
+        dims = [int(n) for n in ph.shape]
+        B, ncell = dims[0], dims[1] * dims[2] * dims[3]
+        n = B * ncell
+        tail = [bnd, 1 if closed else 0, closed_value, _stream()]
+        mask = _u8((n,), ph)
+        counts = _u8((2, n), ph)
+        call("df_mesh_count", _ptr(ph), _ptr(mask), _ptr(counts[0]), _ptr(counts[1]), *(dims + tail))
+        offsets = torch.zeros((2, n + 1), dtype=torch.int32, device=ph.device)
+        torch.cumsum(counts[0], 0, dtype=torch.int32, out=offsets[0, 1:])
+        torch.cumsum(counts[1], 0, dtype=torch.int32, out=offsets[1, 1:])
+        V, T = (int(x) for x in offsets[:, -1].cpu().numpy())           # the one synchronisation
+        _mesh_fit(V, T, capacity)
+        vcap, fcap = (V, T) if capacity is None else capacity
+        vertices = _empty((vcap, 3), ph)
+        nrm = _empty((vcap, 3), ph) if normals else None
+        faces = torch.empty((fcap, 3), dtype=torch.int32, device=ph.device)
+        call("df_mesh_emit", _ptr(ph), _ptr(mask), _ptr(offsets[0]), _ptr(offsets[1]), _ptr(vertices), _ptr(nrm), _ptr(faces), vcap, fcap,
+             *(dims + tail))
+        return SurfaceMesh(vertices[:V], faces[:T], None if nrm is None else nrm[:V], offsets[0, ::ncell].contiguous(),
+                           offsets[1, ::ncell].contiguous())
 
 
 def plane_view_np(x, xy_plane=True, project=True):

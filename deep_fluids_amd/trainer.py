@@ -29,7 +29,7 @@ from .ops import curl, curl3, jacobian, jacobian3, l1_mean, mse_mean, get_conv_s
 from .model import GeneratorBE, GeneratorBE3, AE, AE3, DiscriminatorPatch, DiscriminatorPatch3
 from .ops import concat, kl_bernoulli
 from .dist import GradSync, broadcast_trainer_state
-from .util import save_image, vort_image
+from .util import save_image, save_obj, vort_image
 
 
 def default_config(**over):
@@ -659,21 +659,28 @@ class Trainer(object):
 
     # ---- `advect()` of the liquid scene scripts (scene/liquid3_vis.py:47-148, scene/liquid_pos_size.py:47-132) ------------------
     def advect_liquid_(self, batch_manager, model_dir=None, p1=10, p2=2, test_b_num=None, *, body, dt=None, bnd=1, radius_factor=1.0,
-                       discretization=2, randomness=0.05, seed=123):
+                       discretization=2, randomness=0.05, seed=123, mesh=False, mesh_closed=True):
         """The sweep of ``test_`` looked at as a liquid, the way the reference's liquid scene scripts do (their ``advect()`` mode):
         seed marker particles in ``body`` (``ops.seed_particles``), generate every frame of the parameter pair (p1, p2), keep the frames
         on the device -- the kernels scale them by ``batch_manager.x_range`` -- and, per frame, rebuild the surface level set from the
         particles, write it as the grey frame ``<model_dir>/<p1>_<p2>/l_adv/%04d.png`` (3-D: of the z mean; clipped to [0,255] where
         the reference's cast wraps), then trace the particles through the frame's velocity with RK4 (``ops.liquid_sequence``).
         mantaflow's advectInGrid / gridParticleIndex / unionParticleLevelset are restated, not bit-identical; extrapolateMACSimple,
-        markFluidCells, resetOutflow, adjustNumber resampling, averagedParticleLevelset (the 2-D scene runs through the union form)
-        and meshing are left out.  ``body``: a level set [(Z,)Y,X], negative inside, or ``{"boxes": [(p0, p1), ...], "spheres":
+        markFluidCells, resetOutflow, adjustNumber resampling and averagedParticleLevelset (the 2-D scene runs through the union form)
+        are left out.  ``mesh=True`` (3-D sets only; ``ValueError`` for a 2-D one): each frame's level set, the one its PNG shows, is also
+        written as the triangle mesh ``<model_dir>/<p1>_<p2>/obj/%04d.obj``, the file scene/liquid3_vis.py:143 names
+        (``ops.extract_surface`` + ``util.save_obj``: this project's marching tetrahedra, not mantaflow's ``createMesh``; no smoothMesh /
+        subdivideMesh, no .bobj.gz).  ``mesh_closed`` caps the liquid where it rests against the wall band (``closed=True`` with
+        ``max(bnd, 1)``), so every file holds closed surfaces; without it the band is simply left out.  The PNGs and the returned
+        tensors do not depend on ``mesh``.  ``body``: a level set [(Z,)Y,X], negative inside, or ``{"boxes": [(p0, p1), ...], "spheres":
         [(center, radius), ...]}`` in fractions of the grid (xyz order; a radius in fractions of X), joined by a minimum
         (``liquid3_vis_body`` builds the one of scene/liquid3_vis.py).  ``dt``: 1.0 by default, as scene/liquid3_vis.py sets
         ``s.timestep = 1``; ``"dataset"`` takes args.txt's ``time_step``, as scene/liquid_pos_size.py does.
         Returns ``(out_dir, final positions [1,N,D], last phi [1,(Z,)Y,X])``, both on the device; the last phi is the level set of the
         positions before the last trace."""
         from PIL import Image
+        if mesh and not self.is_3d:
+            raise ValueError("advect_liquid_: mesh=True needs a 3-D set (2-D contours are not built)")
         model_dir = model_dir or self.effective_model_dir()
         z_c, niter, test_b_num = self._sweep_codes(batch_manager, p1, p2, test_b_num, "advect_liquid_")
         if dt is None:
@@ -690,8 +697,17 @@ class Trainer(object):
         if pos0.shape[0] == 0:
             raise ValueError("advect_liquid_: the body holds no cell inside the boundary band: nothing to trace")
         pos0 = torch.from_numpy(pos0).to(frames.device).unsqueeze(0)
+        on_frame = None
+        if mesh:
+            obj_dir = os.path.join(model_dir, "%d_%d" % (p1, p2), "obj")
+            os.makedirs(obj_dir, exist_ok=True)
+            mesh_bnd = max(int(bnd), 1) if mesh_closed else int(bnd)
+
+            def on_frame(t, phi):
+                m = ops.extract_surface(phi, bnd=mesh_bnd, closed=bool(mesh_closed))
+                save_obj(os.path.join(obj_dir, "%04d.obj" % t), m.vertices, m.faces)
         pos, phi, imgs = ops.liquid_sequence(pos0, frames.unsqueeze(1), dt, bnd=bnd, vel_scale=float(batch_manager.x_range),
-                                             radius_factor=radius_factor, images=True)
+                                             radius_factor=radius_factor, images=True, on_frame=on_frame)
         out_dir = os.path.join(model_dir, "%d_%d" % (p1, p2), "l_adv")
         os.makedirs(out_dir, exist_ok=True)
         for t in range(imgs.shape[0]):

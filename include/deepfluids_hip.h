@@ -545,7 +545,8 @@ int df_density_image3d(const float* density, uint8_t* img, int64_t B, int64_t Z,
  * pp.advectInGrid(IntRK4, deleteInObstacle=False) and rebuild a surface level set with gridParticleIndex + unionParticleLevelset.
  * mantaflow cannot be run beside this library, so bit parity with it is NOT claimed: the definition below is the contract
  * (tests/particles_ref.py restates it).  Left out: extrapolateMACSimple (a generator emits velocities everywhere), markFluidCells,
- * resetOutflow, adjustNumber resampling (N is constant over a sequence), averagedParticleLevelset, phi.setBound and meshing.
+ * resetOutflow, adjustNumber resampling (N is constant over a sequence), averagedParticleLevelset and phi.setBound (meshing: the
+ * "liquid surface meshes" block at the end of this header).
  *
  * pos [B,N,D] fp32 positions in cell units (x, y[, z]), D = 2 | 3; cell (i,j,k) spans [i,i+1) x [j,j+1) x [k,k+1) and is [..,k,j,i] in
  * the grids.  vel [B,(Z,)Y,X,D] fp32 MAC face values (component a of cell i sits on the cell's low-a face: the layout of df_advect_*),
@@ -1190,6 +1191,61 @@ int df_pressure_cg_direction_mg(void* ws, int64_t ws_bytes, void* hierarchy, int
                                 df_stream_t stream);
 int df_pressure_cg_update_mg(float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int dim, int64_t B, int64_t Z, int64_t Y,
                              int64_t X, int bnd, int64_t k, df_stream_t stream);
+
+/* ---- liquid surface meshes: a 3-D level set as an indexed triangle mesh (opt-in; nothing above calls it) ------------------------------
+ * What the reference's 3-D liquid scripts get from phi.createMesh(mesh) + mesh.save('obj/%04d.obj') (scene/liquid3_vis.py:136-143).  The
+ * definition below is this library's own, NOT mantaflow's marching cubes, and no parity with mantaflow's mesh is claimed:
+ * tests/liquid_mesh_ref.py restates it in fp64 and as an op-for-op fp32 twin whose bits the kernels give.  Marching tetrahedra on the Kuhn
+ * (Freudenthal) split of the cubes between cell centres; 3-D only (no 2-D contours, no smoothMesh / subdivideMesh: smooth phi instead).
+ * DF_VERSION is NOT raised by this block either (tests pin 207): look the symbols up.
+ *
+ *   samples    the cell centres of phi [B,Z,Y,X] (fp32, negative inside): sample (x, y, z) sits at (x + 0.5, y + 0.5, z + 0.5) in grid
+ *              units, the particles' coordinates.  Inside means phi < 0 strictly: an exact zero (of either sign) is outside.
+ *   meshed box samples lo .. hi per axis, lo = bnd', hi = extent - 1 - bnd'; bnd' = bnd, or bnd - 1 with `closed` (which needs bnd >= 1).
+ *              With `closed` every sample with a coordinate <= lo or >= hi (the box's outer layer, and whatever lies beyond it for the
+ *              normals' differences) is read as fmax(phi, closed_value), closed_value > 0: a liquid resting against a wall is capped
+ *              and every mesh is a closed surface.  "The value of a sample" below is this effective value.
+ *   edges      sample v owns the edges v -- v + d for the 7 non-zero 0/1 vectors d (a number 1..7: bit 0 = x, bit 1 = y, bit 2 = z)
+ *              whose far end lies in the box.  An edge carries a vertex when exactly one of its ends is inside.  mask[v] holds bit d - 1
+ *              for every such edge, and in bit 7 whether v itself is inside; 0 outside the box.
+ *   vertices   p = (v + 0.5) + t * d with t = s_v / (s_v - s_{v+d}), always from the owner's end; per coordinate (float)v_a + 0.5f, plus t
+ *              where d has the axis.  fp32, no contraction.  Order: by owner sample index (x fastest, over the whole batch), then d
+ *              ascending; the edge (v, d) is row vertex_offset[v] + popcount(mask[v] & ((1 << (d - 1)) - 1)).  No hashing, no atomics,
+ *              no sort: a mesh is indexed, one vertex per crossing edge, shared by every triangle around it.
+ *   normals    (optional)  g(u) = the central differences of the sample values at u, (s(u + e_a) - s(u - e_a)) * 0.5, on the GRID's border
+ *              the one-sided difference s(u + e_a) - s(u) resp. s(u) - s(u - e_a);  n = g(v) + t * (g(v + d) - g(v)) per component;
+ *              len = sqrt((n_x n_x + n_y n_y) + n_z n_z);  n / len, or (0, 0, 0) unless len > 0.
+ *   tets       the cube with corner c (every c with c + (1,1,1) in the box; cube index = the sample index of c) splits into 6 tets, one
+ *              per permutation (a, b, g) of the axes, in lexicographic order with x < y < z (xyz, xzy, yxz, yzx, zxy, zyx):
+ *              p0 = c, p1 = c + e_a, p2 = c + e_a + e_b, p3 = c + (1,1,1).  Tet edges are numbered by their corner pairs 01, 02, 03, 12,
+ *              13, 23; the pair (i, j), i < j, is the grid edge owned by p_i with d = p_j - p_i.
+ *   triangles  of a tet with n inside corners: n = 0, 4 none.  n = 1 (corner k inside, the others q1 < q2 < q3) and n = 3 (corner k
+ *              outside): the triangle (k q1, k q2, k q3).  n = 2 (i < j inside, k < l outside): (i k, i l, j l), then (i k, j l, j k).
+ *              Each is written with its last two vertices exchanged when flip = sigma ^ (n == 3) ^ (the permutation (a, b, g) is odd),
+ *              sigma the parity of (k, q1, q2, q3) resp. (i, j, k, l) as a permutation of (0, 1, 2, 3).  That winds every triangle so
+ *              that its normal points out of the liquid, towards larger phi.  At most 12 triangles per cube.  Order: by cube index (x
+ *              fastest, over the whole batch), then tet, then as listed.  A face holds vertex rows LOCAL to its batch entry (row -
+ *              vertex_offset[b * Z*Y*X]).
+ *
+ *   df_mesh_capacity_bound   what = 0: the edges of the box, the most vertices any phi can give; what = 1: 12 per cube; both times B.
+ *                            Pure host arithmetic (no device); a DF_E* code (< 0) for bad arguments.
+ *   df_mesh_count            mask, nvert (the vertices v owns, 0..7), ntri (the triangles of the cube with corner v, 0..12): [B*Z*Y*X] uint8.
+ *                            The caller scans nvert and ntri over the whole batch into vertex_offset, face_offset [B*Z*Y*X + 1] int32
+ *                            (exclusive; the last elements are the totals V and T), reads the two totals, and allocates.
+ *   df_mesh_emit             vertices [V,3] (xyz), normals [V,3] (nullable: not computed), faces [T,3] int32.  Rows >= vertex_capacity
+ *                            resp. face_capacity are not written, whatever the offsets hold: the caller, who holds the totals, has to
+ *                            refuse a result that did not fit.  A mask bit is believed only where its edge exists by the sample's index.
+ *                            bnd, closed and closed_value must be those of the count.  The batch is ragged in the entry_start style:
+ *                            vertex_start[b] = vertex_offset[b * Z*Y*X], face_start[b] = face_offset[b * Z*Y*X].
+ * Errors, on the host and before any launch: DF_EINVAL (null pointer, non-positive extent, bnd < 0, closed outside 0..1, closed with
+ * bnd = 0, a closed_value that is not finite and > 0, a negative capacity), DF_ESHAPE (an extent below 2, bnd too wide for the grid: the box
+ * has no cube; 12 * B*Z*Y*X >= 2^31, which covers the 7 vertices per sample as well), DF_EALIGN (4 bytes). */
+int64_t df_mesh_capacity_bound(int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, int closed, int what);
+int df_mesh_count(const float* phi, uint8_t* mask, uint8_t* nvert, uint8_t* ntri, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
+                  int closed, float closed_value, df_stream_t stream);
+int df_mesh_emit(const float* phi, const uint8_t* mask, const int32_t* vertex_offset, const int32_t* face_offset, float* vertices,
+                 float* normals, int32_t* faces, int64_t vertex_capacity, int64_t face_capacity, int64_t B, int64_t Z, int64_t Y, int64_t X,
+                 int bnd, int closed, float closed_value, df_stream_t stream);
 
 #ifdef __cplusplus
 }
