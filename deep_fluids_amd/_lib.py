@@ -15,250 +15,55 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "deepfluids_hip.h"
 P, I64, I32, F32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
 U32 = ctypes.c_uint32
 
-# name -> (restype, argtypes)
-SIGNATURES = {
-    "df_version": (I32, []),
-    "df_last_error": (ctypes.c_char_p, []),
-    "df_curl2d_fwd": (I32, [P, P, I64, I64, I64, P]),
-    "df_curl2d_bwd": (I32, [P, P, I64, I64, I64, P]),
-    "df_jacobian2d_fwd": (I32, [P, P, P, I64, I64, I64, P]),
-    "df_jacobian2d_bwd": (I32, [P, P, P, I64, I64, I64, P]),
-    "df_jacobian3d_fwd": (I32, [P, P, P, I64, I64, I64, I64, P]),
-    "df_jacobian3d_bwd": (I32, [P, P, P, I64, I64, I64, I64, P]),
-    "df_divergence2d": (I32, [P, P, I64, I64, I64, P]),
-    "df_divergence3d": (I32, [P, P, I64, I64, I64, I64, P]),
-    "df_velocity_loss3d_workspace_bytes": (I64, [I64, I64, I64, I64]),
-    "df_velocity_loss3d_fwd": (I32, [P, P, P, P, P, I64, I64, I64, I64, P, I64, P]),
-    "df_velocity_loss3d_bwd": (I32, [P, P, P, P, P, I64, I64, I64, I64, P, I64, P]),
-    "df_velocity_loss2d_workspace_bytes": (I64, [I64, I64, I64]),
-    "df_velocity_loss2d_fwd": (I32, [P, P, P, P, P, I64, I64, I64, P, I64, P]),
-    "df_velocity_loss2d_bwd": (I32, [P, P, P, P, P, I64, I64, I64, P, I64, P]),
-    "df_l1_mean_workspace_bytes": (I64, [I64]),
-    "df_l1_mean_fwd": (I32, [P, P, I64, P, P, I64, P]),
-    "df_l1_mean_bwd": (I32, [P, P, P, F32, P, I64, P]),
-    "df_lrelu_fwd": (I32, [P, P, F32, I64, P]),
-    "df_lrelu_bwd": (I32, [P, P, P, F32, I64, P]),
-    "df_add": (I32, [P, P, P, I64, P]),
-    "df_upsample2x_fwd": (I32, [P, P, I64, I64, I64, I64, I64, I32, P]),
-    "df_conv_general_out_dims": (I32, [I64, I64, I64, I32, I32, I32, P, P, P]),
-    "df_conv_general_fwd": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32, F32, P]),
-    "df_conv_general_dgrad": (I32, [P, P, P, I64, I64, I64, I64, I64, I64, I32, I32, I32, P]),
-    "df_conv_general_wgrad": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, I32, I32, P]),
-    "df_resize_nn_fwd": (I32, [P, P, I64, I64, I64, I64, I64, I64, I64, I64, P]),
-    "df_resize_nn_bwd": (I32, [P, P, I64, I64, I64, I64, I64, I64, I64, I64, P]),
-    "df_upsample2x_bwd": (I32, [P, P, I64, I64, I64, I64, I64, I32, P]),
-    "df_lrelu_bwd_pool2x": (I32, [P, P, P, P, F32, I64, I64, I64, I64, I64, I32, P]),
-    "df_linear_workspace_bytes": (I64, [I64, I64, I64]),
-    "df_linear_fwd": (I32, [P, P, P, P, I64, I64, I64, P, I64, P]),
-    "df_linear_bwd": (I32, [P, P, P, P, P, P, I64, I64, I64, P]),
-    "df_concat2_fwd": (I32, [P, P, P, I64, I64, I64, P]),
-    "df_concat2_bwd": (I32, [P, P, P, I64, I64, I64, P]),
-    "df_dilate2_odd": (I32, [P, P, I64, I64, I64, I64, I64, I32, P]),
-    "df_kl_bernoulli_fwd": (I32, [P, I64, I64, I64, F32, P, P]),
-    "df_kl_bernoulli_bwd": (I32, [P, P, F32, P, I64, I64, I64, F32, P]),
-    "df_sigmoid_fwd": (I32, [P, P, I64, P]),
-    "df_sigmoid_bwd": (I32, [P, P, P, I64, P]),
-    "df_mse_mean_fwd": (I32, [P, P, I64, P, P, I64, P]),
-    "df_mse_mean_bwd": (I32, [P, P, P, F32, P, I64, P]),
-    "df_colsum_workspace_bytes": (I64, [I64, I64]),
-    "df_colsum": (I32, [P, P, I64, I64, P, I64, P]),
-    "df_adam_tf1_step": (I32, [P, P, P, P, I64, F32, F32, F32, F32, F32, P]),
-    "df_conv_packed_elems": (I64, [I64, I64, I64, I32]),
-    "df_conv_pack_weights": (I32, [P, P, I64, I64, I64, I32, P]),
-    "df_conv_fwd": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I32, I32, F32, P]),
-    "df_conv_s2_fwd": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, I32, F32, P]),
-    "df_conv_s2_wgrad_workspace_bytes": (I64, [I64, I64, I64, I64, I64, I64, I32]),
-    "df_conv_s2_wgrad": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, P, I64, P]),
-    "df_conv_s2_dgrad": (I32, [P, P, P, I64, I64, I64, I64, I64, I64, I32, P]),
-    "df_conv_s2_dgrad_form": (I32, [P, I64, I64]),
-    "df_upconv_packed_elems": (I64, [I64, I64, I32, I32]),
-    "df_upconv_pack_weights": (I32, [P, P, I64, I64, I32, I32, P]),
-    "df_upconv_fwd": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, I32, F32, P]),
-    "df_upconv_dgrad": (I32, [P, P, P, I64, I64, I64, I64, I64, I64, I32, P]),
-    "df_upconv_wgrad_workspace_bytes": (I64, [I64, I64, I64, I64, I64, I64, I32]),
-    "df_upconv_wgrad": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, P, I64, P]),
-    "df_add_up2x": (I32, [P, P, P, I64, I64, I64, I64, I64, I32, P]),
-    "df_wino_packed_elems": (I64, [I64, I64, I32]),
-    "df_wino_pack_weights": (I32, [P, P, I64, I64, I32, P]),
-    "df_wino_conv_fwd": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I32, F32, P]),
-    "df_wino_conv_fwd_addup": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, F32, P]),
-    "df_wino_conv_fwd_addup_bits": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, F32, P]),
-    "df_lrelu_bits_bwd_pool2x": (I32, [P, P, P, P, F32, I64, I64, I64, I64, I64, P]),
-    "df_wino_upconv_fwd": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, F32, P]),
-    "df_wino_upconv_dgrad": (I32, [P, P, P, I64, I64, I64, I64, I64, I64, P]),
-    "df_wino_signbits_bytes": (I64, [I64, I64, I64, I64, I64]),
-    "df_wino_conv_fwd_bits": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I32, F32, P]),
-    "df_wino_upconv_fwd_bits": (I32, [P, P, P, P, P, I64, I64, I64, I64, I64, I64, F32, P]),
-    "df_wino43_packed_elems": (I64, [I64, I64, I32]),
-    "df_wino43_pack_weights": (I32, [P, P, I64, I64, I32, P]),
-    "df_wino43_conv": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I32, F32, P]),
-    "df_wino2d43_packed_elems": (I64, [I64, I64, I32]),
-    "df_wino2d43_pack_weights": (I32, [P, P, I64, I64, I32, P]),
-    "df_wino2d43_conv": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I32, F32, P]),
-    "df_wino2d43_signbits_bytes": (I64, [I64, I64, I64, I64]),
-    "df_wino2d43_conv_bits": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I32, F32, P]),
-    "df_wino2d43_conv_addup_bits": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, F32, P]),
-    "df_lrelu_words2d_bwd_pool2x": (I32, [P, P, P, P, F32, I64, I64, I64, I64, P]),
-    "df_wino2d_packed_elems": (I64, [I64, I64, I32]),
-    "df_wino2d_pack_weights": (I32, [P, P, I64, I64, I32, P]),
-    "df_wino2d_conv_fwd": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I32, F32, P]),
-    "df_wino2d_upconv_fwd": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I32, F32, P]),
-    "df_wino2d_upconv_dgrad": (I32, [P, P, P, I64, I64, I64, I64, I64, P]),
-    "df_conv_packed_elems_bf16x3": (I64, [I64, I64, I64, I32]),
-    "df_conv_pack_weights_bf16x3": (I32, [P, P, I64, I64, I64, I32, P]),
-    "df_conv_fwd_bf16x3": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I32, I32, F32, P]),
-    "df_upconv_packed_elems_bf16x3": (I64, [I64, I64, I32, I32]),
-    "df_upconv_pack_weights_bf16x3": (I32, [P, P, I64, I64, I32, I32, P]),
-    "df_upconv_fwd_bf16x3": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, I32, F32, P]),
-    "df_upconv_dgrad_bf16x3": (I32, [P, P, P, I64, I64, I64, I64, I64, I64, I32, P]),
-    "df_conv_wgrad_bf16x3": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, P, I64, P]),
-    "df_upconv_wgrad_bf16x3": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, P, I64, P]),
-    "df_adam_tf1_step_dev": (I32, [P, P, P, P, I64, P, F32, F32, F32, P]),
-    "df_gd_step": (I32, [P, P, I64, F32, F32, P]),
-    "df_gd_step_dev": (I32, [P, P, I64, P, P]),
-    "df_store_scalars": (I32, [P, I64, F32, F32, F32, F32, P]),
-    "df_conv_wgrad_workspace_bytes": (I64, [I64, I64, I64, I64, I64, I64, I32]),
-    "df_conv_wgrad": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, P, I64, P]),
-    "df_conv_wgrad_algo": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, P, I64, I32, P]),
-    "df_upconv_wgrad_algo": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, P, I64, I32, P]),
-    "df_conv_wgrad_form": (I32, [I64, I64, I64, I64, I64, I64, I32, I32]),
-    "df_upconv_wgrad_form": (I32, [I64, I64, I64, I64, I64, I64, I32, I32]),
-    "df_plane_views3d": (I32, [P, P, P, P, P, I64, I64, I64, I64, I64, P]),
-    "df_velocity_views3d": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P]),
-    "df_denorm_img2d": (I32, [P, P, I64, I64, I64, I64, I32, P]),
-    "df_advect_sl2d": (I32, [P, P, P, I64, I64, I64, F32, F32, I32, P]),
-    "df_advect_sl3d": (I32, [P, P, P, I64, I64, I64, I64, F32, F32, I32, P]),
-    "df_advect_mc2d": (I32, [P, P, P, P, I64, I64, I64, F32, F32, I32, I32, P]),
-    "df_advect_mc3d": (I32, [P, P, P, P, I64, I64, I64, I64, F32, F32, I32, I32, P]),
-    "df_density_source": (I32, [P, P, F32, P, I64, P]),
-    "df_density_image2d": (I32, [P, P, I64, I64, I64, P]),
-    "df_density_image3d": (I32, [P, P, I64, I64, I64, I64, P]),
-    "df_particles_advect2d": (I32, [P, P, P, I64, I64, I64, I64, F32, F32, I32, P]),
-    "df_particles_advect3d": (I32, [P, P, P, I64, I64, I64, I64, I64, F32, F32, I32, P]),
-    "df_particles_cell_keys2d": (I32, [P, P, I64, I64, I64, I64, P]),
-    "df_particles_cell_keys3d": (I32, [P, P, I64, I64, I64, I64, I64, P]),
-    "df_particles_gather": (I32, [P, P, P, I64, I32, P]),
-    "df_particle_levelset_union2d": (I32, [P, P, P, I64, I64, I64, I64, F32, P]),
-    "df_particle_levelset_union3d": (I32, [P, P, P, I64, I64, I64, I64, I64, F32, P]),
-    "df_mac_advect_sl2d": (I32, [P, P, I64, I64, I64, F32, I32, P]),
-    "df_mac_advect_sl3d": (I32, [P, P, I64, I64, I64, I64, F32, I32, P]),
-    "df_mac_advect_mc2d": (I32, [P, P, P, I64, I64, I64, F32, I32, I32, P]),
-    "df_mac_advect_mc3d": (I32, [P, P, P, I64, I64, I64, I64, F32, I32, I32, P]),
-    "df_wall_buoyancy2d": (I32, [P, P, P, I64, I64, I64, F32, F32, I32, P]),
-    "df_wall_buoyancy3d": (I32, [P, P, P, I64, I64, I64, I64, F32, F32, F32, I32, P]),
-    "df_pressure_workspace_bytes": (I64, [I64, I64, I64, I64]),
-    "df_pressure_init2d": (I32, [P, P, P, I64, I64, I64, I64, I32, P]),
-    "df_pressure_init3d": (I32, [P, P, P, I64, I64, I64, I64, I64, I32, P]),
-    "df_pressure_cg_direction2d": (I32, [P, I64, I64, I64, I64, I32, I64, F32, I64, P]),
-    "df_pressure_cg_direction3d": (I32, [P, I64, I64, I64, I64, I64, I32, I64, F32, I64, P]),
-    "df_pressure_cg_update2d": (I32, [P, P, I64, I64, I64, I64, I32, I64, P]),
-    "df_pressure_cg_update3d": (I32, [P, P, I64, I64, I64, I64, I64, I32, I64, P]),
-    "df_pressure_status": (I32, [P, I64, I64, I64, I64, I64, I64, P, P, P]),
-    "df_pressure_correct2d": (I32, [P, P, P, I64, I64, I64, I32, P]),
-    "df_pressure_correct3d": (I32, [P, P, P, I64, I64, I64, I64, I32, P]),
-    "df_obstacle_flags2d": (I32, [P, P, I64, I64, I64, I32, P]),
-    "df_obstacle_flags3d": (I32, [P, P, I64, I64, I64, I64, I32, P]),
-    "df_advect_mc2d_flags": (I32, [P, P, P, P, P, I64, I64, I64, F32, F32, I32, I32, P]),
-    "df_advect_mc3d_flags": (I32, [P, P, P, P, P, I64, I64, I64, I64, F32, F32, I32, I32, P]),
-    "df_mac_advect_mc2d_flags": (I32, [P, P, P, P, I64, I64, I64, F32, I32, I32, P]),
-    "df_mac_advect_mc3d_flags": (I32, [P, P, P, P, I64, I64, I64, I64, F32, I32, I32, P]),
-    "df_wall_buoyancy2d_flags": (I32, [P, P, P, P, I64, I64, I64, F32, F32, I32, P]),
-    "df_wall_buoyancy3d_flags": (I32, [P, P, P, P, I64, I64, I64, I64, F32, F32, F32, I32, P]),
-    "df_pressure_init2d_flags": (I32, [P, P, P, I64, P, I64, I64, I64, I32, P]),
-    "df_pressure_init3d_flags": (I32, [P, P, P, I64, P, I64, I64, I64, I64, I32, P]),
-    "df_pressure_cg_direction2d_flags": (I32, [P, I64, P, I64, I64, I64, I32, I64, F32, I64, P]),
-    "df_pressure_cg_direction3d_flags": (I32, [P, I64, P, I64, I64, I64, I64, I32, I64, F32, I64, P]),
-    "df_pressure_cg_update2d_flags": (I32, [P, P, I64, P, I64, I64, I64, I32, I64, P]),
-    "df_pressure_cg_update3d_flags": (I32, [P, P, I64, P, I64, I64, I64, I64, I32, I64, P]),
-    "df_pressure_correct2d_flags": (I32, [P, P, P, P, I64, I64, I64, I32, P]),
-    "df_pressure_correct3d_flags": (I32, [P, P, P, P, I64, I64, I64, I64, I32, P]),
-    "df_mac_advect_sl2d_open": (I32, [P, P, I64, I64, I64, F32, I32, I32, P]),
-    "df_mac_advect_sl3d_open": (I32, [P, P, I64, I64, I64, I64, F32, I32, I32, P]),
-    "df_mac_advect_mc2d_open": (I32, [P, P, P, P, I64, I64, I64, F32, I32, I32, I32, P]),
-    "df_mac_advect_mc3d_open": (I32, [P, P, P, P, I64, I64, I64, I64, F32, I32, I32, I32, P]),
-    "df_wall_buoyancy2d_open": (I32, [P, P, P, P, I64, I64, I64, F32, F32, I32, I32, P]),
-    "df_wall_buoyancy3d_open": (I32, [P, P, P, P, I64, I64, I64, I64, F32, F32, F32, I32, I32, P]),
-    "df_pressure_cg_direction2d_open": (I32, [P, I64, P, I64, I64, I64, I32, I32, I64, F32, I64, P]),
-    "df_pressure_cg_direction3d_open": (I32, [P, I64, P, I64, I64, I64, I64, I32, I32, I64, F32, I64, P]),
-    "df_pressure_correct2d_open": (I32, [P, P, P, P, I64, I64, I64, I32, I32, P]),
-    "df_pressure_correct3d_open": (I32, [P, P, P, P, I64, I64, I64, I64, I32, I32, P]),
-    "df_open_extrapolate2d": (I32, [P, I64, I64, I64, I32, I32, P]),
-    "df_open_extrapolate3d": (I32, [P, I64, I64, I64, I64, I32, I32, P]),
-    "df_density_sphere_source2d": (I32, [P, P, F32, F32, P, I64, I64, I64, P]),
-    "df_density_sphere_source3d": (I32, [P, P, F32, F32, P, I64, I64, I64, I64, P]),
-    "df_density_noise_inflow2d": (I32, [P, P, P, P, F32, F32, F32, I64, I64, I64, I32, P]),
-    "df_density_noise_inflow3d": (I32, [P, P, P, P, F32, F32, F32, I64, I64, I64, I64, I32, P]),
-    "df_mac_cylinder_stamp2d": (I32, [P, P, P, P, I64, I64, I64, P]),
-    "df_mac_cylinder_stamp3d": (I32, [P, P, P, P, I64, I64, I64, I64, P]),
-    "df_wall_buoyancy2d_open_dev": (I32, [P, P, P, P, P, I64, I64, I64, I32, I32, P]),
-    "df_wall_buoyancy3d_open_dev": (I32, [P, P, P, P, P, I64, I64, I64, I64, I32, I32, P]),
-    "df_liquid_p2g2d": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, P]),
-    "df_liquid_p2g3d": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, P]),
-    "df_mac_extrapolate2d": (I32, [P, P, P, P, I64, I64, I64, I32, I32, P]),
-    "df_mac_extrapolate3d": (I32, [P, P, P, P, I64, I64, I64, I64, I32, I32, P]),
-    "df_liquid_flags2d": (I32, [P, P, P, I64, I64, I64, I64, I32, P]),
-    "df_liquid_flags3d": (I32, [P, P, P, I64, I64, I64, I64, I64, I32, P]),
-    "df_liquid_forces2d": (I32, [P, P, P, I64, I64, I64, F32, F32, I32, P]),
-    "df_liquid_forces3d": (I32, [P, P, P, I64, I64, I64, I64, F32, F32, F32, I32, P]),
-    "df_particle_levelset_averaged2d": (I32, [P, P, P, I64, I64, I64, I64, F32, P]),
-    "df_particle_levelset_averaged3d": (I32, [P, P, P, I64, I64, I64, I64, I64, F32, P]),
-    "df_levelset_smooth2d": (I32, [P, P, I64, I64, I64, I32, I32, F32, P]),
-    "df_levelset_smooth3d": (I32, [P, P, I64, I64, I64, I64, I32, I32, F32, P]),
-    "df_pressure_workspace_bytes_gf": (I64, [I64, I64, I64, I64]),
-    "df_pressure_init2d_gf": (I32, [P, P, P, I64, P, P, I64, I64, I64, I32, F32, P]),
-    "df_pressure_init3d_gf": (I32, [P, P, P, I64, P, P, I64, I64, I64, I64, I32, F32, P]),
-    "df_pressure_cg_direction2d_gf": (I32, [P, I64, P, I64, I64, I64, I32, I64, F32, I64, P]),
-    "df_pressure_cg_direction3d_gf": (I32, [P, I64, P, I64, I64, I64, I64, I32, I64, F32, I64, P]),
-    "df_pressure_cg_update2d_gf": (I32, [P, P, I64, P, I64, I64, I64, I32, I64, P]),
-    "df_pressure_cg_update3d_gf": (I32, [P, P, I64, P, I64, I64, I64, I64, I32, I64, P]),
-    "df_pressure_correct2d_gf": (I32, [P, P, P, P, P, I64, I64, I64, I32, F32, P]),
-    "df_pressure_correct3d_gf": (I32, [P, P, P, P, P, I64, I64, I64, I64, I32, F32, P]),
-    "df_pressure_cg_direction2d_liquid": (I32, [P, I64, P, I64, I64, I64, I32, I64, F32, I64, P]),
-    "df_pressure_cg_direction3d_liquid": (I32, [P, I64, P, I64, I64, I64, I64, I32, I64, F32, I64, P]),
-    "df_pressure_correct2d_liquid": (I32, [P, P, P, P, I64, I64, I64, I32, P]),
-    "df_pressure_correct3d_liquid": (I32, [P, P, P, P, I64, I64, I64, I64, I32, P]),
-    "df_flip_update2d": (I32, [P, P, P, P, P, I64, I64, I64, I64, F32, P]),
-    "df_flip_update3d": (I32, [P, P, P, P, P, I64, I64, I64, I64, I64, F32, P]),
-    "df_diffuse_workspace_bytes": (I64, [I64, I64, I64, I64, I32]),
-    "df_diffuse_init2d": (I32, [P, P, P, I64, I64, I64, I64, I32, P]),
-    "df_diffuse_init3d": (I32, [P, P, P, I64, I64, I64, I64, I64, I32, P]),
-    "df_diffuse_cg_direction2d": (I32, [P, P, I64, I64, I64, I64, I32, I64, F32, I64, P]),
-    "df_diffuse_cg_direction3d": (I32, [P, P, I64, I64, I64, I64, I64, I32, I64, F32, I64, P]),
-    "df_diffuse_cg_update2d": (I32, [P, I64, I64, I64, I64, I32, I64, P]),
-    "df_diffuse_cg_update3d": (I32, [P, I64, I64, I64, I64, I64, I32, I64, P]),
-    "df_diffuse_finish2d": (I32, [P, I64, P, I64, I64, I64, I32, P]),
-    "df_diffuse_finish3d": (I32, [P, I64, P, I64, I64, I64, I64, I32, P]),
-    "df_particles_advect2d_ragged": (I32, [P, P, P, P, I64, I64, I64, I64, F32, F32, I32, P]),
-    "df_particles_advect3d_ragged": (I32, [P, P, P, P, I64, I64, I64, I64, I64, F32, F32, I32, P]),
-    "df_particles_cell_keys2d_ragged": (I32, [P, P, P, I64, I64, I64, I64, P]),
-    "df_particles_cell_keys3d_ragged": (I32, [P, P, P, I64, I64, I64, I64, I64, P]),
-    "df_flip_update2d_ragged": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, F32, P]),
-    "df_flip_update3d_ragged": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, F32, P]),
-    "df_levelset_extrapolate_marks2d": (I32, [P, P, I64, I64, I64, I32, P]),
-    "df_levelset_extrapolate_marks3d": (I32, [P, P, I64, I64, I64, I64, I32, P]),
-    "df_levelset_extrapolate_layer2d": (I32, [P, P, I64, I64, I64, I32, I32, P]),
-    "df_levelset_extrapolate_layer3d": (I32, [P, P, I64, I64, I64, I64, I32, I32, P]),
-    "df_resample_count2d": (I32, [P, P, P, P, P, P, P, I64, I64, I64, I64, I32, I32, I32, F32, P]),
-    "df_resample_count3d": (I32, [P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I32, I32, I32, F32, P]),
-    "df_resample_scatter2d": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I32, U32, U32, P]),
-    "df_resample_scatter3d": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I32, U32, U32, P]),
-    "df_mg_hierarchy_bytes": (I64, [I32, I64, I64, I64, I64]),
-    "df_mg_levels": (I32, [I32, I64, I64, I64]),
-    "df_mg_sweeps": (I32, [I32]),
-    "df_mg_omega": (F32, []),
-    "df_mg_cycle_launches": (I32, [I32, I64, I64, I64]),
-    "df_mg_level_offset": (I64, [I32, I64, I64, I64, I64, I32, I32]),
-    "df_mg_build": (I32, [P, I64, P, I32, I64, I64, I64, I64, I32, I32, P]),
-    "df_mg_apply": (I32, [P, I64, P, I32, I64, I64, I64, I64, F32, P]),
-    "df_pressure_mg_precondition": (I32, [P, I64, P, I64, I32, I64, I64, I64, I64, F32, I64, P]),
-    "df_pressure_cg_direction_mg": (I32, [P, I64, P, I64, P, I32, I64, I64, I64, I64, I32, I32, I64, F32, I64, P]),
-    "df_pressure_cg_update_mg": (I32, [P, P, I64, P, I32, I64, I64, I64, I64, I32, I64, P]),
-    "df_mesh_capacity_bound": (I64, [I64, I64, I64, I64, I32, I32, I32]),
-    "df_mesh_count": (I32, [P, P, P, P, I64, I64, I64, I64, I32, I32, F32, P]),
-    "df_mesh_emit": (I32, [P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I32, I32, F32, P]),
-}
+# the header's scalar types; a parameter with a `*` in it is a pointer whatever it points to
+CTYPES = {"int": I32, "int64_t": I64, "float": F32, "uint32_t": U32, "df_stream_t": P, "const char*": ctypes.c_char_p}
 
-DF_CONV_LRELU, DF_CONV_RESIDUAL, DF_CONV_MASK, DF_CONV_BIAS, DF_CONV_ADDUP, DF_CONV_VALU_ONLY = 1, 2, 4, 8, 16, 32
+
+class DeepFluidsHipError(RuntimeError):
+    pass
+
+
+def parse_header(text):
+    """The header is the only description of the C-ABI:  ``(signatures, constants)`` of its text, signatures as name -> (restype, argtypes),
+    constants as name -> int for ``DF_VERSION`` and every enumerator.  Strict: every statement with a parenthesis in it must be a
+    ``ret df_name(params);`` whose types are all in ``CTYPES``; anything else raises instead of binding a guess."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    constants = {n: int(v) for n, v in re.findall(r"^\s*#\s*define\s+(DF_VERSION)\s+(\d+)", text, re.M)}
+    for body in re.findall(r"\benum\s*\{(.*?)\}", text, re.S):
+        constants.update((n, int(v, 0)) for n, v in re.findall(r"(\w+)\s*=\s*([-+\w]+)", body))
+
+    def ctype(decl, proto):
+        t = re.sub(r"\s*\*\s*", "* ", decl).strip()
+        if t not in CTYPES:
+            raise DeepFluidsHipError("%s: type `%s` is not one the ctypes binding knows (%s)" % (proto, t, ", ".join(sorted(CTYPES))))
+        return CTYPES[t]
+
+    signatures = {}
+    for stmt in re.split(r"[;{}]", re.sub(r"^\s*#.*$", "", text, flags=re.M)):
+        if "(" not in stmt:
+            continue
+        proto = " ".join(stmt.split())
+        m = re.fullmatch(r"(.+?)\b(df_\w+) ?\((.*)\)", proto)
+        if m is None:
+            raise DeepFluidsHipError("not a `ret df_name(params)` prototype: %s" % proto)
+        params = [] if m.group(3).strip() == "void" else [q.strip() for q in m.group(3).split(",")]
+        # a parameter is `type name`: the name goes, and what holds a `*` is a pointer
+        signatures[m.group(2)] = (ctype(m.group(1), proto), [P if "*" in q else ctype(re.sub(r"\w+$", "", q), proto) for q in params])
+    return signatures, constants
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return f.read()
+    except OSError as e:
+        raise DeepFluidsHipError("the C-ABI header %s cannot be read (%s): the ctypes binding is derived from it" % (HEADER_PATH, e))
+
+
+# SIGNATURES: name -> (restype, argtypes) of every entry point;  CONSTANTS: DF_VERSION, the status codes DF_OK / DF_EINVAL / DF_ESHAPE / DF_EALIGN /
+# DF_EWORKSPACE and the conv flags DF_CONV_LRELU / _RESIDUAL / _MASK / _BIAS / _ADDUP / _VALU_ONLY, each also a module attribute of its own name
+SIGNATURES, CONSTANTS = parse_header(_read_header())
+globals().update(CONSTANTS)
 
 
 class NoiseParams(ctypes.Structure):
@@ -268,10 +73,6 @@ class NoiseParams(ctypes.Structure):
 
 
 _lib = None
-
-
-class DeepFluidsHipError(RuntimeError):
-    pass
 
 
 def declared_symbols():
@@ -357,14 +158,15 @@ _QUERY_CACHE = {}
 
 
 def query(name, *args):
-    """Call a value-returning helper (workspace sizes, packed-operand sizes, algorithm forms, version).  Every one of them is a pure function of
-    its integer arguments, so the answers are memoised: a 2-D train step at the reference's default batch asks ~150 of them, and its host issue
-    time (2.6 ms) is within a millisecond of the device time (3.5 ms)."""
+    """Call a value-returning helper (workspace sizes, packed-operand sizes, algorithm forms, version).  One without a pointer argument is a pure
+    function of its integer arguments, so its answers are memoised: a 2-D train step at the reference's default batch asks ~150 of them, and its
+    host issue time (2.6 ms) is within a millisecond of the device time (3.5 ms).  One that takes a pointer is asked every time (a cache keyed on
+    addresses only grows)."""
     key = (name,) + args
     try:
         return _QUERY_CACHE[key]
     except KeyError:
-        v = _QUERY_CACHE[key] = getattr(lib(), name)(*args)
+        v = getattr(lib(), name)(*args)
+        if P not in SIGNATURES[name][1]:
+            _QUERY_CACHE[key] = v
         return v
-    except TypeError:      # an unhashable argument: not memoised
-        return getattr(lib(), name)(*args)
