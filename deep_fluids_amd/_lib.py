@@ -11,6 +11,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdeepfluids_hip.so")
 TUNING_LIB_PATH = os.path.join(_HERE, "csrc", "libdeepfluids_hip_tuning.so")      # tools/ only: `use_tuning_library()`
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "deepfluids_hip.h")
+# the fused field metrics: a library and a header of their own (deepfluids_hip.h is frozen at DF_VERSION 207), bound the same way
+METRICS_LIB_PATH = os.path.join(_HERE, "csrc", "libdeepfluids_hip_metrics.so")
+METRICS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "deepfluids_hip_metrics.h")
 
 P, I64, I32, F32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
 U32 = ctypes.c_uint32
@@ -52,18 +55,22 @@ def parse_header(text):
     return signatures, constants
 
 
-def _read_header():
+def _read_header(path=None):
+    path = path or HEADER_PATH
     try:
-        with open(HEADER_PATH) as f:
+        with open(path) as f:
             return f.read()
     except OSError as e:
-        raise DeepFluidsHipError("the C-ABI header %s cannot be read (%s): the ctypes binding is derived from it" % (HEADER_PATH, e))
+        raise DeepFluidsHipError("the C-ABI header %s cannot be read (%s): the ctypes binding is derived from it" % (path, e))
 
 
 # SIGNATURES: name -> (restype, argtypes) of every entry point;  CONSTANTS: DF_VERSION, the status codes DF_OK / DF_EINVAL / DF_ESHAPE / DF_EALIGN /
 # DF_EWORKSPACE and the conv flags DF_CONV_LRELU / _RESIDUAL / _MASK / _BIAS / _ADDUP / _VALU_ONLY, each also a module attribute of its own name
 SIGNATURES, CONSTANTS = parse_header(_read_header())
 globals().update(CONSTANTS)
+# ... and of deepfluids_hip_metrics.h: df_field_metrics* and the DF_FM_* word indices of their output rows
+METRICS_SIGNATURES, METRICS_CONSTANTS = parse_header(_read_header(METRICS_HEADER_PATH))
+globals().update(METRICS_CONSTANTS)
 
 
 class NoiseParams(ctypes.Structure):
@@ -73,6 +80,7 @@ class NoiseParams(ctypes.Structure):
 
 
 _lib = None
+_metrics_lib = None
 
 
 def declared_symbols():
@@ -111,6 +119,27 @@ def lib():
     return _lib
 
 
+def metrics_lib():
+    """libdeepfluids_hip_metrics.so; the main library is loaded first (it holds the error buffer the metrics library writes to)"""
+    global _metrics_lib
+    if _metrics_lib is None:
+        lib()
+        if not os.path.exists(METRICS_LIB_PATH):
+            raise DeepFluidsHipError("libdeepfluids_hip_metrics.so not found at %s -- `make -C deep_fluids_amd/csrc` builds it with the main "
+                                     "library. There is no CPU fallback." % METRICS_LIB_PATH)
+        handle = ctypes.CDLL(METRICS_LIB_PATH)
+        for name, (res, args) in METRICS_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype = res
+            fn.argtypes = args
+        _metrics_lib = handle
+    return _metrics_lib
+
+
+def _handle(name):
+    return metrics_lib() if name in METRICS_SIGNATURES else lib()
+
+
 class KernelTimer(object):
     """Optional HIP-event timing of selected C-ABI calls (bench.py's live roofline measurement).
 
@@ -144,11 +173,11 @@ def call(name, *args):
         import torch
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
         e0.record()
-        rc = getattr(h, name)(*args)
+        rc = getattr(_handle(name), name)(*args)
         e1.record()
         TIMER.records.append((hit[0], hit[1], e0, e1))
     else:
-        rc = getattr(h, name)(*args)
+        rc = getattr(_handle(name), name)(*args)
     if rc != 0:
         msg = h.df_last_error()
         raise DeepFluidsHipError("%s failed (%d): %s" % (name, rc, msg.decode() if msg else ""))
@@ -166,7 +195,7 @@ def query(name, *args):
     try:
         return _QUERY_CACHE[key]
     except KeyError:
-        v = getattr(lib(), name)(*args)
-        if P not in SIGNATURES[name][1]:
+        v = getattr(_handle(name), name)(*args)
+        if P not in (METRICS_SIGNATURES.get(name) or SIGNATURES[name])[1]:
             _QUERY_CACHE[key] = v
         return v

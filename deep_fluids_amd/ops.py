@@ -28,7 +28,7 @@ __all__ = [
     "lrelu", "conv2d", "conv3d", "linear", "upscale", "upscale3", "resize_nearest_neighbor", "reshape",
     "int_shape", "get_conv_shape", "nchw_to_nhwc", "nhwc_to_nchw", "add", "concat", "sigmoid", "mse_mean",
     "jacobian", "jacobian3", "curl", "curl3", "divergence", "divergence3", "pgrad",
-    "vort_np", "curl_np", "grad_np", "jacobian_np3", "l1_mean", "velocity_loss",
+    "vort_np", "curl_np", "grad_np", "jacobian_np3", "l1_mean", "velocity_loss", "field_metrics", "field_metrics_workspace", "FieldMetrics",
     "denorm_img", "plane_view", "denorm_img3", "plane_view_np", "velocity_views3", "add_channels", "remove_channels",
     "advect", "advect_sequence", "advect_workspace", "density_image", "sphere_mask",
     "advect_velocity", "wall_buoyancy", "solve_pressure", "pressure_workspace", "smoke_step", "simulate_smoke", "default_buoyancy_force", "default_max_iter", "obstacle_flags", "ObstacleFlags",
@@ -1573,6 +1573,165 @@ def velocity_loss(psi, x):
     ``u = curl(psi) | jacobian3(psi)[1]``, ``l1 = reduce_mean(abs(u - x))``, ``j_l1 = reduce_mean(abs(jacobian(u)[0] - jacobian(x)[0]))``.
     Gradients flow to ``psi`` through ``l1`` and ``j_l1``; ``u`` is returned detached (for metrics / summaries)."""
     return _VelocityLoss.apply(psi, x)
+
+
+# ---- fused field metrics (include/deepfluids_hip_metrics.h; csrc/metrics.hip): evaluation only, no autograd ----
+class FieldMetrics(object):
+    """The result of ``field_metrics``: per batch entry, over its counted cells.  ``raw`` is the int32 tensor [B, DF_FM_WORDS] the kernel
+    wrote; every quantity is a view [B] of it (int32: ``count``, ``div_count``, ``argmax``; float32: the rest), on the device of the
+    fields:
+      ``count``          the counted cells;  ``div_count``: those of them that hold a divergence (x < X-1, y < Y-1 (, z < Z-1))
+      ``sum_abs``, ``sum_sq``, ``max_abs``, ``argmax``    sum |g-x| and sum (g-x)^2 over cells and components, max |g-x| and the flat
+                         cell index of it (the lowest on a tie, -1 when nothing is counted)
+      ``sum_abs_x``, ``sum_sq_x``                         the same two sums of x alone
+      ``sum_abs_jac``    sum |J(g)-J(x)| over cells and the D*D components of ``jacobian`` / ``jacobian3`` (what g_loss_j_l1 averages)
+      ``sum_abs_div_g``, ``max_abs_div_g``, ``sum_abs_div_x``, ``max_abs_div_x``   of ``divergence`` / ``divergence3`` of g and of x
+    The derived properties are float64 [B], computed from these without another pass: ``l1`` = sum_abs / (count D), ``rmse`` =
+    sqrt(sum_sq / (count D)), ``rel_l1`` = sum_abs / sum_abs_x, ``rel_l2`` = sqrt(sum_sq / sum_sq_x), ``jacobian_l1`` = sum_abs_jac /
+    (count D D), ``div_l1_g`` / ``div_l1_x`` = sum_abs_div_* / div_count.  An entry with nothing counted has zero sums and ``nan`` means;
+    ``rel_*`` of an entry whose x sums are 0 are ``nan``."""
+    INTS = ("count", "div_count", "argmax")
+    FLOATS = ("sum_abs", "sum_sq", "max_abs", "sum_abs_x", "sum_sq_x", "sum_abs_jac", "sum_abs_div_g", "max_abs_div_g", "sum_abs_div_x",
+              "max_abs_div_x")
+    QUANTITIES = INTS + FLOATS
+    DERIVED = ("l1", "rmse", "rel_l1", "rel_l2", "jacobian_l1", "div_l1_g", "div_l1_x")
+    LINEAR = ("max_abs", "max_abs_div_g", "max_abs_div_x", "l1", "rmse", "jacobian_l1", "div_l1_g", "div_l1_x")   # scale with the velocity unit
+
+    def __init__(self, raw, dim):
+        if raw.dtype != torch.int32 or raw.dim() != 2 or raw.shape[1] != _lib.DF_FM_WORDS or dim not in (2, 3):
+            raise ValueError("FieldMetrics: raw must be int32 [B, %d] and dim 2 or 3" % _lib.DF_FM_WORDS)
+        self.raw, self.dim = raw, dim
+
+    def __getattr__(self, name):
+        if name in FieldMetrics.QUANTITIES:
+            word = getattr(_lib, "DF_FM_" + name.upper())
+            return (self.raw if name in FieldMetrics.INTS else self.raw.view(torch.float32))[:, word]
+        raise AttributeError(name)
+
+    @property
+    def batch(self):
+        return self.raw.shape[0]
+
+    def cpu(self):
+        return FieldMetrics(self.raw.cpu(), self.dim)
+
+    @staticmethod
+    def cat(parts):
+        """the entries of several results in one (still on the device)"""
+        return FieldMetrics(torch.cat([p.raw for p in parts], dim=0), parts[0].dim)
+
+    def _n(self, power):
+        return self.count.double() * float(self.dim ** power)
+
+    @staticmethod
+    def _rel(num, den):
+        return torch.where(den == 0, torch.full_like(num, float("nan")), num / den)
+
+    @property
+    def l1(self):
+        return self.sum_abs.double() / self._n(1)
+
+    @property
+    def rmse(self):
+        return torch.sqrt(self.sum_sq.double() / self._n(1))
+
+    @property
+    def rel_l1(self):
+        return self._rel(self.sum_abs.double(), self.sum_abs_x.double())
+
+    @property
+    def rel_l2(self):
+        return torch.sqrt(self._rel(self.sum_sq.double(), self.sum_sq_x.double()))
+
+    @property
+    def jacobian_l1(self):
+        return self.sum_abs_jac.double() / self._n(2)
+
+    @property
+    def div_l1_g(self):
+        return self.sum_abs_div_g.double() / self.div_count.double()
+
+    @property
+    def div_l1_x(self):
+        return self.sum_abs_div_x.double() / self.div_count.double()
+
+
+def _field_metrics_args(g, x, mask, workspace):
+    """the checks of ``field_metrics`` that need no device: ``(dim, extents [B,Z,Y,X], mask as uint8 | None, mask_per_entry, workspace bytes)``"""
+    who = "field_metrics"
+    for t, name in ((g, "g"), (x, "x")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a torch.Tensor on the MI355X (got %r)" % (who, name, type(t)))
+    if g.dim() not in (4, 5) or g.shape[-1] != g.dim() - 2:
+        raise ValueError("%s expects velocity fields [B,Y,X,2] or [B,Z,Y,X,3], got g %s" % (who, tuple(g.shape)))
+    if tuple(x.shape) != tuple(g.shape):
+        raise ValueError("%s: g %s and x %s disagree in shape" % (who, tuple(g.shape), tuple(x.shape)))
+    for t, name in ((g, "g"), (x, "x")):
+        if t.dtype != torch.float32:
+            raise ValueError("%s: %s must be float32 (g and x in the same dtype), got %s" % (who, name, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous (strides %s for shape %s)" % (who, name, tuple(t.stride()), tuple(t.shape)))
+    dim = g.dim() - 2
+    spatial = tuple(int(n) for n in g.shape[1:-1])
+    B = int(g.shape[0])
+    if B < 1 or min(spatial) < 2:
+        raise ValueError("%s: the forward differences need every extent >= 2 (and B >= 1), got %s" % (who, tuple(g.shape)))
+    ext = [B] + ([1] if dim == 2 else []) + list(spatial)
+    need = query("df_field_metrics_workspace_bytes", dim, *ext)
+    if need < 0:
+        raise ValueError("%s: %s cells per entry do not fit the int32 cell index" % (who, " x ".join(str(n) for n in spatial)))
+    per_entry = 0
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("%s: mask must be a uint8 (or bool) tensor, got %s" % (who, getattr(mask, "dtype", type(mask))))
+        if tuple(mask.shape) not in (spatial, (B,) + spatial):
+            raise ValueError("%s: mask must be [(Z,)Y,X] = %s (shared by the batch) or [B,(Z,)Y,X], got %s" % (who, spatial, tuple(mask.shape)))
+        if not mask.is_contiguous():
+            raise ValueError("%s: mask must be contiguous" % who)
+        # ([B,..] with B = 1 and the shared form hold the same bytes)
+        per_entry = 1 if mask.dim() == dim + 1 else 0
+        mask = mask.view(torch.uint8)
+    if workspace is not None:
+        if not isinstance(workspace, torch.Tensor) or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
+            raise ValueError("%s: workspace must be a contiguous tensor of >= %d bytes (field_metrics_workspace)" % (who, need))
+    return dim, ext, mask, per_entry, need
+
+
+def field_metrics_workspace(g):
+    """The scratch ``field_metrics`` needs for fields of the shape of ``g`` (80 bytes per 1024 cells); reusable across calls."""
+    dim = g.dim() - 2
+    ext = [int(g.shape[0])] + ([1] if dim == 2 else []) + [int(n) for n in g.shape[1:-1]]
+    need = query("df_field_metrics_workspace_bytes", dim, *ext)
+    if need < 0:
+        raise ValueError("field_metrics_workspace: no workspace for fields of shape %s" % (tuple(g.shape),))
+    return torch.empty((need // 8,), dtype=torch.float64, device=g.device)
+
+
+def field_metrics(g, x, mask=None, workspace=None):
+    """How well a generated velocity field ``g`` reproduces the ground truth ``x`` ([B,Y,X,2] or [B,Z,Y,X,3], float32, contiguous), per
+    batch entry, as ONE fused pass: each field is read once, nothing the size of a field is allocated.  Returns a ``FieldMetrics``:
+    the counted cells, sum |g-x|, sum (g-x)^2, max |g-x| and its cell, sum |x|, sum x^2, sum |J(g)-J(x)| with the forward-difference
+    Jacobian of ``jacobian`` / ``jacobian3`` (the quantity g_loss_j_l1 averages), and the sum and max of |div g| and |div x| with the
+    divergence of ``divergence`` / ``divergence3`` -- and, derived from them, ``l1``, ``rmse``, ``rel_l1``, ``rel_l2``,
+    ``jacobian_l1``, ``div_l1_g``, ``div_l1_x``.
+    ``mask``: uint8 (or bool) [(Z,)Y,X], shared by the batch, or [B,(Z,)Y,X]; a cell is counted where it is non-zero (everywhere without
+    a mask).  A stencil value belongs to the cell where the stencil ops store it and is counted with that cell, whatever the mask says
+    about the neighbours it reads.
+    include/deepfluids_hip_metrics.h fixes the arithmetic and the order of every sum (fp32 per thread, fp64 across threads and
+    workgroups, no atomics): two calls give the same bits, an entry's numbers do not depend on the rest of the batch, and
+    tests/field_metrics_ref.py restates it in NumPy.  ``workspace``: see ``field_metrics_workspace``.  No autograd."""
+    dim, ext, mask, per_entry, need = _field_metrics_args(g, x, mask, workspace)
+    with torch.no_grad():
+        g, x = _prep(g.detach(), "g"), _prep(x.detach(), "x")
+        if x.device != g.device or (mask is not None and mask.device != g.device) or (workspace is not None and workspace.device != g.device):
+            raise ValueError("field_metrics: g, x, mask and workspace must be on one device")
+        ws = workspace if workspace is not None else field_metrics_workspace(g)
+        if ws.data_ptr() % 8:
+            raise ValueError("field_metrics: workspace must be 8-byte aligned")
+        raw = torch.empty((ext[0], _lib.DF_FM_WORDS), dtype=torch.int32, device=g.device)
+        call("df_field_metrics%dd" % dim, _ptr(g), _ptr(x), _ptr(mask), per_entry, _ptr(raw), _ptr(ws), ws.numel() * ws.element_size(),
+             *(ext[:1] + ext[-dim:] + [_stream()]))
+        return FieldMetrics(raw, dim)
 
 
 # ---- uint8 image views (ops.py:138-188): inference only, no autograd, torch.uint8 out ----

@@ -59,6 +59,69 @@ def latest_checkpoint(model_dir):
     return None if best is None else best[1]
 
 
+# ---- `evaluate_`: what the sweep of a trained model over its data set writes ------------------------------------------------------
+EVAL_SUMMARY = ("l1", "rel_l2", "jacobian_l1", "div_l1_g")      # mean and max over frames of each, per group and in total
+
+
+def _eval_mask(mask, device):
+    """``mask`` of ``evaluate_`` -> uint8 [(Z,)Y,X] on the device (None stays None)"""
+    if mask is None:
+        return None
+    m = torch.as_tensor(np.ascontiguousarray(mask) if isinstance(mask, np.ndarray) else mask)
+    return (m != 0).to(torch.uint8).contiguous().to(device)
+
+
+def _eval_arrays(metrics, x_range):
+    """the arrays of one ``eval/<group>.npz``: every quantity and derived mean of a host ``FieldMetrics``, one value per frame, in
+    normalised units; with ``x_range`` also ``<name>_denorm`` of the quantities that scale with the velocity unit, and ``x_range``"""
+    FM = ops.FieldMetrics
+    out = {k: getattr(metrics, k).numpy().copy() for k in FM.QUANTITIES + FM.DERIVED}
+    if x_range is not None:
+        for k in FM.LINEAR:
+            out[k + "_denorm"] = out[k] * float(x_range)
+        out["x_range"] = np.float64(x_range)
+    return out
+
+
+def _eval_stats(arrays):
+    """``{"frames", "<q>_mean", "<q>_max" for q in EVAL_SUMMARY, "worst_frame"}`` of per-frame arrays (the worst frame: the largest l1)"""
+    s = {"frames": int(len(arrays["l1"]))}
+    for q in EVAL_SUMMARY:
+        s[q + "_mean"], s[q + "_max"] = float(np.mean(arrays[q])), float(np.max(arrays[q]))
+    s["worst_frame"] = int(np.argmax(arrays["l1"]))
+    return s
+
+
+def _eval_write(model_dir, groups, x_range):
+    """Write ``<model_dir>/eval/<name>.npz`` for every ``(name, host FieldMetrics)`` of ``groups`` and ``eval/summary.txt`` (one line per
+    group, then ``total``: the statistics over the frames of all groups, its worst frame as ``<name>:<frame>``); return the summary
+    ``{"dir", "groups": {name: stats}, "total": stats}``."""
+    out_dir = os.path.join(model_dir, "eval")
+    os.makedirs(out_dir, exist_ok=True)
+    summary = {"dir": out_dir, "groups": {}}
+    every = {}
+    for name, metrics in groups:
+        arrays = _eval_arrays(metrics, x_range)
+        np.savez_compressed(os.path.join(out_dir, name + ".npz"), **arrays)
+        summary["groups"][name] = _eval_stats(arrays)
+        for q in EVAL_SUMMARY:
+            every.setdefault(q, []).append(arrays[q])
+    total = _eval_stats({q: np.concatenate(v) for q, v in every.items()})
+    worst, frame = None, total["worst_frame"]
+    for name, metrics in groups:          # the group that holds frame `frame` of the concatenation
+        if worst is None and frame < metrics.batch:
+            worst = "%s:%d" % (name, frame)
+        frame -= metrics.batch
+    total["worst_frame"] = worst
+    summary["total"] = total
+    cols = [q + s for q in EVAL_SUMMARY for s in ("_mean", "_max")]
+    with open(os.path.join(out_dir, "summary.txt"), "w") as f:
+        f.write("# %s frames %s worst_frame (normalised units; worst = largest l1)\n" % ("group", " ".join(cols)))
+        for name, st in list(summary["groups"].items()) + [("total", total)]:
+            f.write("%s %d %s %s\n" % (name, st["frames"], " ".join("%.9g" % st[c] for c in cols), st["worst_frame"]))
+    return summary
+
+
 def _detached(m):
     """The step's outputs without their autograd graph.  A graph-mode trainer never hands out tensors that keep the graph alive: the
     variables' AccumulateGrad nodes live as long as any graph that reaches them, remember the stream they were created on, and a later
@@ -621,6 +684,60 @@ class Trainer(object):
             np.savez_compressed(os.path.join(out_dir, "%d.npz" % i), x=G_)
         return out_dir
 
+    # ---- `evaluate_`: the sweep of `test_` measured against the data set (the reference leaves this to off-line scripts) ----------
+    def _pair_codes(self, batch_manager, pair, test_b_num):
+        """``(z_c, number of batches, batch size, parameter indices per frame)`` of one parameter pair: ``_sweep_codes`` for a
+        3-parameter set; a 2-parameter set (one index and the frame number, e.g. liquid3_vis) is swept the same way."""
+        y_num = [int(v) for v in batch_manager.y_num]
+        if len(pair) != len(y_num) - 1 or len(y_num) not in (2, 3) or any(not 0 <= int(p) < n for p, n in zip(pair, y_num)):
+            raise ValueError("evaluate_: %r is not a parameter index of a set with %s values per parameter" % (tuple(pair), y_num))
+        pair = tuple(int(p) for p in pair)
+        if len(y_num) == 3:
+            z_c, niter, test_b_num = self._sweep_codes(batch_manager, pair[0], pair[1], test_b_num, "evaluate_")
+        else:
+            test_b_num = test_b_num or self.config.test_batch_size
+            if y_num[-1] % test_b_num != 0:
+                raise ValueError("evaluate_: the number of frames (%d) must be a multiple of test_batch_size (%d)" % (y_num[-1], test_b_num))
+            niter = y_num[-1] // test_b_num
+            z_c = np.zeros((y_num[-1], self.c_num), np.float32)
+            z_c[:, 0] = pair[0] / float(y_num[0] - 1) * 2 - 1
+            z_c[:, -1] = np.linspace(-1, 1, num=y_num[-1])
+        return z_c, niter, test_b_num, [pair + (t,) for t in range(y_num[-1])]
+
+    def evaluate_(self, batch_manager, model_dir=None, pairs=None, test_b_num=None, denorm=True, mask=None):
+        """How well the model reproduces its data set.  For every ``(p1, p2)`` of ``pairs`` (default: every pair of the set; ``(p1,)``
+        for a 2-parameter set) sweep the frames as ``test_`` does, load the matching ground-truth frames the way training reads them
+        (``data.preprocess``: the same files, the same ``x_range`` normalisation), and run ``generate`` and ``ops.field_metrics`` batch
+        by batch.  Only the per-frame numbers stay on the device; they are read once per pair.  Writes
+          ``<model_dir>/eval/<p1>_<p2>.npz``   one array [frames] per quantity and derived mean of ``ops.FieldMetrics``, in normalised
+                                               units; with ``denorm`` also ``<name>_denorm`` = the value times ``x_range`` for the
+                                               quantities that scale with the velocity (``FieldMetrics.LINEAR``), and ``x_range``
+          ``<model_dir>/eval/summary.txt``     per pair and in total: frames, mean and max over frames of l1, rel_l2, jacobian_l1 and
+                                               div_l1_g, and the worst frame (largest l1)
+        and returns the summary as a dict ``{"dir", "groups": {"<p1>_<p2>": {...}}, "total": {...}}``.  ``mask``: cells to count,
+        [(Z,)Y,X], non-zero = counted.  Nothing is captured into a graph and nothing is trained."""
+        import itertools
+        from .data import preprocess
+        model_dir = model_dir or self.effective_model_dir()
+        y_num = [int(v) for v in batch_manager.y_num]
+        if pairs is None:
+            pairs = list(itertools.product(*(range(n) for n in y_num[:-1])))
+        mask = _eval_mask(mask, self.device)
+        groups = []
+        for pair in pairs:
+            pair = (pair,) if isinstance(pair, (int, np.integer)) else tuple(pair)
+            z_c, niter, b_num, p_list = self._pair_codes(batch_manager, pair, test_b_num)
+            paths = batch_manager.list_from_p(p_list)
+            parts = []
+            for b in range(niter):
+                rows = slice(b_num * b, b_num * (b + 1))
+                truth = np.stack([preprocess(p, batch_manager.data_type, batch_manager.x_range, batch_manager.y_range)[0] for p in paths[rows]])
+                x = torch.from_numpy(np.ascontiguousarray(truth, np.float32)).to(self.device)
+                g = self.generate(torch.from_numpy(z_c[rows]).to(self.device))
+                parts.append(ops.field_metrics(g.contiguous(), x, mask=mask))
+            groups.append(("_".join(str(p) for p in pair), ops.FieldMetrics.cat(parts).cpu()))      # the pair's one read
+        return _eval_write(model_dir, groups, batch_manager.x_range if denorm else None)
+
     # ---- `advect()` of the scene scripts (scene/smoke_pos_size.py:45-109): smoke carried through the generated velocities ------
     def advect_(self, batch_manager, model_dir=None, p1=10, p2=2, test_b_num=None, *, source, dt=None, order=2, clamp_mode=2, bnd=1,
                 obstacle=None):
@@ -1001,6 +1118,30 @@ class AETrainer(Trainer):
         """Positional arguments as ``Trainer.test_`` up to ``model_dir``; the batch size and ``code_path`` by keyword (the base class has
         ``p1, p2`` in between, so a positional batch size could not mean the same thing on both)."""
         return self.test_ae(batch_manager, model_dir, code_path=code_path, test_b_num=test_b_num)
+
+    def evaluate_(self, batch_manager, model_dir=None, test_b_num=None, denorm=True, mask=None):
+        """``Trainer.evaluate_`` for the auto-encoder: there is no code sweep, every frame of the data set is read in file order
+        (scene by scene, as ``batch_manager.batch_`` does), reconstructed (``reconstruct``) and measured against itself with
+        ``ops.field_metrics``.  Writes ``<model_dir>/eval/<scene>.npz`` per scene of ``num_frames`` frames (one group ``0`` when the
+        file count is no multiple of it) and ``eval/summary.txt``; same arrays, same summary.  The last batch may be short."""
+        from .data import preprocess
+        model_dir = model_dir or self.effective_model_dir()
+        b_num = int(test_b_num or self.config.test_batch_size)
+        if b_num < 1:
+            raise ValueError("evaluate_: test_b_num must be >= 1, got %r" % (test_b_num,))
+        mask = _eval_mask(mask, self.device)
+        paths = batch_manager.paths
+        parts = []
+        for i in range(0, len(paths), b_num):
+            truth = np.stack([preprocess(p, batch_manager.data_type, batch_manager.x_range, batch_manager.y_range)[0] for p in paths[i:i + b_num]])
+            x = torch.from_numpy(np.ascontiguousarray(truth, np.float32)).to(self.device)
+            parts.append(ops.field_metrics(self.reconstruct(x).contiguous(), x, mask=mask))
+        raw = ops.FieldMetrics.cat(parts).cpu().raw                          # the one read
+        nf = int(batch_manager.args.get("num_frames", 0))
+        if nf < 1 or len(paths) % nf != 0:
+            nf = len(paths)
+        groups = [(str(s), ops.FieldMetrics(raw[s * nf:(s + 1) * nf], parts[0].dim)) for s in range(len(paths) // nf)]
+        return _eval_write(model_dir, groups, batch_manager.x_range if denorm else None)
 
     def test_ae(self, batch_manager, model_dir=None, *, code_path=None, test_b_num=None):
         """``Trainer.test_ae``.  Without ``code_path`` (trainer.py:478-523): encode the whole dataset in file order
