@@ -91,3 +91,62 @@ class Guarded(object):
         got = host(self.payload()).reshape(self.shape)
         assert not np.isnan(got).any(), "%s: %d of %d elements were never written" % (what, int(np.isnan(got).sum()), got.size)
         return got
+
+
+# ---- the byte and integer siblings of Guarded (tests/test_gpu_particle_edges.py: marks, flags, keep bytes; keys, ranges, counts, the sort order)
+BYTE_FILL = 0xA5            # no mark, flags byte or keep byte of the tests takes this value
+WORD_FILL = 0x5A5A5A5A      # no key, range, count or row index of the tests takes this value (int64: the word twice)
+
+
+class _GuardedInts(object):
+    """``shape`` elements of ``dtype`` inside a larger allocation that holds ``fill`` everywhere: 256 bytes in front, the payload, 256 bytes
+    behind.  ``offset`` (elements) shifts the payload.  ``data`` fills the payload (an input operand); without it the payload holds the fill
+    too (an output).  The object owns the allocation: keep it in a named variable until the result has been read."""
+    dtype, fill = None, None
+
+    def __init__(self, shape, data=None, offset=0):
+        self.shape = tuple(shape)
+        self.n = int(np.prod(self.shape)) if self.shape else 1
+        size = torch.empty((), dtype=self.dtype).element_size()
+        guard = 4 * GUARD // size
+        self.lo = guard + int(offset)
+        self.bits = torch.full((self.lo + self.n + guard,), self.fill, dtype=self.dtype, device="cuda")
+        if data is not None:
+            self.bits[self.lo:self.lo + self.n] = torch.from_numpy(np.ascontiguousarray(data).reshape(-1)).to(self.dtype).cuda()
+        self.ptr = self.bits.data_ptr() + size * self.lo
+        assert self.bits.data_ptr() % 16 == 0 and self.ptr % 16 == (size * offset) % 16
+
+    def payload(self):
+        return self.bits[self.lo:self.lo + self.n]
+
+    def refill(self):
+        self.bits[self.lo:self.lo + self.n] = self.fill
+
+    def check_guards(self, what=""):
+        front, back = self.bits[:self.lo], self.bits[self.lo + self.n:]
+        assert bool((front == self.fill).all()), "%s: the guard in front of the buffer was written" % what
+        assert bool((back == self.fill).all()), "%s: the guard behind the buffer was written" % what
+
+    def raw(self, what=""):
+        """guards intact -> the payload as a host array, the fill still in it wherever nothing was written"""
+        self.check_guards(what)
+        return host(self.payload()).reshape(self.shape)
+
+    def get(self, what=""):
+        """guards intact, no fill left inside -> the payload as a host array"""
+        got = self.raw(what)
+        left = int((got == self.fill).sum())
+        assert left == 0, "%s: %d of %d elements were never written" % (what, left, got.size)
+        return got
+
+
+class GuardedBytes(_GuardedInts):
+    dtype, fill = torch.uint8, BYTE_FILL
+
+
+class GuardedInts(_GuardedInts):
+    dtype, fill = torch.int32, WORD_FILL
+
+
+class GuardedLongs(_GuardedInts):
+    dtype, fill = torch.int64, (WORD_FILL << 32) | WORD_FILL

@@ -35,6 +35,7 @@ def levelset_raw(pos_sorted, cell_start, shape, radius_factor=1.0, dtype=np.floa
     pacc = np.zeros((B, Z, Y, X, D), dtype)
     half, one, zero = dtype(0.5), dtype(1), dtype(0)
     if N > 0:
+        cell_start = pref.clamp_ranges(cell_start, B * N)                # the header's last sentence of the particle block
         for b in range(B):
             for k in range(Z):
                 for j in range(Y):
@@ -50,22 +51,22 @@ def levelset_raw(pos_sorted, cell_start, shape, radius_factor=1.0, dtype=np.floa
                         if not rows:
                             continue
                         q = sp[np.concatenate(rows)]
-                        d = c - q
-                        s2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
-                        if D == 3:
-                            s2 = s2 + d[:, 2] * d[:, 2]
-                        with np.errstate(invalid="ignore"):
-                            w = np.fmax(zero, one - s2 / r4).astype(dtype)
-                        wa = np.cumsum(w, dtype=dtype)[-1]                 # sequential sums from 0, in the order of the rows
-                        pa = np.array([np.cumsum((w * q[:, a]).astype(dtype), dtype=dtype)[-1] for a in range(D)], dtype)
-                        wacc[b, k, j, i] = wa
-                        pacc[b, k, j, i] = pa
-                        if wa > dtype(1e-6):
-                            e_ = c - pa / wa
-                            t = e_[0] * e_[0] + e_[1] * e_[1]
+                        with np.errstate(invalid="ignore", over="ignore"):
+                            d = c - q
+                            s2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
                             if D == 3:
-                                t = t + e_[2] * e_[2]
-                            phi[b, k, j, i] = np.sqrt(t) - R
+                                s2 = s2 + d[:, 2] * d[:, 2]
+                            w = np.fmax(zero, one - s2 / r4).astype(dtype)
+                            wa = np.cumsum(w, dtype=dtype)[-1]             # sequential sums from 0, in the order of the rows
+                            pa = np.array([np.cumsum((w * q[:, a]).astype(dtype), dtype=dtype)[-1] for a in range(D)], dtype)
+                            wacc[b, k, j, i] = wa
+                            pacc[b, k, j, i] = pa
+                            if wa > dtype(1e-6):
+                                e_ = c - pa / wa
+                                t = e_[0] * e_[0] + e_[1] * e_[1]
+                                if D == 3:
+                                    t = t + e_[2] * e_[2]
+                                phi[b, k, j, i] = np.sqrt(t) - R
     sh = (B,) + tuple(shape)
     if parts:
         return phi.reshape(sh), wacc.reshape(sh), pacc.reshape(sh + (D,))

@@ -62,6 +62,7 @@ def p2g(pos, pvel, cell_start, shape, dtype=np.float64, normalise=True):
     num = np.zeros((B, Z, Y, X, D), dtype)
     den = np.zeros((B, Z, Y, X, D), dtype)
     if N > 0:
+        cell_start = pref.clamp_ranges(cell_start, B * N)                # the header's last sentence of the liquid solver block
         wc = [pref.axis_weights(p[:, b] - half, ext[b], dtype) for b in range(D)]
         wf = [pref.axis_weights(p[:, b], ext[b], dtype) for b in range(D)]
         for e in range(B):
@@ -127,29 +128,35 @@ def both_interior(shape, bnd, a):
     return inter & np.roll(inter, 1, axis=nd - 1 - a)
 
 
+def extrapolate_layer(v, m, layer, bnd, dtype):
+    """ONE layer of df_mac_extrapolate* from (v, m) of ``dtype`` / uint8; returns new arrays"""
+    shape = v.shape[1:-1]
+    nd = len(shape)
+    vn, mn = v.copy(), m.copy()
+    for a in range(nd):
+        s = np.zeros(v.shape[:-1], dtype)
+        cnt = np.zeros(v.shape[:-1], np.int64)
+        for b in range(nd):
+            for sh in (1, -1):                                       # roll by +1 brings c - e_b
+                mk = np.roll(m[..., a], sh, axis=_ax(nd, b))
+                ok = (mk >= 1) & (mk <= layer)
+                with np.errstate(invalid="ignore"):
+                    s = np.where(ok, s + np.roll(v[..., a], sh, axis=_ax(nd, b)), s).astype(dtype)
+                cnt = cnt + ok
+        fill = (m[..., a] == 0) & both_interior(shape, bnd, a)[None] & (cnt > 0)
+        with np.errstate(all="ignore"):
+            vn[..., a] = np.where(fill, s / np.maximum(cnt, 1).astype(dtype), v[..., a])
+        mn[..., a] = np.where(fill, layer + 1, m[..., a])
+    return vn, mn
+
+
 def extrapolate(vel, mark, distance, bnd=1, dtype=np.float64):
     """``distance`` layers; returns (vel, marks)"""
     dtype = _type(dtype)
     v = np.asarray(vel).astype(dtype).copy()
     m = np.asarray(mark).astype(np.uint8).copy()
-    shape = v.shape[1:-1]
-    nd = len(shape)
     for layer in range(1, int(distance) + 1):
-        vn, mn = v.copy(), m.copy()
-        for a in range(nd):
-            s = np.zeros(v.shape[:-1], dtype)
-            cnt = np.zeros(v.shape[:-1], np.int64)
-            for b in range(nd):
-                for sh in (1, -1):                                       # roll by +1 brings c - e_b
-                    mk = np.roll(m[..., a], sh, axis=_ax(nd, b))
-                    ok = (mk >= 1) & (mk <= layer)
-                    s = np.where(ok, s + np.roll(v[..., a], sh, axis=_ax(nd, b)), s).astype(dtype)
-                    cnt = cnt + ok
-            fill = (m[..., a] == 0) & both_interior(shape, bnd, a)[None] & (cnt > 0)
-            with np.errstate(all="ignore"):
-                vn[..., a] = np.where(fill, s / np.maximum(cnt, 1).astype(dtype), v[..., a])
-            mn[..., a] = np.where(fill, layer + 1, m[..., a])
-        v, m = vn, mn
+        v, m = extrapolate_layer(v, m, layer, bnd, dtype)
     return v, m
 
 

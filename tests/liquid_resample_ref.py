@@ -34,8 +34,16 @@ def entries(entry_start, P):
     """[P]: the entry of every row, (the number of starts <= row) - 1; -1 for an unused row"""
     es = np.asarray(entry_start, np.int64)
     B = len(es) - 1
-    e = np.searchsorted(es, np.arange(P), side="right") - 1
-    return np.where(e == B, -1, e)
+    # the header's bisection ("ragged batches": whatever entry_start holds, the entry found lies in 0..B-1 or the row is unused): for
+    # non-decreasing starts it is searchsorted(es, row, "right") - 1; for anything else it is still what the kernels find
+    idx = np.arange(P, dtype=np.int64)
+    lo, hi = np.zeros(P, np.int64), np.full(P, B + 1, np.int64)
+    while (lo < hi).any():
+        act = lo < hi
+        mid = (lo + hi) >> 1
+        le = es[np.minimum(mid, B)] <= idx
+        lo, hi = np.where(act & le, mid + 1, lo), np.where(act & ~le, mid, hi)
+    return np.where(lo == B + 1, -1, lo - 1)
 
 
 def trace(pos, vel, entry_start, dt, bnd=1, vel_scale=1.0, dtype=np.float64):
@@ -103,24 +111,29 @@ def extrapolate_levelset(phi, distance=4, inside=True, dtype=np.float64, marks=F
     ph = np.asarray(phi).astype(dtype).copy()
     if distance <= 1:
         return (ph, np.zeros(ph.shape, np.uint8)) if marks else ph
+    m = extrapolate_marks(ph, inside)
+    for d in range(2, int(distance) + 1):
+        ph, m = extrapolate_layer(ph, m, d, inside, dtype)
+    return (ph, m) if marks else ph
+
+
+def extrapolate_layer(ph, m, layer, inside, dtype):
+    """ONE call of df_levelset_extrapolate_layer* on (phi of ``dtype``, marks uint8); returns new arrays"""
     shape = ph.shape[1:]
     nd = len(shape)
     inner = np.broadcast_to(interior_mask(shape, 1)[None], ph.shape)
-    m = extrapolate_marks(ph, inside)
     direction = dtype(-1) if inside else dtype(1)
-    for d in range(2, int(distance) + 1):
-        s = np.zeros(ph.shape, dtype)
-        cnt = np.zeros(ph.shape, np.int64)
-        for a, sh in DIRS[:2 * nd]:
-            ok = np.roll(m, sh, axis=_ax(nd, a)) == d
-            with np.errstate(invalid="ignore"):
-                s = np.where(ok, s + np.roll(ph, sh, axis=_ax(nd, a)), s).astype(dtype)
-            cnt = cnt + ok
-        fill = inner & (m == 0) & (cnt > 0)
-        with np.errstate(all="ignore"):
-            ph = np.where(fill, (s / np.maximum(cnt, 1).astype(dtype)).astype(dtype) + direction, ph).astype(dtype)
-        m = np.where(fill, d + 1, m).astype(np.uint8)
-    return (ph, m) if marks else ph
+    s = np.zeros(ph.shape, dtype)
+    cnt = np.zeros(ph.shape, np.int64)
+    for a, sh in DIRS[:2 * nd]:
+        ok = np.roll(m, sh, axis=_ax(nd, a)) == layer
+        with np.errstate(invalid="ignore"):
+            s = np.where(ok, s + np.roll(ph, sh, axis=_ax(nd, a)), s).astype(dtype)
+        cnt = cnt + ok
+    fill = inner & (m == 0) & (cnt > 0)
+    with np.errstate(all="ignore"):
+        ph = np.where(fill, (s / np.maximum(cnt, 1).astype(dtype)).astype(dtype) + direction, ph).astype(dtype)
+    return ph, np.where(fill, layer + 1, m).astype(np.uint8)
 
 
 # ---- the resampling -------------------------------------------------------------------------------------------------------------------------------
@@ -224,6 +237,78 @@ def resample(spos, spvel, cell_start, phi, liquid, vel, min_particles, max_parti
         seeded[dst:dst + ns] = True
     return dict(pos=pos_out, pvel=pvel_out, entry_start=new_start[::ncell].astype(np.int32), cell_start=new_start.astype(np.int32), keep=keep,
                 kept=kept, seeds=seeds, phiv=phiv, seeded=seeded, total=total)
+
+
+def resample_count(spos, cell_start, phi, flags, bnd, min_particles, max_particles, radius_factor=1.0, dtype=np.float64):
+    """df_resample_count* as ONE call states it, with the header's "every index read from device memory (cell_start, new_start, seeds,
+    entry_start) is clamped before use; a flags byte is believed only where the cell is interior by its index": every (entry, cell) walks
+    rows min(max(cell_start[c], 0), P) .. min(max(cell_start[c + 1], 0), P) - 1 against the phi of ITS entry.  Returns (keep [P] with
+    255 on the rows no cell holds, kept, seeds [B*ncell] int32)."""
+    dtype = _type(dtype)
+    p = np.asarray(spos).astype(dtype)
+    ph = np.asarray(phi).astype(dtype)
+    P, D = p.shape
+    B = ph.shape[0]
+    shape = ph.shape[1:]
+    ncell = int(np.prod(shape))
+    surface = surface_of(D, radius_factor, dtype)
+    cs = pref.clamp_ranges(cell_start, P)
+    keep = np.full(P, 255, np.uint8)
+    kept = np.zeros(B * ncell, np.int32)
+    for c in range(B * ncell):
+        k = 0
+        if cs[c + 1] > cs[c]:
+            phiv = phi_sample(ph[c // ncell], p[cs[c]:cs[c + 1]], dtype)
+            for r, v in zip(range(cs[c], cs[c + 1]), phiv):
+                drop = v > 0 or (k > max_particles and v <= surface)
+                keep[r] = 0 if drop else 1
+                k += 0 if drop else 1
+        kept[c] = k
+    liquid = ((np.asarray(flags).reshape(ph.shape) & ref.FLUID) != 0) & interior_mask(shape, bnd)[None]
+    with np.errstate(invalid="ignore"):
+        deep = liquid.reshape(-1) & (ph.reshape(-1) <= surface)
+    return keep, kept, np.where(deep & (kept < min_particles), min_particles - kept, 0).astype(np.int32)
+
+
+def resample_scatter(spos, spvel, cell_start, keep, seeds, new_start, vel, min_particles, seed=123, step=0, dtype=np.float64):
+    """df_resample_scatter* as ONE call states it, on a capacity of P = len(spos) rows, with the same clamps: rows from
+    min(max(new_start[c], 0), P), at most min(max(seeds[c], 0), min_particles) seeds, and no row >= P.  Returns (pos_out, pvel_out [P,D],
+    written [P] bool); rows not written hold NaN."""
+    dtype = _type(dtype)
+    p = np.asarray(spos).astype(dtype)
+    u = np.asarray(spvel).astype(dtype)
+    v = np.asarray(vel).astype(dtype)
+    P, D = p.shape
+    shape = v.shape[1:-1]
+    ncell = int(np.prod(shape))
+    X, Y = shape[-1], shape[-2]
+    cs = pref.clamp_ranges(cell_start, P)
+    ns_ = pref.clamp_ranges(new_start, P)
+    nseed = pref.clamp_ranges(seeds, min_particles)
+    pos_out = np.full((P, D), np.nan, dtype)
+    pvel_out = np.full((P, D), np.nan, dtype)
+    written = np.zeros(P, bool)
+    for c in range(v.shape[0] * ncell):
+        dst = int(ns_[c])
+        for r in range(cs[c], cs[c + 1]):
+            if keep[r] and dst < P:
+                pos_out[dst], pvel_out[dst], written[dst] = p[r], u[r], True
+                dst += 1
+        b, local = divmod(c, ncell)
+        cell = (local % X, (local // X) % Y, local // (X * Y))
+        for m in range(int(nseed[c])):
+            if dst >= P:
+                break
+            q = np.zeros(D, dtype)
+            for a in range(D):
+                h = mix4(seed & 0xFFFFFFFF, step & 0xFFFFFFFF, c, m * D + a)
+                lo, up = dtype(cell[a]), dtype(cell[a] + 1)
+                val = lo + dtype(h >> 8) * dtype(2.0 ** -24)
+                q[a] = val if val < up else np.nextafter(up, dtype(0))
+            pos_out[dst], written[dst] = q, True
+            pvel_out[dst] = pref.mac_sample(v[b:b + 1], q[None, None], 1.0, dtype)[0, 0]
+            dst += 1
+    return pos_out, pvel_out, written
 
 
 def check_invariants(r, phi, liquid, min_particles, max_particles, radius_factor=1.0):

@@ -148,37 +148,63 @@ def levelset_brute(pos, shape, radius_factor=1.0, dtype=np.float64):
     return phi
 
 
-def levelset_window(pos, shape, radius_factor=1.0, dtype=np.float64):
-    """phi as the header defines it: over a cell index of the fp32 positions, the particles of the cells within +-w of each cell."""
+def clamp_ranges(cell_start, total):
+    """min(max(cell_start, 0), total): the header's "out-of-range entries of order / cell_start select edge cells or edge particles, never
+    memory outside the arrays" (the last sentences of the particle and of the liquid solver blocks), as the kernels apply it to every
+    range end they read.  A pair with start > end is an empty range."""
+    return np.minimum(np.maximum(np.asarray(cell_start, np.int64), 0), int(total))
+
+
+def gather(pos, order):
+    """pos_sorted[r] = pos[order[r]], an order entry outside 0..n-1 taken as the nearest edge row (the same sentence of the header)"""
+    p = np.asarray(pos)
+    return p[np.clip(np.asarray(order, np.int64), 0, len(p) - 1)]
+
+
+def levelset_union_sorted(pos_sorted, cell_start, shape, B, radius_factor=1.0, dtype=np.float64):
+    """phi as the header defines it, of SORTED particles [B*N,D] and their ranges: the particles of the cells within +-w of each cell.
+    The header's level-set row writes `min` and does not say what a NaN distance does; here the minimum is C's fmin (IEEE minNum), the
+    reading the same block states for the trace's clamp ("a NaN becomes bnd"): a NaN distance is skipped and never wins.  Before, a
+    range that held one NaN position was dropped as a whole, finite particles included (ndarray.min() gave NaN and Python's
+    min(r, NaN) kept r); on finite positions nothing changes."""
     dtype = _type(dtype)
-    p32 = np.asarray(pos, np.float32)
-    B, N, D = p32.shape
+    sp = np.asarray(pos_sorted).astype(dtype)
+    D = sp.shape[-1]
     ncell = int(np.prod(shape))
-    order, cell_start = cell_ranges(cell_keys(p32, shape), B * ncell)
-    sp = p32.reshape(-1, D)[order].astype(dtype)
     radius = radius_of(D, radius_factor, dtype)
     w = window_of(radius_factor)
     Z, Y, X = ((1,) + tuple(shape))[-3:]
     phi = np.full((B, Z, Y, X), radius, dtype)
     half = dtype(0.5)
-    for b in range(B):
-        for k in range(Z):
-            for j in range(Y):
-                for i in range(X):
-                    c = np.array([dtype(i) + half, dtype(j) + half, dtype(k) + half][:D], dtype)
-                    r = radius
-                    for z in range(max(k - w, 0), min(k + w, Z - 1) + 1):
-                        for y in range(max(j - w, 0), min(j + w, Y - 1) + 1):
-                            key = b * ncell + (z * Y + y) * X
-                            s, e = cell_start[key + max(i - w, 0)], cell_start[key + min(i + w, X - 1) + 1]
-                            if e > s:
-                                d = c - sp[s:e]
-                                s2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
-                                if D == 3:
-                                    s2 = s2 + d[:, 2] * d[:, 2]
-                                r = min(r, (np.sqrt(s2) - radius).min())
-                    phi[b, k, j, i] = r
+    if len(sp):
+        cell_start = clamp_ranges(cell_start, len(sp))
+        for b in range(B):
+            for k in range(Z):
+                for j in range(Y):
+                    for i in range(X):
+                        c = np.array([dtype(i) + half, dtype(j) + half, dtype(k) + half][:D], dtype)
+                        r = radius
+                        for z in range(max(k - w, 0), min(k + w, Z - 1) + 1):
+                            for y in range(max(j - w, 0), min(j + w, Y - 1) + 1):
+                                key = b * ncell + (z * Y + y) * X
+                                s, e = cell_start[key + max(i - w, 0)], cell_start[key + min(i + w, X - 1) + 1]
+                                if e > s:
+                                    with np.errstate(invalid="ignore", over="ignore"):
+                                        d = c - sp[s:e]
+                                        s2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
+                                        if D == 3:
+                                            s2 = s2 + d[:, 2] * d[:, 2]
+                                        r = np.fmin(r, np.fmin.reduce(np.sqrt(s2) - radius))
+                        phi[b, k, j, i] = r
     return phi.reshape((B,) + tuple(shape))
+
+
+def levelset_window(pos, shape, radius_factor=1.0, dtype=np.float64):
+    """phi as the header defines it: over a cell index of the fp32 positions, the particles of the cells within +-w of each cell."""
+    p32 = np.asarray(pos, np.float32)
+    B, N, D = p32.shape
+    order, cell_start = cell_ranges(cell_keys(p32, shape), B * int(np.prod(shape)))
+    return levelset_union_sorted(p32.reshape(-1, D)[order], cell_start, shape, B, radius_factor, dtype)
 
 
 def sequence(pos0, vels, dt, bnd=1, vel_scale=1.0, radius_factor=1.0, dtype=np.float64):

@@ -6,7 +6,8 @@ NumPy's pairwise sum in the twin, so it is bounded through `accuracy` as tests/t
 margin over the twin's own distance from fp64.  Every parity test prints its figures before it asserts.
 
 Shapes: (7,9) and (5,7,6) are odd on every axis, (16,12) with bnd 2 has a two-cell band, B = 2 puts two entries into one launch whose
-particles differ."""
+particles differ.
+Loose alignments, guarded buffers, the block remap's remainder and the documented hostile inputs: tests/test_gpu_particle_edges.py."""
 import ctypes
 import os
 from types import SimpleNamespace

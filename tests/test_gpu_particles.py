@@ -4,7 +4,8 @@
 
 The twin's side of those figures (it needs no GPU; tests/test_particles_host.py prints it): single trace steps e32 0 (one particle
 resting on the clamp) .. 3.6e-06 cell units over the nine cases, 8-frame sequences e32 4.2e-06 (2-D) and 5.6e-06 (3-D) on the
-positions and 2.2e-06 / 4.3e-06 on the last level set, level sets on given positions e32 2.6e-08 .. 3.8e-07."""
+positions and 2.2e-06 / 4.3e-06 on the last level set, level sets on given positions e32 2.6e-08 .. 3.8e-07.
+Loose alignments, guarded buffers, the block remap's remainder and the documented hostile inputs: tests/test_gpu_particle_edges.py."""
 import ctypes
 import os
 from types import SimpleNamespace
