@@ -14,6 +14,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "deepfluids_hip.h"
 # the fused field metrics: a library and a header of their own (deepfluids_hip.h is frozen at DF_VERSION 207), bound the same way
 METRICS_LIB_PATH = os.path.join(_HERE, "csrc", "libdeepfluids_hip_metrics.so")
 METRICS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "deepfluids_hip_metrics.h")
+# the latent-space integrator (arch='nn'): likewise a library and a header of its own
+NN_LIB_PATH = os.path.join(_HERE, "csrc", "libdeepfluids_hip_nn.so")
+NN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "deepfluids_hip_nn.h")
 
 P, I64, I32, F32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
 U32 = ctypes.c_uint32
@@ -71,6 +74,8 @@ globals().update(CONSTANTS)
 # ... and of deepfluids_hip_metrics.h: df_field_metrics* and the DF_FM_* word indices of their output rows
 METRICS_SIGNATURES, METRICS_CONSTANTS = parse_header(_read_header(METRICS_HEADER_PATH))
 globals().update(METRICS_CONSTANTS)
+# ... and of deepfluids_hip_nn.h: df_nn_*
+NN_SIGNATURES, NN_CONSTANTS = parse_header(_read_header(NN_HEADER_PATH))
 
 
 class NoiseParams(ctypes.Structure):
@@ -81,6 +86,7 @@ class NoiseParams(ctypes.Structure):
 
 _lib = None
 _metrics_lib = None
+_nn_lib = None
 
 
 def declared_symbols():
@@ -136,7 +142,26 @@ def metrics_lib():
     return _metrics_lib
 
 
+def nn_lib():
+    """libdeepfluids_hip_nn.so; the main library is loaded first (it holds the error buffer the nn library writes to)"""
+    global _nn_lib
+    if _nn_lib is None:
+        lib()
+        if not os.path.exists(NN_LIB_PATH):
+            raise DeepFluidsHipError("libdeepfluids_hip_nn.so not found at %s -- `make -C deep_fluids_amd/csrc` builds it with the main "
+                                     "library. There is no CPU fallback." % NN_LIB_PATH)
+        handle = ctypes.CDLL(NN_LIB_PATH)
+        for name, (res, args) in NN_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype = res
+            fn.argtypes = args
+        _nn_lib = handle
+    return _nn_lib
+
+
 def _handle(name):
+    if name in NN_SIGNATURES:
+        return nn_lib()
     return metrics_lib() if name in METRICS_SIGNATURES else lib()
 
 
@@ -196,6 +221,6 @@ def query(name, *args):
         return _QUERY_CACHE[key]
     except KeyError:
         v = getattr(_handle(name), name)(*args)
-        if P not in (METRICS_SIGNATURES.get(name) or SIGNATURES[name])[1]:
+        if P not in (NN_SIGNATURES.get(name) or METRICS_SIGNATURES.get(name) or SIGNATURES[name])[1]:
             _QUERY_CACHE[key] = v
         return v

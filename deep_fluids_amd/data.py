@@ -224,6 +224,128 @@ class BatchManager(object):
         return x, y
 
 
+class NNBatchManager(object):
+    """The reference's ``data_nn.BatchManager`` (data_nn.py:12-160) for ``arch='nn'``: the codes ``<config.code_path>/code<z_num>.npz``
+    that ``AETrainer.test_ae`` wrote, normalised and cut into windows exactly as data_nn.py:62-126 does (``code_std``, ``out_std``,
+    ``p_std``; the first ``int(s * 0.95)`` scenes train, the rest test; windows of ``w_size`` consecutive rows per scene with the
+    reference's own index ``i * (f - 1) + j``, ``j < f - w_size``), all fp32.  ``p_num`` (``dof``) is ``num_dof`` of
+    ``<config.data_path>/args.txt``.
+
+    Batches are consecutive slices of ``batch_size`` rows and the remainder is kept, so the last batch of an epoch is short.  The
+    reference shuffles the batches through a ``tf.data`` buffer of 50, which cannot be restated: here the ORDER of an epoch's batches is
+    a permutation seeded by (``random_seed``, epoch, window or not) -- this project's own -- so ``seek(step)`` puts a resumed run where
+    the interrupted one was.  ``batch`` / ``test_batch`` return ``(x, y)`` tensors on ``device``; the test batches come in file order
+    and start over after ``init_test_it()`` or at their end."""
+
+    def __init__(self, config, device="cuda"):
+        self.root = config.data_path
+        self.args = {}
+        with open(os.path.join(self.root, "args.txt"), "r") as f:   # data_nn.py:18-25
+            for line in f:
+                if line.strip():
+                    arg, arg_value = line.rstrip("\n").split(": ")
+                    self.args[arg] = arg_value
+        self.is_3d = config.is_3d
+        self.w_num = int(config.w_size)
+        self.z_num = int(config.z_num)
+        self.dof = self.p_num = int(self.args["num_dof"])
+        self.code_path = os.path.join(config.code_path, "code%d.npz" % self.z_num)
+        self.batch_size = int(config.batch_size)
+        self.seed = int(config.random_seed)
+        self.device = torch.device(device)
+        with np.load(self.code_path) as code:                         # data_nn.py:62-69
+            x, y, p = (np.array(code[k], np.float32) for k in ("x", "y", "p"))
+            self.num_scenes, self.num_frames = int(code["s"]), int(code["f"])
+        if x.shape[1] != self.z_num or p.shape[1] != self.p_num or self.p_num > self.z_num:
+            raise ValueError("%s: codes of %d with %d parameters, the configuration says z_num %d and args.txt num_dof %d" % (
+                self.code_path, x.shape[1], p.shape[1], self.z_num, self.p_num))
+        if not 1 <= self.w_num < self.num_frames:
+            raise ValueError("w_size %d does not fit scenes of %d frames" % (self.w_num, self.num_frames))
+        self.code_std = np.std(x)                                     # data_nn.py:71-78
+        y -= x
+        self.out_std = np.std(y)
+        self.p_std = np.std(p)
+        x /= self.code_std
+        y /= self.out_std
+        p /= self.p_std
+        self.x_train = np.concatenate((x, p), axis=-1)
+        self.y_train = y
+        self.num_train_scenes = int(self.num_scenes * 0.95)           # data_nn.py:83-89
+        self.num_test_scenes = self.num_scenes - self.num_train_scenes
+        self.num_train = self.num_train_scenes * (self.num_frames - 1)
+        self.num_test = self.x_train.shape[0] - self.num_train
+        self.x_test, self.y_test = self.x_train[self.num_train:], self.y_train[self.num_train:]
+        self.x_train, self.y_train = self.x_train[:self.num_train], self.y_train[:self.num_train]
+        self.x_train_w, self.y_train_w = self._windows(self.x_train, self.y_train, self.num_train_scenes)      # data_nn.py:91-113
+        self.x_test_w, self.y_test_w = self._windows(self.x_test, self.y_test, self.num_test_scenes)
+        self.num_train_w, self.num_test_w = self.x_train_w.shape[0], self.x_test_w.shape[0]
+        self.num_samples = self.num_train + self.num_test
+        if self.num_train_w < 1 or self.num_test_w < 1:
+            raise ValueError("%s: %d scenes leave %d training and %d test windows; both must exist" % (
+                self.code_path, self.num_scenes, self.num_train_w, self.num_test_w))
+        self.train_steps = max(int(self.num_train / self.batch_size + 0.5), 1)          # data_nn.py:121-126
+        self.test_steps = max(int(self.num_test / self.batch_size + 0.5), 1)
+        self.train_w_steps = max(int(self.num_train_w / self.batch_size + 0.5), 1)
+        self.test_w_steps = max(int(self.num_test_w / self.batch_size + 0.5), 1)
+        self.epochs_per_step = 1 / self.train_w_steps
+        self.c_num = 0
+        self._count = {False: 0, True: 0}
+        self._test_at = {False: 0, True: 0}
+        self._dev = {}
+
+    def _windows(self, xs, ys, num_scenes):
+        n = num_scenes * (self.num_frames - self.w_num)
+        xw = np.zeros([n, self.w_num, xs.shape[1]], np.float32)
+        yw = np.zeros([n, self.w_num, ys.shape[1]], np.float32)
+        k = 0
+        for i in range(num_scenes):
+            for j in range(self.num_frames - self.w_num):
+                idx = i * (self.num_frames - 1) + j
+                xw[k], yw[k] = xs[idx:idx + self.w_num], ys[idx:idx + self.w_num]
+                k += 1
+        return xw, yw
+
+    def _on_device(self, name):
+        if name not in self._dev:
+            self._dev[name] = torch.from_numpy(np.ascontiguousarray(getattr(self, name), np.float32)).to(self.device)
+        return self._dev[name]
+
+    def _slice(self, tag, is_window, b):
+        sfx = "_w" if is_window else ""
+        x, y = self._on_device("x_%s%s" % (tag, sfx)), self._on_device("y_%s%s" % (tag, sfx))
+        return x[b * self.batch_size:(b + 1) * self.batch_size].contiguous(), y[b * self.batch_size:(b + 1) * self.batch_size].contiguous()
+
+    def num_batches(self, is_window=False, test=False):
+        """batches per pass over the set, the short last one included"""
+        n = {(False, False): self.num_train, (True, False): self.num_train_w, (False, True): self.num_test, (True, True): self.num_test_w}[
+            (bool(is_window), bool(test))]
+        return -(-n // self.batch_size)
+
+    def batch_index(self, count, is_window=False):
+        """which batch of the training set the ``count``-th call of ``batch`` returns"""
+        nb = self.num_batches(is_window)
+        order = np.random.RandomState([self.seed, count // nb, int(bool(is_window))]).permutation(nb)
+        return int(order[count % nb])
+
+    def seek(self, count, is_window=False):
+        self._count[bool(is_window)] = int(count)
+
+    def batch(self, is_window=False):
+        w = bool(is_window)
+        b = self.batch_index(self._count[w], w)
+        self._count[w] += 1
+        return self._slice("train", w, b)
+
+    def init_test_it(self):
+        self._test_at = {False: 0, True: 0}
+
+    def test_batch(self, is_window=False):
+        w = bool(is_window)
+        b = self._test_at[w]
+        self._test_at[w] = (b + 1) % self.num_batches(w, test=True)
+        return self._slice("test", w, b)
+
+
 def _curl_np3(x):
     """Host NumPy curl of x [Z,Y,X,3] -- the ``c`` of ``jacobian_np3`` (ops.py:344-374): forward differences with the last difference
     replicated, c = (dwdy - dvdz, dudz - dwdx, dvdx - dudy).  On the host because ``random_list`` runs once, on ``b_num`` samples."""

@@ -9,10 +9,10 @@ import numpy as np
 from . import ops as ops_mod
 from .ops import *          # noqa: F401,F403  (the reference does `from ops import *`, model.py:3)
 from .ops import (variable_scope, get_variables, add, lrelu, linear, reshape, conv2d, conv3d, upscale, upscale3, concat,
-                  sigmoid, get_conv_shape)
+                  sigmoid, get_conv_shape, batch_norm_variables, nn_bn_elu_dropout, nn_mask_state)
 
 __all__ = ["GeneratorBE", "GeneratorBE3", "EncoderBE", "EncoderBE3", "AE", "AE3", "DiscriminatorPatch",
-           "DiscriminatorPatch3"]
+           "DiscriminatorPatch3", "NN"]
 
 
 def _generator(z, filters, output_shape, name, num_conv, conv_k, last_k, repeat, skip_concat, act, reuse, is_3d):
@@ -178,3 +178,27 @@ def DiscriminatorPatch(x, filters, name="D", train=True, reuse=False):
 def DiscriminatorPatch3(x, filters, name="D", train=True, reuse=False):
     """model.py:105-116."""
     return _discriminator(x, filters, name, reuse, True)
+
+
+def NN(x, filters, onum, name="NN", keep_prob=0.1, train=True, reuse=False):
+    """model.py:218-224: linear(2 filters) -> BN -> ELU -> dropout -> linear(filters) -> BN -> ELU -> dropout -> linear(onum); returns
+    ``(out, variables)``.  Variables under slim's default names: ``NN/fully_connected[_1|_2]/{weights,biases}`` and
+    ``NN/BatchNorm[_1]/{beta,gamma,moving_mean,moving_variance}``.
+
+    ``keep_prob`` is the reference's ``dropout=0.1``: it is passed to ``slim.dropout`` as its second positional argument, which is the
+    probability to KEEP -- the reference keeps 10 % of the activations and scales them by 10, and so does this.  (The activation is
+    always ELU, the only one the reference's trainer uses.)  ``train=True`` normalises with the batch statistics (biased variance)
+    and moves the averages in place, ``moving = 0.9 moving + 0.1 batch``; the moving variance takes the Bessel-corrected batch
+    variance, factor B / max(B - 1, 1) -- restated from memory of TF 1.15's fused batch norm, UNPINNED: no TensorFlow was at hand to
+    capture a golden from.  The dropout mask is a hash of ``ops.nn_mask_state()`` (seed, step, window), the layer and the element's
+    row and column: this project's own, never stored, recomputed by the backward pass."""
+    st = nn_mask_state()
+    with variable_scope(name, reuse=reuse) as vs:
+        for layer, n in enumerate((filters * 2, filters)):
+            x = linear(x, n)
+            beta, gamma, mm, mv = batch_norm_variables(n, device=x.device)
+            x = nn_bn_elu_dropout(x, gamma, beta, mm, mv, train=train, keep_prob=keep_prob, seed=st["seed"], step=st["step"],
+                                  window=st["window"], layer=layer)
+        out = linear(x, onum)
+    variables = get_variables(vs)
+    return out, variables

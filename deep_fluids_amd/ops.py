@@ -35,6 +35,7 @@ __all__ = [
     "open_sides", "SphereSource",
     "advect_particles", "particle_cells", "particle_levelset", "particle_levelset_averaged", "liquid_sequence", "seed_particles", "box_levelset", "sphere_levelset",
     "pack_particles", "unpack_particles", "extrapolate_levelset", "resample_particles", "Resample",
+    "nn_bn_elu_dropout", "nn_window_advance", "nn_window_stack", "nn_mse", "nn_rollout", "nn_mask_state", "batch_norm_variables",
     "variable_scope", "get_variables", "get_variable", "reset_variables", "set_random_seed", "all_variables",
 ]
 
@@ -148,6 +149,8 @@ def get_variable(name, shape, init="xavier", device=None):
         rf = int(np.prod(shape[:-2])) if len(shape) > 2 else 1
         lim = math.sqrt(6.0 / (rf * shape[-2] + rf * shape[-1]))
         host = _RNG.uniform(-lim, lim, size=shape).astype(np.float32)
+    elif init == "ones":
+        host = np.ones(shape, np.float32)
     else:
         host = np.zeros(shape, np.float32)
     v = torch.from_numpy(host).to(device or _DEFAULT_DEVICE).requires_grad_(True)
@@ -3929,3 +3932,190 @@ def jacobian_np3(x):
     """ops.py:344-374."""
     j, c = jacobian3(_np_in(x))
     return j.cpu().numpy(), c.cpu().numpy()
+
+
+# --------------------------------------------------------------------------------------------------
+# latent-space integrator, arch='nn' (model.py:218-224, trainer.py:586-747): libdeepfluids_hip_nn.so, include/deepfluids_hip_nn.h
+# --------------------------------------------------------------------------------------------------
+NN_BN_EPSILON = 1e-5        # ops.py:26 batch_norm(epsilon=1e-5, momentum=0.9)
+NN_BN_DECAY = 0.9
+
+# what the dropout mask of a training-mode `NN` application is a hash of, besides the element's row and column and the layer: the
+# trainer's seed, the global step and the index of the application inside the window (see `nn_mask_state`)
+_NN_MASK = {"seed": 123, "step": 0, "window": 0}
+
+
+def nn_mask_state(seed=None, step=None, window=None):
+    """Set (the arguments given) and return the mask state ``{"seed", "step", "window"}`` the next training-mode ``NN`` reads.  The
+    reference's masks come from TensorFlow's generator, which cannot be restated; this hash is this project's own."""
+    for k, v in (("seed", seed), ("step", step), ("window", window)):
+        if v is not None:
+            _NN_MASK[k] = int(v) & 0xFFFFFFFF
+    return dict(_NN_MASK)
+
+
+def batch_norm_variables(n, name=None, device=None):
+    """The variables of ``slim.batch_norm(scale=True)`` under the current scope, slim's names and creation order:
+    ``<BatchNorm>/beta`` (0), ``gamma`` (1), ``moving_mean`` (0), ``moving_variance`` (1)."""
+    lname = _layer_name(name, "BatchNorm")
+    return (get_variable(lname + "/beta", (int(n),), "zeros", device), get_variable(lname + "/gamma", (int(n),), "ones", device),
+            get_variable(lname + "/moving_mean", (int(n),), "zeros", device), get_variable(lname + "/moving_variance", (int(n),), "ones", device))
+
+
+class _NNBlockTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, moving_mean, moving_var, keep_prob, seed, step, window, layer):
+        x = _prep(x, "x"); gamma = _prep(gamma, "gamma"); beta = _prep(beta, "beta")
+        B, N = x.shape
+        act, out = torch.empty_like(x), torch.empty_like(x)
+        mean, rstd = _empty((N,), x), _empty((N,), x)
+        call("df_nn_bn_elu_dropout_fwd", _ptr(x), _ptr(gamma), _ptr(beta), _ptr(moving_mean), _ptr(moving_var), _ptr(act), _ptr(out),
+             _ptr(mean), _ptr(rstd), B, N, NN_BN_EPSILON, NN_BN_DECAY, float(keep_prob), seed, step, window, layer, _stream())
+        ctx.save_for_backward(x, act, gamma, mean, rstd)
+        ctx.mask = (float(keep_prob), seed, step, window, layer)
+        ctx.bptr = beta.data_ptr()
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, act, gamma, mean, rstd = ctx.saved_tensors
+        gout = _prep(gout, "grad")
+        B, N = x.shape
+        gx = torch.empty_like(x)
+        gg, gb = _empty((N,), x), _empty((N,), x)
+        call("df_nn_bn_elu_dropout_bwd", _ptr(x), _ptr(act), _ptr(gout), _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(gx), _ptr(gg), _ptr(gb),
+             B, N, *(ctx.mask + (_stream(),)))
+        return (gx, gg, gb) + (None,) * 7
+
+
+def nn_bn_elu_dropout(x, gamma, beta, moving_mean, moving_var, train=True, keep_prob=0.1, seed=0, step=0, window=0, layer=0):
+    """``slim.dropout(slim.batch_norm(x, activation_fn=elu), keep_prob, is_training=train)`` on [B,N] as one launch (two with its
+    backward).  ``train=True``: batch statistics, ``moving_mean`` / ``moving_var`` updated IN PLACE (``updates_collections=None``), the
+    hash mask of (seed, step, window, layer, row, column) kept with probability ``keep_prob`` and scaled by 1 / keep_prob.
+    ``train=False``: moving statistics, no mask, no gradient."""
+    mm, mv = _prep(moving_mean.detach(), "moving_mean"), _prep(moving_var.detach(), "moving_var")
+    if train:
+        u32 = [int(v) & 0xFFFFFFFF for v in (seed, step, window, layer)]
+        return _NNBlockTrain.apply(x, gamma, beta, mm, mv, keep_prob, *u32)
+    x = _prep(x.detach(), "x"); gamma = _prep(gamma.detach(), "gamma"); beta = _prep(beta.detach(), "beta")
+    B, N = x.shape
+    out = torch.empty_like(x)
+    call("df_nn_bn_elu_infer", _ptr(x), _ptr(gamma), _ptr(beta), _ptr(mm), _ptr(mv), _ptr(out), B, N, NN_BN_EPSILON, _stream())
+    return out
+
+
+class _NNWindowAdvance(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, xw, i, ratio):
+        x = _prep(x, "x"); y = _prep(y, "y"); xw = _prep(xw, "xw")
+        B, K = x.shape
+        Z = y.shape[1]
+        if xw.dim() != 3 or xw.shape[0] != B or xw.shape[2] != K or y.shape[0] != B or Z >= K:
+            raise ValueError("nn_window_advance: x %s, y %s, xw %s do not belong together" % (tuple(x.shape), tuple(y.shape), tuple(xw.shape)))
+        xn = torch.empty_like(x)
+        call("df_nn_window_advance_fwd", _ptr(x), _ptr(y), _ptr(xw), _ptr(xn), B, xw.shape[1], Z, K - Z, int(i), float(ratio), _stream())
+        ctx.dims = (B, Z, K - Z, float(ratio))
+        return xn
+
+    @staticmethod
+    def backward(ctx, gxn):
+        gxn = _prep(gxn, "grad")
+        B, Z, P, ratio = ctx.dims
+        gx = torch.empty_like(gxn) if ctx.needs_input_grad[0] else None
+        gy = _empty((B, Z), gxn) if ctx.needs_input_grad[1] else None
+        call("df_nn_window_advance_bwd", _ptr(gxn), _ptr(gx), _ptr(gy), B, Z, P, ratio, _stream())
+        return gx, gy, None, None, None
+
+
+def nn_window_advance(x, y, xw, i, ratio):
+    """trainer.py:608-614: ``concat(x[:, :-p] + y * ratio, xw[:, i+1, -p:])`` with ratio = out_std / code_std; x [B,z+p], y [B,z],
+    xw [B,w,z+p].  The gradient flows to ``x[:, :-p]`` and to ``y``."""
+    return _NNWindowAdvance.apply(x, y, xw, i, ratio)
+
+
+class _NNWindowStack(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, *ys):
+        ys = [_prep(y, "y") for y in ys]
+        B, Z = ys[0].shape
+        W = len(ys)
+        out = _empty((B, W, Z), ys[0])
+        for i, y in enumerate(ys):
+            if tuple(y.shape) != (B, Z):
+                raise ValueError("nn_window_stack: entry %d is %s, entry 0 is %s" % (i, tuple(y.shape), (B, Z)))
+            call("df_nn_rows_copy", _ptr(y), Z, out.data_ptr() + 4 * i * Z, W * Z, B, Z, _stream())
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        g = _prep(g, "grad")
+        B, W, Z = g.shape
+        gys = []
+        for i in range(W):
+            gy = None
+            if ctx.needs_input_grad[i]:
+                gy = _empty((B, Z), g)
+                call("df_nn_rows_copy", g.data_ptr() + 4 * i * Z, W * Z, _ptr(gy), Z, B, Z, _stream())
+            gys.append(gy)
+        return tuple(gys)
+
+
+def nn_window_stack(ys):
+    """The window's predictions, w tensors [B,z], as yw_ [B,w,z] (``tf.concat`` of the expanded entries, trainer.py:597-606)."""
+    return _NNWindowStack.apply(*ys)
+
+
+class _NNMse(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        a = _prep(a, "a"); b = _prep(b, "b")
+        if a.shape != b.shape:
+            raise ValueError("nn_mse: shapes differ %s vs %s" % (tuple(a.shape), tuple(b.shape)))
+        n = a.numel()
+        out = _empty((), a)
+        nbytes = query("df_nn_mse_workspace_bytes", n)
+        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=a.device)
+        call("df_nn_mse_fwd", _ptr(a), _ptr(b), n, _ptr(out), _ptr(ws), nbytes, _stream())
+        ctx.save_for_backward(a, b)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        a, b = ctx.saved_tensors
+        gout = _prep(gout, "grad")
+        ga = torch.empty_like(a)
+        call("df_nn_mse_bwd", _ptr(a), _ptr(b), _ptr(gout), _ptr(ga), a.numel(), _stream())
+        return ga, None
+
+
+def nn_mse(pred, target):
+    """``tf.losses.mean_squared_error(target, pred)`` (trainer.py:630): the mean over every element, summed in the fixed order of
+    deepfluids_hip_nn.h; the gradient 2 (pred - target) / count goes to ``pred``."""
+    return _NNMse.apply(pred, target.detach())
+
+
+def nn_rollout(x_test, y_test, variables, num_scenes, num_frames, z_num, code_std, out_std):
+    """``test_nn`` (trainer.py:698-747) for every test scene in ONE launch: ``z_out`` [num_scenes, num_frames, z_num].  ``x_test``
+    [num_scenes (num_frames - 1), z_num + p_num] and ``y_test`` [.., z_num] are the normalised rows of the batch manager; ``variables``
+    maps the slim names below the network's scope (``fully_connected/weights`` ... ``BatchNorm_1/moving_variance``) to tensors."""
+    x_test = _prep(x_test, "x_test"); y_test = _prep(y_test, "y_test")
+    S, F, Z = int(num_scenes), int(num_frames), int(z_num)
+    K0 = x_test.shape[1]
+    if tuple(x_test.shape) != (S * (F - 1), K0) or tuple(y_test.shape) != (S * (F - 1), Z) or K0 <= Z:
+        raise ValueError("nn_rollout: x_test %s / y_test %s are not %d scenes of %d frames with a code of %d" % (
+            tuple(x_test.shape), tuple(y_test.shape), S, F, Z))
+    v = {k: _prep(t.detach(), k) for k, t in variables.items()}
+    names = ["fully_connected/weights", "fully_connected/biases", "BatchNorm/gamma", "BatchNorm/beta", "BatchNorm/moving_mean",
+             "BatchNorm/moving_variance", "fully_connected_1/weights", "fully_connected_1/biases", "BatchNorm_1/gamma", "BatchNorm_1/beta",
+             "BatchNorm_1/moving_mean", "BatchNorm_1/moving_variance", "fully_connected_2/weights", "fully_connected_2/biases"]
+    w1, w2, w3 = v[names[0]], v[names[6]], v[names[12]]
+    N1, N2 = w1.shape[1], w2.shape[1]
+    if tuple(w1.shape) != (K0, N1) or tuple(w2.shape) != (N1, N2) or tuple(w3.shape) != (N2, Z):
+        raise ValueError("nn_rollout: weights %s, %s, %s do not chain from %d to %d" % (tuple(w1.shape), tuple(w2.shape), tuple(w3.shape), K0, Z))
+    for k, n in zip(names, [None, N1, N1, N1, N1, N1, None, N2, N2, N2, N2, N2, None, Z]):
+        if n is not None and tuple(v[k].shape) != (n,):
+            raise ValueError("nn_rollout: %s is %s, expected (%d,)" % (k, tuple(v[k].shape), n))
+    z_out = _empty((S, F, Z), x_test)
+    call("df_nn_rollout", _ptr(x_test), _ptr(y_test), *([_ptr(v[k]) for k in names] + [_ptr(z_out), S, F, Z, K0 - Z, N1, N2, NN_BN_EPSILON,
+                                                                                        float(code_std), float(out_std), _stream()]))
+    return z_out

@@ -26,7 +26,7 @@ import torch
 from . import ops
 from . import _lib as _lib_mod
 from .ops import curl, curl3, jacobian, jacobian3, l1_mean, mse_mean, get_conv_shape, _ptr, _stream, call
-from .model import GeneratorBE, GeneratorBE3, AE, AE3, DiscriminatorPatch, DiscriminatorPatch3
+from .model import GeneratorBE, GeneratorBE3, AE, AE3, DiscriminatorPatch, DiscriminatorPatch3, NN
 from .ops import concat, kl_bernoulli
 from .dist import GradSync, broadcast_trainer_state
 from .util import save_image, save_obj, vort_image
@@ -40,7 +40,8 @@ def default_config(**over):
              start_step=0, random_seed=123, num_samples=21000, c_num=3, use_curl3_alias=True,
              z_num=16, use_sparse=False, sparsity=0.01, w4=1.0, w5=1.0, p_num=2, x_channels=None, w3=0.005,
              log_step=500, test_step=1000, test_batch_size=100, model_dir=None, load_path="", code_path="", save_sec=3600,   # config.py:62-68
-             fused_tail=True, graph=False, direct_grads=True, sample_images=False)
+             fused_tail=True, graph=False, direct_grads=True, sample_images=False,
+             w_size=5)                                                  # config.py: --w_size (arch='nn')
     c.update(over)
     return SimpleNamespace(**c)
 
@@ -1326,3 +1327,148 @@ class GANTrainer(Trainer):
         s = self.grad_sync.reduce_all()
         self.grad_sync_d.reduce_all()
         return s
+
+
+class NNTrainer(Trainer):
+    """arch='nn': the latent-space integrator of ``build_model_nn`` / ``train_nn`` / ``test_nn`` (trainer.py:586-747).  ``NN`` steps the
+    auto-encoder's code forward; it is trained on windows of ``w_size`` consecutive codes, the prediction of one application fed into the
+    next (``ops.nn_window_advance``), with ``loss = mean((yw - yw_)**2)`` over [B, w_size, z_num] as the only term, and TF1 Adam (the
+    reference refuses any other optimizer, and so does this).  Each of the ``w_size`` training-mode applications has its own batch
+    statistics, its own dropout mask -- a hash of (``random_seed``, global step, application, layer, row, column), this project's own --
+    and its own in-place update of the moving averages.
+
+    ``batch_manager`` (a ``data.NNBatchManager``, or anything with ``code_std``, ``out_std``, ``p_num`` and ``epochs_per_step``) supplies
+    the scale ``out_std / code_std`` of the window step.  The moving averages live in the parameter slab next to the trainable
+    variables (their gradient is always zero, which TF1 Adam turns into an update of exactly zero), so ``save`` / ``load`` hold them
+    and a resumed run equals the uninterrupted one bit for bit.  The linear layers are ``df_linear_fwd`` / ``df_linear_bwd``; an MFMA
+    GEMM for these shapes, graph capture and data parallelism are left out."""
+    _direct_grads_ok = False          # every variable receives w_size gradients per step
+
+    def __init__(self, config, batch_manager, device="cuda", name="NN", keep_prob=0.1):
+        if config.optimizer != "adam":                                  # trainer.py:621-624
+            raise Exception("[!] Caution! Paper didn't use {} opimizer other than Adam".format(config.optimizer))
+        if bool(getattr(config, "graph", False)):
+            raise NotImplementedError("NNTrainer: graph=True is not implemented; the step runs eagerly, launch by launch")
+        self.z_num = int(config.z_num)
+        self.p_num = int(batch_manager.p_num)
+        self.w_num = int(config.w_size)
+        self.keep_prob = float(keep_prob)
+        self.code_std, self.out_std = float(batch_manager.code_std), float(batch_manager.out_std)
+        self.ratio = float(np.float32(batch_manager.out_std) / np.float32(batch_manager.code_std))
+        self.seed = int(config.random_seed)
+        super(NNTrainer, self).__init__(config, device, name)
+        self.max_step = int(config.max_epoch // batch_manager.epochs_per_step)      # trainer.py:67 with data_nn.py:126
+
+    def _create_variables(self):
+        x = torch.zeros((1, self.z_num + self.p_num), dtype=torch.float32, device=self.device)
+        with torch.no_grad():      # one inference-mode pass creates NN/fully_connected*/... and NN/BatchNorm*/... (nothing is updated)
+            NN(x, self.filters, self.z_num, name=self.name, keep_prob=self.keep_prob, train=False)
+
+    def enable_data_parallel(self, group=None, profile=False, force=False):
+        raise NotImplementedError("NNTrainer: data parallelism is not implemented; batch norm would need its statistics exchanged")
+
+    def _window(self, xw, yw, train):
+        """build_model_nn's loop (trainer.py:590-617): -> (yw_ [B,w,z], loss)"""
+        xw, yw = ops._prep(xw, "xw"), ops._prep(yw, "yw")
+        B, W, K0 = xw.shape
+        if W != self.w_num or K0 != self.z_num + self.p_num or tuple(yw.shape) != (B, W, self.z_num):
+            raise ValueError("NNTrainer: xw %s / yw %s are not windows of %d codes of %d + %d" % (
+                tuple(xw.shape), tuple(yw.shape), self.w_num, self.z_num, self.p_num))
+        x_ = torch.empty((B, K0), dtype=torch.float32, device=xw.device)
+        call("df_nn_rows_copy", _ptr(xw), W * K0, _ptr(x_), K0, B, K0, _stream())          # xw[:, 0, :]
+        ys = []
+        for i in range(W):
+            ops.nn_mask_state(seed=self.seed, step=self.step, window=i)
+            y_, _ = NN(x_, self.filters, self.z_num, name=self.name, keep_prob=self.keep_prob, train=train, reuse=True)
+            ys.append(y_)
+            if i < W - 1:
+                x_ = ops.nn_window_advance(x_, y_, xw, i, self.ratio)
+        yw_ = ops.nn_window_stack(ys)
+        return yw_, ops.nn_mse(yw_, yw)
+
+    def build_model(self, xw, yw):
+        yw_, loss = self._window(xw, yw, True)
+        return SimpleNamespace(yw_=yw_, loss=loss, loss_train_w=loss, g_loss=loss)
+
+    def predict(self, x):
+        """``NN(x, train=False)``: one inference-mode step on [B, z_num + p_num]"""
+        with torch.no_grad():
+            return NN(ops._prep(x, "x"), self.filters, self.z_num, name=self.name, keep_prob=self.keep_prob, train=False, reuse=True)[0]
+
+    def test_losses(self, batch_manager):
+        """``l_test`` and ``l_test_w`` of train_nn (trainer.py:666-677): the single-step and the windowed MSE in evaluation mode (moving
+        statistics, no dropout), each the mean over ``test_steps`` / ``test_w_steps`` test batches"""
+        batch_manager.init_test_it()
+        with torch.no_grad():
+            tl = []
+            for _ in range(batch_manager.test_steps):
+                x, y = batch_manager.test_batch()
+                tl.append(ops.nn_mse(self.predict(x), y))
+            tw = []
+            for _ in range(batch_manager.test_w_steps):
+                xw, yw = batch_manager.test_batch(is_window=True)
+                tw.append(self._window(xw, yw, False)[1])
+            return float(torch.stack(tl).double().mean()), float(torch.stack(tw).double().mean())
+
+    def _scalars(self, m, ep):
+        return {"loss/total_loss": float(m.loss), "loss/loss_train_w": float(m.loss), "misc/lr": self.g_lr, "misc/epoch": ep}
+
+    def train(self, batch_manager, max_step=None, model_dir=None, log_step=None):
+        """``train_nn`` (trainer.py:657-696): steps ``self.step .. max_step-1`` on windowed batches; every ``log_step`` steps (and at the
+        last) the test losses are evaluated and one JSON line goes to ``<model_dir>/scalars.jsonl``; NaN guard; the last checkpoint at
+        the end.  (``loss_train``, the single-step loss the reference only logs, is not evaluated.)  Returns the logged records."""
+        model_dir = model_dir or self.effective_model_dir()
+        log_step = log_step or self.config.log_step
+        max_step = self.max_step if max_step is None else max_step
+        if model_dir:
+            os.makedirs(model_dir, exist_ok=True)
+            with open(os.path.join(model_dir, "params.json"), "w") as fp:
+                json.dump({k: v for k, v in sorted(vars(self.config).items())}, fp, indent=4, sort_keys=True, default=str)
+        if hasattr(batch_manager, "seek"):
+            batch_manager.seek(self.step, is_window=True)
+        records, ep, t0 = [], 0, time.time()
+        for step in range(self.step, max_step):
+            xw, yw = batch_manager.batch(is_window=True)
+            m = self.train_step(xw, yw)
+            if step % log_step == 0 or step == max_step - 1:
+                ep += 1
+                test_loss, test_loss_w = self.test_losses(batch_manager)
+                rec = self._scalars(m, ep)
+                assert not np.isnan(rec["loss/total_loss"]), "Model diverged with loss = NaN"      # trainer.py:682
+                rec.update({"loss/loss_test": test_loss, "loss/loss_test_w": test_loss_w, "step": step, "wall_s": time.time() - t0})
+                records.append(rec)
+                print("[{}/{}/ep{:.2f}] Loss: {:.6f}/{:.6f}".format(step, max_step, ep, rec["loss/total_loss"], test_loss))
+                if model_dir:
+                    with open(os.path.join(model_dir, "scalars.jsonl"), "a") as f:
+                        f.write(json.dumps(rec) + "\n")
+        if model_dir:
+            self.save(os.path.join(model_dir, "model.ckpt-%d.npz" % self.step))
+        return records
+
+    def rollout(self, batch_manager):
+        """``z_out`` [num_test_scenes, num_frames, z_num] of ``test_nn`` on the device: every scene, every frame, one launch"""
+        prefix = self.name + "/"
+        variables = {k[len(prefix):]: v for k, v in ops.all_variables().items() if k.startswith(prefix)}
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(self.device)
+        return ops.nn_rollout(dev(batch_manager.x_test), dev(batch_manager.y_test), variables, batch_manager.num_test_scenes,
+                              batch_manager.num_frames, self.z_num, np.float32(batch_manager.code_std), np.float32(batch_manager.out_std))
+
+    def test_nn(self, batch_manager, model_dir=None):
+        """``test_nn`` (trainer.py:698-747): roll every test scene out from its first code, ``num_frames - 1`` steps, the supervised
+        parameters (the last ``p_num`` entries of the code) overwritten with the ground truth's at every step, and write
+        ``<model_dir>/code_out.npz`` with ``z_out`` and ``z_gt`` [num_test_scenes, num_frames, z_num] -- what
+        ``AETrainer.test_ae(code_path=<model_dir>)`` decodes.  Returns the path."""
+        model_dir = model_dir or self.effective_model_dir()
+        os.makedirs(model_dir, exist_ok=True)
+        z_out = self.rollout(batch_manager).cpu().numpy()
+        S, F, z = batch_manager.num_test_scenes, batch_manager.num_frames, self.z_num
+        cs, os_ = np.float32(batch_manager.code_std), np.float32(batch_manager.out_std)
+        x, y = np.asarray(batch_manager.x_test, np.float32), np.asarray(batch_manager.y_test, np.float32)
+        z_gt = np.zeros((S, F, z), np.float32)
+        for s in range(S):                                                # trainer.py:710-715
+            r0 = s * (F - 1)
+            z_gt[s, 0] = x[r0, :z] * cs
+            z_gt[s, 1:] = y[r0:r0 + F - 1] * os_ + x[r0:r0 + F - 1, :z] * cs
+        path = os.path.join(model_dir, "code_out.npz")
+        np.savez_compressed(path, z_out=z_out, z_gt=z_gt)
+        return path
