@@ -17,6 +17,9 @@ METRICS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "deepfluid
 # the latent-space integrator (arch='nn'): likewise a library and a header of its own
 NN_LIB_PATH = os.path.join(_HERE, "csrc", "libdeepfluids_hip_nn.so")
 NN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "deepfluids_hip_nn.h")
+# SSIM / MS-SSIM: likewise
+SSIM_LIB_PATH = os.path.join(_HERE, "csrc", "libdeepfluids_hip_ssim.so")
+SSIM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "deepfluids_hip_ssim.h")
 
 P, I64, I32, F32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
 U32 = ctypes.c_uint32
@@ -76,6 +79,9 @@ METRICS_SIGNATURES, METRICS_CONSTANTS = parse_header(_read_header(METRICS_HEADER
 globals().update(METRICS_CONSTANTS)
 # ... and of deepfluids_hip_nn.h: df_nn_*
 NN_SIGNATURES, NN_CONSTANTS = parse_header(_read_header(NN_HEADER_PATH))
+# ... and of deepfluids_hip_ssim.h: df_ssim* and the DF_SSIM_* word indices and limits
+SSIM_SIGNATURES, SSIM_CONSTANTS = parse_header(_read_header(SSIM_HEADER_PATH))
+globals().update(SSIM_CONSTANTS)
 
 
 class NoiseParams(ctypes.Structure):
@@ -87,6 +93,7 @@ class NoiseParams(ctypes.Structure):
 _lib = None
 _metrics_lib = None
 _nn_lib = None
+_ssim_lib = None
 
 
 def declared_symbols():
@@ -159,9 +166,28 @@ def nn_lib():
     return _nn_lib
 
 
+def ssim_lib():
+    """libdeepfluids_hip_ssim.so; the main library is loaded first (it holds the error buffer the ssim library writes to)"""
+    global _ssim_lib
+    if _ssim_lib is None:
+        lib()
+        if not os.path.exists(SSIM_LIB_PATH):
+            raise DeepFluidsHipError("libdeepfluids_hip_ssim.so not found at %s -- `make -C deep_fluids_amd/csrc` builds it with the main "
+                                     "library. There is no CPU fallback." % SSIM_LIB_PATH)
+        handle = ctypes.CDLL(SSIM_LIB_PATH)
+        for name, (res, args) in SSIM_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype = res
+            fn.argtypes = args
+        _ssim_lib = handle
+    return _ssim_lib
+
+
 def _handle(name):
     if name in NN_SIGNATURES:
         return nn_lib()
+    if name in SSIM_SIGNATURES:
+        return ssim_lib()
     return metrics_lib() if name in METRICS_SIGNATURES else lib()
 
 
@@ -221,6 +247,6 @@ def query(name, *args):
         return _QUERY_CACHE[key]
     except KeyError:
         v = getattr(_handle(name), name)(*args)
-        if P not in (NN_SIGNATURES.get(name) or METRICS_SIGNATURES.get(name) or SIGNATURES[name])[1]:
+        if P not in (NN_SIGNATURES.get(name) or SSIM_SIGNATURES.get(name) or METRICS_SIGNATURES.get(name) or SIGNATURES[name])[1]:
             _QUERY_CACHE[key] = v
         return v

@@ -29,6 +29,7 @@ __all__ = [
     "int_shape", "get_conv_shape", "nchw_to_nhwc", "nhwc_to_nchw", "add", "concat", "sigmoid", "mse_mean",
     "jacobian", "jacobian3", "curl", "curl3", "divergence", "divergence3", "pgrad",
     "vort_np", "curl_np", "grad_np", "jacobian_np3", "l1_mean", "velocity_loss", "field_metrics", "field_metrics_workspace", "FieldMetrics",
+    "fspecial_gauss", "ssim", "ms_ssim", "field_ssim", "ssim_workspace", "SSIMWorkspace",
     "denorm_img", "plane_view", "denorm_img3", "plane_view_np", "velocity_views3", "add_channels", "remove_channels",
     "advect", "advect_sequence", "advect_workspace", "density_image", "sphere_mask",
     "advect_velocity", "wall_buoyancy", "solve_pressure", "pressure_workspace", "smoke_step", "simulate_smoke", "default_buoyancy_force", "default_max_iter", "obstacle_flags", "ObstacleFlags",
@@ -1735,6 +1736,207 @@ def field_metrics(g, x, mask=None, workspace=None):
         call("df_field_metrics%dd" % dim, _ptr(g), _ptr(x), _ptr(mask), per_entry, _ptr(raw), _ptr(ws), ws.numel() * ws.element_size(),
              *(ext[:1] + ext[-dim:] + [_stream()]))
         return FieldMetrics(raw, dim)
+
+
+# ---- SSIM / MS-SSIM (include/deepfluids_hip_ssim.h; csrc/ssim.hip; ops.py:382-501): evaluation only, no autograd ----
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # ops.py:467
+_SSIM_TAPS = {}
+_SSIM_WEIGHTS = {}
+
+
+def _ssim_taps(size, sigma):
+    """the normalised 1-D factor of ``fspecial_gauss(size, sigma, .)`` as the header defines it: fp64, rounded to fp32 once.
+    ``(float32 array [size], the same as a ctypes array)``"""
+    key = (int(size), float(sigma))
+    if key not in _SSIM_TAPS:
+        u = np.arange(size, dtype=np.float64) - size // 2 + (0.5 if size % 2 == 0 else 0.0)
+        e = np.exp(-(u * u) / (2.0 * float(sigma) ** 2))
+        t = (e / e.sum()).astype(np.float32)
+        if not np.isfinite(t).all():
+            raise ValueError("ssim: a window of %d taps with sigma %r is not finite" % (size, sigma))
+        _SSIM_TAPS[key] = (t, (ctypes.c_float * int(size))(*[float(v) for v in t]))
+    return _SSIM_TAPS[key]
+
+
+def fspecial_gauss(size, sigma, channels):
+    """ops.py:382-407: the Gaussian window [size,size,C,C], normalised over ALL its entries (so every channel pair holds the 2-D
+    window over C^2), with the half-cell offset of an even ``size``.  Computed in fp64 on the host, float32 CPU tensor."""
+    size, channels = int(size), int(channels)
+    if size < 1 or channels < 1 or not float(sigma) > 0:
+        raise ValueError("fspecial_gauss: size and channels must be >= 1 and sigma > 0, got %r, %r, %r" % (size, sigma, channels))
+    u = np.arange(size, dtype=np.float64) - size // 2 + (0.5 if size % 2 == 0 else 0.0)
+    g = np.exp(-(u[:, None] ** 2 + u[None, :] ** 2) / (2.0 * float(sigma) ** 2))
+    g = np.broadcast_to(g[:, :, None, None], (size, size, channels, channels))
+    return torch.from_numpy((g / g.sum()).astype(np.float32))
+
+
+def _ssim_args(who, img1, img2, filter_size, filter_sigma, min_val, max_val):
+    """the checks of the SSIM entry points that need no device: ``(N, H, W, C, size, sigma)``"""
+    for t, name in ((img1, "img1"), (img2, "img2")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a torch.Tensor on the MI355X (got %r)" % (who, name, type(t)))
+    if img1.dim() != 4 or not 1 <= img1.shape[-1] <= _lib.DF_SSIM_MAX_CHANNELS or min(img1.shape) < 1:
+        raise ValueError("%s expects images [N,H,W,C] with C in 1..%d, got img1 %s" % (who, _lib.DF_SSIM_MAX_CHANNELS, tuple(img1.shape)))
+    if tuple(img2.shape) != tuple(img1.shape):
+        raise ValueError("%s: img1 %s and img2 %s disagree in shape" % (who, tuple(img1.shape), tuple(img2.shape)))
+    for t, name in ((img1, "img1"), (img2, "img2")):
+        if t.dtype != torch.float32:
+            raise ValueError("%s: %s must be float32 (both images in the same dtype), got %s" % (who, name, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous (strides %s for shape %s)" % (who, name, tuple(t.stride()), tuple(t.shape)))
+        if t.requires_grad:
+            raise NotImplementedError("%s: %s requires grad; SSIM has no backward here (detach it: evaluation only)" % (who, name))
+    if int(filter_size) != filter_size or filter_size < 1:
+        # the reference's filter_size = 0 branch does not run (`mu1 = img1, mu2 = img2` unpacks a tensor into two names)
+        raise ValueError("%s: filter_size must be an integer >= 1, got %r" % (who, filter_size))
+    if not float(filter_sigma) > 0:
+        raise ValueError("%s: filter_sigma must be > 0, got %r" % (who, filter_sigma))
+    if not (math.isfinite(min_val) and math.isfinite(max_val)) or np.float32(max_val) == np.float32(min_val):
+        raise ValueError("%s: min_val and max_val must be finite and differ, got %r, %r" % (who, min_val, max_val))
+    N, H, W, C = (int(n) for n in img1.shape)
+    size = min(int(filter_size), H, W)
+    if size > _lib.DF_SSIM_MAX_SIZE:
+        raise ValueError("%s: a window of %d taps; the kernel's staged tile holds at most %d" % (who, size, _lib.DF_SSIM_MAX_SIZE))
+    if query("df_ssim_workspace_bytes", N, H, W, int(filter_size)) < 0:
+        raise ValueError("%s: images of shape %s do not fit the int32 index of the kernel" % (who, tuple(img1.shape)))
+    return N, H, W, C, size, float(filter_sigma) * size / int(filter_size)
+
+
+class SSIMWorkspace(object):
+    """What repeated SSIM calls on images of one shape need (``ssim_workspace``): per level the tile sums, the output rows, the two
+    map planes when asked for and the pooled pair that is the next level's input, and the fp64 means [levels, groups, 2]."""
+
+    def __init__(self, shape, device, levels, filter_size, groups, maps=False):
+        N, H, W, C = (int(n) for n in shape)
+        self.shape, self.levels, self.filter_size, self.groups, self.device = (N, H, W, C), int(levels), int(filter_size), int(groups), torch.device(device)
+        if N % self.groups:
+            raise ValueError("ssim_workspace: %d images are not %d groups" % (N, self.groups))
+        self.level = []
+        for k in range(self.levels):
+            need = query("df_ssim_workspace_bytes", N, H, W, self.filter_size)
+            if need < 0:
+                raise ValueError("ssim_workspace: no workspace for images of shape %s" % ((N, H, W, C),))
+            size = min(self.filter_size, H, W)
+            lv = {"shape": (N, H, W, C), "ws": torch.empty((need // 8,), dtype=torch.float64, device=device),
+                  "out": torch.empty((N, _lib.DF_SSIM_WORDS), dtype=torch.int32, device=device), "maps": None, "pool": None}
+            if maps:
+                lv["maps"] = (torch.empty((N, H - size + 1, W - size + 1), dtype=torch.float32, device=device),
+                              torch.empty((N, H - size + 1, W - size + 1), dtype=torch.float32, device=device))
+            H, W = (H + 1) // 2, (W + 1) // 2
+            if k < self.levels - 1:
+                lv["pool"] = (torch.empty((N, H, W, C), dtype=torch.float32, device=device), torch.empty((N, H, W, C), dtype=torch.float32, device=device))
+            self.level.append(lv)
+        self.mean = torch.empty((self.levels, self.groups, 2), dtype=torch.float64, device=device)
+
+
+def ssim_workspace(x, multiscale=False, filter_size=11):
+    """The buffers ``field_ssim(g, x, multiscale=...)`` needs for fields of the shape of ``x`` ([B,Y,X,C] or [B,Z,Y,X,C]); reusable
+    across calls, so that a sweep allocates nothing per batch."""
+    if x.dim() not in (4, 5):
+        raise ValueError("ssim_workspace expects fields [B,Y,X,C] or [B,Z,Y,X,C], got %s" % (tuple(x.shape),))
+    B = int(x.shape[0])
+    shape = (B * int(np.prod(x.shape[1:-3])),) + tuple(int(n) for n in x.shape[-3:])
+    return SSIMWorkspace(shape, x.device, len(MS_SSIM_WEIGHTS) if multiscale else 1, 11 if multiscale else filter_size, B)
+
+
+def _ssim_run(who, a, b, ws, filter_sigma, k1, k2, min_val, max_val):
+    """the levels of ``ws`` on the images a, b: one fused launch (and its small second one) per level, each but the last also
+    writing the next level's images; then the group means of every level.  Nothing is read back."""
+    a, b = _prep(a, "img1"), _prep(b, "img2")
+    if b.device != a.device or ws.device != a.device:
+        raise ValueError("%s: the images and the workspace must be on one device" % who)
+    if tuple(a.shape) != ws.shape:
+        raise ValueError("%s: the workspace is for images %s, got %s" % (who, ws.shape, tuple(a.shape)))
+    s = _stream()
+    for k, lv in enumerate(ws.level):
+        N, H, W, C = lv["shape"]
+        size = min(ws.filter_size, H, W)
+        taps = _ssim_taps(size, float(filter_sigma) * size / ws.filter_size)[1]
+        maps, pool = lv["maps"] or (None, None), lv["pool"] or (None, None)
+        call("df_ssim", _ptr(a), _ptr(b), taps, _ptr(maps[0]), _ptr(maps[1]), _ptr(pool[0]), _ptr(pool[1]), _ptr(lv["out"]), _ptr(lv["ws"]),
+             lv["ws"].numel() * 8, N, H, W, C, ws.filter_size, float(k1), float(k2), float(min_val), float(max_val), s)
+        call("df_ssim_group_mean", _ptr(lv["out"]), _ptr(ws.mean[k]), ws.groups, N // ws.groups, s)
+        a, b = pool
+    return ws.mean
+
+
+def _ms_combine(mean):
+    """mean [5, G, 2] fp64 (ssim, cs per level) -> [G] fp64: prod(mcs[0:4] ** w[0:4]) * mssim[4] ** w[4], on the device"""
+    key = mean.device
+    if key not in _SSIM_WEIGHTS:
+        _SSIM_WEIGHTS[key] = torch.tensor(MS_SSIM_WEIGHTS, dtype=torch.float64, device=mean.device)
+    w = _SSIM_WEIGHTS[key]
+    return torch.prod(mean[:-1, :, 1] ** w[:-1, None], dim=0) * mean[-1, :, 0] ** w[-1]
+
+
+def ssim(img1, img2, mean_metric=True, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03, min_val=-1.0, max_val=1.0):
+    """ops.py:410-462: the structural similarity of two image batches [N,H,W,C] (float32, contiguous, C in 1..4, values in
+    [min_val, max_val]) as ONE fused pass (include/deepfluids_hip_ssim.h fixes every operation and the order of every sum;
+    tests/ssim_ref.py restates it).  The window shrinks to ``min(filter_size, H, W)`` taps (at most 11 here) and sigma with it.
+    ``mean_metric=True``: a 0-d float32 tensor on the device, the mean over the whole batch: the images' fp64 totals added and
+    divided by N H' W', rounded once.  ``mean_metric=False``: the reference's dict, ``ssim_map`` and ``cs_map`` [N,H',W',C] (the
+    reference's C channels are equal: an expanded view of the one plane) and ``g``, the window [size,size,C,C].
+    As in the reference every output channel is 1/C^2 times the sum over the input channels (the window is normalised over all its
+    C^2 channel pairs).  No autograd: inputs that require grad are refused."""
+    N, H, W, C, size, sigma = _ssim_args("ssim", img1, img2, filter_size, filter_sigma, min_val, max_val)
+    with torch.no_grad():
+        _prep(img1, "img1"), _prep(img2, "img2")
+        ws = SSIMWorkspace((N, H, W, C), img1.device, 1, filter_size, 1, maps=not mean_metric)
+        mean = _ssim_run("ssim", img1, img2, ws, filter_sigma, k1, k2, min_val, max_val)
+        if mean_metric:
+            return mean[0, 0, 0].float()
+        sm, cm = ws.level[0]["maps"]
+        return {"ssim_map": sm.unsqueeze(-1).expand(-1, -1, -1, C), "cs_map": cm.unsqueeze(-1).expand(-1, -1, -1, C),
+                "g": fspecial_gauss(size, sigma, C).to(img1.device)}
+
+
+def ms_ssim(img1, img2, mean_metric=True, min_val=-1.0, max_val=1.0):
+    """ops.py:465-501: multi-scale SSIM with the reference's five weights.  Each level is one fused launch that also writes the 2x2
+    average-pooled images ('SAME': ceil(H/2) x ceil(W/2), an edge cell averages what exists) the next level reads; the last writes
+    none.  The levels' batch means (fp64) are combined on the device, prod(mcs[0:4] ** w[0:4]) * mssim[4] ** w[4], without a host
+    read; a 0-d float32 tensor either way (the reference's ``mean_metric`` averages a scalar).  NaN where the reference gives NaN:
+    a non-positive level mean (cs of levels 0..3, ssim of level 4) under a fractional power."""
+    N, H, W, C, _, _ = _ssim_args("ms_ssim", img1, img2, 11, 1.5, min_val, max_val)
+    with torch.no_grad():
+        _prep(img1, "img1"), _prep(img2, "img2")
+        ws = SSIMWorkspace((N, H, W, C), img1.device, len(MS_SSIM_WEIGHTS), 11, 1)
+        return _ms_combine(_ssim_run("ms_ssim", img1, img2, ws, 1.5, 0.01, 0.03, min_val, max_val))[0].float()
+
+
+def field_ssim(g, x, multiscale=False, workspace=None, **ssim_kwargs):
+    """SSIM (``multiscale``: MS-SSIM) of a generated field ``g`` against the ground truth ``x``, per batch ENTRY: float64 [B] on the
+    device.  Fields are [B,Y,X,C] or [B,Z,Y,X,C]; a 3-D field is taken as its B Z slices [Y,X,C] (a view; window and pooling stay
+    in-plane), and an entry's mean is over the pixels of all its slices: the slices' fp64 totals added, divided by Z H' W'
+    (``df_ssim_group_mean``).  ``ssim_kwargs``: ``filter_size, filter_sigma, k1, k2, min_val, max_val`` of ``ssim`` (``multiscale``:
+    ``min_val, max_val`` only).  ``workspace``: see ``ssim_workspace``.  No autograd."""
+    who = "field_ssim"
+    allowed = ("min_val", "max_val") if multiscale else ("filter_size", "filter_sigma", "k1", "k2", "min_val", "max_val")
+    for k in ssim_kwargs:
+        if k not in allowed:
+            raise TypeError("%s: unexpected argument %r (multiscale=%s takes %s)" % (who, k, bool(multiscale), ", ".join(allowed)))
+    kw = dict(filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03, min_val=-1.0, max_val=1.0)
+    kw.update(ssim_kwargs)
+    for t, name in ((g, "g"), (x, "x")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a torch.Tensor on the MI355X (got %r)" % (who, name, type(t)))
+    if g.dim() not in (4, 5):
+        raise ValueError("%s expects fields [B,Y,X,C] or [B,Z,Y,X,C], got g %s" % (who, tuple(g.shape)))
+    if tuple(x.shape) != tuple(g.shape):
+        raise ValueError("%s: g %s and x %s disagree in shape" % (who, tuple(g.shape), tuple(x.shape)))
+    for t, name in ((g, "g"), (x, "x")):
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous (strides %s for shape %s)" % (who, name, tuple(t.stride()), tuple(t.shape)))
+    B = int(g.shape[0])
+    a, b = g.reshape((-1,) + tuple(g.shape[-3:])), x.reshape((-1,) + tuple(x.shape[-3:]))      # views: both are contiguous
+    _ssim_args(who, a, b, kw["filter_size"], kw["filter_sigma"], kw["min_val"], kw["max_val"])
+    with torch.no_grad():
+        _prep(a, "g"), _prep(b, "x")
+        ws = workspace if workspace is not None else ssim_workspace(g, multiscale, kw["filter_size"])
+        if not isinstance(ws, SSIMWorkspace) or ws.groups != B or ws.levels != (len(MS_SSIM_WEIGHTS) if multiscale else 1) or \
+                ws.filter_size != int(kw["filter_size"]):
+            raise ValueError("%s: the workspace was made for another call (ssim_workspace(x, multiscale, filter_size))" % who)
+        mean = _ssim_run(who, a, b, ws, kw["filter_sigma"], kw["k1"], kw["k2"], kw["min_val"], kw["max_val"])
+        return _ms_combine(mean) if multiscale else mean[0, :, 0].clone()
 
 
 # ---- uint8 image views (ops.py:138-188): inference only, no autograd, torch.uint8 out ----

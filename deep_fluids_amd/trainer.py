@@ -93,21 +93,38 @@ def _eval_stats(arrays):
     return s
 
 
-def _eval_write(model_dir, groups, x_range):
+EVAL_SSIM = ("ssim", "ms_ssim")      # `evaluate_(ssim=True)`: per-frame arrays, and mean, min and max over frames per group and in total
+
+
+def _eval_ssim_stats(arrays):
+    """``{"<q>_mean", "<q>_min", "<q>_max" for q in EVAL_SSIM}`` of per-frame arrays"""
+    return {q + s: float(f(arrays[q])) for q in EVAL_SSIM for s, f in (("_mean", np.mean), ("_min", np.min), ("_max", np.max))}
+
+
+def _eval_write(model_dir, groups, x_range, ssim=None):
     """Write ``<model_dir>/eval/<name>.npz`` for every ``(name, host FieldMetrics)`` of ``groups`` and ``eval/summary.txt`` (one line per
     group, then ``total``: the statistics over the frames of all groups, its worst frame as ``<name>:<frame>``); return the summary
-    ``{"dir", "groups": {name: stats}, "total": stats}``."""
+    ``{"dir", "groups": {name: stats}, "total": stats}``.  ``ssim``: None, or ``{name: {"ssim": [frames], "ms_ssim": [frames]}}`` of host
+    float64 arrays: they join the group's ``.npz``, their mean, min and max the stats, and ``summary.txt`` gains a second block of
+    lines for them."""
     out_dir = os.path.join(model_dir, "eval")
     os.makedirs(out_dir, exist_ok=True)
     summary = {"dir": out_dir, "groups": {}}
     every = {}
     for name, metrics in groups:
         arrays = _eval_arrays(metrics, x_range)
+        if ssim is not None:
+            arrays.update({q: np.asarray(ssim[name][q], np.float64) for q in EVAL_SSIM})
         np.savez_compressed(os.path.join(out_dir, name + ".npz"), **arrays)
         summary["groups"][name] = _eval_stats(arrays)
-        for q in EVAL_SUMMARY:
+        if ssim is not None:
+            summary["groups"][name].update(_eval_ssim_stats(arrays))
+        for q in EVAL_SUMMARY + (EVAL_SSIM if ssim is not None else ()):
             every.setdefault(q, []).append(arrays[q])
-    total = _eval_stats({q: np.concatenate(v) for q, v in every.items()})
+    every = {q: np.concatenate(v) for q, v in every.items()}
+    total = _eval_stats(every)
+    if ssim is not None:
+        total.update(_eval_ssim_stats(every))
     worst, frame = None, total["worst_frame"]
     for name, metrics in groups:          # the group that holds frame `frame` of the concatenation
         if worst is None and frame < metrics.batch:
@@ -120,7 +137,22 @@ def _eval_write(model_dir, groups, x_range):
         f.write("# %s frames %s worst_frame (normalised units; worst = largest l1)\n" % ("group", " ".join(cols)))
         for name, st in list(summary["groups"].items()) + [("total", total)]:
             f.write("%s %d %s %s\n" % (name, st["frames"], " ".join("%.9g" % st[c] for c in cols), st["worst_frame"]))
+        if ssim is not None:
+            cols = [q + s for q in EVAL_SSIM for s in ("_mean", "_min", "_max")]
+            f.write("# %s %s (normalised fields, min_val -1, max_val 1)\n" % ("group", " ".join(cols)))
+            for name, st in list(summary["groups"].items()) + [("total", total)]:
+                f.write("%s %s\n" % (name, " ".join("%.9g" % st[c] for c in cols)))
     return summary
+
+
+def _eval_ssim(workspaces, g, x):
+    """``(ssim, ms_ssim)`` float64 [frames] on the device of one batch of normalised fields; the workspaces are made once per shape"""
+    key = tuple(g.shape)
+    if key not in workspaces:
+        workspaces[key] = (ops.ssim_workspace(g), ops.ssim_workspace(g, multiscale=True))
+    one, multi = workspaces[key]
+    return (ops.field_ssim(g, x, workspace=one, min_val=-1.0, max_val=1.0),
+            ops.field_ssim(g, x, multiscale=True, workspace=multi, min_val=-1.0, max_val=1.0))
 
 
 def _detached(m):
@@ -705,7 +737,7 @@ class Trainer(object):
             z_c[:, -1] = np.linspace(-1, 1, num=y_num[-1])
         return z_c, niter, test_b_num, [pair + (t,) for t in range(y_num[-1])]
 
-    def evaluate_(self, batch_manager, model_dir=None, pairs=None, test_b_num=None, denorm=True, mask=None):
+    def evaluate_(self, batch_manager, model_dir=None, pairs=None, test_b_num=None, denorm=True, mask=None, ssim=False):
         """How well the model reproduces its data set.  For every ``(p1, p2)`` of ``pairs`` (default: every pair of the set; ``(p1,)``
         for a 2-parameter set) sweep the frames as ``test_`` does, load the matching ground-truth frames the way training reads them
         (``data.preprocess``: the same files, the same ``x_range`` normalisation), and run ``generate`` and ``ops.field_metrics`` batch
@@ -716,7 +748,10 @@ class Trainer(object):
           ``<model_dir>/eval/summary.txt``     per pair and in total: frames, mean and max over frames of l1, rel_l2, jacobian_l1 and
                                                div_l1_g, and the worst frame (largest l1)
         and returns the summary as a dict ``{"dir", "groups": {"<p1>_<p2>": {...}}, "total": {...}}``.  ``mask``: cells to count,
-        [(Z,)Y,X], non-zero = counted.  Nothing is captured into a graph and nothing is trained."""
+        [(Z,)Y,X], non-zero = counted.  Nothing is captured into a graph and nothing is trained.
+        ``ssim=True``: also ``ops.field_ssim`` and its ``multiscale`` form of every frame on the normalised fields (``min_val=-1,
+        max_val=1``; the mask does not apply to them): arrays ``ssim`` and ``ms_ssim`` [frames] in each ``.npz``, their mean, min and
+        max in the summary and in a second block of ``summary.txt``.  With the default nothing of this runs or is allocated."""
         import itertools
         from .data import preprocess
         model_dir = model_dir or self.effective_model_dir()
@@ -725,19 +760,26 @@ class Trainer(object):
             pairs = list(itertools.product(*(range(n) for n in y_num[:-1])))
         mask = _eval_mask(mask, self.device)
         groups = []
+        sims, workspaces = ({}, {}) if ssim else (None, None)
         for pair in pairs:
             pair = (pair,) if isinstance(pair, (int, np.integer)) else tuple(pair)
             z_c, niter, b_num, p_list = self._pair_codes(batch_manager, pair, test_b_num)
             paths = batch_manager.list_from_p(p_list)
-            parts = []
+            parts, sparts = [], []
             for b in range(niter):
                 rows = slice(b_num * b, b_num * (b + 1))
                 truth = np.stack([preprocess(p, batch_manager.data_type, batch_manager.x_range, batch_manager.y_range)[0] for p in paths[rows]])
                 x = torch.from_numpy(np.ascontiguousarray(truth, np.float32)).to(self.device)
                 g = self.generate(torch.from_numpy(z_c[rows]).to(self.device))
-                parts.append(ops.field_metrics(g.contiguous(), x, mask=mask))
-            groups.append(("_".join(str(p) for p in pair), ops.FieldMetrics.cat(parts).cpu()))      # the pair's one read
-        return _eval_write(model_dir, groups, batch_manager.x_range if denorm else None)
+                g = g.contiguous()
+                parts.append(ops.field_metrics(g, x, mask=mask))
+                if ssim:
+                    sparts.append(_eval_ssim(workspaces, g, x))
+            name = "_".join(str(p) for p in pair)
+            groups.append((name, ops.FieldMetrics.cat(parts).cpu()))      # the pair's one read
+            if ssim:
+                sims[name] = {q: torch.cat([p[i] for p in sparts]).cpu().numpy() for i, q in enumerate(EVAL_SSIM)}
+        return _eval_write(model_dir, groups, batch_manager.x_range if denorm else None, sims)
 
     # ---- `advect()` of the scene scripts (scene/smoke_pos_size.py:45-109): smoke carried through the generated velocities ------
     def advect_(self, batch_manager, model_dir=None, p1=10, p2=2, test_b_num=None, *, source, dt=None, order=2, clamp_mode=2, bnd=1,
@@ -1120,11 +1162,12 @@ class AETrainer(Trainer):
         ``p1, p2`` in between, so a positional batch size could not mean the same thing on both)."""
         return self.test_ae(batch_manager, model_dir, code_path=code_path, test_b_num=test_b_num)
 
-    def evaluate_(self, batch_manager, model_dir=None, test_b_num=None, denorm=True, mask=None):
+    def evaluate_(self, batch_manager, model_dir=None, test_b_num=None, denorm=True, mask=None, ssim=False):
         """``Trainer.evaluate_`` for the auto-encoder: there is no code sweep, every frame of the data set is read in file order
         (scene by scene, as ``batch_manager.batch_`` does), reconstructed (``reconstruct``) and measured against itself with
         ``ops.field_metrics``.  Writes ``<model_dir>/eval/<scene>.npz`` per scene of ``num_frames`` frames (one group ``0`` when the
-        file count is no multiple of it) and ``eval/summary.txt``; same arrays, same summary.  The last batch may be short."""
+        file count is no multiple of it) and ``eval/summary.txt``; same arrays, same summary.  The last batch may be short.
+        ``ssim=True``: as in ``Trainer.evaluate_``."""
         from .data import preprocess
         model_dir = model_dir or self.effective_model_dir()
         b_num = int(test_b_num or self.config.test_batch_size)
@@ -1132,17 +1175,24 @@ class AETrainer(Trainer):
             raise ValueError("evaluate_: test_b_num must be >= 1, got %r" % (test_b_num,))
         mask = _eval_mask(mask, self.device)
         paths = batch_manager.paths
-        parts = []
+        parts, sparts, workspaces = [], [], {}
         for i in range(0, len(paths), b_num):
             truth = np.stack([preprocess(p, batch_manager.data_type, batch_manager.x_range, batch_manager.y_range)[0] for p in paths[i:i + b_num]])
             x = torch.from_numpy(np.ascontiguousarray(truth, np.float32)).to(self.device)
-            parts.append(ops.field_metrics(self.reconstruct(x).contiguous(), x, mask=mask))
+            g = self.reconstruct(x).contiguous()
+            parts.append(ops.field_metrics(g, x, mask=mask))
+            if ssim:
+                sparts.append(_eval_ssim(workspaces, g, x))
         raw = ops.FieldMetrics.cat(parts).cpu().raw                          # the one read
         nf = int(batch_manager.args.get("num_frames", 0))
         if nf < 1 or len(paths) % nf != 0:
             nf = len(paths)
         groups = [(str(s), ops.FieldMetrics(raw[s * nf:(s + 1) * nf], parts[0].dim)) for s in range(len(paths) // nf)]
-        return _eval_write(model_dir, groups, batch_manager.x_range if denorm else None)
+        sims = None
+        if ssim:
+            every = [torch.cat([p[i] for p in sparts]).cpu().numpy() for i in range(len(EVAL_SSIM))]
+            sims = {str(s): {q: every[i][s * nf:(s + 1) * nf] for i, q in enumerate(EVAL_SSIM)} for s in range(len(paths) // nf)}
+        return _eval_write(model_dir, groups, batch_manager.x_range if denorm else None, sims)
 
     def test_ae(self, batch_manager, model_dir=None, *, code_path=None, test_b_num=None):
         """``Trainer.test_ae``.  Without ``code_path`` (trainer.py:478-523): encode the whole dataset in file order
