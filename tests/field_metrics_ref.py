@@ -97,10 +97,10 @@ def metrics(g, x, mask=None, dtype=F32):
     D, B = g.shape[-1], g.shape[0]
     cnt = counted_cells(g.shape, mask)
     d = g - x
-    a1, a2, m = np.abs(d[..., 0]) + np.abs(d[..., 1]), d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1], np.maximum(np.abs(d[..., 0]), np.abs(d[..., 1]))
+    a1, a2, m = np.abs(d[..., 0]) + np.abs(d[..., 1]), d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1], np.fmax(np.abs(d[..., 0]), np.abs(d[..., 1]))
     x1, x2 = np.abs(x[..., 0]) + np.abs(x[..., 1]), x[..., 0] * x[..., 0] + x[..., 1] * x[..., 1]
     if D == 3:
-        a1, a2, m = a1 + np.abs(d[..., 2]), a2 + d[..., 2] * d[..., 2], np.maximum(m, np.abs(d[..., 2]))
+        a1, a2, m = a1 + np.abs(d[..., 2]), a2 + d[..., 2] * d[..., 2], np.fmax(m, np.abs(d[..., 2]))
         x1, x2 = x1 + np.abs(x[..., 2]), x2 + x[..., 2] * x[..., 2]
     jg, jx = ((orc.jacobian3(g)[0], orc.jacobian3(x)[0]) if D == 3 else (orc.jacobian(g)[0], orc.jacobian(x)[0]))
     aj = np.zeros(g.shape[:-1], dtype)
@@ -121,11 +121,16 @@ def metrics(g, x, mask=None, dtype=F32):
     for name, v, c in (("sum_abs", a1, cnt), ("sum_sq", a2, cnt), ("sum_abs_x", x1, cnt), ("sum_sq_x", x2, cnt), ("sum_abs_jac", aj, cnt),
                        ("sum_abs_div_g", dg, dcnt), ("sum_abs_div_x", dx, dcnt)):
         out[name] = ordered_sum(np.where(c, flat(v), zero), dtype)
-    mm = np.where(cnt, flat(m), dtype(-1))
-    out["argmax"] = np.where(out["count"] > 0, mm.argmax(1), -1).astype(np.int32)      # np.argmax: the first, i.e. lowest, of equals
+    # Non-finite values (the header is silent; this is C's fmaxf and the kernel's `mm > m` from m = -1, idx = -1, stated here and not
+    # read off a result): a NaN component is dropped by fmax, so m is a NaN only where every component of d is one; such a cell never
+    # wins the comparison, it neither moves max_abs nor becomes the arg-max (an entry whose counted cells ALL have m = NaN keeps
+    # -1 / -1); the maxima of |div| drop a NaN in the same way.  The sums take every counted cell and become non-finite.
+    with np.errstate(invalid="ignore"):
+        mm = np.where(cnt & ~np.isnan(flat(m)), flat(m), dtype(-1))
+    out["argmax"] = np.where((mm >= 0).any(1), mm.argmax(1), -1).astype(np.int32)      # np.argmax: the first, i.e. lowest, of equals
     out["max_abs"] = np.where(out["count"] > 0, mm.max(1), zero).astype(dtype)
-    out["max_abs_div_g"] = np.where(dcnt, flat(dg), zero).max(1).astype(dtype)
-    out["max_abs_div_x"] = np.where(dcnt, flat(dx), zero).max(1).astype(dtype)
+    out["max_abs_div_g"] = np.fmax.reduce(np.where(dcnt, flat(dg), zero), axis=1).astype(dtype)
+    out["max_abs_div_x"] = np.fmax.reduce(np.where(dcnt, flat(dx), zero), axis=1).astype(dtype)
     return out
 
 

@@ -85,6 +85,12 @@ class Guarded(object):
     def untouched(self):
         return bool((self.bits == NAN_BITS).all())
 
+    def raw(self, what=""):
+        """guards intact -> the payload's int32 words as a host array, NAN_BITS still in it wherever nothing was written (a strided
+        output whose gaps must keep the fill; rows of fp64 halves, which may look like a NaN; results that hold a NaN on purpose)"""
+        self.check_guards(what)
+        return host(self.bits[self.lo:self.lo + self.n]).reshape(self.shape)
+
     def get(self, what=""):
         """guards intact, no NaN left inside -> the payload as a host array"""
         self.check_guards(what)

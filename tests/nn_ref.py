@@ -75,7 +75,7 @@ class Ops64(object):
     def elu(self, y):
         return np.where(y > 0, y, np.expm1(np.minimum(y, 0)))
 
-    def bn_fwd(self, x, gamma, beta, mm, mv, kept, keep_prob):
+    def bn_fwd(self, x, gamma, beta, mm, mv, kept, keep_prob, decay=DECAY):
         """-> out, act, mean, rstd, new moving mean, new moving variance"""
         dt = self.dt
         B = x.shape[0]
@@ -83,7 +83,7 @@ class Ops64(object):
         act = self.elu(((x - mean) * rstd) * gamma + beta)
         inv = dt(1) / dt(F32(keep_prob))
         out = np.where(kept, act * inv, dt(0))
-        decay = dt(F32(DECAY)); omd = dt(1) - decay
+        decay = dt(F32(decay)); omd = dt(1) - decay
         bessel = dt(B) / dt(max(B - 1, 1))
         return out, act, mean, rstd, mm * decay + mean * omd, mv * decay + (var * bessel) * omd
 
@@ -233,10 +233,24 @@ class Ops32(Ops64):
         return out
 
 
-def init_params(rng, k0, filters, z_num, scale=1.0):
+def matvec_chunks(K, N):
+    """the branches ``Ops32.matvec`` (and ``matvec`` of rollout_kernel) takes for a [K,N] layer: per chunk of 1024 columns
+    ``(n0, nb, sk, idle)`` -- its first column, its columns, the interleaved parts of k, and the threads of the workgroup beyond
+    sk * nb, which hold no partial sum"""
+    out = []
+    for n0 in range(0, N, 1024):
+        nb = min(N - n0, 1024)
+        sk = 1024 // nb
+        out.append((n0, nb, sk, 1024 - sk * nb))
+    return out
+
+
+def init_params(rng, k0, filters, z_num, scale=1.0, n2=None):
     """fp64 parameters under the slim names (Xavier-uniform weights times ``scale``; biases, beta, gamma and the moving statistics drawn
-    too, so that no term of a test is hidden behind a zero or a one)"""
-    dims = [(k0, 2 * filters), (2 * filters, filters), (filters, z_num)]
+    too, so that no term of a test is hidden behind a zero or a one).  ``n2``: the second hidden width where it is not ``filters``
+    (the first is 2 * filters, or ``filters`` itself when ``n2`` is given: the edge tests' N1 / N2 are not tied to each other)"""
+    n1, n2 = (2 * filters, filters) if n2 is None else (filters, n2)
+    dims = [(k0, n1), (n1, n2), (n2, z_num)]
     p = {}
     for fc, (i, o) in zip(FC, dims):
         lim = np.sqrt(6.0 / (i + o)) * scale
