@@ -81,6 +81,11 @@ constexpr unsigned kFluid = 1u;
 __device__ __forceinline__ unsigned lo_bit(int a) { return 2u << (2 * a); }
 __device__ __forceinline__ unsigned hi_bit(int a) { return 4u << (2 * a); }
 
+// open_sides `os` of the `_open` entry points: bit 2a = the low side of axis a is open, bit 2a + 1 = its high side (the order of the flags
+// byte's neighbour bits)
+__device__ __forceinline__ bool open_lo(int os, int a) { return ((os >> (2 * a)) & 1) != 0; }
+__device__ __forceinline__ bool open_hi(int os, int a) { return ((os >> (2 * a + 1)) & 1) != 0; }
+
 // min / max of orig over the interior corners c, c+1 of the integer cell c = clamp(trunc(t), 0, ext - 2) per axis; with MASKED only
 // those of them that are fluid (fl: the flags of this batch entry)
 template <int D, int S = 1, bool MASKED = false>

@@ -17,9 +17,10 @@
 //     correct_sweep  x + alpha e[parent] formed on the fly at the cell and its neighbours, then one sweep.
 //     sweep        one sweep; on level 0 it writes z and the workgroup's r.z partial (the `rr` partials of the solve's workspace).
 //                  The coarsest level (every extent <= 2) runs presmooth2 and six sweeps (inside mg_small_kernel).
-//   iteration      cg_direction_mg / cg_update_mg: the solve's two kernels for the preconditioned recurrence, as cg_direction_gf /
-//                  cg_update_gf have it: `rr` holds r.z, p = z + beta p.  update writes r and the max|r| partials; z comes from the
-//                  cycle that runs after it.  Every V-cycle kernel returns at once for an entry whose CgState::active is 0.
+//   iteration      the solve's own two kernels (smoke_common.hpp) for the preconditioned recurrence: cg_direction_kernel with the plain
+//                  rows and the direction built from z (`rr` holds r.z, p = z + beta p), cg_update_kernel<kLeaveMg>, which writes r and
+//                  the max|r| partials; z and the r.z partials come from the cycle that runs after it.  Every V-cycle kernel returns at
+//                  once for an entry whose CgState::active is 0.
 //   The levels are L2 resident at the sizes this is used for; the arrays are planar and every access of a pass is coalesced along x.
 #include "smoke_common.hpp"
 
@@ -29,6 +30,8 @@ using df::ceil_div;
 using dfadv::apart;
 using dfadv::hi_bit;
 using dfadv::lo_bit;
+using dfadv::open_hi;
+using dfadv::open_lo;
 
 constexpr int kMaxLevels = 26;                          // extents < 2^24
 constexpr float kOmega = 2.0f / 3.0f;
@@ -129,7 +132,7 @@ __global__ __launch_bounds__(kThreads) void mg_level0_kernel(MgLevel L, const ui
     const bool hi = fluid && (flags ? (fl & hi_bit(a)) != 0u : c.p[a] + 1 < ext[a] - bnd);
     L.w[a][g] = lo ? 1.0f : 0.0f;
     cnt += (lo ? 1 : 0) + (hi ? 1 : 0);
-    if (fluid) dir += ((c.p[a] == bnd && ((os >> (2 * a)) & 1)) ? 1 : 0) + ((c.p[a] + 1 == ext[a] - bnd && ((os >> (2 * a + 1)) & 1)) ? 1 : 0);
+    if (fluid) dir += ((c.p[a] == bnd && open_lo(os, a)) ? 1 : 0) + ((c.p[a] + 1 == ext[a] - bnd && open_hi(os, a)) ? 1 : 0);
   }
   L.dir[g] = static_cast<float>(dir);
   L.diag[g] = static_cast<float>(cnt + dir);
@@ -326,86 +329,7 @@ __global__ __launch_bounds__(kThreads) void mg_small_kernel(MgSmall S, float alp
 }
 #undef MG_EACH
 
-// ---- the preconditioned iteration ------------------------------------------------------------------------------------------------------------
-// cg_direction_kernel of smoke.hip with z in the place of r in the direction and r.z in the place of r.r (as cg_direction_gf): the same
-// matrix, read from the flags byte / the index tests
-template <int D, bool MASKED, bool OPEN>
-__global__ __launch_bounds__(kThreads) void cg_direction_mg(PWs w, const float* __restrict__ zz, const uint8_t* __restrict__ flags, PDims d,
-                                                            int par, int first, float accuracy, int max_iter, int os) {
-  __shared__ float lds[4];
-  const PCell c = pdecode<D, MASKED>(d, flags);
-  const bool writer = c.j == 0 && threadIdx.x == 0;
-  CgState s;
-  if (first) s = CgState{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1, 0, 0};
-  else s = w.state[par][c.e];
-  if (!s.active) {                                      // frozen: carry the record over, touch nothing else
-    if (writer) w.state[par ^ 1][c.e] = s;
-    return;
-  }
-  const int64_t po = static_cast<int64_t>(c.e) * d.nblk;
-  const float rz = entry_reduce<false>(w.rr_part + po, d.nblk, lds);
-  const float mx = entry_reduce<true>(w.mx_part + po, d.nblk, lds);
-  const bool act = mx > accuracy && rz > 0.0f && s.iters < max_iter;
-  const float beta = first ? 0.0f : rz / s.rr;          // s.rr > 0: the entry was active
-  if (writer) w.state[par ^ 1][c.e] = CgState{rz, mx, s.alpha, act ? beta : s.beta, s.pq, act ? 1 : 0, s.iters + (act ? 1 : 0), 0};
-  if (!act) return;
-  float pq = 0.0f;
-  if (c.interior) {
-    const int64_t eo = static_cast<int64_t>(c.e) * d.n;
-    const float* __restrict__ z = zz + eo;
-    const float* __restrict__ po_ = w.p[par] + eo;
-    const int64_t st[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
-    const int ext[3] = {d.X, d.Y, d.Z};
-    const float pc = z[c.cell] + beta * po_[c.cell];
-    float sum = 0.0f;
-    int cnt = 0;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-      const bool lo = MASKED ? (c.fl & lo_bit(a)) != 0u : c.p[a] > d.bnd;
-      const bool hi = MASKED ? (c.fl & hi_bit(a)) != 0u : c.p[a] + 1 < ext[a] - d.bnd;
-      if (lo) { const int64_t nb = c.cell - st[a]; sum += z[nb] + beta * po_[nb]; ++cnt; }
-      if (hi) { const int64_t nb = c.cell + st[a]; sum += z[nb] + beta * po_[nb]; ++cnt; }
-    }
-    if (OPEN) {
-#pragma unroll
-      for (int a = 0; a < D; ++a)
-        cnt += ((c.p[a] == d.bnd && ((os >> (2 * a)) & 1)) ? 1 : 0) + ((c.p[a] + 1 == ext[a] - d.bnd && ((os >> (2 * a + 1)) & 1)) ? 1 : 0);
-    }
-    const float qv = static_cast<float>(cnt) * pc - sum;
-    w.p[par ^ 1][eo + c.cell] = pc;
-    w.q[eo + c.cell] = qv;
-    pq = pc * qv;
-  }
-  pq = block_reduce<false>(pq, lds);
-  if (threadIdx.x == 0) w.pq_part[po + c.j] = pq;
-}
-
-// cg_update_kernel with alpha = r.z / p.q; it writes r and the max|r| partials, z and the r.z partials come from the cycle after it
-template <int D, bool MASKED>
-__global__ __launch_bounds__(kThreads) void cg_update_mg(float* __restrict__ x, PWs w, const uint8_t* __restrict__ flags, PDims d, int par) {
-  __shared__ float lds[4];
-  const PCell c = pdecode<D, MASKED>(d, flags);
-  CgState* s = w.state[par ^ 1] + c.e;                  // what direction(k) has just written
-  if (!s->active) return;
-  const float rz_old = s->rr;
-  const int64_t po = static_cast<int64_t>(c.e) * d.nblk;
-  const float pq = entry_reduce<false>(w.pq_part + po, d.nblk, lds);
-  const float alpha = pq > 0.0f ? rz_old / pq : 0.0f;
-  if (c.j == 0 && threadIdx.x == 0) { s->alpha = alpha; s->pq = pq; }   // words no workgroup of this launch reads
-  float mx = 0.0f;
-  if (c.interior) {
-    const int64_t g = static_cast<int64_t>(c.e) * d.n + c.cell;
-    x[g] = x[g] + alpha * w.p[par ^ 1][g];
-    const float rn = w.r[g] - alpha * w.q[g];
-    w.r[g] = rn;
-    mx = fabsf(rn);
-  }
-  mx = block_reduce<true>(mx, lds);
-  if (threadIdx.x == 0) w.mx_part[po + c.j] = mx;
-}
-
-// ---- host side -----------------------------------------------------------------------------------------------------------------------------
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+// ---- host side (aligned4, check_ws, check_apart, check_open, check_iter, DF_OPEN_CALL: smoke_common.hpp) --------------------------------------
 
 // the extents the solves accept (check_dims / pplan of smoke.hip), without a boundary width
 int mg_dims(const char* fn, int dim, int64_t B, int64_t Z, int64_t Y, int64_t X) {
@@ -507,22 +431,12 @@ int mg_alpha_ok(const char* fn, float alpha) {
   return DF_OK;
 }
 
-// the workspace of the plain solve beside a hierarchy
-int mg_ws(const char* fn, void* ws, int64_t ws_bytes, const MgPlan& p, const void* h, PDims* d) {
+// the workspace of the plain solve beside a hierarchy (`h` may be null: none)
+int mg_ws(const char* fn, void* ws, int64_t ws_bytes, const MgPlan& p, const void* h, int bnd, PDims* d) {
   const MgLevel& L = p.lev[0];
-  *d = PDims{L.n, L.nblk, (int)p.B, L.Z, L.Y, L.X, 0};
-  DF_REQUIRE(ws, DF_EINVAL, "%s: null workspace", fn);
-  DF_REQUIRE(aligned4(ws), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  const int64_t need = 4 * ws_floats(p.B, L.n, L.nblk);
-  DF_REQUIRE(ws_bytes >= need, DF_EWORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes, (long long)need);
-  DF_REQUIRE(!h || apart(ws, need, h, 4 * p.floats), DF_EINVAL, "%s: the workspace overlaps the hierarchy", fn);
-  return DF_OK;
-}
-
-int mg_open_ok(const char* fn, int dim, int open_sides) {
-  DF_REQUIRE(open_sides >= 0 && open_sides <= 63, DF_EINVAL, "%s: open_sides must be in 0..63 (got %d)", fn, open_sides);
-  DF_REQUIRE(dim == 3 || open_sides < 16, DF_EINVAL, "%s: open_sides %d opens a z side of a 2-D grid", fn, open_sides);
-  return DF_OK;
+  *d = PDims{L.n, L.nblk, (int)p.B, L.Z, L.Y, L.X, bnd};
+  if (int e = check_ws(fn, ws, ws_bytes, *d)) return e;
+  return check_apart(fn, ws, ws_bytes_needed(*d), h, 4 * p.floats, "hierarchy");
 }
 
 int mg_bnd_ok(const char* fn, int dim, int64_t Z, int64_t Y, int64_t X, int bnd) {
@@ -532,23 +446,22 @@ int mg_bnd_ok(const char* fn, int dim, int64_t Z, int64_t Y, int64_t X, int bnd)
   return DF_OK;
 }
 
-template <int D>
-int direction_mg(const char* fn, PWs w, const float* z, const uint8_t* flags, PDims d, int64_t k, float accuracy, int max_iter, int os,
-                 hipStream_t s) {
+// the solve's direction kernel (the plain rows) with the direction built from z, the cycle's output, and r.z in the `rr` partials
+template <int D, bool MASKED, bool OPEN>
+int direction_mg(const char* fn, PWs w, const float* z, const uint8_t* flags, PDims d, int64_t k, float accuracy, int max_iter, hipStream_t s,
+                 int os = 0) {
   const dim3 grid(static_cast<unsigned>(static_cast<int64_t>(d.nblk) * d.B)), blk(kThreads);
-  const int par = (int)(k & 1), first = k == 0 ? 1 : 0;
-  if (flags && os) hipLaunchKernelGGL((cg_direction_mg<D, true, true>), grid, blk, 0, s, w, z, flags, d, par, first, accuracy, max_iter, os);
-  else if (flags) hipLaunchKernelGGL((cg_direction_mg<D, true, false>), grid, blk, 0, s, w, z, flags, d, par, first, accuracy, max_iter, os);
-  else if (os) hipLaunchKernelGGL((cg_direction_mg<D, false, true>), grid, blk, 0, s, w, z, flags, d, par, first, accuracy, max_iter, os);
-  else hipLaunchKernelGGL((cg_direction_mg<D, false, false>), grid, blk, 0, s, w, z, flags, d, par, first, accuracy, max_iter, os);
+  hipLaunchKernelGGL((cg_direction_kernel<D, MASKED, OPEN>), grid, blk, 0, s, w, z, nullptr, flags, d, (int)(k & 1), k == 0 ? 1 : 0, accuracy,
+                     max_iter, os);
   return df::launched(fn);
 }
 
 template <int D>
 int update_mg(const char* fn, float* pressure, PWs w, const uint8_t* flags, PDims d, int64_t k, hipStream_t s) {
   const dim3 grid(static_cast<unsigned>(static_cast<int64_t>(d.nblk) * d.B)), blk(kThreads);
-  if (flags) hipLaunchKernelGGL((cg_update_mg<D, true>), grid, blk, 0, s, pressure, w, flags, d, (int)(k & 1));
-  else hipLaunchKernelGGL((cg_update_mg<D, false>), grid, blk, 0, s, pressure, w, flags, d, (int)(k & 1));
+  const GfWs none{nullptr, nullptr};
+  if (flags) hipLaunchKernelGGL((cg_update_kernel<D, true, kLeaveMg>), grid, blk, 0, s, pressure, w, none, flags, d, (int)(k & 1));
+  else hipLaunchKernelGGL((cg_update_kernel<D, false, kLeaveMg>), grid, blk, 0, s, pressure, w, none, flags, d, (int)(k & 1));
   return df::launched(fn);
 }
 
@@ -591,7 +504,7 @@ int df_mg_build(void* hierarchy, int64_t hierarchy_bytes, const uint8_t* flags, 
   MgPlan p;
   if (int e = mg_block(fn, dim, B, Z, Y, X, hierarchy, hierarchy_bytes, &p)) return e;
   if (int e = mg_bnd_ok(fn, dim, Z, Y, X, bnd)) return e;
-  if (int e = mg_open_ok(fn, dim, open_sides)) return e;
+  if (int e = check_open(fn, dim, open_sides)) return e;
   DF_REQUIRE(!flags || apart(flags, B * Z * Y * X, hierarchy, 4 * p.floats), DF_EINVAL, "%s: the flags overlap the hierarchy", fn);
   return dim == 2 ? mg_build<2>(fn, p, flags, bnd, open_sides, df::as_stream(stream)) : mg_build<3>(fn, p, flags, bnd, open_sides, df::as_stream(stream));
 }
@@ -616,7 +529,7 @@ int df_pressure_mg_precondition(void* hierarchy, int64_t hierarchy_bytes, void* 
   PDims d;
   if (int e = mg_block(fn, dim, B, Z, Y, X, hierarchy, hierarchy_bytes, &p)) return e;
   if (int e = mg_alpha_ok(fn, alpha)) return e;
-  if (int e = mg_ws(fn, ws, ws_bytes, p, hierarchy, &d)) return e;
+  if (int e = mg_ws(fn, ws, ws_bytes, p, hierarchy, 0, &d)) return e;
   DF_REQUIRE(k >= -1, DF_EINVAL, "%s: iteration %lld", fn, (long long)k);
   const PWs w = carve(ws, B, d.n, d.nblk);
   const CgState* st = k < 0 ? nullptr : w.state[(k & 1) ^ 1];   // the record direction(k) wrote and update(k) read
@@ -632,16 +545,14 @@ int df_pressure_cg_direction_mg(void* ws, int64_t ws_bytes, void* hierarchy, int
   PDims d;
   if (int e = mg_block(fn, dim, B, Z, Y, X, hierarchy, hierarchy_bytes, &p)) return e;
   if (int e = mg_bnd_ok(fn, dim, Z, Y, X, bnd)) return e;
-  if (int e = mg_open_ok(fn, dim, open_sides)) return e;
-  if (int e = mg_ws(fn, ws, ws_bytes, p, hierarchy, &d)) return e;
-  d.bnd = bnd;
-  DF_REQUIRE(k >= 0 && max_iter >= 0 && max_iter < (1ll << 31), DF_EINVAL, "%s: iteration %lld of at most %lld", fn, (long long)k,
-             (long long)max_iter);
-  DF_REQUIRE(accuracy >= 0.0f, DF_EINVAL, "%s: accuracy must be >= 0", fn);
-  DF_REQUIRE(!flags || apart(flags, B * d.n, ws, 4 * ws_floats(B, d.n, d.nblk)), DF_EINVAL, "%s: the workspace overlaps the flags", fn);
+  if (int e = check_open(fn, dim, open_sides)) return e;
+  if (int e = mg_ws(fn, ws, ws_bytes, p, hierarchy, bnd, &d)) return e;
+  if (int e = check_iter(fn, k, accuracy, max_iter)) return e;
+  if (int e = check_apart(fn, ws, ws_bytes_needed(d), flags, B * d.n, "flags")) return e;
   const PWs w = carve(ws, B, d.n, d.nblk);
-  return dim == 2 ? direction_mg<2>(fn, w, p.lev[0].r, flags, d, k, accuracy, (int)max_iter, open_sides, df::as_stream(stream))
-                  : direction_mg<3>(fn, w, p.lev[0].r, flags, d, k, accuracy, (int)max_iter, open_sides, df::as_stream(stream));
+  hipStream_t s = df::as_stream(stream);
+  return dim == 2 ? DF_OPEN_CALL(direction_mg, 2, fn, w, p.lev[0].r, flags, d, k, accuracy, (int)max_iter, s)
+                  : DF_OPEN_CALL(direction_mg, 3, fn, w, p.lev[0].r, flags, d, k, accuracy, (int)max_iter, s);
 }
 
 int df_pressure_cg_update_mg(float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int dim, int64_t B, int64_t Z, int64_t Y,
@@ -652,12 +563,11 @@ int df_pressure_cg_update_mg(float* pressure, void* ws, int64_t ws_bytes, const 
   PDims d;
   if (int e = mg_plan(fn, dim, B, Z, Y, X, nullptr, &p)) return e;
   if (int e = mg_bnd_ok(fn, dim, Z, Y, X, bnd)) return e;
-  if (int e = mg_ws(fn, ws, ws_bytes, p, nullptr, &d)) return e;
-  d.bnd = bnd;
+  if (int e = mg_ws(fn, ws, ws_bytes, p, nullptr, bnd, &d)) return e;
   DF_REQUIRE(k >= 0, DF_EINVAL, "%s: iteration %lld", fn, (long long)k);
-  const int64_t need = 4 * ws_floats(B, d.n, d.nblk);
+  const int64_t need = ws_bytes_needed(d);
   DF_REQUIRE(aligned4(pressure), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  DF_REQUIRE(apart(pressure, 4 * B * d.n, ws, need), DF_EINVAL, "%s: the workspace overlaps the pressure", fn);
+  if (int e = check_apart(fn, ws, need, pressure, 4 * B * d.n, "pressure")) return e;
   DF_REQUIRE(!flags || (apart(flags, B * d.n, ws, need) && apart(flags, B * d.n, pressure, 4 * B * d.n)), DF_EINVAL,
              "%s: the flags overlap the workspace or the pressure", fn);
   const PWs w = carve(ws, B, d.n, d.nblk);

@@ -37,17 +37,19 @@
 //   sphere_source     the source stamp with one sphere per batch entry, the centres read from device memory.
 //   diffusion         cgSolveDiffusion of the viscous liquid scene (scene/liquid3_vis.py:281), restated from memory as the header says: the
 //                     same CG over the B*D components of a velocity, each its own system (I + alpha * Laplacian on the interior cells,
-//                     the band Dirichlet data).  diffuse_init de-interleaves into planar x, r, p; the DIFFUSE instantiation of the
+//                     the band Dirichlet data).  diffuse_init de-interleaves into planar x, r, p; the kRowDiffuse instantiation of the
 //                     direction kernel reads the entry's alpha from device memory; the update kernel is the pressure solve's;
 //                     diffuse_finish interleaves x back.  The component reads of init (stride D) and the component gathers of finish
 //                     (D planes) are each coalesced along x within a plane; every other pass is planar.
 //
 //   ghost fluid       the `_gf` entry points: the liquid rows with the surface where phi = 0 between a liquid cell and an air neighbour
 //                     (mantaflow's solvePressure(phi=), restated from memory as the header says; parity is with tests/liquid_gf_ref.py).
-//                     New kernels, not instantiations of the ones above: init also writes diag (1 per liquid neighbour, 1/theta per
-//                     air neighbour) and z = r / diag behind the plain workspace, direction and update run the Jacobi-preconditioned
-//                     iteration with r.z in the place of r.r, the correction puts the ghost value on the air side of a surface face.
-//                     The loop, the partials, the state words and df_pressure_status are the plain solve's.
+//                     Init and correction are kernels of their own: init also writes diag (1 per liquid neighbour, 1/theta per air
+//                     neighbour) and z = r / diag behind the plain workspace, the correction puts the ghost value on the air side of a
+//                     surface face.  Direction and update are the kRowDiag / kLeaveJacobi instantiations of the kernels above: the
+//                     Jacobi-preconditioned iteration with r.z in the place of r.r.  The loop, the partials, the state words and
+//                     df_pressure_status are the plain solve's.
+//   The two kernels of the iteration and the checks of the solve entry points live in smoke_common.hpp; multigrid.hip launches them too.
 //
 // Float -> int conversions are taken only of values already known to be inside the grid (advect_common.hpp).
 #include "advect_common.hpp"
@@ -68,17 +70,15 @@ using dfadv::hi_bit;
 using dfadv::interp;
 using dfadv::kFluid;
 using dfadv::lo_bit;
+using dfadv::open_hi;
+using dfadv::open_lo;
 using dfst::kThreads;
 using dfst::xcd_block;
 
 template <int D>
 struct VelRec { float v[D]; };
 
-// ---- open sides ----------------------------------------------------------------------------------------------------------------------------
-// open_sides `os`: bit 2a = the low side of axis a is open, bit 2a + 1 = its high side (the order of the flags byte's neighbour bits)
-__device__ __forceinline__ bool open_lo(int os, int a) { return ((os >> (2 * a)) & 1) != 0; }
-__device__ __forceinline__ bool open_hi(int os, int a) { return ((os >> (2 * a + 1)) & 1) != 0; }
-
+// ---- open sides (open_lo / open_hi: advect_common.hpp) ---------------------------------------------------------------------------------------
 // a band cell is open when, on every axis where its index lies outside [bnd, extent - bnd), the side it lies on is open (an edge or a
 // corner shared with a closed side stays wall)
 template <int D>
@@ -270,7 +270,19 @@ __global__ __launch_bounds__(kThreads) void wall_buoyancy_dev_kernel(const float
 }
 
 // ---- pressure projection ---------------------------------------------------------------------------------------------------------------------
-// PDims, CgState, pdecode, block_reduce, entry_reduce, PWs, ws_floats and carve live in smoke_common.hpp (multigrid.hip shares them)
+// PDims, CgState, pdecode, the reductions, PWs and the iteration itself (cg_direction_kernel, cg_update_kernel) live in smoke_common.hpp
+// (multigrid.hip shares them)
+
+// the right-hand side b = -div u of fluid cell g (its high faces are the low faces of cells inside the grid)
+template <int D>
+__device__ __forceinline__ float neg_divergence(const float* __restrict__ vel, int64_t g, const PDims& d) {
+  const int64_t st[3] = {D, static_cast<int64_t>(d.X) * D, static_cast<int64_t>(d.X) * d.Y * D};
+  const float* v = vel + g * D;
+  float div = v[st[0]] - v[0];
+  div = div + (v[st[1] + 1] - v[1]);
+  if (D == 3) div = div + (v[st[2] + 2] - v[2]);
+  return -div;
+}
 
 template <int D, bool MASKED>
 __global__ __launch_bounds__(kThreads) void pressure_init_kernel(const float* __restrict__ vel, float* __restrict__ x,
@@ -279,14 +291,7 @@ __global__ __launch_bounds__(kThreads) void pressure_init_kernel(const float* __
   const PCell c = pdecode<D, MASKED>(d, flags);
   const int64_t g = static_cast<int64_t>(c.e) * d.n + c.cell;
   float b = 0.0f;
-  if (c.interior) {
-    const int64_t st[3] = {D, static_cast<int64_t>(d.X) * D, static_cast<int64_t>(d.X) * d.Y * D};
-    const float* v = vel + g * D;
-    float div = v[st[0]] - v[0];
-    div = div + (v[st[1] + 1] - v[1]);
-    if (D == 3) div = div + (v[st[2] + 2] - v[2]);
-    b = -div;
-  }
+  if (c.interior) b = neg_divergence<D>(vel, g, d);
   if (c.cell < d.n) {
     x[g] = 0.0f; w.r[g] = b; w.p[0][g] = b; w.p[1][g] = 0.0f; w.q[g] = 0.0f;
   }
@@ -296,93 +301,6 @@ __global__ __launch_bounds__(kThreads) void pressure_init_kernel(const float* __
     w.rr_part[static_cast<int64_t>(c.e) * d.nblk + c.j] = rr;
     w.mx_part[static_cast<int64_t>(c.e) * d.nblk + c.j] = mx;
   }
-}
-
-// OPEN: p = 0 in open cells (Dirichlet), so an open neighbour counts in n_c and adds nothing to the sum
-// LIQUID (with MASKED; "fluid" reads "liquid"): p = 0 in air cells, so n_c counts every neighbour that is interior by its index, as
-// the unmasked path does, while the sums run over the liquid neighbours of the flags byte
-// DIFFUSE (unmasked, closed): the entries are the B*D (entry, component) pairs of a velocity, A = I + alpha * (2D - neighbours in I), the
-// alpha of pair e is dalpha[e / D]; the sum is the one of the unmasked path (the direction is 0 off I)
-template <int D, bool MASKED, bool OPEN, bool LIQUID = false, bool DIFFUSE = false>
-__global__ __launch_bounds__(kThreads) void cg_direction_kernel(PWs w, const uint8_t* __restrict__ flags, PDims d, int par, int first,
-                                                                float accuracy, int max_iter, int os, const float* __restrict__ dalpha) {
-  __shared__ float lds[4];
-  const PCell c = pdecode<D, MASKED>(d, flags);
-  const bool writer = c.j == 0 && threadIdx.x == 0;
-  CgState s;
-  if (first) s = CgState{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1, 0, 0};
-  else s = w.state[par][c.e];
-  if (!s.active) {                                      // frozen: carry the record over, touch nothing else
-    if (writer) w.state[par ^ 1][c.e] = s;
-    return;
-  }
-  const int64_t po = static_cast<int64_t>(c.e) * d.nblk;
-  const float rr = entry_reduce<false>(w.rr_part + po, d.nblk, lds);
-  const float mx = entry_reduce<true>(w.mx_part + po, d.nblk, lds);
-  const bool act = mx > accuracy && rr > 0.0f && s.iters < max_iter;
-  const float beta = first ? 0.0f : rr / s.rr;          // s.rr > 0: the entry was active
-  if (writer) w.state[par ^ 1][c.e] = CgState{rr, mx, s.alpha, act ? beta : s.beta, s.pq, act ? 1 : 0, s.iters + (act ? 1 : 0), 0};
-  if (!act) return;
-  float pq = 0.0f;
-  if (c.interior) {
-    const int64_t eo = static_cast<int64_t>(c.e) * d.n;
-    const float* __restrict__ r = w.r + eo;
-    const float* __restrict__ po_ = w.p[par] + eo;
-    const int64_t st[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
-    const int ext[3] = {d.X, d.Y, d.Z};
-    const float pc = r[c.cell] + beta * po_[c.cell];
-    float sum = 0.0f;
-    int cnt = 0;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-      const bool lo = MASKED ? (c.fl & lo_bit(a)) != 0u : c.p[a] > d.bnd;
-      const bool hi = MASKED ? (c.fl & hi_bit(a)) != 0u : c.p[a] + 1 < ext[a] - d.bnd;
-      if (lo) { const int64_t nb = c.cell - st[a]; sum += r[nb] + beta * po_[nb]; if (!MASKED) ++cnt; }
-      if (hi) { const int64_t nb = c.cell + st[a]; sum += r[nb] + beta * po_[nb]; if (!MASKED) ++cnt; }
-    }
-    if (MASKED) cnt = __popc((c.fl >> 1) & ((1u << (2 * D)) - 1u));   // n_c: the neighbour bits of the D axes, those the loop visited
-    if (LIQUID) {
-      cnt = 0;
-#pragma unroll
-      for (int a = 0; a < D; ++a) cnt += (c.p[a] > d.bnd ? 1 : 0) + (c.p[a] + 1 < ext[a] - d.bnd ? 1 : 0);
-    }
-    if (OPEN) {
-#pragma unroll
-      for (int a = 0; a < D; ++a) cnt += ((c.p[a] == d.bnd && open_lo(os, a)) ? 1 : 0) + ((c.p[a] + 1 == ext[a] - d.bnd && open_hi(os, a)) ? 1 : 0);
-    }
-    float qv = static_cast<float>(cnt) * pc - sum;
-    if (DIFFUSE) qv = pc + dalpha[c.e / D] * (static_cast<float>(2 * D) * pc - sum);
-    w.p[par ^ 1][eo + c.cell] = pc;
-    w.q[eo + c.cell] = qv;
-    pq = pc * qv;
-  }
-  pq = block_reduce<false>(pq, lds);
-  if (threadIdx.x == 0) w.pq_part[po + c.j] = pq;
-}
-
-template <int D, bool MASKED>
-__global__ __launch_bounds__(kThreads) void cg_update_kernel(float* __restrict__ x, PWs w, const uint8_t* __restrict__ flags, PDims d, int par) {
-  __shared__ float lds[4];
-  const PCell c = pdecode<D, MASKED>(d, flags);
-  CgState* s = w.state[par ^ 1] + c.e;                  // what direction(k) has just written
-  if (!s->active) return;
-  const float rr_old = s->rr;
-  const int64_t po = static_cast<int64_t>(c.e) * d.nblk;
-  const float pq = entry_reduce<false>(w.pq_part + po, d.nblk, lds);
-  const float alpha = pq > 0.0f ? rr_old / pq : 0.0f;
-  if (c.j == 0 && threadIdx.x == 0) { s->alpha = alpha; s->pq = pq; }   // words no workgroup of this launch reads
-  float rr = 0.0f, mx = 0.0f;
-  if (c.interior) {
-    const int64_t g = static_cast<int64_t>(c.e) * d.n + c.cell;
-    x[g] = x[g] + alpha * w.p[par ^ 1][g];
-    const float rn = w.r[g] - alpha * w.q[g];
-    w.r[g] = rn;
-    rr = rn * rn;
-    mx = fabsf(rn);
-  }
-  rr = block_reduce<false>(rr, lds);
-  mx = block_reduce<true>(mx, lds);
-  if (threadIdx.x == 0) { w.rr_part[po + c.j] = rr; w.mx_part[po + c.j] = mx; }
 }
 
 // one workgroup: the number of active entries (an integer sum: order-free) and, if asked for, every entry's iteration count
@@ -480,10 +398,6 @@ __device__ __forceinline__ float gf_inv_theta(float pi, float pa, float gf_clamp
   return 1.0f / theta;
 }
 
-struct GfWs {
-  float *diag, *z;
-};
-
 // the two arrays of the ghost-fluid path lie behind the workspace of the plain solve (df_pressure_status finds its words unchanged)
 GfWs carve_gf(void* ws, int64_t B, int64_t n, int64_t nblk) {
   float* f = static_cast<float*>(ws) + ws_floats(B, n, nblk);
@@ -501,12 +415,7 @@ __global__ __launch_bounds__(kThreads) void pressure_init_gf(const float* __rest
   const int64_t g = static_cast<int64_t>(c.e) * d.n + c.cell;
   float b = 0.0f, dg = 1.0f, z = 0.0f;
   if (c.interior) {
-    const int64_t st[3] = {D, static_cast<int64_t>(d.X) * D, static_cast<int64_t>(d.X) * d.Y * D};
-    const float* v = vel + g * D;
-    float div = v[st[0]] - v[0];
-    div = div + (v[st[1] + 1] - v[1]);
-    if (D == 3) div = div + (v[st[2] + 2] - v[2]);
-    b = -div;
+    b = neg_divergence<D>(vel, g, d);
     const int64_t sc[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
     const int ext[3] = {d.X, d.Y, d.Z};
     const float pi = phi[g];
@@ -530,79 +439,6 @@ __global__ __launch_bounds__(kThreads) void pressure_init_gf(const float* __rest
     w.rr_part[static_cast<int64_t>(c.e) * d.nblk + c.j] = rz;
     w.mx_part[static_cast<int64_t>(c.e) * d.nblk + c.j] = mx;
   }
-}
-
-// cg_direction_kernel for the Jacobi-preconditioned iteration: the `rr` partials and CgState::rr hold r.z, p = z + beta * p_old,
-// q = diag * p - (sum over the liquid neighbours); the decision reads max|r| of the UNscaled residual, as the plain solve does
-template <int D>
-__global__ __launch_bounds__(kThreads) void cg_direction_gf(PWs w, GfWs gw, const uint8_t* __restrict__ flags, PDims d, int par, int first,
-                                                            float accuracy, int max_iter) {
-  __shared__ float lds[4];
-  const PCell c = pdecode<D, true>(d, flags);
-  const bool writer = c.j == 0 && threadIdx.x == 0;
-  CgState s;
-  if (first) s = CgState{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1, 0, 0};
-  else s = w.state[par][c.e];
-  if (!s.active) {                                      // frozen: carry the record over, touch nothing else
-    if (writer) w.state[par ^ 1][c.e] = s;
-    return;
-  }
-  const int64_t po = static_cast<int64_t>(c.e) * d.nblk;
-  const float rz = entry_reduce<false>(w.rr_part + po, d.nblk, lds);
-  const float mx = entry_reduce<true>(w.mx_part + po, d.nblk, lds);
-  const bool act = mx > accuracy && rz > 0.0f && s.iters < max_iter;
-  const float beta = first ? 0.0f : rz / s.rr;          // s.rr > 0: the entry was active
-  if (writer) w.state[par ^ 1][c.e] = CgState{rz, mx, s.alpha, act ? beta : s.beta, s.pq, act ? 1 : 0, s.iters + (act ? 1 : 0), 0};
-  if (!act) return;
-  float pq = 0.0f;
-  if (c.interior) {
-    const int64_t eo = static_cast<int64_t>(c.e) * d.n;
-    const float* __restrict__ z = gw.z + eo;
-    const float* __restrict__ po_ = w.p[par] + eo;
-    const int64_t st[3] = {1, d.X, static_cast<int64_t>(d.X) * d.Y};
-    const float pc = z[c.cell] + beta * po_[c.cell];
-    float sum = 0.0f;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-      if (c.fl & lo_bit(a)) { const int64_t nb = c.cell - st[a]; sum += z[nb] + beta * po_[nb]; }
-      if (c.fl & hi_bit(a)) { const int64_t nb = c.cell + st[a]; sum += z[nb] + beta * po_[nb]; }
-    }
-    const float qv = gw.diag[eo + c.cell] * pc - sum;
-    w.p[par ^ 1][eo + c.cell] = pc;
-    w.q[eo + c.cell] = qv;
-    pq = pc * qv;
-  }
-  pq = block_reduce<false>(pq, lds);
-  if (threadIdx.x == 0) w.pq_part[po + c.j] = pq;
-}
-
-// cg_update_kernel with z = r / diag written beside r, and r.z for r.r in the partials
-template <int D>
-__global__ __launch_bounds__(kThreads) void cg_update_gf(float* __restrict__ x, PWs w, GfWs gw, const uint8_t* __restrict__ flags, PDims d,
-                                                         int par) {
-  __shared__ float lds[4];
-  const PCell c = pdecode<D, true>(d, flags);
-  CgState* s = w.state[par ^ 1] + c.e;                  // what direction(k) has just written
-  if (!s->active) return;
-  const float rz_old = s->rr;
-  const int64_t po = static_cast<int64_t>(c.e) * d.nblk;
-  const float pq = entry_reduce<false>(w.pq_part + po, d.nblk, lds);
-  const float alpha = pq > 0.0f ? rz_old / pq : 0.0f;
-  if (c.j == 0 && threadIdx.x == 0) { s->alpha = alpha; s->pq = pq; }   // words no workgroup of this launch reads
-  float rz = 0.0f, mx = 0.0f;
-  if (c.interior) {
-    const int64_t g = static_cast<int64_t>(c.e) * d.n + c.cell;
-    x[g] = x[g] + alpha * w.p[par ^ 1][g];
-    const float rn = w.r[g] - alpha * w.q[g];
-    const float zn = rn / gw.diag[g];
-    w.r[g] = rn;
-    gw.z[g] = zn;
-    rz = rn * zn;
-    mx = fabsf(rn);
-  }
-  rz = block_reduce<false>(rz, lds);
-  mx = block_reduce<true>(mx, lds);
-  if (threadIdx.x == 0) { w.rr_part[po + c.j] = rz; w.mx_part[po + c.j] = mx; }
 }
 
 // the correction with the ghost value on the air side of a surface face: between interior cells c and c - e_a, both liquid:
@@ -671,9 +507,7 @@ __global__ __launch_bounds__(kThreads) void sphere_source_kernel(const float* de
   out[idx] = s <= radius * radius ? value : density[idx];   // a NaN centre compares false: nothing is stamped
 }
 
-// ---- host side -----------------------------------------------------------------------------------------------------------------------------
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
+// ---- host side (aligned4, check_ws, check_apart, check_open, check_iter, DF_OPEN_CALL: smoke_common.hpp) --------------------------------------
 int check_dims(const char* fn, int dim, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd) {
   DF_REQUIRE(B > 0 && Z > 0 && Y > 0 && X > 0, DF_EINVAL, "%s: non-positive extent", fn);
   DF_REQUIRE(bnd >= 1, DF_EINVAL, "%s: boundary width must be >= 1 (got %d)", fn, bnd);
@@ -702,30 +536,6 @@ int pplan(const char* fn, int dim, int64_t B, int64_t Z, int64_t Y, int64_t X, i
   DF_REQUIRE(nblk * B < (1ll << 31), DF_ESHAPE, "%s: extent too large", fn);
   *d = PDims{n, (int)nblk, (int)B, (int)Z, (int)Y, (int)X, bnd};
   *grid = static_cast<unsigned>(nblk * B);
-  return DF_OK;
-}
-
-int check_ws(const char* fn, const void* ws, int64_t ws_bytes, const PDims& d) {
-  DF_REQUIRE(ws, DF_EINVAL, "%s: null workspace", fn);
-  DF_REQUIRE(aligned4(ws), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  const int64_t need = 4 * ws_floats(d.B, d.n, d.nblk);
-  DF_REQUIRE(ws_bytes >= need, DF_EWORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes, (long long)need);
-  return DF_OK;
-}
-
-// the workspace (the `need`ed part of it) must not share a byte with an array the kernels read or write beside it
-int check_apart(const char* fn, const void* ws, const PDims& d, const void* p, int64_t bytes, const char* what) {
-  if (!p) return DF_OK;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(ws), b = reinterpret_cast<uintptr_t>(p);
-  const uintptr_t na = static_cast<uintptr_t>(4 * ws_floats(d.B, d.n, d.nblk)), nb = static_cast<uintptr_t>(bytes);
-  DF_REQUIRE(a + na <= b || b + nb <= a, DF_EINVAL, "%s: the workspace overlaps the %s", fn, what);
-  return DF_OK;
-}
-
-// open_sides of an `_open` entry point: bits 0..5, and no z bit in 2-D
-int check_open(const char* fn, int dim, int open_sides) {
-  DF_REQUIRE(open_sides >= 0 && open_sides <= 63, DF_EINVAL, "%s: open_sides must be in 0..63 (got %d)", fn, open_sides);
-  DF_REQUIRE(dim == 3 || open_sides < 16, DF_EINVAL, "%s: open_sides %d opens a z side of a 2-D grid", fn, open_sides);
   return DF_OK;
 }
 
@@ -812,50 +622,60 @@ int pressure_init(const char* fn, const float* vel, float* pressure, void* ws, i
   unsigned grid;
   if (int e = pplan(fn, D, B, Z, Y, X, bnd, &d, &grid)) return e;
   if (int e = check_ws(fn, ws, ws_bytes, d)) return e;
+  const int64_t need = ws_bytes_needed(d);
   DF_REQUIRE(static_cast<const void*>(pressure) != static_cast<const void*>(vel), DF_EINVAL,
              "%s: the pressure must not be the velocity (it is read at a neighbour)", fn);
-  if (int e = check_apart(fn, ws, d, vel, 4 * d.n * B * D, "velocity")) return e;
-  if (int e = check_apart(fn, ws, d, pressure, 4 * d.n * B, "pressure")) return e;
+  if (int e = check_apart(fn, ws, need, vel, 4 * d.n * B * D, "velocity")) return e;
+  if (int e = check_apart(fn, ws, need, pressure, 4 * d.n * B, "pressure")) return e;
   if (int e = check_flags<MASKED>(fn, flags, d.n * B, pressure, 4 * d.n * B, "pressure")) return e;
-  if (MASKED) if (int e = check_apart(fn, ws, d, flags, d.n * B, "flags")) return e;
+  if (MASKED) if (int e = check_apart(fn, ws, need, flags, d.n * B, "flags")) return e;
   DF_REQUIRE(aligned4(vel) && aligned4(pressure), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
   hipLaunchKernelGGL((pressure_init_kernel<D, MASKED>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), vel, pressure, flags,
                      carve(ws, B, d.n, d.nblk), d);
   return df::launched(fn);
 }
 
-template <int D, bool MASKED, bool OPEN = false, bool LIQUID = false, bool DIFFUSE = false>
+// the floats of the ghost-fluid solve behind the plain workspace: diag and z (carve_gf)
+int64_t gf_floats(const PDims& d) { return 2 * static_cast<int64_t>(d.B) * d.n; }
+
+// ROW = kRowDiag is the ghost-fluid solve (Jacobi: the direction from z, diag the row's coefficient); kRowDiffuse reads `dalpha`
+template <int D, bool MASKED, bool OPEN = false, bool LIQUID = false, CgRow ROW = kRowCount>
 int cg_direction(const char* fn, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
                  int64_t k, float accuracy, int64_t max_iter, df_stream_t stream, int os = 0, const float* dalpha = nullptr) {
   PDims d;
   unsigned grid;
   if (int e = pplan(fn, D, B, Z, Y, X, bnd, &d, &grid)) return e;
-  if (int e = check_ws(fn, ws, ws_bytes, d)) return e;
-  DF_REQUIRE(k >= 0 && max_iter >= 0 && max_iter < (1ll << 31), DF_EINVAL, "%s: iteration %lld of at most %lld", fn, (long long)k,
-             (long long)max_iter);
-  DF_REQUIRE(accuracy >= 0.0f, DF_EINVAL, "%s: accuracy must be >= 0", fn);
+  const int64_t extra = ROW == kRowDiag ? gf_floats(d) : 0;
+  if (int e = check_ws(fn, ws, ws_bytes, d, extra)) return e;
+  if (int e = check_iter(fn, k, accuracy, max_iter)) return e;
   if (int e = check_flags<MASKED>(fn, flags, d.n * B, nullptr, 0, "")) return e;
-  if (MASKED) if (int e = check_apart(fn, ws, d, flags, d.n * B, "flags")) return e;
-  hipLaunchKernelGGL((cg_direction_kernel<D, MASKED, OPEN, LIQUID, DIFFUSE>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream),
-                     carve(ws, B, d.n, d.nblk), flags, d, (int)(k & 1), k == 0 ? 1 : 0, accuracy, (int)max_iter, os, dalpha);
+  if (MASKED) if (int e = check_apart(fn, ws, ws_bytes_needed(d, extra), flags, d.n * B, "flags")) return e;
+  const PWs w = carve(ws, B, d.n, d.nblk);
+  const GfWs gw = carve_gf(ws, B, d.n, d.nblk);
+  hipLaunchKernelGGL((cg_direction_kernel<D, MASKED, OPEN, LIQUID, ROW>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), w,
+                     ROW == kRowDiag ? gw.z : w.r, ROW == kRowDiag ? gw.diag : dalpha, flags, d, (int)(k & 1), k == 0 ? 1 : 0, accuracy,
+                     (int)max_iter, os);
   return df::launched(fn);
 }
 
-template <int D, bool MASKED>
+// LEAVE = kLeaveJacobi is the ghost-fluid solve
+template <int D, bool MASKED, CgLeave LEAVE = kLeavePlain>
 int cg_update(const char* fn, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X,
               int bnd, int64_t k, df_stream_t stream) {
   DF_REQUIRE(pressure, DF_EINVAL, "%s: null pressure", fn);
   PDims d;
   unsigned grid;
   if (int e = pplan(fn, D, B, Z, Y, X, bnd, &d, &grid)) return e;
-  if (int e = check_ws(fn, ws, ws_bytes, d)) return e;
+  const int64_t extra = LEAVE == kLeaveJacobi ? gf_floats(d) : 0, need = ws_bytes_needed(d, extra);
+  if (int e = check_ws(fn, ws, ws_bytes, d, extra)) return e;
   DF_REQUIRE(k >= 0, DF_EINVAL, "%s: iteration %lld", fn, (long long)k);
-  if (int e = check_apart(fn, ws, d, pressure, 4 * d.n * B, "pressure")) return e;
+  if (int e = check_apart(fn, ws, need, pressure, 4 * d.n * B, "pressure")) return e;
   if (int e = check_flags<MASKED>(fn, flags, d.n * B, pressure, 4 * d.n * B, "pressure")) return e;
-  if (MASKED) if (int e = check_apart(fn, ws, d, flags, d.n * B, "flags")) return e;
+  if (MASKED) if (int e = check_apart(fn, ws, need, flags, d.n * B, "flags")) return e;
   DF_REQUIRE(aligned4(pressure), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  hipLaunchKernelGGL((cg_update_kernel<D, MASKED>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), pressure, carve(ws, B, d.n, d.nblk),
-                     flags, d, (int)(k & 1));
+  hipLaunchKernelGGL((cg_update_kernel<D, MASKED, LEAVE>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), pressure,
+                     carve(ws, B, d.n, d.nblk), LEAVE == kLeaveJacobi ? carve_gf(ws, B, d.n, d.nblk) : GfWs{nullptr, nullptr}, flags, d,
+                     (int)(k & 1));
   return df::launched(fn);
 }
 
@@ -910,19 +730,13 @@ template <int D>
 int dplan(const char* fn, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, PDims* d, unsigned* grid, float** x) {
   DF_REQUIRE(B > 0 && B < (1 << 24) / D, B > 0 ? DF_ESHAPE : DF_EINVAL, "%s: %s", fn, B > 0 ? "extent too large" : "non-positive extent");
   if (int e = pplan(fn, D, B * D, Z, Y, X, bnd, d, grid)) return e;
-  DF_REQUIRE(ws, DF_EINVAL, "%s: null workspace", fn);
-  DF_REQUIRE(aligned4(ws), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  const int64_t cg = ws_floats(d->B, d->n, d->nblk), need = 4 * (cg + d->B * d->n);
-  DF_REQUIRE(ws_bytes >= need, DF_EWORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes, (long long)need);
-  *x = static_cast<float*>(ws) + cg;
+  if (int e = check_ws(fn, ws, ws_bytes, *d, d->B * d->n)) return e;
+  *x = static_cast<float*>(ws) + ws_floats(d->B, d->n, d->nblk);
   return DF_OK;
 }
 
-// an array beside the workspace shares no byte with it
-int dapart(const char* fn, const void* ws, const PDims& d, const void* p, int64_t bytes, const char* what) {
-  DF_REQUIRE(apart(ws, 4 * (ws_floats(d.B, d.n, d.nblk) + d.B * d.n), p, bytes), DF_EINVAL, "%s: the workspace overlaps the %s", fn, what);
-  return DF_OK;
-}
+// the bytes of that workspace
+int64_t dbytes(const PDims& d) { return ws_bytes_needed(d, d.B * d.n); }
 
 template <int D>
 int diffuse_init(const char* fn, const float* vel, const float* alpha, void* ws, int64_t ws_bytes, int64_t B, int64_t Z, int64_t Y, int64_t X,
@@ -932,8 +746,8 @@ int diffuse_init(const char* fn, const float* vel, const float* alpha, void* ws,
   unsigned grid;
   float* x;
   if (int e = dplan<D>(fn, ws, ws_bytes, B, Z, Y, X, bnd, &d, &grid, &x)) return e;
-  if (int e = dapart(fn, ws, d, vel, 4 * d.n * d.B, "velocity")) return e;
-  if (int e = dapart(fn, ws, d, alpha, 4 * B, "alpha")) return e;
+  if (int e = check_apart(fn, ws, dbytes(d), vel, 4 * d.n * d.B, "velocity")) return e;
+  if (int e = check_apart(fn, ws, dbytes(d), alpha, 4 * B, "alpha")) return e;
   DF_REQUIRE(aligned4(vel) && aligned4(alpha), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
   hipLaunchKernelGGL((diffuse_init_kernel<D>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), vel, alpha, x, carve(ws, d.B, d.n, d.nblk), d);
   return df::launched(fn);
@@ -947,9 +761,9 @@ int diffuse_direction(const char* fn, const float* alpha, void* ws, int64_t ws_b
   unsigned grid;
   float* x;
   if (int e = dplan<D>(fn, ws, ws_bytes, B, Z, Y, X, bnd, &d, &grid, &x)) return e;
-  if (int e = dapart(fn, ws, d, alpha, 4 * B, "alpha")) return e;
+  if (int e = check_apart(fn, ws, dbytes(d), alpha, 4 * B, "alpha")) return e;
   DF_REQUIRE(aligned4(alpha), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  return cg_direction<D, false, false, false, true>(fn, ws, ws_bytes, nullptr, d.B, Z, Y, X, bnd, k, accuracy, max_iter, stream, 0, alpha);
+  return cg_direction<D, false, false, false, kRowDiffuse>(fn, ws, ws_bytes, nullptr, d.B, Z, Y, X, bnd, k, accuracy, max_iter, stream, 0, alpha);
 }
 
 template <int D>
@@ -970,7 +784,7 @@ int diffuse_finish(const char* fn, void* ws, int64_t ws_bytes, float* out, int64
   unsigned grid;
   float* x;
   if (int e = dplan<D>(fn, ws, ws_bytes, B, Z, Y, X, bnd, &d, &grid, &x)) return e;
-  if (int e = dapart(fn, ws, d, out, 4 * d.n * d.B, "output")) return e;
+  if (int e = check_apart(fn, ws, dbytes(d), out, 4 * d.n * d.B, "output")) return e;
   DF_REQUIRE(aligned4(out), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
   const int64_t ncell = B * d.n;                        // B * nblk < 2^31 (pplan): so is ceil(ncell / kThreads)
   hipLaunchKernelGGL((diffuse_finish_kernel<D>), dim3((unsigned)ceil_div(ncell, kThreads)), dim3(kThreads), 0, df::as_stream(stream), x, out,
@@ -979,20 +793,6 @@ int diffuse_finish(const char* fn, void* ws, int64_t ws_bytes, float* out, int64
 }
 
 // ---- the ghost-fluid solve: the workspace of the plain solve, then diag and z ----
-int64_t gf_bytes(const PDims& d) { return 4 * (ws_floats(d.B, d.n, d.nblk) + 2 * static_cast<int64_t>(d.B) * d.n); }
-
-int gf_ws(const char* fn, const void* ws, int64_t ws_bytes, const PDims& d) {
-  DF_REQUIRE(ws, DF_EINVAL, "%s: null workspace", fn);
-  DF_REQUIRE(aligned4(ws), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  DF_REQUIRE(ws_bytes >= gf_bytes(d), DF_EWORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes, (long long)gf_bytes(d));
-  return DF_OK;
-}
-
-int gf_apart(const char* fn, const void* ws, const PDims& d, const void* p, int64_t bytes, const char* what) {
-  DF_REQUIRE(!p || apart(ws, gf_bytes(d), p, bytes), DF_EINVAL, "%s: the workspace overlaps the %s", fn, what);
-  return DF_OK;
-}
-
 int gf_clamp_ok(const char* fn, float gf_clamp) {
   DF_REQUIRE(gf_clamp > 0.0f && gf_clamp <= 1.0f, DF_EINVAL, "%s: gf_clamp must lie in (0, 1] (got %g)", fn, (double)gf_clamp);
   return DF_OK;
@@ -1006,52 +806,18 @@ int pressure_init_gf_(const char* fn, const float* vel, float* pressure, void* w
   PDims d;
   unsigned grid;
   if (int e = pplan(fn, D, B, Z, Y, X, bnd, &d, &grid)) return e;
-  if (int e = gf_ws(fn, ws, ws_bytes, d)) return e;
+  if (int e = check_ws(fn, ws, ws_bytes, d, gf_floats(d))) return e;
+  const int64_t need = ws_bytes_needed(d, gf_floats(d));
   DF_REQUIRE(static_cast<const void*>(pressure) != static_cast<const void*>(vel) && static_cast<const void*>(pressure) != static_cast<const void*>(phi),
              DF_EINVAL, "%s: the pressure must not be the velocity or the level set (they are read at a neighbour)", fn);
-  if (int e = gf_apart(fn, ws, d, vel, 4 * d.n * B * D, "velocity")) return e;
-  if (int e = gf_apart(fn, ws, d, pressure, 4 * d.n * B, "pressure")) return e;
-  if (int e = gf_apart(fn, ws, d, phi, 4 * d.n * B, "level set")) return e;
+  if (int e = check_apart(fn, ws, need, vel, 4 * d.n * B * D, "velocity")) return e;
+  if (int e = check_apart(fn, ws, need, pressure, 4 * d.n * B, "pressure")) return e;
+  if (int e = check_apart(fn, ws, need, phi, 4 * d.n * B, "level set")) return e;
   if (int e = check_flags<true>(fn, flags, d.n * B, pressure, 4 * d.n * B, "pressure")) return e;
-  if (int e = gf_apart(fn, ws, d, flags, d.n * B, "flags")) return e;
+  if (int e = check_apart(fn, ws, need, flags, d.n * B, "flags")) return e;
   DF_REQUIRE(aligned4(vel) && aligned4(pressure) && aligned4(phi), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
   hipLaunchKernelGGL((pressure_init_gf<D>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), vel, pressure, flags, phi,
                      carve(ws, B, d.n, d.nblk), carve_gf(ws, B, d.n, d.nblk), d, gf_clamp);
-  return df::launched(fn);
-}
-
-template <int D>
-int cg_direction_gf_(const char* fn, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
-                     int64_t k, float accuracy, int64_t max_iter, df_stream_t stream) {
-  PDims d;
-  unsigned grid;
-  if (int e = pplan(fn, D, B, Z, Y, X, bnd, &d, &grid)) return e;
-  if (int e = gf_ws(fn, ws, ws_bytes, d)) return e;
-  DF_REQUIRE(k >= 0 && max_iter >= 0 && max_iter < (1ll << 31), DF_EINVAL, "%s: iteration %lld of at most %lld", fn, (long long)k,
-             (long long)max_iter);
-  DF_REQUIRE(accuracy >= 0.0f, DF_EINVAL, "%s: accuracy must be >= 0", fn);
-  if (int e = check_flags<true>(fn, flags, d.n * B, nullptr, 0, "")) return e;
-  if (int e = gf_apart(fn, ws, d, flags, d.n * B, "flags")) return e;
-  hipLaunchKernelGGL((cg_direction_gf<D>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), carve(ws, B, d.n, d.nblk),
-                     carve_gf(ws, B, d.n, d.nblk), flags, d, (int)(k & 1), k == 0 ? 1 : 0, accuracy, (int)max_iter);
-  return df::launched(fn);
-}
-
-template <int D>
-int cg_update_gf_(const char* fn, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X,
-                  int bnd, int64_t k, df_stream_t stream) {
-  DF_REQUIRE(pressure, DF_EINVAL, "%s: null pressure", fn);
-  PDims d;
-  unsigned grid;
-  if (int e = pplan(fn, D, B, Z, Y, X, bnd, &d, &grid)) return e;
-  if (int e = gf_ws(fn, ws, ws_bytes, d)) return e;
-  DF_REQUIRE(k >= 0, DF_EINVAL, "%s: iteration %lld", fn, (long long)k);
-  if (int e = gf_apart(fn, ws, d, pressure, 4 * d.n * B, "pressure")) return e;
-  if (int e = check_flags<true>(fn, flags, d.n * B, pressure, 4 * d.n * B, "pressure")) return e;
-  if (int e = gf_apart(fn, ws, d, flags, d.n * B, "flags")) return e;
-  DF_REQUIRE(aligned4(pressure), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
-  hipLaunchKernelGGL((cg_update_gf<D>), dim3(grid), dim3(kThreads), 0, df::as_stream(stream), pressure, carve(ws, B, d.n, d.nblk),
-                     carve_gf(ws, B, d.n, d.nblk), flags, d, (int)(k & 1));
   return df::launched(fn);
 }
 
@@ -1070,11 +836,6 @@ int pressure_correct_gf_(const char* fn, const float* vel, const float* pressure
   hipLaunchKernelGGL((pressure_correct_gf<D>), dim3(nblk), dim3(kThreads), 0, df::as_stream(stream), vel, pressure, out, flags, phi, d, gf_clamp);
   return df::launched(fn);
 }
-
-// an `_open` entry point: the closed instantiation for open_sides = 0 (the same bits by construction), flags may be null (no obstacles)
-#define DF_OPEN_CALL(F, D, ...)                                                                                       \
-  (open_sides == 0 ? (flags ? F<D, true, false>(__VA_ARGS__) : F<D, false, false>(__VA_ARGS__))                      \
-                   : (flags ? F<D, true, true>(__VA_ARGS__, open_sides) : F<D, false, true>(__VA_ARGS__, open_sides)))
 
 }  // namespace
 
@@ -1145,8 +906,8 @@ int df_pressure_status(const void* ws, int64_t ws_bytes, int64_t B, int64_t Z, i
   const PDims d{Z * Y * X, (int)ceil_div(Z * Y * X, kThreads), (int)B, (int)Z, (int)Y, (int)X, 1};
   if (int e = check_ws(fn, ws, ws_bytes, d)) return e;
   DF_REQUIRE(active_count || iterations, DF_EINVAL, "%s: null outputs", fn);
-  if (int e = check_apart(fn, ws, d, active_count, 4, "active count")) return e;
-  if (int e = check_apart(fn, ws, d, iterations, 4 * B, "iteration counts")) return e;
+  if (int e = check_apart(fn, ws, ws_bytes_needed(d), active_count, 4, "active count")) return e;
+  if (int e = check_apart(fn, ws, ws_bytes_needed(d), iterations, 4 * B, "iteration counts")) return e;
   DF_REQUIRE(k >= 0, DF_EINVAL, "%s: iteration %lld", fn, (long long)k);
   DF_REQUIRE(aligned4(active_count) && aligned4(iterations), DF_EALIGN, "%s: pointers must be 4-byte aligned", fn);
   const PWs w = carve(const_cast<void*>(ws), B, d.n, d.nblk);
@@ -1323,19 +1084,19 @@ int df_pressure_init3d_gf(const float* vel, float* pressure, void* ws, int64_t w
 }
 int df_pressure_cg_direction2d_gf(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd, int64_t k,
                                   float accuracy, int64_t max_iter, df_stream_t stream) {
-  return cg_direction_gf_<2>("df_pressure_cg_direction2d_gf", ws, ws_bytes, flags, B, 1, Y, X, bnd, k, accuracy, max_iter, stream);
+  return cg_direction<2, true, false, false, kRowDiag>("df_pressure_cg_direction2d_gf", ws, ws_bytes, flags, B, 1, Y, X, bnd, k, accuracy, max_iter, stream);
 }
 int df_pressure_cg_direction3d_gf(void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd,
                                   int64_t k, float accuracy, int64_t max_iter, df_stream_t stream) {
-  return cg_direction_gf_<3>("df_pressure_cg_direction3d_gf", ws, ws_bytes, flags, B, Z, Y, X, bnd, k, accuracy, max_iter, stream);
+  return cg_direction<3, true, false, false, kRowDiag>("df_pressure_cg_direction3d_gf", ws, ws_bytes, flags, B, Z, Y, X, bnd, k, accuracy, max_iter, stream);
 }
 int df_pressure_cg_update2d_gf(float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Y, int64_t X, int bnd,
                                int64_t k, df_stream_t stream) {
-  return cg_update_gf_<2>("df_pressure_cg_update2d_gf", pressure, ws, ws_bytes, flags, B, 1, Y, X, bnd, k, stream);
+  return cg_update<2, true, kLeaveJacobi>("df_pressure_cg_update2d_gf", pressure, ws, ws_bytes, flags, B, 1, Y, X, bnd, k, stream);
 }
 int df_pressure_cg_update3d_gf(float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, int64_t B, int64_t Z, int64_t Y, int64_t X,
                                int bnd, int64_t k, df_stream_t stream) {
-  return cg_update_gf_<3>("df_pressure_cg_update3d_gf", pressure, ws, ws_bytes, flags, B, Z, Y, X, bnd, k, stream);
+  return cg_update<3, true, kLeaveJacobi>("df_pressure_cg_update3d_gf", pressure, ws, ws_bytes, flags, B, Z, Y, X, bnd, k, stream);
 }
 int df_pressure_correct2d_gf(const float* vel, const float* pressure, float* out, const uint8_t* flags, const float* phi, int64_t B, int64_t Y,
                              int64_t X, int bnd, float gf_clamp, df_stream_t stream) {
