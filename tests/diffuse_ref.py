@@ -84,9 +84,12 @@ def _dot(a, b):
     return (a * b).reshape(a.shape[0], -1).sum(axis=1, dtype=a.dtype)
 
 
-def cg(vel, alpha, bnd=1, accuracy=1e-4, max_iter=None, dtype=np.float64):
+def cg(vel, alpha, bnd=1, accuracy=1e-4, max_iter=None, dtype=np.float64, dot=None, amax=None):
     """The iteration of the header, every (entry, component) pair on its own.  Returns (vel_out [B,..,D], iterations [B,D], r [B*D,..],
-    x [B*D,..]); cells off I keep the input's bits."""
+    x [B*D,..]); cells off I keep the input's bits.  ``dot`` / ``amax``: the reductions (defaults: NumPy's sum and max); with
+    cg_ref.ordered_dot / ordered_amax and float32 the run is the kernels' twin bit for bit."""
+    dot = _dot if dot is None else dot
+    amax = lref._amax if amax is None else amax
     dtype = _type(dtype)
     B, D = vel.shape[0], vel.shape[-1]
     max_iter = default_max_iter(vel.shape[1:-1]) if max_iter is None else max_iter
@@ -103,8 +106,8 @@ def cg(vel, alpha, bnd=1, accuracy=1e-4, max_iter=None, dtype=np.float64):
     iters = np.zeros(P, np.int32)
     k = 0
     while True:
-        rr = _dot(r, r)
-        mx = np.abs(r).reshape(P, -1).max(axis=1)
+        rr = dot(r, r)
+        mx = amax(r)
         with np.errstate(invalid="ignore"):
             active = active & (mx > dtype(accuracy)) & (rr > 0) & (iters < max_iter)
         if not active.any():
@@ -113,7 +116,7 @@ def cg(vel, alpha, bnd=1, accuracy=1e-4, max_iter=None, dtype=np.float64):
             beta = np.zeros(P, dtype) if k == 0 else (rr / rr_old).astype(dtype)
             pn = (r + beta[ex] * p).astype(dtype)
             q = apply_A(pn, al, bnd)
-            pq = _dot(pn, q)
+            pq = dot(pn, q)
             step = np.where(pq > 0, rr / pq, dtype(0)).astype(dtype)
         a_ = active[ex] & inter
         x = np.where(a_, x + step[ex] * pn, x).astype(dtype)

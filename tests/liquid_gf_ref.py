@@ -186,8 +186,11 @@ def apply_A(x, liquid, diag):
     return np.where(liquid, diag * x - s, dtype(0)).astype(dtype)
 
 
-def pcg(vel, liquid, phi, bnd=1, accuracy=1e-4, max_iter=100, gf_clamp=1e-4, dtype=np.float64):
-    """The Jacobi-preconditioned iteration of the header on the liquid rows, every batch entry on its own.  Returns (x, iterations [B], r)."""
+def pcg(vel, liquid, phi, bnd=1, accuracy=1e-4, max_iter=100, gf_clamp=1e-4, dtype=np.float64, dot=None, amax=None):
+    """The Jacobi-preconditioned iteration of the header on the liquid rows, every batch entry on its own (``dot`` / ``amax`` as in
+    liquid_ref.cg).  Returns (x, iterations [B], r)."""
+    dot = ref._dot if dot is None else dot
+    amax = ref._amax if amax is None else amax
     dtype = _type(dtype)
     b = ref.rhs(vel, liquid, dtype)
     dg = diagonal(phi, liquid, bnd, gf_clamp, dtype)
@@ -199,8 +202,8 @@ def pcg(vel, liquid, phi, bnd=1, accuracy=1e-4, max_iter=100, gf_clamp=1e-4, dty
     iters = np.zeros(B, np.int32)
     k = 0
     while True:
-        rz = ref._dot(r, z)
-        mx = np.abs(r).reshape(B, -1).max(axis=1)
+        rz = dot(r, z)
+        mx = amax(r)
         active = active & (mx > dtype(accuracy)) & (rz > 0) & (iters < max_iter)
         if not active.any():
             break
@@ -208,7 +211,7 @@ def pcg(vel, liquid, phi, bnd=1, accuracy=1e-4, max_iter=100, gf_clamp=1e-4, dty
             beta = np.zeros(B, dtype) if k == 0 else (rz / rz_old).astype(dtype)
             pn = (z + beta[ex] * p).astype(dtype)
             q = apply_A(pn, liquid, dg)
-            pq = ref._dot(pn, q)
+            pq = dot(pn, q)
             alpha = np.where(pq > 0, rz / pq, dtype(0)).astype(dtype)
         a_ = active[ex]
         x = np.where(a_, x + alpha[ex] * pn, x).astype(dtype)

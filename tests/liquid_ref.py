@@ -233,8 +233,16 @@ def _dot(a, b):
     return (a * b).reshape(a.shape[0], -1).sum(axis=1, dtype=a.dtype)
 
 
-def cg(vel, liquid, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.float64):
-    """The iteration of the header on the liquid rows, every batch entry on its own.  Returns (x, iterations [B], r)."""
+def _amax(r):
+    return np.abs(r).reshape(r.shape[0], -1).max(axis=1)
+
+
+def cg(vel, liquid, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.float64, dot=None, amax=None):
+    """The iteration of the header on the liquid rows, every batch entry on its own.  Returns (x, iterations [B], r).
+    ``dot`` / ``amax``: the reductions (defaults: NumPy's sum and max); with cg_ref.ordered_dot / ordered_amax and float32 the run is the
+    kernels' twin bit for bit."""
+    dot = _dot if dot is None else dot
+    amax = _amax if amax is None else amax
     dtype = _type(dtype)
     b = rhs(vel, liquid, dtype)
     B = b.shape[0]
@@ -245,8 +253,8 @@ def cg(vel, liquid, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.float64):
     iters = np.zeros(B, np.int32)
     k = 0
     while True:
-        rr = _dot(r, r)
-        mx = np.abs(r).reshape(B, -1).max(axis=1)
+        rr = dot(r, r)
+        mx = amax(r)
         active = active & (mx > dtype(accuracy)) & (rr > 0) & (iters < max_iter)
         if not active.any():
             break
@@ -254,7 +262,7 @@ def cg(vel, liquid, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.float64):
             beta = np.zeros(B, dtype) if k == 0 else (rr / rr_old).astype(dtype)
             pn = (r + beta[ex] * p).astype(dtype)
             q = apply_A(pn, liquid, bnd)
-            pq = _dot(pn, q)
+            pq = dot(pn, q)
             alpha = np.where(pq > 0, rr / pq, dtype(0)).astype(dtype)
         a_ = active[ex]
         x = np.where(a_, x + alpha[ex] * pn, x).astype(dtype)

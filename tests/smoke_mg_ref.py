@@ -11,7 +11,7 @@ import numpy as np
 import smoke_obs_ref as oref
 import smoke_open_ref as pref
 from smoke_obs_ref import _shift, fluid_mask
-from smoke_ref import _dot
+from smoke_ref import _amax, _dot
 
 NU = 2
 COARSEST_SWEEPS = 8
@@ -140,9 +140,12 @@ def vcycle(levs, r, alpha=ALPHA, l=0):
 
 
 # ---- the iteration ---------------------------------------------------------------------------------------------------------------------------
-def pcg(vel, obstacle, bits=0, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.float64, alpha=ALPHA, precondition=True):
+def pcg(vel, obstacle, bits=0, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.float64, alpha=ALPHA, precondition=True, dot=None, amax=None):
     """smoke_open_ref.cg with z = M r: rr holds r.z, p = z + beta p; stops on the unscaled max|r|.  ``precondition=False``: z = r, the
-    plain solve.  Returns (x, iterations [B], r, broke [B]); ``broke``: the entry ended on r.z <= 0 with max|r| above the accuracy."""
+    plain solve.  Returns (x, iterations [B], r, broke [B]); ``broke``: the entry ended on r.z <= 0 with max|r| above the accuracy.
+    ``dot`` / ``amax`` as in smoke_ref.cg."""
+    dot = _dot if dot is None else dot
+    amax = _amax if amax is None else amax
     dtype = np.dtype(dtype).type
     b = pref.rhs(vel, obstacle, bnd, dtype)
     levs = hierarchy(obstacle, bnd, bits, dtype) if precondition else None
@@ -156,8 +159,8 @@ def pcg(vel, obstacle, bits=0, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.floa
     k = 0
     while True:
         z = vcycle(levs, r, alpha) if precondition else r
-        rz = _dot(r, z)
-        mx = np.abs(r).reshape(B, -1).max(axis=1)
+        rz = dot(r, z)
+        mx = amax(r)
         broke = broke | (active & (mx > dtype(accuracy)) & ~(rz > 0))
         active = active & (mx > dtype(accuracy)) & (rz > 0) & (iters < max_iter)
         if not active.any():
@@ -166,7 +169,7 @@ def pcg(vel, obstacle, bits=0, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.floa
             beta = np.zeros(B, dtype) if k == 0 else (rz / rz_old).astype(dtype)
             pn = (z + beta[ex] * p).astype(dtype)
             q = pref.apply_A(pn, obstacle, bits, bnd)
-            pq = _dot(pn, q)
+            pq = dot(pn, q)
             a_cg = np.where(pq > 0, rz / pq, dtype(0)).astype(dtype)
         a_ = active[ex]
         x = np.where(a_, x + a_cg[ex] * pn, x).astype(dtype)

@@ -246,8 +246,10 @@ def neighbour_count(obstacle, bnd=1):
     return np.where(f & 1, n, 0)
 
 
-def cg(vel, obstacle, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.float64):
-    """smoke_ref.cg on the fluid cells.  Returns (x, iterations [B], r)."""
+def cg(vel, obstacle, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.float64, dot=None, amax=None):
+    """smoke_ref.cg on the fluid cells (``dot`` / ``amax`` as there).  Returns (x, iterations [B], r)."""
+    dot = _dot if dot is None else dot
+    amax = sref._amax if amax is None else amax
     dtype = np.dtype(dtype).type
     b = rhs(vel, obstacle, bnd, dtype)
     B = b.shape[0]
@@ -258,8 +260,8 @@ def cg(vel, obstacle, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.float64):
     iters = np.zeros(B, np.int32)
     k = 0
     while True:
-        rr = _dot(r, r)
-        mx = np.abs(r).reshape(B, -1).max(axis=1)
+        rr = dot(r, r)
+        mx = amax(r)
         active = active & (mx > dtype(accuracy)) & (rr > 0) & (iters < max_iter)
         if not active.any():
             break
@@ -267,7 +269,7 @@ def cg(vel, obstacle, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.float64):
             beta = np.zeros(B, dtype) if k == 0 else (rr / rr_old).astype(dtype)
             pn = (r + beta[ex] * p).astype(dtype)
             q = apply_A(pn, obstacle, bnd)
-            pq = _dot(pn, q)
+            pq = dot(pn, q)
             alpha = np.where(pq > 0, rr / pq, dtype(0)).astype(dtype)
         a_ = active[ex]
         x = np.where(a_, x + alpha[ex] * pn, x).astype(dtype)

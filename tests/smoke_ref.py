@@ -181,8 +181,15 @@ def _dot(a, b):
     return (a * b).reshape(a.shape[0], -1).sum(axis=1, dtype=a.dtype)
 
 
-def cg(vel, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.float64):
-    """The iteration of the header, every batch entry on its own.  Returns (x, iterations [B], r)."""
+def _amax(r):
+    return np.abs(r).reshape(r.shape[0], -1).max(axis=1)
+
+
+def cg(vel, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.float64, dot=None, amax=None):
+    """The iteration of the header, every batch entry on its own.  Returns (x, iterations [B], r).
+    ``dot`` / ``amax``: the reductions (defaults: NumPy's sum and max); with cg_ref.ordered_dot / ordered_amax and
+    float32 the run is the kernels' twin bit for bit."""
+    dot = _dot if dot is None else dot
     dtype = np.dtype(dtype).type
     b = rhs(vel, bnd, dtype)
     B = b.shape[0]
@@ -193,8 +200,8 @@ def cg(vel, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.float64):
     iters = np.zeros(B, np.int32)
     k = 0
     while True:
-        rr = _dot(r, r)
-        mx = np.abs(r).reshape(B, -1).max(axis=1)
+        rr = dot(r, r)
+        mx = _amax(r) if amax is None else amax(r)
         active = active & (mx > dtype(accuracy)) & (rr > 0) & (iters < max_iter)
         if not active.any():
             break
@@ -202,7 +209,7 @@ def cg(vel, bnd=1, accuracy=1e-4, max_iter=100, dtype=np.float64):
             beta = np.zeros(B, dtype) if k == 0 else (rr / rr_old).astype(dtype)
             pn = (r + beta[ex] * p).astype(dtype)
             q = apply_A(pn, bnd)
-            pq = _dot(pn, q)
+            pq = dot(pn, q)
             alpha = np.where(pq > 0, rr / pq, dtype(0)).astype(dtype)
         a_ = active[ex]
         x = np.where(a_, x + alpha[ex] * pn, x).astype(dtype)
