@@ -9,7 +9,6 @@ import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdeepfluids_hip.so")
-TUNING_LIB_PATH = os.path.join(_HERE, "csrc", "libdeepfluids_hip_tuning.so")      # tools/ only: `use_tuning_library()`
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "deepfluids_hip.h")
 # the fused field metrics: a library and a header of their own (deepfluids_hip.h is frozen at DF_VERSION 207), bound the same way
 METRICS_LIB_PATH = os.path.join(_HERE, "csrc", "libdeepfluids_hip_metrics.so")
@@ -101,17 +100,6 @@ def declared_symbols():
     src = open(HEADER_PATH).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     return sorted(set(re.findall(r"\b(df_[a-z0-9_]+)\s*\(", src)))
-
-
-def use_tuning_library():
-    """tools/ probes only: bind the -DDF_TUNING build (instrumented kernels + the knobs of deepfluids_hip_debug.h) instead of
-    the release library.  Must be called before the first kernel call of the process."""
-    global LIB_PATH, _lib
-    if _lib is not None:
-        raise DeepFluidsHipError("use_tuning_library() must precede the first call into the library")
-    if not os.path.exists(TUNING_LIB_PATH):
-        raise DeepFluidsHipError("%s not found -- `make -C deep_fluids_amd/csrc tuning`" % TUNING_LIB_PATH)
-    LIB_PATH = TUNING_LIB_PATH
 
 
 def lib():

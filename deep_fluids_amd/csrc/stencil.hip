@@ -84,7 +84,7 @@ __global__ __launch_bounds__(kThreads) void jacobian3d_fwd_kernel(const float* _
 // voxel); the y and z neighbours are the same three float4 one row / one slice further (16-byte aligned because
 // 3*X*4 bytes is a multiple of 16).  10 global_load_dwordx4 per 4 voxels instead of 48 dword loads; all but the
 // own records are L1/L2 hits.  Results leave through the same LDS transpose -> 1 KiB-contiguous stores.
-template <bool WJ, bool WC, bool NT>
+template <bool WJ, bool WC>
 __global__ __launch_bounds__(kThreads) void jacobian3d_fwd_vec_kernel(const float* __restrict__ x, float* __restrict__ j,
                                                                       float* __restrict__ c, Dims3 dm) {
   __shared__ __attribute__((aligned(16))) float smem[(WJ ? kVoxPerBlock * 9 : 0) + (WC ? kVoxPerBlock * 3 : 0)];
@@ -161,8 +161,8 @@ __global__ __launch_bounds__(kThreads) void jacobian3d_fwd_vec_kernel(const floa
   __syncthreads();
   const int64_t left = dm.nvox - v0;
   const int64_t nv = left < kVoxPerBlock ? left : kVoxPerBlock;
-  if (WJ) flush_lds<NT>(sj, j + v0 * 9, nv * 9, tid);
-  if (WC) flush_lds<NT>(sc, c + v0 * 3, nv * 3, tid);
+  if (WJ) flush_lds<true>(sj, j + v0 * 9, nv * 9, tid);
+  if (WC) flush_lds<true>(sc, c + v0 * 3, nv * 3, tid);
 }
 
 // ---- adjoint helpers ---------------------------------------------------------------------------
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(kThreads) void jacobian3d_bwd_kernel(const float* _
 // of the quad one row up (y-1) and one slice up (z-1) (L1/L2 hits: they are other threads' own quads), the single record at x-1,
 // and on the two boundary rows / slices the few extra records by dword loads.  HBM sees every gradient byte once
 // (48 B/voxel with gj, 24 B/voxel with gc only); the 12 results per thread leave through LDS as 1 KiB-contiguous stores.
-template <bool HJ, bool HC, bool NT>
+template <bool HJ, bool HC>
 __global__ __launch_bounds__(kThreads) void jacobian3d_bwd_vec_kernel(const float* __restrict__ gj, const float* __restrict__ gc,
                                                                       float* __restrict__ gx, Dims3 dm) {
   __shared__ __attribute__((aligned(16))) float so[kVoxPerBlock * 3];
@@ -338,7 +338,7 @@ __global__ __launch_bounds__(kThreads) void jacobian3d_bwd_vec_kernel(const floa
   __syncthreads();
   const int64_t left = dm.nvox - v0;
   const int64_t nv = left < kVoxPerBlock ? left : kVoxPerBlock;
-  flush_lds<NT>(so, gx + v0 * 3, nv * 3, tid);
+  flush_lds<true>(so, gx + v0 * 3, nv * 3, tid);
 }
 
 // ---- LDS-staged adjoint (X % 4 == 0, X <= 128, ONE incoming gradient) ---------------------------------------------------------
@@ -364,7 +364,7 @@ __device__ __forceinline__ float fold_rec(const float* rec, int e) {   // G[e] o
   }
 }
 
-template <int R, bool NT>
+template <int R>
 __global__ __launch_bounds__(kThreads) void jacobian3d_bwd_lds_kernel(const float* __restrict__ g, float* __restrict__ gx, Dims3 dm) {
   constexpr int QB = kVoxPerBlock * R / 4;       // float4 per 1024-record span
   constexpr int PER = QB / kThreads;             // 9 | 3 per thread
@@ -515,7 +515,7 @@ __global__ __launch_bounds__(kThreads) void jacobian3d_bwd_lds_kernel(const floa
   __syncthreads();
   const int64_t left = dm.nvox - v0;
   const int64_t nv = left < kVoxPerBlock ? left : kVoxPerBlock;
-  flush_lds<NT>(sZ, gx + v0 * 3, nv * 3, tid);
+  flush_lds<true>(sZ, gx + v0 * 3, nv * 3, tid);
 }
 
 __global__ __launch_bounds__(kThreads) void divergence3d_kernel(const float* __restrict__ x, float* __restrict__ d,
@@ -642,16 +642,6 @@ __global__ __launch_bounds__(kThreads) void divergence2d_kernel(const float* __r
   d[o] = (x[(v + 1) * 2 + 0] - x[v * 2 + 0]) + (x[(v + X) * 2 + 1] - x[v * 2 + 1]);
 }
 
-#ifdef DF_TUNING      // knobs of the tuning library only (include/deepfluids_hip_debug.h); constants in the release library
-int g_stencil_group = 48;
-int g_stencil_nt = 1;
-int g_stencil_lds = 1;
-#else
-constexpr int g_stencil_group = dfst::kXcdGroup;
-constexpr int g_stencil_nt = 1;      // non-temporal output stores
-constexpr int g_stencil_lds = 1;     // LDS-staged adjoints where they apply
-#endif
-
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 int check3(const void* in, int64_t B, int64_t Z, int64_t Y, int64_t X, const char* fn) {
@@ -675,12 +665,6 @@ int check2(const void* in, int64_t B, int64_t Y, int64_t X, const char* fn) {
 
 extern "C" {
 
-#ifdef DF_TUNING
-void df_debug_set_stencil_nt(int v) { g_stencil_nt = v; }
-void df_debug_set_stencil_group(int v) { g_stencil_group = v; }
-void df_debug_set_stencil_lds(int v) { g_stencil_lds = v; }
-#endif
-
 int df_jacobian3d_fwd(const float* x, float* j, float* c, int64_t B, int64_t Z, int64_t Y, int64_t X,
                       df_stream_t stream) {
   if (int e = check3(x, B, Z, Y, X, "df_jacobian3d_fwd")) return e;
@@ -688,15 +672,12 @@ int df_jacobian3d_fwd(const float* x, float* j, float* c, int64_t B, int64_t Z, 
   DF_REQUIRE(df::aligned16(j) && df::aligned16(c), DF_EALIGN, "df_jacobian3d_fwd: outputs must be 16-byte aligned");
   Dims3 dm{B * Z * Y * X, (int)Z, (int)Y, (int)X, 0};
   dim3 grid((unsigned)ceil_div(dm.nvox, kVoxPerBlock)), block(kThreads);
-  if (g_stencil_group > 0 && grid.x % (8 * g_stencil_group) == 0) dm.group = g_stencil_group;
+  if (grid.x % (8 * kXcdGroup) == 0) dm.group = kXcdGroup;
   hipStream_t s = df::as_stream(stream);
   if (X % 4 == 0 && df::aligned16(x)) {
-    const int nt = g_stencil_nt;
-#define DF_J3(WJ, WC)                                                                                              \
-  if (nt) hipLaunchKernelGGL((jacobian3d_fwd_vec_kernel<WJ, WC, true>), grid, block, 0, s, x, j, c, dm);           \
-  else hipLaunchKernelGGL((jacobian3d_fwd_vec_kernel<WJ, WC, false>), grid, block, 0, s, x, j, c, dm)
-    if (j && c) { DF_J3(true, true); } else if (j) { DF_J3(true, false); } else { DF_J3(false, true); }
-#undef DF_J3
+    if (j && c) hipLaunchKernelGGL((jacobian3d_fwd_vec_kernel<true, true>), grid, block, 0, s, x, j, c, dm);
+    else if (j) hipLaunchKernelGGL((jacobian3d_fwd_vec_kernel<true, false>), grid, block, 0, s, x, j, c, dm);
+    else hipLaunchKernelGGL((jacobian3d_fwd_vec_kernel<false, true>), grid, block, 0, s, x, j, c, dm);
     return df::launched("df_jacobian3d_fwd");
   }
   if (j && c) hipLaunchKernelGGL((jacobian3d_fwd_kernel<true, true>), grid, block, 0, s, x, j, c, dm);
@@ -713,13 +694,13 @@ int df_jacobian3d_bwd(const float* gj, const float* gc, float* gx, int64_t B, in
   hipStream_t s = df::as_stream(stream);
   if (X % 4 == 0 && df::aligned16(gj) && df::aligned16(gc) && df::aligned16(gx)) {
     dim3 gridv((unsigned)ceil_div(dm.nvox, kVoxPerBlock)), blockv(kThreads);
-    if (g_stencil_group > 0 && gridv.x % (8 * g_stencil_group) == 0) dm.group = g_stencil_group;
-    const bool lds = X <= kLdsMaxX && g_stencil_lds;
-    if (gj && gc) hipLaunchKernelGGL((jacobian3d_bwd_vec_kernel<true, true, true>), gridv, blockv, 0, s, gj, gc, gx, dm);
-    else if (gj && lds) hipLaunchKernelGGL((jacobian3d_bwd_lds_kernel<9, true>), gridv, blockv, 0, s, gj, gx, dm);
-    else if (gc && lds) hipLaunchKernelGGL((jacobian3d_bwd_lds_kernel<3, true>), gridv, blockv, 0, s, gc, gx, dm);
-    else if (gj) hipLaunchKernelGGL((jacobian3d_bwd_vec_kernel<true, false, true>), gridv, blockv, 0, s, gj, gc, gx, dm);
-    else hipLaunchKernelGGL((jacobian3d_bwd_vec_kernel<false, true, true>), gridv, blockv, 0, s, gj, gc, gx, dm);
+    if (gridv.x % (8 * kXcdGroup) == 0) dm.group = kXcdGroup;
+    const bool lds = X <= kLdsMaxX;
+    if (gj && gc) hipLaunchKernelGGL((jacobian3d_bwd_vec_kernel<true, true>), gridv, blockv, 0, s, gj, gc, gx, dm);
+    else if (gj && lds) hipLaunchKernelGGL((jacobian3d_bwd_lds_kernel<9>), gridv, blockv, 0, s, gj, gx, dm);
+    else if (gc && lds) hipLaunchKernelGGL((jacobian3d_bwd_lds_kernel<3>), gridv, blockv, 0, s, gc, gx, dm);
+    else if (gj) hipLaunchKernelGGL((jacobian3d_bwd_vec_kernel<true, false>), gridv, blockv, 0, s, gj, gc, gx, dm);
+    else hipLaunchKernelGGL((jacobian3d_bwd_vec_kernel<false, true>), gridv, blockv, 0, s, gj, gc, gx, dm);
     return df::launched("df_jacobian3d_bwd");
   }
   dim3 grid((unsigned)ceil_div(dm.nvox, kThreads)), block(kThreads);

@@ -53,7 +53,7 @@ __device__ __forceinline__ void flush_lds(const float* __restrict__ s, float* __
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kXcdGroup = 48;      // runs of 48 blocks per XCD (sweep in tools/stencil_probe.py: best warm + cold)
+constexpr int kXcdGroup = 48;      // runs of 48 blocks per XCD (sweep in tools/archive/stencil_probe.py: best warm + cold)
 
 }  // namespace dfst
 #endif

@@ -249,7 +249,10 @@ __global__ __launch_bounds__(kThreads) void velocity_jl1_3d_vec_kernel(const flo
 // CU, loads and stores on different waves so that no wave waits for a store acknowledgement) 58 us -- a tile's compute phases last
 // ~1.1 us, less than the ~2.4 us a CU needs to take in the 51 KB of the next tile's boxes (halo rows included: 2.1x the tile's own
 // bytes), so a SECOND workgroup's tile in flight matters more than freeing the registers.  What bounds all of them is the fabric
-// traffic of the forward halos (psi: 40 rows per 16); marching along z with a ring of planes would fetch every plane once.
+// traffic of the forward halos (psi: 40 rows per 16).
+// Marching along z with rings of planes fed by LDS-DMA, so that every plane is fetched once, was built and measured: 58.4 us against 57.5 us
+// for this kernel at the cfg3 shape (both with the final reduce launch) -- the tiles' halo re-reads are L2 hits, not HBM traffic.  That
+// kernel (velocity_loss3d_march_kernel) is in the history at 33bb34b, the parent of the change that removed it.
 constexpr int kTileZ = 2, kTileY = 8;      // default tile: 2 planes x 8 rows x X voxels
 
 struct TileGeo {
@@ -258,7 +261,7 @@ struct TileGeo {
   unsigned bytes;      // of psi (== of x, of u)
 };
 
-template <int XQ, int kTZ, int kTY, bool NT>
+template <int XQ, int kTZ, int kTY>
 __global__ __launch_bounds__(kThreads) void velocity_loss3d_tile_kernel(const float* __restrict__ psi, const float* __restrict__ x,
                                                                         float* __restrict__ u, double* __restrict__ partial, TileGeo g) {
   constexpr int kPsiRows = (kTZ + 2) * (kTY + 2), kURows = (kTZ + 1) * (kTY + 1);
@@ -393,12 +396,7 @@ __global__ __launch_bounds__(kThreads) void velocity_loss3d_tile_kernel(const fl
         a1s += a1; a9s += a9;
       }
       f32x4* dst = reinterpret_cast<f32x4*>(u) + ((static_cast<int64_t>(b) * g.Z + z) * g.Y + y) * rowf4 + 3 * q;
-      if (NT) {
-        __builtin_nontemporal_store(f32x4{uo[0], uo[1], uo[2], uo[3]}, dst); __builtin_nontemporal_store(f32x4{uo[4], uo[5], uo[6], uo[7]}, dst + 1);
-        __builtin_nontemporal_store(f32x4{uo[8], uo[9], uo[10], uo[11]}, dst + 2);
-      } else {
-        dst[0] = f32x4{uo[0], uo[1], uo[2], uo[3]}; dst[1] = f32x4{uo[4], uo[5], uo[6], uo[7]}; dst[2] = f32x4{uo[8], uo[9], uo[10], uo[11]};
-      }
+      dst[0] = f32x4{uo[0], uo[1], uo[2], uo[3]}; dst[1] = f32x4{uo[4], uo[5], uo[6], uo[7]}; dst[2] = f32x4{uo[8], uo[9], uo[10], uo[11]};
     }
     s1 += a1s; s9 += a9s;
     lds_barrier();                                              // everyone is done with the boxes before the next tile overwrites them
@@ -408,179 +406,9 @@ __global__ __launch_bounds__(kThreads) void velocity_loss3d_tile_kernel(const fl
   if (tid == 0) { partial[2 * blockIdx.x] = s1; partial[2 * blockIdx.x + 1] = s9; }
 }
 
-#ifdef DF_TUNING
-// ================================ 3-D, ONE kernel, marching along z [r3; tuning library only] ==========================================
-// MEASURED (cfg3, 16x64x96x64): 58.4 us per forward against 57.5 us for the tile kernel above (both incl. the 1-block final reduction), so
-// the tiles stay the production path and this kernel is kept under DF_TUNING (df_debug_set_tail(8), tools/tail_probe.py) as the record of
-// the experiment: fetching every plane once does not pay because the halo re-reads of the tiles are L2 hits, not HBM traffic.
-// The tiles above load (TZ+2)(TY+2) rows of psi per TZ x TY rows of output: 2.5x at 2 x 8.  Here a workgroup owns a COLUMN of TY rows x X
-// voxels of one batch element and marches through all Z planes: every plane of psi and x is fetched once (+ the forward halo rows of the
-// column: (TY+2)/TY, (TY+1)/TY), by LDS-DMA (`buffer_load_dwordx4 ... lds`: the planes are verbatim runs of image rows) into rings of 8
-// planes, SEVEN z-steps ahead of their use -- the memory latency is covered by ring depth, not by occupancy.  6 waves:
-//   waves 0-1  issue the DMA of plane s+7 (3 + 3 instructions each), wait for plane s+3 with `s_waitcnt vmcnt(18)` (loads only: these waves
-//              never store), and compute u(s+2) = curl3(psi) from psi(s+2), psi(s+3) into a ring of 4 u planes;
-//   waves 2-5  take |u - x| and |J(u) - J(x)| of plane s from u(s), u(s+1), x(s), x(s+1) (two threads per quad: x, y terms + l1 | z terms)
-//              and store u(s) -- they never wait for a load.
-// ONE LDS-only barrier per z-step.  Same arithmetic as the tile kernel (u bit-identical to df_jacobian3d_fwd).  X = 64, Y % TY == 0, Z >= 4.
-constexpr int kMarchT = 384, kMarchP = 7;
-
-struct MarchGeo {
-  int B, Z, Y, ncol;       // ncol = Y / TY columns per batch element
-  unsigned bytes;
-};
-
-template <int XQ, int TY>
-__global__ __launch_bounds__(kMarchT) void velocity_loss3d_march_kernel(const float* __restrict__ psi, const float* __restrict__ x,
-                                                                         float* __restrict__ u, double* __restrict__ partial, MarchGeo g) {
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  constexpr int RF4 = 3 * XQ;                       // float4 per image row
-  constexpr int PR = TY + 2;                        // rows per ring plane (psi needs TY + 2, x and u TY + 1)
-  constexpr int PL = PR * RF4;                      // float4 per ring plane; == 6 DMA instructions of 64 pieces for XQ = 16, TY = 6
-  constexpr int NDMA = (PL + 127) / 128;            // DMA instructions per loader wave, plane and tensor
-  static_assert(PL % 64 == 0, "plane must be whole 64-piece DMA instructions");
-  extern __shared__ f32x4 smem[];                   // [psi ring 8][x ring 8][u ring 4] planes of PL float4
-  f32x4* sPsi = smem;
-  f32x4* sX = smem + 8 * PL;
-  f32x4* sU = smem + 16 * PL;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const bool loader = wave < 2;
-  const int col = blockIdx.x % g.ncol, b = blockIdx.x / g.ncol;
-  const int y0 = col * TY;
-  const int64_t rowf4 = RF4;
-
-  const __amdgpu_buffer_rsrc_t psrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(psi), 0, g.bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t xsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, g.bytes, 0x00020000);
-  // loader lane: piece (wave & 1) * 64 + lane of every 128-piece group of a plane; byte offset within the plane's run of rows
-  unsigned koff[NDMA];
-#pragma unroll
-  for (int k = 0; k < NDMA; ++k) koff[k] = static_cast<unsigned>(k * 128 + (wave & 1) * 64 + lane) * 16u;
-  const unsigned colbase = static_cast<unsigned>((b * g.Z * g.Y + y0) * RF4) * 16u;      // row (b, z = 0, y0)
-  const unsigned planeb = static_cast<unsigned>(g.Y * RF4) * 16u;
-  auto dma_plane = [&](int z) {      // psi and x rows y0 .. y0 + TY + 1 of plane z -> ring slot z & 7 (rows past the column's needs are never read)
-    const unsigned base = colbase + static_cast<unsigned>(z) * planeb;
-#pragma unroll
-    for (int k = 0; k < NDMA; ++k) {
-      if (k * 128 + (wave & 1) * 64 < PL) {
-        lds_ptr dp = (lds_ptr)(sPsi + (z & 7) * PL + k * 128 + (wave & 1) * 64);
-        const unsigned vo = koff[k] + base;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(psrd, dp, 16, vo, 0u, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < NDMA; ++k) {
-      if (k * 128 + (wave & 1) * 64 < PL) {
-        lds_ptr dx = (lds_ptr)(sX + (z & 7) * PL + k * 128 + (wave & 1) * 64);
-        const unsigned vo = koff[k] + base;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(xsrd, dx, 16, vo, 0u, 0, 0);
-      }
-    }
-  };
-  auto quad = [&](const f32x4* rowp, int q, float (&o)[16]) {
-    const f32x4 a0 = rowp[3 * q], a1 = rowp[3 * q + 1], a2 = rowp[3 * q + 2];
-    const f32x4 a3 = rowp[q + 1 < XQ ? 3 * q + 3 : 3 * q + 2];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { o[e] = a0[e]; o[4 + e] = a1[e]; o[8 + e] = a2[e]; }
-    o[12] = a3[0]; o[13] = a3[1]; o[14] = a3[2]; o[15] = 0.f;
-  };
-
-  // prologue: planes 0 .. P-3 (step s issues plane s + P; the first step is s = -2)
-  if (loader) {
-    for (int z = 0; z < kMarchP - 2 && z < g.Z; ++z) dma_plane(z);
-  }
-  double s1 = 0.0, s9 = 0.0;
-  for (int s = -2; s < g.Z; ++s) {
-    if (loader) {
-      // plane s + 3 (the newest one this step reads) has landed: at most the 3 planes issued after it may still be in flight
-      if (s + kMarchP - 1 < g.Z) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * 2 * ((PL / 64 + 1) / 2)) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    lds_barrier();
-    if (loader) {
-      if (s + kMarchP < g.Z) dma_plane(s + kMarchP);
-      // ---- u(s+2) = curl3(psi) on rows 0 .. TY of the column ---------------------------------------------------------------------
-      const int zu = s + 2;
-      const int it = tid;                                      // 128 loader threads >= (TY + 1) * XQ items
-      if (zu < g.Z && it < (TY + 1) * XQ) {
-        const int r = it / XQ, q = it - r * XQ;
-        const int y = y0 + r;
-        if (y < g.Y) {
-          const bool ly = y == g.Y - 1, lz = zu == g.Z - 1;
-          float po[16], py[16], pz[16];
-          quad(sPsi + (zu & 7) * PL + r * RF4, q, po);
-          quad(sPsi + (zu & 7) * PL + (ly ? r - 1 : r + 1) * RF4, q, py);
-          quad(sPsi + ((lz ? zu - 1 : zu + 1) & 7) * PL + r * RF4, q, pz);
-          float uo[12];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const bool lx = q == XQ - 1 && i == 3;
-            const float o0 = po[i * 3], o1 = po[i * 3 + 1], o2 = po[i * 3 + 2];
-            const float x1 = lx ? po[(i - 1) * 3 + 1] : po[(i + 1) * 3 + 1], x2 = lx ? po[(i - 1) * 3 + 2] : po[(i + 1) * 3 + 2];
-            const float dx1 = lx ? o1 - x1 : x1 - o1, dx2 = lx ? o2 - x2 : x2 - o2;
-            const float dy0 = ly ? o0 - py[i * 3] : py[i * 3] - o0, dy2 = ly ? o2 - py[i * 3 + 2] : py[i * 3 + 2] - o2;
-            const float dz0 = lz ? o0 - pz[i * 3] : pz[i * 3] - o0, dz1 = lz ? o1 - pz[i * 3 + 1] : pz[i * 3 + 1] - o1;
-            uo[i * 3] = dy2 - dz1; uo[i * 3 + 1] = dz0 - dx2; uo[i * 3 + 2] = dx1 - dy0;
-          }
-          f32x4* d = sU + (zu & 3) * PL + r * RF4 + 3 * q;
-          d[0] = f32x4{uo[0], uo[1], uo[2], uo[3]}; d[1] = f32x4{uo[4], uo[5], uo[6], uo[7]}; d[2] = f32x4{uo[8], uo[9], uo[10], uo[11]};
-        }
-      }
-    } else if (s >= 0) {
-      // ---- losses of plane s: every quad of the TY rows by two threads ----------------------------------------------------------------
-      const int it = tid - 128;                                // 0 .. 255 >= 2 * TY * XQ
-      if (it < 2 * TY * XQ) {
-        const int role = it / (TY * XQ), iq = it - role * (TY * XQ);
-        const int r = iq / XQ, q = iq - r * XQ;
-        const int y = y0 + r;
-        const bool ly = y == g.Y - 1, lz = s == g.Z - 1;
-        const int zn = role == 0 ? s : (lz ? s - 1 : s + 1), rn = role == 0 ? (ly ? r - 1 : r + 1) : r;
-        float uo[16], xo[16], un[16], xn[16];
-        quad(sU + (s & 3) * PL + r * RF4, q, uo); quad(sX + (s & 7) * PL + r * RF4, q, xo);
-        quad(sU + (zn & 3) * PL + rn * RF4, q, un); quad(sX + (zn & 7) * PL + rn * RF4, q, xn);
-        const bool lxq = q == XQ - 1;
-        float a1 = 0.f, a9 = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const float fu = uo[i * 3 + c], fx = xo[i * 3 + c];
-            a9 += fabsf((un[i * 3 + c] - fu) - (xn[i * 3 + c] - fx));
-            if (role == 0) {
-              const int ia = i == 3 ? 2 : i;
-              const float tx3 = fabsf((uo[(ia + 1) * 3 + c] - uo[ia * 3 + c]) - (xo[(ia + 1) * 3 + c] - xo[ia * 3 + c]));
-              const float txn = fabsf((uo[(i + 1) * 3 + c] - fu) - (xo[(i + 1) * 3 + c] - fx));
-              a9 += (i == 3 && lxq) ? tx3 : txn;
-              a1 += fabsf(fu - fx);
-            }
-          }
-        }
-        s1 += a1; s9 += a9;
-        if (role == 1) {
-          f32x4* dst = reinterpret_cast<f32x4*>(u) + ((static_cast<int64_t>(b) * g.Z + s) * g.Y + y) * rowf4 + 3 * q;
-          dst[0] = f32x4{uo[0], uo[1], uo[2], uo[3]}; dst[1] = f32x4{uo[4], uo[5], uo[6], uo[7]}; dst[2] = f32x4{uo[8], uo[9], uo[10], uo[11]};
-        }
-      }
-    }
-  }
-  // block sums over the 6 waves (the loaders contribute zeros), fixed order
-  __syncthreads();
-  double* red = reinterpret_cast<double*>(smem);
-  s1 = wave_sum(s1); s9 = wave_sum(s9);
-  if (lane == 0) { red[wave] = s1; red[8 + wave] = s9; }
-  __syncthreads();
-  if (tid == 0) {
-    double a = 0.0, c = 0.0;
-    for (int w = 0; w < kMarchT / 64; ++w) { a += red[w]; c += red[8 + w]; }
-    partial[2 * blockIdx.x] = a; partial[2 * blockIdx.x + 1] = c;
-  }
-}
-#endif  // DF_TUNING
-
 // du of 4 consecutive voxels per thread: the adjoint of D along an axis at position k needs f = (u, x) at k-1, k, k+1 only
 // (on the last two positions the replicated difference folds back onto the same three values), i.e. the quads one
 // row / slice before and after and the two records left / right of the quad.  Same operation order as velocity_loss3d_bwd_kernel.
-template <bool NT>
 __global__ __launch_bounds__(kThreads) void velocity_du3d_vec_kernel(const float* __restrict__ u, const float* __restrict__ x,
                                                                      const float* __restrict__ g_l1, const float* __restrict__ g_jl1,
                                                                      float inv_n1, float inv_nj, float* __restrict__ du, Dims3 dm) {
@@ -649,90 +477,7 @@ __global__ __launch_bounds__(kThreads) void velocity_du3d_vec_kernel(const float
   __syncthreads();
   const int64_t left = dm.nvox - v0;
   const int64_t nv = left < kVoxPerBlock ? left : kVoxPerBlock;
-  dfst::flush_lds<NT>(so, du + v0 * 3, nv * 3, tid);
-}
-
-// ================================ 3-D, one voxel per lane with 12-byte record loads =================================================
-// A wave's 64 records form ONE contiguous 768-byte span per load (6 cache lines; the 16-byte-per-lane quads above touch 24 lines per
-// load instruction, which bounds them at ~3 TB/s in the texture-address unit).  hipcc merges the struct copies into
-// global_load_dwordx3 (own + x-neighbour: dwordx4 + dwordx2).  Any extents >= 2.
-struct F3 {
-  float a, b, c;
-};
-__device__ __forceinline__ F3 ld3(const float* __restrict__ p) { return *reinterpret_cast<const F3*>(p); }
-
-__global__ __launch_bounds__(kThreads) void velocity_jl1_3d_kernel(const float* __restrict__ u, const float* __restrict__ x,
-                                                                   double* __restrict__ partial, Geo3 g) {
-  const int64_t sy = g.X, sz = static_cast<int64_t>(g.X) * g.Y;
-  double s1 = 0.0, s9 = 0.0;
-#pragma unroll
-  for (int it = 0; it < kVpt3; ++it) {
-    const int64_t v = (static_cast<int64_t>(blockIdx.x) * kVpt3 + it) * kThreads + threadIdx.x;
-    if (v < g.nvox) {
-      int xx, yy, zz;
-      coords3(v, g, xx, yy, zz);
-      const bool lx = xx == g.X - 1, ly = yy == g.Y - 1, lz = zz == g.Z - 1;
-      const int64_t nx = lx ? v - 1 : v + 1, ny = ly ? v - sy : v + sy, nz = lz ? v - sz : v + sz;
-      const F3 uc = ld3(u + v * 3), ux = ld3(u + nx * 3), uy = ld3(u + ny * 3), uz = ld3(u + nz * 3);
-      const F3 xc = ld3(x + v * 3), xx_ = ld3(x + nx * 3), xy = ld3(x + ny * 3), xz = ld3(x + nz * 3);
-      const float a1 = (fabsf(uc.a - xc.a) + fabsf(uc.b - xc.b)) + fabsf(uc.c - xc.c);
-      auto d = [](bool last, float f, float n) { return last ? f - n : n - f; };
-      float a9 = 0.f;
-      a9 += fabsf(d(lx, uc.a, ux.a) - d(lx, xc.a, xx_.a)); a9 += fabsf(d(lx, uc.b, ux.b) - d(lx, xc.b, xx_.b)); a9 += fabsf(d(lx, uc.c, ux.c) - d(lx, xc.c, xx_.c));
-      a9 += fabsf(d(ly, uc.a, uy.a) - d(ly, xc.a, xy.a)); a9 += fabsf(d(ly, uc.b, uy.b) - d(ly, xc.b, xy.b)); a9 += fabsf(d(ly, uc.c, uy.c) - d(ly, xc.c, xy.c));
-      a9 += fabsf(d(lz, uc.a, uz.a) - d(lz, xc.a, xz.a)); a9 += fabsf(d(lz, uc.b, uz.b) - d(lz, xc.b, xz.b)); a9 += fabsf(d(lz, uc.c, uz.c) - d(lz, xc.c, xz.c));
-      s1 += a1; s9 += a9;
-    }
-  }
-  block_sum2(s1, s9);
-  if (threadIdx.x == 0) { partial[2 * blockIdx.x] = s1; partial[2 * blockIdx.x + 1] = s9; }
-}
-
-__global__ __launch_bounds__(kThreads) void velocity_du3d_kernel(const float* __restrict__ u, const float* __restrict__ x,
-                                                                 const float* __restrict__ g_l1, const float* __restrict__ g_jl1,
-                                                                 float inv_n1, float inv_nj, float* __restrict__ du, Geo3 g) {
-  const int64_t v = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
-  if (v >= g.nvox) return;
-  const float s1 = inv_n1 * (g_l1 ? g_l1[0] : 1.f), s9 = inv_nj * (g_jl1 ? g_jl1[0] : 1.f);
-  int xx, yy, zz;
-  coords3(v, g, xx, yy, zz);
-  const int64_t sy = g.X, sz = static_cast<int64_t>(g.X) * g.Y;
-  // the three values around position k of an axis (clamped at the ends: adj() ignores the clamped side there)
-  auto adj = [&](float um, float u0, float up, float xm, float x0, float xp, int k, int n) -> float {
-    const float gm = sgn((u0 - um) - (x0 - xm)) * s9;      // g(k-1)   (k >= 1)
-    const float gk = sgn((up - u0) - (xp - x0)) * s9;      // g(k)     (k <= n-2)
-    if (k == n - 1) return gm + gm;                        // gp(n-2) = g(n-2) + g(n-1), D(n-1) == D(n-2)
-    const float gpk = k == n - 2 ? gk + gk : gk;
-    return k == 0 ? -gpk : gm - gpk;
-  };
-  const F3 u0 = ld3(u + v * 3), x0 = ld3(x + v * 3);
-  F3 acc;
-  {
-    const int64_t m = xx > 0 ? v - 1 : v, p = xx < g.X - 1 ? v + 1 : v;
-    const F3 um = ld3(u + m * 3), up = ld3(u + p * 3), xm = ld3(x + m * 3), xp = ld3(x + p * 3);
-    acc.a = adj(um.a, u0.a, up.a, xm.a, x0.a, xp.a, xx, g.X);
-    acc.b = adj(um.b, u0.b, up.b, xm.b, x0.b, xp.b, xx, g.X);
-    acc.c = adj(um.c, u0.c, up.c, xm.c, x0.c, xp.c, xx, g.X);
-  }
-  {
-    const int64_t m = yy > 0 ? v - sy : v, p = yy < g.Y - 1 ? v + sy : v;
-    const F3 um = ld3(u + m * 3), up = ld3(u + p * 3), xm = ld3(x + m * 3), xp = ld3(x + p * 3);
-    acc.a += adj(um.a, u0.a, up.a, xm.a, x0.a, xp.a, yy, g.Y);
-    acc.b += adj(um.b, u0.b, up.b, xm.b, x0.b, xp.b, yy, g.Y);
-    acc.c += adj(um.c, u0.c, up.c, xm.c, x0.c, xp.c, yy, g.Y);
-  }
-  {
-    const int64_t m = zz > 0 ? v - sz : v, p = zz < g.Z - 1 ? v + sz : v;
-    const F3 um = ld3(u + m * 3), up = ld3(u + p * 3), xm = ld3(x + m * 3), xp = ld3(x + p * 3);
-    acc.a += adj(um.a, u0.a, up.a, xm.a, x0.a, xp.a, zz, g.Z);
-    acc.b += adj(um.b, u0.b, up.b, xm.b, x0.b, xp.b, zz, g.Z);
-    acc.c += adj(um.c, u0.c, up.c, xm.c, x0.c, xp.c, zz, g.Z);
-  }
-  F3 o;
-  o.a = sgn(u0.a - x0.a) * s1 + acc.a;
-  o.b = sgn(u0.b - x0.b) * s1 + acc.b;
-  o.c = sgn(u0.c - x0.c) * s1 + acc.c;
-  *reinterpret_cast<F3*>(du + v * 3) = o;
+  dfst::flush_lds<false>(so, du + v0 * 3, nv * 3, tid);
 }
 
 // ================================================= 2-D ===========================================================================
@@ -822,19 +567,51 @@ int check(const void* a, const void* b, int64_t B, int64_t Z, int64_t Y, int64_t
 
 inline int64_t nblocks_fwd(int64_t n) { return ceil_div(n, static_cast<int64_t>(kThreads) * kVpt3); }
 
-#ifdef DF_TUNING      // tuning library only: 0 = default dispatch, 1 = force the 16-byte quad kernels, 2 = force the record-per-lane kernels
-int g_tail_variant = 0;
-#else
-constexpr int g_tail_variant = 0;
-#endif
+// the fixed-order sum of the forward kernels' per-workgroup partials -> the two means of a 3-D field of nvox voxels
+void launch_final3d(const double* part, int64_t nparts, int64_t nvox, float* l1, float* jl1, hipStream_t s) {
+  hipLaunchKernelGGL(velocity_loss_final_kernel, dim3(1), dim3(kThreads), 0, s, part, (int)nparts, 1.0 / (3.0 * static_cast<double>(nvox)),
+                     1.0 / (9.0 * static_cast<double>(nvox)), l1, jl1);
+}
+
+template <int XQ>
+bool launch_tile_xq(const float* psi, const float* x, float* u, double* part, const TileGeo& tg, int64_t grid, size_t lds, hipStream_t s) {
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&velocity_loss3d_tile_kernel<XQ, kTileZ, kTileY>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  hipLaunchKernelGGL((velocity_loss3d_tile_kernel<XQ, kTileZ, kTileY>), dim3((unsigned)grid), dim3(kThreads), lds, s, psi, x, u, part, tg);
+  return true;
+}
+
+// The persistent LDS-tiled kernel where it applies: psi, x -> u and `*nparts` partial sums in one launch (36 B/voxel of HBM traffic, nothing
+// read back).  Tiles of kTileZ x kTileY rows (two workgroups per CU at X = 64); the grid is the workgroups that are resident at once,
+// lds_cap / tile_lds per CU and at most 8.  Returns false -- nothing launched -- where the shape or the alignment rules it out, and where
+// the device refuses the LDS opt-in (a partitioned one): the caller then takes the two-launch path instead of failing.
+bool launch_tile(const float* psi, const float* x, float* u, double* part, int64_t B, int64_t Z, int64_t Y, int64_t X, int64_t nb,
+                 int64_t* nparts, hipStream_t s) {
+  const int64_t nvox = B * Z * Y * X;
+  const int64_t ntl = (Z / kTileZ) * (Y / kTileY) * B;
+  const int64_t rf4 = 3 * (X / 4), prow = (kTileZ + 2) * (kTileY + 2), urow = (kTileZ + 1) * (kTileY + 1);
+  const size_t tile_lds = static_cast<size_t>((ceil_div(prow * rf4, kThreads) + ceil_div(urow * rf4, kThreads)) * kThreads + urow * rf4) * sizeof(f32x4);
+  const int64_t lds_cap = df::lds_optin_bytes();          // 160 KiB per CU on an unpartitioned MI355X
+  int64_t tile_grid = (tile_lds == 0 ? 1 : lds_cap / static_cast<int64_t>(tile_lds)) * df::kCUs;      // (X < 4: no tile, ruled out below)
+  if (tile_grid > 8 * df::kCUs) tile_grid = 8 * df::kCUs;
+  if (tile_grid > ntl) tile_grid = ntl;
+  if (!(u && (X == 64 || X == 112 || X == 128) && Z % kTileZ == 0 && Y % kTileY == 0 && df::aligned16(psi) && df::aligned16(x) &&
+        df::aligned16(u) && ntl < (1LL << 30) && tile_grid <= nb && tile_grid > 0 && nvox * 12 < (1LL << 32) &&
+        static_cast<int64_t>(tile_lds) <= lds_cap))
+    return false;
+  const TileGeo tg{(int)B, (int)Z, (int)Y, (int)(Z / kTileZ), (int)(Y / kTileY), (int)ntl, (unsigned)(nvox * 12)};
+  *nparts = tile_grid;
+  if (X == 64) return launch_tile_xq<16>(psi, x, u, part, tg, tile_grid, tile_lds, s);
+  if (X == 112) return launch_tile_xq<28>(psi, x, u, part, tg, tile_grid, tile_lds, s);
+  return launch_tile_xq<32>(psi, x, u, part, tg, tile_grid, tile_lds, s);
+}
 
 }  // namespace
 
 extern "C" {
-
-#ifdef DF_TUNING
-void df_debug_set_tail(int v) { g_tail_variant = v; }
-#endif
 
 int df_jacobian3d_fwd(const float* x, float* j, float* c, int64_t B, int64_t Z, int64_t Y, int64_t X, df_stream_t stream);
 int df_jacobian3d_bwd(const float* gj, const float* gc, float* gx, int64_t B, int64_t Z, int64_t Y, int64_t X, df_stream_t stream);
@@ -858,82 +635,21 @@ int df_velocity_loss3d_fwd(const float* psi, const float* x, float* u, float* l1
   DF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, DF_EALIGN, "df_velocity_loss3d_fwd: workspace must be 8-byte aligned");
   hipStream_t s = df::as_stream(stream);
   double* part = static_cast<double*>(workspace);
-  if (u && g_tail_variant == 2) {
-    if (int e = df_jacobian3d_fwd(psi, nullptr, u, B, Z, Y, X, stream)) return e;
-    hipLaunchKernelGGL(velocity_jl1_3d_kernel, dim3((unsigned)nb), dim3(kThreads), 0, s, u, x, part, g);
-    hipLaunchKernelGGL(velocity_loss_final_kernel, dim3(1), dim3(kThreads), 0, s, part, (int)nb, 1.0 / (3.0 * static_cast<double>(g.nvox)),
-                       1.0 / (9.0 * static_cast<double>(g.nvox)), l1, jl1);
-    return df::launched("df_velocity_loss3d_fwd");
-  }
-#ifdef DF_TUNING      // z-marching columns (one workgroup per column of 6 rows: 256 columns at cfg3)
-  if (u && g_tail_variant == 8 && X == 64 && Y % 6 == 0 && Z >= 4 && df::aligned16(psi) && df::aligned16(x) &&
-      df::aligned16(u) && B * (Y / 6) >= 192 && B * (Y / 6) <= nb && g.nvox * 12 < (1LL << 32)) {
-    MarchGeo mg{(int)B, (int)Z, (int)Y, (int)(Y / 6), (unsigned)(g.nvox * 12)};
-    const int64_t mgrid = B * (Y / 6);
-    const size_t mlds = static_cast<size_t>(20) * (6 + 2) * 3 * 16 * sizeof(f32x4);      // 8 + 8 + 4 ring planes of 8 rows
-    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&velocity_loss3d_march_kernel<16, 6>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds))
-      return df::fail((int)e, "df_velocity_loss3d_fwd: dynamic LDS opt-in: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL((velocity_loss3d_march_kernel<16, 6>), dim3((unsigned)mgrid), dim3(kMarchT), mlds, s, psi, x, u, part, mg);
-    hipLaunchKernelGGL(velocity_loss_final_kernel, dim3(1), dim3(kThreads), 0, s, part, (int)mgrid, 1.0 / (3.0 * static_cast<double>(g.nvox)),
-                       1.0 / (9.0 * static_cast<double>(g.nvox)), l1, jl1);
-    return df::launched("df_velocity_loss3d_fwd");
-  }
-#endif
-  // tile shape: 2 x 8 rows (two workgroups per CU at X = 64); (tuning library: df_debug_set_tail 3 = one workgroup per CU, 4 = 2 x 4 rows,
-  // 5 = non-temporal u stores)
-  const int tzv = kTileZ, tyv = g_tail_variant == 4 ? 4 : kTileY;
-  const bool tile_mode = g_tail_variant == 0 || (g_tail_variant >= 3 && g_tail_variant != 8);
-  const int64_t ntl = (Z / tzv) * (Y / tyv) * B;
-  const int64_t rf4 = 3 * (X / 4), prow = (tzv + 2) * (tyv + 2), urow = (tzv + 1) * (tyv + 1);
-  const size_t tile_lds = static_cast<size_t>((ceil_div(prow * rf4, kThreads) + ceil_div(urow * rf4, kThreads)) * kThreads + urow * rf4) * sizeof(f32x4);
-  const int64_t lds_cap = df::lds_optin_bytes();          // 160 KiB per CU on an unpartitioned MI355X
-  int64_t tile_grid = (g_tail_variant == 3 || tile_lds == 0 ? 1 : static_cast<int64_t>(lds_cap / static_cast<int64_t>(tile_lds))) * df::kCUs;      // workgroups resident at once
-  if (tile_grid > 8 * df::kCUs) tile_grid = 8 * df::kCUs;
-  if (tile_grid > ntl) tile_grid = ntl;
-  if (u && tile_mode && (X == 64 || X == 112 || X == 128) && Z % tzv == 0 && Y % tyv == 0 && df::aligned16(psi) && df::aligned16(x) &&
-      df::aligned16(u) && ntl < (1LL << 30) && tile_grid <= nb && tile_grid > 0 && g.nvox * 12 < (1LL << 32) &&
-      static_cast<int64_t>(tile_lds) <= lds_cap) {
-    // one persistent LDS-tiled kernel: psi, x -> u, l1, j_l1 (36 B/voxel of HBM traffic, nothing read back); grid = the workgroups that
-    // are resident at once
-    TileGeo tg{(int)B, (int)Z, (int)Y, (int)(Z / tzv), (int)(Y / tyv), (int)ntl, (unsigned)(g.nvox * 12)};
-    bool tile_ok = true;      // a refused LDS opt-in (partitioned device) falls through to the two-launch path below instead of failing
-#define DF_TILE(XQV, TYV, NTV)                                                                                                             \
-  do {                                                                                                                                     \
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&velocity_loss3d_tile_kernel<XQV, kTileZ, TYV, NTV>),                            \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds) != hipSuccess) {                                    \
-      (void)hipGetLastError();                                                                                                             \
-      tile_ok = false;                                                                                                                     \
-    } else {                                                                                                                               \
-      hipLaunchKernelGGL((velocity_loss3d_tile_kernel<XQV, kTileZ, TYV, NTV>), dim3((unsigned)tile_grid), dim3(kThreads), tile_lds, s,     \
-                         psi, x, u, part, tg);                                                                                             \
-    }                                                                                                                                      \
-  } while (0)
-#ifdef DF_TUNING
-    if (g_tail_variant == 4 && X == 64) DF_TILE(16, 4, false); else if (g_tail_variant == 5 && X == 64) DF_TILE(16, kTileY, true); else
-#endif
-    if (X == 64) DF_TILE(16, kTileY, false); else if (X == 112) DF_TILE(28, kTileY, false); else DF_TILE(32, kTileY, false);
-#undef DF_TILE
-    if (tile_ok) {
-      hipLaunchKernelGGL(velocity_loss_final_kernel, dim3(1), dim3(kThreads), 0, s, part, (int)tile_grid, 1.0 / (3.0 * static_cast<double>(g.nvox)),
-                         1.0 / (9.0 * static_cast<double>(g.nvox)), l1, jl1);
-      return df::launched("df_velocity_loss3d_fwd");
-    }
-  }
-  if (u && X % 4 == 0 && df::aligned16(psi) && df::aligned16(x) && df::aligned16(u)) {
-    // fast path: u = curl3(psi) with the 16-byte-load stencil kernel, then one reduction pass over (u, x)
+  int64_t nparts = nb;      // every path writes at most nb partials: the workspace covers it
+  if (launch_tile(psi, x, u, part, B, Z, Y, X, nb, &nparts, s)) {
+    // the tile kernel did it all: only its partials are left to sum
+  } else if (u && X % 4 == 0 && df::aligned16(psi) && df::aligned16(x) && df::aligned16(u)) {
+    // 16-byte path: u = curl3(psi) with the 16-byte-load stencil kernel, then one reduction pass over (u, x)
     if (int e = df_jacobian3d_fwd(psi, nullptr, u, B, Z, Y, X, stream)) return e;
     Dims3 dm{g.nvox, (int)Z, (int)Y, (int)X, 0};
-    const int64_t nbv = ceil_div(g.nvox, kVoxPerBlock);      // <= nb: the workspace covers it
-    if (nbv % (8 * dfst::kXcdGroup) == 0) dm.group = dfst::kXcdGroup;
-    hipLaunchKernelGGL(velocity_jl1_3d_vec_kernel, dim3((unsigned)nbv), dim3(kThreads), 0, s, u, x, part, dm);
-    hipLaunchKernelGGL(velocity_loss_final_kernel, dim3(1), dim3(kThreads), 0, s, part, (int)nbv, 1.0 / (3.0 * static_cast<double>(g.nvox)),
-                       1.0 / (9.0 * static_cast<double>(g.nvox)), l1, jl1);
-    return df::launched("df_velocity_loss3d_fwd");
+    nparts = ceil_div(g.nvox, kVoxPerBlock);
+    if (nparts % (8 * dfst::kXcdGroup) == 0) dm.group = dfst::kXcdGroup;
+    hipLaunchKernelGGL(velocity_jl1_3d_vec_kernel, dim3((unsigned)nparts), dim3(kThreads), 0, s, u, x, part, dm);
+  } else {
+    // any extents, any alignment, u optional
+    hipLaunchKernelGGL(velocity_loss3d_fwd_kernel, dim3((unsigned)nb), dim3(kThreads), 0, s, psi, x, u, part, g);
   }
-  hipLaunchKernelGGL(velocity_loss3d_fwd_kernel, dim3((unsigned)nb), dim3(kThreads), 0, s, psi, x, u, part, g);
-  hipLaunchKernelGGL(velocity_loss_final_kernel, dim3(1), dim3(kThreads), 0, s, part, (int)nb, 1.0 / (3.0 * static_cast<double>(g.nvox)),
-                     1.0 / (9.0 * static_cast<double>(g.nvox)), l1, jl1);
+  launch_final3d(part, nparts, g.nvox, l1, jl1, s);
   return df::launched("df_velocity_loss3d_fwd");
 }
 
@@ -945,18 +661,17 @@ int df_velocity_loss3d_bwd(const float* u, const float* x, const float* g_l1, co
   DF_REQUIRE(workspace_bytes >= g.nvox * 3 * static_cast<int64_t>(sizeof(float)), DF_EWORKSPACE, "df_velocity_loss3d_bwd: workspace too small");
   DF_REQUIRE(df::aligned16(workspace), DF_EALIGN, "df_velocity_loss3d_bwd: workspace must be 16-byte aligned");
   float* du = static_cast<float*>(workspace);
-  if (g_tail_variant == 2) {
-    hipLaunchKernelGGL(velocity_du3d_kernel, dim3((unsigned)ceil_div(g.nvox, kThreads)), dim3(kThreads), 0, df::as_stream(stream), u, x, g_l1,
-                       g_jl1, 1.f / static_cast<float>(3 * g.nvox), 1.f / static_cast<float>(9 * g.nvox), du, g);
-  } else if (X % 4 == 0 && df::aligned16(u) && df::aligned16(x)) {
+  hipStream_t s = df::as_stream(stream);
+  const float inv_n1 = 1.f / static_cast<float>(3 * g.nvox), inv_nj = 1.f / static_cast<float>(9 * g.nvox);
+  if (X % 4 == 0 && df::aligned16(u) && df::aligned16(x)) {
     Dims3 dm{g.nvox, (int)Z, (int)Y, (int)X, 0};
     const int64_t nbv = ceil_div(g.nvox, kVoxPerBlock);
     if (nbv % (8 * dfst::kXcdGroup) == 0) dm.group = dfst::kXcdGroup;
-    hipLaunchKernelGGL((velocity_du3d_vec_kernel<false>), dim3((unsigned)nbv), dim3(kThreads), 0, df::as_stream(stream), u, x, g_l1, g_jl1,
-                       1.f / static_cast<float>(3 * g.nvox), 1.f / static_cast<float>(9 * g.nvox), du, dm);
-  } else
-  hipLaunchKernelGGL(velocity_loss3d_bwd_kernel, dim3((unsigned)ceil_div(g.nvox, kThreads)), dim3(kThreads), 0, df::as_stream(stream), u, x,
-                     g_l1, g_jl1, 1.f / static_cast<float>(3 * g.nvox), 1.f / static_cast<float>(9 * g.nvox), du, g);
+    hipLaunchKernelGGL(velocity_du3d_vec_kernel, dim3((unsigned)nbv), dim3(kThreads), 0, s, u, x, g_l1, g_jl1, inv_n1, inv_nj, du, dm);
+  } else {
+    hipLaunchKernelGGL(velocity_loss3d_bwd_kernel, dim3((unsigned)ceil_div(g.nvox, kThreads)), dim3(kThreads), 0, s, u, x, g_l1, g_jl1,
+                       inv_n1, inv_nj, du, g);
+  }
   if (int e = df::launched("df_velocity_loss3d_bwd")) return e;
   return df_jacobian3d_bwd(nullptr, du, gpsi, B, Z, Y, X, stream);      // curl adjoint: du -> dpsi
 }

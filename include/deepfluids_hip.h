@@ -17,9 +17,7 @@
  *   - return 0 on success, <0 = DF_E* argument error, >0 = hipError_t; never throws, never
  *     aborts; a message for the calling thread's last failure is kept in df_last_error();
  *   - re-entrant; no global state besides read-only kernel handles: algorithm choices are call arguments
- *     (`algo`, DF_CONV_VALU_ONLY), never process-wide switches.  (Tuning builds, `make tuning` with -DDF_TUNING, add
- *     the launch knobs and timing variants declared in deepfluids_hip_debug.h to a SEPARATE library; the release
- *     library exports exactly what this header declares.)
+ *     (`algo`, DF_CONV_VALU_ONLY), never process-wide switches.  The library exports exactly what this header declares.
  */
 #ifndef DEEPFLUIDS_HIP_H
 #define DEEPFLUIDS_HIP_H

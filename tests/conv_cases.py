@@ -83,7 +83,7 @@ def _names(r):
     if fam == "bf16":          # (nt,): the N tile follows the padded N alone (no narrowing)
         up = r["entry"].startswith("up_")
         n = (8 if d3 else 4) if r["entry"] == "up_dgrad_bf16x3" else 1
-        return ["conv_bf16x3_kernel<%d,%s,%s,%d,0>" % ((2 if d3 else 1) if up else r["kz"], t, WAVES[what[1]], 2 if up else 3)] * n
+        return ["conv_bf16x3_kernel<%d,%s,%s,%d>" % ((2 if d3 else 1) if up else r["kz"], t, WAVES[what[1]], 2 if up else 3)] * n
     raise ValueError(what)
 
 

@@ -152,9 +152,29 @@ def test_release_library_holds_only_the_production_kernel_instantiations():
     assert all(len(g) == 2 and g[1] in (0, 2, 3) for g in got), got
     want = sorted([(f, 0) for f in (-1, 0, 2, 4, 9, 25, 73, 132, 345)] + [(0, 2), (9, 3), (73, 3)])
     assert got == want, got
-    # the 2-D twin and the weight-gradient kernels have no experiment template switches; the tuning knobs are entry points the release
-    # library must not export (checked above by name: no df_debug_*)
+    # the 2-D twin and the weight-gradient kernels have no experiment template switches; there are no tuning knobs (df_debug_* entry points)
     assert "df_debug_" not in out
+
+    def family(name):
+        """the template argument lists of `name<...>` in the library, as a set of tuples"""
+        return {tuple(v.strip() for v in a.split(",")) for a in re.findall(r"\b%s<([^<>]*)>" % name, out)}
+
+    # the 3-D stencils (stencil.hip, df_jacobian3d_fwd / _bwd): <WJ, WC> | <HJ, HC> = which outputs / incoming gradients there are -- both,
+    # the Jacobian alone, the curl alone; the LDS-staged adjoint takes one gradient of 9 or 3 floats per record
+    pairs = {("true", "true"), ("true", "false"), ("false", "true")}
+    assert family("jacobian3d_fwd_vec_kernel") == pairs
+    assert family("jacobian3d_bwd_vec_kernel") == pairs
+    assert family("jacobian3d_bwd_lds_kernel") == {("3",), ("9",)}
+    # the fused tail (velocity_loss.hip): tiles of kTileZ x kTileY = 2 x 8 rows of X = 64 | 112 | 128 voxels (XQ = X / 4), and the two
+    # 16-byte kernels, which are no templates
+    assert family("velocity_loss3d_tile_kernel") == {(xq, "2", "8") for xq in ("16", "28", "32")}
+    for name in ("velocity_du3d_vec_kernel", "velocity_jl1_3d_vec_kernel"):
+        assert name + "(" in out and name + "<" not in out, name
+    for gone in ("velocity_loss3d_march", "velocity_jl1_3d_kernel(", "velocity_du3d_kernel("):
+        assert gone not in out, gone
+    # conv_bf16x3_kernel<KZ, TZ, TY, TX, WM, WN, MB, NB, KT>: nine arguments, no debug variant behind them
+    bf16 = family("conv_bf16x3_kernel")
+    assert bf16 and all(len(a) == 9 for a in bf16), sorted(bf16)
 
 
 def test_version_and_error_convention():

@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# ARCHIVED: needs a checkout of 33bb34b or earlier: the tuning library (`make tuning`, `_lib.use_tuning_library()`) left the source after it.
 """Workload for a rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES pass (tuning library): effective shader clock (GRBM_GUI_ACTIVE / duration)
 and wave cycles of wino3d_kernel (production), its x-blocked DMA-staging variant, the no-staging timing variant, the direct MFMA conv
 and the (x,y,z) weight gradient at the top-level shape (B = 16, 64x96x64, F = 128), on random data."""

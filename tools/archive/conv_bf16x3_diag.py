@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# ARCHIVED: needs a checkout of 33bb34b or earlier: the tuning library (`make tuning`, `_lib.use_tuning_library()`) left the source after it.
 """Where the time of the direct bf16x3 convolution (conv_bf16.hip) goes: tuning-library variants whose results are wrong by construction."""
 import ctypes
 import os

@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# ARCHIVED: needs a checkout of 33bb34b or earlier: the tuning library (`make tuning`, `_lib.use_tuning_library()`) left the source after it.
 """Round-5 time breakdown (tuning library; variant results wrong by construction -- timing only) of the second-tier Winograd kernels:
   * the 27-point up-sampling-aware forward `wino3d_kernel<.., 1>` and its pooled adjoint `<.., 2>` at cfg3's top level;
   * the plain F(2^3,3^3) kernel at 64 -> 64 channels (cfg5 / every auto-encoder run of the reference), beside 128 -> 128.

@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# ARCHIVED: needs a checkout of 33bb34b or earlier: the tuning library (`make tuning`, `_lib.use_tuning_library()`) left the source after it.
 """Round 5: the up-sampling-aware Winograd forward with the COARSE halo block staged as such (wino3d_kernel MODE 3, production) against the
 fine-grid staging of rounds 2-4 (MODE 1, tuning-library variant 1000): results must be BIT-identical (same operands, same MFMA order);
 then the time of both at cfg3's top level."""

@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# ARCHIVED: needs a checkout of 33bb34b or earlier: the tuning library (`make tuning`, `_lib.use_tuning_library()`) left the source after it.
 # ARCHIVED: needs the tuning library as of the parent of the change that removed df_debug_set_wgrad (variant 16 no longer exists).
 """Round 5: 64 -> 64 (x,y,z)-Winograd weight gradient (cfg5 / every AE run): interleaved tile-row pairs per wave (production since round 5) vs contiguous
 sub-ranges (tuning variant 16, rounds 3-4) -- timing and agreement with the direct kernel."""

@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# ARCHIVED: needs a checkout of 33bb34b or earlier: the tuning library (`make tuning`, `_lib.use_tuning_library()`) left the source after it.
 """Tuning probe for the 3-D stencil kernels (GPU box): variants x cold/warm input."""
 import os, sys
 import torch

@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# ARCHIVED: needs a checkout of 33bb34b or earlier: the tuning library (`make tuning`, `_lib.use_tuning_library()`) left the source after it.
 """Fused-tail kernel variants (tuning library): timing at cfg3 and agreement of the results."""
 import ctypes
 import os

@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# ARCHIVED: needs a checkout of 33bb34b or earlier: the tuning library (`make tuning`, `_lib.use_tuning_library()`) left the source after it.
 """The "bf16x3 in the Winograd domain" experiment (conv_wino.hip, wino3d_kernel PREC = 1; tuning library only): agreement with the fp32
 Winograd kernel, timing against it and against the direct bf16x3 kernel, and where its time goes (variants whose results are wrong by
 construction).  Result: correct at the first run (rel-Linf 9e-6 vs fp32), compute parts overlap (MFMA + transforms 1.7 ms

@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# ARCHIVED: needs a checkout of 33bb34b or earlier: the tuning library (`make tuning`, `_lib.use_tuning_library()`) left the source after it.
 """Timing of the diagnosis variants of wino3d_kernel (tuning library): which part of the main loop the time goes to.
 Results of the variants are wrong by construction -- timing only."""
 import ctypes

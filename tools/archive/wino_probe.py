@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# ARCHIVED: needs a checkout of 33bb34b or earlier: the tuning library (`make tuning`, `_lib.use_tuning_library()`) left the source after it.
 """Winograd conv kernel vs the direct MFMA kernel: difference and timing at cfg3 shapes (gpurun tuning aid)."""
 import os
 import sys

@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# ARCHIVED: needs a checkout of 33bb34b or earlier: the tuning library (`make tuning`, `_lib.use_tuning_library()`) left the source after it.
 """Round-4 probe: wino3d_kernel with its input staged by LDS-DMA from an x-blocked copy (tuning library, df_debug_wino_conv_fwd_xblk;
 DESIGN.md 4.1b).  Checks every variant against the production kernel (bit-identical expected: same operands, same order) on ragged
 small shapes and on the top-level shape, then times them.  usage: wino_xblk_probe.py [B ...]"""
