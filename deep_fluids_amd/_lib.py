@@ -19,6 +19,9 @@ NN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "deepfluids_hip
 # SSIM / MS-SSIM: likewise
 SSIM_LIB_PATH = os.path.join(_HERE, "csrc", "libdeepfluids_hip_ssim.so")
 SSIM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "deepfluids_hip_ssim.h")
+# the multigrid preconditioner for the liquid and diffusion systems: likewise
+LIQUID_MG_LIB_PATH = os.path.join(_HERE, "csrc", "libdeepfluids_hip_liquid_mg.so")
+LIQUID_MG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "deepfluids_hip_liquid_mg.h")
 
 P, I64, I32, F32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
 U32 = ctypes.c_uint32
@@ -81,6 +84,8 @@ NN_SIGNATURES, NN_CONSTANTS = parse_header(_read_header(NN_HEADER_PATH))
 # ... and of deepfluids_hip_ssim.h: df_ssim* and the DF_SSIM_* word indices and limits
 SSIM_SIGNATURES, SSIM_CONSTANTS = parse_header(_read_header(SSIM_HEADER_PATH))
 globals().update(SSIM_CONSTANTS)
+# ... and of deepfluids_hip_liquid_mg.h: the level-0 builders and the iteration of the liquid and diffusion systems
+LIQUID_MG_SIGNATURES, _ = parse_header(_read_header(LIQUID_MG_HEADER_PATH))
 
 
 class NoiseParams(ctypes.Structure):
@@ -93,6 +98,7 @@ _lib = None
 _metrics_lib = None
 _nn_lib = None
 _ssim_lib = None
+_liquid_mg_lib = None
 
 
 def declared_symbols():
@@ -171,9 +177,28 @@ def ssim_lib():
     return _ssim_lib
 
 
+def liquid_mg_lib():
+    """libdeepfluids_hip_liquid_mg.so; the main library is loaded first (it holds the error buffer this library writes to)"""
+    global _liquid_mg_lib
+    if _liquid_mg_lib is None:
+        lib()
+        if not os.path.exists(LIQUID_MG_LIB_PATH):
+            raise DeepFluidsHipError("libdeepfluids_hip_liquid_mg.so not found at %s -- `make -C deep_fluids_amd/csrc` builds it with the main "
+                                     "library. There is no CPU fallback." % LIQUID_MG_LIB_PATH)
+        handle = ctypes.CDLL(LIQUID_MG_LIB_PATH)
+        for name, (res, args) in LIQUID_MG_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype = res
+            fn.argtypes = args
+        _liquid_mg_lib = handle
+    return _liquid_mg_lib
+
+
 def _handle(name):
     if name in NN_SIGNATURES:
         return nn_lib()
+    if name in LIQUID_MG_SIGNATURES:
+        return liquid_mg_lib()
     if name in SSIM_SIGNATURES:
         return ssim_lib()
     return metrics_lib() if name in METRICS_SIGNATURES else lib()
@@ -235,6 +260,7 @@ def query(name, *args):
         return _QUERY_CACHE[key]
     except KeyError:
         v = getattr(_handle(name), name)(*args)
-        if P not in (NN_SIGNATURES.get(name) or SSIM_SIGNATURES.get(name) or METRICS_SIGNATURES.get(name) or SIGNATURES[name])[1]:
+        if P not in (NN_SIGNATURES.get(name) or SSIM_SIGNATURES.get(name) or METRICS_SIGNATURES.get(name) or LIQUID_MG_SIGNATURES.get(name)
+                     or SIGNATURES[name])[1]:
             _QUERY_CACHE[key] = v
         return v

@@ -390,13 +390,7 @@ __global__ __launch_bounds__(kThreads) void pressure_correct_kernel(const float*
 }
 
 // ---- ghost-fluid free surface: the liquid rows with the surface where phi = 0 between a liquid cell and an air neighbour ------------------
-// theta of liquid cell i (phi pi) and an interior air neighbour (phi pa), as 1/theta: denom = pi - pa; theta = 0.5 if denom > -1e-4,
-// else min(max(pi / denom, gf_clamp), 1).  A NaN comes out as gf_clamp.
-__device__ __forceinline__ float gf_inv_theta(float pi, float pa, float gf_clamp) {
-  const float denom = pi - pa;
-  const float theta = denom > -1e-4f ? 0.5f : fminf(fmaxf(pi / denom, gf_clamp), 1.0f);
-  return 1.0f / theta;
-}
+// (gf_inv_theta, the 1/theta of a liquid cell towards an interior air neighbour, and gf_clamp_ok: smoke_common.hpp)
 
 // the two arrays of the ghost-fluid path lie behind the workspace of the plain solve (df_pressure_status finds its words unchanged)
 GfWs carve_gf(void* ws, int64_t B, int64_t n, int64_t nblk) {
@@ -793,11 +787,6 @@ int diffuse_finish(const char* fn, void* ws, int64_t ws_bytes, float* out, int64
 }
 
 // ---- the ghost-fluid solve: the workspace of the plain solve, then diag and z ----
-int gf_clamp_ok(const char* fn, float gf_clamp) {
-  DF_REQUIRE(gf_clamp > 0.0f && gf_clamp <= 1.0f, DF_EINVAL, "%s: gf_clamp must lie in (0, 1] (got %g)", fn, (double)gf_clamp);
-  return DF_OK;
-}
-
 template <int D>
 int pressure_init_gf_(const char* fn, const float* vel, float* pressure, void* ws, int64_t ws_bytes, const uint8_t* flags, const float* phi,
                       int64_t B, int64_t Z, int64_t Y, int64_t X, int bnd, float gf_clamp, df_stream_t stream) {

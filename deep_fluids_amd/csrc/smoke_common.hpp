@@ -221,6 +221,20 @@ __global__ __launch_bounds__(kThreads) void cg_update_kernel(float* __restrict__
   }
 }
 
+// ---- ghost-fluid free surface: what the `_gf` kernels of smoke.hip and the ghost-fluid level 0 of liquid_mg.hip share ---------------------
+// theta of liquid cell i (phi pi) and an interior air neighbour (phi pa), as 1/theta: denom = pi - pa; theta = 0.5 if denom > -1e-4,
+// else min(max(pi / denom, gf_clamp), 1).  A NaN comes out as gf_clamp.
+__device__ __forceinline__ float gf_inv_theta(float pi, float pa, float gf_clamp) {
+  const float denom = pi - pa;
+  const float theta = denom > -1e-4f ? 0.5f : fminf(fmaxf(pi / denom, gf_clamp), 1.0f);
+  return 1.0f / theta;
+}
+
+int gf_clamp_ok(const char* fn, float gf_clamp) {
+  DF_REQUIRE(gf_clamp > 0.0f && gf_clamp <= 1.0f, DF_EINVAL, "%s: gf_clamp must lie in (0, 1] (got %g)", fn, (double)gf_clamp);
+  return DF_OK;
+}
+
 // ---- host side: the workspace and the checks every solve entry point makes -------------------------------------------------------------------
 int64_t ws_floats(int64_t B, int64_t n, int64_t nblk) { return 4 * B * n + 3 * B * nblk + 2 * B * (int64_t)(sizeof(CgState) / 4); }
 

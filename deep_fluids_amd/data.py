@@ -478,13 +478,14 @@ def generate_smoke_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="sr
 
 
 def _simulate_liquid_scenes(root, path_format, scenes, shape, num_frames, time_step, gravity, bWidth, accuracy, flip_ratio, device, keep,
-                            alphas=None, substeps=1, label=None, ghost_fluid=False, radius_factor=1.0, resample=None):
+                            alphas=None, substeps=1, label=None, ghost_fluid=False, radius_factor=1.0, resample=None, preconditioner=None):
     """the frame loop of the liquid scene scripts: ``scenes`` = (i, j, p0, p1, phi0, velocity spheres); scenes that seed the same number
     of particles run as one batch of ``ops.simulate_liquid``.  Writes v/ and v_range.txt; returns the number of files written.
     ``alphas``: one diffusion number per scene (the viscous step); ``substeps``: solver steps per frame, frame f is step f * substeps;
     ``label(scene, frame)``: the numbers of a file's name and its ``y``; ``ghost_fluid``: every step builds the averaged level set
     (``radius_factor``) and projects against the ghost-fluid surface (``ops.liquid_step``).  ``resample``: None, or ``min_particles``: the
-    steps run extrapolateLsSimple and adjustNumber on a ragged batch, and ALL scenes, whatever they seed, share one batch."""
+    steps run extrapolateLsSimple and adjustNumber on a ragged batch, and ALL scenes, whatever they seed, share one batch.
+    ``preconditioner``: None or an ``ops.Multigrid``, handed to ``ops.simulate_liquid``."""
     from . import ops
     if label is None:
         def label(sc, t):
@@ -514,6 +515,8 @@ def _simulate_liquid_scenes(root, path_format, scenes, shape, num_frames, time_s
             more.update(ghost_fluid=True, radius_factor=float(radius_factor))
         if resample is not None:
             more.update(resample=ops.Resample(int(resample)), entry_start=es, radius_factor=float(radius_factor))
+        if preconditioner is not None:
+            more.update(preconditioner=preconditioner)
         frames = ops.simulate_liquid(pos, pvel, vel, (num_frames - 1) * substeps + 1 if num_frames > 0 else 0, dt=time_step, force=force,
                                      bnd=bWidth, accuracy=accuracy, flip_ratio=flip_ratio, stack=False, **more)
         for t, frame in enumerate(frames):
@@ -547,7 +550,7 @@ def generate_liquid_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="s
                             min_src_x_pos=0.2, max_src_x_pos=0.8, src_y_pos=0.6, num_src_radius=4, min_src_radius=0.04, max_src_radius=0.08,
                             basin_y_pos=0.2, num_frames=200, min_frames=0, max_frames=None, num_simulations=None, resolution_x=128,
                             resolution_y=64, gravity=-1e-3, radius_factor=1, min_particles=2, bWidth=1, open_bound=False, time_step=0.5,
-                            accuracy=1e-4, flip_ratio=0.97, device="cuda", ghost_fluid=False, resample=False):
+                            accuracy=1e-4, flip_ratio=0.97, device="cuda", ghost_fluid=False, resample=False, preconditioner=None):
     """Simulate the reference's 2-D liquid training set (scene/liquid_pos_size.py:148-325, ``liquid_pos10_size4_f200``) on the GPU and
     write it in the reference's on-disk format: ``args.txt`` with every argument of the scene script, ``v/%d_%d_%d.npz`` (x [Y,X,2]
     float32 velocity after frame t, y = [p0, p1, t]) and ``v_range.txt``.  The keyword arguments are the script's, with its defaults
@@ -558,7 +561,9 @@ def generate_liquid_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="s
     ``ops.simulate_liquid``.  The step is this library's restatement (include/deepfluids_hip.h), not mantaflow's: by default a
     first-order free surface (p = 0 at the air cell centres) and plain CG; with ``ghost_fluid=True`` (not a script argument: the same
     files, the same ``args.txt`` keys) every step builds the averaged level set of ``radius_factor`` and projects against the
-    ghost-fluid surface with preconditioned CG, as the script's loop does (``ops.liquid_step``).  ``open_bound=True`` is refused.  Returns the number of files written."""
+    ghost-fluid surface with preconditioned CG, as the script's loop does (``ops.liquid_step``).  ``open_bound=True`` is refused.
+    ``preconditioner=ops.Multigrid(...)`` (not a script argument either: the same files, the same ``args.txt`` keys): the projections are
+    multigrid-preconditioned (``ops.liquid_step``).  Returns the number of files written."""
     from . import ops
     _liquid_refusals("generate_liquid_dataset", open_bound, num_param, (p0, p1, p2), ("src_x_pos", "src_radius", "frames"))
     max_frames = num_frames - 1 if max_frames is None else max_frames
@@ -584,19 +589,20 @@ def generate_liquid_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="s
             phi = np.minimum(basin, ops.sphere_levelset((Y, X), c, X * pr))
             scenes.append((i, j, px, pr, phi, [(c, X * (pr + 0.05))]))
     return _simulate_liquid_scenes(root, path_format, scenes, (Y, X), num_frames, time_step, gravity, bWidth, accuracy, flip_ratio, device, 2,
-                                   ghost_fluid=ghost_fluid, radius_factor=radius_factor, resample=min_particles if resample else None)
+                                   ghost_fluid=ghost_fluid, radius_factor=radius_factor, resample=min_particles if resample else None,
+                                   preconditioner=preconditioner)
 
 
 def generate_liquid3_d_r_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="dist", p1="rot", p2="frames", min_dist=0.15, max_dist=0.25,
                                  num_dist=5, min_rot=0, max_rot=162, num_rot=10, src_y_pos=0.6, src_radius=0.1, basin_y_pos=0.2,
                                  min_frames=0, max_frames=None, num_frames=150, num_simulations=None, resolution_x=96, resolution_y=48,
                                  resolution_z=96, gravity=-1e-3, radius_factor=1, min_particles=3, bWidth=1, open_bound=False,
-                                 time_step=0.8, accuracy=1e-4, flip_ratio=0.97, device="cuda", ghost_fluid=False, resample=False):
+                                 time_step=0.8, accuracy=1e-4, flip_ratio=0.97, device="cuda", ghost_fluid=False, resample=False, preconditioner=None):
     """Simulate the reference's 3-D liquid training set (scene/liquid3_d_r.py main(), ``liquid3_d5_r10_f150``) on the GPU, in the same
     on-disk format (x [Z,Y,X,3]): two drops of radius src_radius at distance p0 (fractions of X) either side of the centre, the pair
     rotated by p1 degrees about the vertical axis, fall into a basin.  The keyword arguments are the script's, with its defaults; what
-    ``generate_liquid_dataset`` says about the step, about ``ghost_fluid`` (which alone uses ``radius_factor``) and about what is left
-    out holds here too."""
+    ``generate_liquid_dataset`` says about the step, about ``ghost_fluid`` (which alone uses ``radius_factor``), about ``preconditioner`` and about what
+    is left out holds here too."""
     from . import ops
     _liquid_refusals("generate_liquid3_d_r_dataset", open_bound, num_param, (p0, p1, p2), ("dist", "rot", "frames"))
     max_frames = num_frames - 1 if max_frames is None else max_frames
@@ -622,14 +628,15 @@ def generate_liquid3_d_r_dataset(root, num_param=3, path_format="%d_%d_%d.npz", 
                 phi = np.minimum(phi, ops.sphere_levelset(shape, c, X * src_radius))
             scenes.append((i, j, float(dist), float(rot), phi, [(c, X * (src_radius + 0.05)) for c in cs]))
     return _simulate_liquid_scenes(root, path_format, scenes, shape, num_frames, time_step, gravity, bWidth, accuracy, flip_ratio, device, 3,
-                                   ghost_fluid=ghost_fluid, radius_factor=radius_factor, resample=min_particles if resample else None)
+                                   ghost_fluid=ghost_fluid, radius_factor=radius_factor, resample=min_particles if resample else None,
+                                   preconditioner=preconditioner)
 
 
 def generate_liquid3_vis_dataset(root, num_param=2, path_format="%d_%d.npz", p0="viscosity", p1="frames", viscosity_base=2, vmin=-5, vmax=-2,
                                  min_viscosity=0, max_viscosity=3, num_viscosity=4, src_x_pos=0.4, src_y_pos=0.8, src_z_pos=0.4,
                                  min_frames=0, max_frames=None, num_frames=150, num_simulations=None, resolution_x=96, resolution_y=72,
                                  resolution_z=48, gravity=-1e-3, radius_factor=1, min_particles=3, bWidth=1, open_bound=False,
-                                 time_step=0.125, accuracy=1e-4, flip_ratio=0.97, device="cuda", ghost_fluid=False, resample=False):
+                                 time_step=0.125, accuracy=1e-4, flip_ratio=0.97, device="cuda", ghost_fluid=False, resample=False, preconditioner=None):
     """Simulate the reference's viscous 3-D liquid training set (scene/liquid3_vis.py main(), ``liquid3_vis4_f150``) on the GPU, in the
     on-disk format of the script: ``args.txt`` with every script argument, ``v/%d_%d.npz`` (x [Z,Y,X,3] float32 velocity of frame f,
     y = [p, f]) and ``v_range.txt``.  The box 0.3..0.7 x 0..0.8 x 0.3..0.7 of the grid (``trainer.liquid3_vis_body``) collapses from rest
@@ -640,7 +647,10 @@ def generate_liquid3_vis_dataset(root, num_param=2, path_format="%d_%d.npz", p0=
     ``timeTotal.is_integer()``), and a ``time_step`` whose reciprocal is not an integer is refused.  All scenes seed the same particles
     and run as ONE batch.  ``src_*_pos`` and ``min_particles`` are recorded only (the script does not use the first three either;
     adjustNumber runs with ``resample=True`` alone, as in ``generate_liquid_dataset``); ``radius_factor`` is recorded, and used by ``ghost_fluid=True`` alone.  What ``generate_liquid_dataset``
-    says about the step and about ``ghost_fluid`` holds here too.
+    says about the step, about ``ghost_fluid`` and about ``preconditioner`` (which, with ``Multigrid.diffusion``, serves the diffusion
+    solves too) holds here too.  With ``Multigrid.diffusion`` the frames of the viscous scenes differ from the plain arm's by far more
+    than ``accuracy``: at this scene's larger alphas the plain diffusion stops at its iteration cap (``max(extent)`` = 96) short of the
+    accuracy and the preconditioned one converges (``ops.liquid_step``); ``Multigrid(diffusion=False)`` keeps the plain diffusion.
     ``open_bound=True`` is refused.  Returns the number of files written."""
     from . import ops
     _liquid_refusals("generate_liquid3_vis_dataset", open_bound, num_param, (p0, p1), ("viscosity", "frames"))
@@ -668,7 +678,7 @@ def generate_liquid3_vis_dataset(root, num_param=2, path_format="%d_%d.npz", p0=
     alphas = [ops.diffusion_alpha(float(vis_list[int(p)]), float(time_step), X) for p in p_list]
     return _simulate_liquid_scenes(root, path_format, scenes, shape, num_frames, time_step, gravity, bWidth, accuracy, flip_ratio, device, 3,
                                    alphas=alphas, substeps=substeps, label=lambda sc, f: ((sc[0], f), [sc[2], f]), ghost_fluid=ghost_fluid, resample=min_particles if resample else None,
-                                   radius_factor=radius_factor)
+                                   radius_factor=radius_factor, preconditioner=preconditioner)
 
 
 def generate_smoke3_obs_dataset(root, num_param=3, path_format="%d_%d_%d.npz", p0="obs_x_pos", p1="buoyancy", p2="frames", min_obs_x_pos=0.2,

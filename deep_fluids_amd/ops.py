@@ -15,6 +15,7 @@ import collections
 import contextlib
 import ctypes
 import math
+import numbers
 import os as _os
 import threading as _threading
 
@@ -2631,14 +2632,31 @@ DEFAULT_MG_ALPHA = 1.8        # the over-correction of the coarse-grid step; the
 DEFAULT_MG_CHECK_EVERY = 4    # a preconditioned solve takes 6-12 iterations: a look every 16 would launch up to 10 idle cycles after the last
 
 
-class MultigridHierarchy(object):
-    """What ``multigrid_hierarchy`` returns: one float32 GPU block that holds, per batch entry and level, the face weights, ``dir``,
-    ``diag``, the level's right-hand side and x scratch, and ``z`` -- and the geometry it was built for (``shape`` [(Z,)Y,X], ``batch``,
-    ``bnd``, ``open_sides`` bits).  Reusable across solves of the same geometry; a solve writes its scratch, so one hierarchy serves one
-    stream at a time."""
+class Multigrid(object):
+    """The settings of ``preconditioner=`` on every solve of the library: ``alpha`` in [1, 2), the over-correction of the coarse-grid
+    step, and ``diffusion``: whether ``liquid_step`` / ``simulate_liquid`` with ``viscosity_alpha=`` precondition the diffusion solve as
+    well as the projection (a diffusion of small ``viscosity_alpha`` takes few plain iterations, and a cycle costs more than it saves:
+    profiles/liquid_mg.md).  On the smoke calls it means ``"mg"`` with that ``alpha``."""
 
-    def __init__(self, block, shape, batch, bnd, osd, alpha):
+    def __init__(self, alpha=DEFAULT_MG_ALPHA, diffusion=True):
+        if not isinstance(diffusion, (bool, np.bool_)):
+            raise ValueError("Multigrid: diffusion must be True or False, got %r" % (diffusion,))
+        self.alpha, self.diffusion = _mg_alpha_arg(alpha, "Multigrid"), bool(diffusion)
+
+
+MG_SYSTEMS = ("smoke", "liquid", "gf", "diffusion")
+
+
+class MultigridHierarchy(object):
+    """What ``multigrid_hierarchy`` (and ``multigrid_hierarchy_liquid`` / ``_diffusion``) returns: one float32 GPU block that holds, per
+    batch entry and level, the face weights, ``dir``, ``diag``, the level's right-hand side and x scratch, and ``z`` -- and the geometry it
+    was built for (``shape`` [(Z,)Y,X], ``batch``, ``bnd``, ``open_sides`` bits) and the ``system`` whose matrix level 0 is: ``"smoke"``,
+    ``"liquid"`` (free surface), ``"gf"`` (ghost fluid) or ``"diffusion"`` (``batch`` then counts the B*D (entry, component) systems).
+    Reusable across solves of the same geometry; a solve writes its scratch, so one hierarchy serves one stream at a time."""
+
+    def __init__(self, block, shape, batch, bnd, osd, alpha, system="smoke"):
         self.block, self.shape, self.batch, self.bnd, self.open_sides, self.alpha = block, tuple(shape), int(batch), int(bnd), int(osd), float(alpha)
+        self.system = system
         self.dim = len(self.shape)
         self.dims4 = [self.batch] + ([1] if self.dim == 2 else []) + list(self.shape)
         self.nbytes = block.numel() * 4
@@ -2724,28 +2742,116 @@ def multigrid_apply(hierarchy, r):
         return hierarchy.z
 
 
+def _mg_alpha_arg(alpha, who):
+    """a real number (Python's or NumPy's, not a bool) in [1, 2), as a float"""
+    if isinstance(alpha, (bool, np.bool_)) or not isinstance(alpha, numbers.Real) or not 1.0 <= alpha < 2.0:
+        raise ValueError("%s: alpha must be a number in [1, 2), got %r" % (who, alpha))
+    return float(alpha)
+
+
+def _hierarchy_block(who, nd, systems, shape, device, out, bnd, alpha, system):
+    """a new hierarchy of ``systems`` entries for ``system``, or the caller's ``out`` -- which must be one of the same system, geometry,
+    ``bnd`` and device, and takes the call's ``alpha``: nothing is allocated then"""
+    dims4 = [systems] + ([1] if nd == 2 else []) + list(shape)
+    if out is not None:
+        if (not isinstance(out, MultigridHierarchy) or out.system != system or out.shape != tuple(shape) or out.batch != systems or out.bnd != bnd
+                or out.device != torch.device(device)):
+            raise ValueError("%s: out must be a %r hierarchy of shape %s, %d systems, bnd %d on %s" % (who, system, tuple(shape), systems, bnd, device))
+        out.alpha = alpha
+        return out
+    nbytes = query("df_mg_hierarchy_bytes", nd, *dims4)
+    if nbytes < 0:
+        raise ValueError("%s: unsupported extents %s" % (who, tuple(dims4)))
+    return MultigridHierarchy(torch.empty((nbytes // 4,), dtype=torch.float32, device=device), shape, systems, bnd, 0, alpha, system)
+
+
+def multigrid_hierarchy_liquid(vel_or_shape, flags, bnd=1, phi=None, gf_clamp=1e-4, alpha=DEFAULT_MG_ALPHA, batch=None, out=None):
+    """The multigrid hierarchy of the free-surface pressure matrix of ``solve_pressure_liquid`` (include/deepfluids_hip_liquid_mg.h) for
+    ``flags`` [B,(Z,)Y,X] (``liquid_flags``) on the grid of a velocity [B,(Z,)Y,X,D] or a shape [(Z,)Y,X]: level 0 has weight 1 between two
+    liquid cells and counts the air neighbours (p = 0 there) on the diagonal; with ``phi`` (and ``gf_clamp``) it is the ghost-fluid
+    matrix, 1 / theta per air neighbour.  The hierarchy's ``system`` is ``"liquid"`` or ``"gf"``.  The liquid moves every step:
+    ``out=`` rebuilds a hierarchy of the same geometry in place, with no allocation."""
+    who = "multigrid_hierarchy_liquid"
+    with torch.no_grad():
+        if not isinstance(flags, torch.Tensor) or flags.dtype != torch.uint8 or not flags.is_cuda or not flags.is_contiguous() or flags.dim() not in (3, 4):
+            raise ValueError("%s: flags must be the uint8 GPU tensor [B,(Z,)Y,X] of liquid_flags" % who)
+        if isinstance(vel_or_shape, torch.Tensor):
+            v, nd = _smoke_vel(vel_or_shape, who)
+            shape, B = tuple(v.shape[1:-1]), v.shape[0]
+            if v.device != flags.device:
+                raise ValueError("%s: the velocity is on %s, the flags on %s" % (who, v.device, flags.device))
+        else:
+            shape, B = tuple(int(n) for n in vel_or_shape), flags.shape[0]
+            nd = len(shape)
+        if batch is not None and int(batch) != B:
+            raise ValueError("%s: batch=%r beside %d entries" % (who, batch, B))
+        if nd not in (2, 3) or tuple(flags.shape) != (B,) + shape:
+            raise ValueError("%s: flags %s for a grid %s of %d entries" % (who, tuple(flags.shape), shape, B))
+        bnd, alpha = _liquid_bnd(bnd, who), _mg_alpha_arg(alpha, who)
+        gfc = 0.0
+        if phi is not None:
+            gfc = _gf_clamp_arg(gf_clamp, who)
+            if (not isinstance(phi, torch.Tensor) or phi.dtype != torch.float32 or tuple(phi.shape) != tuple(flags.shape) or phi.device != flags.device
+                    or not phi.is_contiguous()):
+                raise ValueError("%s: phi must be a contiguous float32 GPU tensor %s on the flags' device" % (who, tuple(flags.shape)))
+            phi = phi.detach()
+        h = _hierarchy_block(who, nd, B, shape, flags.device, out, bnd, alpha, "liquid" if phi is None else "gf")
+        call("df_mg_build_liquid", _ptr(h.block), h.nbytes, _ptr(flags), _ptr(phi), nd, *(h.dims4 + [bnd, gfc, _stream()]))
+        return h
+
+
+def multigrid_hierarchy_diffusion(vel, alpha_v, bnd=1, alpha=DEFAULT_MG_ALPHA, out=None):
+    """The multigrid hierarchy of ``(I - alpha_v * Laplacian)`` of ``diffuse_velocity`` (include/deepfluids_hip_liquid_mg.h) on the grid of
+    ``vel`` [B,(Z,)Y,X,D]: one system per (entry, component) pair, so ``batch`` is B*D; ``alpha_v`` a number or B numbers as in
+    ``diffuse_velocity`` (or the [B] float32 device tensor a caller already holds).  ``system`` is ``"diffusion"``.  ``alpha`` in [1, 2)
+    scales the coarse-grid correction.  ``out=``: rebuild in place, no allocation beside the [B] numbers."""
+    who = "multigrid_hierarchy_diffusion"
+    with torch.no_grad():
+        v, nd = _smoke_vel(vel, who)
+        bnd, alpha = _liquid_bnd(bnd, who), _mg_alpha_arg(alpha, who)
+        B = v.shape[0]
+        if isinstance(alpha_v, torch.Tensor) and alpha_v.is_cuda:
+            if alpha_v.dtype != torch.float32 or tuple(alpha_v.shape) != (B,) or alpha_v.device != v.device or not alpha_v.is_contiguous():
+                raise ValueError("%s: a device alpha_v must be a contiguous float32 tensor [%d] on the velocity's device" % (who, B))
+            al = alpha_v
+        else:
+            al = torch.from_numpy(_diffusion_alpha_arg(alpha_v, B, who)).to(v.device)
+        h = _hierarchy_block(who, nd, B * nd, tuple(v.shape[1:-1]), v.device, out, bnd, alpha, "diffusion")
+        call("df_mg_build_diffusion", _ptr(h.block), h.nbytes, _ptr(al), nd, B, *(h.dims4[1:] + [bnd, _stream()]))
+        return h
+
+
 def _preconditioner_arg(preconditioner, who):
-    """``None``, ``"mg"`` or a ``MultigridHierarchy``; checked before anything touches a GPU"""
-    if preconditioner is None or isinstance(preconditioner, MultigridHierarchy) or (isinstance(preconditioner, str) and preconditioner == "mg"):
+    """``None``, ``"mg"``, a ``Multigrid`` or a ``MultigridHierarchy``; checked before anything touches a GPU"""
+    if (preconditioner is None or isinstance(preconditioner, (MultigridHierarchy, Multigrid))
+            or (isinstance(preconditioner, str) and preconditioner == "mg")):
         return preconditioner
-    raise ValueError("%s: preconditioner must be None, 'mg' or the hierarchy of multigrid_hierarchy, got %r" % (who, preconditioner))
+    raise ValueError("%s: preconditioner must be None, 'mg', an ops.Multigrid or the hierarchy of multigrid_hierarchy, got %r" % (who, preconditioner))
 
 
-def _no_preconditioner(preconditioner, who):
-    if preconditioner is not None:
-        raise ValueError("%s: there is no preconditioner for this system (got preconditioner=%r); the multigrid preconditioner serves the "
-                         "smoke projections (solve_pressure, smoke_step, simulate_smoke) only" % (who, preconditioner))
+def _liquid_preconditioner_arg(preconditioner, who):
+    """the ``preconditioner=`` of the liquid calls: ``None``, an ``ops.Multigrid`` or a ``MultigridHierarchy``; the string ``"mg"`` belongs
+    to the smoke calls and stays refused here.  Checked before anything else is looked at."""
+    if preconditioner is None or isinstance(preconditioner, (MultigridHierarchy, Multigrid)):
+        return preconditioner
+    raise ValueError("%s: preconditioner must be None, an ops.Multigrid(...) or a fitting hierarchy (multigrid_hierarchy_liquid / "
+                     "multigrid_hierarchy_diffusion), got preconditioner=%r; the string 'mg' serves the smoke projections (solve_pressure, "
+                     "smoke_step, simulate_smoke) only" % (who, preconditioner))
 
 
-def _hierarchy_for(preconditioner, v, bnd, flags, osd, who):
-    """the hierarchy a solve on ``v`` uses: built here for ``"mg"``, or the caller's, which must fit the call"""
+def _hierarchy_for(preconditioner, v, bnd, flags, osd, who, system="smoke", systems=None):
+    """the hierarchy a smoke solve on ``v`` uses: built here for ``"mg"`` or a ``Multigrid``, or the caller's, which must fit the call --
+    its ``system`` too (``systems``: the number of systems of the call, default the entries of ``v``)"""
     if not isinstance(preconditioner, MultigridHierarchy):
-        return multigrid_hierarchy(v, bnd, flags, osd)
+        return multigrid_hierarchy(v, bnd, flags, osd, alpha=preconditioner.alpha if isinstance(preconditioner, Multigrid) else DEFAULT_MG_ALPHA)
     h = preconditioner
-    if h.shape != tuple(v.shape[1:-1]) or h.batch != v.shape[0] or h.bnd != int(bnd) or h.device != v.device or h.open_sides != osd:
+    systems = v.shape[0] if systems is None else systems
+    if h.system != system:
+        raise ValueError("%s: the hierarchy holds the %r system, the call solves the %r system" % (who, h.system, system))
+    if h.shape != tuple(v.shape[1:-1]) or h.batch != systems or h.bnd != int(bnd) or h.device != v.device or h.open_sides != osd:
         raise ValueError("%s: the hierarchy was built for shape %s, batch %d, bnd %d, open sides %d on %s; the call has shape %s, batch %d, "
                          "bnd %d, open sides %d on %s" % (who, h.shape, h.batch, h.bnd, h.open_sides, h.device, tuple(v.shape[1:-1]),
-                                                          v.shape[0], int(bnd), osd, v.device))
+                                                          systems, int(bnd), osd, v.device))
     return h
 
 
@@ -2763,7 +2869,7 @@ def solve_pressure(vel, bnd=1, accuracy=1e-4, max_iter=None, check_every=None, o
     ``open_bound``: the open sides (see ``open_sides``); p = 0 in open cells (Dirichlet), so a fluid region that touches one is a
     non-singular system, the faces between fluid and open cells are corrected too (every fluid cell ends divergence free -- mantaflow,
     as far as can be recalled, leaves those faces alone), and the open cells are filled (zero gradient) before returning.
-    ``preconditioner``: ``"mg"`` or the hierarchy of ``multigrid_hierarchy`` for this geometry makes it multigrid-preconditioned
+    ``preconditioner``: ``"mg"``, an ``ops.Multigrid`` (``"mg"`` with its ``alpha``) or the hierarchy of ``multigrid_hierarchy`` for this geometry makes it multigrid-preconditioned
     conjugate gradients (one V-cycle per iteration, include/deepfluids_hip.h); it stops on the same unscaled ``max|r|``, so the fields
     agree with the plain solve's to the accuracy and not beyond; ``check_every`` then defaults to 4.  A hierarchy passed in is checked
     for shape, batch, ``bnd``, open sides and device; it must also have been built for the SAME ``obstacle``, which is NOT checked (a
@@ -3433,6 +3539,24 @@ def _cg_loop(direction, update, s):
     return s.iters.clone()
 
 
+def _mg_rows_loop(h, s, nd, update):
+    """``_cg_loop`` for the recurrence preconditioned with hierarchy ``h``, whose level 0 also gives the rows of ``q = A p``
+    (include/deepfluids_hip_liquid_mg.h): ``z = M r`` after the init and after every ``update(k)``, r.z in the place of r.r"""
+    hb, mg = [_ptr(h.block), h.nbytes], [nd] + s.status4
+
+    def precondition(k):
+        call("df_pressure_mg_precondition", *(hb + [_ptr(s.ws), s.nbytes] + mg + [h.alpha, k, _stream()]))
+
+    def direction(k):
+        call("df_pressure_cg_direction_mg_rows", _ptr(s.ws), s.nbytes, *(hb + mg + [k, s.acc, s.max_iter, _stream()]))
+
+    def step(k):
+        update(k)
+        precondition(k)
+    precondition(-1)
+    return _cg_loop(direction, step, s)
+
+
 def _gf_phi_arg(phi, vel, who):
     """checked against ``vel``'s shape and device before anything asks where ``vel`` lives (a bad phi is refused without a GPU): a
     contiguous float32 tensor of the cells' shape, on a GPU, and on the SAME device as ``vel`` -- the kernels take raw pointers"""
@@ -3466,9 +3590,13 @@ def solve_pressure_liquid(vel, flags, bnd=1, accuracy=1e-4, max_iter=None, check
     > -1e-4, else clamped to [``gf_clamp``, 1]): the row of i gets p_i / theta for that neighbour, and the face is corrected with
     p_i / theta.  The solve is then Jacobi-preconditioned CG (the clamp puts diagonals up to 1 / gf_clamp beside diagonals of 4-6),
     stopping on the UNscaled residual as before, and needs ``pressure_workspace(vel, ghost_fluid=True)``.  With ``phi=None`` nothing of
-    this is launched.  The multigrid preconditioner of ``solve_pressure`` is deliberately out of scope for the free-surface and
-    ghost-fluid systems: any ``preconditioner`` but ``None`` is refused."""
-    _no_preconditioner(preconditioner, "solve_pressure_liquid")
+    this is launched.
+    ``preconditioner``: an ``ops.Multigrid`` (the hierarchy is then built here from ``flags`` and ``phi``) or a hierarchy of
+    ``multigrid_hierarchy_liquid`` built for the SAME flags (and phi), which is NOT checked beyond its system, geometry and device: the
+    solve becomes multigrid-preconditioned conjugate gradients on the same matrix (include/deepfluids_hip_liquid_mg.h; with ``phi`` the
+    cycle replaces Jacobi), stops on the same unscaled ``max|r|``, and ``check_every`` then defaults to 4.  The string ``"mg"`` is the
+    smoke calls' and is refused.  With ``None`` nothing of it is allocated or launched."""
+    pre = _liquid_preconditioner_arg(preconditioner, "solve_pressure_liquid")
     with torch.no_grad():
         gf = phi is not None
         if gf:
@@ -3477,6 +3605,8 @@ def solve_pressure_liquid(vel, flags, bnd=1, accuracy=1e-4, max_iter=None, check
         v, nd = _smoke_vel(vel, "solve_pressure_liquid")
         bnd = _liquid_bnd(bnd, "solve_pressure_liquid")
         fl = _liquid_flags_arg(flags, v, "solve_pressure_liquid")
+        if pre is not None and check_every is None:
+            check_every = DEFAULT_MG_CHECK_EVERY
         s = _solve_begin("solve_pressure_liquid", v, nd, accuracy, max_iter, check_every,
                          workspace if workspace is not None else pressure_workspace(v, ghost_fluid=gf))
         out = _smoke_out(out, v, "solve_pressure_liquid")
@@ -3486,9 +3616,17 @@ def solve_pressure_liquid(vel, flags, bnd=1, accuracy=1e-4, max_iter=None, check
         sfx, twin = "%dd_" % nd, ("gf", "gf") if gf else ("flags", "liquid")
         surface = [_ptr(fl)] + ([_ptr(phi)] if gf else []) + dims + [bnd] + ([gfc] if gf else [])
         call("df_pressure_init" + sfx + twin[0], _ptr(v), _ptr(pressure), _ptr(ws), nbytes, *(surface + [_stream()]))
-        iters = _cg_loop(
-            lambda k: call("df_pressure_cg_direction" + sfx + twin[1], _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, s.acc, s.max_iter, _stream()])),
-            lambda k: call("df_pressure_cg_update" + sfx + twin[0], _ptr(pressure), _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, _stream()])), s)
+        if pre is not None:
+            if isinstance(pre, Multigrid):
+                h = multigrid_hierarchy_liquid(v, fl, bnd, phi, gfc if gf else 1e-4, pre.alpha)
+            else:
+                h = _hierarchy_for(pre, v, bnd, None, 0, "solve_pressure_liquid", "gf" if gf else "liquid")
+            iters = _mg_rows_loop(h, s, nd, lambda k: call("df_pressure_cg_update_mg", _ptr(pressure), _ptr(ws), nbytes, _ptr(fl), nd,
+                                                           *(s.status4 + [bnd, k, _stream()])))
+        else:
+            iters = _cg_loop(
+                lambda k: call("df_pressure_cg_direction" + sfx + twin[1], _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, s.acc, s.max_iter, _stream()])),
+                lambda k: call("df_pressure_cg_update" + sfx + twin[0], _ptr(pressure), _ptr(ws), nbytes, _ptr(fl), *(dims + [bnd, k, _stream()])), s)
         call("df_pressure_correct" + sfx + twin[1], _ptr(v), _ptr(pressure), _ptr(out), *(surface + [_stream()]))
         return out, pressure, iters
 
@@ -3538,15 +3676,21 @@ def diffuse_velocity(vel, alpha, bnd=1, accuracy=1e-4, max_iter=None, check_ever
     host (``diffusion_alpha``), finite and >= 0.  Every (entry, component) pair is its own system and stops on its own at
     ``max|r| <= accuracy`` or after ``max_iter`` iterations (default ``default_diffusion_max_iter``); the host reads one word every
     ``check_every`` iterations, as in ``solve_pressure``.  ``alpha = 0`` returns the input's bits.  No preconditioner, no obstacles.
-    Returns ``(vel_out, iterations)``, ``iterations`` int32 [B, D].  ``out`` may be ``vel``.  The multigrid preconditioner of
-    ``solve_pressure`` is deliberately out of scope for the diffusion system: any ``preconditioner`` but ``None`` is refused."""
-    _no_preconditioner(preconditioner, "diffuse_velocity")
+    Returns ``(vel_out, iterations)``, ``iterations`` int32 [B, D].  ``out`` may be ``vel``.
+    ``preconditioner``: an ``ops.Multigrid`` (the hierarchy is built here) or a hierarchy of ``multigrid_hierarchy_diffusion`` built for
+    the SAME ``alpha`` (not checked beyond system, geometry and device): multigrid-preconditioned conjugate gradients on the same matrix
+    (include/deepfluids_hip_liquid_mg.h), the same stop, ``check_every`` then defaults to 4.  It pays for large ``alpha`` only: a plain
+    solve of a few iterations is cheaper than the cycles (profiles/liquid_mg.md).  ``"mg"`` is the smoke calls' and is refused; with
+    ``None`` nothing of it is allocated or launched."""
+    pre = _liquid_preconditioner_arg(preconditioner, "diffuse_velocity")
     with torch.no_grad():
         if not isinstance(vel, torch.Tensor) or vel.dtype != torch.float32 or not vel.is_cuda or not vel.is_contiguous():
             raise ValueError("diffuse_velocity: vel must be a contiguous float32 GPU tensor [B,(Z,)Y,X,D]")
         v, nd = _smoke_vel(vel, "diffuse_velocity")
         bnd = _liquid_bnd(bnd, "diffuse_velocity")
         a32 = _diffusion_alpha_arg(alpha, v.shape[0], "diffuse_velocity")
+        if pre is not None and check_every is None:
+            check_every = DEFAULT_MG_CHECK_EVERY
         s = _solve_begin("diffuse_velocity", v, nd, accuracy, max_iter, check_every, workspace if workspace is not None else diffusion_workspace(v),
                          diffusion=True)
         out = _smoke_out(out, v, "diffuse_velocity")
@@ -3554,15 +3698,24 @@ def diffuse_velocity(vel, alpha, bnd=1, accuracy=1e-4, max_iter=None, check_ever
         if need < 0 or s.nbytes < need:
             raise ValueError("diffuse_velocity: unsupported extents %s or a workspace of %d bytes where %d are needed (diffusion_workspace)"
                              % (tuple(v.shape), s.nbytes, need))
-        return _diffuse(v, torch.from_numpy(a32).to(v.device), out, bnd, s)
+        al = torch.from_numpy(a32).to(v.device)
+        if isinstance(pre, Multigrid):
+            pre = multigrid_hierarchy_diffusion(v, al, bnd, pre.alpha)
+        elif pre is not None:
+            pre = _hierarchy_for(pre, v, bnd, None, 0, "diffuse_velocity", "diffusion", v.shape[0] * nd)
+        return _diffuse(v, al, out, bnd, s, pre)
 
 
-def _diffuse(v, al, out, bnd, s):
-    """the launches of ``diffuse_velocity``; ``al`` [B] float32 on the device, ``s`` the ``_solve_begin`` of a diffusion"""
+def _diffuse(v, al, out, bnd, s, h=None):
+    """the launches of ``diffuse_velocity``; ``al`` [B] float32 on the device, ``s`` the ``_solve_begin`` of a diffusion, ``h`` the
+    diffusion hierarchy built for ``al`` (None: the plain solve)"""
     nd, dims, ws, nbytes = v.dim() - 2, list(v.shape[:-1]), s.ws, s.nbytes
     call("df_diffuse_init%dd" % nd, _ptr(v), _ptr(al), _ptr(ws), nbytes, *(dims + [bnd, _stream()]))
-    iters = _cg_loop(lambda k: call("df_diffuse_cg_direction%dd" % nd, _ptr(al), _ptr(ws), nbytes, *(dims + [bnd, k, s.acc, s.max_iter, _stream()])),
-                     lambda k: call("df_diffuse_cg_update%dd" % nd, _ptr(ws), nbytes, *(dims + [bnd, k, _stream()])), s)
+    if h is not None:
+        iters = _mg_rows_loop(h, s, nd, lambda k: call("df_diffuse_cg_update_mg", _ptr(ws), nbytes, nd, dims[0], *(s.status4[1:] + [bnd, k, _stream()])))
+    else:
+        iters = _cg_loop(lambda k: call("df_diffuse_cg_direction%dd" % nd, _ptr(al), _ptr(ws), nbytes, *(dims + [bnd, k, s.acc, s.max_iter, _stream()])),
+                         lambda k: call("df_diffuse_cg_update%dd" % nd, _ptr(ws), nbytes, *(dims + [bnd, k, _stream()])), s)
     call("df_diffuse_finish%dd" % nd, _ptr(ws), nbytes, _ptr(out), *(dims + [bnd, _stream()]))
     return out, iters.reshape(dims[0], nd)
 
@@ -3746,7 +3899,11 @@ class _LiquidSettings(object):
     (``ghost_fluid`` or ``resample``), the pressure workspace (ghost-fluid-sized only with ``ghost_fluid``).  ``rs`` is the ``Resample``."""
 
     def __init__(self, who, dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, open_bound, viscosity_alpha, ghost_fluid, radius_factor,
-                 gf_clamp, resample, entry_start):
+                 gf_clamp, resample, entry_start, preconditioner=None):
+        self.pre = _liquid_preconditioner_arg(preconditioner, who)
+        if isinstance(self.pre, MultigridHierarchy):
+            raise ValueError("%s: preconditioner must be None or an ops.Multigrid(...): the liquid moves, so the step builds its hierarchies itself, got "
+                             "preconditioner=%r" % (who, preconditioner))
         if open_bound:
             raise NotImplementedError("%s: open sides (resetOutflow) are not implemented for the liquid solver" % who)
         if ghost_fluid:
@@ -3773,6 +3930,14 @@ class _LiquidSettings(object):
         if self.viscosity_alpha is not None:
             self.alpha = torch.from_numpy(_diffusion_alpha_arg(self.viscosity_alpha, v.shape[0], self.who)).to(v.device)
             self.dws = diffusion_workspace(v)
+        # the hierarchy blocks of preconditioner=Multigrid(...): the projection's is allocated here and rebuilt from every step's flags
+        # (and phi); the diffusion's matrix does not change, so it is built here once.  None: nothing is allocated.
+        self.hp = self.hd = None
+        if self.pre is not None:
+            self.hp = _hierarchy_block(self.who, v.dim() - 2, v.shape[0], tuple(v.shape[1:-1]), v.device, None, self.bnd, self.pre.alpha,
+                                       "gf" if self.ghost_fluid else "liquid")
+            if self.alpha is not None and self.pre.diffusion:
+                self.hd = multigrid_hierarchy_diffusion(v, self.alpha, self.bnd, self.pre.alpha)
 
     def frame(self, r, counts=False):
         """the public tuple of a ``_LiquidResult``: ``(pos, pvel, vel[, iterations[, diffusion_iterations]][, entry_start])``"""
@@ -3859,11 +4024,14 @@ def _liquid_step(p, u, v, es, cfg):
         # the viscous step of scene/liquid3_vis.py:256-296: setWallBcs as a zero-force pass (+ 0.0 leaves a value's bits but for -0),
         # then cgSolveDiffusion: the step's accuracy, the iteration cap of cgSolveDiffusion's own default (max_iter is the pressure solve's)
         liquid_forces(vel, flags, (0.0,) * nd, bnd=bnd, out=vel)
-        _, diters = _diffuse(vel, cfg.alpha, vel, bnd, _solve_begin(cfg.who, vel, nd, cfg.accuracy, None, cfg.check_every, cfg.dws, diffusion=True))
+        dce = DEFAULT_MG_CHECK_EVERY if cfg.hd is not None and cfg.check_every is None else cfg.check_every
+        _, diters = _diffuse(vel, cfg.alpha, vel, bnd, _solve_begin(cfg.who, vel, nd, cfg.accuracy, None, dce, cfg.dws, diffusion=True), cfg.hd)
     liquid_forces(vel, flags, cfg.force, bnd=bnd, out=vel)
     surface = dict(phi=phi, gf_clamp=cfg.gf_clamp) if cfg.ghost_fluid else dict()
+    if cfg.hp is not None:
+        multigrid_hierarchy_liquid(vel, flags, bnd, alpha=cfg.pre.alpha, out=cfg.hp, **surface)       # this step's liquid, in place
     _, _, iters = solve_pressure_liquid(vel, flags, bnd=bnd, accuracy=cfg.accuracy, max_iter=cfg.max_iter, check_every=cfg.check_every, out=vel,
-                                        workspace=cfg.pws, **surface)
+                                        workspace=cfg.pws, preconditioner=cfg.hp, **surface)
     if rs is not None:
         # pVel.setSource(vel, isMAC=True) + adjustNumber against the projected velocity, then extrapolateMACSimple and the FLIP update on
         # old and new particles alike
@@ -3903,11 +4071,18 @@ def liquid_step(pos, pvel, vel, dt, force=None, bnd=1, accuracy=1e-4, max_iter=N
     forces and the solve; ``resample_particles`` against the projected velocity (``resample.step`` feeds the hash and advances);
     the 4-layer extrapolation; the FLIP update on old and new particles alike.  The result is ``(pos [P,D], pvel [P,D], vel,
     iterations[, diffusion_iterations], entry_start)``; a state that does not fit the capacity raises before the step returns.  With
-    ``None`` nothing of this is launched and every result keeps its bits.  The liquid systems are out of the multigrid preconditioner's
-    scope: any ``preconditioner`` but ``None`` is refused."""
-    _no_preconditioner(preconditioner, "liquid_step")
+    ``None`` nothing of this is launched and every result keeps its bits.
+    ``preconditioner=ops.Multigrid(...)``: the projection -- free surface or ghost fluid, according to ``ghost_fluid`` -- is
+    multigrid-preconditioned (``solve_pressure_liquid``; the hierarchy is rebuilt from the step's flags and phi), and with
+    ``viscosity_alpha`` and ``Multigrid.diffusion`` the diffusion is too (``diffuse_velocity``).  Nothing else of the step changes, so it
+    combines with ``resample`` and ``entry_start`` as it is.  The string ``"mg"`` is refused; with ``None`` nothing is allocated or
+    launched and every result keeps its bits.  The projections of the two arms agree to ``accuracy``.  The diffusions do NOT wherever
+    the plain solve stops at its iteration cap (``default_diffusion_max_iter``: ``max(extent)`` in 3-D) short of ``accuracy``, as it
+    does at the large ``viscosity_alpha`` of the 96x72x48 scene: the preconditioned solve converges under the same cap, so the viscous
+    frames then differ from the plain arm's by the plain solve's truncation, far more than ``accuracy`` (profiles/liquid_mg.md);
+    ``Multigrid(diffusion=False)`` keeps the plain diffusion."""
     cfg = _LiquidSettings("liquid_step", dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, open_bound, viscosity_alpha, ghost_fluid,
-                          radius_factor, gf_clamp, resample, entry_start)
+                          radius_factor, gf_clamp, resample, entry_start, preconditioner)
     with torch.no_grad():
         p, u, v, es = _liquid_state(pos, pvel, vel, entry_start, cfg)
         cfg.prepare(v)
@@ -3944,14 +4119,15 @@ def simulate_liquid(pos0, pvel0, vel0, steps, dt=0.5, force=None, bnd=1, accurac
     is ``k`` solver steps) -- every step still runs and reports to ``stats``, and with ``stack`` the returned particles are those after
     the LAST step.  ``ghost_fluid``, ``radius_factor``, ``gf_clamp``: as in ``liquid_step``.  ``resample`` (and ``entry_start`` for a
     ragged start): as in ``liquid_step``; the state is ragged, the result is ``(pos [P,D], pvel [P,D], vels, entry_start)`` or a generator
-    of ``(pos, pvel, vel, entry_start)``, and a state that does not fit the capacity raises at the next kept frame at the latest.  Any
-    ``preconditioner`` but ``None`` is refused (out of the multigrid preconditioner's scope)."""
-    _no_preconditioner(preconditioner, "simulate_liquid")
+    of ``(pos, pvel, vel, entry_start)``, and a state that does not fit the capacity raises at the next kept frame at the latest.
+    ``preconditioner``: as in ``liquid_step`` -- what is said there about viscous frames and the plain diffusion's iteration cap holds for
+    every frame here; the hierarchy blocks are allocated once for the sequence and rebuilt per step."""
+    _liquid_preconditioner_arg(preconditioner, "simulate_liquid")
     keep_every = int(keep_every)
     if keep_every < 1:
         raise ValueError("simulate_liquid: keep_every must be >= 1, got %r" % (keep_every,))
     cfg = _LiquidSettings("simulate_liquid", dt, force, bnd, accuracy, max_iter, check_every, flip_ratio, open_bound, viscosity_alpha, ghost_fluid,
-                          radius_factor, gf_clamp, resample, entry_start)
+                          radius_factor, gf_clamp, resample, entry_start, preconditioner)
     with torch.no_grad():
         gen = _liquid_frames(pos0, pvel0, vel0, entry_start, steps, keep_every, stats, cfg)
         if not stack:

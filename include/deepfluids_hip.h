@@ -1128,7 +1128,8 @@ int df_resample_scatter3d(const float* pos_sorted, const float* pvel_sorted, con
  * A V-cycle z = M r for the matrices of the plain, `_flags` and `_open` smoke solves, and the two kernels of the preconditioned
  * recurrence.  The definition below is this library's own (as the projection's is) and it is the one that is tested:
  * tests/smoke_mg_ref.py restates it in fp64 and as an op-for-op fp32 twin whose bits the kernels give.  The free-surface, ghost-fluid
- * and diffusion systems are out of scope.  DF_VERSION is NOT raised by this block either (tests pin 207): look the symbols up.
+ * and diffusion systems use the same hierarchy block and the same cycle through deepfluids_hip_liquid_mg.h (a library of its own: this
+ * header is frozen), which adds their level 0 and an iteration whose rows are level 0.  DF_VERSION is NOT raised by this block either (tests pin 207): look the symbols up.
  *
  * Level 0 is the solve's own grid, band included, and the solve's own matrix, stored as face weights: w_a[c] for the face between c and
  *   c - e_a, 1 if both cells are fluid, else 0 (a neighbour outside the grid has no face); dir[c] = the number of open neighbours of a
